@@ -8,6 +8,12 @@ BASELINE.json's north_star.
 
 Prints ONE JSON line on rank 0 (contract in the task description) with `roofline` and
 `cpu_baseline` objects.
+
+Order of a run: reset with random episode clocks, `--preroll` steps, `--warmup` steps, `--steps`
+untimed steps that carry the kernel timer (roofline), then exactly `--steps` timed steps: `value`
+and `ms_per_step` describe these.  The inputs depend only on the arguments (seeded config, seeded
+action bank), so `--dump-outputs DIR` (what the last timed step returned) can be compared between
+two builds output for output.
 """
 import argparse
 import json
@@ -306,6 +312,46 @@ def stream_copy_gbs(dev, nbytes=1 << 30, iters=20):
     return float(g.value)
 
 
+DUMP_BYTES = 64 << 20
+# names of what step() returns, by arity (envs/: legged_robot.py, go2_ee.py, go2_ts.py LeggedRobotTS, go2_ts.py Go2Dreamwaq); extras comes last
+STEP_OUTPUTS = {5: ("obs", "privileged_obs", "rew", "done"),
+                6: ("estimator_features", "estimator_labels", "privileged_obs", "rew", "done"),
+                7: ("obs", "privileged_obs", "obs_history", "critic_obs", "rew", "done"),
+                8: ("obs", "privileged_obs", "obs_history", "explicit_labels", "next_state", "rew", "done")}
+
+
+def dump_outputs(out_dir, out):
+    """Write one step's outputs `out` (the tuple env.step() returned) as out_dir/<name>.npy: every tensor of the tuple and every tensor of
+    extras (time_outs) as float32 with the env index first, every entry of extras["episode"] as a float64 array named episode_<key>.
+    Above DUMP_BYTES in all, the per-env arrays keep a fixed seeded sample of envs (ascending ids, written as env_ids.npy).
+    -> summary for the JSON line."""
+    import numpy as np
+    import torch
+    tensors = dict(zip(STEP_OUTPUTS[len(out)], out[:-1]))
+    episode = {}
+    for k, v in out[-1].items():
+        if k == "episode":
+            episode = {f"episode_{ek}": torch.as_tensor(ev).detach().double().cpu().numpy() for ek, ev in v.items()}
+        elif torch.is_tensor(v):
+            tensors[k] = v
+    per_env = {k: v.detach().float().cpu().numpy() for k, v in tensors.items() if v is not None}
+    n = len(next(iter(per_env.values())))
+    row_bytes = sum(a[0].nbytes for a in per_env.values())
+    budget = DUMP_BYTES - sum(a.nbytes for a in episode.values())
+    ids = None
+    if n * row_bytes > budget:
+        keep = budget // (row_bytes + 8)           # + the float64 id of each kept env
+        ids = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        per_env = {k: a[ids] for k, a in per_env.items()}
+        per_env["env_ids"] = ids.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {**per_env, **episode}
+    for k, a in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), a)
+    return {"dir": out_dir, "arrays": sorted(arrays), "bytes": int(sum(a.nbytes for a in arrays.values())),
+            "envs": n if ids is None else int(len(ids)), "envs_total": n}
+
+
 _REAL_STDOUT = sys.stdout      # main() swaps in a private copy of fd 1 and points fd 1 at stderr (see there)
 
 
@@ -472,11 +518,8 @@ def launcher_dry_run(args, world, rank):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=2000)
+    ap.add_argument("--steps", type=int, default=2000, help="timed steps: value and ms_per_step are taken over exactly these")
     ap.add_argument("--warmup", type=int, default=100)
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="timed regions of --steps steps each after the one warm-up; value / ms_per_step are the median region's, the "
-                         "list is reported as repeats_ms_per_step (SURVEY 8d: 5 repeats, median)")
     ap.add_argument("--envs-per-gpu", type=int, default=ENVS_PER_GPU)
     ap.add_argument("--no-stream-copy", action="store_true", help="skip the measured stream-copy bandwidth (roofline.peak_measured)")
     ap.add_argument("--no-gather", action="store_true", help="skip the RCCL all-gather of the step outputs at N>1")
@@ -506,7 +549,12 @@ def main():
     ap.add_argument("--launcher-dry-run", action="store_true",
                     help="rank plumbing only (spawn, rendezvous, gather, max-over-ranks timing, one JSON line) on the CPU with the "
                          "gloo backend and a stand-in for the env step: the world-2 test of this file's N > 1 path")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last one returned to its caller (rank 0's env outputs) as DIR/<name>.npy "
+                         "(see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(spawn_ranks(args.gpus))          # before anything here touches the GPU
@@ -569,6 +617,7 @@ def main():
         out = env.step(bank[i % len(bank)])
         if gather is not None:
             gather(obs_outputs(out), out[-3], out[-2])      # same tail in both arities: (rew, done, extras)
+        return out
 
     def probe(n_steps):         # microseconds per step of n_steps steps under the current `gather`, bracketed like a timed region
         if dist is not None:
@@ -601,40 +650,21 @@ def main():
         one_step(i)
     if gather is not None:
         gather.finish()
-        gather.wait_s = gather.finish_s = 0.0
-    # roofline: the dominant kernel (physics) of every `--kernel-timer-stride`-th step is bracketed by HIP events on the launch stream.
-    # A timed launch is not free -- events attached to the dispatch cost ~10 us of bubble around it: stride 8 made the driver's 20-step
-    # regions 6 % slower (27.5 vs 25.9 us per step, same build) -- so with R >= 3 regions only the FIRST carries the timer (it is the slowest
-    # anyway: first dispatches after the warm-up): the median region, which is what `value` reports, is then one of at least four without it, and the kernel is still timed live inside timed regions of this
-    # very run.  `roofline.timer` says which regions were sampled.
-    n_rep = max(args.repeats, 1)
-    timer_regions = list(range(n_rep)) if n_rep < 3 else [0]
-    if args.kernel_timer_stride <= 0:
-        timer_regions = []
-    # at least ~10 samples in the sampled region, so that its first launch (right behind a synchronize: up to 10 us slower) does not
-    # dominate the mean of a short region -- the driver's 20 steps are timed at every 2nd step, the default 2000 at every 8th
-    timer_stride = max(1, min(args.kernel_timer_stride, args.steps // 10)) if args.kernel_timer_stride > 0 else 0
-    # R timed regions of `--steps` steps each after the one warm-up, median reported.  A region is bracketed by a
-    # barrier + synchronize on both sides and its time is the maximum over ranks, as the contract says for "the" timed region
-    region_s, region_dev_ms = [], []
-    step_i = args.warmup
-    for rep in range(max(args.repeats, 1)):
-        env._engine.profile(timer_stride if rep in timer_regions else 0)     # stride 0 = off; samples taken so far are kept
+
+    def region(first, n_steps, dev_bracket):
+        """Steps first .. first + n_steps - 1, bracketed by a barrier + synchronize on both sides.  -> (seconds, the maximum over ranks;
+        device-side milliseconds between HIP events around the steps, or None; what the last step returned)."""
         if dist is not None:
             dist.barrier()
         torch.cuda.synchronize()
-        # device-side bracket of the region (step_device_us): two more packets on the queue, so -- like the kernel timer -- only in the regions
-        # that are sampled anyway (all of them when there are fewer than three)
-        dev_bracket = rep in timer_regions or not timer_regions
         ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         t0 = time.perf_counter()
         if dev_bracket:
             ev0.record()       # torch's current stream == the stream lg_step launches on (engine.py)
-        for i in range(args.steps):
-            one_step(step_i + i)
-        step_i += args.steps
+        for i in range(n_steps):
+            out = one_step(first + i)
         if gather is not None:
-            gather.finish()        # every record of the timed region has arrived before the clock stops
+            gather.finish()        # every record of the region has arrived before the clock stops
         if dev_bracket:
             ev1.record()
         torch.cuda.synchronize()
@@ -645,21 +675,30 @@ def main():
             t = torch.tensor([el], device=dev, dtype=torch.float64)
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
             el = float(t.item())
-        region_s.append(el)
-        region_dev_ms.append(ev0.elapsed_time(ev1) if dev_bracket else None)
+        return el, (ev0.elapsed_time(ev1) if dev_bracket else None), out
+
+    # roofline: the dominant kernel (physics) of every `--kernel-timer-stride`-th step is bracketed by HIP events on the launch stream, and
+    # the region by two more (step_device_us).  A timed launch is not free -- events attached to the dispatch cost ~10 us of bubble around
+    # it: stride 8 made the driver's 20-step regions 6 % slower (27.5 vs 25.9 us per step, same build) -- so the timers run in a region of
+    # `--steps` untimed steps of their own between the warm-up and the timed steps, and the timed steps carry none.  At least ~10 samples
+    # there, so that its first launch (right behind a synchronize: up to 10 us slower) does not dominate the mean of a short region -- the
+    # driver's 20 steps are sampled at every 2nd step, the default 2000 at every 8th.
+    timer_stride = max(1, min(args.kernel_timer_stride, args.steps // 10)) if args.kernel_timer_stride > 0 else 0
+    env._engine.profile(timer_stride)              # stride 0 = off
+    _, dev_ms, _ = region(args.warmup, args.steps, True)
+    env._engine.profile(0)                         # samples taken so far are kept for profile_read()
+    if gather is not None:
+        gather.wait_s = gather.finish_s = 0.0
+    # the timed region: exactly `--steps` steps, bracketed by a barrier + synchronize on both sides, its time the maximum over ranks
+    elapsed, _, last_out = region(args.warmup + args.steps, args.steps, False)
     if gather_info is not None:
-        n_timed = args.steps * max(args.repeats, 1)
-        gather_info.update({"step_us_with_gather": sorted(region_s)[len(region_s) // 2] / args.steps * 1e6,
-                            "wait_us_per_step": gather.wait_s / n_timed * 1e6, "exposed_us_per_step": gather.finish_s / n_timed * 1e6,
-                            "exposed_us_per_region": gather.finish_s / max(args.repeats, 1) * 1e6,
+        gather_info.update({"step_us_with_gather": elapsed / args.steps * 1e6,
+                            "wait_us_per_step": gather.wait_s / args.steps * 1e6, "exposed_us_per_step": gather.finish_s / args.steps * 1e6,
+                            "exposed_us_per_region": gather.finish_s * 1e6,
                             "note": "rank 0's own waits; wait = host time blocked on an exchange inside the steps, exposed = time from the last step's "
-                                    "completion to the arrival of every record (gather.finish()), both inside the timed regions"})
-    order = sorted(range(len(region_s)), key=lambda k: region_s[k])
-    mid = order[len(order) // 2]                     # the median region (upper median for an even count)
-    elapsed = region_s[mid]
-    dev_all = sorted(x for x in region_dev_ms if x is not None)
-    dev_ms = dev_all[len(dev_all) // 2]              # device-side bracket: median of the regions that carry one
+                                    "completion to the arrival of every record (gather.finish()), both inside the timed region"})
     if rank == 0:
+        dumped = dump_outputs(args.dump_outputs, last_out) if args.dump_outputs else None
         total_envs = n_local * world
         value = total_envs * args.steps / elapsed
         kern_us, kern_n = env._engine.profile_read()
@@ -689,14 +728,13 @@ def main():
             "config": {"workload": f"{WORKLOADS[args.task]}, {n_local} envs per GPU, fused LeggedRobot.step "
                                    f"(4 sub-steps dt=0.005) with synthetic N(0,1) actions" + (f", population pre-rolled {args.preroll} steps" if args.preroll > 0 else ""),
                        "envs_total": total_envs, "parallelism": f"env-shard x{world}" + (" [gloo rehearsal, ranks may share a GPU]" if world > 1 and args.backend == "gloo" else "") + ((f" + exchange of (obs, rew, done) of every step by {gather_info['mode']}, {gather_info['steps_per_exchange']} step(s) per exchange" + ("" if gather_info["mode"] == "rccl-sync" else ", overlapped with the following steps")) if gather_info else "")},
-            "repeats": len(region_s), "repeats_ms_per_step": [x / args.steps * 1e3 for x in region_s],
             "roofline": {"bound": "hbm", "achieved": achieved, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                          "frac": achieved / HBM_PEAK_GBS, "traffic": traffic, "traffic_counters": traffic_stamp,
                          "peak_measured": peak_meas, "frac_of_measured": (achieved / peak_meas) if peak_meas else None,
                          "peak_measured_how": "lg_stream_copy: float4 grid-stride copy of 1 GiB x 20 on this device, (read + write) bytes / time",
                          "kernel": layout, "launch_us": launch_s * 1e6, "samples": kern_n,
-                         "timer": {"stride": timer_stride, "sampled_regions": timer_regions, "regions": n_rep,
-                                   "note": "HIP events attached to the dispatch of every stride-th step, in the listed timed regions only (a timed launch costs ~10 us of bubble; the median region carries none when regions >= 3)"},
+                         "timer": {"stride": timer_stride, "steps": args.steps,
+                                   "note": "HIP events attached to the dispatch of every stride-th step, and around the region (step_device_us), in an untimed region of `steps` steps just before the timed one (a timed launch costs ~10 us of bubble; the timed steps carry no events)"},
                          "step_device_us": dev_ms * 1e3 / args.steps,
                          "algorithmic_bytes_per_launch": bytes_env * n_local,
                          "valu": valu_roofline(wkey, launch_s, n_local)},
@@ -704,6 +742,8 @@ def main():
         }
         if gather_info is not None:
             out["gather"] = gather_info
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if world == 1 and args.ppo_rollout > 0:
             del env
             try:

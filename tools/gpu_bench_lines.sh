@@ -17,8 +17,4 @@ python bench.py --steps 20 --warmup 5 > gpurun_out/${TAG}_bench_go2_driver_cmd.j
 python bench.py --steps 20 --warmup 5 > gpurun_out/${TAG}_bench_go2_driver_cmd_again.json 2>> gpurun_out/${TAG}_bench_go2_driver_cmd.err
 rocprofv3 --kernel-trace --stats -d gpurun_out/prof_stats_drv --output-format csv -- python3 bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-stream-copy > /dev/null 2> gpurun_out/prof_stats_drv.err
 head -6 "$(find gpurun_out/prof_stats_drv -name '*kernel_stats.csv' | head -1)" > gpurun_out/${TAG}_kernel_stats_driver_cmd.csv
-python -c "
-import json
-for f in ('','_again'):
-    d=json.load(open('gpurun_out/${TAG}_bench_go2_driver_cmd'+f+'.json')); print('driver cmd'+f, round(d['value']/1e6,2), 'M', round(d['ms_per_step']*1e3,2), [round(x*1e3,1) for x in d['repeats_ms_per_step']])"
 head -3 gpurun_out/${TAG}_kernel_stats.csv | cut -c1-200
