@@ -560,13 +560,30 @@ __global__ __launch_bounds__(256) void terrain_tile_kernel(const LgTerrainTile *
         for (int lo = 0, hi = W; hi - lo > plat; lo += w, hi -= w) rings++;
         const int d = min(min(x, W - 1 - x), min(y, W - 1 - y));
         v = rings > 0 ? min(d / w, rings - 1) * h : 0;
-    } else if (T.kind == LG_TILE_OBSTACLES) {
-        const int n = T.ip[0], plat = T.ip[1];
+    } else if (T.kind == LG_TILE_OBSTACLES || T.kind == LG_TILE_STONES) {
+        // background, rectangles in draw order (the last one covering the pixel wins), then the zero platform
+        const bool stones = T.kind == LG_TILE_STONES;
+        const int n = T.ip[0];
+        const int a = stones ? T.ip[1] : (W - T.ip[1]) / 2, b = stones ? T.ip[2] : (W + T.ip[1]) / 2;
         const int32_t *r = iaux + T.aux_off;
-        for (int k = 0; k < n; k++)          // later rectangles overwrite earlier ones
-            if (x >= r[5 * k] && x < r[5 * k] + r[5 * k + 2] && y >= r[5 * k + 1] && y < r[5 * k + 1] + r[5 * k + 3]) v = r[5 * k + 4];
-        const int a = (W - plat) / 2, b = (W + plat) / 2;
+        v = stones ? T.ip[3] : 0;
+        for (int k = n - 1; k >= 0; k--)
+            if (x >= r[5 * k] && x < r[5 * k] + r[5 * k + 2] && y >= r[5 * k + 1] && y < r[5 * k + 1] + r[5 * k + 3]) { v = r[5 * k + 4]; break; }
         if (x >= a && x < b && y >= a && y < b) v = 0;
+    } else if (T.kind == LG_TILE_GAP) {
+        // the -1000 square, then the zero platform inside it (terrain_utils.py:489-490)
+        if (x >= T.ip[0] && x < T.ip[1] && y >= T.ip[0] && y < T.ip[1]) v = -1000;
+        if (x >= T.ip[2] && x < T.ip[3] && y >= T.ip[2] && y < T.ip[3]) v = 0;
+    } else if (T.kind == LG_TILE_PIT) {
+        if (x >= T.ip[0] && x < T.ip[1] && y >= T.ip[0] && y < T.ip[1]) v = T.ip[2];
+    } else if (T.kind == LG_TILE_WAVE) {
+        // (amplitude cos(yy / div) + amplitude sin(xx / div)).astype(int16) inside the edge (terrain_utils.py:300-301); both factors
+        // come from the host (numpy's cos / sin), so the only arithmetic here is numpy's one float64 add and the truncation
+        const int edge = T.ip[0], n = T.ip[1], i = x - edge, j = y - edge;
+        if (i >= 0 && i < n && j >= 0 && j < n) {
+            const double *cy = aux + T.aux_off, *sx = cy + n;
+            v = (int)(int16_t)__dadd_rn(cy[j], sx[i]);
+        }
     } else if (T.kind == LG_TILE_UNIFORM) {
         // np.rint(RectBivariateSpline(kx = ky = 1)(xs, ys)) inside the edge: FITPACK fpbisp / fpbspl for degree 1
         const int edge = T.ip[0], nx = T.ip[1], ny = T.ip[2], mx = T.ip[3], my = T.ip[4];
@@ -615,6 +632,8 @@ __global__ __launch_bounds__(256) void terrain_origin_kernel(const LgTerrainTile
     for (int s = 128; s > 0; s >>= 1) { if ((int)threadIdx.x < s) smax[threadIdx.x] = max(smax[threadIdx.x], smax[threadIdx.x + s]); __syncthreads(); }
     if (threadIdx.x == 0) origin_z[blockIdx.x] = __dmul_rn((double)smax[0], vscale);
 }
+
+extern "C" int lg_terrain_max_kind(void) { return LG_TILE_MAX_KIND; }
 
 extern "C" int lg_terrain_generate(const LgTerrainTile *tiles, int32_t n_tiles, const double *aux, const int32_t *iaux, int16_t *hf, int32_t rows,
                                    int32_t cols, int32_t tile_px, int32_t border_px, int32_t o1, int32_t o2, double vertical_scale, double *origin_z,

@@ -385,20 +385,30 @@ int lg_profile_read(LgHandle h, float *mean_us, int32_t *samples);
  * `iters` times with a float4 grid-stride kernel on `stream`, timed with HIP events after one untimed pass; *gbs = (read + write)
  * bytes per second / 1e9.  src / dst: device pointers, 16-byte aligned, not overlapping. */
 int lg_stream_copy(const void *src, void *dst, int64_t bytes, int32_t iters, void *stream, float *gbs);
-/* ---- heightfield generation on the device (legged_gym/utils/terrain.py:37-203, terrain_utils.py:34-372).
+/* ---- heightfield generation on the device (legged_gym/utils/terrain.py:37-203, terrain_utils.py:34-519).
  * One tile of the terrain map.  The host side (hcr_genesis_lr_cl_amd/terrain.py) walks the tiles in the reference's order, takes the
  * numpy draws the reference would take (np.random.choice call order) and describes each tile here; the kernel then evaluates every pixel
  * of every tile: integers for the stairs and the obstacles, the reference's float64 arithmetic for the slopes, and FITPACK's own evaluation
- * recurrences (fpbspl / fpbisp, kx = ky = 1) for the up-sampled random-uniform tiles, whose spline knots and coefficients the host fitted.
+ * recurrences (fpbspl / fpbisp, kx = ky = 1) for the up-sampled random-uniform tiles, whose spline knots and coefficients the host fitted;
+ * for the wave tiles one float64 add of the two host-evaluated factors (numpy's own cos / sin) and the int16 truncation of .astype.
+ * Spans [lo, hi) are numpy's reading of the reference's slices, resolved on the host.
  * Result: the int16 grid of the reference sample for sample (tests/golden/terrain_*.npz). */
 #define LG_TILE_SLOPE 0      /* terrain_utils.py:128-181  ip: peak, edge, half platform; */
 #define LG_TILE_UNIFORM 1    /* terrain_utils.py:34-96    ip: edge, nx (knots), ny, n eval x, n eval y; aux: tx | ty | c | x | y (doubles) */
 #define LG_TILE_STAIRS 2     /* terrain_utils.py:330-372  ip: step width px, step height (int16 units, signed), platform px */
 #define LG_TILE_OBSTACLES 3  /* terrain_utils.py:204-258  ip: n rectangles, platform px; iaux: (i0, j0, w, l, height) per rectangle, in draw order */
+#define LG_TILE_STONES 4     /* terrain_utils.py:391-469  ip: n rectangles, platform lo, platform hi, background (int(depth / vscale));
+                                iaux: (i0, j0, w, l, height) per stone, in draw order (later ones overwrite earlier ones), then the zero
+                                platform [lo, hi)^2 */
+#define LG_TILE_GAP 5        /* terrain_utils.py:471-497  ip: outer lo, outer hi, inner lo, inner hi: -1000 on the outer square, 0 on the inner */
+#define LG_TILE_PIT 6        /* terrain_utils.py:499-519  ip: lo, hi, height: `height` on the square [lo, hi)^2 */
+#define LG_TILE_WAVE 7       /* terrain_utils.py:273-303  ip: edge, n (0: flat tile); aux: amplitude cos(y / div) (n) | amplitude sin(x / div) (n),
+                                for x, y = edge .. edge + n - 1 */
+#define LG_TILE_MAX_KIND 7
 typedef struct LgTerrainTile {
     int32_t kind, row, col;  /* tile (row, col) of the map: rows = levels (x), cols = types (y) */
     int32_t ip[5];
-    int32_t aux_off;         /* first double of this tile in `aux` / first int in `iaux` */
+    int32_t aux_off;         /* first double of this tile in `aux` / first int in `iaux` (OBSTACLES, STONES) */
 } LgTerrainTile;
 /* Fill the (rows x cols) int16 heightfield `hf` (device, zeroed here: the border stays flat) and the per-tile origin heights
  * `origin_z` (n_tiles doubles, device: max over the central 2 m x 2 m times vertical_scale, terrain.py:197-202).  tiles / aux / iaux: device
@@ -407,6 +417,8 @@ typedef struct LgTerrainTile {
 int lg_terrain_generate(const LgTerrainTile *tiles, int32_t n_tiles, const double *aux, const int32_t *iaux, int16_t *hf, int32_t rows,
                         int32_t cols, int32_t tile_px, int32_t border_px, int32_t o1, int32_t o2, double vertical_scale, double *origin_z,
                         void *stream);
+/* The highest LG_TILE_* kind this library's lg_terrain_generate evaluates (older libraries lack the symbol and leave unknown kinds flat). */
+int lg_terrain_max_kind(void);
 /* Diagnostic: one Philox4x32-10 block computed on the device by the kernel's own generator (known-answer tests). */
 int lg_philox(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4]);
 /* Known-answer test of the DPP operand behaviour the build's hazard pass relies on (hcr_genesis_lr_cl_amd/dpp_hazard_pass.py; no
