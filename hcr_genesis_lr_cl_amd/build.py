@@ -7,7 +7,10 @@ the flags are unchanged (content hash), so an edit of lg_quad.h rebuilds the twe
 The kernel groups go through the compiler's ASSEMBLY: hipcc -S (device) -> dpp_hazard_pass.fix (the s_nop each DPP read needs, no
 more: the inline-asm products of lg_quad.h otherwise pay a two-slot nop per block) -> assembler -> lld -> offload bundle -> host
 compile with that bundle.  These are the steps `hipcc -c` runs itself (hipcc -###), with the pass in the middle; the rewritten text is
-re-checked and a finding fails the build.  LG_NO_DPP_PASS=1 compiles the groups with plain `hipcc -c` (every marked nop stays)."""
+re-checked and a finding fails the build.  LG_NO_DPP_PASS=1 compiles the groups with plain `hipcc -c` (every marked nop stays).
+LG_DPP_PASS_MODE=strict runs the pass in its strict mode (LLVM's rule: two wait states behind a write of ANY VGPR operand of a DPP
+instruction, asm blocks included, nothing removed); __graft_entry__.build() builds csrc/liblgsim_strict.so that way next to the product
+library, and tests/test_gpu_dpp_strict_ab.py compares the two."""
 import hashlib
 import json
 import os
@@ -23,6 +26,9 @@ OUT = os.environ.get("LG_BUILD_OUT") or os.path.join(CSRC, "liblgsim.so")
 OBJ = os.path.join(CSRC, "obj" if "LG_BUILD_OUT" not in os.environ else "obj_" + os.path.splitext(os.path.basename(OUT))[0])
 LLVM_BIN = os.environ.get("LG_LLVM_BIN", "/opt/rocm/lib/llvm/bin")
 DPP_PASS = os.environ.get("LG_NO_DPP_PASS", "0") != "1"
+PASS_MODE = os.environ.get("LG_DPP_PASS_MODE", "default")
+if PASS_MODE not in ("default", "strict"):
+    raise ValueError(f"LG_DPP_PASS_MODE={PASS_MODE!r}: expected 'default' or 'strict'")
 N_GROUPS = 22
 QUAD_GROUPS = list(range(0, 9)) + list(range(17, 22))   # lg_inst.hip: groups that include lg_quad.h
 COMMON = ["lg_shared.h", "lg_math.h", os.path.join(INC, "lgsim.h")]
@@ -36,7 +42,7 @@ FALLBACK_FLAGS = [["-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-i
 
 def units():
     """(object name, source, extra defines, dependencies) of every translation unit."""
-    u = [("lg_host", "lg_host.hip", [], COMMON), ("lg_rollout", "lg_rollout.hip", [], [os.path.join(INC, "lgrollout.h")])]
+    u = [("lg_host", "lg_host.hip", [], COMMON + ["lg_dpp_kat.h"]), ("lg_rollout", "lg_rollout.hip", [], [os.path.join(INC, "lgrollout.h")])]
     for g in range(N_GROUPS):
         deps = COMMON + ["lg_kernel.h"] + (["lg_quad.h"] if g in QUAD_GROUPS else []) + ([os.path.join(HERE, "dpp_hazard_pass.py")] if DPP_PASS else [])
         u.append((f"lg_inst_{g}", "lg_inst.hip", [f"-DLG_GROUP={g}"], deps))
@@ -62,7 +68,7 @@ def source_hash():
 
 
 def _unit_key(src, defs, deps, flags):
-    h = hashlib.sha256(" ".join(flags + defs + (["dpp-pass"] if DPP_PASS else [])).encode())
+    h = hashlib.sha256(" ".join(flags + defs + (["dpp-pass", PASS_MODE] if DPP_PASS else [])).encode())
     for f in [src] + list(deps):
         with open(_path(f), "rb") as fh:
             h.update(fh.read())
@@ -129,9 +135,12 @@ def _compile_through_pass(name, base, src, obj):
     r = subprocess.run(steps[0], capture_output=True, text=True)
     if r.returncode != 0:
         return r
-    with open(stem + ".s") as f:
-        text, stats = dpp_hazard_pass.fix(f.read())
-    left = dpp_hazard_pass.check(text)
+    try:
+        with open(stem + ".s") as f:
+            text, stats = dpp_hazard_pass.fix(f.read(), mode=PASS_MODE)
+        left = dpp_hazard_pass.check(text, mode=PASS_MODE)
+    except dpp_hazard_pass.PassError as e:
+        return _Result(1, str(e))
     if left:
         return _Result(1, f"dpp_hazard_pass: {len(left)} unresolved DPP hazard(s), first: {left[0]}")
     with open(stem + ".fix.s", "w") as f:
@@ -212,7 +221,8 @@ def build(force=False, verbose=False, allow_fallback=None, jobs=None):
                            "primary_flags": EXTRA_FLAGS, "primary_error": first_err[-1500:] if fell else "",
                            "hipcc": next((l for l in ver if "HIP version" in l), ver[0] if ver else ""),
                            "source_hash": source_hash(), "translation_units": len(objs),
-                           "dpp_hazard_pass": pass_stats() if DPP_PASS else None}, f, indent=1)
+                           "dpp_hazard_pass": pass_stats() if DPP_PASS else None,
+                           "dpp_pass_mode": PASS_MODE if DPP_PASS else None}, f, indent=1)
             done = True
             break
         first_err = first_err or err

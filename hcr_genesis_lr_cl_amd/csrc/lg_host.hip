@@ -2,6 +2,7 @@
 // The kernels themselves are instantiated in lg_inst.hip (lg_kernel.h: one leg per lane; lg_quad.h: one vector component per lane) and
 // reached through the launchers declared in lg_shared.h.
 #include "lg_shared.h"
+#include "lg_dpp_kat.h"
 #include <algorithm>
 
 // ---------------------------------------------------------------------------------------------
@@ -701,6 +702,65 @@ extern "C" int lg_dpp_kat(const float *in_host, float *out_host) {
     hipError_t e = hipMemcpy(out_host, d + 128, 320 * sizeof(float), hipMemcpyDeviceToHost);
     (void)hipFree(d);
     if (e != hipSuccess) return fail(std::string("lg_dpp_kat: ") + hipGetErrorString(e));
+    return 0;
+}
+
+// The table-driven DPP operand known-answer test (csrc/lg_dpp_kat.h; tests/test_gpu_dpp_operands.py): every (mnemonic, role, writer, distance,
+// control) the built kernels forward, a grid of them under one control, and the fresh-DPP-source negative controls.  Each case is one asm block
+// between `s_nop 4`s (tests/test_dpp_hazard_pass.py checks in the disassembly that it reaches the chip exactly as written: this file is compiled
+// with plain hipcc, the pass never sees it).  Launched with one wave or many per SIMD: outputs go to addresses derived from the case and
+// threadIdx / blockIdx only -- the first wave's two registers per case in full, every wave's lanes that differ from `expect` as counts.
+#define LG_KAT_ONE(role, writer, dist, text) +1
+constexpr int LG_DPP_KAT_N = 0 LG_DPP_KAT_CASES(LG_KAT_ONE);
+#undef LG_KAT_ONE
+
+__device__ __forceinline__ void kat_store(int k, float d, float r, int lane, bool first_wave, float *first, const unsigned *expect, unsigned *mismatch) {
+    const int i = 2 * k * 64 + lane;
+    if (first_wave) { first[i] = d; first[i + 64] = r; }
+    if (expect) {
+        if (__float_as_uint(d) != expect[i]) atomicAdd(mismatch + i, 1u);
+        if (__float_as_uint(r) != expect[i + 64]) atomicAdd(mismatch + i + 64, 1u);
+    }
+}
+
+__global__ void __launch_bounds__(1024) dpp_kat_table_kernel(const float *in, const unsigned *expect, float *first, unsigned *mismatch) {
+    const int lane = threadIdx.x & 63;
+    const bool first_wave = blockIdx.x == 0 && threadIdx.x < 64;
+    const float x = in[lane], y = in[64 + lane], z = in[128 + lane], s = in[192 + lane], o = in[256 + lane];
+    int k = 0;
+#define LG_KAT_RUN(role, writer, dist, text) { \
+        float d_, r_, t_; \
+        asm volatile("s_nop 4\n\tv_mov_b32_e32 %[r], %[s]\n\tv_mov_b32_e32 %[d], %[o]\n\ts_nop 4\n\t" text "s_nop 4" \
+                     : [d] "=&v"(d_), [r] "=&v"(r_), [t] "=&v"(t_) : [x] "v"(x), [y] "v"(y), [z] "v"(z), [s] "v"(s), [o] "v"(o)); \
+        (void)t_; \
+        kat_store(k++, d_, r_, lane, first_wave, first, expect, mismatch); }
+    LG_DPP_KAT_CASES(LG_KAT_RUN)
+#undef LG_KAT_RUN
+}
+
+extern "C" int lg_dpp_kat_cases(void) { return LG_DPP_KAT_N; }
+
+extern "C" int lg_dpp_kat_run(const float *in_host, const uint32_t *expect_host, int32_t blocks, int32_t threads, float *first_host,
+                              uint32_t *mismatch_host) {
+    if (!in_host || !first_host || (expect_host && !mismatch_host) || blocks < 1 || blocks > 65536 || threads < 64 || threads > 1024 || threads % 64)
+        return fail("lg_dpp_kat_run: bad argument");
+    const size_t n_out = (size_t)2 * LG_DPP_KAT_N * 64;
+    char *d = nullptr;
+    HIPCHK(hipMalloc(&d, 5 * 64 * sizeof(float) + 3 * n_out * sizeof(float)));
+    float *d_in = (float *)d, *d_first = d_in + 5 * 64;
+    unsigned *d_expect = (unsigned *)(d_first + n_out), *d_mis = d_expect + n_out;
+    hipError_t e = hipMemcpy(d_in, in_host, 5 * 64 * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess) e = hipMemset(d_first, 0, n_out * sizeof(float));
+    if (e == hipSuccess && expect_host) e = hipMemcpy(d_expect, expect_host, n_out * sizeof(unsigned), hipMemcpyHostToDevice);
+    if (e == hipSuccess && expect_host) e = hipMemset(d_mis, 0, n_out * sizeof(unsigned));
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(dpp_kat_table_kernel, dim3(blocks), dim3(threads), 0, 0, d_in, expect_host ? d_expect : nullptr, d_first, d_mis);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpy(first_host, d_first, n_out * sizeof(float), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && expect_host) e = hipMemcpy(mismatch_host, d_mis, n_out * sizeof(unsigned), hipMemcpyDeviceToHost);
+    (void)hipFree(d);
+    if (e != hipSuccess) return fail(std::string("lg_dpp_kat_run: ") + hipGetErrorString(e));
     return 0;
 }
 

@@ -7,8 +7,10 @@ products of csrc/lg_quad.h (v_mul_f32_dpp / v_fmac_f32_dpp sequences) are inline
 needed or not.  One wave per SIMD hides nothing: an `s_nop 1` is two issue slots, ~8.6 cycles (tools/ubench/pk_issue.hip), and the
 physics loop had 50 of them per sub-step -- 1.0 us of the 25.6 us go2 step.
 
-Only the DPP-routed operand (src0) is subject to the rule: the accumulator of a v_fmac_f32_dpp chain is written and re-read in
-consecutive slots throughout lg_quad.h's blocks, and the physics matches its f64 CPU restatement.  The compiler pads for every VGPR operand of a
+Only the DPP-routed operand (src0) is subject to the rule: a src1, the accumulator of v_fmac_f32_dpp (written and re-read in consecutive
+slots throughout lg_quad.h's blocks) and the old destination of a masked DPP move are forwarded.  Every such form the built kernels contain
+(hazard_classes) is a case of the on-chip table csrc/lg_dpp_kat.h (tests/test_gpu_dpp_operands.py), and mode='strict' -- two wait states
+behind a write of ANY operand, LLVM's rule -- builds the reference library tests/test_gpu_dpp_strict_ab.py compares the product with.  The compiler pads for every VGPR operand of a
 DPP instruction; where that padding stands in front of a plain f32 / mov DPP instruction and nothing nearby has wait-state rules of its
 own (_blocks_relaxing: SGPR / VCC / EXEC writers, transcendentals, partial-register writes, memory, ...), it is dropped too
 (`_relax_compiler_nops`: 44 of the loop's remaining wait states, another 0.4 us).
@@ -30,6 +32,28 @@ EXEC_DPP_WAIT = 5       # VALU writes EXEC -> DPP op
 _LABEL = re.compile(r"^([.\w$]+):")
 _REG = re.compile(r"^v(\d+)$")
 _RANGE = re.compile(r"^v\[(\d+):(\d+)\]$")
+_SDST = re.compile(r"^(vcc(_lo|_hi)?|s\d+|s\[\d+:\d+\])$")
+_CTRL = re.compile(r"(quad_perm|row_|wave_|row_mirror|row_half_mirror)\S*(\s+(row_mask|bank_mask|bound_ctrl|fi)\S*)*")
+# the DPP instructions whose operand layout roles() knows (vdst [, sdst], src0 [, src1 [, src2]]); any other *_dpp fails the build
+DPP_MNEMONICS = frozenset(m + "_dpp" for m in (
+    "v_mov_b32", "v_add_f32", "v_sub_f32", "v_subrev_f32", "v_mul_f32", "v_fmac_f32", "v_max_f32", "v_min_f32", "v_sqrt_f32",
+    "v_or_b32", "v_and_b32", "v_xor_b32", "v_add_u32", "v_sub_u32", "v_add_co_u32", "v_sub_co_u32", "v_cndmask_b32"))
+
+
+def _reads_old(text):
+    """A DPP instruction leaves lanes unwritten -- and so reads its destination -- under a partial row / bank mask, or when its control
+    can name a lane outside the row and bound_ctrl does not substitute zero."""
+    code = text.split(";")[0]
+    m = re.search(r"row_mask:(0x[0-9a-fA-F]+|\d+)", code)
+    b = re.search(r"bank_mask:(0x[0-9a-fA-F]+|\d+)", code)
+    if (m and int(m.group(1), 0) != 0xF) or (b and int(b.group(1), 0) != 0xF):
+        return True
+    always_valid = ("quad_perm", "row_ror", "row_mirror", "row_half_mirror")
+    return "bound_ctrl" not in code and not any(c in code for c in always_valid)
+
+
+class PassError(ValueError):
+    """The instruction stream holds something the hazard model does not cover: the build stops."""
 
 
 def _operands(rest):
@@ -86,15 +110,41 @@ class Inst:
         if not mn.startswith("v_") or mn.startswith(("v_cmp", "v_readlane", "v_readfirstlane")):
             return set()
         w = _vgprs(self.ops[0]) if self.ops else set()
-        if mn.startswith("v_swap") and len(self.ops) > 1:
-            w |= _vgprs(self.ops[1])
+        if (mn.startswith("v_swap") or (mn.startswith("v_permlane") and "_swap" in mn)) and len(self.ops) > 1:
+            w |= _vgprs(self.ops[1])        # both operands are written
         return w
 
     def writes_exec(self):
         return self.mn.startswith("v_cmpx") or (self.mn.startswith("v_") and bool(self.ops) and self.ops[0].split()[0] in ("exec", "exec_lo", "exec_hi"))
 
+    def roles(self):
+        """{role: VGPRs} of what this DPP instruction reads: 'dpp_src' (src0, routed across lanes), 'src1' / 'src2' (plain sources),
+        'acc' (the destination of v_fmac / v_mac, read as the addend), 'old' (the destination's previous content, kept in the lanes a
+        partial row / bank mask or an out-of-row source without bound_ctrl leaves unwritten).  SGPR / VCC destinations (carry-out) are
+        skipped when locating src0."""
+        ops, r = self.ops, {}
+        k = 1
+        while k < len(ops) and not _vgprs(ops[k]) and _SDST.match(ops[k].split()[0]):
+            k += 1
+        for role, j in (("dpp_src", k), ("src1", k + 1), ("src2", k + 2)):
+            if j < len(ops):
+                v = _vgprs(ops[j])
+                if v:
+                    r[role] = v
+        dst = _vgprs(ops[0]) if ops else set()
+        if self.mn.startswith(("v_fmac", "v_mac")):
+            r["acc"] = dst
+        elif dst and _reads_old(self.text):
+            r["old"] = dst
+        return r
+
     def dpp_source(self):
-        return _vgprs(self.ops[1]) if len(self.ops) > 1 else set()
+        return self.roles().get("dpp_src", set())
+
+    def dpp_control(self):
+        """The DPP modifiers as written (control, row / bank mask, bound_ctrl)."""
+        m = _CTRL.search(self.text.split(";")[0])
+        return " ".join(m.group(0).split()) if m else ""
 
     def branch_target(self):
         if self.mn.startswith(("s_cbranch", "s_branch")) and self.ops:
@@ -136,48 +186,92 @@ def _parse(lines):
     return funcs
 
 
-def _needed(items, idx, labels, branches):
-    """Wait states missing in front of the DPP instruction items[idx] (0 = none)."""
-    inst = items[idx]
-    src = inst.dpp_source()
-    worst = 0
+def _recent_writes(items, idx, branches):
+    """Every write that lies fewer wait states in front of the DPP instruction items[idx] than the hardware could ask for, over all paths
+    that reach it: a list of (role, writer, wait states between).  role is one of the instruction's roles() ('dpp_src', 'src1', 'src2',
+    'acc', 'old'; window: two wait states), 'exec' (a VALU write of EXEC; five) or 'unknown' (a predecessor the walk cannot follow: a
+    label that no branch names and nothing falls through to, or more than eight branches deep; writer None -- it counts as a write of
+    every operand)."""
+    roles = items[idx].roles()
+    found = []
 
     def walk(j, ws, depth):
-        # scan backwards from item j (exclusive) with `ws` wait states already between; returns nothing, updates `worst`
-        nonlocal worst
+        # scan backwards from item j (exclusive) with `ws` wait states already between
         while j > 0:
             j -= 1
             it = items[j]
             if isinstance(it, tuple):          # a label: whoever branches here is a predecessor too
-                for b in branches.get(it[1], ()):  # the branch instruction itself is one wait state
+                preds = branches.get(it[1], ())
+                for b in preds:                # the branch instruction itself is one wait state
                     if depth < 8:
                         walk(b + 1, ws, depth + 1)
-                    else:                      # never seen; if it happens the path counts as an immediate writer
-                        worst = max(worst, VGPR_DPP_WAIT - min(ws, VGPR_DPP_WAIT))
+                    else:
+                        found.append(("unknown", None, ws))
+                if not preds and not _falls_into(items, j):
+                    found.append(("unknown", None, ws))
+                    return
                 continue                       # ... and so is the fall-through path above the label (if it falls through)
             if it.mn == "s_branch" or it.mn == "s_endpgm" or it.mn.startswith("s_setpc"):
                 return                         # nothing falls through an unconditional branch
-            if ws < VGPR_DPP_WAIT and (it.vgpr_writes() & src):
-                worst = max(worst, VGPR_DPP_WAIT - ws)
+            if ws < VGPR_DPP_WAIT:
+                w = it.vgpr_writes()
+                if w:
+                    for role, regs in roles.items():
+                        if w & regs:
+                            found.append((role, it, ws))
             if ws < EXEC_DPP_WAIT and it.writes_exec():
-                worst = max(worst, EXEC_DPP_WAIT - ws)
+                found.append(("exec", it, ws))
             ws += it.wait_states
             if ws >= EXEC_DPP_WAIT:
                 return
         # ran off the top of the function with the window still open: the kernel entry, no writer before it
     walk(idx, 0, 0)
+    return found
+
+
+def _falls_into(items, j):
+    """True when execution can fall through into the label items[j] from the instruction above it (or j is the function's entry)."""
+    k = j - 1
+    while k >= 0 and isinstance(items[k], tuple):
+        k -= 1
+    if k < 0:
+        return True
+    it = items[k]
+    return not (it.mn in ("s_branch", "s_endpgm") or it.mn.startswith("s_setpc"))
+
+
+STRICT_ROLES = ("dpp_src", "src1", "src2", "acc", "old")
+
+
+def _needed(items, idx, branches, mode="default"):
+    """Wait states missing in front of the DPP instruction items[idx] (0 = none).  mode 'default': the hardware rule as this project
+    has measured it -- only a write of the DPP-routed source (and of EXEC) needs wait states; 'strict': LLVM's rule, two wait states
+    behind a write of ANY VGPR operand (tests/test_gpu_dpp_strict_ab.py compares the two builds)."""
+    roles = ("dpp_src",) if mode == "default" else STRICT_ROLES
+    if mode not in ("default", "strict"):
+        raise ValueError(f"dpp_hazard_pass: unknown mode {mode!r}")
+    worst = 0
+    for role, _, ws in _recent_writes(items, idx, branches):
+        if role == "exec":
+            worst = max(worst, EXEC_DPP_WAIT - ws)
+        elif role in roles or role == "unknown":
+            worst = max(worst, VGPR_DPP_WAIT - ws)
     return worst
 
 
 def _analyse(items):
-    labels = {it[1]: k for k, it in enumerate(items) if isinstance(it, tuple)}
+    """-> {label: [indices of the branches to it]}; fails on what the model does not cover (unknown DPP forms, indirect jumps)."""
     branches = {}
     for k, it in enumerate(items):
         if isinstance(it, Inst):
+            if it.is_dpp and it.mn not in DPP_MNEMONICS:
+                raise PassError(f"dpp_hazard_pass: {items[0][1]}: {it.mn} is not a DPP form the hazard model knows: {it.text}")
+            if it.mn.startswith(("s_setpc", "s_swappc")):
+                raise PassError(f"dpp_hazard_pass: {items[0][1]}: indirect jump ({it.text}): its targets are not known to the walk")
             t = it.branch_target()
             if t is not None:
                 branches.setdefault(t, []).append(k)
-    return labels, branches
+    return branches
 
 
 _PLAIN_DPP = ("v_mov_b32_dpp", "v_add_f32_dpp", "v_sub_f32_dpp", "v_subrev_f32_dpp", "v_mul_f32_dpp", "v_fmac_f32_dpp", "v_max_f32_dpp", "v_min_f32_dpp")
@@ -233,16 +327,19 @@ def _relax_compiler_nops(lines, stats):
     return [raw for i, raw in enumerate(lines) if i not in drop]
 
 
-def fix(text, relax=True):
-    """-> (new text, stats).  Removes the marked nops (and, `relax`, the compiler's over-wide padding in front of plain DPP instructions),
-    then inserts the minimal s_nop in front of every DPP read that needs one."""
+def fix(text, relax=True, mode="default"):
+    """-> (new text, stats).  mode 'default': removes the marked nops (and, `relax`, the compiler's over-wide padding in front of plain DPP
+    instructions), then inserts the minimal s_nop in front of every DPP read whose DPP source needs one.  mode 'strict': removes and relaxes
+    nothing and pads every DPP read to two wait states behind a write of any of its VGPR operands, inside asm blocks too."""
+    if mode == "strict":
+        relax = False
     lines = text.split("\n")
     stats = {"marked": 0, "kept_or_inserted": 0, "wait_states_inserted": 0, "dpp": 0, "functions": 0, "compiler_nops_relaxed": 0, "compiler_wait_states_relaxed": 0}
     # 1. drop the marked nops
     keep = []
     for raw in lines:
         s = raw.strip()
-        if MARK in s and s.startswith("s_nop"):
+        if mode == "default" and MARK in s and s.startswith("s_nop"):
             stats["marked"] += 1
             continue
         keep.append(raw)
@@ -254,13 +351,13 @@ def fix(text, relax=True):
     stats["functions"] = len(funcs)
     inserts = {}                                # line index -> s_nop operand
     for items in funcs:
-        labels, branches = _analyse(items)
+        branches = _analyse(items)
         k = 0
         while k < len(items):
             it = items[k]
             if isinstance(it, Inst) and it.is_dpp:
                 stats["dpp"] += 1
-                need = _needed(items, k, labels, branches)
+                need = _needed(items, k, branches, mode)
                 if need > 0:
                     nop = Inst("s_nop", [str(need - 1)], it.line, False, "")
                     items.insert(k, nop)
@@ -280,18 +377,52 @@ def fix(text, relax=True):
     return "\n".join(out), stats
 
 
-def check(text):
-    """Findings (function, line number, instruction, missing wait states) of a text as it stands; [] = clean."""
+def check(text, mode="default"):
+    """Findings (function, line number, instruction, missing wait states) of a text as it stands under `mode`'s rule; [] = clean."""
     lines = text.split("\n")
     bad = []
     for items in _parse(lines):
-        labels, branches = _analyse(items)
+        branches = _analyse(items)
         for k, it in enumerate(items):
             if isinstance(it, Inst) and it.is_dpp:
-                need = _needed(items, k, labels, branches)
+                need = _needed(items, k, branches, mode)
                 if need > 0:
                     bad.append((items[0][1], it.line + 1, it.text, need))
     return bad
+
+
+def check_strict(text):
+    return check(text, mode="strict")
+
+
+def writer_kind(it):
+    """'dpp' (a DPP VALU), 'trans' (a transcendental), 'valu' (any other VALU); 'unknown' for an unresolved predecessor."""
+    if it is None:
+        return "unknown"
+    if it.is_dpp:
+        return "dpp"
+    if it.mn.startswith(_TRANS):
+        return "trans"
+    return "valu"
+
+
+def hazard_classes(text):
+    """{(mnemonic, role, writer kind, wait states, control): count} of the DPP reads in `text` that have an operand written fewer than two
+    wait states before (over all paths, as fix() walks them) -- the forms the chip has to forward for the default rule to hold."""
+    out = {}
+    for items in _parse(text.split("\n")):
+        branches = _analyse(items)
+        for k, it in enumerate(items):
+            if isinstance(it, Inst) and it.is_dpp:
+                seen = set()
+                for role, w, ws in _recent_writes(items, k, branches):
+                    if role == "exec" or ws >= VGPR_DPP_WAIT:
+                        continue
+                    key = (it.mn, role, writer_kind(w), ws, it.dpp_control())
+                    if key not in seen:
+                        seen.add(key)
+                        out[key] = out.get(key, 0) + 1
+    return out
 
 
 if __name__ == "__main__":

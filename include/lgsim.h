@@ -425,6 +425,12 @@ int lg_philox(const uint32_t counter[4], const uint32_t key[2], uint32_t out[4])
  * reference counterpart).  in: 64 x then 64 y (host); out: 5 x 64 floats (host) -- rot1(x) + x y with the product written in the slot
  * before | x y + rot1(x) y likewise (fused) | rot1(x y) + x behind the two wait states | the same without them (negative control) | x y. */
 int lg_dpp_kat(const float *in_host, float *out_host);
+/* The table-driven DPP operand known-answer test (the cases of hcr_genesis_lr_cl_amd/csrc/lg_dpp_kat.h, in order).  in: 5 x 64 floats (host):
+ * x, y, z, the sentinel of %[r], the old value of %[d].  first: 2 N x 64 floats (host): per case %[d] then %[r] of the first wave.
+ * expect (host, may be NULL): 2 N x 64 result bit patterns; mismatch (host, needed with expect): per case and lane, the number of waves
+ * whose result differs.  blocks x threads: the launch (threads a multiple of 64, at most 1024). */
+int lg_dpp_kat_cases(void);
+int lg_dpp_kat_run(const float *in_host, const uint32_t *expect_host, int32_t blocks, int32_t threads, float *first_host, uint32_t *mismatch_host);
 const char *lg_last_error(void);
 int lg_abi_version(void);
 
