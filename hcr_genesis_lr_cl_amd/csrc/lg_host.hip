@@ -4,6 +4,7 @@
 #include "lg_shared.h"
 #include "lg_dpp_kat.h"
 #include <algorithm>
+#include <unistd.h>
 
 // ---------------------------------------------------------------------------------------------
 // sliding observation history ran out of slack: move the newest stack-1 frames of every row back to frames [1, stack)
@@ -33,6 +34,8 @@ struct LgEngine {
     int obs_win = 0;     // window of the latest stacked observation (obs_slack > 0)
     int obs_set = 0;     // copy of the observation buffers the latest observation launch wrote (obs_sets == 2)
     std::string last_kernel;   // launcher instantiation(s) of the latest lg_step (lg_last_kernel)
+    // fixed by the model (model_frames): KParams.k.joint_axis / .jrot_identity, and whether the component-per-lane kernels apply
+    int joint_axis[4], jrot_identity; bool quad_ok;
     // bounded run-ahead: the host never gets more than ~128 lg_step calls ahead of the device (see lg_step)
     hipEvent_t ra_ev[4] = {nullptr, nullptr, nullptr, nullptr}; long long ra_calls = 0;
     // sampling timer of the physics kernel (lg_profile)
@@ -90,6 +93,29 @@ static int validate_model(const LgModelDesc *m) {
     return 0;
 }
 
+// identity joint frames and hip-x / thigh-y / knee-y (/ y) axes: what the component-per-lane kernels are specialised for (lg_quad.h)
+static void model_frames(LgEngine *h) {
+    const LgModelDesc &m = h->model;
+    const int J = m.n_bodies == 1 + 3 * m.n_legs ? 3 : 4;     // joints per leg (validate_model)
+    h->joint_axis[3] = -1;
+    for (int j = 0; j < J; j++) {
+        int code = -2;
+        for (int l = 0; l < m.n_legs; l++) {
+            const float *ax = m.axis[1 + J * l + j];
+            int c = -1;
+            for (int k = 0; k < 3; k++)
+                if (fabsf(fabsf(ax[k]) - 1.f) < 1e-6f && fabsf(ax[(k + 1) % 3]) < 1e-6f && fabsf(ax[(k + 2) % 3]) < 1e-6f) c = k;
+            code = (code == -2 || code == c) ? c : -1;
+        }
+        h->joint_axis[j] = code;
+    }
+    h->jrot_identity = 1;
+    for (int b = 1; b < m.n_bodies; b++)
+        for (int k = 0; k < 9; k++)
+            if (m.jrot[b][k] != ((k % 4 == 0) ? 1.f : 0.f)) h->jrot_identity = 0;
+    h->quad_ok = h->jrot_identity && h->joint_axis[0] == 0 && h->joint_axis[1] == 1 && h->joint_axis[2] == 1 && (J == 3 || h->joint_axis[3] == 1);
+}
+
 extern "C" int lg_create(const LgModelDesc *model, const LgSimOptions *opts, const LgTaskCfg *task, LgHandle *out) {
     if (!model || !opts || !task || !out) return fail("lg_create: null argument");
     if (validate_model(model)) return 1;
@@ -104,6 +130,7 @@ extern "C" int lg_create(const LgModelDesc *model, const LgSimOptions *opts, con
     if (task->obs_sets > 4096) return fail("lg_create: obs_sets out of range");
     LgEngine *h = new LgEngine();
     h->model = *model; h->opts = *opts; h->task = *task;
+    model_frames(h);
     memset(&h->bufs, 0, sizeof(h->bufs));
     hipError_t e;
     if ((e = hipMalloc(&h->d_model, MODEL_STG * BLOCK * 16)) != hipSuccess || (e = hipMalloc(&h->d_opts, sizeof(LgSimOptions))) != hipSuccess ||
@@ -171,64 +198,65 @@ static int prof_begin(LgEngine *h, hipStream_t st) {
     (void)st;
     return h->prof_count++;
 }
-// launch with the kernel's own begin / end timestamps when this step is sampled (hipExtLaunchKernelGGL attaches the
-// events to the dispatch packet itself, so the reading is the kernel's duration, comparable with rocprofv3's).
-// `kern`: a launcher instantiation of lg_shared.h, e.g. (lg_launch_quad<4, true, 12u, 1, 3>)
-#define LG_LAUNCH(pi, kern, grid_) (h->last_kernel = #kern, kern(grid_, st, (pi) >= 0 ? h->prof_ev[2 * (pi)] : nullptr, (pi) >= 0 ? h->prof_ev[2 * (pi) + 1] : nullptr, p))
-// a control step made of two launches (physics, then the MDP phases): begin timestamp of the first, end timestamp of
-// the second, so that the sample is the whole step including the gap between the two
-#define LG_LAUNCH_FIRST(pi, kern, grid_) (h->last_kernel = #kern, kern(grid_, st, (pi) >= 0 ? h->prof_ev[2 * (pi)] : nullptr, nullptr, p))
-#define LG_LAUNCH_LAST(pi, kern, grid_) (h->last_kernel += " + " #kern, kern(grid_, st, nullptr, (pi) >= 0 ? h->prof_ev[2 * (pi) + 1] : nullptr, p))
-#define LG_LAUNCH_PLAIN(kern, grid_) (h->last_kernel = #kern, kern(grid_, st, nullptr, nullptr, p))
-
 static bool flat_noise_ok(const LgEngine *h) {   // commands and actions carry no observation noise (go2.py:92-117)
     const int A = h->model.n_bodies - 1;
     for (int i = 0; i < 3; i++) if (h->task.noise_vec[i] != 0.f) return false;
     for (int i = 0; i < A; i++) if (h->task.noise_vec[9 + 2 * A + i] != 0.f) return false;
     return true;
 }
-// the plain go2-on-a-plane task: every switch the FLAT instantiations hard-wire (env_step_body) really has that value
-static bool flat_profile(const LgEngine *h, bool inj = false) {   // inj: the injected-uniform test instantiation (rand_in REQUIRED instead of forbidden)
-    const LgTaskCfg &t = h->task;
-    const LgSimOptions &o = h->opts;
-    const LgBuffers &b = h->bufs;
-    return t.obs_layout == LG_OBS_GO2 && t.gait_mode == 0 && t.double_shift == 0 && t.obs_stack == 1 && t.obs_slack == 0 && t.priv_frame == 0 &&
-           t.priv_stack <= 1 && t.num_priv_obs == 0 && t.terrain_curriculum == 0 && t.custom_origins == 0 && t.sit_percent == 0.f &&
-           t.behavior_resample_steps == 0 && t.num_labels == 0 && t.cat_enable == 0 && t.noise_vec[9 + 6 * h->model.n_legs] == 0.f && t.air_time_cmd_dims != 3 &&
-           h->model.n_bodies == 1 + 3 * h->model.n_legs &&
-           o.n_height_points == 0 && o.terrain_rows == 0 && o.feet_terrain_info == 0 && !b.link_contact_states && !b.task_state && !h->hf &&
-           (inj ? b.rand_in != nullptr : !b.rand_in) && !b.joint_armature && !t.dr_joint_on && !t.dr_pd_on && t.reset_lin_vel_span == 0.f && t.reset_ang_vel_span == 0.f && flat_noise_ok(h) &&
-           // reward terms the component-layout tail (lg_quad.h) does not carry: gait clocks, biped and wtw-only terms
-           ((unsigned)h->hot.reward_mask & ((1u << LG_R_BIPED_PERIODIC_GAIT) | (1u << LG_R_QUAD_PERIODIC_GAIT) | (1u << LG_R_FEET_DISTANCE) |
-                                            (1u << LG_R_TRACKING_BASE_HEIGHT) | (1u << LG_R_TRACKING_FOOT_CLEARANCE) |
-                                            (1u << LG_R_TRACKING_ORIENTATION))) == 0;
-}
 
-// go2_wtw on the plane (PROF 2)
-static bool wtw_profile(const LgEngine *h, bool inj = false) {
-    const LgTaskCfg &t = h->task;
-    const LgSimOptions &o = h->opts;
-    const LgBuffers &b = h->bufs;
-    return t.obs_layout == LG_OBS_GO2_WTW && t.gait_mode == 1 && t.double_shift == 1 && t.terrain_curriculum == 0 && t.custom_origins == 0 &&
-           t.sit_percent == 0.f && t.num_labels == 0 && t.cat_enable == 0 && t.noise_vec[9 + 6 * h->model.n_legs] == 0.f &&
-           o.n_height_points == 0 && o.terrain_rows == 0 && o.feet_terrain_info == 0 && !b.link_contact_states && !h->hf && b.task_state &&
-           // what the component-layout tail of lg_quad.h (PROF 2) hard-wires: sliding-window stacks of 61 | 99-wide frames, Philox draws,
-           // no per-env joint parameters, no noise on commands / actions
-           t.obs_slack > 0 && t.obs_frame == 61 && t.priv_frame == 61 + 10 + 6 * h->model.n_legs + h->model.n_legs && t.obs_stack > 1 && t.priv_stack > 1 &&
-           t.obs_sets <= 2 && (t.obs_sets < 2 || b.obs_dirty) && (inj ? b.rand_in != nullptr : !b.rand_in) && !b.joint_armature && !t.dr_joint_on && flat_noise_ok(h) &&
-           h->model.n_legs == 4 && h->model.n_bodies == 13 && b.priv_obs_buf && b.rand_push_vels &&
-           ((unsigned)h->hot.reward_mask & ((1u << LG_R_BIPED_PERIODIC_GAIT) | (1u << LG_R_FEET_DISTANCE))) == 0;
-}
-
-// the Go2-rough family (PROF 3: go2_ee packaging, PROF 4: observation programs -- go2_ts / go2_cts / go2_dreamwaq / go2_cat): no gait
-// clock, no sit pose, no noise on actions; terrain, curriculum, stacks and (PROF 4) CaT stay runtime
-static int rough_profile(const LgEngine *h, bool inj = false) {
-    const LgTaskCfg &t = h->task;
+// The task profile (lg_quad.h PROF) whose hard-wired switches the task really has, 0 for none: 1 go2 on the plane, 2 go2_wtw, 3 / 4 the
+// Go2-rough family, 6 tron1_pf_ee.  inj: the injected-uniform test instantiations (rand_in REQUIRED instead of forbidden)
+static int task_profile(const LgEngine *h, bool inj) {
+    const LgTaskCfg &t = h->task; const LgSimOptions &o = h->opts; const LgBuffers &b = h->bufs;
+    if (h->model.n_legs == 2) {
+        // biped_profile: tron1_pf_ee (PROF 6 = the component-layout tail of lg_quad.h for the three-joint biped): what it hard-wires
+        if (h->model.n_bodies != 7 || !h->hf || h->opts.terrain_rows <= 0) return 0;
+        const int K = __builtin_popcount(h->model.state_link_mask), P = h->opts.n_height_points, A = 6, F = 2;
+        return t.obs_layout == LG_OBS_TRON1_EE && t.gait_mode == 2 && t.double_shift == 1 && t.cat_enable == 0 && t.behavior_resample_steps == 0 &&
+               t.obs_slack > 0 && t.obs_stack > 1 && t.priv_stack > 1 && t.obs_sets <= 2 && (t.obs_sets < 2 || b.obs_dirty) && (inj ? b.rand_in != nullptr : !b.rand_in) &&
+               t.obs_frame == 9 + 3 * A + 2 * F && t.priv_frame == t.obs_frame + 7 + 2 * A + 3 + F + K + P + 3 * F + 9 * F && t.num_labels == 3 + K + F + 3 * F &&
+               P > 0 && P <= 7 * 8 && h->opts.feet_terrain_info && b.priv_obs_buf && b.labels_buf && b.task_state && b.rand_push_vels &&
+               t.task_state_width == LG_TASK_STATE_BIPED && b.link_contact_states &&
+               (!t.terrain_curriculum || (b.terrain_levels && b.terrain_types && b.terrain_origins && b.env_origins)) &&
+               (!t.dr_joint_on || (b.joint_armature && b.joint_friction && b.joint_damping)) &&
+               (t.slots.reset_root_xy & 3) != 3 &&       // the two root xy draws share a Philox block
+               // 32-bit byte offsets into the observation allocations (lg_quad.h)
+               (double)b.n_envs * (t.priv_stack + t.obs_slack) * t.priv_frame * 4.0 < 4.0e9 && (double)b.n_envs * (t.obs_stack + t.obs_slack) * t.obs_frame * 4.0 < 4.0e9 &&
+               // commands carry no observation noise (tron1_pf_ee.py:322-342)
+               t.noise_vec[0] == 0.f && t.noise_vec[1] == 0.f && t.noise_vec[2] == 0.f &&
+               ((unsigned)h->hot.reward_mask & ((1u << LG_R_QUAD_PERIODIC_GAIT) | (1u << LG_R_TRACKING_FOOT_CLEARANCE) | (1u << LG_R_TRACKING_ORIENTATION))) == 0
+               ? 6 : 0;
+    }
+    // flat_profile: the plain go2-on-a-plane task (PROF 1), every switch the FLAT instantiations hard-wire (env_step_body) really has that value
+    if (t.obs_layout == LG_OBS_GO2 && t.gait_mode == 0 && t.double_shift == 0 && t.obs_stack == 1 && t.obs_slack == 0 && t.priv_frame == 0 &&
+        t.priv_stack <= 1 && t.num_priv_obs == 0 && t.terrain_curriculum == 0 && t.custom_origins == 0 && t.sit_percent == 0.f &&
+        t.behavior_resample_steps == 0 && t.num_labels == 0 && t.cat_enable == 0 && t.noise_vec[9 + 6 * h->model.n_legs] == 0.f && t.air_time_cmd_dims != 3 &&
+        h->model.n_bodies == 1 + 3 * h->model.n_legs &&
+        o.n_height_points == 0 && o.terrain_rows == 0 && o.feet_terrain_info == 0 && !b.link_contact_states && !b.task_state && !h->hf &&
+        (inj ? b.rand_in != nullptr : !b.rand_in) && !b.joint_armature && !t.dr_joint_on && !t.dr_pd_on && t.reset_lin_vel_span == 0.f && t.reset_ang_vel_span == 0.f && flat_noise_ok(h) &&
+        // reward terms the component-layout tail (lg_quad.h) does not carry: gait clocks, biped and wtw-only terms
+        ((unsigned)h->hot.reward_mask & ((1u << LG_R_BIPED_PERIODIC_GAIT) | (1u << LG_R_QUAD_PERIODIC_GAIT) | (1u << LG_R_FEET_DISTANCE) |
+                                         (1u << LG_R_TRACKING_BASE_HEIGHT) | (1u << LG_R_TRACKING_FOOT_CLEARANCE) |
+                                         (1u << LG_R_TRACKING_ORIENTATION))) == 0)
+        return 1;
+    // wtw_profile: go2_wtw on the plane (PROF 2)
+    if (t.obs_layout == LG_OBS_GO2_WTW && t.gait_mode == 1 && t.double_shift == 1 && t.terrain_curriculum == 0 && t.custom_origins == 0 &&
+        t.sit_percent == 0.f && t.num_labels == 0 && t.cat_enable == 0 && t.noise_vec[9 + 6 * h->model.n_legs] == 0.f &&
+        o.n_height_points == 0 && o.terrain_rows == 0 && o.feet_terrain_info == 0 && !b.link_contact_states && !h->hf && b.task_state &&
+        // what the component-layout tail of lg_quad.h (PROF 2) hard-wires: sliding-window stacks of 61 | 99-wide frames, Philox draws,
+        // no per-env joint parameters, no noise on commands / actions
+        t.obs_slack > 0 && t.obs_frame == 61 && t.priv_frame == 61 + 10 + 6 * h->model.n_legs + h->model.n_legs && t.obs_stack > 1 && t.priv_stack > 1 &&
+        t.obs_sets <= 2 && (t.obs_sets < 2 || b.obs_dirty) && (inj ? b.rand_in != nullptr : !b.rand_in) && !b.joint_armature && !t.dr_joint_on && flat_noise_ok(h) &&
+        h->model.n_legs == 4 && h->model.n_bodies == 13 && b.priv_obs_buf && b.rand_push_vels &&
+        ((unsigned)h->hot.reward_mask & ((1u << LG_R_BIPED_PERIODIC_GAIT) | (1u << LG_R_FEET_DISTANCE))) == 0)
+        return 2;
+    // rough_profile: the Go2-rough family (PROF 3: go2_ee packaging, PROF 4: observation programs -- go2_ts / go2_cts / go2_dreamwaq / go2_cat): no gait
+    // clock, no sit pose, no noise on actions; terrain, curriculum, stacks and (PROF 4) CaT stay runtime
     if (t.gait_mode != 0 || t.sit_percent != 0.f || t.behavior_resample_steps != 0 || t.noise_vec[9 + 6 * h->model.n_legs] != 0.f || h->bufs.task_state)
         return 0;
     if (!h->hf || h->opts.terrain_rows <= 0) return 0;     // the profiles hard-wire "there is a heightfield" (lg_quad.h HFC)
     // PROF 3 / 4 = the component-layout tail of lg_quad.h for the go2_ee family: what it hard-wires
-    const LgBuffers &b = h->bufs;
     const int K = __builtin_popcount(h->model.state_link_mask), P = h->opts.n_height_points, A = h->model.n_bodies - 1;
     const bool common = t.double_shift == 0 && t.cat_enable == 0 && t.obs_slack > 0 && t.obs_frame == 9 + 3 * A && t.obs_stack > 1 && t.priv_stack > 1 &&
                         t.obs_sets <= 2 && (t.obs_sets < 2 || b.obs_dirty) && (inj ? b.rand_in != nullptr : !b.rand_in) && !b.joint_armature && !t.dr_joint_on && flat_noise_ok(h) &&
@@ -251,58 +279,150 @@ static int rough_profile(const LgEngine *h, bool inj = false) {
     return 0;
 }
 
-// tron1_pf_ee (PROF 6 = the component-layout tail of lg_quad.h for the three-joint biped): what it hard-wires
-static bool biped_profile(const LgEngine *h, bool inj = false) {
-    const LgTaskCfg &t = h->task;
-    const LgBuffers &b = h->bufs;
-    if (h->model.n_legs != 2 || h->model.n_bodies != 7 || !h->hf || h->opts.terrain_rows <= 0) return false;
-    const int K = __builtin_popcount(h->model.state_link_mask), P = h->opts.n_height_points, A = 6, F = 2;
-    return t.obs_layout == LG_OBS_TRON1_EE && t.gait_mode == 2 && t.double_shift == 1 && t.cat_enable == 0 && t.behavior_resample_steps == 0 &&
-           t.obs_slack > 0 && t.obs_stack > 1 && t.priv_stack > 1 && t.obs_sets <= 2 && (t.obs_sets < 2 || b.obs_dirty) && (inj ? b.rand_in != nullptr : !b.rand_in) &&
-           t.obs_frame == 9 + 3 * A + 2 * F && t.priv_frame == t.obs_frame + 7 + 2 * A + 3 + F + K + P + 3 * F + 9 * F && t.num_labels == 3 + K + F + 3 * F &&
-           P > 0 && P <= 7 * 8 && h->opts.feet_terrain_info && b.priv_obs_buf && b.labels_buf && b.task_state && b.rand_push_vels &&
-           t.task_state_width == LG_TASK_STATE_BIPED && b.link_contact_states &&
-           (!t.terrain_curriculum || (b.terrain_levels && b.terrain_types && b.terrain_origins && b.env_origins)) &&
-           (!t.dr_joint_on || (b.joint_armature && b.joint_friction && b.joint_damping)) &&
-           (t.slots.reset_root_xy & 3) != 3 &&       // the two root xy draws share a Philox block
-           // 32-bit byte offsets into the observation allocations (lg_quad.h)
-           (double)b.n_envs * (t.priv_stack + t.obs_slack) * t.priv_frame * 4.0 < 4.0e9 && (double)b.n_envs * (t.obs_stack + t.obs_slack) * t.obs_frame * 4.0 < 4.0e9 &&
-           // commands carry no observation noise (tron1_pf_ee.py:322-342)
-           t.noise_vec[0] == 0.f && t.noise_vec[1] == 0.f && t.noise_vec[2] == 0.f &&
-           ((unsigned)h->hot.reward_mask & ((1u << LG_R_QUAD_PERIODIC_GAIT) | (1u << LG_R_TRACKING_FOOT_CLEARANCE) | (1u << LG_R_TRACKING_ORIENTATION))) == 0;
+// Developer switches: 1 / 0 when the environment variable is set to a non-zero number / 0, -1 when unset.  Read on every lg_step (the
+// tests flip them between steps), in one pass over the environment: as cheap as one getenv.
+enum { SW_MDP_REPLICAS, SW_REWARD_SET_CONST, SW_BIPED_FUSE, SW_BIPED_TAIL, SW_SPLIT_ALL, SW_COUNT };
+static void read_switches(int sw[SW_COUNT]) {
+    static const char *const name[SW_COUNT] = {"LG_MDP_REPLICAS=", "LG_REWARD_SET_CONST=", "LG_BIPED_FUSE=", "LG_BIPED_TAIL=", "LG_SPLIT_ALL="};
+    for (int i = 0; i < SW_COUNT; i++) sw[i] = -1;
+    for (char **e = environ; *e; e++) {
+        if (strncmp(*e, "LG_", 3)) continue;
+        for (int i = 0; i < SW_COUNT; i++)
+            if (sw[i] < 0 && !strncmp(*e, name[i], strlen(name[i]))) sw[i] = atoi(*e + strlen(name[i])) != 0;   // the first, as getenv
+    }
 }
 
-template <int LEGS, int JPL = 3> static int launch(LgEngine *h, uint32_t ph, const float *actions, int64_t counter, hipStream_t st) {
+// ---- launch selection: lg_step validates, plan() picks at most two launches without side effects, execute() runs them ----------------
+using LgLauncher = void (*)(dim3, hipStream_t, hipEvent_t, hipEvent_t, const KParams &);
+struct LgKernel { LgLauncher fn; const char *name; };   // a launcher of lg_shared.h and the name lg_last_kernel reports for it
+#define LG_KERNEL(kern) LgKernel{kern, #kern}
+template <int LEGS, int PROF> static void launch_inj(dim3 grid, hipStream_t st, hipEvent_t, hipEvent_t, const KParams &p) { lg_launch_quad_inj<LEGS, PROF>(grid, st, p); }
+
+// Every kernel lg_step launches, named once, as the launcher expression lg_step has always reported (LEGS / JPL / PR tokens included:
+// bench.py's roofline.kernel and the GPU tests match on these strings).  A row is instantiated only where plan() uses it.
+template <int LEGS, int JPL> struct Kernels {
+    static constexpr unsigned PR = LG_PHASE_POST | LG_PHASE_RESET;
+    // leg per lane (lg_kernel.h), one launch per phase set; POST | RESET also replicated (env_step_kernel<..., REPL>)
+    static constexpr LgKernel all = LG_KERNEL((lg_launch_env<LEGS, LG_PHASE_ALL, 0, JPL, false>)), all_flat = LG_KERNEL((lg_launch_env<4, LG_PHASE_ALL, 1, 3, false>)),
+        sim = LG_KERNEL((lg_launch_env<LEGS, LG_PHASE_SIM, 0, JPL, false>)), pre_sim = LG_KERNEL((lg_launch_env<LEGS, LG_PHASE_PRE | LG_PHASE_SIM, 0, JPL, false>)),
+        pre_sim_post = LG_KERNEL((lg_launch_env<LEGS, LG_PHASE_PRE | LG_PHASE_SIM | LG_PHASE_POST, 0, JPL, false>)),
+        pre_post_reset = LG_KERNEL((lg_launch_env<LEGS, LG_PHASE_PRE | PR, 0, JPL, false>)), pre_post = LG_KERNEL((lg_launch_env<LEGS, LG_PHASE_PRE | LG_PHASE_POST, 0, JPL, false>)),
+        post_reset = LG_KERNEL((lg_launch_env<LEGS, PR, 0, JPL, false>)), post_reset_repl = LG_KERNEL((lg_launch_env<LEGS, PR, 0, JPL, true>)),
+        post = LG_KERNEL((lg_launch_env<LEGS, LG_PHASE_POST, 0, JPL, false>)), reset = LG_KERNEL((lg_launch_env<LEGS, LG_PHASE_RESET, 0, JPL, false>));
+    // component per lane (lg_quad.h), three joints per leg.  Physics only by [PRE][heightfield bound]: PROF 3 here only says "a heightfield
+    // is bound" (lg_quad.h HFC: no branch in front of the terrain loads)
+    static constexpr LgKernel phys[2][2] = {{LG_KERNEL((lg_launch_quad<LEGS, false, 0u, 0, 3>)), LG_KERNEL((lg_launch_quad<LEGS, false, 0u, 3, 3>))},
+                                            {LG_KERNEL((lg_launch_quad<LEGS, true, 0u, 0, 3>)), LG_KERNEL((lg_launch_quad<LEGS, true, 0u, 3, 3>))}};
+    // quadruped whole step: the leg-per-lane MDP body in the tail, the tails of PROF 1-4 and the same with the profile's default reward set
+    // as a constant (lg_quad.h RS); biped whole step: the leg-per-lane MDP body in the tail (PROF 0, 5: a heightfield is bound), tron1_pf_ee's (6)
+    static constexpr LgKernel quad_pre_sim_post = LG_KERNEL((lg_launch_quad<4, true, LG_PHASE_POST, 0, 3>)), quad_all = LG_KERNEL((lg_launch_quad<4, true, PR, 0, 3>)),
+        biped_all = LG_KERNEL((lg_launch_quad<2, true, PR, 0, 3>)), biped_all_hf = LG_KERNEL((lg_launch_quad<2, true, PR, 5, 3>)),
+        biped_all_ee = LG_KERNEL((lg_launch_quad<2, true, PR, 6, 3>));
+    static constexpr LgKernel quad_prof[4] = {LG_KERNEL((lg_launch_quad<4, true, PR, 1, 3>)), LG_KERNEL((lg_launch_quad<4, true, PR, 2, 3>)),
+                                              LG_KERNEL((lg_launch_quad<4, true, PR, 3, 3>)), LG_KERNEL((lg_launch_quad<4, true, PR, 4, 3>))};
+    static constexpr LgKernel quad_prof_rs[4] = {LG_KERNEL((lg_launch_quad_rs<4, 1, false>)), LG_KERNEL((lg_launch_quad_rs<4, 2, false>)),
+                                                 LG_KERNEL((lg_launch_quad_rs<4, 3, false>)), LG_KERNEL((lg_launch_quad_rs<4, 4, false>))};
+    // golden replays: PRE | POST | RESET through the tails of PROF 1-4 / 6 on injected read-backs and uniforms (lg_quad.h INJ)
+    static constexpr LgKernel inj[4] = {{launch_inj<4, 1>, "(lg_launch_quad_inj<4, 1>)"}, {launch_inj<4, 2>, "(lg_launch_quad_inj<4, 2>)"},
+                                        {launch_inj<4, 3>, "(lg_launch_quad_inj<4, 3>)"}, {launch_inj<4, 4>, "(lg_launch_quad_inj<4, 4>)"}};
+    static constexpr LgKernel inj_rs[4] = {{lg_launch_quad_rs<4, 1, true>, "(lg_launch_quad_inj<4, 1>, reward set constant)"}, {lg_launch_quad_rs<4, 2, true>, "(lg_launch_quad_inj<4, 2>, reward set constant)"},
+                                           {lg_launch_quad_rs<4, 3, true>, "(lg_launch_quad_inj<4, 3>, reward set constant)"}, {lg_launch_quad_rs<4, 4, true>, "(lg_launch_quad_inj<4, 4>, reward set constant)"}};
+    static constexpr LgKernel inj_biped = {launch_inj<2, 6>, "(lg_launch_quad_inj<2, 6>)"};
+    // four joints per leg (TRON1 sole foot; these exist for the biped alone, hence plan()'s `if constexpr`): physics by [PRE], then the MDP phases
+    static constexpr LgKernel sole_phys[2] = {LG_KERNEL((lg_launch_quad<LEGS, false, 0u, 0, 4>)), LG_KERNEL((lg_launch_quad<LEGS, true, 0u, 0, 4>))};
+    static constexpr LgKernel sole_post_reset = LG_KERNEL((lg_launch_env<LEGS, PR, 0, 4, false>)), sole_post_reset_repl = LG_KERNEL((lg_launch_env<LEGS, PR, 0, 4, true>)),
+        sole_post = LG_KERNEL((lg_launch_env<LEGS, LG_PHASE_POST, 0, 4, false>));
+};
+
+struct LgPlan { struct { LgKernel k; dim3 grid; } l[2]; int n = 0; bool sim = false; };   // launches in order; sim: a sampled (SIM) step
+
+// The launches of one lg_step for a robot shape, on phases lg_step has validated.  No side effects.
+template <int LEGS, int JPL> static LgPlan plan(const LgEngine *h, uint32_t ph, const int sw[SW_COUNT]) {
+    using K = Kernels<LEGS, JPL>;
+    constexpr unsigned PR = K::PR;
+    LgPlan pl; pl.sim = (ph & LG_PHASE_SIM) != 0;
+    const auto add = [&pl](const LgKernel &k, dim3 grid) { pl.l[pl.n].k = k; pl.l[pl.n].grid = grid; pl.n++; };
+    const int threads = h->bufs.n_envs * LEGS;
+    const dim3 grid((threads + BLOCK - 1) / BLOCK), qgrid((threads * 4 + BLOCK - 1) / BLOCK), rgrid((threads + 15) / 16);
+    const bool pre = (ph & LG_PHASE_PRE) != 0, hfb = h->hf != nullptr && h->opts.terrain_rows > 0;
+    const uint32_t rest = ph & PR;
+    // MDP-only launches of small biped batches run replicated (env_step_kernel<..., REPL>) while four times the waves still fit one per
+    // SIMD.  Measured at 4096 envs, us per step, plain / replicated: tron1_pf_ee 55.8 / 53.7, tron1_sf 52.3 / 50.7, tron1_pf 43.4 / 43.4;
+    // go2_cat (16 k leg-lanes already) 59.4 / 59.6: quadrupeds stay plain.  LG_MDP_REPLICAS=0/1 forces either.
+    const bool repl = sw[SW_MDP_REPLICAS] >= 0 ? sw[SW_MDP_REPLICAS] != 0 : (LEGS == 2 && (long long)threads * 4 <= 1024LL * BLOCK);
+    const auto mdp = [&](uint32_t m) {   // POST | RESET or POST leg per lane, behind a physics launch or on its own
+        if (m == PR) add(repl ? K::post_reset_repl : K::post_reset, repl ? rgrid : grid); else add(K::post, grid); };
+    // rs(P): the task's reward set is profile P's default one -> the instantiation with it as a constant (lg_quad.h RS; LG_REWARD_SET_CONST=0: off)
+    const auto rs = [&](int prof) { return (unsigned)h->hot.reward_mask == lg_default_reward_mask(prof) && sw[SW_REWARD_SET_CONST] != 0; };
+    // physics layout (lg_quad.h): one vector component per lane while the batch cannot fill the SIMDs with one leg per
+    // lane; the MDP phases then follow in a second launch on the same stream
+    // auto: component-per-lane while that needs at most two waves per SIMD (1024 SIMDs).  Measured go2, us per step,
+    // component vs leg layout: 4096 envs 34.7 / 56.6, 8192: 50.9 / 55.2, 12288: 69.2 / 55.5, 16384: 92 / 60
+    // the component-per-lane kernel is specialised for identity joint frames and hip-x / thigh-y / knee-y axes (lg_quad.h)
+    const int layout = h->opts.sim_layout ? h->opts.sim_layout : ((h->quad_ok && (long long)threads * 4 <= 2048LL * BLOCK) ? 2 : 1);
+    if (layout == 2 && pl.sim) {   // ALL, SIM, PRE | SIM, PRE | SIM | POST
+        if constexpr (JPL == 4) {   // four-joint legs: physics in component layout, then the MDP phases
+            add(K::sole_phys[pre], qgrid);
+            if (rest == PR) add(repl ? K::sole_post_reset_repl : K::sole_post_reset, repl ? rgrid : grid);
+            else if (rest == LG_PHASE_POST) add(K::sole_post, grid);
+        } else if (LEGS == 4 && pre && rest == LG_PHASE_POST) {
+            // the quadruped runs the MDP phases in the tail of the same launch (measured 39.5 vs 40.6 us for go2, 69.6 vs 72.5 for go2_ee)
+            add(K::quad_pre_sim_post, qgrid);
+        } else if (LEGS == 4 && pre && rest == PR) {
+            const int prof = task_profile(h, false);
+            add(prof == 0 ? K::quad_all : rs(prof) ? K::quad_prof_rs[prof - 1] : K::quad_prof[prof - 1], qgrid);
+        } else if (LEGS == 2 && pre && rest == PR && sw[SW_BIPED_FUSE] != 0) {
+            // biped (TRON1 point foot): the whole step in one launch too -- the leg-per-lane MDP body in the tail, four replicas of the
+            // wave's 16 leg-lanes (8 envs) -- unless the job-wide CaT flag has to pass between the phases (lg_step refuses that fused).
+            // LG_BIPED_FUSE=0: two launches.  PROF 6: workgroups of two waves per group of 8 envs (lg_quad.h DUO: both run the physics,
+            // then split the tail); LG_BIPED_TAIL=0: the leg-per-lane MDP body in the tail even where the component-layout tail applies
+            if (hfb && task_profile(h, false) == 6 && sw[SW_BIPED_TAIL] != 0) add(K::biped_all_ee, qgrid);
+            else add(hfb ? K::biped_all_hf : K::biped_all, qgrid);
+        } else {   // physics, then the MDP phases as a second launch (84.7 vs 90.6 us for tron1_pf_ee: 8 envs per wave there)
+            add(K::phys[pre][hfb], qgrid);
+            if (rest) mdp(rest);
+        }
+        return pl;
+    }
+    if (JPL == 3 && ph == (LG_PHASE_PRE | PR) && h->opts.sim_layout == 2 && h->bufs.rand_in) {
+        // golden replays through the benchmarked tails (tests/test_gpu_mdp.py, tail = "fused-profile"): the component-layout tail of the task's
+        // profile on injected read-backs and uniforms (lg_quad.h INJ); a task outside every profile takes the leg-per-lane launch below
+        const int prof = task_profile(h, true);
+        if (LEGS == 4 && prof != 0) { add(rs(prof) ? K::inj_rs[prof - 1] : K::inj[prof - 1], qgrid); return pl; }
+        if (LEGS == 2 && prof == 6) { add(K::inj_biped, qgrid); return pl; }
+    }
+    switch (ph) {
+    case LG_PHASE_ALL:
+        // LG_SPLIT_ALL=1: PRE | SIM and POST | RESET as two launches instead of the whole-step kernel, whose 480-512 registers per
+        // lane spill a few dwords to scratch (tools/register_table.py)
+        if (sw[SW_SPLIT_ALL] > 0) { add(K::pre_sim, grid); add(K::post_reset, grid); }
+        else if (LEGS == 4 && JPL == 3 && task_profile(h, false) == 1) add(K::all_flat, grid);   // large go2 batches: same FLAT constants
+        else add(K::all, grid);
+        break;
+    case LG_PHASE_SIM: add(K::sim, grid); break;
+    case LG_PHASE_PRE | LG_PHASE_SIM: add(K::pre_sim, grid); break;
+    case LG_PHASE_PRE | LG_PHASE_SIM | LG_PHASE_POST: add(K::pre_sim_post, grid); break;
+    case LG_PHASE_PRE | PR: add(K::pre_post_reset, grid); break;
+    case LG_PHASE_PRE | LG_PHASE_POST: add(K::pre_post, grid); break;
+    case LG_PHASE_RESET: add(K::reset, grid); break;
+    case PR: case LG_PHASE_POST: mdp(ph); break;
+    }
+    return pl;
+}
+
+// Runs a plan: the observation bookkeeping of a RESET step, then the launches.  A sampled step (lg_profile) has the begin timestamp on its
+// first launch and the end timestamp on its last (a two-launch sample includes the gap); hipExtLaunchKernelGGL attaches the events to the
+// dispatch packet itself, so the reading is the kernel's duration, comparable with rocprofv3's.
+static int execute(LgEngine *h, const LgPlan &pl, uint32_t ph, const float *actions, int64_t counter, hipStream_t st) {
     KParams p;
     p.M = h->d_model; p.O = h->d_opts; p.T = h->d_task; p.H = h->d_hot; p.LT = h->d_lane; p.hf = h->hf; p.B = h->bufs; p.actions = actions; p.counter = counter;
-    p.jrot_identity = 1;
-    {
-        const LgHot &hot = h->hot;   // refreshed by upload_hot
-        p.k.m_n_links = hot.m_n_links;
-        for (int i = 0; i < 4; i++) p.k.m_foot_link[i] = hot.m_foot_link[i];
-        p.k.obs_layout = hot.obs_layout; p.k.o_n_height_points = hot.o_n_height_points;
-        p.k.reward_mask = (unsigned)hot.reward_mask; p.k.clip_actions = hot.clip_actions;
-        p.k.cat_enable = h->task.cat_enable;
-        p.k.joint_axis[3] = -1;
-        for (int j = 0; j < JPL; j++) {
-            int code = -2;
-            for (int l = 0; l < LEGS; l++) {
-                const float *ax = h->model.axis[1 + JPL * l + j];
-                int c = -1;
-                for (int k = 0; k < 3; k++)
-                    if (fabsf(fabsf(ax[k]) - 1.f) < 1e-6f && fabsf(ax[(k + 1) % 3]) < 1e-6f && fabsf(ax[(k + 2) % 3]) < 1e-6f) c = k;
-                code = (code == -2 || code == c) ? c : -1;
-            }
-            p.k.joint_axis[j] = code;
-        }
-    }
-    for (int b = 1; b < h->model.n_bodies; b++)
-        for (int k = 0; k < 9; k++)
-            if (h->model.jrot[b][k] != ((k % 4 == 0) ? 1.f : 0.f)) p.jrot_identity = 0;
-    const int threads = h->bufs.n_envs * LEGS;
-    dim3 grid((threads + BLOCK - 1) / BLOCK), block(BLOCK);
-    p.obs_win = 0;
-    p.obs_set = h->obs_set;
+    p.jrot_identity = h->jrot_identity;
+    const LgHot &hot = h->hot;   // refreshed by upload_hot
+    p.k.m_n_links = hot.m_n_links;
+    for (int i = 0; i < 4; i++) { p.k.m_foot_link[i] = hot.m_foot_link[i]; p.k.joint_axis[i] = h->joint_axis[i]; }
+    p.k.obs_layout = hot.obs_layout; p.k.o_n_height_points = hot.o_n_height_points; p.k.cat_enable = h->task.cat_enable;
+    p.k.reward_mask = (unsigned)hot.reward_mask; p.k.clip_actions = hot.clip_actions;
+    p.obs_win = 0; p.obs_set = h->obs_set;
     if (ph & LG_PHASE_RESET) {
         const LgTaskCfg &t = h->task;
         const int sets = t.obs_sets > 1 ? t.obs_sets : 1;
@@ -323,147 +443,16 @@ template <int LEGS, int JPL = 3> static int launch(LgEngine *h, uint32_t ph, con
             p.obs_win = ++h->obs_win;
         }
     }
-    // physics layout (lg_quad.h): one vector component per lane while the batch cannot fill the SIMDs with one leg per
-    // lane; the MDP phases then follow in a second launch on the same stream
-    // auto: component-per-lane while that needs at most two waves per SIMD (1024 SIMDs).  Measured go2, us per step,
-    // component vs leg layout: 4096 envs 34.7 / 56.6, 8192: 50.9 / 55.2, 12288: 69.2 / 55.5, 16384: 92 / 60
-    // the component-per-lane kernel is specialised for identity joint frames and hip-x / thigh-y / knee-y axes (lg_quad.h)
-    // MDP-only launches of small biped batches run replicated (env_step_kernel<..., REPL>) while four times the waves still fit one per
-    // SIMD.  Measured at 4096 envs, us per step, plain / replicated: tron1_pf_ee 55.8 / 53.7, tron1_sf 52.3 / 50.7, tron1_pf 43.4 / 43.4;
-    // go2_cat (16 k leg-lanes already) 59.4 / 59.6: quadrupeds stay plain.  LG_MDP_REPLICAS=0/1 forces either (read per call: tests flip it).
-    const char *repl_s = getenv("LG_MDP_REPLICAS");
-    const bool repl = repl_s ? atoi(repl_s) != 0 : (LEGS == 2 && (long long)threads * 4 <= 1024LL * BLOCK);
-    const dim3 rgrid((threads + 15) / 16);
-    const bool quad_ok = p.jrot_identity && p.k.joint_axis[0] == 0 && p.k.joint_axis[1] == 1 && p.k.joint_axis[2] == 1 && (JPL == 3 || p.k.joint_axis[3] == 1);
-    if (h->opts.sim_layout == 2 && !quad_ok) return fail("lg_step: sim_layout 2 needs identity joint frames and x / y / y (/ y) joint axes");
-    const int layout = h->opts.sim_layout ? h->opts.sim_layout : ((quad_ok && (long long)threads * 4 <= 2048LL * BLOCK) ? 2 : 1);
-    constexpr unsigned PR = LG_PHASE_POST | LG_PHASE_RESET;
-    if constexpr (JPL == 4) if (layout == 2 && (ph & LG_PHASE_SIM)) {   // four-joint legs: physics in component layout, then the MDP phases
-        dim3 qgrid((threads * 4 + BLOCK - 1) / BLOCK);
-        const bool pre = (ph & LG_PHASE_PRE) != 0;
-        if (!pre && !actions) p.actions = nullptr;
-        const int pi = prof_begin(h, st);
-        const uint32_t rest = ph & PR;
-        if (pre && rest) LG_LAUNCH_FIRST(pi, (lg_launch_quad<LEGS, true, 0u, 0, 4>), qgrid);
-        else if (pre) LG_LAUNCH(pi, (lg_launch_quad<LEGS, true, 0u, 0, 4>), qgrid);
-        else if (rest) LG_LAUNCH_FIRST(pi, (lg_launch_quad<LEGS, false, 0u, 0, 4>), qgrid);
-        else LG_LAUNCH(pi, (lg_launch_quad<LEGS, false, 0u, 0, 4>), qgrid);
+    const int pi = pl.sim ? prof_begin(h, st) : -1;
+    h->last_kernel.clear();
+    for (int i = 0; i < pl.n; i++) {
+        if (i) h->last_kernel += " + ";
+        h->last_kernel += pl.l[i].k.name;
+        pl.l[i].k.fn(pl.l[i].grid, st, pi >= 0 && i == 0 ? h->prof_ev[2 * pi] : nullptr, pi >= 0 && i == pl.n - 1 ? h->prof_ev[2 * pi + 1] : nullptr, p);
         HIPCHK(hipGetLastError());
-        if (rest == PR && repl) LG_LAUNCH_LAST(pi, (lg_launch_env<LEGS, PR, 0, 4, true>), rgrid);
-        else if (rest == PR) LG_LAUNCH_LAST(pi, (lg_launch_env<LEGS, PR, 0, 4, false>), grid);
-        else if (rest == LG_PHASE_POST) LG_LAUNCH_LAST(pi, (lg_launch_env<LEGS, LG_PHASE_POST, 0, 4, false>), grid);
-        else if (rest) return fail("lg_step: unsupported phase combination");
-        HIPCHK(hipGetLastError());
-        return 0;
     }
-    if constexpr (JPL == 3) if (layout == 2 && (ph & LG_PHASE_SIM)) {
-        dim3 qgrid((threads * 4 + BLOCK - 1) / BLOCK);
-        const bool pre = (ph & LG_PHASE_PRE) != 0;
-        if (!pre && !actions) p.actions = nullptr;
-        const int pi = prof_begin(h, st);
-        const uint32_t rest = ph & PR;
-        // MDP phases: in the tail of the same launch for the quadruped (measured 39.5 vs 40.6 us for go2, 69.6 vs 72.5
-        // for go2_ee), as a second launch for the biped (84.7 vs 90.6 us for tron1_pf_ee: 8 envs per wave there)
-        bool fuse = false;
-        const bool hfb = h->hf != nullptr && h->opts.terrain_rows > 0;
-        if constexpr (LEGS == 4) {
-            fuse = pre && rest != 0;
-            // rs(P): the task's reward set is the default one of profile P -> the instantiation that has it as a constant (lg_quad.h RS)
-            const char *rse = getenv("LG_REWARD_SET_CONST");
-            auto rs = [&](int prof) { return (unsigned)h->hot.reward_mask == lg_default_reward_mask(prof) && !(rse && atoi(rse) == 0); };
-            if (fuse && rest == PR && flat_profile(h)) { if (rs(1)) LG_LAUNCH(pi, (lg_launch_quad_rs<4, 1, false>), qgrid); else LG_LAUNCH(pi, (lg_launch_quad<4, true, PR, 1, 3>), qgrid); }
-            else if (fuse && rest == PR && wtw_profile(h)) { if (rs(2)) LG_LAUNCH(pi, (lg_launch_quad_rs<4, 2, false>), qgrid); else LG_LAUNCH(pi, (lg_launch_quad<4, true, PR, 2, 3>), qgrid); }
-            else if (fuse && rest == PR && rough_profile(h) == 3) { if (rs(3)) LG_LAUNCH(pi, (lg_launch_quad_rs<4, 3, false>), qgrid); else LG_LAUNCH(pi, (lg_launch_quad<4, true, PR, 3, 3>), qgrid); }
-            else if (fuse && rest == PR && rough_profile(h) == 4) { if (rs(4)) LG_LAUNCH(pi, (lg_launch_quad_rs<4, 4, false>), qgrid); else LG_LAUNCH(pi, (lg_launch_quad<4, true, PR, 4, 3>), qgrid); }
-            else if (fuse && rest == PR) LG_LAUNCH(pi, (lg_launch_quad<4, true, PR, 0, 3>), qgrid);
-            else if (fuse && rest == LG_PHASE_POST) LG_LAUNCH(pi, (lg_launch_quad<4, true, LG_PHASE_POST, 0, 3>), qgrid);
-        } else {
-            // biped (TRON1 point foot): the whole step in one launch too -- the leg-per-lane MDP body in the tail, four replicas of the
-            // wave's 16 leg-lanes (8 envs) -- unless the job-wide CaT flag has to pass between the phases.  LG_BIPED_FUSE=0: two launches
-            const char *bf = getenv("LG_BIPED_FUSE");
-            fuse = pre && rest == PR && !h->task.cat_enable && (bf ? atoi(bf) != 0 : true);
-            const char *bt = getenv("LG_BIPED_TAIL");    // 0: the leg-per-lane MDP body in the tail even where the component-layout tail applies
-            // PROF 6: workgroups of two waves per group of 8 envs (lg_quad.h DUO: both run the physics, then split the tail)
-            if (fuse && hfb && biped_profile(h) && !(bt && atoi(bt) == 0)) LG_LAUNCH(pi, (lg_launch_quad<2, true, PR, 6, 3>), qgrid);
-            else if (fuse && hfb) LG_LAUNCH(pi, (lg_launch_quad<2, true, PR, 5, 3>), qgrid);
-            else if (fuse) LG_LAUNCH(pi, (lg_launch_quad<2, true, PR, 0, 3>), qgrid);
-        }
-        // physics-only launches: PROF 3 here only says "a heightfield is bound" (lg_quad.h HFC: no branch in front of the terrain loads)
-        if (fuse) {}
-        else if (pre && rest && hfb) LG_LAUNCH_FIRST(pi, (lg_launch_quad<LEGS, true, 0u, 3, 3>), qgrid);
-        else if (pre && rest) LG_LAUNCH_FIRST(pi, (lg_launch_quad<LEGS, true, 0u, 0, 3>), qgrid);
-        else if (pre && hfb) LG_LAUNCH(pi, (lg_launch_quad<LEGS, true, 0u, 3, 3>), qgrid);
-        else if (pre) LG_LAUNCH(pi, (lg_launch_quad<LEGS, true, 0u, 0, 3>), qgrid);
-        else if (rest && hfb) LG_LAUNCH_FIRST(pi, (lg_launch_quad<LEGS, false, 0u, 3, 3>), qgrid);
-        else if (rest) LG_LAUNCH_FIRST(pi, (lg_launch_quad<LEGS, false, 0u, 0, 3>), qgrid);
-        else if (hfb) LG_LAUNCH(pi, (lg_launch_quad<LEGS, false, 0u, 3, 3>), qgrid);
-        else LG_LAUNCH(pi, (lg_launch_quad<LEGS, false, 0u, 0, 3>), qgrid);
-        HIPCHK(hipGetLastError());
-        if (!fuse && rest) {
-            if (rest == PR && repl) LG_LAUNCH_LAST(pi, (lg_launch_env<LEGS, PR, 0, JPL, true>), rgrid);
-            else if (rest == PR) LG_LAUNCH_LAST(pi, (lg_launch_env<LEGS, PR, 0, JPL, false>), grid);
-            else if (rest == LG_PHASE_POST) LG_LAUNCH_LAST(pi, (lg_launch_env<LEGS, LG_PHASE_POST, 0, JPL, false>), grid);
-            else return fail("lg_step: unsupported phase combination");
-        }
-        HIPCHK(hipGetLastError());
-        return 0;
-    }
-    if constexpr (JPL == 3) if (ph == (LG_PHASE_PRE | PR) && h->opts.sim_layout == 2 && quad_ok && h->bufs.rand_in) {
-        // golden replays through the benchmarked tails (tests/test_gpu_mdp.py, tail = "fused-profile"): the component-layout tail of the
-        // task's profile on injected read-backs and uniforms (lg_quad.h INJ); a task outside every profile takes the leg-per-lane launch below
-        dim3 qgrid((threads * 4 + BLOCK - 1) / BLOCK);
-        bool done = true;
-        if constexpr (LEGS == 4) {
-            const int rp = rough_profile(h, true);
-            // the same choice of instantiation as the whole-step launch: constant reward set where the task's is the profile's default
-            const char *rse = getenv("LG_REWARD_SET_CONST");
-            auto rs = [&](int prof) { return (unsigned)h->hot.reward_mask == lg_default_reward_mask(prof) && !(rse && atoi(rse) == 0); };
-#define LG_INJ(L_, P_) do { if (rs(P_)) { h->last_kernel = "(lg_launch_quad_inj<" #L_ ", " #P_ ">, reward set constant)"; lg_launch_quad_rs<L_, P_, true>(qgrid, st, nullptr, nullptr, p); } \
-                            else { h->last_kernel = "(lg_launch_quad_inj<" #L_ ", " #P_ ">)"; lg_launch_quad_inj<L_, P_>(qgrid, st, p); } } while (0)
-            if (flat_profile(h, true)) LG_INJ(4, 1);
-            else if (wtw_profile(h, true)) LG_INJ(4, 2);
-            else if (rp == 3) LG_INJ(4, 3);
-            else if (rp == 4) LG_INJ(4, 4);
-            else done = false;
-#undef LG_INJ
-        } else {
-            if (biped_profile(h, true)) { h->last_kernel = "(lg_launch_quad_inj<2, 6>)"; lg_launch_quad_inj<2, 6>(qgrid, st, p); }
-            else done = false;
-        }
-        if (done) { HIPCHK(hipGetLastError()); return 0; }
-    }
-    const int pi = (ph & LG_PHASE_SIM) ? prof_begin(h, st) : -1;
-    switch (ph) {
-    case LG_PHASE_ALL: {
-        // LG_SPLIT_ALL=1 (developer switch): PRE | SIM and POST | RESET as two launches instead of the whole-step kernel, whose 480-512
-        // registers per lane spill a few dwords to scratch (tools/register_table.py)
-        const char *sp = getenv("LG_SPLIT_ALL");
-        if (sp && atoi(sp) != 0) {
-            LG_LAUNCH_FIRST(pi, (lg_launch_env<LEGS, LG_PHASE_PRE | LG_PHASE_SIM, 0, JPL, false>), grid);
-            LG_LAUNCH_LAST(pi, (lg_launch_env<LEGS, PR, 0, JPL, false>), grid);
-            break;
-        }
-        if constexpr (JPL == 3 && LEGS == 4) { if (flat_profile(h)) { LG_LAUNCH(pi, (lg_launch_env<4, LG_PHASE_ALL, 1, 3, false>), grid); break; } }   // large go2 batches: same FLAT constants
-        LG_LAUNCH(pi, (lg_launch_env<LEGS, LG_PHASE_ALL, 0, JPL, false>), grid);
-        break;
-    }
-    case LG_PHASE_SIM: LG_LAUNCH(pi, (lg_launch_env<LEGS, LG_PHASE_SIM, 0, JPL, false>), grid); break;
-    case LG_PHASE_PRE | LG_PHASE_POST | LG_PHASE_RESET: LG_LAUNCH_PLAIN((lg_launch_env<LEGS, LG_PHASE_PRE | PR, 0, JPL, false>), grid); break;
-    case LG_PHASE_PRE | LG_PHASE_SIM | LG_PHASE_POST: LG_LAUNCH(pi, (lg_launch_env<LEGS, LG_PHASE_PRE | LG_PHASE_SIM | LG_PHASE_POST, 0, JPL, false>), grid); break;
-    case LG_PHASE_PRE | LG_PHASE_SIM: LG_LAUNCH(pi, (lg_launch_env<LEGS, LG_PHASE_PRE | LG_PHASE_SIM, 0, JPL, false>), grid); break;
-    case LG_PHASE_RESET: LG_LAUNCH_PLAIN((lg_launch_env<LEGS, LG_PHASE_RESET, 0, JPL, false>), grid); break;
-    case LG_PHASE_PRE | LG_PHASE_POST: LG_LAUNCH_PLAIN((lg_launch_env<LEGS, LG_PHASE_PRE | LG_PHASE_POST, 0, JPL, false>), grid); break;
-    case LG_PHASE_POST | LG_PHASE_RESET:
-        if (repl) LG_LAUNCH_PLAIN((lg_launch_env<LEGS, PR, 0, JPL, true>), rgrid);
-        else LG_LAUNCH_PLAIN((lg_launch_env<LEGS, PR, 0, JPL, false>), grid);
-        break;
-    case LG_PHASE_POST: LG_LAUNCH_PLAIN((lg_launch_env<LEGS, LG_PHASE_POST, 0, JPL, false>), grid); break;
-    default: return fail("lg_step: unsupported phase combination (ALL, SIM, PRE|SIM, PRE|POST|RESET, PRE|SIM|POST, PRE|POST, POST|RESET, POST, RESET)");
-    }
-    HIPCHK(hipGetLastError());
     return 0;
 }
-
 
 static int check_mdp_bufs(const LgEngine *h, uint32_t ph) {
     const LgBuffers &b = h->bufs;
@@ -481,14 +470,23 @@ static int check_mdp_bufs(const LgEngine *h, uint32_t ph) {
 }
 
 extern "C" int lg_step(LgHandle h, uint32_t phases, const float *actions, int64_t counter, void *stream) {
+    // everything is checked before the first side effect: a refused call leaves the engine as it was
     if (!h) return fail("lg_step: null handle");
     if (!h->bound) return fail("lg_step: lg_bind has not been called");
-    if ((phases & (LG_PHASE_PRE | LG_PHASE_SIM)) && !actions && (phases & LG_PHASE_PRE || !(phases & LG_PHASE_POST)))
-        return fail("lg_step: actions pointer is NULL");
+    if ((phases & (LG_PHASE_PRE | LG_PHASE_SIM)) && !actions) return fail("lg_step: actions pointer is NULL");
     if (h->opts.terrain_rows > 0 && !h->hf) return fail("lg_step: heightfield options set but lg_set_terrain was not called");
     if (check_mdp_bufs(h, phases)) return 1;
     if (h->task.cat_enable && (phases & LG_PHASE_SIM) && (phases & LG_PHASE_POST))
         return fail("lg_step: with cat_enable the physics and the MDP phases must be separate launches (job-wide constraint flag, LG_CR_ANY_FAST)");
+    if (h->opts.sim_layout == 2 && !h->quad_ok) return fail("lg_step: sim_layout 2 needs identity joint frames and x / y / y (/ y) joint axes");
+    constexpr uint32_t PRE = LG_PHASE_PRE, SIM = LG_PHASE_SIM, POST = LG_PHASE_POST, RESET = LG_PHASE_RESET;
+    switch (phases) {
+    case LG_PHASE_ALL: case SIM: case PRE | SIM: case PRE | SIM | POST: case PRE | POST | RESET: case PRE | POST: case POST | RESET: case POST: case RESET: break;
+    default: return fail("lg_step: unsupported phase combination (ALL, SIM, PRE|SIM, PRE|POST|RESET, PRE|SIM|POST, PRE|POST, POST|RESET, POST, RESET)");
+    }
+    int sw[SW_COUNT]; read_switches(sw);
+    const LgPlan pl = h->model.n_bodies == 1 + 4 * h->model.n_legs ? plan<2, 4>(h, phases, sw)    // validate_model: two legs
+                      : h->model.n_legs == 4                        ? plan<4, 3>(h, phases, sw) : plan<2, 3>(h, phases, sw);
     hipStream_t st = (hipStream_t)stream;
     // Bounded run-ahead.  A host that enqueues thousands of launches ahead of the device (a bench loop without a
     // policy in between) drives the runtime into a slow submission path: measured 90 us per step instead of 42 with
@@ -500,8 +498,7 @@ extern "C" int lg_step(LgHandle h, uint32_t phases, const float *actions, int64_
         else HIPCHK(hipEventCreateWithFlags(&h->ra_ev[slot], hipEventDisableTiming));
         HIPCHK(hipEventRecord(h->ra_ev[slot], st));
     }
-    if (h->model.n_bodies == 1 + 4 * h->model.n_legs) return launch<2, 4>(h, phases, actions, counter, st);   // validate_model: two legs
-    return h->model.n_legs == 4 ? launch<4>(h, phases, actions, counter, st) : launch<2>(h, phases, actions, counter, st);
+    return execute(h, pl, phases, actions, counter, st);
 }
 
 __global__ __launch_bounds__(256) void stream_copy_kernel(const float4 *__restrict__ src, float4 *__restrict__ dst, long long n4) {

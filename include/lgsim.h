@@ -347,7 +347,9 @@ int lg_set_task(LgHandle h, const LgTaskCfg *task);
 int lg_set_terrain(LgHandle h, const int16_t *height_samples_dev, int32_t rows, int32_t cols);
 /* Record the caller-owned device buffers (validated: required pointers non-NULL). */
 int lg_bind(LgHandle h, const LgBuffers *bufs);
-/* Enqueue one launch covering `phases` of a control step on `stream`.
+/* Enqueue the launch(es) covering `phases` of a control step on `stream`.  `phases` is one of ALL, SIM, PRE|SIM, PRE|SIM|POST,
+ * PRE|POST|RESET, PRE|POST, POST|RESET, POST, RESET, for every robot and physics layout.  A refused call launches nothing and
+ * leaves the observation window and copy (lg_obs_window, lg_obs_set) and lg_last_kernel as they were.
  * actions: (N,A) device pointer (required with LG_PHASE_PRE or LG_PHASE_SIM);
  * common_step_counter: value AFTER this step's increment (legged_robot.py:61). */
 int lg_step(LgHandle h, uint32_t phases, const float *actions, int64_t common_step_counter, void *stream);

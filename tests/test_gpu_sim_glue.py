@@ -271,3 +271,47 @@ def test_hip_simulator_public_methods_match_the_reference(task, monkeypatch):
     # ---- the rest of the surface exists and is callable (simulator.py:28, 67, 90, 96) ----
     assert sim.post_physics_step() is None and sim.update_sensors() is None
     assert sim.draw_debug_vis() is None and sim.set_viewer_camera([0, 0, 1], [0, 0, 0]) is None
+
+
+PHASE_SETS = (15, 2, 3, 7, 13, 5, 12, 4, 8)   # include/lgsim.h lg_step: ALL, SIM, PRE|SIM, PRE|SIM|POST, PRE|POST|RESET, PRE|POST, POST|RESET, POST, RESET
+
+
+@pytest.mark.parametrize("layout", LAYOUTS)
+@pytest.mark.parametrize("task", ["go2", "tron1_pf", "tron1_sf"])
+def test_lg_step_accepts_the_documented_phase_sets_and_refuses_the_rest_untouched(task, layout):
+    """All fifteen non-empty phase masks, on a quadruped, a biped and the four-joint biped in both physics layouts: the nine documented
+    sets run; the other six are refused before anything happens -- every engine buffer, the observation window and copy and
+    lg_last_kernel as they were.  (A component-layout quadruped once accepted PRE|SIM|RESET and launched nothing, a biped refused
+    SIM|RESET after its physics launch, a refused RESET had already flipped the observation copy, and SIM|POST ran in one layout only.)"""
+    import ctypes as C
+    import torch
+    from hcr_genesis_lr_cl_amd.envs import TASKS as REG
+    cls, cfg_cls = REG[task]
+    cfg = cfg_cls()
+    cfg.env.num_envs = n = 64
+    cfg.hip.sim_layout = layout
+    env = cls(cfg, None, "cuda:0", True)
+    env.reset()
+    eng = env._engine
+    act = torch.zeros(n, env.num_actions, device="cuda:0")
+    stream = torch.cuda.current_stream().cuda_stream
+
+    def snapshot():
+        torch.cuda.synchronize()
+        w, s_ = C.c_int32(), C.c_int32()
+        assert eng.lib.lg_obs_window(eng.handle, C.byref(w)) == 0 and eng.lib.lg_obs_set(eng.handle, C.byref(s_)) == 0
+        return w.value, s_.value, eng.last_kernel(), {k: eng.buf.raw(k).cpu().numpy().tobytes() for k in eng.buf.keys()}
+
+    for ph in range(1, 16):
+        before = snapshot()
+        rc = eng.lib.lg_step(eng.handle, ph, act.data_ptr(), 100 + ph, stream)
+        after = snapshot()
+        if ph in PHASE_SETS:
+            assert rc == 0, (ph, eng.lib.lg_last_error().decode())
+            assert after[2], ph
+        else:
+            assert rc != 0, f"phase mask {ph} was accepted (launched {after[2]!r})"
+            assert "unsupported phase combination" in eng.lib.lg_last_error().decode(), ph
+            assert after[:3] == before[:3], ph
+            changed = [k for k in before[3] if before[3][k] != after[3][k]]
+            assert not changed, (ph, changed)
