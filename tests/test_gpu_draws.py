@@ -137,6 +137,7 @@ PRODUCT = [
 GATE_LAUNCHES = ("lg_launch_quad<4, true, LG_PHASE_POST, 0, 3>", "lg_launch_env<LEGS, LG_PHASE_RESET, 0, JPL, false>")
 PHYS_TOL = dict(base_pos=2e-5, base_quat=2e-5, base_lin_vel_w=2e-3, base_ang_vel_w=1e-2, dof_pos=2e-4, dof_vel=3e-2, torques=5e-3,
                 feet_pos=1e-4, feet_vel=2e-2)      # DESIGN.md section 2 (tests/test_gpu_physics.py TOL)
+MDP_ORACLE_LAYOUTS = (mo.abi.OBS_GO2, mo.abi.OBS_GO2_WTW, mo.abi.OBS_GO2_EE, mo.abi.OBS_TRON1_EE)   # go2, go2_wtw, go2_ee, tron1_pf_ee
 MDP_SIM_KEYS = ("base_pos", "base_quat", "base_lin_vel_w", "base_ang_vel_w", "dof_pos", "dof_vel", "torques", "link_contact_forces",
                 "feet_pos", "feet_vel", "last_dof_vel", "last_feet_vel")
 
@@ -172,7 +173,9 @@ def test_product_launch_draws_follow_the_map(case, monkeypatch):
         equals what the launch wrote, terrain levels sent from the top row and the new origins included;
       * envs that do not reset: the physics equals oracle.sim_step(.., "f64") on the same pre-step state and actions (DESIGN.md
         section 2 contract, at most 0.5 % of envs off on a heightfield), push velocities, callback commands and go2_wtw's behaviour
-        targets follow the map, and for go2 every MDP output equals MdpOracle.step fed the launch's read-backs and R = draw_map;
+        targets follow the map, and for go2, go2_wtw, go2_ee and tron1_pf_ee (the layouts bench.py times) every MDP output equals
+        MdpOracle.step seeded from the launch's pre-step state and fed its read-backs and R = draw_map (env 0 of the gait tasks
+        left out, see _check_mdp_oracle);
       * all envs: the observation noise follows the map."""
     import torch
     from hcr_genesis_lr_cl_amd import abi
@@ -350,9 +353,11 @@ def test_product_launch_draws_follow_the_map(case, monkeypatch):
                 to = post["terrain_origins"]
                 assert to.ndim == 3, to.shape
                 _close(post["env_origins"][ids], to[lv[ids], post["terrain_types"][ids]], "terrain origins")
-        # ---- go2: every MDP output of the envs that did not reset against MdpOracle.step on the launch's own read-backs
-        if task.obs_layout == abi.OBS_GO2 and not is_gate:
-            seen["mdp"] += _check_mdp_oracle(model, cfg, task, N, pre, post, push, np.clip(act.cpu().numpy(), -ca, ca), U, c, keep)
+        # ---- go2 and the other benchmarked layouts: every MDP output of the envs that did not reset against MdpOracle.step on the
+        #      launch's own read-backs
+        if task.obs_layout in MDP_ORACLE_LAYOUTS and not is_gate:
+            seen["mdp"] += _check_mdp_oracle(model, cfg, task, N, pre, post, push, np.clip(act.cpu().numpy(), -ca, ca), U, c, keep,
+                                             env.simulator._terrain if hf is not None else None)
         # ---- observation noise: the newest actor frame minus the same frame formed noise-free from the launch's own state
         _check_obs_noise(env, task, model, cfg, post, U, nv, q0, b)
     print("product", _pid(case), seen)
@@ -362,32 +367,75 @@ def test_product_launch_draws_follow_the_map(case, monkeypatch):
     assert seen["sit"] == ({True, False} if sit else set()), seen
     assert seen["behavior"] > 20 if task.gait_mode == 1 else True, seen
     assert seen["top"] > 10 if task.terrain_curriculum else True, seen
-    assert seen["mdp"] > 2 * N - 1000 if task.obs_layout == abi.OBS_GO2 and not gate else True, seen
+    assert seen["mdp"] > 2 * N - 1000 if task.obs_layout in MDP_ORACLE_LAYOUTS and not gate else True, seen
 
 
-def _check_mdp_oracle(model, cfg, task, N, pre, post, push, actions, U, c, keep):
+def _check_mdp_oracle(model, cfg, task, N, pre, post, push, actions, U, c, keep, terrain=None):
     """MdpOracle.step from the launch's pre-step MDP state and post-step physics read-backs (the push taken out of the velocity: the
-    oracle applies it), R = draw_map; compared on the envs that did not reset, tolerances of tests/test_gpu_mdp.py."""
+    oracle applies it), R = draw_map; compared on the envs that did not reset, tolerances of tests/test_gpu_mdp.py.  The gait tasks
+    leave out env 0: the oracle reproduces the reference's index-flatten bug on its gait clock and indicator (go2_wtw.py:33-34,
+    455-462), which the kernel does not (envs/go2_wtw.py docstring)."""
+    from hcr_genesis_lr_cl_amd import abi
+    L = task.obs_layout
     orc = mo.MdpOracle(model, cfg, task, N, pre["env_origins"].copy())
     for k in ("actions", "last_actions", "llast_actions", "commands", "feet_air_time", "friction_values", "added_base_mass",
-              "base_com_bias", "kp_scale", "kd_scale"):
-        getattr(orc, k)[:] = pre[k].reshape(getattr(orc, k).shape)
+              "base_com_bias", "rand_push_vels", "kp_scale", "kd_scale", "joint_armature", "joint_friction", "joint_damping"):
+        if k in pre:
+            getattr(orc, k)[:] = pre[k].reshape(getattr(orc, k).shape)
     orc.last_contacts[:] = pre["last_contacts"] != 0
     orc.episode_length_buf[:] = pre["episode_length_buf"]
     orc.fail_buf[:] = pre["fail_buf"]
     orc.episode_sums[:] = pre["episode_sums"]
     orc.command_ranges[:] = pre["command_ranges"][:8]
+    ts = pre["task_state"] if task.gait_mode else None
+    if task.gait_mode == 1:           # layout LG_TASK_STATE_WTW, behaviour ranges from command_ranges[8:17]
+        orc.gait_time[:], orc.phi[:], orc.gait_period[:] = ts[:, 0:1], ts[:, 1:2], ts[:, 2:3]
+        orc.base_height_target[:], orc.foot_clearance_target[:], orc.pitch_target[:] = ts[:, 3:4], ts[:, 4:5], ts[:, 5:6]
+        orc.theta[:], orc.clock_input[:], orc.exp_C_frc[:] = ts[:, 6:10], ts[:, 10:18], ts[:, 18:22]
+        br = pre["command_ranges"][8:17]
+        orc.gait_period_range, orc.base_height_target_range = list(br[0:2]), list(br[2:4])
+        orc.foot_clearance_target_range, orc.pitch_target_range, orc.num_gaits = list(br[4:6]), list(br[6:8]), int(br[8])
+    if task.gait_mode == 2:           # layout LG_TASK_STATE_BIPED
+        orc.gait_time[:], orc.phi[:] = ts[:, 0:1], ts[:, 1:2]
+        orc.theta[:], orc.clock_input[:], orc.exp_C_frc[:] = ts[:, 4:6], ts[:, 6:10], ts[:, 10:12]
+    if terrain is not None:
+        orc.terrain_levels[:], orc.terrain_types[:] = pre["terrain_levels"], pre["terrain_types"]
+        orc.terrain_origins = terrain.env_origins.astype(np.float32)
     sim = {k: post[k].reshape(N, -1).copy() for k in MDP_SIM_KEYS}
     sim["base_lin_vel_w"] -= push
+    if "measured_heights" in post and post["measured_heights"].size:       # the SIM phase's terrain read-backs of this step
+        sim["measured_heights"] = post["measured_heights"].reshape(N, -1).copy()
+        sim["height_around_feet"] = post["height_around_feet"].reshape(N, -1).copy()
+        sim["normals"] = post["normal_vector_around_feet"].reshape(N, -1).copy()
     orc.step(sim, actions, U, c)
-    k = keep
+    k = keep.copy()
+    if task.gait_mode:
+        k[0] = False
     assert not orc.reset_buf[k].any()
+    np.testing.assert_array_equal(post["reset_buf"][k].astype(bool), orc.reset_buf[k])
     np.testing.assert_array_equal(post["episode_length_buf"][k], orc.episode_length_buf[k])
     np.testing.assert_array_equal(post["fail_buf"][k], orc.fail_buf[k])
     np.testing.assert_array_equal(post["last_contacts"][k].astype(bool), orc.last_contacts[k])
-    for name, got, ref, tol in (("obs_buf", post["obs_buf"].reshape(N, -1), orc.obs_buf, 5e-5), ("rew_buf", post["rew_buf"], orc.rew_buf, 1e-5),
-                                ("commands", post["commands"], orc.commands, 5e-5), ("feet_air_time", post["feet_air_time"], orc.feet_air_time, 1e-5),
-                                ("actions", post["actions"], orc.actions, 1e-5)):
+    FR = int(task.obs_frame)
+    # the newest actor frame (observation noise from R = draw_map) and critic frame; the yaw command goes through atan2f: 5e-5 on
+    # the frames and the commands, 1e-5 elsewhere
+    checks = [("obs_buf", post["obs_buf"].reshape(N, -1)[:, -FR:], orc.obs_buf[:, -FR:], 5e-5), ("rew_buf", post["rew_buf"], orc.rew_buf, 1e-5),
+              ("commands", post["commands"], orc.commands, 5e-5), ("feet_air_time", post["feet_air_time"], orc.feet_air_time, 1e-5),
+              ("actions", post["actions"], orc.actions, 1e-5)]
+    if L != abi.OBS_GO2:
+        PF = int(task.priv_frame)
+        checks.append(("priv_obs_buf", post["priv_obs_buf"].reshape(N, -1)[:, -PF:], orc.priv_obs_buf[:, -PF:], 5e-5))
+    if L in (abi.OBS_GO2_EE, abi.OBS_TRON1_EE):
+        checks.append(("labels_buf", post["labels_buf"].reshape(N, -1), orc.labels_buf, 1e-5))
+    if task.gait_mode == 1:
+        checks.append(("task_state", post["task_state"], np.concatenate([orc.gait_time, orc.phi, orc.gait_period, orc.base_height_target,
+                                                                         orc.foot_clearance_target, orc.pitch_target, orc.theta,
+                                                                         orc.clock_input, orc.exp_C_frc], 1), 1e-5))
+    if task.gait_mode == 2:
+        got = post["task_state"]
+        checks.append(("task_state", np.concatenate([got[:, 0:2], got[:, 4:12]], 1),
+                       np.concatenate([orc.gait_time, orc.phi, orc.theta, orc.clock_input, orc.exp_C_frc], 1), 1e-5))
+    for name, got, ref, tol in checks:
         np.testing.assert_allclose(got[k], ref[k], rtol=1e-5, atol=tol, err_msg=name)
     np.testing.assert_allclose(post["episode_sums"][:, k], orc.episode_sums[:, k], rtol=1e-5, atol=1e-5, err_msg="episode_sums")
     return int(k.sum())

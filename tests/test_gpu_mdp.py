@@ -229,21 +229,38 @@ class WtwKernelStepper:
 def test_kernel_reproduces_reference_go2_wtw_golden_vectors(tail):
     """Env 0 is excluded: the reference couples it to the whole batch through two index-flatten bugs
     (go2_wtw.py:33-34, 455-462) which the kernel does not reproduce (envs/go2_wtw.py docstring)."""
-    from tests.test_mdp_oracle import GOLD_WTW, WTW_EXACT, WTW_FLOAT
+    from tests.test_mdp_oracle import GOLD_WTW
+    from tests.test_mdp_oracle import check_wtw
+    replay(WtwKernelStepper, lambda t, fx, out: check_wtw(t, fx, out, rtol=1e-5, atol=1e-5, skip_env0=True), GOLD_WTW)
 
-    def check(t, fx, out):
-        for k in WTW_EXACT:
-            np.testing.assert_array_equal(np.asarray(out[k]).astype(np.int64)[1:], fx[k][t].astype(np.int64)[1:], err_msg=f"{k} @ {t}")
-        for k in WTW_FLOAT:
-            got, ref = np.asarray(out[k]), fx[k][t]
-            if k == "episode_sums":
-                got, ref = got[:, 1:], ref[:, 1:]
-            elif k == "act_hist":
-                got, ref = got[:, 1:], ref[:, 1:]
-            else:
-                got, ref = got[1:], ref[1:]
-            np.testing.assert_allclose(got, ref, rtol=1e-5, atol=1e-5, err_msg=f"{k} @ step {t}")
-    replay(WtwKernelStepper, check, GOLD_WTW)
+
+# ------------------------------- every task against the oracle on synthetic batches ---------------------------------------
+def synth_kernel_stepper(task):
+    if task in ("go2_ts", "go2_cts", "go2_dreamwaq", "go2_cat"):
+        return type("KStepper_" + task, (EEKernelStepper,), {"head": task})
+    return {"go2": KernelStepper, "go2_wtw": WtwKernelStepper, "go2_ee": EEKernelStepper, "tron1_pf_ee": Tron1KernelStepper,
+            "tron1_pf": PFKernelStepper, "tron1_sf": SFKernelStepper}[task]
+
+
+def _synth_params():
+    """(task, tail, history mode): fused-profile only where the task has an INJ profile tail and only with the sliding window
+    (the component-layout tails hard-wire it); go2_cat, tron1_pf and tron1_sf are split only."""
+    from tests.synthetic_mdp import TASKS, INJ_TAIL
+    modes = (("64", "history-window"), ("1", "history-window-min-slack"), ("0", "history-shift"))
+    return [pytest.param(task, tail, m, id=f"{task}-{tail}-{mid}") for task in TASKS for tail in ("split", "fused-profile")
+            for m, mid in modes if tail == "split" or (task in INJ_TAIL and m != "0")]
+
+
+@pytest.mark.parametrize("N", [4096, 4093])
+@pytest.mark.parametrize("task,tail,history_mode", _synth_params(), indirect=["tail", "history_mode"])
+def test_kernel_matches_oracle_on_synthetic_batches(task, N, tail):
+    """Every task's MDP instantiations against the oracle on a synthetic batch (tests/synthetic_mdp.py): 4096 envs, and 4093 for a
+    partly filled last wave / workgroup / PROF 6 group of 8 envs; long enough for two compactions of the smallest-slack history
+    window; inputs that cross every decision of the MDP phases with a margin.  Expected values are the oracle's, recorded once
+    per batch; tolerances of sm.synth_check (the golden replays' kernel tolerances)."""
+    from tests import synthetic_mdp as sm
+    fx = sm.recorded(task, N)
+    sm.replay(task, fx, synth_kernel_stepper(task), sm.synth_check(task))
 
 
 def test_wtw_env_runs_and_histories_shift():
