@@ -281,9 +281,9 @@ static int task_profile(const LgEngine *h, bool inj) {
 
 // Developer switches: 1 / 0 when the environment variable is set to a non-zero number / 0, -1 when unset.  Read on every lg_step (the
 // tests flip them between steps), in one pass over the environment: as cheap as one getenv.
-enum { SW_MDP_REPLICAS, SW_REWARD_SET_CONST, SW_BIPED_FUSE, SW_BIPED_TAIL, SW_SPLIT_ALL, SW_COUNT };
+enum { SW_MDP_REPLICAS, SW_REWARD_SET_CONST, SW_BIPED_FUSE, SW_BIPED_TAIL, SW_COUNT };
 static void read_switches(int sw[SW_COUNT]) {
-    static const char *const name[SW_COUNT] = {"LG_MDP_REPLICAS=", "LG_REWARD_SET_CONST=", "LG_BIPED_FUSE=", "LG_BIPED_TAIL=", "LG_SPLIT_ALL="};
+    static const char *const name[SW_COUNT] = {"LG_MDP_REPLICAS=", "LG_REWARD_SET_CONST=", "LG_BIPED_FUSE=", "LG_BIPED_TAIL="};
     for (int i = 0; i < SW_COUNT; i++) sw[i] = -1;
     for (char **e = environ; *e; e++) {
         if (strncmp(*e, "LG_", 3)) continue;
@@ -393,10 +393,7 @@ template <int LEGS, int JPL> static LgPlan plan(const LgEngine *h, uint32_t ph, 
     }
     switch (ph) {
     case LG_PHASE_ALL:
-        // LG_SPLIT_ALL=1: PRE | SIM and POST | RESET as two launches instead of the whole-step kernel, whose 480-512 registers per
-        // lane spill a few dwords to scratch (tools/register_table.py)
-        if (sw[SW_SPLIT_ALL] > 0) { add(K::pre_sim, grid); add(K::post_reset, grid); }
-        else if (LEGS == 4 && JPL == 3 && task_profile(h, false) == 1) add(K::all_flat, grid);   // large go2 batches: same FLAT constants
+        if (LEGS == 4 && JPL == 3 && task_profile(h, false) == 1) add(K::all_flat, grid);   // large go2 batches: same FLAT constants
         else add(K::all, grid);
         break;
     case LG_PHASE_SIM: add(K::sim, grid); break;

@@ -171,9 +171,6 @@ struct RandSrc {
     const float *in;  // injected row or nullptr
     unsigned k0, k1, e_lo, e_hi, step;
     LG_DEV float draw(int slot) const {
-#ifdef LG_DBG_NO_DRAWS
-        return 0.5f;
-#endif
         if (in) return in[slot];
         U4 c = {e_lo, e_hi, step, (unsigned)(slot >> 2)};
         U4 r = philox4x32_10(c, k0, k1);
@@ -183,18 +180,12 @@ struct RandSrc {
     // three consecutive slots from ONE Philox call (integer multiplies are quarter-rate: a call is ~800 cycles);
     // injected mode still reads the slots one by one
     LG_DEV void draw3(int slot, float &a, float &b, float &c) const {
-#ifdef LG_DBG_NO_DRAWS
-        a = b = c = 0.5f; return;
-#endif
         if (in) { a = in[slot]; b = in[slot + 1]; c = in[slot + 2]; return; }
         U4 ctr = {e_lo, e_hi, step, 0x40000000u + (unsigned)slot};
         U4 r = philox4x32_10(ctr, k0, k1);
         a = u01(r.x); b = u01(r.y); c = u01(r.z);
     }
     LG_DEV void draw4(int slot, float &a, float &b, float &c, float &d) const {   // four-joint legs: the block's fourth output too
-#ifdef LG_DBG_NO_DRAWS
-        a = b = c = d = 0.5f; return;
-#endif
         if (in) { a = in[slot]; b = in[slot + 1]; c = in[slot + 2]; d = in[slot + 3]; return; }
         U4 ctr = {e_lo, e_hi, step, 0x40000000u + (unsigned)slot};
         U4 r = philox4x32_10(ctr, k0, k1);
@@ -1300,9 +1291,6 @@ LG_DEV void env_step_body(const KParams &p, uint4 *sMraw, int *sHot, float *sStF
         }
         if (WTW && hc_behavior_resample_steps > 0 && ep_len % hc_behavior_resample_steps == 0)   // go2_wtw.py:258-263
             resample_behavior(HOT(slots.task_cb));
-#ifdef LG_DBG_RET_CALLBACK
-        if (p.counter >= 0) { if (lead) B.rew_buf[e] = cmd2 + (float)ep_len; return; }
-#endif
         STAMP(6);
         // ---- check_termination (legged_robot.py:78-92) ----
         const int l0 = foot_link - 3;
@@ -1318,9 +1306,6 @@ LG_DEV void env_step_body(const KParams &p, uint4 *sMraw, int *sHot, float *sStF
         time_out = (float)ep_len > hc_max_episode_length;
         reset = ((float)fail_buf > hc_fail_threshold) || time_out;
 
-#ifdef LG_DBG_RET_TERM
-        if (p.counter >= 0) { if (lead) B.rew_buf[e] = cmd2 + (float)fail_buf + (reset ? 1.f : 0.f); return; }
-#endif
         // ---- constraints as terminations (go2_cat.py:143-205): nine 0/1 violation flags; p = 1 for a violated hard constraint,
         //      soft_p for a violated soft / style one (constraint_manager.py:25-74 with binary inputs), per-episode violation counts
         float cat_keep = 1.f;     // (1 - p), applied to the reward before the positive clip (go2_cat.py:219-223)
@@ -1547,9 +1532,6 @@ LG_DEV void env_step_body(const KParams &p, uint4 *sMraw, int *sHot, float *sStF
             const float dp = eul.y - pitch_tgt;
             add(LG_R_TRACKING_ORIENTATION, __expf(-(eul.x * eul.x + dp * dp) / HOT(euler_sigma)));
         }
-#ifdef LG_DBG_RET_REW
-        if (p.counter >= 0) { if (lead) B.rew_buf[e] = total + es[0] + es[5] + es[28]; return; }
-#endif
         STAMP(7);
         if (hc_only_positive_rewards) total = fmaxf(total * cat_keep, 0.f);        // :161-162; go2_cat.py:219-223 scales by (1 - p) first
         if (RON(LG_R_TERMINATION)) add(LG_R_TERMINATION, (reset && !time_out) ? 1.f : 0.f);  // :163-168

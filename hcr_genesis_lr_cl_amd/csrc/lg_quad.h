@@ -96,8 +96,7 @@ LG_DEV float dot3(float a, float b) { return sum3(a * b); }
 // LLVM folds a DPP mov into v_mul / v_add but not into v_fmac, leaving one v_mov_b32_dpp per multiply-add (~20 % of the physics
 // loop's issue slots); these helpers spell the sequences out.  One `s_nop 1` in front of a group covers the DPP read-after-VALU-
 // write hazard of every source in it (2 wait states; the hazard recogniser does not look inside inline asm); inside a group
-// the DPP sources are never written.  LG_NO_DPP_ASM selects the plain C++ forms (same arithmetic, same order).
-#ifndef LG_NO_DPP_ASM
+// the DPP sources are never written.  Each helper's comment gives what it computes.
 // The marker lets hcr_genesis_lr_cl_amd/dpp_hazard_pass.py (run by build.py on the compiler's assembly) drop the nop wherever the
 // sources of the block turn out to be old enough in the instruction stream the compiler actually produced, and keep or shorten it
 // where they are not -- an `s_nop 1` is two issue slots of a lone wave (~8.6 cycles), and most blocks do not need it.  Compiled without
@@ -132,7 +131,7 @@ template <int K> LG_DEV float dpp_mac3t(float m0, float m1, float m2, float a, f
              : "=&v"(r) : "v"(m0), "v"(m1), "v"(m2), "v"(a), "v"(b), "v"(c));
     return r;
 }
-LG_DEV float mulv(const QM &m, float v) { return dpp_mac3(m.c0, m.c1, m.c2, v); }
+LG_DEV float mulv(const QM &m, float v) { return dpp_mac3(m.c0, m.c1, m.c2, v); }   // m v = m.c0 v[0] + m.c1 v[1] + m.c2 v[2]
 // Whole products in ONE asm block: a single `s_nop 1` in front covers the DPP read-after-write hazard of every source (none is written
 // inside the block), instead of one per three-instruction group (each s_nop is an issue slot of the lone wave: the physics loop had ~190
 // of them per sub-step).  The three accumulators are interleaved, so no instruction waits on the one before it.
@@ -166,45 +165,22 @@ LG_DEV void mulmm2(const QM &a, const QM &b, const QM &c, const QM &d, QM &r, QM
         : "=&v"(r.c0), "=&v"(r.c1), "=&v"(r.c2), "=&v"(q.c0), "=&v"(q.c1), "=&v"(q.c2)
         : "v"(a.c0), "v"(a.c1), "v"(a.c2), "v"(b.c0), "v"(b.c1), "v"(b.c2), "v"(c.c0), "v"(c.c1), "v"(c.c2), "v"(d.c0), "v"(d.c1), "v"(d.c2));
 }
-#else
-LG_DEV float mulv(const QM &m, float v) { return m.c0 * bc<0>(v) + m.c1 * bc<1>(v) + m.c2 * bc<2>(v); }
-LG_DEV QM mulmm(const QM &a, const QM &b) {     // a b
-    QM r;
-    r.c0 = a.c0 * bc<0>(b.c0) + a.c1 * bc<1>(b.c0) + a.c2 * bc<2>(b.c0);
-    r.c1 = a.c0 * bc<0>(b.c1) + a.c1 * bc<1>(b.c1) + a.c2 * bc<2>(b.c1);
-    r.c2 = a.c0 * bc<0>(b.c2) + a.c1 * bc<1>(b.c2) + a.c2 * bc<2>(b.c2);
-    return r;
-}
-LG_DEV QM mulmmt(const QM &a, const QM &b) {    // a b^T
-    QM r;
-    r.c0 = a.c0 * bc<0>(b.c0) + a.c1 * bc<0>(b.c1) + a.c2 * bc<0>(b.c2);
-    r.c1 = a.c0 * bc<1>(b.c0) + a.c1 * bc<1>(b.c1) + a.c2 * bc<1>(b.c2);
-    r.c2 = a.c0 * bc<2>(b.c0) + a.c1 * bc<2>(b.c1) + a.c2 * bc<2>(b.c2);
-    return r;
-}
-LG_DEV void mulmm2(const QM &a, const QM &b, const QM &c, const QM &d, QM &r, QM &q) { r = mulmm(a, b); q = mulmm(c, d); }
-#endif
 // Cross products.  (a x b)_c = a_{c+1} b_{c+2} - a_{c+2} b_{c+1} = rot1(a) rot2(b) - rot2(a) rot1(b): with ONE operand given by its two quad
 // rotations (QR, two v_mov_b32_dpp, shared by every product that operand enters) the other rides through DPP on a multiply and a
 // multiply-add -- two instructions per product, and no rotation of the RESULT: the older form rot1(a rot1(b) - rot1(a) b) was three
 // plus a DPP read of the value just computed, i.e. two wait states in front of whatever consumed it (~50 products per sub-step).
 struct QR { float r1, r2; };                                               // rot1(v), rot2(v)
 LG_DEV QR rots(float v) { QR r = {rot1(v), rot2(v)}; return r; }
-#ifndef LG_NO_DPP_ASM
-LG_DEV float cross(float a, const QR &b) {      // a x b, b by its rotations
+LG_DEV float cross(float a, const QR &b) {      // a x b, b by its rotations: rot1(a) b.r2 - rot2(a) b.r1
     float r;
     asm(LG_SNOP "v_mul_f32_dpp %0, %1, %2 " LG_QPR1 "\n\tv_fmac_f32_dpp %0, %1, -%3 " LG_QPR2 : "=&v"(r) : "v"(a), "v"(b.r2), "v"(b.r1));
     return r;
 }
-LG_DEV float cross(const QR &a, float b) {      // a x b, a by its rotations
+LG_DEV float cross(const QR &a, float b) {      // a x b, a by its rotations: a.r1 rot2(b) - a.r2 rot1(b)
     float r;
     asm(LG_SNOP "v_mul_f32_dpp %0, %1, %2 " LG_QPR2 "\n\tv_fmac_f32_dpp %0, %1, -%3 " LG_QPR1 : "=&v"(r) : "v"(b), "v"(a.r1), "v"(a.r2));
     return r;
 }
-#else
-LG_DEV float cross(float a, const QR &b) { return rot1(a) * b.r2 - rot2(a) * b.r1; }
-LG_DEV float cross(const QR &a, float b) { return a.r1 * rot2(b) - a.r2 * rot1(b); }
-#endif
 LG_DEV float cross(float a, float b) { return cross(a, rots(b)); }
 LG_DEV float multv(const Lane &L, const QM &m, float v) {   // m^T v
     return L.sel(sum3(m.c0 * v), sum3(m.c1 * v), sum3(m.c2 * v));
@@ -231,21 +207,11 @@ LG_DEV QM inv_sym(const Lane &L, const QM &m) {
     QM r = {x0 * inv, x1 * inv, x2 * inv};
     return r;
 }
-// LG_PK_F32 (off; kept for the record): the elementwise spatial-vector / 6x6 arithmetic and the rank-1 downdate written as
-// packed FP32 (<2 x float>: v_pk_add_f32 / v_pk_mul_f32 / v_pk_fma_f32).  Measured slower -- the pairs cost v_mov_b32 to form and 64-bit
-// tuples to allocate -- and the iterative-ilp build of it crashes clang's register allocator.
-#ifdef LG_PK_F32
-LG_DEV QV6 operator+(const QV6 &a, const QV6 &b) { const f2 r = f2{a.a, a.l} + f2{b.a, b.l}; QV6 o = {r.x, r.y}; return o; }
-LG_DEV QV6 operator-(const QV6 &a, const QV6 &b) { const f2 r = f2{a.a, a.l} - f2{b.a, b.l}; QV6 o = {r.x, r.y}; return o; }
-LG_DEV QV6 operator*(const QV6 &a, float s) { const f2 r = f2{a.a, a.l} * f2{s, s}; QV6 o = {r.x, r.y}; return o; }
-#else
 LG_DEV QV6 operator+(const QV6 &a, const QV6 &b) { QV6 r = {a.a + b.a, a.l + b.l}; return r; }
 LG_DEV QV6 operator-(const QV6 &a, const QV6 &b) { QV6 r = {a.a - b.a, a.l - b.l}; return r; }
 LG_DEV QV6 operator*(const QV6 &a, float s) { QV6 r = {a.a * s, a.l * s}; return r; }
-#endif
 LG_DEV float dot6(const QV6 &a, const QV6 &b) { return sum3(a.a * b.a + a.l * b.l); }
-LG_DEV QV6 muli6(const QI6 &I, const QV6 &v) {
-#ifndef LG_NO_DPP_ASM
+LG_DEV QV6 muli6(const QI6 &I, const QV6 &v) {   // r.a = A v.a + B v.l, r.l = B^T v.a + C v.l
     QV6 r;      // rows of (A | B) and of (B^T | C) against [v.a; v.l]: twelve multiply-adds, two interleaved accumulators, one s_nop
     asm(LG_SNOP
         "v_mul_f32_dpp %0, %14, %2 " LG_QP0 "\n\tv_mul_f32_dpp %1, %14, %8 " LG_QP0 "\n\t"
@@ -258,37 +224,10 @@ LG_DEV QV6 muli6(const QI6 &I, const QV6 &v) {
         : "v"(I.A.c0), "v"(I.A.c1), "v"(I.A.c2), "v"(I.B.c0), "v"(I.B.c1), "v"(I.B.c2),
           "v"(I.Bt.c0), "v"(I.Bt.c1), "v"(I.Bt.c2), "v"(I.C.c0), "v"(I.C.c1), "v"(I.C.c2), "v"(v.a), "v"(v.l));
     return r;
-#else
-    const float a0 = bc<0>(v.a), a1 = bc<1>(v.a), a2 = bc<2>(v.a), l0 = bc<0>(v.l), l1 = bc<1>(v.l), l2 = bc<2>(v.l);
-    QV6 r;
-    r.a = I.A.c0 * a0 + I.A.c1 * a1 + I.A.c2 * a2 + I.B.c0 * l0 + I.B.c1 * l1 + I.B.c2 * l2;
-    r.l = I.Bt.c0 * a0 + I.Bt.c1 * a1 + I.Bt.c2 * a2 + I.C.c0 * l0 + I.C.c1 * l1 + I.C.c2 * l2;
-    return r;
-#endif
 }
-#ifdef LG_PK_F32
-LG_DEV QI6 operator+(const QI6 &a, const QI6 &b) {
-    QI6 r;
-#define LG_PKADD(X, Y) { const f2 t = f2{a.X, a.Y} + f2{b.X, b.Y}; r.X = t.x; r.Y = t.y; }
-    LG_PKADD(A.c0, Bt.c0) LG_PKADD(A.c1, Bt.c1) LG_PKADD(A.c2, Bt.c2) LG_PKADD(B.c0, C.c0) LG_PKADD(B.c1, C.c1) LG_PKADD(B.c2, C.c2)
-#undef LG_PKADD
-    return r;
-}
-// I - U U^T dinv: rows of (A | B) and (B^T | C) share the broadcast operand -> six v_pk_fma_f32
-LG_DEV QI6 rank1_down(const QI6 &I, const QV6 &U, float dinv) {
-    const f2 u = f2{U.a, U.l} * f2{-dinv, -dinv};
-    const float a0 = bc<0>(U.a), a1 = bc<1>(U.a), a2 = bc<2>(U.a), l0 = bc<0>(U.l), l1 = bc<1>(U.l), l2 = bc<2>(U.l);
-    QI6 r;
-#define LG_PKFMA(X, Y, S) { const f2 t = __builtin_elementwise_fma(u, f2{S, S}, f2{I.X, I.Y}); r.X = t.x; r.Y = t.y; }
-    LG_PKFMA(A.c0, Bt.c0, a0) LG_PKFMA(A.c1, Bt.c1, a1) LG_PKFMA(A.c2, Bt.c2, a2) LG_PKFMA(B.c0, C.c0, l0) LG_PKFMA(B.c1, C.c1, l1) LG_PKFMA(B.c2, C.c2, l2)
-#undef LG_PKFMA
-    return r;
-}
-#else
 LG_DEV QI6 operator+(const QI6 &a, const QI6 &b) { QI6 r = {a.A + b.A, a.B + b.B, a.Bt + b.Bt, a.C + b.C}; return r; }
 // I - U U^T dinv
 LG_DEV QI6 rank1_down(const QI6 &I, const QV6 &U, float dinv) {
-#ifndef LG_NO_DPP_ASM
     // entry (c, k) of each block -= u_c dinv u_k: the broadcast of u_k rides on v_fmac_f32_dpp (twelve instructions, one s_nop) instead
     // of six v_mov_b32_dpp + twelve v_fma
     const float na = -(U.a * dinv), nl = -(U.l * dinv);
@@ -302,18 +241,7 @@ LG_DEV QI6 rank1_down(const QI6 &I, const QV6 &U, float dinv) {
           "+v"(r.Bt.c0), "+v"(r.Bt.c1), "+v"(r.Bt.c2), "+v"(r.C.c0), "+v"(r.C.c1), "+v"(r.C.c2)
         : "v"(U.a), "v"(U.l), "v"(na), "v"(nl));
     return r;
-#else
-    const float ua = U.a * dinv, ul = U.l * dinv;
-    const float a0 = bc<0>(U.a), a1 = bc<1>(U.a), a2 = bc<2>(U.a), l0 = bc<0>(U.l), l1 = bc<1>(U.l), l2 = bc<2>(U.l);
-    QI6 r;
-    r.A.c0 = I.A.c0 - ua * a0; r.A.c1 = I.A.c1 - ua * a1; r.A.c2 = I.A.c2 - ua * a2;
-    r.B.c0 = I.B.c0 - ua * l0; r.B.c1 = I.B.c1 - ua * l1; r.B.c2 = I.B.c2 - ua * l2;
-    r.Bt.c0 = I.Bt.c0 - ul * a0; r.Bt.c1 = I.Bt.c1 - ul * a1; r.Bt.c2 = I.Bt.c2 - ul * a2;
-    r.C.c0 = I.C.c0 - ul * l0; r.C.c1 = I.C.c1 - ul * l1; r.C.c2 = I.C.c2 - ul * l2;
-    return r;
-#endif
 }
-#endif
 // inverse of an SPD 6x6 by Schur complement on the C block
 LG_DEV QI6 inv6(const Lane &L, const QI6 &N) {
     const QM Ci = inv_sym(L, N.C);
@@ -483,11 +411,7 @@ LG_DEV void blank_histories(unsigned long long rm, int e, float *obs, size_t oro
 // blocks, each term's reduction over the env's lanes (four dependent DPP adds with their wait states) alone in its own; with the set known
 // the unused terms are gone and the others interleave (go2: -0.5 us).  Any other set of terms runs the RS = false instantiation.
 template <int LEGS, bool DO_PRE, unsigned MPH, int PROF = 0, int JPL = 3, bool INJ = false, bool RS = false>
-#ifdef LG_PK_F32   // one wave per SIMD by design: let the allocator use the accumulation registers instead of spilling the 64-bit tuples
-__global__ __launch_bounds__(BLOCK) __attribute__((amdgpu_waves_per_eu(1, 1))) void quad_sim_kernel(KParams p) {
-#else
 __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET) ? 2 * BLOCK : BLOCK) void quad_sim_kernel(KParams p) {
-#endif
     using namespace q4;
     const unsigned tl_ = threadIdx.x & 63u;   // lane of the wave (a workgroup is one wave, two for the DUO tail below)
     static_assert(JPL == 3 || (JPL == 4 && LEGS == 2 && MPH == 0 && PROF == 0), "four-joint legs: biped physics only");
@@ -1093,7 +1017,6 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
             // bilinear height and normal): probe, force, probe, force ... exposed one L2 round trip per slot and sub-step in the serial
             // chain (rough terrain: +14 k cycles per control step over the plane); issued together the loads overlap.
             Hit tb, ta, tc, td, te;
-#ifndef LG_NO_PK_TERRAIN
             if constexpr (HFC && JPL == 3) {
                 // heightfield bound (compile time): the five slots' sphere centres and the foot's, then the six lookups as three packed pairs
                 // (base | hip, thigh | calf, calf's second slot | foot)
@@ -1124,7 +1047,6 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
                 te = finish(3, cx[4], cy[4], cz[4], hh[2].x, nnx[2].x, nny[2].x, nnz[2].x);
                 ft_h = hh[2].y; ft_nx = nnx[2].y; ft_ny = nny[2].y; ft_nz = nnz[2].y;
             } else
-#endif
             {
             tb = probe(4, Rb, 0.f); ta = probe(0, K[0].R, K[0].P); tc = probe(1, K[1].R, K[1].P);
             td = probe(2, K[2].R, K[2].P);
@@ -1136,7 +1058,6 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
             }
             }
             slot(4, tb, Rb, 0.f, V0, extb);
-#ifndef LG_NO_PK_SPHERES
             {   // hip and thigh slots: as a packed pair when both are live somewhere in the wave, on their own otherwise
                 const bool on0 = __builtin_amdgcn_ballot_w64(ta.on) != 0ull, on1 = __builtin_amdgcn_ballot_w64(tc.on) != 0ull;
                 if (on0 && on1) {
@@ -1150,10 +1071,6 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
                     slot(1, tc, K[1].R, K[1].P, K[1].V, ext[1]);
                 }
             }
-#else
-            slot(0, ta, K[0].R, K[0].P, K[0].V, ext[0]);
-            slot(1, tc, K[1].R, K[1].P, K[1].V, ext[1]);
-#endif
             if constexpr (JPL == 4) {
                 slot(2, td, K[2].R, K[2].P, K[2].V, ext[2]);
                 // the sole corners: penetration / approach velocity relative to the sole centre's while that one is in the ground
@@ -1184,17 +1101,10 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
                 const Hit t2 = td, t3 = te;
                 if (__builtin_amdgcn_ballot_w64(t2.on || t3.on) != 0ull) {
                     const BodyS g = gather(K[2].R, K[2].P, K[2].V);
-#ifndef LG_NO_PK_SPHERES
                     const f2 z2 = {0.f, 0.f};
                     Acc2 a2 = {z2, z2, z2, z2, z2, z2};
                     force2(2, 3, t2, t3, pair_bodies(g, g), a2);
                     reduce6(a2.mx.x + a2.mx.y, a2.my.x + a2.my.y, a2.mz.x + a2.mz.y, a2.fx.x + a2.fx.y, a2.fy.x + a2.fy.y, a2.fz.x + a2.fz.y, ext[2]);
-#else
-                    float m[3] = {0.f, 0.f, 0.f}, f[3] = {0.f, 0.f, 0.f};
-                    force(2, t2, g, m, f);
-                    force(3, t3, g, m, f);
-                    reduce(m, f, ext[2]);
-#endif
                 }
             }
         }
@@ -1706,117 +1616,241 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
     if (DUO) __syncthreads();   // role 0's read-back stores are issued; role 1's tail may now store into the same arrays (resets)
     STAMP(22);
     STAMPB(8192);
-    // ---------------- MDP phases in the same launch, go2-flat and go2_wtw profiles: component layout, all 64 lanes ------------
-    // Same statements as env_step_body's POST / RESET phases (legged_robot.py:55-168, 300-348, go2.py:17-134) for the plain go2
-    // task, computed on the registers the physics left behind: per-joint values sit in joint lanes, vectors one component per
-    // lane, per-env scalars replicated over the env's 16 lanes.  No LDS hand-off, every lane loads / stores its own share of the
-    // MDP state (two episode sums, one command component ...), and independent Philox blocks are evaluated side by side in
-    // different lanes (a call is ~800 cycles of quarter-rate multiplies whatever the number of lanes using it).  The random
-    // stream is the one of env_step_body (same counters), so both instantiations produce the same rollout.
-    if constexpr (QTAIL) {
+    // ---------------- MDP phases in the same launch, component layout: go2 flat, go2_wtw, the go2_ee family, tron1_pf_ee ---------------
+    // Same statements as env_step_body's POST / RESET phases (legged_robot.py:55-168, 300-348; go2.py:17-134; tron1_pf_ee.py:12-141,
+    // 193-256, 347-463), computed on the registers the physics left behind: per-joint values sit in joint lanes, vectors one component
+    // per lane, per-env scalars replicated over the env's lanes (16 for a quadruped, 8 for the biped).  No LDS hand-off, every lane loads
+    // / stores its own share of the MDP state (the episode sums it owns, one command component ...), and independent Philox blocks are
+    // evaluated side by side in different lanes (a call is ~800 cycles of quarter-rate multiplies whatever the number of lanes using it).
+    // The random stream is the one of env_step_body (same counters, same words), so both instantiations produce the same rollout.
+    // Sections that only some profiles have are compiled in by the profile flags (WQ, EQ, PQ, SQ, BQ).  The DUO split (tron1_pf_ee)
+    // shares the tail out between the workgroup's two waves: A_ (role 0) the rewards, episode sums and noisy actor frames, B_ (role 1)
+    // the critic frames, labels, pushes, resets and task state; a quadruped's one wave does both.
+    if constexpr (CTAIL) {
         STAMP(5);
         // hot constants of the MDP phases in ONE burst of LDS reads (a read at the point of use costs an exposed LDS round trip each:
-        // one wave per SIMD, every reward term in its own basic block)
-        const auto h_about_landing_threshold = HOT(about_landing_threshold);
-        const auto h_add_noise = HOT(add_noise);
-        const auto h_base_height_target = HOT(base_height_target);
-        const auto h_base_init_quat_0 = HOT(base_init_quat[0]);
-        const auto h_base_init_quat_1 = HOT(base_init_quat[1]);
-        const auto h_base_init_quat_2 = HOT(base_init_quat[2]);
-        const auto h_base_init_quat_3 = HOT(base_init_quat[3]);
-        const auto h_clip_obs = HOT(clip_obs);
-        const auto h_control_dt = HOT(control_dt);
-        const auto h_dr_com_lo_0 = HOT(dr_com_lo[0]);
-        const auto h_dr_com_lo_1 = HOT(dr_com_lo[1]);
-        const auto h_dr_com_lo_2 = HOT(dr_com_lo[2]);
-        const auto h_dr_com_on = HOT(dr_com_on);
-        const auto h_dr_com_span_0 = HOT(dr_com_span[0]);
-        const auto h_dr_com_span_1 = HOT(dr_com_span[1]);
-        const auto h_dr_com_span_2 = HOT(dr_com_span[2]);
-        const auto h_dr_friction_lo = HOT(dr_friction_lo);
-        const auto h_dr_friction_on = HOT(dr_friction_on);
-        const auto h_dr_friction_span = HOT(dr_friction_span);
-        const auto h_dr_mass_lo = HOT(dr_mass_lo);
-        const auto h_dr_mass_on = HOT(dr_mass_on);
-        const auto h_dr_mass_span = HOT(dr_mass_span);
-        const auto h_env_id_offset = HOT(env_id_offset);
-        const auto h_fail_threshold = HOT(fail_threshold);
-        const auto h_feet_air_time_threshold = HOT(feet_air_time_threshold);
-        const auto h_foot_clearance_sigma = HOT(foot_clearance_sigma);
-        const auto h_foot_clearance_target = HOT(foot_clearance_target);
-        const auto h_foot_height_offset = HOT(foot_height_offset);
-        const auto h_heading_command = HOT(heading_command);
-        const auto h_max_episode_length = HOT(max_episode_length);
-        const auto h_max_projected_gravity = HOT(max_projected_gravity);
-        const auto h_max_push_vel_xy = HOT(max_push_vel_xy);
-        const auto h_noise_lead_0 = HOT(noise_lead[0]);
-        const auto h_noise_lead_1 = HOT(noise_lead[1]);
-        const auto h_noise_lead_2 = HOT(noise_lead[2]);
-        const auto h_noise_lead_3 = HOT(noise_lead[3]);
-        const auto h_noise_lead_4 = HOT(noise_lead[4]);
-        const auto h_noise_lead_5 = HOT(noise_lead[5]);
-        const auto h_o_base_init_pos_0 = HOT(o_base_init_pos[0]);
-        const auto h_o_base_init_pos_1 = HOT(o_base_init_pos[1]);
-        const auto h_o_base_init_pos_2 = HOT(o_base_init_pos[2]);
-        const auto h_obs_scale_ang_vel = HOT(obs_scale_ang_vel);
-        const auto h_obs_scale_dof_pos = HOT(obs_scale_dof_pos);
-        const auto h_obs_scale_dof_vel = HOT(obs_scale_dof_vel);
-        const auto h_obs_scale_lin_vel = HOT(obs_scale_lin_vel);
-        const auto h_obs_sets = HOT(obs_sets);
-        const auto h_only_positive_rewards = HOT(only_positive_rewards);
-        const auto h_push_interval = HOT(push_interval);
-        const auto h_resample_steps = HOT(resample_steps);
-        const auto h_reset_ang_vel_lo = HOT(reset_ang_vel_lo);
-        const auto h_reset_lin_vel_lo = HOT(reset_lin_vel_lo);
-        const auto h_seed = HOT(seed);
-        const auto h_slots_cb_cmd = HOT(slots.cb_cmd);
-        const auto h_slots_push = HOT(slots.push);
-        const auto h_slots_reset_dof = HOT(slots.reset_dof);
-        const auto h_tracking_sigma = HOT(tracking_sigma);
-        const auto h_yaw_clip_0 = HOT(yaw_clip[0]);
-        const auto h_yaw_clip_1 = HOT(yaw_clip[1]);
-        // go2_wtw only (the reads fold away in the go2 instantiation)
-        const auto h_b_swing = WQ ? HOT(b_swing) : 0.f;
-        const auto h_base_height_sigma = WQ ? HOT(base_height_sigma) : 1.f;
+        // one wave per SIMD, every reward term in its own basic block); the reads a profile does not use fold away.  tron1_pf_ee's
+        // tail issues them in an order of its own (b_*, the quadruped tails' order below would schedule it differently)
+        const auto b_about_landing_threshold = BQ ? HOT(about_landing_threshold) : HOT_T(about_landing_threshold)();
+        const auto b_add_noise = BQ ? HOT(add_noise) : HOT_T(add_noise)();
+        const auto b_air_time_cmd_dims = BQ ? HOT(air_time_cmd_dims) : HOT_T(air_time_cmd_dims)();
+        const auto b_b_swing = BQ ? HOT(b_swing) : HOT_T(b_swing)();
+        const auto b_base_height_sigma = BQ ? HOT(base_height_sigma) : HOT_T(base_height_sigma)();
+        const auto b_base_height_target = BQ ? HOT(base_height_target) : HOT_T(base_height_target)();
+        const auto b_base_init_quat_0 = BQ ? HOT(base_init_quat[0]) : HOT_T(base_init_quat[0])();
+        const auto b_base_init_quat_1 = BQ ? HOT(base_init_quat[1]) : HOT_T(base_init_quat[1])();
+        const auto b_base_init_quat_2 = BQ ? HOT(base_init_quat[2]) : HOT_T(base_init_quat[2])();
+        const auto b_base_init_quat_3 = BQ ? HOT(base_init_quat[3]) : HOT_T(base_init_quat[3])();
+        const auto b_clip_obs = BQ ? HOT(clip_obs) : HOT_T(clip_obs)();
+        const auto b_control_dt = BQ ? HOT(control_dt) : HOT_T(control_dt)();
+        const auto b_custom_origins = BQ ? HOT(custom_origins) : HOT_T(custom_origins)();
+        const auto b_dr_com_lo_0 = BQ ? HOT(dr_com_lo[0]) : HOT_T(dr_com_lo[0])();
+        const auto b_dr_com_lo_1 = BQ ? HOT(dr_com_lo[1]) : HOT_T(dr_com_lo[1])();
+        const auto b_dr_com_lo_2 = BQ ? HOT(dr_com_lo[2]) : HOT_T(dr_com_lo[2])();
+        const auto b_dr_com_on = BQ ? HOT(dr_com_on) : HOT_T(dr_com_on)();
+        const auto b_dr_com_span_0 = BQ ? HOT(dr_com_span[0]) : HOT_T(dr_com_span[0])();
+        const auto b_dr_com_span_1 = BQ ? HOT(dr_com_span[1]) : HOT_T(dr_com_span[1])();
+        const auto b_dr_com_span_2 = BQ ? HOT(dr_com_span[2]) : HOT_T(dr_com_span[2])();
+        const auto b_dr_friction_lo = BQ ? HOT(dr_friction_lo) : HOT_T(dr_friction_lo)();
+        const auto b_dr_friction_on = BQ ? HOT(dr_friction_on) : HOT_T(dr_friction_on)();
+        const auto b_dr_friction_span = BQ ? HOT(dr_friction_span) : HOT_T(dr_friction_span)();
+        const auto b_dr_joint_lo_0 = BQ ? HOT(dr_joint_lo[0]) : HOT_T(dr_joint_lo[0])();
+        const auto b_dr_joint_lo_1 = BQ ? HOT(dr_joint_lo[1]) : HOT_T(dr_joint_lo[1])();
+        const auto b_dr_joint_lo_2 = BQ ? HOT(dr_joint_lo[2]) : HOT_T(dr_joint_lo[2])();
+        const auto b_dr_joint_on = BQ ? HOT(dr_joint_on) : HOT_T(dr_joint_on)();
+        const auto b_dr_joint_span_0 = BQ ? HOT(dr_joint_span[0]) : HOT_T(dr_joint_span[0])();
+        const auto b_dr_joint_span_1 = BQ ? HOT(dr_joint_span[1]) : HOT_T(dr_joint_span[1])();
+        const auto b_dr_joint_span_2 = BQ ? HOT(dr_joint_span[2]) : HOT_T(dr_joint_span[2])();
+        const auto b_dr_kd_lo = BQ ? HOT(dr_kd_lo) : HOT_T(dr_kd_lo)();
+        const auto b_dr_kd_span = BQ ? HOT(dr_kd_span) : HOT_T(dr_kd_span)();
+        const auto b_dr_kp_lo = BQ ? HOT(dr_kp_lo) : HOT_T(dr_kp_lo)();
+        const auto b_dr_kp_span = BQ ? HOT(dr_kp_span) : HOT_T(dr_kp_span)();
+        const auto b_dr_mass_lo = BQ ? HOT(dr_mass_lo) : HOT_T(dr_mass_lo)();
+        const auto b_dr_mass_on = BQ ? HOT(dr_mass_on) : HOT_T(dr_mass_on)();
+        const auto b_dr_mass_span = BQ ? HOT(dr_mass_span) : HOT_T(dr_mass_span)();
+        const auto b_dr_pd_on = BQ ? HOT(dr_pd_on) : HOT_T(dr_pd_on)();
+        const auto b_env_id_offset = BQ ? HOT(env_id_offset) : HOT_T(env_id_offset)();
+        const auto b_episode_length_s = BQ ? HOT(episode_length_s) : HOT_T(episode_length_s)();
+        const auto b_fail_threshold = BQ ? HOT(fail_threshold) : HOT_T(fail_threshold)();
+        const auto b_feet_air_time_threshold = BQ ? HOT(feet_air_time_threshold) : HOT_T(feet_air_time_threshold)();
+        const auto b_foot_clearance_ref = BQ ? HOT(foot_clearance_ref) : HOT_T(foot_clearance_ref)();
+        const auto b_foot_clearance_sigma = BQ ? HOT(foot_clearance_sigma) : HOT_T(foot_clearance_sigma)();
+        const auto b_foot_clearance_target = BQ ? HOT(foot_clearance_target) : HOT_T(foot_clearance_target)();
+        const auto b_foot_distance_threshold = BQ ? HOT(foot_distance_threshold) : HOT_T(foot_distance_threshold)();
+        const auto b_foot_height_offset = BQ ? HOT(foot_height_offset) : HOT_T(foot_height_offset)();
+        const auto b_friction_offset = BQ ? HOT(friction_offset) : HOT_T(friction_offset)();
+        const auto b_gait_period_fixed = BQ ? HOT(gait_period_fixed) : HOT_T(gait_period_fixed)();
+        const auto b_heading_command = BQ ? HOT(heading_command) : HOT_T(heading_command)();
+        const auto b_heights_clip_scale = BQ ? HOT(heights_clip_scale) : HOT_T(heights_clip_scale)();
+        const auto b_heights_offset = BQ ? HOT(heights_offset) : HOT_T(heights_offset)();
+        const auto b_kd_offset = BQ ? HOT(kd_offset) : HOT_T(kd_offset)();
+        const auto b_kp_offset = BQ ? HOT(kp_offset) : HOT_T(kp_offset)();
+        const auto b_max_episode_length = BQ ? HOT(max_episode_length) : HOT_T(max_episode_length)();
+        const auto b_max_projected_gravity = BQ ? HOT(max_projected_gravity) : HOT_T(max_projected_gravity)();
+        const auto b_max_push_vel_xy = BQ ? HOT(max_push_vel_xy) : HOT_T(max_push_vel_xy)();
+        const auto b_max_terrain_level = BQ ? HOT(max_terrain_level) : HOT_T(max_terrain_level)();
+        const auto b_noise_act0 = BQ ? HOT(noise_act0) : HOT_T(noise_act0)();
+        const auto b_noise_lead_0 = BQ ? HOT(noise_lead[0]) : HOT_T(noise_lead[0])();
+        const auto b_noise_lead_1 = BQ ? HOT(noise_lead[1]) : HOT_T(noise_lead[1])();
+        const auto b_noise_lead_2 = BQ ? HOT(noise_lead[2]) : HOT_T(noise_lead[2])();
+        const auto b_noise_lead_3 = BQ ? HOT(noise_lead[3]) : HOT_T(noise_lead[3])();
+        const auto b_noise_lead_4 = BQ ? HOT(noise_lead[4]) : HOT_T(noise_lead[4])();
+        const auto b_noise_lead_5 = BQ ? HOT(noise_lead[5]) : HOT_T(noise_lead[5])();
+        const auto b_num_labels = BQ ? HOT(num_labels) : HOT_T(num_labels)();
+        const auto b_num_obs = BQ ? HOT(num_obs) : HOT_T(num_obs)();
+        const auto b_num_priv_obs = BQ ? HOT(num_priv_obs) : HOT_T(num_priv_obs)();
+        const auto b_o_base_init_pos_0 = BQ ? HOT(o_base_init_pos[0]) : HOT_T(o_base_init_pos[0])();
+        const auto b_o_base_init_pos_1 = BQ ? HOT(o_base_init_pos[1]) : HOT_T(o_base_init_pos[1])();
+        const auto b_o_base_init_pos_2 = BQ ? HOT(o_base_init_pos[2]) : HOT_T(o_base_init_pos[2])();
+        const auto b_obs_frame = BQ ? HOT(obs_frame) : HOT_T(obs_frame)();
+        const auto b_obs_scale_ang_vel = BQ ? HOT(obs_scale_ang_vel) : HOT_T(obs_scale_ang_vel)();
+        const auto b_obs_scale_dof_pos = BQ ? HOT(obs_scale_dof_pos) : HOT_T(obs_scale_dof_pos)();
+        const auto b_obs_scale_dof_vel = BQ ? HOT(obs_scale_dof_vel) : HOT_T(obs_scale_dof_vel)();
+        const auto b_obs_scale_height = BQ ? HOT(obs_scale_height) : HOT_T(obs_scale_height)();
+        const auto b_obs_scale_lin_vel = BQ ? HOT(obs_scale_lin_vel) : HOT_T(obs_scale_lin_vel)();
+        const auto b_obs_sets = BQ ? HOT(obs_sets) : HOT_T(obs_sets)();
+        const auto b_obs_slack = BQ ? HOT(obs_slack) : HOT_T(obs_slack)();
+        const auto b_obs_stack = BQ ? HOT(obs_stack) : HOT_T(obs_stack)();
+        const auto b_only_positive_rewards = BQ ? HOT(only_positive_rewards) : HOT_T(only_positive_rewards)();
+        const auto b_priv_frame = BQ ? HOT(priv_frame) : HOT_T(priv_frame)();
+        const auto b_priv_stack = BQ ? HOT(priv_stack) : HOT_T(priv_stack)();
+        const auto b_push_interval = BQ ? HOT(push_interval) : HOT_T(push_interval)();
+        const auto b_resample_steps = BQ ? HOT(resample_steps) : HOT_T(resample_steps)();
+        const auto b_reset_ang_vel_lo = BQ ? HOT(reset_ang_vel_lo) : HOT_T(reset_ang_vel_lo)();
+        const auto b_reset_ang_vel_span = BQ ? HOT(reset_ang_vel_span) : HOT_T(reset_ang_vel_span)();
+        const auto b_reset_lin_vel_lo = BQ ? HOT(reset_lin_vel_lo) : HOT_T(reset_lin_vel_lo)();
+        const auto b_reset_lin_vel_span = BQ ? HOT(reset_lin_vel_span) : HOT_T(reset_lin_vel_span)();
+        const auto b_reset_root_xy_lo = BQ ? HOT(reset_root_xy_lo) : HOT_T(reset_root_xy_lo)();
+        const auto b_reset_root_xy_span = BQ ? HOT(reset_root_xy_span) : HOT_T(reset_root_xy_span)();
+        const auto b_seed = BQ ? HOT(seed) : HOT_T(seed)();
+        const auto b_sit_percent = BQ ? HOT(sit_percent) : HOT_T(sit_percent)();
+        const auto b_slots_cb_cmd = BQ ? HOT(slots.cb_cmd) : HOT_T(slots.cb_cmd)();
+        const auto b_slots_dr_kd = BQ ? HOT(slots.dr_kd) : HOT_T(slots.dr_kd)();
+        const auto b_slots_dr_kp = BQ ? HOT(slots.dr_kp) : HOT_T(slots.dr_kp)();
+        const auto b_slots_push = BQ ? HOT(slots.push) : HOT_T(slots.push)();
+        const auto b_slots_reset_dof = BQ ? HOT(slots.reset_dof) : HOT_T(slots.reset_dof)();
+        const auto b_slots_reset_root_xy = BQ ? HOT(slots.reset_root_xy) : HOT_T(slots.reset_root_xy)();
+        const auto b_slots_task_reset = BQ ? HOT(slots.task_reset) : HOT_T(slots.task_reset)();
+        const auto b_terrain_cols_n = BQ ? HOT(terrain_cols_n) : HOT_T(terrain_cols_n)();
+        const auto b_terrain_curriculum = BQ ? HOT(terrain_curriculum) : HOT_T(terrain_curriculum)();
+        const auto b_terrain_env_length = BQ ? HOT(terrain_env_length) : HOT_T(terrain_env_length)();
+        const auto b_tracking_sigma = BQ ? HOT(tracking_sigma) : HOT_T(tracking_sigma)();
+        const auto b_yaw_clip_0 = BQ ? HOT(yaw_clip[0]) : HOT_T(yaw_clip[0])();
+        const auto b_yaw_clip_1 = BQ ? HOT(yaw_clip[1]) : HOT_T(yaw_clip[1])();
+        const auto h_about_landing_threshold = BQ ? b_about_landing_threshold : HOT(about_landing_threshold);
+        const auto h_add_noise = BQ ? b_add_noise : HOT(add_noise);
+        const auto h_base_height_target = BQ ? b_base_height_target : HOT(base_height_target);
+        const auto h_base_init_quat_0 = BQ ? b_base_init_quat_0 : HOT(base_init_quat[0]);
+        const auto h_base_init_quat_1 = BQ ? b_base_init_quat_1 : HOT(base_init_quat[1]);
+        const auto h_base_init_quat_2 = BQ ? b_base_init_quat_2 : HOT(base_init_quat[2]);
+        const auto h_base_init_quat_3 = BQ ? b_base_init_quat_3 : HOT(base_init_quat[3]);
+        const auto h_clip_obs = BQ ? b_clip_obs : HOT(clip_obs);
+        const auto h_control_dt = BQ ? b_control_dt : HOT(control_dt);
+        const auto h_dr_com_lo_0 = BQ ? b_dr_com_lo_0 : HOT(dr_com_lo[0]);
+        const auto h_dr_com_lo_1 = BQ ? b_dr_com_lo_1 : HOT(dr_com_lo[1]);
+        const auto h_dr_com_lo_2 = BQ ? b_dr_com_lo_2 : HOT(dr_com_lo[2]);
+        const auto h_dr_com_on = BQ ? b_dr_com_on : HOT(dr_com_on);
+        const auto h_dr_com_span_0 = BQ ? b_dr_com_span_0 : HOT(dr_com_span[0]);
+        const auto h_dr_com_span_1 = BQ ? b_dr_com_span_1 : HOT(dr_com_span[1]);
+        const auto h_dr_com_span_2 = BQ ? b_dr_com_span_2 : HOT(dr_com_span[2]);
+        const auto h_dr_friction_lo = BQ ? b_dr_friction_lo : HOT(dr_friction_lo);
+        const auto h_dr_friction_on = BQ ? b_dr_friction_on : HOT(dr_friction_on);
+        const auto h_dr_friction_span = BQ ? b_dr_friction_span : HOT(dr_friction_span);
+        const auto h_dr_mass_lo = BQ ? b_dr_mass_lo : HOT(dr_mass_lo);
+        const auto h_dr_mass_on = BQ ? b_dr_mass_on : HOT(dr_mass_on);
+        const auto h_dr_mass_span = BQ ? b_dr_mass_span : HOT(dr_mass_span);
+        const auto h_env_id_offset = BQ ? b_env_id_offset : HOT(env_id_offset);
+        const auto h_fail_threshold = BQ ? b_fail_threshold : HOT(fail_threshold);
+        const auto h_feet_air_time_threshold = BQ ? b_feet_air_time_threshold : HOT(feet_air_time_threshold);
+        const auto h_foot_clearance_sigma = BQ ? b_foot_clearance_sigma : HOT(foot_clearance_sigma);
+        const auto h_foot_clearance_target = BQ ? b_foot_clearance_target : HOT(foot_clearance_target);
+        const auto h_foot_height_offset = BQ ? b_foot_height_offset : HOT(foot_height_offset);
+        const auto h_heading_command = BQ ? b_heading_command : HOT(heading_command);
+        const auto h_max_episode_length = BQ ? b_max_episode_length : HOT(max_episode_length);
+        const auto h_max_projected_gravity = BQ ? b_max_projected_gravity : HOT(max_projected_gravity);
+        const auto h_max_push_vel_xy = BQ ? b_max_push_vel_xy : HOT(max_push_vel_xy);
+        const auto h_noise_lead_0 = BQ ? b_noise_lead_0 : HOT(noise_lead[0]);
+        const auto h_noise_lead_1 = BQ ? b_noise_lead_1 : HOT(noise_lead[1]);
+        const auto h_noise_lead_2 = BQ ? b_noise_lead_2 : HOT(noise_lead[2]);
+        const auto h_noise_lead_3 = BQ ? b_noise_lead_3 : HOT(noise_lead[3]);
+        const auto h_noise_lead_4 = BQ ? b_noise_lead_4 : HOT(noise_lead[4]);
+        const auto h_noise_lead_5 = BQ ? b_noise_lead_5 : HOT(noise_lead[5]);
+        const auto h_o_base_init_pos_0 = BQ ? b_o_base_init_pos_0 : HOT(o_base_init_pos[0]);
+        const auto h_o_base_init_pos_1 = BQ ? b_o_base_init_pos_1 : HOT(o_base_init_pos[1]);
+        const auto h_o_base_init_pos_2 = BQ ? b_o_base_init_pos_2 : HOT(o_base_init_pos[2]);
+        const auto h_obs_scale_ang_vel = BQ ? b_obs_scale_ang_vel : HOT(obs_scale_ang_vel);
+        const auto h_obs_scale_dof_pos = BQ ? b_obs_scale_dof_pos : HOT(obs_scale_dof_pos);
+        const auto h_obs_scale_dof_vel = BQ ? b_obs_scale_dof_vel : HOT(obs_scale_dof_vel);
+        const auto h_obs_scale_lin_vel = BQ ? b_obs_scale_lin_vel : HOT(obs_scale_lin_vel);
+        const auto h_obs_sets = BQ ? b_obs_sets : HOT(obs_sets);
+        const auto h_only_positive_rewards = BQ ? b_only_positive_rewards : HOT(only_positive_rewards);
+        const auto h_push_interval = BQ ? b_push_interval : HOT(push_interval);
+        const auto h_resample_steps = BQ ? b_resample_steps : HOT(resample_steps);
+        const auto h_reset_ang_vel_lo = BQ ? b_reset_ang_vel_lo : HOT(reset_ang_vel_lo);
+        const auto h_reset_lin_vel_lo = BQ ? b_reset_lin_vel_lo : HOT(reset_lin_vel_lo);
+        const auto h_seed = BQ ? b_seed : HOT(seed);
+        const auto h_slots_cb_cmd = BQ ? b_slots_cb_cmd : HOT(slots.cb_cmd);
+        const auto h_slots_push = BQ ? b_slots_push : HOT(slots.push);
+        const auto h_slots_reset_dof = BQ ? b_slots_reset_dof : HOT(slots.reset_dof);
+        const auto h_tracking_sigma = BQ ? b_tracking_sigma : HOT(tracking_sigma);
+        const auto h_yaw_clip_0 = BQ ? b_yaw_clip_0 : HOT(yaw_clip[0]);
+        const auto h_yaw_clip_1 = BQ ? b_yaw_clip_1 : HOT(yaw_clip[1]);
+        // go2_wtw (some also tron1_pf_ee)
+        const auto h_b_swing = BQ ? b_b_swing : (WQ ? HOT(b_swing) : 0.f);
+        const auto h_base_height_sigma = BQ ? b_base_height_sigma : (WQ ? HOT(base_height_sigma) : 1.f);
         const auto h_euler_sigma = WQ ? HOT(euler_sigma) : 1.f;
         const auto h_behavior_resample_steps = WQ ? HOT(behavior_resample_steps) : 0;
         const auto h_slots_task_cb = WQ ? HOT(slots.task_cb) : 0;
-        const auto h_slots_task_reset = WQ ? HOT(slots.task_reset) : 0;
-        const auto h_slots_dr_kp = SQ ? HOT(slots.dr_kp) : 0;
-        const auto h_slots_dr_kd = SQ ? HOT(slots.dr_kd) : 0;
-        const auto h_dr_pd_on = SQ ? HOT(dr_pd_on) : 0;
-        const auto h_dr_kp_lo = SQ ? HOT(dr_kp_lo) : 0.f;
-        const auto h_dr_kp_span = SQ ? HOT(dr_kp_span) : 0.f;
-        const auto h_dr_kd_lo = SQ ? HOT(dr_kd_lo) : 0.f;
-        const auto h_dr_kd_span = SQ ? HOT(dr_kd_span) : 0.f;
-        const auto h_reset_lin_vel_span = SQ ? HOT(reset_lin_vel_span) : 0.f;
-        const auto h_reset_ang_vel_span = SQ ? HOT(reset_ang_vel_span) : 0.f;
-        const auto h_obs_frame = SQ ? HOT(obs_frame) : 0;
-        const auto h_priv_frame = SQ ? HOT(priv_frame) : 0;
-        const auto h_obs_stack = SQ ? HOT(obs_stack) : 1;
-        const auto h_priv_stack = SQ ? HOT(priv_stack) : 1;
-        const auto h_obs_slack = SQ ? HOT(obs_slack) : 0;
-        const auto h_num_obs = SQ ? HOT(num_obs) : 0;
-        const auto h_num_priv_obs = SQ ? HOT(num_priv_obs) : 0;
-        // go2_ee only
-        const auto h_terrain_curriculum = EQ ? HOT(terrain_curriculum) : 0;
-        const auto h_max_terrain_level = EQ ? HOT(max_terrain_level) : 1;
-        const auto h_terrain_cols_n = EQ ? HOT(terrain_cols_n) : 1;
-        const auto h_terrain_env_length = EQ ? HOT(terrain_env_length) : 0.f;
-        const auto h_episode_length_s = EQ ? HOT(episode_length_s) : 0.f;
-        const auto h_slots_reset_root_xy = EQ ? HOT(slots.reset_root_xy) : 0;
+        const auto h_slots_task_reset = BQ ? b_slots_task_reset : (WQ ? HOT(slots.task_reset) : 0);
+        // the stacked-observation profiles: go2_wtw, the go2_ee family, tron1_pf_ee
+        const auto h_slots_dr_kp = BQ ? b_slots_dr_kp : (SQ ? HOT(slots.dr_kp) : 0);
+        const auto h_slots_dr_kd = BQ ? b_slots_dr_kd : (SQ ? HOT(slots.dr_kd) : 0);
+        const auto h_dr_pd_on = BQ ? b_dr_pd_on : (SQ ? HOT(dr_pd_on) : 0);
+        const auto h_dr_kp_lo = BQ ? b_dr_kp_lo : (SQ ? HOT(dr_kp_lo) : 0.f);
+        const auto h_dr_kp_span = BQ ? b_dr_kp_span : (SQ ? HOT(dr_kp_span) : 0.f);
+        const auto h_dr_kd_lo = BQ ? b_dr_kd_lo : (SQ ? HOT(dr_kd_lo) : 0.f);
+        const auto h_dr_kd_span = BQ ? b_dr_kd_span : (SQ ? HOT(dr_kd_span) : 0.f);
+        const auto h_reset_lin_vel_span = BQ ? b_reset_lin_vel_span : (SQ ? HOT(reset_lin_vel_span) : 0.f);
+        const auto h_reset_ang_vel_span = BQ ? b_reset_ang_vel_span : (SQ ? HOT(reset_ang_vel_span) : 0.f);
+        const auto h_obs_frame = BQ ? b_obs_frame : (SQ ? HOT(obs_frame) : 0);
+        const auto h_priv_frame = BQ ? b_priv_frame : (SQ ? HOT(priv_frame) : 0);
+        const auto h_obs_stack = BQ ? b_obs_stack : (SQ ? HOT(obs_stack) : 1);
+        const auto h_priv_stack = BQ ? b_priv_stack : (SQ ? HOT(priv_stack) : 1);
+        const auto h_obs_slack = BQ ? b_obs_slack : (SQ ? HOT(obs_slack) : 0);
+        const auto h_num_obs = BQ ? b_num_obs : (SQ ? HOT(num_obs) : 0);
+        const auto h_num_priv_obs = BQ ? b_num_priv_obs : (SQ ? HOT(num_priv_obs) : 0);
+        // the heightfield profiles: the go2_ee family, tron1_pf_ee
+        const auto h_terrain_curriculum = BQ ? b_terrain_curriculum : (EQ ? HOT(terrain_curriculum) : 0);
+        const auto h_max_terrain_level = BQ ? b_max_terrain_level : (EQ ? HOT(max_terrain_level) : 1);
+        const auto h_terrain_cols_n = BQ ? b_terrain_cols_n : (EQ ? HOT(terrain_cols_n) : 1);
+        const auto h_terrain_env_length = BQ ? b_terrain_env_length : (EQ ? HOT(terrain_env_length) : 0.f);
+        const auto h_episode_length_s = BQ ? b_episode_length_s : (EQ ? HOT(episode_length_s) : 0.f);
+        const auto h_slots_reset_root_xy = BQ ? b_slots_reset_root_xy : (EQ ? HOT(slots.reset_root_xy) : 0);
         const auto h_slots_terrain_level = EQ ? HOT(slots.terrain_level) : 0;
-        const auto h_reset_root_xy_lo = EQ ? HOT(reset_root_xy_lo) : 0.f;
-        const auto h_reset_root_xy_span = EQ ? HOT(reset_root_xy_span) : 0.f;
-        const auto h_custom_origins = EQ ? HOT(custom_origins) : 0;
-        const auto h_heights_offset = EQ ? HOT(heights_offset) : 0.f;
-        const auto h_heights_clip_scale = EQ ? HOT(heights_clip_scale) : 0;
-        const auto h_obs_scale_height = EQ ? HOT(obs_scale_height) : 1.f;
-        const auto h_num_labels = EQ ? HOT(num_labels) : 0;
-        const auto h_foot_clearance_ref = EQ ? HOT(foot_clearance_ref) : 0;
-        const auto h_friction_offset = EQ ? HOT(friction_offset) : 0.f;
-        const auto h_kp_offset = EQ ? HOT(kp_offset) : 0.f;
-        const auto h_kd_offset = EQ ? HOT(kd_offset) : 0.f;
+        const auto h_reset_root_xy_lo = BQ ? b_reset_root_xy_lo : (EQ ? HOT(reset_root_xy_lo) : 0.f);
+        const auto h_reset_root_xy_span = BQ ? b_reset_root_xy_span : (EQ ? HOT(reset_root_xy_span) : 0.f);
+        const auto h_custom_origins = BQ ? b_custom_origins : (EQ ? HOT(custom_origins) : 0);
+        const auto h_heights_offset = BQ ? b_heights_offset : (EQ ? HOT(heights_offset) : 0.f);
+        const auto h_heights_clip_scale = BQ ? b_heights_clip_scale : (EQ ? HOT(heights_clip_scale) : 0);
+        const auto h_obs_scale_height = BQ ? b_obs_scale_height : (EQ ? HOT(obs_scale_height) : 1.f);
+        const auto h_num_labels = BQ ? b_num_labels : (EQ ? HOT(num_labels) : 0);
+        const auto h_foot_clearance_ref = BQ ? b_foot_clearance_ref : (EQ ? HOT(foot_clearance_ref) : 0);
+        const auto h_friction_offset = BQ ? b_friction_offset : (EQ ? HOT(friction_offset) : 0.f);
+        const auto h_kp_offset = BQ ? b_kp_offset : (EQ ? HOT(kp_offset) : 0.f);
+        const auto h_kd_offset = BQ ? b_kd_offset : (EQ ? HOT(kd_offset) : 0.f);
+        // tron1_pf_ee only
+        const auto h_air_time_cmd_dims = BQ ? b_air_time_cmd_dims : 0;
+        const auto h_dr_joint_lo_0 = BQ ? b_dr_joint_lo_0 : 0.f;
+        const auto h_dr_joint_lo_1 = BQ ? b_dr_joint_lo_1 : 0.f;
+        const auto h_dr_joint_lo_2 = BQ ? b_dr_joint_lo_2 : 0.f;
+        const auto h_dr_joint_on = BQ ? b_dr_joint_on : 0;
+        const auto h_dr_joint_span_0 = BQ ? b_dr_joint_span_0 : 0.f;
+        const auto h_dr_joint_span_1 = BQ ? b_dr_joint_span_1 : 0.f;
+        const auto h_dr_joint_span_2 = BQ ? b_dr_joint_span_2 : 0.f;
+        const auto h_foot_distance_threshold = BQ ? b_foot_distance_threshold : 0.f;
+        const auto h_gait_period_fixed = BQ ? b_gait_period_fixed : 1.f;
+        const auto h_noise_act0 = BQ ? b_noise_act0 : 0.f;
+        const auto h_sit_percent = BQ ? b_sit_percent : 0.f;
         asm volatile("" ::: "memory");
         const float cdt = h_control_dt;
         const unsigned rmask = RS ? RS_MASK : (unsigned)p.k.reward_mask;
@@ -1830,15 +1864,21 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
         const unsigned rstep = (unsigned)p.counter;
         const float *const rin = INJ ? B.rand_in + (size_t)e * HOT(slots.n_slots) : nullptr;   // this env's injected uniforms (LgRandSlots)
         auto philox = [&](unsigned c3) { const U4 c = {e_lo, e_hi, rstep, c3}; return philox4x32_10(c, k0, k1); };
+        auto philox_e = [&](unsigned elo, unsigned ehi, unsigned c3) { const U4 c = {elo, ehi, rstep, c3}; return philox4x32_10(c, k0, k1); };
         auto pick = [](const U4 &r, int k) { return k == 0 ? r.x : (k == 1 ? r.y : (k == 2 ? r.z : r.w)); };
         auto anyl = [](bool b) { return __builtin_amdgcn_ballot_w64(b) != 0ull; };
-        auto lane_of_row = [&](int l16) { return (int)((tl_ & 48u) | (unsigned)l16) << 2; };   // byte address for ds_bpermute
-        auto fetch = [&](float v, int l16) { return __int_as_float(__builtin_amdgcn_ds_bpermute(lane_of_row(l16), __float_as_int(v))); };
+        // lane l of this env's 16 (quadruped) / 8 (biped) lanes, to every lane of the env (ds_bpermute)
+        auto fetch = [&](float v, int l) { return __int_as_float(__builtin_amdgcn_ds_bpermute((int)((tl_ & (BQ ? 56u : 48u)) | (unsigned)l) << 2, __float_as_int(v))); };
         auto jsum = [&](float v) { return bc<0>(legsum<LEGS>(sum3(v))); };       // over the env's joints (value in joint lanes), to all lanes
         auto vnorm2 = [&](float v) { return bc<0>(sum3(v * v)); };               // |v|^2 of a component-layout vector, to the quad
+        const bool A_ = !DUO || role == 0, B_ = !DUO || role == 1;               // this wave's share of the tail (wave-uniform)
+        const bool liveB = DUO ? alive && B_ : live, stB = DUO ? liveB && !L.is3 : st, sv = alive && !L.is3;   // B_'s stores
 
+        // a quadruped lane owns the episode sums of terms ei and ei + 16 of its env (es0, es1), a biped lane those of terms ei + 8 k (es[k])
         float cmdv = m_cmd, air = m_air, es0 = m_es0, es1 = m_es1;
-        float o_fric = dr_fric, o_mass = dr_mass, o_com = dr_com, o_kp = dr_kp, o_kd = dr_kd, o_push = w_push;   // what the critic frame shows (go2_wtw)
+        float es[4] = {b_es[0], b_es[1], b_es[2], b_es[3]};
+        float o_fric = dr_fric, o_mass = dr_mass, o_com = dr_com, o_kp = dr_kp, o_kd = dr_kd, o_push = w_push;   // what the critic frame shows
+        float o_jnt = BQ ? L.sel(dr_arm, dr_jf, dr_jd) : 0.f;                    // tron1_pf_ee: per-env joint DR (armature, frictionloss, damping), component c
         int ep_len = m_ep + 1, failb = m_fail, last_contact = m_lc;              // legged_robot.py:60
         const float CRlo = L.is0 ? CR(0) : (L.is1 ? CR(2) : (L.is2 ? CR(4) : CR(6)));
         const float CRhi = L.is0 ? CR(1) : (L.is1 ? CR(3) : (L.is2 ? CR(5) : CR(7)));
@@ -1879,13 +1919,14 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
                 const bool xy = L.c < 2;
                 vw = xy ? vw + pv : vw;
                 o_push = xy ? pv : o_push;
-                if (live && leg == 0 && xy) { B.rand_push_vels[3 * e + L.c] = pv; B.base_lin_vel_w[3 * e + L.c] = vw; }
+                if (liveB && leg == 0 && xy) { B.rand_push_vels[3 * e + L.c] = pv; B.base_lin_vel_w[3 * e + L.c] = vw; }   // DUO: role 1, in program order with its reset stores
             }
         }
         // ---- go2_wtw behaviour parameters (go2_wtw.py:180-218): lane c of every quad evaluates the block that holds draw `slot + c` and
         //      picks it -- gait period, base-height, foot-clearance and pitch targets side by side --, one more call with the
         //      env-independent counter picks the gait (one index per call for the whole batch, as in the reference)
-        float gait_time = w_gt, phi = w_phi, gait_period = w_gp, bh_tgt = w_bh, fc_tgt = w_fc, pitch_tgt = w_pt, theta = w_th, expC = w_ec;
+        // gait clock (go2_wtw, tron1_pf_ee) and go2_wtw's behaviour targets
+        float gait_time = w_gt, phi = w_phi, gait_period = BQ ? h_gait_period_fixed : w_gp, bh_tgt = w_bh, fc_tgt = w_fc, pitch_tgt = w_pt, theta = w_th, expC = w_ec;
         // `u`: lane c holds the uniform of parameter c (gait period, base height, clearance, pitch); `ug`: the gait draw, replicated
         auto behavior_apply = [&](const float u, const float ug, const bool who) {
             const float lo = L.is0 ? CR(8) : (L.is1 ? CR(10) : (L.is2 ? CR(12) : CR(14)));
@@ -1904,7 +1945,6 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
             const float ngp = bc<0>(val), nbh = bc<1>(val), npt = bc<3>(val);
             if (who) { gait_period = ngp; bh_tgt = nbh; fc_tgt = nfc; pitch_tgt = npt; theta = nth; }
         };
-        auto philox_e = [&](unsigned elo, unsigned ehi, unsigned c3) { const U4 c = {elo, ehi, rstep, c3}; return philox4x32_10(c, k0, k1); };
         if constexpr (WQ) {
             const int brs = h_behavior_resample_steps;
             const bool needb = brs > 0 && (ep_len % brs) == 0;                  // go2_wtw.py:258-263
@@ -1931,756 +1971,23 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
         int fail = 0;
 #pragma unroll
         for (int k = 0; k < 4; k++) fail |= (((tmask >> (l0 + k)) & 1u) && n2[k] > 100.0f) ? 1 : 0;
-        fail = __builtin_amdgcn_update_dpp(0, fail, 0x124, 0xF, 0xF, true) | fail;
-        fail = __builtin_amdgcn_update_dpp(0, fail, 0x128, 0xF, 0xF, true) | fail;
+        if constexpr (BQ) fail |= xor4i(fail);                                  // the other leg (lane ^ 4)
+        else {                                                                   // the other legs (row_ror:4, row_ror:8)
+            fail = __builtin_amdgcn_update_dpp(0, fail, 0x124, 0xF, 0xF, true) | fail;
+            fail = __builtin_amdgcn_update_dpp(0, fail, 0x128, 0xF, 0xF, true) | fail;
+        }
         fail |= ((tmask & 1u) && nb2 > 100.0f) ? 1 : 0;
         fail |= pgz > h_max_projected_gravity ? 1 : 0;
         if (guard_bad) failb = LG_FAIL_NONFINITE;   // a re-seated env ends its episode here (lgsim.h)
         failb += fail;
         const bool time_out = (float)ep_len > h_max_episode_length;
         const bool reset = ((float)failb > h_fail_threshold) || time_out;
-
-        // ---- compute_reward (legged_robot.py:150-168): every term replicated over the env's lanes, summed in alphabetical order ----
-        float scl[LG_R_COUNT];
-#pragma unroll
-        for (int k = 0; k < LG_R_COUNT; k++) scl[k] = HOT(reward_scales[k]);
-        float total = 0.f;
-        auto add = [&](int id, float r) {
-            const float rew = r * scl[id];
-            total += rew;
-            if (id < 16) es0 = ei == id ? es0 + rew : es0;
-            else es1 = ei == id - 16 ? es1 + rew : es1;
-        };
-        const float cmd_xy = sqrtf(cmd0 * cmd0 + cmd1 * cmd1);
-        const float cmd_xyz = sqrtf(cmd0 * cmd0 + cmd1 * cmd1 + cmd2 * cmd2);
-        const float dq0 = q - q0;
-        const float fz = bc<2>(f_link[3]);                          // vertical foot force of this leg
-        const float fpz = bc<2>(foot_p), fvx = bc<0>(foot_v), fvy = bc<1>(foot_v), fvz = bc<2>(foot_v);
-        if (RON(LG_R_ACTION_RATE)) { const float d = last_act - act; add(LG_R_ACTION_RATE, jsum(d * d)); }                     // :495-497
-        if (RON(LG_R_ACTION_SMOOTHNESS)) { const float d = act - 2.f * last_act + llast_act; add(LG_R_ACTION_SMOOTHNESS, jsum(d * d)); }   // :499-503
-        if (RON(LG_R_ANG_VEL_XY)) { const float bx = bc<0>(bav), by = bc<1>(bav); add(LG_R_ANG_VEL_XY, bx * bx + by * by); }    // :462-464
-        if (RON(LG_R_BASE_HEIGHT)) { const float d = bc<2>(pos) - h_base_height_target; add(LG_R_BASE_HEIGHT, d * d); }     // :470-476 (plane)
-        if (RON(LG_R_COLLISION)) {                                                                                               // :505-512
-            float sc_ = 0.f;
-#pragma unroll
-            for (int k = 0; k < 4; k++) sc_ += (((pmask >> (l0 + k)) & 1u) && n2[k] > 0.1f * 0.1f) ? 1.f : 0.f;
-            sc_ = legsum<LEGS>(sc_);
-            sc_ += ((pmask & 1u) && nb2 > 0.1f * 0.1f) ? 1.f : 0.f;
-            add(LG_R_COLLISION, sc_);
-        }
-        if (RON(LG_R_DOF_ACC)) { const float d = (qd_start - qd) / cdt; add(LG_R_DOF_ACC, jsum(d * d)); }                       // :490-493
-        if (RON(LG_R_DOF_CLOSE_TO_DEFAULT)) add(LG_R_DOF_CLOSE_TO_DEFAULT, jsum(dq0 * dq0));                                     // :571-573
-        if (RON(LG_R_DOF_POS_LIMITS)) add(LG_R_DOF_POS_LIMITS, jsum(-fminf(q - m_slo, 0.f) + fmaxf(q - m_shi, 0.f)));            // :518-522
-        if (RON(LG_R_DOF_POS_STAND_STILL)) add(LG_R_DOF_POS_STAND_STILL, jsum(dq0 * dq0) * (cmd_xyz < 0.1f ? 1.f : 0.f));        // :561-563
-        if (RON(LG_R_DOF_POWER)) add(LG_R_DOF_POWER, jsum(fabsf(torque * qd)));                                                  // :486-488
-        if (RON(LG_R_DOF_VEL)) add(LG_R_DOF_VEL, jsum(qd * qd));                                                                 // :482-484
-        if (RON(LG_R_DOF_VEL_STAND_STILL)) add(LG_R_DOF_VEL_STAND_STILL, jsum(fabsf(qd)) * (cmd_xyz < 0.1f ? 1.f : 0.f));        // :557-559
-        if (RON(LG_R_FEET_AIR_TIME)) {                                                                                           // :545-555 (stateful)
-            const int contact = fz > 1.0f ? 1 : 0;
-            const int filt = contact | last_contact;
-            last_contact = contact;
-            const float first = (air > 0.f ? 1.f : 0.f) * (float)filt;
-            air += cdt;
-            float r = legsum<LEGS>((air - h_feet_air_time_threshold) * first);
-            r *= cmd_xy > 0.1f ? 1.f : 0.f;
-            air *= filt ? 0.f : 1.f;
-            add(LG_R_FEET_AIR_TIME, r);
-        }
-        if (RON(LG_R_FEET_CONTACT_STAND_STILL)) {                                                                                // :565-569
-            const float cnt = legsum<LEGS>(fz > 0.1f ? 1.f : 0.f);
-            add(LG_R_FEET_CONTACT_STAND_STILL, (cnt == (float)LEGS ? 1.f : 0.f) * (cmd_xyz < 0.1f ? 1.f : 0.f));
-        }
-        if (RON(LG_R_FOOT_ACC)) { const float a = (foot_v - last_foot_v) * (1.f / cdt); add(LG_R_FOOT_ACC, legsum<LEGS>(vnorm2(a))); }    // :605-608
-        if (RON(LG_R_FOOT_CLEARANCE)) {                                                                                          // :575-588
-            const float vxy = sqrtf(fvx * fvx + fvy * fvy);
-            const float d = fpz - (h_foot_clearance_ref == 1 ? f_hmean : (h_foot_clearance_ref == 2 ? f_hmax : 0.f)) - h_foot_clearance_target - h_foot_height_offset;
-            add(LG_R_FOOT_CLEARANCE, __expf(-legsum<LEGS>(vxy * (d * d)) / h_foot_clearance_sigma));
-        }
-        if (RON(LG_R_FOOT_LANDING_VEL)) {                                                                                        // :590-599
-            const bool land = ((fpz - h_foot_height_offset) < h_about_landing_threshold) && !(fz > 0.1f) && (fvz < 0.f);
-            const float vz = land ? fvz : 0.f;
-            add(LG_R_FOOT_LANDING_VEL, legsum<LEGS>(vz * vz));
-        }
-        if (RON(LG_R_HIP_POS)) { const float h = bc<0>(dq0); add(LG_R_HIP_POS, legsum<LEGS>(h * h)); }                           // go2_ee.py:152-159
-        if (RON(LG_R_KEEP_BALANCE)) add(LG_R_KEEP_BALANCE, 1.f);                                                                 // :601-603
-        if (RON(LG_R_LIN_VEL_Z)) { const float z = bc<2>(blv); add(LG_R_LIN_VEL_Z, z * z); }                                     // :458-460
-        if (RON(LG_R_NO_FLY)) add(LG_R_NO_FLY, legsum<LEGS>(fz > 0.1f ? 1.f : 0.f) == 1.f ? 1.f : 0.f);                         // tron1_pf.py:151-154
-        if (RON(LG_R_ORIENTATION)) { const float x = bc<0>(pg), y = bc<1>(pg); add(LG_R_ORIENTATION, x * x + y * y); }           // :466-468
-        if (WQ && RON(LG_R_QUAD_PERIODIC_GAIT)) {                                                                              // go2_wtw.py:377-484 ("step" indicator)
-            const float two_pi = 6.283185307179586f;
-            float ph = phi + theta;
-            ph = (ph - floorf(ph)) * two_pi;
-            const float b_sw = h_b_swing * two_pi;
-            const float c_frc = (ph >= 0.f && ph < b_sw) ? -1.f : 0.f;
-            const float c_spd = (ph >= b_sw && ph < two_pi) ? -1.f : 0.f;
-            expC = c_frc;
-            add(LG_R_QUAD_PERIODIC_GAIT, __expf(legsum<LEGS>(c_spd * sqrtf(vnorm2(foot_v)) + c_frc * sqrtf(n2[3]))));
-        }
-        if (RON(LG_R_TORQUES)) add(LG_R_TORQUES, jsum(torque * torque));                                                         // :478-480
-        if (RON(LG_R_TRACKING_ANG_VEL)) { const float d = cmd2 - bc<2>(bav); add(LG_R_TRACKING_ANG_VEL, __expf(-(d * d) / h_tracking_sigma)); }   // :539-543
-        if (WQ && RON(LG_R_TRACKING_BASE_HEIGHT)) { const float d = bc<2>(pos) - bh_tgt; add(LG_R_TRACKING_BASE_HEIGHT, __expf(-(d * d) / h_base_height_sigma)); }   // go2_wtw.py:495-500
-        if (WQ && RON(LG_R_TRACKING_FOOT_CLEARANCE)) {                                                                           // go2_wtw.py:507-519
-            const float vxy = sqrtf(fvx * fvx + fvy * fvy);
-            const float d = fpz - fc_tgt - h_foot_height_offset;
-            add(LG_R_TRACKING_FOOT_CLEARANCE, __expf(-legsum<LEGS>(vxy * (d * d)) / h_foot_clearance_sigma));
-        }
-        if (RON(LG_R_TRACKING_LIN_VEL)) {                                                                                        // :533-537
-            const float dx = cmd0 - bc<0>(blv), dy = cmd1 - bc<1>(blv);
-            add(LG_R_TRACKING_LIN_VEL, __expf(-(dx * dx + dy * dy) / h_tracking_sigma));
-        }
-        if (WQ && RON(LG_R_TRACKING_ORIENTATION)) {                                                                              // go2_wtw.py:502-505
-            const float ex = bc<0>(eul), dp = bc<1>(eul) - pitch_tgt;
-            add(LG_R_TRACKING_ORIENTATION, __expf(-(ex * ex + dp * dp) / h_euler_sigma));
-        }
-        if (h_only_positive_rewards) total = fmaxf(total, 0.f);                                                               // :161-162
-        if (RON(LG_R_TERMINATION)) add(LG_R_TERMINATION, (reset && !time_out) ? 1.f : 0.f);                                      // :163-168
-        if constexpr (WQ) {   // gait clock (go2_wtw.py:29-36)
-            gait_time += cdt;
-            if (gait_time >= gait_period - cdt / 2.f) gait_time = 0.f;
-            phi = gait_time / gait_period;
-        }
-
-        STAMP(7);
-        // ONE Philox call per step and lane for everything drawn every step or at a reset: the four lanes of a quad evaluate four
-        // different blocks side by side -- lane 0 / 1: the observation-noise blocks 2 leg / 2 leg + 1 of env_step_body, lane 2: the
-        // leg's `_reset_dofs` block, lane 3: the env-level reset block 0x200 + leg.  A launch ends with its slowest wave, and that is
-        // always one with a reset in it: with the reset draws inside the call every wave makes anyway, a reset costs no Philox call
-        // (a call is ~800 cycles of quarter-rate multiplies).
-        U4 rall = {0u, 0u, 0u, 0u};      // (issuing this call under the start-of-kernel load burst paid 0.15 us for go2 until the lane table took the
-        if constexpr (!INJ)               //  registers it was hiding in: +0.3 us since, taken out)
-            rall = philox(L.is0 ? 0x80000000u + (unsigned)(2 * leg) : (L.is1 ? 0x80000000u + (unsigned)(2 * leg) + 1u
-                          : (L.is2 ? 0x40000000u + (unsigned)(h_slots_reset_dof + d0) : 0x80000000u + 0x200u + (unsigned)leg)));
-        const float rux = u01(rall.x), ruy = u01(rall.y), ruz = u01(rall.z), ruw = u01(rall.w);
-        const float ud_p = L.sel(bc<2>(rux), bc<2>(ruy), bc<2>(ruz));                        // element c of lane 2's block
-        const float ud = INJ ? rin[h_slots_reset_dof + d0 + cj] : ud_p;
-        const float rc = L.sel4(bc<3>(rux), bc<3>(ruy), bc<3>(ruz), bc<3>(ruw));             // element c of lane 3's block
-        // ---- reset_idx (legged_robot.py:94-148, go2.py:17-37, 119-134) + simulator.reset_idx (genesis_simulator.py:62-82) ----
-        if (anyl(reset)) {
-            // env-level uniforms (block 0x200 + leg sits in quad `leg`): the element each lane needs is fetched from the quad that
-            // holds it: v0 = (cmd u0 u1 u2 | friction), v1 = (CoM xyz | mass), v2 / v3 = root twist (slots of env_step_body's eu[])
-            float v0 = fetch(rc, L.c), v1 = fetch(rc, 4 + L.c);
-            float v2 = SQ ? fetch(rc, 8 + L.c) : 0.f, v3 = SQ ? fetch(rc, 12 + L.c) : 0.f;   // root twist draws (slots 8-10, 12-14)
-            if constexpr (INJ) {   // the same quantities from their slots of the injected row
-                v0 = L.is3 ? rin[HOT(slots.dr_friction)] : rin[HOT(slots.reset_cmd) + cj];
-                v1 = L.is3 ? rin[HOT(slots.dr_mass)] : rin[HOT(slots.dr_com) + cj];
-                v2 = rin[HOT(slots.reset_lin_vel) + cj]; v3 = rin[HOT(slots.reset_ang_vel) + cj];
-            }
-            // go2_wtw: ONE more call for what only a reset of this task draws -- lane 0 / 1: the leg's kp / kd blocks
-            // (genesis_simulator.py:735-739), lanes 2 / 3 of quads 0 and 1: the four behaviour parameters' draws, lane 2 of quad 2: the
-            // gait draw with the env-independent counter (go2_wtw.py:124-142, 180-218)
-            float nkp = 1.f, nkd = 1.f;
-            if constexpr (WQ) {
-                const int sb = h_slots_task_reset + (leg == 2 ? 4 : 2 * leg + (L.c - 2));    // lanes 2 / 3: behaviour draw index
-                const bool gl = leg == 2;
-                const unsigned c3 = L.is0 ? 0x40000000u + (unsigned)(h_slots_dr_kp + d0)
-                                          : (L.is1 ? 0x40000000u + (unsigned)(h_slots_dr_kd + d0) : (unsigned)(sb >> 2));
-                const bool envc = L.c < 2 || !gl;      // this lane's block is keyed on the env (the gait draw is not)
-                U4 rB = {0u, 0u, 0u, 0u};
-                if constexpr (!INJ) rB = philox_e(envc ? e_lo : 0xFFFFFFFFu, envc ? e_hi : 0xFFFFFFFFu, c3);
-                const float bx = u01(rB.x), by = u01(rB.y), bz = u01(rB.z);
-                const float kpu = L.sel(bc<0>(bx), bc<0>(by), bc<0>(bz)), kdu = L.sel(bc<1>(bx), bc<1>(by), bc<1>(bz));   // element c of lane 0's / lane 1's block
-                nkp = h_dr_kp_span * (INJ ? rin[h_slots_dr_kp + d0 + cj] : kpu) + h_dr_kp_lo;
-                nkd = h_dr_kd_span * (INJ ? rin[h_slots_dr_kd + d0 + cj] : kdu) + h_dr_kd_lo;
-                const float ub = u01(pick(rB, sb & 3));                                            // valid in lanes 2 / 3
-                // parameter c was drawn in lane 2 + (c & 1) of quad c >> 1; the gait draw in lane 2 of quad 2
-                const float ubp = fetch(ub, (L.c < 2 ? 2 : 4) + L.c), ubg = fetch(ub, 10);
-                if constexpr (INJ) behavior_apply(rin[h_slots_task_reset + L.c], rin[h_slots_task_reset + 4], reset);
-                else behavior_apply(ubp, ubg, reset);
-            }
-            // go2_ee: ONE more call likewise -- lane 0 / 1: the leg's kp / kd blocks, lanes 2 / 3 of quad 0: the root xy draws
-            // (legged_robot.py:288), lane 2 of quad 1: the terrain-level draw (legged_robot.py:266-268)
-            float u_xy = 0.5f, u_tl = 0.f;
-            if constexpr (EQ) {
-                const int sb = leg == 0 ? h_slots_reset_root_xy + (L.c - 2) : h_slots_terrain_level;
-                const unsigned c3 = L.is0 ? 0x40000000u + (unsigned)(h_slots_dr_kp + d0)
-                                          : (L.is1 ? 0x40000000u + (unsigned)(h_slots_dr_kd + d0) : (unsigned)(sb >> 2));
-                U4 rB = {0u, 0u, 0u, 0u};
-                if constexpr (!INJ) rB = philox(c3);
-                const float bx = u01(rB.x), by = u01(rB.y), bz = u01(rB.z);
-                const float kpu = L.sel(bc<0>(bx), bc<0>(by), bc<0>(bz)), kdu = L.sel(bc<1>(bx), bc<1>(by), bc<1>(bz));
-                nkp = h_dr_kp_span * (INJ ? rin[h_slots_dr_kp + d0 + cj] : kpu) + h_dr_kp_lo;
-                nkd = h_dr_kd_span * (INJ ? rin[h_slots_dr_kd + d0 + cj] : kdu) + h_dr_kd_lo;
-                const float ub = u01(pick(rB, sb & 3));          // valid in lanes 2 / 3
-                u_xy = fetch(ub, 2 + (L.c & 1));                 // x / y draw for components 0 / 1 (quad 0, lanes 2 / 3)
-                u_tl = fetch(ub, 6);                             // quad 1, lane 2
-                if constexpr (INJ) { u_xy = rin[h_slots_reset_root_xy + (L.c & 1)]; u_tl = rin[h_slots_terrain_level]; }
-            }
-            // terrain curriculum (legged_robot.py:254-272 + genesis_simulator.py:140-148; skipped on the construction-time reset, where
-            // the reference returns early because init_done is False)
-            float norg = origin;
-            int nlvl = w_lvl;
-            if (EQ && h_terrain_curriculum && p.counter > 0) {
-                const float dd = pos - origin;
-                const float dx = bc<0>(dd), dy = bc<1>(dd);
-                const float dist = sqrtf(dx * dx + dy * dy);
-                const bool up = dist > h_terrain_env_length / 2.f;
-                const bool down = (dist < sqrtf(cmd0 * cmd0 + cmd1 * cmd1) * h_episode_length_s * 0.5f) && !up;
-                int lvl = w_lvl + (up ? 1 : 0) - (down ? 1 : 0);
-                if (lvl >= h_max_terrain_level) lvl = min((int)floorf(u_tl * (float)h_max_terrain_level), h_max_terrain_level - 1);
-                else lvl = max(lvl, 0);
-                nlvl = lvl;
-                norg = B.terrain_origins[((size_t)lvl * h_terrain_cols_n + w_type) * 3 + cj];
-            }
-            const float ncmd = resample(cmdv, bc<0>(v0), bc<1>(v0), bc<2>(v0));
-            float ipos = L.sel(h_o_base_init_pos_0, h_o_base_init_pos_1, h_o_base_init_pos_2) + (EQ ? norg : origin);
-            if (EQ && h_custom_origins && L.c < 2) ipos += h_reset_root_xy_span * u_xy + h_reset_root_xy_lo;      // legged_robot.py:288
-            const float iq = L.is3 ? h_base_init_quat_3 : L.sel(h_base_init_quat_0, h_base_init_quat_1, h_base_init_quat_2);
-            // go2.py:131-133 draws U(0, 0) (flat_profile: zero spans); go2_wtw: legged_robot.py:289-292
-            const float nvw = h_reset_lin_vel_span * v2 + h_reset_lin_vel_lo, nww = h_reset_ang_vel_span * v3 + h_reset_ang_vel_lo;
-            // quad broadcasts stay outside the divergent branch
-            const float nfric = bc<3>(h_dr_friction_span * v0 + h_dr_friction_lo), nmass = bc<3>(h_dr_mass_span * v1 + h_dr_mass_lo);
-            const float ncom = L.sel(h_dr_com_span_0, h_dr_com_span_1, h_dr_com_span_2) * v1 + L.sel(h_dr_com_lo_0, h_dr_com_lo_1, h_dr_com_lo_2);
-            if (reset) {
-                if (WQ) { gait_time = 0.f; phi = 0.f; }
-                if (SQ && h_dr_pd_on) { o_kp = nkp; o_kd = nkd; }
-                if (h_dr_friction_on) o_fric = nfric;
-                if (h_dr_mass_on) o_mass = nmass;
-                if (h_dr_com_on) o_com = ncom;
-                cmdv = ncmd;
-                q = q0 + (m_rsp * ud + m_rlo); qd = 0.f;
-                act = 0.f; last_act = 0.f; llast_act = 0.f;
-                pos = ipos; quat = iq; vw = nvw; ww = nww;
-                air = 0.f; ep_len = 0; failb = 0;
-            }
-            // the reference stores the commanded reset twist verbatim in the body-frame properties (genesis_simulator.py:128-129)
-            // and refreshes projected gravity (:125)
-            const QM Rr = quat_rows(L, quat);
-            const float npg = -L.sel(bc<2>(Rr.c0), bc<2>(Rr.c1), bc<2>(Rr.c2));
-            if (reset) { blv = vw; bav = ww; pg = npg; }
-            if (reset && st) {
-                B.dof_pos[ja] = q; B.dof_vel[ja] = 0.f; B.last_dof_vel[ja] = 0.f;
-                B.actions[ja] = 0.f; B.last_actions[ja] = 0.f; B.llast_actions[ja] = 0.f;
-                if (SQ && h_dr_pd_on) { B.kp_scale[ja] = o_kp; B.kd_scale[ja] = o_kd; }
-                if (EQ && h_terrain_curriculum && p.counter > 0 && leg == 0) { B.env_origins[3 * e + cj] = norg; if (L.is0) B.terrain_levels[e] = nlvl; }
-                B.last_feet_vel[(e * F + foot_slot) * 3 + cj] = 0.f;
-                if (leg == 0) {
-                    B.base_pos[3 * e + cj] = pos; B.base_lin_vel_w[3 * e + cj] = vw; B.base_ang_vel_w[3 * e + cj] = ww;
-                    B.base_lin_vel[3 * e + cj] = blv; B.base_ang_vel[3 * e + cj] = bav; B.projected_gravity[3 * e + cj] = pg;
-                    B.last_base_lin_vel[3 * e + cj] = 0.f; B.last_base_ang_vel[3 * e + cj] = 0.f;
-                    if (h_dr_com_on) B.base_com_bias[3 * e + cj] = L.sel(h_dr_com_span_0, h_dr_com_span_1, h_dr_com_span_2) * v1 +
-                                                                       L.sel(h_dr_com_lo_0, h_dr_com_lo_1, h_dr_com_lo_2);
-                }
-            }
-            if (reset && live && leg == 0) {
-                B.base_quat[4 * e + L.c] = quat;
-                if (L.is3) {   // the lane holding the fourth element of blocks 0 / 1: friction and mass draws
-                    if (h_dr_friction_on) B.friction_values[e] = h_dr_friction_span * v0 + h_dr_friction_lo;
-                    if (h_dr_mass_on) B.added_base_mass[e] = h_dr_mass_span * v1 + h_dr_mass_lo;
-                    B.episode_done_step[e] = (int)p.counter;
-                }
-            }
-            if (reset && live) {    // extras["episode"] snapshot (legged_robot.py:128-132), then the sums restart
-                if ((rmask >> ei) & 1u) { B.episode_done_sums[(size_t)ei * N + e] = es0; es0 = 0.f; }
-                if (ei + 16 < LG_R_COUNT && ((rmask >> (ei + 16)) & 1u)) { B.episode_done_sums[(size_t)(ei + 16) * N + e] = es1; es1 = 0.f; }
-            }
-        }
-        STAMP(9);
-        if constexpr (EQ) {
-            // ---- compute_observations + clip, go2_ee.py:10-75: actor frame = go2's 45, stacked 20 deep; critic frame = the frame without
-            //      noise | DR 31 (friction - offset, mass, CoM 3, push 2, kp - offset 12, kd - offset 12) | contact states K | heights P,
-            //      stacked 5 deep; labels = v_b 3 | contact states K | foot height above the local terrain mean F.  Same window / copy /
-            //      blanking bookkeeping as the go2_wtw block below; the env's 16 lanes write consecutive columns, every lane the terrain
-            //      samples it took itself.
-            const float co = h_clip_obs;
-            const bool nz = h_add_noise != 0;
-            const int FR = h_obs_frame, PF = h_priv_frame, ST = h_obs_stack, PST = h_priv_stack, SL = h_obs_slack;
-            const size_t orow = (size_t)(h_num_obs + SL * FR), prow = (size_t)(h_num_priv_obs + SL * PF);
-            const bool two = h_obs_sets > 1;
-            const int cs = two ? p.obs_set : 0, xs = (two && cs < 2) ? 1 - cs : cs;   // the other copy (two sets); with more sets nothing is stacked and xs is unused
-            float *oc = B.obs_buf + ((size_t)cs * N + e) * orow + (size_t)p.obs_win * FR;
-            float *ox = B.obs_buf + ((size_t)xs * N + e) * orow + (size_t)p.obs_win * FR;
-            float *pc = B.priv_obs_buf + ((size_t)cs * N + e) * prow + (size_t)p.obs_win * PF;
-            float *px = B.priv_obs_buf + ((size_t)xs * N + e) * prow + (size_t)p.obs_win * PF;
-            float *lab = B.labels_buf + ((size_t)cs * N + e) * h_num_labels;
-            if (anyl(reset)) {                         // legged_robot_ee.py: the histories of a reset env restart from zeros
-                blank_histories(__builtin_amdgcn_ballot_w64(reset && live && ei == 0), e, B.obs_buf + (size_t)cs * N * orow + (size_t)p.obs_win * FR, orow, (ST - 1) * FR,
-                                B.priv_obs_buf + (size_t)cs * N * prow + (size_t)p.obs_win * PF, prow, (PST - 1) * PF);
-            }
-            if (two && anyl(!reset && w_dirty != 0)) {
-                blank_histories(__builtin_amdgcn_ballot_w64(!reset && w_dirty != 0 && live && ei == 0), e, B.obs_buf + (size_t)cs * N * orow + (size_t)p.obs_win * FR, orow,
-                                (ST - 2) * FR, B.priv_obs_buf + (size_t)cs * N * prow + (size_t)p.obs_win * PF, prow, (PST - 2) * PF);
-            }
-            float *on = oc + (ST - 1) * FR, *on2 = ox + (ST - 1) * FR, *pn = pc + (PST - 1) * PF, *pn2 = px + (PST - 1) * PF;
-            const bool w2o = two && ST > 1, w2p = two && PST > 1;
-            float uq = 0.5f, uqd = 0.5f, ug = 0.5f, ua = 0.5f;
-            if (nz) {
-                const float ux = rux, uy = ruy, uz = ruz, uw = ruw;   // lanes 0 / 1 hold blocks 2 leg / 2 leg + 1 (shared call above)
-                uq = L.sel(bc<0>(ux), bc<0>(uy), bc<0>(uz));
-                uqd = L.sel(bc<1>(ux), bc<1>(uy), bc<1>(uz));
-                ug = fetch(uw, 4 * (cj >> 1) + (cj & 1));
-                ua = fetch(uw, 4 * ((3 + cj) >> 1) + ((3 + cj) & 1));
-                if constexpr (INJ) {   // the frame's entries of the injected row (slots.noise + index in the frame)
-                    const int ns_ = HOT(slots.noise);
-                    uq = rin[ns_ + 9 + d0 + cj]; uqd = rin[ns_ + 9 + A + d0 + cj]; ug = rin[ns_ + 3 + cj]; ua = rin[ns_ + 6 + cj];
-                }
-            }
-            // observation programs (PROF 4): where the noise-free actor frame sits in the critic frame (-1: nowhere), where the "next state"
-            // copy sits in the labels row (-1: none), whether the critic frame is clipped
-            int pfo = 0, nxo = -1;
-            float pclip = co;
-            if constexpr (PQ) {
-                pfo = -1;
-                for (int s_ = 0; s_ < PRG_I(0, 0); s_++) if (PRG_I(0, 2 + s_) == LG_SEG_FRAME) pfo = PRG_I(0, 10 + s_);
-                for (int s_ = 0; s_ < PRG_I(1, 0); s_++) if (PRG_I(1, 2 + s_) == LG_SEG_NEXT_STATE) nxo = PRG_I(1, 10 + s_);
-                pclip = PRG_I(0, 1) ? co : 3.0e38f;
-            }
-            const float ascl = HOT(o_action_scale);
-            auto W = [&](int idx, float v, float u, float ns) {
-                const float nv = clampf(nz ? v + (2.f * u - 1.f) * ns : v, -co, co);
-                on[idx] = nv; if (w2o) on2[idx] = nv;
-                if (pfo >= 0) { const float cl = clampf(v, -pclip, pclip); pn[pfo + idx] = cl; if (w2p) pn2[pfo + idx] = cl; }
-                if (PQ && nxo >= 0) lab[nxo + idx] = idx >= 9 + 2 * A ? v * ascl : v;      // go2_dreamwaq.py:66-74, not clipped
-            };
-            auto WP = [&](int idx, float v) { const float cl = clampf(v, -co, co); pn[idx] = cl; if (w2p) pn2[idx] = cl; };
-            // quad broadcasts outside the divergent branches
-            const float env4 = L.sel4(o_fric - h_friction_offset, o_mass, bc<0>(o_push), bc<1>(o_push));
-            const float pzn = bc<2>(pos);
-            const unsigned smask = m_smask;
-            const int K = __popc(smask);
-            const float csv = (L.sel4(n2[0], n2[1], n2[2], n2[3]) > 1.f) ? 1.f : 0.f;     // contact state of link l0 + c (physics read-back, stale after a reset as in the reference)
-            const int cl_ = l0 + L.c;
-            const bool chas = ((smask >> cl_) & 1u) != 0;
-            const int cidx = __popc(smask & ((1u << cl_) - 1u));
-            // the actor frame (both profiles)
-            if (st) {
-                W(9 + d0 + cj, (q - q0) * h_obs_scale_dof_pos, uq, m_nq);
-                W(9 + A + d0 + cj, qd * h_obs_scale_dof_vel, uqd, m_nqd);
-                W(9 + 2 * A + d0 + cj, act, 0.5f, 0.f);
-                if (leg == 0) {
-                    W(cj, cmdv * (L.is2 ? h_obs_scale_ang_vel : h_obs_scale_lin_vel), 0.5f, 0.f);
-                    W(3 + cj, pg, ug, L.sel(h_noise_lead_0, h_noise_lead_1, h_noise_lead_2));
-                    W(6 + cj, bav * h_obs_scale_ang_vel, ua, L.sel(h_noise_lead_3, h_noise_lead_4, h_noise_lead_5));
-                }
-            }
-            if constexpr (!PQ) {
-            if (st) {
-                WP(FR + 7 + d0 + cj, o_kp - h_kp_offset);
-                WP(FR + 7 + A + d0 + cj, o_kd - h_kd_offset);
-                if (leg == 0) lab[cj] = blv * h_obs_scale_lin_vel;
-                if (leg == 2) WP(FR + 2 + cj, o_com);
-                if (L.is0) lab[3 + K + foot_slot] = clampf(fpz - f_hmean - h_foot_height_offset, -1.f, 1.f);
-            }
-            if (live) {
-                if (leg == 1) WP(FR + (L.c < 2 ? L.c : 3 + L.c), env4);                 // friction, mass | push x, y at FR + 5, 6
-                if (chas) { WP(FR + 7 + 2 * A + cidx, csv); lab[3 + cidx] = csv; }
-                if (leg == 0 && L.is3 && (smask & 1u)) { const float cb = nb2 > 1.f ? 1.f : 0.f; WP(FR + 7 + 2 * A, cb); lab[3] = cb; }
-#pragma unroll
-                for (int i = 0; i < HQ; i++) {
-                    const int k = hk0 + i * kstride;
-                    float hv = pzn - h_heights_offset - hq[i];
-                    if (h_heights_clip_scale) hv = clampf(hv, -1.f, 1.f) * h_obs_scale_height;
-                    if (k < P) WP(FR + 7 + 2 * A + K + k, hv);
-                }
-            }
-            } else {
-                // observation programs (include/lgsim.h LgObsSeg): the critic frame and the auxiliary row are concatenations of blocks; each
-                // block is written by the lanes that hold its values -- joint lanes, component lanes, the lane of a link, the lane that
-                // took a terrain sample
-                const float blvs = blv * h_obs_scale_lin_vel;
-                const float clr = clampf(fpz - f_hmean - h_foot_height_offset, -1.f, 1.f);
-                for (int which = 0; which < 2; which++) {
-                    const bool to_lab = which == 1;
-                    if (to_lab ? h_num_labels <= 0 : h_num_priv_obs <= 0) continue;
-                    const float cl = PRG_I(which, 1) ? co : 3.0e38f;
-                    auto WS = [&](int idx, float v) {
-                        v = clampf(v, -cl, cl);
-                        if (to_lab) lab[idx] = v;
-                        else { pn[idx] = v; if (w2p) pn2[idx] = v; }
-                    };
-                    const int n_segs = PRG_I(which, 0);
-                    for (int s_ = 0; s_ < n_segs; s_++) {
-                        const int kind = PRG_I(which, 2 + s_), off = PRG_I(which, 10 + s_);
-                        const float sc = PRG_F(which, 18 + s_);
-                        if (kind == LG_SEG_DR || kind == LG_SEG_DR_BASE) {
-                            if (st && kind == LG_SEG_DR) { WS(off + 7 + d0 + cj, o_kp - h_kp_offset); WS(off + 7 + A + d0 + cj, o_kd - h_kd_offset); }
-                            if (st && leg == 2) WS(off + 2 + cj, o_com);
-                            if (live && leg == 1) WS(off + (L.c < 2 ? L.c : 3 + L.c), env4);
-                        } else if (kind == LG_SEG_KP || kind == LG_SEG_KD) {
-                            if (st) WS(off + d0 + cj, kind == LG_SEG_KP ? o_kp - h_kp_offset : o_kd - h_kd_offset);
-                        } else if (kind == LG_SEG_BASE_LIN_VEL) {
-                            if (st && leg == 0) WS(off + cj, blvs * sc);
-                        } else if (kind == LG_SEG_CONTACT_STATES) {
-                            if (live && chas) WS(off + cidx, csv);
-                            if (live && leg == 0 && L.is3 && (smask & 1u)) WS(off, nb2 > 1.f ? 1.f : 0.f);
-                        } else if (kind == LG_SEG_HEIGHTS) {
-                            if (live) {
-#pragma unroll
-                                for (int i = 0; i < HQ; i++) {
-                                    const int k = hk0 + i * kstride;
-                                    float hv = pzn - h_heights_offset - hq[i];
-                                    if (h_heights_clip_scale) hv = clampf(hv, -1.f, 1.f) * h_obs_scale_height;
-                                    if (k < P) WS(off + k, hv);
-                                }
-                            }
-                        } else if (kind == LG_SEG_FEET_REL_HEIGHTS || kind == LG_SEG_FEET_HEIGHTS) {
-                            if (live) {   // nine per foot: lane c of the leg's quad writes entries c, c + 4 (and 8)
-#pragma unroll
-                                for (int k = 0; k < 9; k++)
-                                    if ((k & 3) == L.c) WS(off + 9 * foot_slot + k, kind == LG_SEG_FEET_HEIGHTS ? f_h9[k] : clampf(fpz - f_h9[k], -1.f, 1.f));
-                            }
-                        } else if (kind == LG_SEG_FEET_NORMALS) {
-                            if (st) WS(off + 3 * foot_slot + cj, L.sel(f_n3[0], f_n3[1], f_n3[2]));
-                        } else if (kind == LG_SEG_FOOT_CLEARANCE) {
-                            if (live && L.is0) WS(off + foot_slot, clr);
-                        } else if (kind == LG_SEG_LAST_ACTIONS) {
-                            if (st) WS(off + d0 + cj, last_act);
-                        } else if (kind == LG_SEG_FEET_AIR_TIME) {
-                            if (live && L.is0) WS(off + foot_slot, air);
-                        }   // LG_SEG_FRAME / LG_SEG_NEXT_STATE: written entry by entry in W(); LG_SEG_DR_JOINT: excluded by the host check
-                    }
-                }
-            }
-            if (live && leg == 0 && L.is0 && B.obs_dirty) B.obs_dirty[e] = reset ? 1 : 0;
-        } else if constexpr (WQ) {
-            // ---- compute_observations + clip, go2_wtw.py:53-111: actor frame 61 = go2's 45 | clock sin 4, cos 4 | gait period, base-height,
-            //      clearance, pitch targets | theta 4; critic frame 99 = the frame without noise | v_b 3, push 2, mass, friction, CoM 3 |
-            //      kp 12 | kd 12 | exp_C_frc 4.  Five-frame stacks as sliding windows over rows with slack, in `obs_sets` copies: the new
-            //      frame goes to this launch's window in this set and to the same frame index of the other set; an env that resets
-            //      blanks the older frames of its window, one that reset at the previous launch the frames older than that (`dirty`) --
-            //      the same bookkeeping as env_step_body's, with the env's 16 lanes writing consecutive columns.
-            const float co = h_clip_obs;
-            const bool nz = h_add_noise != 0;
-            const int FR = h_obs_frame, PF = h_priv_frame, ST = h_obs_stack, PST = h_priv_stack, SL = h_obs_slack;
-            const size_t orow = (size_t)(h_num_obs + SL * FR), prow = (size_t)(h_num_priv_obs + SL * PF);
-            const bool two = h_obs_sets > 1;
-            const int cs = two ? p.obs_set : 0, xs = (two && cs < 2) ? 1 - cs : cs;   // the other copy (two sets); with more sets nothing is stacked and xs is unused
-            float *oc = B.obs_buf + ((size_t)cs * N + e) * orow + (size_t)p.obs_win * FR;
-            float *ox = B.obs_buf + ((size_t)xs * N + e) * orow + (size_t)p.obs_win * FR;
-            float *pc = B.priv_obs_buf + ((size_t)cs * N + e) * prow + (size_t)p.obs_win * PF;
-            float *px = B.priv_obs_buf + ((size_t)xs * N + e) * prow + (size_t)p.obs_win * PF;
-            if (anyl(reset)) {                         // go2_wtw.py:174-178
-                blank_histories(__builtin_amdgcn_ballot_w64(reset && live && ei == 0), e, B.obs_buf + (size_t)cs * N * orow + (size_t)p.obs_win * FR, orow, (ST - 1) * FR,
-                                B.priv_obs_buf + (size_t)cs * N * prow + (size_t)p.obs_win * PF, prow, (PST - 1) * PF);
-            }
-            if (two && anyl(!reset && w_dirty != 0)) {
-                blank_histories(__builtin_amdgcn_ballot_w64(!reset && w_dirty != 0 && live && ei == 0), e, B.obs_buf + (size_t)cs * N * orow + (size_t)p.obs_win * FR, orow,
-                                (ST - 2) * FR, B.priv_obs_buf + (size_t)cs * N * prow + (size_t)p.obs_win * PF, prow, (PST - 2) * PF);
-            }
-            float *on = oc + (ST - 1) * FR, *on2 = ox + (ST - 1) * FR, *pn = pc + (PST - 1) * PF, *pn2 = px + (PST - 1) * PF;
-            const bool w2o = two && ST > 1, w2p = two && PST > 1;
-            float uq = 0.5f, uqd = 0.5f, ug = 0.5f, ua = 0.5f;
-            if (nz) {   // same blocks as the go2 frame below
-                const float ux = rux, uy = ruy, uz = ruz, uw = ruw;   // lanes 0 / 1 hold blocks 2 leg / 2 leg + 1 (shared call above)
-                uq = L.sel(bc<0>(ux), bc<0>(uy), bc<0>(uz));
-                uqd = L.sel(bc<1>(ux), bc<1>(uy), bc<1>(uz));
-                ug = fetch(uw, 4 * (cj >> 1) + (cj & 1));
-                ua = fetch(uw, 4 * ((3 + cj) >> 1) + ((3 + cj) & 1));
-                if constexpr (INJ) {   // the frame's entries of the injected row (slots.noise + index in the frame)
-                    const int ns_ = HOT(slots.noise);
-                    uq = rin[ns_ + 9 + d0 + cj]; uqd = rin[ns_ + 9 + A + d0 + cj]; ug = rin[ns_ + 3 + cj]; ua = rin[ns_ + 6 + cj];
-                }
-            }
-            // W: an actor-frame entry (noisy into the actor windows, noise-free into the critic frame); WP: a critic-only entry
-            auto W = [&](int idx, float v, float u, float ns) {
-                const float cl = clampf(v, -co, co);
-                const float nv = clampf(nz ? v + (2.f * u - 1.f) * ns : v, -co, co);
-                on[idx] = nv; if (w2o) on2[idx] = nv;
-                pn[idx] = cl; if (w2p) pn2[idx] = cl;
-            };
-            auto WP = [&](int idx, float v) { const float cl = clampf(v, -co, co); pn[idx] = cl; if (w2p) pn2[idx] = cl; };
-            const float ang = 6.283185307179586f * (phi + theta);        // clock inputs (go2_wtw.py:251-256)
-            const float sn = sinf(ang), csn = cosf(ang);
-            if (st) {
-                W(9 + d0 + cj, (q - q0) * h_obs_scale_dof_pos, uq, m_nq);
-                W(9 + A + d0 + cj, qd * h_obs_scale_dof_vel, uqd, m_nqd);
-                W(9 + 2 * A + d0 + cj, act, 0.5f, 0.f);
-                W((L.is0 ? 45 : (L.is1 ? 49 : 57)) + foot_slot, L.sel(sn, csn, theta), 0.5f, 0.f);
-                WP(FR + 10 + d0 + cj, o_kp);
-                WP(FR + 10 + A + d0 + cj, o_kd);
-                if (L.is0) WP(FR + 10 + 2 * A + foot_slot, expC);
-                if (leg == 0) {
-                    W(cj, cmdv * (L.is2 ? h_obs_scale_ang_vel : h_obs_scale_lin_vel), 0.5f, 0.f);
-                    W(3 + cj, pg, ug, L.sel(h_noise_lead_0, h_noise_lead_1, h_noise_lead_2));
-                    W(6 + cj, bav * h_obs_scale_ang_vel, ua, L.sel(h_noise_lead_3, h_noise_lead_4, h_noise_lead_5));
-                    WP(FR + cj, blv * h_obs_scale_lin_vel);
-                }
-                if (leg == 2) WP(FR + 7 + cj, o_com);
-            }
-            const float env4 = L.sel4(bc<0>(o_push), bc<1>(o_push), o_mass, o_fric);   // quad broadcasts outside the divergent branches
-            if (live && leg == 0) W(53 + L.c, L.sel4(gait_period, bh_tgt, fc_tgt, pitch_tgt), 0.5f, 0.f);
-            if (live && leg == 1) WP(FR + 3 + L.c, env4);
-            // task state as the env class exposes it (go2_wtw.py:295-346), the deferred-blanking flag, the second action-history shift
-            // (go2_wtw.py:45-46: afterwards last == llast == a_t)
-            float *ts = B.task_state + (size_t)e * LG_TASK_STATE_WTW;
-            if (st) {
-                ts[(L.is0 ? 6 : (L.is1 ? 10 : 14)) + foot_slot] = L.sel(theta, sn, csn);
-                if (L.is0) ts[18 + foot_slot] = expC;
-                B.llast_actions[ja] = reset ? 0.f : last_act;
-                B.last_actions[ja] = act;
-            }
-            if (live && leg == 0) {
-                ts[L.c] = L.sel4(gait_time, phi, gait_period, bh_tgt);
-                if (L.c < 2) ts[4 + L.c] = L.is0 ? fc_tgt : pitch_tgt;
-                if (L.is0 && B.obs_dirty) B.obs_dirty[e] = reset ? 1 : 0;
-            }
-        } else
-        // ---- compute_observations + clip (go2.py:40-64, legged_robot.py:48-49) ----
-        {
-            const float co = h_clip_obs;
-            const bool nz = h_add_noise != 0;
-            float uq = 0.5f, uqd = 0.5f, ug = 0.5f, ua = 0.5f;
-            if (nz) {
-                // blocks 2 leg and 2 leg + 1 of env_step_body in lanes 0 and 1 of the quad, side by side: (x, y, z) = the three joints'
-                // uniforms (positions / velocities), w = one of the base's six
-                const float ux = rux, uy = ruy, uz = ruz, uw = ruw;   // lanes 0 / 1 hold blocks 2 leg / 2 leg + 1 (shared call above)
-                uq = L.sel(bc<0>(ux), bc<0>(uy), bc<0>(uz));
-                uqd = L.sel(bc<1>(ux), bc<1>(uy), bc<1>(uz));
-                // base uniform k sits in quad k / 2, lane k % 2: gravity component c takes k = c, angular velocity k = 3 + c
-                ug = fetch(uw, 4 * (cj >> 1) + (cj & 1));
-                ua = fetch(uw, 4 * ((3 + cj) >> 1) + ((3 + cj) & 1));
-                if constexpr (INJ) {   // the frame's entries of the injected row (slots.noise + index in the frame)
-                    const int ns_ = HOT(slots.noise);
-                    uq = rin[ns_ + 9 + d0 + cj]; uqd = rin[ns_ + 9 + A + d0 + cj]; ug = rin[ns_ + 3 + cj]; ua = rin[ns_ + 6 + cj];
-                }
-            }
-            float *o = B.obs_buf + ((size_t)(h_obs_sets > 1 ? p.obs_set : 0) * N + e) * (size_t)(9 + 3 * A);
-            auto noisy = [&](float v, float u, float ns) { if (nz) v += (2.f * u - 1.f) * ns; return clampf(v, -co, co); };
-            if (st) {
-                o[9 + d0 + cj] = noisy((q - q0) * h_obs_scale_dof_pos, uq, m_nq);
-                o[9 + A + d0 + cj] = noisy(qd * h_obs_scale_dof_vel, uqd, m_nqd);
-                o[9 + 2 * A + d0 + cj] = clampf(act, -co, co);
-                if (leg == 0) {
-                    const float cs_ = L.is2 ? h_obs_scale_ang_vel : h_obs_scale_lin_vel;
-                    o[cj] = clampf(cmdv * cs_, -co, co);
-                    o[3 + cj] = noisy(pg, ug, L.sel(h_noise_lead_0, h_noise_lead_1, h_noise_lead_2));
-                    o[6 + cj] = noisy(bav * h_obs_scale_ang_vel, ua, L.sel(h_noise_lead_3, h_noise_lead_4, h_noise_lead_5));
-                }
-            }
-        }
-        STAMP(10);
-        // ---- persistent MDP state ----
-        if (live) {
-            // (32-bit byte offsets from wave-uniform bases, as the read-back stores: (term, N) rows stay below 4 GiB, host-checked)
-            const unsigned o_es = 4u * ((unsigned)ei * (unsigned)N + (unsigned)e);
-            if ((rmask >> ei) & 1u) stq(B.episode_sums, o_es, es0);
-            if (ei + 16 < LG_R_COUNT && ((rmask >> (ei + 16)) & 1u)) stq(B.episode_sums, o_es + 64u * (unsigned)N, es1);
-            if (L.is0) { stq(B.feet_air_time, 4u * (unsigned)(e * F + foot_slot), air); stq(B.last_contacts, (unsigned)(e * F + foot_slot), (uint8_t)last_contact); }
-            if (leg == 0) {
-                stq(B.commands, 4u * (unsigned)(4 * e + L.c), cmdv);
-                if (L.is0) {
-                    const unsigned ue = (unsigned)e;
-                    stq(B.episode_length_buf, 4u * ue, (int32_t)ep_len); stq(B.fail_buf, 8u * ue, (int64_t)failb);
-                    stq(B.reset_buf, ue, (uint8_t)(reset ? 1 : 0)); stq(B.time_out_buf, ue, (uint8_t)(time_out ? 1 : 0)); stq(B.rew_buf, 4u * ue, total);
-                }
-            }
-        }
-        STAMP(11);
-    }
-    // ---------------- MDP phases in the same launch, tron1_pf_ee profile: component layout on the env's eight lanes ---------------------
-    // Same statements as env_step_body's POST / RESET phases for LG_OBS_TRON1_EE (legged_robot.py:55-168, 300-348; tron1_pf_ee.py:12-141,
-    // 193-256, 347-463), computed on the registers the physics left behind like the quadruped tails above: per-joint values in joint lanes,
-    // vectors one component per lane, per-env scalars replicated over the env's 8 lanes (lane el = 4 leg + c owns episode sums el + 8 k).
-    // The random stream is env_step_body's (same counters, same words), three Philox calls per lane at most:
-    //   A (every step)  lane c of leg l: observation-noise block 2 l | 2 l + 1 | 2 LEGS + 2 + l (actions) | 3 LEGS + 2 + l (clock)
-    //   B (every step)  lane 0: noise block 2 LEGS (base); lanes 1-6: the env-level reset bundle 0x200 + 0 .. 5; lane 7: the job-wide sit coin
-    //   C (a reset in the wave)  lane c of leg l: `_reset_dofs` | kp | kd blocks of the leg; lane 3 of leg 0: the root xy block
-    if constexpr (BQ) {
-        STAMP(5);
-        const auto h_about_landing_threshold = HOT(about_landing_threshold);
-        const auto h_add_noise = HOT(add_noise);
-        const auto h_air_time_cmd_dims = HOT(air_time_cmd_dims);
-        const auto h_b_swing = HOT(b_swing);
-        const auto h_base_height_sigma = HOT(base_height_sigma);
-        const auto h_base_height_target = HOT(base_height_target);
-        const auto h_base_init_quat_0 = HOT(base_init_quat[0]);
-        const auto h_base_init_quat_1 = HOT(base_init_quat[1]);
-        const auto h_base_init_quat_2 = HOT(base_init_quat[2]);
-        const auto h_base_init_quat_3 = HOT(base_init_quat[3]);
-        const auto h_clip_obs = HOT(clip_obs);
-        const auto h_control_dt = HOT(control_dt);
-        const auto h_custom_origins = HOT(custom_origins);
-        const auto h_dr_com_lo_0 = HOT(dr_com_lo[0]);
-        const auto h_dr_com_lo_1 = HOT(dr_com_lo[1]);
-        const auto h_dr_com_lo_2 = HOT(dr_com_lo[2]);
-        const auto h_dr_com_on = HOT(dr_com_on);
-        const auto h_dr_com_span_0 = HOT(dr_com_span[0]);
-        const auto h_dr_com_span_1 = HOT(dr_com_span[1]);
-        const auto h_dr_com_span_2 = HOT(dr_com_span[2]);
-        const auto h_dr_friction_lo = HOT(dr_friction_lo);
-        const auto h_dr_friction_on = HOT(dr_friction_on);
-        const auto h_dr_friction_span = HOT(dr_friction_span);
-        const auto h_dr_joint_lo_0 = HOT(dr_joint_lo[0]);
-        const auto h_dr_joint_lo_1 = HOT(dr_joint_lo[1]);
-        const auto h_dr_joint_lo_2 = HOT(dr_joint_lo[2]);
-        const auto h_dr_joint_on = HOT(dr_joint_on);
-        const auto h_dr_joint_span_0 = HOT(dr_joint_span[0]);
-        const auto h_dr_joint_span_1 = HOT(dr_joint_span[1]);
-        const auto h_dr_joint_span_2 = HOT(dr_joint_span[2]);
-        const auto h_dr_kd_lo = HOT(dr_kd_lo);
-        const auto h_dr_kd_span = HOT(dr_kd_span);
-        const auto h_dr_kp_lo = HOT(dr_kp_lo);
-        const auto h_dr_kp_span = HOT(dr_kp_span);
-        const auto h_dr_mass_lo = HOT(dr_mass_lo);
-        const auto h_dr_mass_on = HOT(dr_mass_on);
-        const auto h_dr_mass_span = HOT(dr_mass_span);
-        const auto h_dr_pd_on = HOT(dr_pd_on);
-        const auto h_env_id_offset = HOT(env_id_offset);
-        const auto h_episode_length_s = HOT(episode_length_s);
-        const auto h_fail_threshold = HOT(fail_threshold);
-        const auto h_feet_air_time_threshold = HOT(feet_air_time_threshold);
-        const auto h_foot_clearance_ref = HOT(foot_clearance_ref);
-        const auto h_foot_clearance_sigma = HOT(foot_clearance_sigma);
-        const auto h_foot_clearance_target = HOT(foot_clearance_target);
-        const auto h_foot_distance_threshold = HOT(foot_distance_threshold);
-        const auto h_foot_height_offset = HOT(foot_height_offset);
-        const auto h_friction_offset = HOT(friction_offset);
-        const auto h_gait_period_fixed = HOT(gait_period_fixed);
-        const auto h_heading_command = HOT(heading_command);
-        const auto h_heights_clip_scale = HOT(heights_clip_scale);
-        const auto h_heights_offset = HOT(heights_offset);
-        const auto h_kd_offset = HOT(kd_offset);
-        const auto h_kp_offset = HOT(kp_offset);
-        const auto h_max_episode_length = HOT(max_episode_length);
-        const auto h_max_projected_gravity = HOT(max_projected_gravity);
-        const auto h_max_push_vel_xy = HOT(max_push_vel_xy);
-        const auto h_max_terrain_level = HOT(max_terrain_level);
-        const auto h_noise_act0 = HOT(noise_act0);
-        const auto h_noise_lead_0 = HOT(noise_lead[0]);
-        const auto h_noise_lead_1 = HOT(noise_lead[1]);
-        const auto h_noise_lead_2 = HOT(noise_lead[2]);
-        const auto h_noise_lead_3 = HOT(noise_lead[3]);
-        const auto h_noise_lead_4 = HOT(noise_lead[4]);
-        const auto h_noise_lead_5 = HOT(noise_lead[5]);
-        const auto h_num_labels = HOT(num_labels);
-        const auto h_num_obs = HOT(num_obs);
-        const auto h_num_priv_obs = HOT(num_priv_obs);
-        const auto h_o_base_init_pos_0 = HOT(o_base_init_pos[0]);
-        const auto h_o_base_init_pos_1 = HOT(o_base_init_pos[1]);
-        const auto h_o_base_init_pos_2 = HOT(o_base_init_pos[2]);
-        const auto h_obs_frame = HOT(obs_frame);
-        const auto h_obs_scale_ang_vel = HOT(obs_scale_ang_vel);
-        const auto h_obs_scale_dof_pos = HOT(obs_scale_dof_pos);
-        const auto h_obs_scale_dof_vel = HOT(obs_scale_dof_vel);
-        const auto h_obs_scale_height = HOT(obs_scale_height);
-        const auto h_obs_scale_lin_vel = HOT(obs_scale_lin_vel);
-        const auto h_obs_sets = HOT(obs_sets);
-        const auto h_obs_slack = HOT(obs_slack);
-        const auto h_obs_stack = HOT(obs_stack);
-        const auto h_only_positive_rewards = HOT(only_positive_rewards);
-        const auto h_priv_frame = HOT(priv_frame);
-        const auto h_priv_stack = HOT(priv_stack);
-        const auto h_push_interval = HOT(push_interval);
-        const auto h_resample_steps = HOT(resample_steps);
-        const auto h_reset_ang_vel_lo = HOT(reset_ang_vel_lo);
-        const auto h_reset_ang_vel_span = HOT(reset_ang_vel_span);
-        const auto h_reset_lin_vel_lo = HOT(reset_lin_vel_lo);
-        const auto h_reset_lin_vel_span = HOT(reset_lin_vel_span);
-        const auto h_reset_root_xy_lo = HOT(reset_root_xy_lo);
-        const auto h_reset_root_xy_span = HOT(reset_root_xy_span);
-        const auto h_seed = HOT(seed);
-        const auto h_sit_percent = HOT(sit_percent);
-        const auto h_slots_cb_cmd = HOT(slots.cb_cmd);
-        const auto h_slots_dr_kd = HOT(slots.dr_kd);
-        const auto h_slots_dr_kp = HOT(slots.dr_kp);
-        const auto h_slots_push = HOT(slots.push);
-        const auto h_slots_reset_dof = HOT(slots.reset_dof);
-        const auto h_slots_reset_root_xy = HOT(slots.reset_root_xy);
-        const auto h_slots_task_reset = HOT(slots.task_reset);
-        const auto h_terrain_cols_n = HOT(terrain_cols_n);
-        const auto h_terrain_curriculum = HOT(terrain_curriculum);
-        const auto h_terrain_env_length = HOT(terrain_env_length);
-        const auto h_tracking_sigma = HOT(tracking_sigma);
-        const auto h_yaw_clip_0 = HOT(yaw_clip[0]);
-        const auto h_yaw_clip_1 = HOT(yaw_clip[1]);
-        asm volatile("" ::: "memory");
-        const float cdt = h_control_dt;
-        const unsigned rmask = RS ? RS_MASK : (unsigned)p.k.reward_mask;
-        const bool heading = h_heading_command != 0;
-        unsigned k0, k1, e_lo, e_hi;
-        {
-            const unsigned long long seed = h_seed, gid = (unsigned long long)(h_env_id_offset + e);
-            k0 = (unsigned)(seed & 0xFFFFFFFFu); k1 = (unsigned)(seed >> 32);
-            e_lo = (unsigned)(gid & 0xFFFFFFFFu); e_hi = (unsigned)(gid >> 32);
-        }
-        const unsigned rstep = (unsigned)p.counter;
-        const float *const rin = INJ ? B.rand_in + (size_t)e * HOT(slots.n_slots) : nullptr;   // this env's injected uniforms (LgRandSlots)
-        auto philox = [&](unsigned c3) { const U4 c = {e_lo, e_hi, rstep, c3}; return philox4x32_10(c, k0, k1); };
-        auto philox_e = [&](unsigned elo, unsigned ehi, unsigned c3) { const U4 c = {elo, ehi, rstep, c3}; return philox4x32_10(c, k0, k1); };
-        auto pick = [](const U4 &r, int k) { return k == 0 ? r.x : (k == 1 ? r.y : (k == 2 ? r.z : r.w)); };
-        auto anyl = [](bool b) { return __builtin_amdgcn_ballot_w64(b) != 0ull; };
-        // lane l8 (0..7) of this env, to every lane of the env
-        auto fetch8 = [&](float v, int l8) { return __int_as_float(__builtin_amdgcn_ds_bpermute((int)((tl_ & 56u) | (unsigned)l8) << 2, __float_as_int(v))); };
-        auto jsum = [&](float v) { return bc<0>(legsum<LEGS>(sum3(v))); };       // over the env's joints (value in joint lanes), to all lanes
-        auto vnorm2 = [&](float v) { return bc<0>(sum3(v * v)); };               // |v|^2 of a component-layout vector, to the quad
-        const int el = ei;                                                       // lane of the env: 4 leg + c
-        const bool A_ = role == 0, B_ = role == 1;                               // this wave's share of the tail (wave-uniform)
-        const bool liveB = alive && B_, stB = liveB && !L.is3, sv = alive && !L.is3;
-
-        float cmdv = m_cmd, air = m_air;
-        float es[4] = {b_es[0], b_es[1], b_es[2], b_es[3]};
-        float o_fric = dr_fric, o_mass = dr_mass, o_com = dr_com, o_kp = dr_kp, o_kd = dr_kd, o_push = w_push;   // what the critic frame shows
-        float o_jnt = L.sel(dr_arm, dr_jf, dr_jd);                               // per-env joint DR (armature, frictionloss, damping), component c
-        int ep_len = m_ep + 1, failb = m_fail, last_contact = m_lc;              // legged_robot.py:60
-        float gait_time = w_gt, phi = w_phi, theta = w_th, expC = w_ec;
-        const float gait_period = h_gait_period_fixed;
-        const float CRlo = L.is0 ? CR(0) : (L.is1 ? CR(2) : (L.is2 ? CR(4) : CR(6)));
-        const float CRhi = L.is0 ? CR(1) : (L.is1 ? CR(3) : (L.is2 ? CR(5) : CR(7)));
-        auto resample = [&](float cv, float u0, float u1, float u2) {            // legged_robot.py:317-334
-            const float u = L.is0 ? u0 : (L.is1 ? u1 : u2);
-            const bool upd = heading ? !L.is2 : !L.is3;                          // heading mode draws the heading, not the yaw rate
-            cv = upd ? (CRhi - CRlo) * u + CRlo : cv;
-            const float keep = sqrtf(bc<0>(sum3(cv * cv))) > 0.2f ? 1.f : 0.f;
-            return L.is3 ? cv : cv * keep;
-        };
-        // ---- _post_physics_step_callback (legged_robot.py:300-315) ----
-        {
-            const bool need = (ep_len % h_resample_steps) == 0;
-            if (anyl(need)) {
-                float u0, u1, u2;
-                if constexpr (INJ) { u0 = rin[h_slots_cb_cmd]; u1 = rin[h_slots_cb_cmd + 1]; u2 = rin[h_slots_cb_cmd + 2]; }
-                else { const U4 r = philox(0x40000000u + (unsigned)h_slots_cb_cmd); u0 = u01(r.x); u1 = u01(r.y); u2 = u01(r.z); }
-                const float nc = resample(cmdv, u0, u1, u2);
-                cmdv = need ? nc : cmdv;
-            }
-        }
-        if (heading) {   // forward = quat_apply(base_quat, [1,0,0]) (math_utils.py:34-40): t = 2 xyz x b = (0, 2 qz, -2 qy)
-            const float ty = 2.f * qz, tz = -2.f * qy;
-            const float fx = 1.f + (qy * tz - qz * ty), fy = ty * qw + (0.f - qx * tz);
-            const float hd = atan2f(fy, fx);
-            const float c2 = clampf(0.5f * wrap_to_pi(bc<3>(cmdv) - hd), h_yaw_clip_0, h_yaw_clip_1);
-            cmdv = L.is2 ? c2 : cmdv;
-        }
-        {
-            const int pi_ = h_push_interval;
-            if (pi_ > 0 && (p.counter % pi_) == 0) {   // genesis_simulator.py:150-158; lanes 0 / 1 evaluate the two draws' blocks side by side
-                const int slot = h_slots_push + (L.is1 ? 1 : 0);
-                float up;
-                if constexpr (INJ) up = rin[slot];
-                else { const U4 r = philox((unsigned)(slot >> 2)); up = u01(pick(r, slot & 3)); }
-                const float m = h_max_push_vel_xy;
-                const float pv = (m + m) * up - m;
-                const bool xy = L.c < 2;
-                vw = xy ? vw + pv : vw;
-                o_push = xy ? pv : o_push;
-                if (liveB && leg == 0 && xy) { B.rand_push_vels[3 * e + L.c] = pv; B.base_lin_vel_w[3 * e + L.c] = vw; }   // role 1: in program order with its reset stores
-            }
-        }
-        const float cmd0 = bc<0>(cmdv), cmd1 = bc<1>(cmdv), cmd2 = bc<2>(cmdv);
-        STAMP(6);
-        // ---- check_termination (legged_robot.py:78-92) ----
-        const unsigned tmask = m_tmask, pmask = m_pmask;
-        const int l0 = foot_link - 3;
-        float n2[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) n2[k] = vnorm2(f_link[k]);
-        const float nb2 = vnorm2(f_base);
-        const float pgz = bc<2>(pg);
-        int fail = 0;
-#pragma unroll
-        for (int k = 0; k < 4; k++) fail |= (((tmask >> (l0 + k)) & 1u) && n2[k] > 100.0f) ? 1 : 0;
-        fail |= xor4i(fail);                                                     // the other leg (lane ^ 4)
-        fail |= ((tmask & 1u) && nb2 > 100.0f) ? 1 : 0;
-        fail |= pgz > h_max_projected_gravity ? 1 : 0;
-        if (guard_bad) failb = LG_FAIL_NONFINITE;   // a re-seated env ends its episode here (lgsim.h)
-        failb += fail;
-        const bool time_out = (float)ep_len > h_max_episode_length;
-        const bool reset = ((float)failb > h_fail_threshold) || time_out;
-        // terrain curriculum of a resetting env (legged_robot.py:254-272): the level it moves to is known here, except when it has solved
-        // the last one (a random level, drawn below).  The origin of that level is loaded NOW, so that the round trip passes under the
-        // reward terms instead of sitting in the reset block of the wave that ends the launch.
-        const bool curr = h_terrain_curriculum && p.counter > 0;
-        int lvl_pre = w_lvl;
+        // tron1_pf_ee: terrain curriculum of a resetting env (legged_robot.py:254-272): the level it moves to is known here, except when it
+        // has solved the last one (a random level, drawn below).  The origin of that level is loaded NOW, so that the round trip passes
+        // under the reward terms instead of sitting in the reset block of the wave that ends the launch.
+        const bool curr = BQ && h_terrain_curriculum && p.counter > 0;
         float norg_pre = origin;
+        int lvl_pre = w_lvl;
         if (curr && anyl(reset)) {
             const float dd = pos - origin;
             const float dx = bc<0>(dd), dy = bc<1>(dd);
@@ -2699,34 +2006,39 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
         auto add = [&](int id, float r) {            // `id` is a compile-time constant at every call
             const float rew = r * scl[id];
             total += rew;
-            es[id >> 3] = el == (id & 7) ? es[id >> 3] + rew : es[id >> 3];
+            if constexpr (BQ) es[id >> 3] = ei == (id & 7) ? es[id >> 3] + rew : es[id >> 3];
+            else if (id < 16) es0 = ei == id ? es0 + rew : es0;
+            else es1 = ei == id - 16 ? es1 + rew : es1;
         };
         const float cmd_xy = sqrtf(cmd0 * cmd0 + cmd1 * cmd1);
         const float cmd_xyz = sqrtf(cmd0 * cmd0 + cmd1 * cmd1 + cmd2 * cmd2);
         const float dq0 = q - q0;
         const float fz = bc<2>(f_link[3]);                          // vertical foot force of this leg
-        const float fpx = bc<0>(foot_p), fpy = bc<1>(foot_p), fpz = bc<2>(foot_p), fvx = bc<0>(foot_v), fvy = bc<1>(foot_v), fvz = bc<2>(foot_v);
-        // mean over the terrain samples of (base z - height) (legged_robot.py:470-476, tron1_pf_ee.py:435-440): every lane adds its own samples
-        float mean_height = bc<2>(pos);
-        if (P > 0) {
-            const float pzv = bc<2>(pos);
-            float acc = 0.f;
+        const float fpx = BQ ? bc<0>(foot_p) : 0.f, fpy = BQ ? bc<1>(foot_p) : 0.f;
+        const float fpz = bc<2>(foot_p), fvx = bc<0>(foot_v), fvy = bc<1>(foot_v), fvz = bc<2>(foot_v);
+        float mean_height = 0.f;
+        if constexpr (BQ) {   // mean over the terrain samples of (base z - height) (legged_robot.py:470-476, tron1_pf_ee.py:435-440): every lane adds its own samples
+            mean_height = bc<2>(pos);
+            if (P > 0) {
+                const float pzv = bc<2>(pos);
+                float acc = 0.f;
 #pragma unroll
-            for (int i = 0; i < HQ; i++) acc += (hk0 + i * kstride < P) ? pzv - hq[i] : 0.f;
-            mean_height = legsum<LEGS>(sum4(acc)) / (float)P;
-        }
-        if (B_ && RON(LG_R_BIPED_PERIODIC_GAIT)) {   // role 1 writes the critic frame's gait block: the force indicator of the reward term below
-            const float two_pi = 6.283185307179586f;
-            float ph = phi + theta;
-            ph = (ph - floorf(ph)) * two_pi;
-            expC = (ph >= 0.f && ph < h_b_swing * two_pi) ? -1.f : 0.f;
+                for (int i = 0; i < HQ; i++) acc += (hk0 + i * kstride < P) ? pzv - hq[i] : 0.f;
+                mean_height = legsum<LEGS>(sum4(acc)) / (float)P;
+            }
+            if (B_ && RON(LG_R_BIPED_PERIODIC_GAIT)) {   // DUO: role 1 writes the critic frame's gait block: the force indicator of the reward term below
+                const float two_pi = 6.283185307179586f;
+                float ph = phi + theta;
+                ph = (ph - floorf(ph)) * two_pi;
+                expC = (ph >= 0.f && ph < h_b_swing * two_pi) ? -1.f : 0.f;
+            }
         }
         if (A_) {
         if (RON(LG_R_ACTION_RATE)) { const float d = last_act - act; add(LG_R_ACTION_RATE, jsum(d * d)); }                     // :495-497
         if (RON(LG_R_ACTION_SMOOTHNESS)) { const float d = act - 2.f * last_act + llast_act; add(LG_R_ACTION_SMOOTHNESS, jsum(d * d)); }   // :499-503
         if (RON(LG_R_ANG_VEL_XY)) { const float bx = bc<0>(bav), by = bc<1>(bav); add(LG_R_ANG_VEL_XY, bx * bx + by * by); }    // :462-464
-        if (RON(LG_R_BASE_HEIGHT)) { const float d = mean_height - h_base_height_target; add(LG_R_BASE_HEIGHT, d * d); }        // :470-476
-        if (RON(LG_R_BIPED_PERIODIC_GAIT)) {                                                                                     // tron1_pf_ee.py:347-433 ("step" indicator)
+        if (RON(LG_R_BASE_HEIGHT)) { const float d = (BQ ? mean_height : bc<2>(pos)) - h_base_height_target; add(LG_R_BASE_HEIGHT, d * d); }   // :470-476 (plane: base z)
+        if (BQ && RON(LG_R_BIPED_PERIODIC_GAIT)) {                                                                              // tron1_pf_ee.py:347-433 ("step" indicator)
             const float two_pi = 6.283185307179586f;
             float ph = phi + theta;
             ph = (ph - floorf(ph)) * two_pi;
@@ -2758,7 +2070,7 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
             const float first = (air > 0.f ? 1.f : 0.f) * (float)filt;
             air += cdt;
             float r = legsum<LEGS>((air - h_feet_air_time_threshold) * first);
-            r *= (h_air_time_cmd_dims == 3 ? cmd_xyz : cmd_xy) > 0.1f ? 1.f : 0.f;
+            r *= ((BQ && h_air_time_cmd_dims == 3) ? cmd_xyz : cmd_xy) > 0.1f ? 1.f : 0.f;
             air *= filt ? 0.f : 1.f;
             add(LG_R_FEET_AIR_TIME, r);
         }
@@ -2766,7 +2078,7 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
             const float cnt = legsum<LEGS>(fz > 0.1f ? 1.f : 0.f);
             add(LG_R_FEET_CONTACT_STAND_STILL, (cnt == (float)LEGS ? 1.f : 0.f) * (cmd_xyz < 0.1f ? 1.f : 0.f));
         }
-        if (RON(LG_R_FEET_DISTANCE)) {                                                                                           // tron1_pf_ee.py:458-463
+        if (BQ && RON(LG_R_FEET_DISTANCE)) {                                                                                     // tron1_pf_ee.py:458-463
             const float ox = xor4(fpx), oy = xor4(fpy);
             const float dxy = sqrtf((fpx - ox) * (fpx - ox) + (fpy - oy) * (fpy - oy));
             add(LG_R_FEET_DISTANCE, fmaxf(0.f, h_foot_distance_threshold - dxy));
@@ -2785,97 +2097,210 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
         if (RON(LG_R_HIP_POS)) { const float h = bc<0>(dq0); add(LG_R_HIP_POS, legsum<LEGS>(h * h)); }                           // go2_ee.py:152-159
         if (RON(LG_R_KEEP_BALANCE)) add(LG_R_KEEP_BALANCE, 1.f);                                                                 // :601-603
         if (RON(LG_R_LIN_VEL_Z)) { const float z = bc<2>(blv); add(LG_R_LIN_VEL_Z, z * z); }                                     // :458-460
-        if (RON(LG_R_NO_FLY)) add(LG_R_NO_FLY, legsum<LEGS>(fz > kT->no_fly_contact_threshold ? 1.f : 0.f) == 1.f ? 1.f : 0.f);  // tron1_pf.py:151-154
+        if (RON(LG_R_NO_FLY)) add(LG_R_NO_FLY, legsum<LEGS>(fz > (BQ ? kT->no_fly_contact_threshold : 0.1f) ? 1.f : 0.f) == 1.f ? 1.f : 0.f);   // tron1_pf.py:151-154
         if (RON(LG_R_ORIENTATION)) { const float x = bc<0>(pg), y = bc<1>(pg); add(LG_R_ORIENTATION, x * x + y * y); }           // :466-468
+        if (WQ && RON(LG_R_QUAD_PERIODIC_GAIT)) {                                                                              // go2_wtw.py:377-484 ("step" indicator)
+            const float two_pi = 6.283185307179586f;
+            float ph = phi + theta;
+            ph = (ph - floorf(ph)) * two_pi;
+            const float b_sw = h_b_swing * two_pi;
+            const float c_frc = (ph >= 0.f && ph < b_sw) ? -1.f : 0.f;
+            const float c_spd = (ph >= b_sw && ph < two_pi) ? -1.f : 0.f;
+            expC = c_frc;
+            add(LG_R_QUAD_PERIODIC_GAIT, __expf(legsum<LEGS>(c_spd * sqrtf(vnorm2(foot_v)) + c_frc * sqrtf(n2[3]))));
+        }
         if (RON(LG_R_TORQUES)) add(LG_R_TORQUES, jsum(torque * torque));                                                         // :478-480
         if (RON(LG_R_TRACKING_ANG_VEL)) { const float d = cmd2 - bc<2>(bav); add(LG_R_TRACKING_ANG_VEL, __expf(-(d * d) / h_tracking_sigma)); }   // :539-543
-        if (RON(LG_R_TRACKING_BASE_HEIGHT)) { const float d = mean_height - h_base_height_target; add(LG_R_TRACKING_BASE_HEIGHT, __expf(-(d * d) / h_base_height_sigma)); }   // tron1_pf_ee.py:435-440
+        if ((WQ || BQ) && RON(LG_R_TRACKING_BASE_HEIGHT)) {                                              // go2_wtw.py:495-500, tron1_pf_ee.py:435-440
+            const float d = BQ ? mean_height - h_base_height_target : bc<2>(pos) - bh_tgt;
+            add(LG_R_TRACKING_BASE_HEIGHT, __expf(-(d * d) / h_base_height_sigma));
+        }
+        if (WQ && RON(LG_R_TRACKING_FOOT_CLEARANCE)) {                                                                           // go2_wtw.py:507-519
+            const float vxy = sqrtf(fvx * fvx + fvy * fvy);
+            const float d = fpz - fc_tgt - h_foot_height_offset;
+            add(LG_R_TRACKING_FOOT_CLEARANCE, __expf(-legsum<LEGS>(vxy * (d * d)) / h_foot_clearance_sigma));
+        }
         if (RON(LG_R_TRACKING_LIN_VEL)) {                                                                                        // :533-537
             const float dx = cmd0 - bc<0>(blv), dy = cmd1 - bc<1>(blv);
             add(LG_R_TRACKING_LIN_VEL, __expf(-(dx * dx + dy * dy) / h_tracking_sigma));
         }
+        if (WQ && RON(LG_R_TRACKING_ORIENTATION)) {                                                                              // go2_wtw.py:502-505
+            const float ex = bc<0>(eul), dp = bc<1>(eul) - pitch_tgt;
+            add(LG_R_TRACKING_ORIENTATION, __expf(-(ex * ex + dp * dp) / h_euler_sigma));
+        }
         if (h_only_positive_rewards) total = fmaxf(total, 0.f);                                                               // :161-162
         if (RON(LG_R_TERMINATION)) add(LG_R_TERMINATION, (reset && !time_out) ? 1.f : 0.f);                                      // :163-168
         }
-        {   // gait clock (tron1_pf_ee.py:28-35)
+        if constexpr (WQ || BQ) {   // gait clock (go2_wtw.py:29-36, tron1_pf_ee.py:28-35)
             gait_time += cdt;
             if (gait_time >= gait_period - cdt / 2.f) gait_time = 0.f;
             phi = gait_time / gait_period;
         }
 
         STAMP(7);
-        // ---- Philox calls A and B (every step; see the head of this block) ----
+        // The draws of every step and of a reset.  Quadrupeds: ONE Philox call per step and lane, the four lanes of a quad evaluating four
+        // different blocks side by side -- lane 0 / 1: the observation-noise blocks 2 leg / 2 leg + 1 of env_step_body, lane 2: the leg's
+        // `_reset_dofs` block, lane 3: the env-level reset block 0x200 + leg.  A launch ends with its slowest wave, and that is always one
+        // with a reset in it: with the reset draws inside the call every wave makes anyway, a reset costs no Philox call.  (Issuing this call
+        // under the start-of-kernel load burst paid 0.15 us for go2 until the lane table took the registers it was hiding in: +0.3 us
+        // since, taken out.)  tron1_pf_ee: three calls per lane at most --
+        //   A (every step)  lane c of leg l: observation-noise block 2 l | 2 l + 1 | 2 LEGS + 2 + l (actions) | 3 LEGS + 2 + l (clock)
+        //   B (every step)  lane 0: noise block 2 LEGS (base); lanes 1-6: the env-level reset bundle 0x200 + 0 .. 5; lane 7: the job-wide sit coin
+        //   C (a reset in the wave)  lane c of leg l: `_reset_dofs` | kp | kd blocks of the leg; lane 3 of leg 0: the root xy block
         U4 rA = {0u, 0u, 0u, 0u}, rB = rA;
-        const bool coin_lane = el == 7;
         if constexpr (!INJ) {
-            if (A_) rA = philox(0x80000000u + (L.is0 ? (unsigned)(2 * leg) : (L.is1 ? (unsigned)(2 * leg) + 1u     // observation noise: the actor frames are role 0's
-                                               : (L.is2 ? (unsigned)(2 * LEGS + 2 + leg) : (unsigned)(3 * LEGS + 2 + leg)))));
-            rB = philox_e(coin_lane ? 0xFFFFFFFFu : e_lo, coin_lane ? 0xFFFFFFFFu : e_hi,
-                          el == 0 ? 0x80000000u + (unsigned)(2 * LEGS) : (coin_lane ? (unsigned)(h_slots_task_reset >> 2) : 0x80000000u + 0x200u + (unsigned)(el - 1)));
+            if constexpr (BQ) {
+                const bool coin_lane = ei == 7;
+                if (A_) rA = philox(0x80000000u + (L.is0 ? (unsigned)(2 * leg) : (L.is1 ? (unsigned)(2 * leg) + 1u     // observation noise: the actor frames are role 0's
+                                                   : (L.is2 ? (unsigned)(2 * LEGS + 2 + leg) : (unsigned)(3 * LEGS + 2 + leg)))));
+                rB = philox_e(coin_lane ? 0xFFFFFFFFu : e_lo, coin_lane ? 0xFFFFFFFFu : e_hi,
+                              ei == 0 ? 0x80000000u + (unsigned)(2 * LEGS) : (coin_lane ? (unsigned)(h_slots_task_reset >> 2) : 0x80000000u + 0x200u + (unsigned)(ei - 1)));
+            } else
+                rA = philox(L.is0 ? 0x80000000u + (unsigned)(2 * leg) : (L.is1 ? 0x80000000u + (unsigned)(2 * leg) + 1u
+                            : (L.is2 ? 0x40000000u + (unsigned)(h_slots_reset_dof + d0) : 0x80000000u + 0x200u + (unsigned)leg)));
         }
         const float ax = u01(rA.x), ay = u01(rA.y), az = u01(rA.z), aw = u01(rA.w);
         const float bx = u01(rB.x), by = u01(rB.y), bz = u01(rB.z), bw = u01(rB.w);
-        // ---- reset_idx (legged_robot.py:94-148, tron1_pf_ee.py:193-256, 277-310) + simulator.reset_idx (genesis_simulator.py:62-82) ----
+        float ud = 0.f, rc = 0.f;
+        if constexpr (!BQ) {
+            const float ud_p = L.sel(bc<2>(ax), bc<2>(ay), bc<2>(az));                        // element c of lane 2's block
+            ud = INJ ? rin[h_slots_reset_dof + d0 + cj] : ud_p;
+            rc = L.sel4(bc<3>(ax), bc<3>(ay), bc<3>(az), bc<3>(aw));                          // element c of lane 3's block
+        }
+        // ---- reset_idx (legged_robot.py:94-148, go2.py:17-37, 119-134, tron1_pf_ee.py:193-256, 277-310) + simulator.reset_idx
+        //      (genesis_simulator.py:62-82) ----
         if (anyl(reset)) {
-            // element c of the bundle block held by lane `src` of the env (uniform i of the bundle = block i / 4, word i % 4; slots of
-            // env_step_body's eu[]: 0-2 commands, 3 friction, 4-6 CoM, 7 mass, 8-10 root lin vel, 12-14 root ang vel, 16-18 joint
-            // armature / friction / damping, 19-20 gait phase offsets, 21 terrain level)
-            auto bundle_c = [&](int src) { return L.sel4(fetch8(bx, src), fetch8(by, src), fetch8(bz, src), fetch8(bw, src)); };
-            float v0 = bundle_c(1), v1 = bundle_c(2), v2 = bundle_c(3), v3_ = bundle_c(4), v4 = bundle_c(5);
-            float u_gt = fetch8(bx, 6), u_tl = fetch8(by, 6);                                     // uniforms 20, 21
-            float u_coin = fetch8(u01(pick(rB, h_slots_task_reset & 3)), 7);                      // tron1_pf_ee.py:204-210: one coin for the whole job
+            // env-level uniforms: v0 = (cmd u0 u1 u2 | friction), v1 = (CoM xyz | mass), v2 / v3 = root twist (slots of env_step_body's eu[]).
+            // Quadrupeds: block 0x200 + leg sits in quad `leg`, the element each lane needs is fetched from the quad that holds it.
+            // tron1_pf_ee: element c of the bundle block held by lane `src` of the env (uniform i of the bundle = block i / 4, word i % 4;
+            // slots 0-2 commands, 3 friction, 4-6 CoM, 7 mass, 8-10 root lin vel, 12-14 root ang vel, 16-18 joint armature / friction /
+            // damping, 19-20 gait phase offsets, 21 terrain level)
+            auto bundle_c = [&](int src) { return L.sel4(fetch(bx, src), fetch(by, src), fetch(bz, src), fetch(bw, src)); };
+            float v0, v1, v2, v3, v4 = 0.f, u_gt = 0.f, u_tl = 0.f, u_coin = 0.f;
+            if constexpr (BQ) {
+                v0 = bundle_c(1); v1 = bundle_c(2); v2 = bundle_c(3); v3 = bundle_c(4); v4 = bundle_c(5);
+                u_gt = fetch(bx, 6); u_tl = fetch(by, 6);                                         // uniforms 20, 21
+                u_coin = fetch(u01(pick(rB, h_slots_task_reset & 3)), 7);                         // tron1_pf_ee.py:204-210: one coin for the whole job
+            } else {
+                v0 = fetch(rc, L.c); v1 = fetch(rc, 4 + L.c);
+                v2 = SQ ? fetch(rc, 8 + L.c) : 0.f; v3 = SQ ? fetch(rc, 12 + L.c) : 0.f;        // root twist draws (slots 8-10, 12-14)
+            }
             if constexpr (INJ) {   // the same quantities from their slots of the injected row (env_step_body's rs.in paths)
                 v0 = L.is3 ? rin[HOT(slots.dr_friction)] : rin[HOT(slots.reset_cmd) + cj];
                 v1 = L.is3 ? rin[HOT(slots.dr_mass)] : rin[HOT(slots.dr_com) + cj];
-                v2 = rin[HOT(slots.reset_lin_vel) + cj]; v3_ = rin[HOT(slots.reset_ang_vel) + cj];
-                v4 = L.is3 ? rin[h_slots_task_reset + 1] : rin[HOT(slots.dr_joint) + cj];
-                u_gt = rin[h_slots_task_reset + 2]; u_tl = rin[HOT(slots.terrain_level)]; u_coin = rin[h_slots_task_reset];
+                v2 = rin[HOT(slots.reset_lin_vel) + cj]; v3 = rin[HOT(slots.reset_ang_vel) + cj];
+                if constexpr (BQ) {
+                    v4 = L.is3 ? rin[h_slots_task_reset + 1] : rin[HOT(slots.dr_joint) + cj];
+                    u_gt = rin[h_slots_task_reset + 2]; u_tl = rin[HOT(slots.terrain_level)]; u_coin = rin[h_slots_task_reset];
+                }
             }
-            // call C: lane 0 / 1 / 2 of the quad: the leg's `_reset_dofs` / kp / kd blocks, lane 3 of leg 0: the root xy block
-            const int sxy = h_slots_reset_root_xy;
-            U4 rC = {0u, 0u, 0u, 0u};
-            if constexpr (!INJ) rC = philox(L.is0 ? 0x40000000u + (unsigned)(h_slots_reset_dof + d0) : (L.is1 ? 0x40000000u + (unsigned)(h_slots_dr_kp + d0)
-                                            : (L.is2 ? 0x40000000u + (unsigned)(h_slots_dr_kd + d0) : (unsigned)(sxy >> 2))));
-            const float cx_ = u01(rC.x), cy_ = u01(rC.y), cz_ = u01(rC.z);
-            const float ud_p = L.sel(bc<0>(cx_), bc<0>(cy_), bc<0>(cz_)), kp_p = L.sel(bc<1>(cx_), bc<1>(cy_), bc<1>(cz_)), kd_p = L.sel(bc<2>(cx_), bc<2>(cy_), bc<2>(cz_));
-            const float ud = INJ ? rin[h_slots_reset_dof + d0 + cj] : ud_p;                       // element c of lane 0's block
-            const float nkp = h_dr_kp_span * (INJ ? rin[h_slots_dr_kp + d0 + cj] : kp_p) + h_dr_kp_lo;
-            const float nkd = h_dr_kd_span * (INJ ? rin[h_slots_dr_kd + d0 + cj] : kd_p) + h_dr_kd_lo;
-            const float pxy0 = u01(pick(rC, sxy & 3)), pxy1 = u01(pick(rC, (sxy + 1) & 3));      // valid in lane 3 of leg 0
-            const float u_x = fetch8(pxy0, 3), u_y = fetch8(pxy1, 3);
-            const float u_xy = INJ ? rin[sxy + (L.c & 1)] : (L.is0 ? u_x : u_y);
-            const bool sit = h_sit_percent > 0.f && u_coin < h_sit_percent;
-            // terrain curriculum (legged_robot.py:254-272 + genesis_simulator.py:140-148; skipped on the construction-time reset)
+            float nkp = 1.f, nkd = 1.f, u_xy = 0.5f;
+            // go2_wtw: ONE more call for what only a reset of this task draws -- lane 0 / 1: the leg's kp / kd blocks
+            // (genesis_simulator.py:735-739), lanes 2 / 3 of quads 0 and 1: the four behaviour parameters' draws, lane 2 of quad 2: the
+            // gait draw with the env-independent counter (go2_wtw.py:124-142, 180-218)
+            if constexpr (WQ) {
+                const int sb = h_slots_task_reset + (leg == 2 ? 4 : 2 * leg + (L.c - 2));    // lanes 2 / 3: behaviour draw index
+                const bool gl = leg == 2;
+                const unsigned c3 = L.is0 ? 0x40000000u + (unsigned)(h_slots_dr_kp + d0)
+                                          : (L.is1 ? 0x40000000u + (unsigned)(h_slots_dr_kd + d0) : (unsigned)(sb >> 2));
+                const bool envc = L.c < 2 || !gl;      // this lane's block is keyed on the env (the gait draw is not)
+                U4 rW = {0u, 0u, 0u, 0u};
+                if constexpr (!INJ) rW = philox_e(envc ? e_lo : 0xFFFFFFFFu, envc ? e_hi : 0xFFFFFFFFu, c3);
+                const float wx = u01(rW.x), wy = u01(rW.y), wz = u01(rW.z);
+                const float kpu = L.sel(bc<0>(wx), bc<0>(wy), bc<0>(wz)), kdu = L.sel(bc<1>(wx), bc<1>(wy), bc<1>(wz));   // element c of lane 0's / lane 1's block
+                nkp = h_dr_kp_span * (INJ ? rin[h_slots_dr_kp + d0 + cj] : kpu) + h_dr_kp_lo;
+                nkd = h_dr_kd_span * (INJ ? rin[h_slots_dr_kd + d0 + cj] : kdu) + h_dr_kd_lo;
+                const float ub = u01(pick(rW, sb & 3));                                            // valid in lanes 2 / 3
+                // parameter c was drawn in lane 2 + (c & 1) of quad c >> 1; the gait draw in lane 2 of quad 2
+                const float ubp = fetch(ub, (L.c < 2 ? 2 : 4) + L.c), ubg = fetch(ub, 10);
+                if constexpr (INJ) behavior_apply(rin[h_slots_task_reset + L.c], rin[h_slots_task_reset + 4], reset);
+                else behavior_apply(ubp, ubg, reset);
+            }
+            // go2_ee: ONE more call likewise -- lane 0 / 1: the leg's kp / kd blocks, lanes 2 / 3 of quad 0: the root xy draws
+            // (legged_robot.py:288), lane 2 of quad 1: the terrain-level draw (legged_robot.py:266-268)
+            if constexpr (EQ) {
+                const int sb = leg == 0 ? h_slots_reset_root_xy + (L.c - 2) : h_slots_terrain_level;
+                const unsigned c3 = L.is0 ? 0x40000000u + (unsigned)(h_slots_dr_kp + d0)
+                                          : (L.is1 ? 0x40000000u + (unsigned)(h_slots_dr_kd + d0) : (unsigned)(sb >> 2));
+                U4 rE = {0u, 0u, 0u, 0u};
+                if constexpr (!INJ) rE = philox(c3);
+                const float ex = u01(rE.x), ey = u01(rE.y), ez = u01(rE.z);
+                const float kpu = L.sel(bc<0>(ex), bc<0>(ey), bc<0>(ez)), kdu = L.sel(bc<1>(ex), bc<1>(ey), bc<1>(ez));
+                nkp = h_dr_kp_span * (INJ ? rin[h_slots_dr_kp + d0 + cj] : kpu) + h_dr_kp_lo;
+                nkd = h_dr_kd_span * (INJ ? rin[h_slots_dr_kd + d0 + cj] : kdu) + h_dr_kd_lo;
+                const float ub = u01(pick(rE, sb & 3));          // valid in lanes 2 / 3
+                u_xy = fetch(ub, 2 + (L.c & 1));                 // x / y draw for components 0 / 1 (quad 0, lanes 2 / 3)
+                u_tl = fetch(ub, 6);                             // quad 1, lane 2
+                if constexpr (INJ) { u_xy = rin[h_slots_reset_root_xy + (L.c & 1)]; u_tl = rin[h_slots_terrain_level]; }
+            }
+            // tron1_pf_ee: call C -- lane 0 / 1 / 2 of the quad: the leg's `_reset_dofs` / kp / kd blocks, lane 3 of leg 0: the root xy block
+            if constexpr (BQ) {
+                const int sxy = h_slots_reset_root_xy;
+                U4 rC = {0u, 0u, 0u, 0u};
+                if constexpr (!INJ) rC = philox(L.is0 ? 0x40000000u + (unsigned)(h_slots_reset_dof + d0) : (L.is1 ? 0x40000000u + (unsigned)(h_slots_dr_kp + d0)
+                                                : (L.is2 ? 0x40000000u + (unsigned)(h_slots_dr_kd + d0) : (unsigned)(sxy >> 2))));
+                const float cx_ = u01(rC.x), cy_ = u01(rC.y), cz_ = u01(rC.z);
+                const float ud_p = L.sel(bc<0>(cx_), bc<0>(cy_), bc<0>(cz_)), kp_p = L.sel(bc<1>(cx_), bc<1>(cy_), bc<1>(cz_)), kd_p = L.sel(bc<2>(cx_), bc<2>(cy_), bc<2>(cz_));
+                ud = INJ ? rin[h_slots_reset_dof + d0 + cj] : ud_p;                               // element c of lane 0's block
+                nkp = h_dr_kp_span * (INJ ? rin[h_slots_dr_kp + d0 + cj] : kp_p) + h_dr_kp_lo;
+                nkd = h_dr_kd_span * (INJ ? rin[h_slots_dr_kd + d0 + cj] : kd_p) + h_dr_kd_lo;
+                const float pxy0 = u01(pick(rC, sxy & 3)), pxy1 = u01(pick(rC, (sxy + 1) & 3));  // valid in lane 3 of leg 0
+                const float u_x = fetch(pxy0, 3), u_y = fetch(pxy1, 3);
+                u_xy = INJ ? rin[sxy + (L.c & 1)] : (L.is0 ? u_x : u_y);
+            }
+            const bool sit = BQ && h_sit_percent > 0.f && u_coin < h_sit_percent;               // tron1_pf_ee: the sit pose
+            // terrain curriculum (legged_robot.py:254-272 + genesis_simulator.py:140-148; skipped on the construction-time reset, where
+            // the reference returns early because init_done is False)
             float norg = origin;
             int nlvl = w_lvl;
-            if (curr) {
-                int lvl = lvl_pre;
-                norg = norg_pre;
-                if (lvl >= h_max_terrain_level) {      // solved the last level: a random one (rare), its origin loaded here
-                    lvl = min((int)floorf(u_tl * (float)h_max_terrain_level), h_max_terrain_level - 1);
-                    norg = B.terrain_origins[((size_t)lvl * h_terrain_cols_n + w_type) * 3 + cj];
-                } else lvl = max(lvl, 0);
+            if constexpr (BQ) {
+                if (curr) {
+                    int lvl = lvl_pre;
+                    norg = norg_pre;
+                    if (lvl >= h_max_terrain_level) {      // solved the last level: a random one (rare), its origin loaded here
+                        lvl = min((int)floorf(u_tl * (float)h_max_terrain_level), h_max_terrain_level - 1);
+                        norg = B.terrain_origins[((size_t)lvl * h_terrain_cols_n + w_type) * 3 + cj];
+                    } else lvl = max(lvl, 0);
+                    nlvl = lvl;
+                }
+            } else if (EQ && h_terrain_curriculum && p.counter > 0) {
+                const float dd = pos - origin;
+                const float dx = bc<0>(dd), dy = bc<1>(dd);
+                const float dist = sqrtf(dx * dx + dy * dy);
+                const bool up = dist > h_terrain_env_length / 2.f;
+                const bool down = (dist < sqrtf(cmd0 * cmd0 + cmd1 * cmd1) * h_episode_length_s * 0.5f) && !up;
+                int lvl = w_lvl + (up ? 1 : 0) - (down ? 1 : 0);
+                if (lvl >= h_max_terrain_level) lvl = min((int)floorf(u_tl * (float)h_max_terrain_level), h_max_terrain_level - 1);
+                else lvl = max(lvl, 0);
                 nlvl = lvl;
+                norg = B.terrain_origins[((size_t)lvl * h_terrain_cols_n + w_type) * 3 + cj];
             }
             const float ncmd = resample(cmdv, bc<0>(v0), bc<1>(v0), bc<2>(v0));
-            float ipos = (sit ? b_sitp : L.sel(h_o_base_init_pos_0, h_o_base_init_pos_1, h_o_base_init_pos_2)) + norg;
-            if (h_custom_origins && L.c < 2) ipos += h_reset_root_xy_span * u_xy + h_reset_root_xy_lo;          // legged_robot.py:288
+            float ipos = (sit ? b_sitp : L.sel(h_o_base_init_pos_0, h_o_base_init_pos_1, h_o_base_init_pos_2)) + ((EQ || BQ) ? norg : origin);
+            if ((EQ || BQ) && h_custom_origins && L.c < 2) ipos += h_reset_root_xy_span * u_xy + h_reset_root_xy_lo;      // legged_robot.py:288
             const float iq = sit ? b_sitr : (L.is3 ? h_base_init_quat_3 : L.sel(h_base_init_quat_0, h_base_init_quat_1, h_base_init_quat_2));
-            const float nvw = sit ? 0.f : h_reset_lin_vel_span * v2 + h_reset_lin_vel_lo;                        // legged_robot.py:289-292; tron1_pf_ee.py:304-309
-            const float nww = sit ? 0.f : h_reset_ang_vel_span * v3_ + h_reset_ang_vel_lo;
-            // quad broadcasts stay outside the divergent branch
-            const float nfric = h_dr_friction_span * bc<3>(v0) + h_dr_friction_lo, nmass = h_dr_mass_span * bc<3>(v1) + h_dr_mass_lo;
+            // go2.py:131-133 draws U(0, 0) (flat_profile: zero spans); legged_robot.py:289-292; tron1_pf_ee.py:304-309
+            const float nvw = sit ? 0.f : h_reset_lin_vel_span * v2 + h_reset_lin_vel_lo;
+            const float nww = sit ? 0.f : h_reset_ang_vel_span * v3 + h_reset_ang_vel_lo;
+            // quad broadcasts stay outside the divergent branch (the two forms give the same values; each profile keeps the one its
+            // kernel was tuned with, as it does for the friction / mass / CoM stores below)
+            const float nfric = BQ ? h_dr_friction_span * bc<3>(v0) + h_dr_friction_lo : bc<3>(h_dr_friction_span * v0 + h_dr_friction_lo);
+            const float nmass = BQ ? h_dr_mass_span * bc<3>(v1) + h_dr_mass_lo : bc<3>(h_dr_mass_span * v1 + h_dr_mass_lo);
             const float ncom = L.sel(h_dr_com_span_0, h_dr_com_span_1, h_dr_com_span_2) * v1 + L.sel(h_dr_com_lo_0, h_dr_com_lo_1, h_dr_com_lo_2);
-            const float njnt = L.sel(h_dr_joint_span_0, h_dr_joint_span_1, h_dr_joint_span_2) * v4 + L.sel(h_dr_joint_lo_0, h_dr_joint_lo_1, h_dr_joint_lo_2);
-            const float th0 = b_th0 + bc<3>(v4);                                                                  // tron1_pf_ee.py:220-226
-            const float ntheta = foot_slot == 0 ? th0 : th0 + (b_th1 - b_th0);
+            float njnt = 0.f, ntheta = 0.f;
+            if constexpr (BQ) {
+                njnt = L.sel(h_dr_joint_span_0, h_dr_joint_span_1, h_dr_joint_span_2) * v4 + L.sel(h_dr_joint_lo_0, h_dr_joint_lo_1, h_dr_joint_lo_2);
+                const float th0 = b_th0 + bc<3>(v4);                                                              // tron1_pf_ee.py:220-226
+                ntheta = foot_slot == 0 ? th0 : th0 + (b_th1 - b_th0);
+            }
             if (reset) {
-                theta = ntheta; gait_time = u_gt * gait_period; phi = gait_time / gait_period;
-                if (h_dr_pd_on) { o_kp = nkp; o_kd = nkd; }
+                if (WQ) { gait_time = 0.f; phi = 0.f; }
+                if (BQ) { theta = ntheta; gait_time = u_gt * gait_period; phi = gait_time / gait_period; }
+                if ((SQ || BQ) && h_dr_pd_on) { o_kp = nkp; o_kd = nkd; }
                 if (h_dr_friction_on) o_fric = nfric;
                 if (h_dr_mass_on) o_mass = nmass;
                 if (h_dr_com_on) o_com = ncom;
-                if (h_dr_joint_on && B.joint_armature) o_jnt = njnt;
+                if (BQ && h_dr_joint_on && B.joint_armature) o_jnt = njnt;
                 cmdv = ncmd;
                 q = sit ? b_sitq : q0 + (m_rsp * ud + m_rlo); qd = 0.f;
                 act = 0.f; last_act = 0.f; llast_act = 0.f;
@@ -2890,40 +2315,47 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
             if (reset && stB) {
                 B.dof_pos[ja] = q; B.dof_vel[ja] = 0.f; B.last_dof_vel[ja] = 0.f;
                 B.actions[ja] = 0.f; B.last_actions[ja] = 0.f; B.llast_actions[ja] = 0.f;
-                if (h_dr_pd_on) { B.kp_scale[ja] = o_kp; B.kd_scale[ja] = o_kd; }
+                if ((SQ || BQ) && h_dr_pd_on) { B.kp_scale[ja] = o_kp; B.kd_scale[ja] = o_kd; }
+                if (EQ && h_terrain_curriculum && p.counter > 0 && leg == 0) { B.env_origins[3 * e + cj] = norg; if (L.is0) B.terrain_levels[e] = nlvl; }
                 B.last_feet_vel[(e * F + foot_slot) * 3 + cj] = 0.f;
                 if (leg == 0) {
                     if (curr) { B.env_origins[3 * e + cj] = norg; if (L.is0) B.terrain_levels[e] = nlvl; }
                     B.base_pos[3 * e + cj] = pos; B.base_lin_vel_w[3 * e + cj] = vw; B.base_ang_vel_w[3 * e + cj] = ww;
                     B.base_lin_vel[3 * e + cj] = blv; B.base_ang_vel[3 * e + cj] = bav; B.projected_gravity[3 * e + cj] = pg;
                     B.last_base_lin_vel[3 * e + cj] = 0.f; B.last_base_ang_vel[3 * e + cj] = 0.f;
-                    if (h_dr_com_on) B.base_com_bias[3 * e + cj] = o_com;
+                    if (h_dr_com_on) B.base_com_bias[3 * e + cj] = BQ ? o_com : L.sel(h_dr_com_span_0, h_dr_com_span_1, h_dr_com_span_2) * v1 +
+                                                                            L.sel(h_dr_com_lo_0, h_dr_com_lo_1, h_dr_com_lo_2);
                 }
-                if (leg == 1 && h_dr_joint_on && B.joint_armature) {   // genesis_simulator.py:704-733: one value per env each
+                if (BQ && leg == 1 && h_dr_joint_on && B.joint_armature) {   // genesis_simulator.py:704-733: one value per env each
                     float *jp = L.is0 ? B.joint_armature : (L.is1 ? B.joint_friction : B.joint_damping);
                     jp[e] = o_jnt;
                 }
             }
             if (reset && liveB && leg == 0) {
                 B.base_quat[4 * e + L.c] = quat;
-                if (L.is3) {
-                    if (h_dr_friction_on) B.friction_values[e] = o_fric;
-                    if (h_dr_mass_on) B.added_base_mass[e] = o_mass;
+                if (L.is3) {   // the lane holding the fourth element of blocks 0 / 1: friction and mass draws
+                    if (h_dr_friction_on) B.friction_values[e] = BQ ? o_fric : h_dr_friction_span * v0 + h_dr_friction_lo;
+                    if (h_dr_mass_on) B.added_base_mass[e] = BQ ? o_mass : h_dr_mass_span * v1 + h_dr_mass_lo;
                     B.episode_done_step[e] = (int)p.counter;
                 }
             }
             if (reset && live) {    // extras["episode"] snapshot (legged_robot.py:128-132), then the sums restart
+                if constexpr (BQ) {
 #pragma unroll
-                for (int k = 0; k < 4; k++)
-                    if (el + 8 * k < LG_R_COUNT && ((rmask >> (el + 8 * k)) & 1u)) { B.episode_done_sums[(size_t)(el + 8 * k) * N + e] = es[k]; es[k] = 0.f; }
+                    for (int k = 0; k < 4; k++)
+                        if (ei + 8 * k < LG_R_COUNT && ((rmask >> (ei + 8 * k)) & 1u)) { B.episode_done_sums[(size_t)(ei + 8 * k) * N + e] = es[k]; es[k] = 0.f; }
+                } else {
+                    if ((rmask >> ei) & 1u) { B.episode_done_sums[(size_t)ei * N + e] = es0; es0 = 0.f; }
+                    if (ei + 16 < LG_R_COUNT && ((rmask >> (ei + 16)) & 1u)) { B.episode_done_sums[(size_t)(ei + 16) * N + e] = es1; es1 = 0.f; }
+                }
             }
         }
         STAMP(9);
-        {
+        if constexpr (BQ) {
             // ---- compute_observations + clip, tron1_pf_ee.py:53-141.  actor frame: 9 + 3 A + clock 2 F, stacked 10 deep; critic frame: the
             //      frame without noise | DR (7 + 2 A + 3) | gait F | contact states K | heights P | normals 3 F | clip(foot_z - h9) 9 F,
             //      stacked 10 deep; labels: v_b 3 | K | foot height above the local terrain max F | normals 3 F.  Same window / copy /
-            //      blanking bookkeeping as the quadruped tails; the env's 8 lanes write consecutive columns.
+            //      blanking bookkeeping as the quadruped frames below; the env's 8 lanes write consecutive columns.
             const float co = h_clip_obs;
             const bool nz = h_add_noise != 0;
             const int FR = h_obs_frame, PF = h_priv_frame, ST = h_obs_stack, PST = h_priv_stack, SL = h_obs_slack;
@@ -2942,11 +2374,11 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
             auto SO = [](float *base, unsigned off, float v) { *reinterpret_cast<float *>(reinterpret_cast<char *>(base) + off) = v; };
             // role 0 blanks the actor rows, role 1 the (four times longer) critic rows
             if (anyl(reset)) {                         // legged_robot_ee.py: the histories of a reset env restart from zeros
-                blank_histories(__builtin_amdgcn_ballot_w64(reset && alive && el == 0), e, B.obs_buf + (size_t)cs * N * orow + (size_t)p.obs_win * FR, orow,
+                blank_histories(__builtin_amdgcn_ballot_w64(reset && alive && ei == 0), e, B.obs_buf + (size_t)cs * N * orow + (size_t)p.obs_win * FR, orow,
                                 A_ ? (ST - 1) * FR : 0, B.priv_obs_buf + (size_t)cs * N * prow + (size_t)p.obs_win * PF, prow, B_ ? (PST - 1) * PF : 0);
             }
             if (two && anyl(!reset && w_dirty != 0)) {
-                blank_histories(__builtin_amdgcn_ballot_w64(!reset && w_dirty != 0 && alive && el == 0), e, B.obs_buf + (size_t)cs * N * orow + (size_t)p.obs_win * FR, orow,
+                blank_histories(__builtin_amdgcn_ballot_w64(!reset && w_dirty != 0 && alive && ei == 0), e, B.obs_buf + (size_t)cs * N * orow + (size_t)p.obs_win * FR, orow,
                                 A_ ? (ST - 2) * FR : 0, B.priv_obs_buf + (size_t)cs * N * prow + (size_t)p.obs_win * PF, prow, B_ ? (PST - 2) * PF : 0);
             }
             const bool w2o = two && ST > 1, w2p = two && PST > 1;
@@ -2955,8 +2387,8 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
                 uq = L.sel(bc<0>(ax), bc<0>(ay), bc<0>(az));                 // block 2 leg in lane 0 of the quad: the three joints' uniforms
                 uqd = L.sel(bc<1>(ax), bc<1>(ay), bc<1>(az));                // block 2 leg + 1 in lane 1
                 // base uniforms (env_step_body's ub[]): 0 / 1 = fourth words of leg 0's two blocks, 2-5 = block 2 LEGS (call B, lane 0)
-                ug = L.sel(fetch8(aw, 0), fetch8(aw, 1), fetch8(bx, 0));
-                ua = L.sel(fetch8(by, 0), fetch8(bz, 0), fetch8(bw, 0));
+                ug = L.sel(fetch(aw, 0), fetch(aw, 1), fetch(bx, 0));
+                ua = L.sel(fetch(by, 0), fetch(bz, 0), fetch(bw, 0));
                 if (h_noise_act0 != 0.f) {                                   // tron1_pf_ee.py:338-342 (quirk 4): actions and clock are noisy too
                     uact = L.sel(bc<2>(ax), bc<2>(ay), bc<2>(az));           // block 2 LEGS + 2 + leg in lane 2
                     const float ck0 = bc<3>(ax), ck1 = bc<3>(ay);            // block 3 LEGS + 2 + leg in lane 3: sin / cos entries
@@ -3040,23 +2472,276 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
                 B.llast_actions[ja] = reset ? 0.f : last_act;
                 B.last_actions[ja] = act;
             }
+        } else if constexpr (SQ) {
+            // ---- compute_observations + clip of the stacked frames.  go2_wtw.py:53-111: actor frame 61 = go2's 45 | clock sin 4, cos 4 |
+            //      gait period, base-height, clearance, pitch targets | theta 4; critic frame 99 = the frame without noise | v_b 3, push 2, mass,
+            //      friction, CoM 3 | kp 12 | kd 12 | exp_C_frc 4.  go2_ee.py:10-75: actor frame = go2's 45, stacked 20 deep; critic frame =
+            //      the frame without noise | DR 31 (friction - offset, mass, CoM 3, push 2, kp - offset 12, kd - offset 12) | contact states K |
+            //      heights P, stacked 5 deep; labels = v_b 3 | contact states K | foot height above the local terrain mean F.  Stacks are
+            //      sliding windows over rows with slack, in `obs_sets` copies: the new frame goes to this launch's window in this set and to
+            //      the same frame index of the other set; an env that resets blanks the older frames of its window, one that reset at the
+            //      previous launch the frames older than that (`dirty`) -- the same bookkeeping as env_step_body's, with the env's 16 lanes
+            //      writing consecutive columns, every lane the terrain samples it took itself.
+            const float co = h_clip_obs;
+            const bool nz = h_add_noise != 0;
+            const int FR = h_obs_frame, PF = h_priv_frame, ST = h_obs_stack, PST = h_priv_stack, SL = h_obs_slack;
+            const size_t orow = (size_t)(h_num_obs + SL * FR), prow = (size_t)(h_num_priv_obs + SL * PF);
+            const bool two = h_obs_sets > 1;
+            const int cs = two ? p.obs_set : 0, xs = (two && cs < 2) ? 1 - cs : cs;   // the other copy (two sets); with more sets nothing is stacked and xs is unused
+            float *oc = B.obs_buf + ((size_t)cs * N + e) * orow + (size_t)p.obs_win * FR;
+            float *ox = B.obs_buf + ((size_t)xs * N + e) * orow + (size_t)p.obs_win * FR;
+            float *pc = B.priv_obs_buf + ((size_t)cs * N + e) * prow + (size_t)p.obs_win * PF;
+            float *px = B.priv_obs_buf + ((size_t)xs * N + e) * prow + (size_t)p.obs_win * PF;
+            float *lab = EQ ? B.labels_buf + ((size_t)cs * N + e) * h_num_labels : nullptr;
+            if (anyl(reset)) {                         // go2_wtw.py:174-178, legged_robot_ee.py: the histories of a reset env restart from zeros
+                blank_histories(__builtin_amdgcn_ballot_w64(reset && live && ei == 0), e, B.obs_buf + (size_t)cs * N * orow + (size_t)p.obs_win * FR, orow, (ST - 1) * FR,
+                                B.priv_obs_buf + (size_t)cs * N * prow + (size_t)p.obs_win * PF, prow, (PST - 1) * PF);
+            }
+            if (two && anyl(!reset && w_dirty != 0)) {
+                blank_histories(__builtin_amdgcn_ballot_w64(!reset && w_dirty != 0 && live && ei == 0), e, B.obs_buf + (size_t)cs * N * orow + (size_t)p.obs_win * FR, orow,
+                                (ST - 2) * FR, B.priv_obs_buf + (size_t)cs * N * prow + (size_t)p.obs_win * PF, prow, (PST - 2) * PF);
+            }
+            float *on = oc + (ST - 1) * FR, *on2 = ox + (ST - 1) * FR, *pn = pc + (PST - 1) * PF, *pn2 = px + (PST - 1) * PF;
+            const bool w2o = two && ST > 1, w2p = two && PST > 1;
+            float uq = 0.5f, uqd = 0.5f, ug = 0.5f, ua = 0.5f;
+            if (nz) {   // the same blocks as the go2 frame below
+                uq = L.sel(bc<0>(ax), bc<0>(ay), bc<0>(az));
+                uqd = L.sel(bc<1>(ax), bc<1>(ay), bc<1>(az));
+                ug = fetch(aw, 4 * (cj >> 1) + (cj & 1));
+                ua = fetch(aw, 4 * ((3 + cj) >> 1) + ((3 + cj) & 1));
+                if constexpr (INJ) {   // the frame's entries of the injected row (slots.noise + index in the frame)
+                    const int ns_ = HOT(slots.noise);
+                    uq = rin[ns_ + 9 + d0 + cj]; uqd = rin[ns_ + 9 + A + d0 + cj]; ug = rin[ns_ + 3 + cj]; ua = rin[ns_ + 6 + cj];
+                }
+            }
+            if constexpr (EQ) {
+                // observation programs (PROF 4): where the noise-free actor frame sits in the critic frame (-1: nowhere), where the "next state"
+                // copy sits in the labels row (-1: none), whether the critic frame is clipped
+                int pfo = 0, nxo = -1;
+                float pclip = co;
+                if constexpr (PQ) {
+                    pfo = -1;
+                    for (int s_ = 0; s_ < PRG_I(0, 0); s_++) if (PRG_I(0, 2 + s_) == LG_SEG_FRAME) pfo = PRG_I(0, 10 + s_);
+                    for (int s_ = 0; s_ < PRG_I(1, 0); s_++) if (PRG_I(1, 2 + s_) == LG_SEG_NEXT_STATE) nxo = PRG_I(1, 10 + s_);
+                    pclip = PRG_I(0, 1) ? co : 3.0e38f;
+                }
+                const float ascl = HOT(o_action_scale);
+                auto W = [&](int idx, float v, float u, float ns) {
+                    const float nv = clampf(nz ? v + (2.f * u - 1.f) * ns : v, -co, co);
+                    on[idx] = nv; if (w2o) on2[idx] = nv;
+                    if (pfo >= 0) { const float cl = clampf(v, -pclip, pclip); pn[pfo + idx] = cl; if (w2p) pn2[pfo + idx] = cl; }
+                    if (PQ && nxo >= 0) lab[nxo + idx] = idx >= 9 + 2 * A ? v * ascl : v;      // go2_dreamwaq.py:66-74, not clipped
+                };
+                auto WP = [&](int idx, float v) { const float cl = clampf(v, -co, co); pn[idx] = cl; if (w2p) pn2[idx] = cl; };
+                // quad broadcasts outside the divergent branches
+                const float env4 = L.sel4(o_fric - h_friction_offset, o_mass, bc<0>(o_push), bc<1>(o_push));
+                const float pzn = bc<2>(pos);
+                const unsigned smask = m_smask;
+                const int K = __popc(smask);
+                const float csv = (L.sel4(n2[0], n2[1], n2[2], n2[3]) > 1.f) ? 1.f : 0.f;     // contact state of link l0 + c (physics read-back, stale after a reset as in the reference)
+                const int cl_ = l0 + L.c;
+                const bool chas = ((smask >> cl_) & 1u) != 0;
+                const int cidx = __popc(smask & ((1u << cl_) - 1u));
+                // the actor frame (both profiles)
+                if (st) {
+                    W(9 + d0 + cj, (q - q0) * h_obs_scale_dof_pos, uq, m_nq);
+                    W(9 + A + d0 + cj, qd * h_obs_scale_dof_vel, uqd, m_nqd);
+                    W(9 + 2 * A + d0 + cj, act, 0.5f, 0.f);
+                    if (leg == 0) {
+                        W(cj, cmdv * (L.is2 ? h_obs_scale_ang_vel : h_obs_scale_lin_vel), 0.5f, 0.f);
+                        W(3 + cj, pg, ug, L.sel(h_noise_lead_0, h_noise_lead_1, h_noise_lead_2));
+                        W(6 + cj, bav * h_obs_scale_ang_vel, ua, L.sel(h_noise_lead_3, h_noise_lead_4, h_noise_lead_5));
+                    }
+                }
+                if constexpr (!PQ) {
+                if (st) {
+                    WP(FR + 7 + d0 + cj, o_kp - h_kp_offset);
+                    WP(FR + 7 + A + d0 + cj, o_kd - h_kd_offset);
+                    if (leg == 0) lab[cj] = blv * h_obs_scale_lin_vel;
+                    if (leg == 2) WP(FR + 2 + cj, o_com);
+                    if (L.is0) lab[3 + K + foot_slot] = clampf(fpz - f_hmean - h_foot_height_offset, -1.f, 1.f);
+                }
+                if (live) {
+                    if (leg == 1) WP(FR + (L.c < 2 ? L.c : 3 + L.c), env4);                 // friction, mass | push x, y at FR + 5, 6
+                    if (chas) { WP(FR + 7 + 2 * A + cidx, csv); lab[3 + cidx] = csv; }
+                    if (leg == 0 && L.is3 && (smask & 1u)) { const float cb = nb2 > 1.f ? 1.f : 0.f; WP(FR + 7 + 2 * A, cb); lab[3] = cb; }
+#pragma unroll
+                    for (int i = 0; i < HQ; i++) {
+                        const int k = hk0 + i * kstride;
+                        float hv = pzn - h_heights_offset - hq[i];
+                        if (h_heights_clip_scale) hv = clampf(hv, -1.f, 1.f) * h_obs_scale_height;
+                        if (k < P) WP(FR + 7 + 2 * A + K + k, hv);
+                    }
+                }
+                } else {
+                    // observation programs (include/lgsim.h LgObsSeg): the critic frame and the auxiliary row are concatenations of blocks; each
+                    // block is written by the lanes that hold its values -- joint lanes, component lanes, the lane of a link, the lane that
+                    // took a terrain sample
+                    const float blvs = blv * h_obs_scale_lin_vel;
+                    const float clr = clampf(fpz - f_hmean - h_foot_height_offset, -1.f, 1.f);
+                    for (int which = 0; which < 2; which++) {
+                        const bool to_lab = which == 1;
+                        if (to_lab ? h_num_labels <= 0 : h_num_priv_obs <= 0) continue;
+                        const float cl = PRG_I(which, 1) ? co : 3.0e38f;
+                        auto WS = [&](int idx, float v) {
+                            v = clampf(v, -cl, cl);
+                            if (to_lab) lab[idx] = v;
+                            else { pn[idx] = v; if (w2p) pn2[idx] = v; }
+                        };
+                        const int n_segs = PRG_I(which, 0);
+                        for (int s_ = 0; s_ < n_segs; s_++) {
+                            const int kind = PRG_I(which, 2 + s_), off = PRG_I(which, 10 + s_);
+                            const float sc = PRG_F(which, 18 + s_);
+                            if (kind == LG_SEG_DR || kind == LG_SEG_DR_BASE) {
+                                if (st && kind == LG_SEG_DR) { WS(off + 7 + d0 + cj, o_kp - h_kp_offset); WS(off + 7 + A + d0 + cj, o_kd - h_kd_offset); }
+                                if (st && leg == 2) WS(off + 2 + cj, o_com);
+                                if (live && leg == 1) WS(off + (L.c < 2 ? L.c : 3 + L.c), env4);
+                            } else if (kind == LG_SEG_KP || kind == LG_SEG_KD) {
+                                if (st) WS(off + d0 + cj, kind == LG_SEG_KP ? o_kp - h_kp_offset : o_kd - h_kd_offset);
+                            } else if (kind == LG_SEG_BASE_LIN_VEL) {
+                                if (st && leg == 0) WS(off + cj, blvs * sc);
+                            } else if (kind == LG_SEG_CONTACT_STATES) {
+                                if (live && chas) WS(off + cidx, csv);
+                                if (live && leg == 0 && L.is3 && (smask & 1u)) WS(off, nb2 > 1.f ? 1.f : 0.f);
+                            } else if (kind == LG_SEG_HEIGHTS) {
+                                if (live) {
+#pragma unroll
+                                    for (int i = 0; i < HQ; i++) {
+                                        const int k = hk0 + i * kstride;
+                                        float hv = pzn - h_heights_offset - hq[i];
+                                        if (h_heights_clip_scale) hv = clampf(hv, -1.f, 1.f) * h_obs_scale_height;
+                                        if (k < P) WS(off + k, hv);
+                                    }
+                                }
+                            } else if (kind == LG_SEG_FEET_REL_HEIGHTS || kind == LG_SEG_FEET_HEIGHTS) {
+                                if (live) {   // nine per foot: lane c of the leg's quad writes entries c, c + 4 (and 8)
+#pragma unroll
+                                    for (int k = 0; k < 9; k++)
+                                        if ((k & 3) == L.c) WS(off + 9 * foot_slot + k, kind == LG_SEG_FEET_HEIGHTS ? f_h9[k] : clampf(fpz - f_h9[k], -1.f, 1.f));
+                                }
+                            } else if (kind == LG_SEG_FEET_NORMALS) {
+                                if (st) WS(off + 3 * foot_slot + cj, L.sel(f_n3[0], f_n3[1], f_n3[2]));
+                            } else if (kind == LG_SEG_FOOT_CLEARANCE) {
+                                if (live && L.is0) WS(off + foot_slot, clr);
+                            } else if (kind == LG_SEG_LAST_ACTIONS) {
+                                if (st) WS(off + d0 + cj, last_act);
+                            } else if (kind == LG_SEG_FEET_AIR_TIME) {
+                                if (live && L.is0) WS(off + foot_slot, air);
+                            }   // LG_SEG_FRAME / LG_SEG_NEXT_STATE: written entry by entry in W(); LG_SEG_DR_JOINT: excluded by the host check
+                        }
+                    }
+                }
+                if (live && leg == 0 && L.is0 && B.obs_dirty) B.obs_dirty[e] = reset ? 1 : 0;
+            } else {   // go2_wtw
+                // W: an actor-frame entry (noisy into the actor windows, noise-free into the critic frame); WP: a critic-only entry
+                auto W = [&](int idx, float v, float u, float ns) {
+                    const float cl = clampf(v, -co, co);
+                    const float nv = clampf(nz ? v + (2.f * u - 1.f) * ns : v, -co, co);
+                    on[idx] = nv; if (w2o) on2[idx] = nv;
+                    pn[idx] = cl; if (w2p) pn2[idx] = cl;
+                };
+                auto WP = [&](int idx, float v) { const float cl = clampf(v, -co, co); pn[idx] = cl; if (w2p) pn2[idx] = cl; };
+                const float ang = 6.283185307179586f * (phi + theta);        // clock inputs (go2_wtw.py:251-256)
+                const float sn = sinf(ang), csn = cosf(ang);
+                if (st) {
+                    W(9 + d0 + cj, (q - q0) * h_obs_scale_dof_pos, uq, m_nq);
+                    W(9 + A + d0 + cj, qd * h_obs_scale_dof_vel, uqd, m_nqd);
+                    W(9 + 2 * A + d0 + cj, act, 0.5f, 0.f);
+                    W((L.is0 ? 45 : (L.is1 ? 49 : 57)) + foot_slot, L.sel(sn, csn, theta), 0.5f, 0.f);
+                    WP(FR + 10 + d0 + cj, o_kp);
+                    WP(FR + 10 + A + d0 + cj, o_kd);
+                    if (L.is0) WP(FR + 10 + 2 * A + foot_slot, expC);
+                    if (leg == 0) {
+                        W(cj, cmdv * (L.is2 ? h_obs_scale_ang_vel : h_obs_scale_lin_vel), 0.5f, 0.f);
+                        W(3 + cj, pg, ug, L.sel(h_noise_lead_0, h_noise_lead_1, h_noise_lead_2));
+                        W(6 + cj, bav * h_obs_scale_ang_vel, ua, L.sel(h_noise_lead_3, h_noise_lead_4, h_noise_lead_5));
+                        WP(FR + cj, blv * h_obs_scale_lin_vel);
+                    }
+                    if (leg == 2) WP(FR + 7 + cj, o_com);
+                }
+                const float env4 = L.sel4(bc<0>(o_push), bc<1>(o_push), o_mass, o_fric);   // quad broadcasts outside the divergent branches
+                if (live && leg == 0) W(53 + L.c, L.sel4(gait_period, bh_tgt, fc_tgt, pitch_tgt), 0.5f, 0.f);
+                if (live && leg == 1) WP(FR + 3 + L.c, env4);
+                // task state as the env class exposes it (go2_wtw.py:295-346), the deferred-blanking flag, the second action-history shift
+                // (go2_wtw.py:45-46: afterwards last == llast == a_t)
+                float *ts = B.task_state + (size_t)e * LG_TASK_STATE_WTW;
+                if (st) {
+                    ts[(L.is0 ? 6 : (L.is1 ? 10 : 14)) + foot_slot] = L.sel(theta, sn, csn);
+                    if (L.is0) ts[18 + foot_slot] = expC;
+                    B.llast_actions[ja] = reset ? 0.f : last_act;
+                    B.last_actions[ja] = act;
+                }
+                if (live && leg == 0) {
+                    ts[L.c] = L.sel4(gait_time, phi, gait_period, bh_tgt);
+                    if (L.c < 2) ts[4 + L.c] = L.is0 ? fc_tgt : pitch_tgt;
+                    if (L.is0 && B.obs_dirty) B.obs_dirty[e] = reset ? 1 : 0;
+                }
+            }
+        } else
+        // ---- compute_observations + clip (go2.py:40-64, legged_robot.py:48-49) ----
+        {
+            const float co = h_clip_obs;
+            const bool nz = h_add_noise != 0;
+            float uq = 0.5f, uqd = 0.5f, ug = 0.5f, ua = 0.5f;
+            if (nz) {
+                // blocks 2 leg and 2 leg + 1 of env_step_body in lanes 0 and 1 of the quad, side by side: (x, y, z) = the three joints'
+                // uniforms (positions / velocities), w = one of the base's six
+                uq = L.sel(bc<0>(ax), bc<0>(ay), bc<0>(az));
+                uqd = L.sel(bc<1>(ax), bc<1>(ay), bc<1>(az));
+                // base uniform k sits in quad k / 2, lane k % 2: gravity component c takes k = c, angular velocity k = 3 + c
+                ug = fetch(aw, 4 * (cj >> 1) + (cj & 1));
+                ua = fetch(aw, 4 * ((3 + cj) >> 1) + ((3 + cj) & 1));
+                if constexpr (INJ) {   // the frame's entries of the injected row (slots.noise + index in the frame)
+                    const int ns_ = HOT(slots.noise);
+                    uq = rin[ns_ + 9 + d0 + cj]; uqd = rin[ns_ + 9 + A + d0 + cj]; ug = rin[ns_ + 3 + cj]; ua = rin[ns_ + 6 + cj];
+                }
+            }
+            float *o = B.obs_buf + ((size_t)(h_obs_sets > 1 ? p.obs_set : 0) * N + e) * (size_t)(9 + 3 * A);
+            auto noisy = [&](float v, float u, float ns) { if (nz) v += (2.f * u - 1.f) * ns; return clampf(v, -co, co); };
+            if (st) {
+                o[9 + d0 + cj] = noisy((q - q0) * h_obs_scale_dof_pos, uq, m_nq);
+                o[9 + A + d0 + cj] = noisy(qd * h_obs_scale_dof_vel, uqd, m_nqd);
+                o[9 + 2 * A + d0 + cj] = clampf(act, -co, co);
+                if (leg == 0) {
+                    const float cs_ = L.is2 ? h_obs_scale_ang_vel : h_obs_scale_lin_vel;
+                    o[cj] = clampf(cmdv * cs_, -co, co);
+                    o[3 + cj] = noisy(pg, ug, L.sel(h_noise_lead_0, h_noise_lead_1, h_noise_lead_2));
+                    o[6 + cj] = noisy(bav * h_obs_scale_ang_vel, ua, L.sel(h_noise_lead_3, h_noise_lead_4, h_noise_lead_5));
+                }
+            }
         }
         STAMP(10);
-        // ---- persistent MDP state ----
-        if (live) {        // role 0: what the reward terms produced
-            const unsigned es4 = ((unsigned)el * (unsigned)N + (unsigned)e) * 4u;      // (term, N) rows: uniform base + 32-bit offset per lane
+        // ---- persistent MDP state (32-bit byte offsets from wave-uniform bases, as the read-back stores: (term, N) rows stay below 4 GiB,
+        //      host-checked) ----
+        if constexpr (BQ) {
+            if (live) {        // DUO: role 0, what the reward terms produced
+                const unsigned es4 = ((unsigned)ei * (unsigned)N + (unsigned)e) * 4u;
 #pragma unroll
-            for (int k = 0; k < 4; k++)
-                if (el + 8 * k < LG_R_COUNT && ((rmask >> (el + 8 * k)) & 1u))
-                    *reinterpret_cast<float *>(reinterpret_cast<char *>(B.episode_sums + (size_t)8 * k * N) + es4) = es[k];
-            if (L.is0) { B.feet_air_time[e * F + foot_slot] = air; B.last_contacts[e * F + foot_slot] = (uint8_t)last_contact; }
-            if (leg == 0 && L.is0) B.rew_buf[e] = total;
-        }
-        if (liveB && leg == 0) {      // role 1: commands, counters, flags
-            B.commands[4 * e + L.c] = cmdv;
-            if (L.is0) {
-                B.episode_length_buf[e] = ep_len; B.fail_buf[e] = (long long)failb;
-                B.reset_buf[e] = reset ? 1 : 0; B.time_out_buf[e] = time_out ? 1 : 0;
+                for (int k = 0; k < 4; k++)
+                    if (ei + 8 * k < LG_R_COUNT && ((rmask >> (ei + 8 * k)) & 1u))
+                        *reinterpret_cast<float *>(reinterpret_cast<char *>(B.episode_sums + (size_t)8 * k * N) + es4) = es[k];
+                if (L.is0) { B.feet_air_time[e * F + foot_slot] = air; B.last_contacts[e * F + foot_slot] = (uint8_t)last_contact; }
+                if (leg == 0 && L.is0) B.rew_buf[e] = total;
+            }
+            if (liveB && leg == 0) {      // role 1: commands, counters, flags
+                B.commands[4 * e + L.c] = cmdv;
+                if (L.is0) {
+                    B.episode_length_buf[e] = ep_len; B.fail_buf[e] = (long long)failb;
+                    B.reset_buf[e] = reset ? 1 : 0; B.time_out_buf[e] = time_out ? 1 : 0;
+                }
+            }
+        } else if (live) {
+            const unsigned o_es = 4u * ((unsigned)ei * (unsigned)N + (unsigned)e);
+            if ((rmask >> ei) & 1u) stq(B.episode_sums, o_es, es0);
+            if (ei + 16 < LG_R_COUNT && ((rmask >> (ei + 16)) & 1u)) stq(B.episode_sums, o_es + 64u * (unsigned)N, es1);
+            if (L.is0) { stq(B.feet_air_time, 4u * (unsigned)(e * F + foot_slot), air); stq(B.last_contacts, (unsigned)(e * F + foot_slot), (uint8_t)last_contact); }
+            if (leg == 0) {
+                stq(B.commands, 4u * (unsigned)(4 * e + L.c), cmdv);
+                if (L.is0) {
+                    const unsigned ue = (unsigned)e;
+                    stq(B.episode_length_buf, 4u * ue, (int32_t)ep_len); stq(B.fail_buf, 8u * ue, (int64_t)failb);
+                    stq(B.reset_buf, ue, (uint8_t)(reset ? 1 : 0)); stq(B.time_out_buf, ue, (uint8_t)(time_out ? 1 : 0)); stq(B.rew_buf, 4u * ue, total);
+                }
             }
         }
         STAMP(11);
