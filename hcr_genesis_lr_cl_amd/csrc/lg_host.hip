@@ -205,78 +205,87 @@ static bool flat_noise_ok(const LgEngine *h) {   // commands and actions carry n
     return true;
 }
 
-// The task profile (lg_quad.h PROF) whose hard-wired switches the task really has, 0 for none: 1 go2 on the plane, 2 go2_wtw, 3 / 4 the
-// Go2-rough family, 6 tron1_pf_ee.  inj: the injected-uniform test instantiations (rand_in REQUIRED instead of forbidden)
-static int task_profile(const LgEngine *h, bool inj) {
+// ---- task profiles (lg_shared.h LG_PROF_*): each predicate checks that the task really has every switch its profile's instantiations
+//      hard-wire.  inj: the injected-uniform test instantiations (rand_in REQUIRED instead of forbidden).  No side effects.
+static bool hf_bound(const LgEngine *h) { return h->hf != nullptr && h->opts.terrain_rows > 0; }
+static bool uniforms_ok(const LgEngine *h, bool inj) { return inj ? h->bufs.rand_in != nullptr : !h->bufs.rand_in; }
+static bool rewards_ok(const LgEngine *h, int prof) { return ((unsigned)h->hot.reward_mask & lg_tail_reward_excluded(prof)) == 0; }
+static bool window_stacks(const LgEngine *h) {   // sliding-window stacks of both outputs, one set or two behind obs_dirty
+    const LgTaskCfg &t = h->task; return t.obs_slack > 0 && t.obs_stack > 1 && t.priv_stack > 1 && t.obs_sets <= 2 && (t.obs_sets < 2 || h->bufs.obs_dirty);
+}
+static bool offset_fits(const LgEngine *h, int stack, int frame) {   // 32-bit byte offsets into an observation allocation (lg_quad.h)
+    return (double)h->bufs.n_envs * (stack + h->task.obs_slack) * frame * 4.0 < 4.0e9; }
+
+// biped_profile: tron1_pf_ee (TRON1_PF_EE = the component-layout tail of lg_quad.h for the three-joint biped)
+static bool biped_profile(const LgEngine *h, bool inj) {
+    const LgTaskCfg &t = h->task; const LgBuffers &b = h->bufs;
+    if (h->model.n_bodies != 7 || !hf_bound(h)) return false;
+    const int K = __builtin_popcount(h->model.state_link_mask), P = h->opts.n_height_points, A = 6, F = 2;
+    return t.obs_layout == LG_OBS_TRON1_EE && t.gait_mode == 2 && t.double_shift == 1 && t.cat_enable == 0 && t.behavior_resample_steps == 0 &&
+           window_stacks(h) && uniforms_ok(h, inj) &&
+           t.obs_frame == 9 + 3 * A + 2 * F && t.priv_frame == t.obs_frame + 7 + 2 * A + 3 + F + K + P + 3 * F + 9 * F && t.num_labels == 3 + K + F + 3 * F &&
+           P > 0 && P <= 7 * 8 && h->opts.feet_terrain_info && b.priv_obs_buf && b.labels_buf && b.task_state && b.rand_push_vels &&
+           t.task_state_width == LG_TASK_STATE_BIPED && b.link_contact_states &&
+           (!t.terrain_curriculum || (b.terrain_levels && b.terrain_types && b.terrain_origins && b.env_origins)) &&
+           (!t.dr_joint_on || (b.joint_armature && b.joint_friction && b.joint_damping)) &&
+           (t.slots.reset_root_xy & 3) != 3 &&       // the two root xy draws share a Philox block
+           offset_fits(h, t.priv_stack, t.priv_frame) && offset_fits(h, t.obs_stack, t.obs_frame) &&
+           t.noise_vec[0] == 0.f && t.noise_vec[1] == 0.f && t.noise_vec[2] == 0.f &&    // commands carry no observation noise (tron1_pf_ee.py:322-342)
+           rewards_ok(h, LG_PROF_TRON1_PF_EE);
+}
+// flat_profile: the plain go2-on-a-plane task (GO2_FLAT), every switch the FLAT instantiations hard-wire (env_step_body) really has that value
+static bool flat_profile(const LgEngine *h, bool inj) {
     const LgTaskCfg &t = h->task; const LgSimOptions &o = h->opts; const LgBuffers &b = h->bufs;
-    if (h->model.n_legs == 2) {
-        // biped_profile: tron1_pf_ee (PROF 6 = the component-layout tail of lg_quad.h for the three-joint biped): what it hard-wires
-        if (h->model.n_bodies != 7 || !h->hf || h->opts.terrain_rows <= 0) return 0;
-        const int K = __builtin_popcount(h->model.state_link_mask), P = h->opts.n_height_points, A = 6, F = 2;
-        return t.obs_layout == LG_OBS_TRON1_EE && t.gait_mode == 2 && t.double_shift == 1 && t.cat_enable == 0 && t.behavior_resample_steps == 0 &&
-               t.obs_slack > 0 && t.obs_stack > 1 && t.priv_stack > 1 && t.obs_sets <= 2 && (t.obs_sets < 2 || b.obs_dirty) && (inj ? b.rand_in != nullptr : !b.rand_in) &&
-               t.obs_frame == 9 + 3 * A + 2 * F && t.priv_frame == t.obs_frame + 7 + 2 * A + 3 + F + K + P + 3 * F + 9 * F && t.num_labels == 3 + K + F + 3 * F &&
-               P > 0 && P <= 7 * 8 && h->opts.feet_terrain_info && b.priv_obs_buf && b.labels_buf && b.task_state && b.rand_push_vels &&
-               t.task_state_width == LG_TASK_STATE_BIPED && b.link_contact_states &&
-               (!t.terrain_curriculum || (b.terrain_levels && b.terrain_types && b.terrain_origins && b.env_origins)) &&
-               (!t.dr_joint_on || (b.joint_armature && b.joint_friction && b.joint_damping)) &&
-               (t.slots.reset_root_xy & 3) != 3 &&       // the two root xy draws share a Philox block
-               // 32-bit byte offsets into the observation allocations (lg_quad.h)
-               (double)b.n_envs * (t.priv_stack + t.obs_slack) * t.priv_frame * 4.0 < 4.0e9 && (double)b.n_envs * (t.obs_stack + t.obs_slack) * t.obs_frame * 4.0 < 4.0e9 &&
-               // commands carry no observation noise (tron1_pf_ee.py:322-342)
-               t.noise_vec[0] == 0.f && t.noise_vec[1] == 0.f && t.noise_vec[2] == 0.f &&
-               ((unsigned)h->hot.reward_mask & ((1u << LG_R_QUAD_PERIODIC_GAIT) | (1u << LG_R_TRACKING_FOOT_CLEARANCE) | (1u << LG_R_TRACKING_ORIENTATION))) == 0
-               ? 6 : 0;
-    }
-    // flat_profile: the plain go2-on-a-plane task (PROF 1), every switch the FLAT instantiations hard-wire (env_step_body) really has that value
-    if (t.obs_layout == LG_OBS_GO2 && t.gait_mode == 0 && t.double_shift == 0 && t.obs_stack == 1 && t.obs_slack == 0 && t.priv_frame == 0 &&
-        t.priv_stack <= 1 && t.num_priv_obs == 0 && t.terrain_curriculum == 0 && t.custom_origins == 0 && t.sit_percent == 0.f &&
-        t.behavior_resample_steps == 0 && t.num_labels == 0 && t.cat_enable == 0 && t.noise_vec[9 + 6 * h->model.n_legs] == 0.f && t.air_time_cmd_dims != 3 &&
-        h->model.n_bodies == 1 + 3 * h->model.n_legs &&
-        o.n_height_points == 0 && o.terrain_rows == 0 && o.feet_terrain_info == 0 && !b.link_contact_states && !b.task_state && !h->hf &&
-        (inj ? b.rand_in != nullptr : !b.rand_in) && !b.joint_armature && !t.dr_joint_on && !t.dr_pd_on && t.reset_lin_vel_span == 0.f && t.reset_ang_vel_span == 0.f && flat_noise_ok(h) &&
-        // reward terms the component-layout tail (lg_quad.h) does not carry: gait clocks, biped and wtw-only terms
-        ((unsigned)h->hot.reward_mask & ((1u << LG_R_BIPED_PERIODIC_GAIT) | (1u << LG_R_QUAD_PERIODIC_GAIT) | (1u << LG_R_FEET_DISTANCE) |
-                                         (1u << LG_R_TRACKING_BASE_HEIGHT) | (1u << LG_R_TRACKING_FOOT_CLEARANCE) |
-                                         (1u << LG_R_TRACKING_ORIENTATION))) == 0)
-        return 1;
-    // wtw_profile: go2_wtw on the plane (PROF 2)
-    if (t.obs_layout == LG_OBS_GO2_WTW && t.gait_mode == 1 && t.double_shift == 1 && t.terrain_curriculum == 0 && t.custom_origins == 0 &&
-        t.sit_percent == 0.f && t.num_labels == 0 && t.cat_enable == 0 && t.noise_vec[9 + 6 * h->model.n_legs] == 0.f &&
-        o.n_height_points == 0 && o.terrain_rows == 0 && o.feet_terrain_info == 0 && !b.link_contact_states && !h->hf && b.task_state &&
-        // what the component-layout tail of lg_quad.h (PROF 2) hard-wires: sliding-window stacks of 61 | 99-wide frames, Philox draws,
-        // no per-env joint parameters, no noise on commands / actions
-        t.obs_slack > 0 && t.obs_frame == 61 && t.priv_frame == 61 + 10 + 6 * h->model.n_legs + h->model.n_legs && t.obs_stack > 1 && t.priv_stack > 1 &&
-        t.obs_sets <= 2 && (t.obs_sets < 2 || b.obs_dirty) && (inj ? b.rand_in != nullptr : !b.rand_in) && !b.joint_armature && !t.dr_joint_on && flat_noise_ok(h) &&
-        h->model.n_legs == 4 && h->model.n_bodies == 13 && b.priv_obs_buf && b.rand_push_vels &&
-        ((unsigned)h->hot.reward_mask & ((1u << LG_R_BIPED_PERIODIC_GAIT) | (1u << LG_R_FEET_DISTANCE))) == 0)
-        return 2;
-    // rough_profile: the Go2-rough family (PROF 3: go2_ee packaging, PROF 4: observation programs -- go2_ts / go2_cts / go2_dreamwaq / go2_cat): no gait
-    // clock, no sit pose, no noise on actions; terrain, curriculum, stacks and (PROF 4) CaT stay runtime
-    if (t.gait_mode != 0 || t.sit_percent != 0.f || t.behavior_resample_steps != 0 || t.noise_vec[9 + 6 * h->model.n_legs] != 0.f || h->bufs.task_state)
-        return 0;
-    if (!h->hf || h->opts.terrain_rows <= 0) return 0;     // the profiles hard-wire "there is a heightfield" (lg_quad.h HFC)
-    // PROF 3 / 4 = the component-layout tail of lg_quad.h for the go2_ee family: what it hard-wires
+    return t.obs_layout == LG_OBS_GO2 && t.gait_mode == 0 && t.double_shift == 0 && t.obs_stack == 1 && t.obs_slack == 0 && t.priv_frame == 0 &&
+           t.priv_stack <= 1 && t.num_priv_obs == 0 && t.terrain_curriculum == 0 && t.custom_origins == 0 && t.sit_percent == 0.f &&
+           t.behavior_resample_steps == 0 && t.num_labels == 0 && t.cat_enable == 0 && t.noise_vec[9 + 6 * h->model.n_legs] == 0.f && t.air_time_cmd_dims != 3 &&
+           h->model.n_bodies == 1 + 3 * h->model.n_legs &&
+           o.n_height_points == 0 && o.terrain_rows == 0 && o.feet_terrain_info == 0 && !b.link_contact_states && !b.task_state && !h->hf &&
+           uniforms_ok(h, inj) && !b.joint_armature && !t.dr_joint_on && !t.dr_pd_on && t.reset_lin_vel_span == 0.f && t.reset_ang_vel_span == 0.f && flat_noise_ok(h) &&
+           rewards_ok(h, LG_PROF_GO2_FLAT);
+}
+// wtw_profile: go2_wtw on the plane (GO2_WTW): sliding-window stacks of 61 | 99-wide frames, Philox draws, no per-env joint parameters,
+// no noise on commands / actions
+static bool wtw_profile(const LgEngine *h, bool inj) {
+    const LgTaskCfg &t = h->task; const LgSimOptions &o = h->opts; const LgBuffers &b = h->bufs;
+    return t.obs_layout == LG_OBS_GO2_WTW && t.gait_mode == 1 && t.double_shift == 1 && t.terrain_curriculum == 0 && t.custom_origins == 0 &&
+           t.sit_percent == 0.f && t.num_labels == 0 && t.cat_enable == 0 && t.noise_vec[9 + 6 * h->model.n_legs] == 0.f &&
+           o.n_height_points == 0 && o.terrain_rows == 0 && o.feet_terrain_info == 0 && !b.link_contact_states && !h->hf && b.task_state &&
+           t.obs_frame == 61 && t.priv_frame == 61 + 10 + 6 * h->model.n_legs + h->model.n_legs &&
+           window_stacks(h) && uniforms_ok(h, inj) && !b.joint_armature && !t.dr_joint_on && flat_noise_ok(h) &&
+           h->model.n_legs == 4 && h->model.n_bodies == 13 && b.priv_obs_buf && b.rand_push_vels && rewards_ok(h, LG_PROF_GO2_WTW);
+}
+// rough_profile: the Go2-rough family on a heightfield (lg_quad.h HFC) -- GO2_EE (go2_ee packaging), GO2_PROGRAM (observation programs: go2_ts / go2_cts /
+// go2_dreamwaq / go2_cat) or NONE.  No gait clock, no sit pose, no noise on actions; terrain, curriculum, stacks and (GO2_PROGRAM) CaT stay runtime
+static int rough_profile(const LgEngine *h, bool inj) {
+    const LgTaskCfg &t = h->task; const LgBuffers &b = h->bufs;
+    if (t.gait_mode != 0 || t.sit_percent != 0.f || t.behavior_resample_steps != 0 || t.noise_vec[9 + 6 * h->model.n_legs] != 0.f || b.task_state || !hf_bound(h))
+        return LG_PROF_NONE;
     const int K = __builtin_popcount(h->model.state_link_mask), P = h->opts.n_height_points, A = h->model.n_bodies - 1;
-    const bool common = t.double_shift == 0 && t.cat_enable == 0 && t.obs_slack > 0 && t.obs_frame == 9 + 3 * A && t.obs_stack > 1 && t.priv_stack > 1 &&
-                        t.obs_sets <= 2 && (t.obs_sets < 2 || b.obs_dirty) && (inj ? b.rand_in != nullptr : !b.rand_in) && !b.joint_armature && !t.dr_joint_on && flat_noise_ok(h) &&
+    const bool common = t.double_shift == 0 && t.cat_enable == 0 && t.obs_frame == 9 + 3 * A && window_stacks(h) && uniforms_ok(h, inj) &&
+                        !b.joint_armature && !t.dr_joint_on && flat_noise_ok(h) &&
                         h->model.n_legs == 4 && h->model.n_bodies == 13 && P > 0 && P <= 7 * 16 && h->opts.feet_terrain_info && b.priv_obs_buf &&
                         b.rand_push_vels && t.air_time_cmd_dims != 3 && t.num_priv_obs > 0 &&
                         (!t.terrain_curriculum || (b.terrain_levels && b.terrain_types && b.terrain_origins && b.env_origins)) &&
-                        ((unsigned)h->hot.reward_mask & ((1u << LG_R_BIPED_PERIODIC_GAIT) | (1u << LG_R_QUAD_PERIODIC_GAIT) | (1u << LG_R_FEET_DISTANCE) |
-                                                         (1u << LG_R_BASE_HEIGHT) | (1u << LG_R_TRACKING_BASE_HEIGHT) | (1u << LG_R_TRACKING_FOOT_CLEARANCE) |
-                                                         (1u << LG_R_TRACKING_ORIENTATION))) == 0;
-    if (!common) return 0;
+                        rewards_ok(h, LG_PROF_GO2_EE);   // the same exclusions as GO2_PROGRAM
+    if (!common) return LG_PROF_NONE;
     if (t.obs_layout == LG_OBS_GO2_EE)
-        return (t.priv_frame == 9 + 3 * A + 7 + 2 * A + K + P && t.num_labels == 3 + K + h->model.n_legs && b.labels_buf) ? 3 : 0;
+        return (t.priv_frame == 9 + 3 * A + 7 + 2 * A + K + P && t.num_labels == 3 + K + h->model.n_legs && b.labels_buf) ? LG_PROF_GO2_EE : LG_PROF_NONE;
     if (t.obs_layout == LG_OBS_PROGRAM) {
-        if (t.num_labels > 0 && !b.labels_buf) return 0;
+        if (t.num_labels > 0 && !b.labels_buf) return LG_PROF_NONE;
         for (const LgObsProgram *pr : {&t.priv_prog, &t.labels_prog})
             for (int i = 0; i < pr->n_segs; i++)
-                if (pr->kind[i] == LG_SEG_DR_JOINT || pr->kind[i] <= LG_SEG_END || pr->kind[i] > LG_SEG_KD) return 0;
-        return 4;
+                if (pr->kind[i] == LG_SEG_DR_JOINT || pr->kind[i] <= LG_SEG_END || pr->kind[i] > LG_SEG_KD) return LG_PROF_NONE;
+        return LG_PROF_GO2_PROGRAM;
     }
-    return 0;
+    return LG_PROF_NONE;
+}
+// The profile whose hard-wired switches the task really has, LG_PROF_NONE for none.
+static int task_profile(const LgEngine *h, bool inj) {
+    if (h->model.n_legs == 2) return biped_profile(h, inj) ? LG_PROF_TRON1_PF_EE : LG_PROF_NONE;
+    if (flat_profile(h, inj)) return LG_PROF_GO2_FLAT;
+    if (wtw_profile(h, inj)) return LG_PROF_GO2_WTW;
+    return rough_profile(h, inj);
 }
 
 // Developer switches: 1 / 0 when the environment variable is set to a non-zero number / 0, -1 when unset.  Read on every lg_step (the
@@ -299,22 +308,25 @@ struct LgKernel { LgLauncher fn; const char *name; };   // a launcher of lg_shar
 template <int LEGS, int PROF> static void launch_inj(dim3 grid, hipStream_t st, hipEvent_t, hipEvent_t, const KParams &p) { lg_launch_quad_inj<LEGS, PROF>(grid, st, p); }
 
 // Every kernel lg_step launches, named once, as the launcher expression lg_step has always reported (LEGS / JPL / PR tokens included:
-// bench.py's roofline.kernel and the GPU tests match on these strings).  A row is instantiated only where plan() uses it.
+// bench.py's roofline.kernel and the GPU tests match on these strings, so profiles are literals: pinned to their names here).  A row is
+// instantiated only where plan() uses it.
+static_assert(LG_PROF_NONE == 0); static_assert(LG_PROF_GO2_FLAT == 1); static_assert(LG_PROF_GO2_WTW == 2); static_assert(LG_PROF_GO2_EE == 3);
+static_assert(LG_PROF_GO2_PROGRAM == 4); static_assert(LG_PROF_NONE_HF == 5); static_assert(LG_PROF_TRON1_PF_EE == 6);
 template <int LEGS, int JPL> struct Kernels {
     static constexpr unsigned PR = LG_PHASE_POST | LG_PHASE_RESET;
-    // leg per lane (lg_kernel.h), one launch per phase set; POST | RESET also replicated (env_step_kernel<..., REPL>)
+    // leg per lane (lg_kernel.h), one launch per phase set; POST | RESET also replicated (env_step_kernel<..., REPL>).  NONE; all_flat GO2_FLAT
     static constexpr LgKernel all = LG_KERNEL((lg_launch_env<LEGS, LG_PHASE_ALL, 0, JPL, false>)), all_flat = LG_KERNEL((lg_launch_env<4, LG_PHASE_ALL, 1, 3, false>)),
         sim = LG_KERNEL((lg_launch_env<LEGS, LG_PHASE_SIM, 0, JPL, false>)), pre_sim = LG_KERNEL((lg_launch_env<LEGS, LG_PHASE_PRE | LG_PHASE_SIM, 0, JPL, false>)),
         pre_sim_post = LG_KERNEL((lg_launch_env<LEGS, LG_PHASE_PRE | LG_PHASE_SIM | LG_PHASE_POST, 0, JPL, false>)),
         pre_post_reset = LG_KERNEL((lg_launch_env<LEGS, LG_PHASE_PRE | PR, 0, JPL, false>)), pre_post = LG_KERNEL((lg_launch_env<LEGS, LG_PHASE_PRE | LG_PHASE_POST, 0, JPL, false>)),
         post_reset = LG_KERNEL((lg_launch_env<LEGS, PR, 0, JPL, false>)), post_reset_repl = LG_KERNEL((lg_launch_env<LEGS, PR, 0, JPL, true>)),
         post = LG_KERNEL((lg_launch_env<LEGS, LG_PHASE_POST, 0, JPL, false>)), reset = LG_KERNEL((lg_launch_env<LEGS, LG_PHASE_RESET, 0, JPL, false>));
-    // component per lane (lg_quad.h), three joints per leg.  Physics only by [PRE][heightfield bound]: PROF 3 here only says "a heightfield
-    // is bound" (lg_quad.h HFC: no branch in front of the terrain loads)
-    static constexpr LgKernel phys[2][2] = {{LG_KERNEL((lg_launch_quad<LEGS, false, 0u, 0, 3>)), LG_KERNEL((lg_launch_quad<LEGS, false, 0u, 3, 3>))},
-                                            {LG_KERNEL((lg_launch_quad<LEGS, true, 0u, 0, 3>)), LG_KERNEL((lg_launch_quad<LEGS, true, 0u, 3, 3>))}};
-    // quadruped whole step: the leg-per-lane MDP body in the tail, the tails of PROF 1-4 and the same with the profile's default reward set
-    // as a constant (lg_quad.h RS); biped whole step: the leg-per-lane MDP body in the tail (PROF 0, 5: a heightfield is bound), tron1_pf_ee's (6)
+    // component per lane (lg_quad.h), three joints per leg.  Physics only by [PRE][heightfield bound]: NONE / NONE_HF (lg_quad.h HFC: no
+    // branch in front of the terrain loads)
+    static constexpr LgKernel phys[2][2] = {{LG_KERNEL((lg_launch_quad<LEGS, false, 0u, 0, 3>)), LG_KERNEL((lg_launch_quad<LEGS, false, 0u, 5, 3>))},
+                                            {LG_KERNEL((lg_launch_quad<LEGS, true, 0u, 0, 3>)), LG_KERNEL((lg_launch_quad<LEGS, true, 0u, 5, 3>))}};
+    // quadruped whole step: the leg-per-lane MDP body in the tail (NONE), the tails of GO2_FLAT .. GO2_PROGRAM [profile - 1] and the same with
+    // the default reward set as a constant (lg_quad.h RS); biped whole step: the leg-per-lane MDP body in the tail (NONE, NONE_HF), TRON1_PF_EE's
     static constexpr LgKernel quad_pre_sim_post = LG_KERNEL((lg_launch_quad<4, true, LG_PHASE_POST, 0, 3>)), quad_all = LG_KERNEL((lg_launch_quad<4, true, PR, 0, 3>)),
         biped_all = LG_KERNEL((lg_launch_quad<2, true, PR, 0, 3>)), biped_all_hf = LG_KERNEL((lg_launch_quad<2, true, PR, 5, 3>)),
         biped_all_ee = LG_KERNEL((lg_launch_quad<2, true, PR, 6, 3>));
@@ -322,13 +334,13 @@ template <int LEGS, int JPL> struct Kernels {
                                               LG_KERNEL((lg_launch_quad<4, true, PR, 3, 3>)), LG_KERNEL((lg_launch_quad<4, true, PR, 4, 3>))};
     static constexpr LgKernel quad_prof_rs[4] = {LG_KERNEL((lg_launch_quad_rs<4, 1, false>)), LG_KERNEL((lg_launch_quad_rs<4, 2, false>)),
                                                  LG_KERNEL((lg_launch_quad_rs<4, 3, false>)), LG_KERNEL((lg_launch_quad_rs<4, 4, false>))};
-    // golden replays: PRE | POST | RESET through the tails of PROF 1-4 / 6 on injected read-backs and uniforms (lg_quad.h INJ)
+    // golden replays: PRE | POST | RESET through the tails of GO2_FLAT .. GO2_PROGRAM [profile - 1] / TRON1_PF_EE on injected inputs (lg_quad.h INJ)
     static constexpr LgKernel inj[4] = {{launch_inj<4, 1>, "(lg_launch_quad_inj<4, 1>)"}, {launch_inj<4, 2>, "(lg_launch_quad_inj<4, 2>)"},
                                         {launch_inj<4, 3>, "(lg_launch_quad_inj<4, 3>)"}, {launch_inj<4, 4>, "(lg_launch_quad_inj<4, 4>)"}};
     static constexpr LgKernel inj_rs[4] = {{lg_launch_quad_rs<4, 1, true>, "(lg_launch_quad_inj<4, 1>, reward set constant)"}, {lg_launch_quad_rs<4, 2, true>, "(lg_launch_quad_inj<4, 2>, reward set constant)"},
                                            {lg_launch_quad_rs<4, 3, true>, "(lg_launch_quad_inj<4, 3>, reward set constant)"}, {lg_launch_quad_rs<4, 4, true>, "(lg_launch_quad_inj<4, 4>, reward set constant)"}};
     static constexpr LgKernel inj_biped = {launch_inj<2, 6>, "(lg_launch_quad_inj<2, 6>)"};
-    // four joints per leg (TRON1 sole foot; these exist for the biped alone, hence plan()'s `if constexpr`): physics by [PRE], then the MDP phases
+    // four joints per leg (TRON1 sole foot; these exist for the biped alone, hence plan()'s `if constexpr`): physics by [PRE], then MDP; NONE
     static constexpr LgKernel sole_phys[2] = {LG_KERNEL((lg_launch_quad<LEGS, false, 0u, 0, 4>)), LG_KERNEL((lg_launch_quad<LEGS, true, 0u, 0, 4>))};
     static constexpr LgKernel sole_post_reset = LG_KERNEL((lg_launch_env<LEGS, PR, 0, 4, false>)), sole_post_reset_repl = LG_KERNEL((lg_launch_env<LEGS, PR, 0, 4, true>)),
         sole_post = LG_KERNEL((lg_launch_env<LEGS, LG_PHASE_POST, 0, 4, false>));
@@ -344,7 +356,7 @@ template <int LEGS, int JPL> static LgPlan plan(const LgEngine *h, uint32_t ph, 
     const auto add = [&pl](const LgKernel &k, dim3 grid) { pl.l[pl.n].k = k; pl.l[pl.n].grid = grid; pl.n++; };
     const int threads = h->bufs.n_envs * LEGS;
     const dim3 grid((threads + BLOCK - 1) / BLOCK), qgrid((threads * 4 + BLOCK - 1) / BLOCK), rgrid((threads + 15) / 16);
-    const bool pre = (ph & LG_PHASE_PRE) != 0, hfb = h->hf != nullptr && h->opts.terrain_rows > 0;
+    const bool pre = (ph & LG_PHASE_PRE) != 0, hfb = hf_bound(h);
     const uint32_t rest = ph & PR;
     // MDP-only launches of small biped batches run replicated (env_step_kernel<..., REPL>) while four times the waves still fit one per
     // SIMD.  Measured at 4096 envs, us per step, plain / replicated: tron1_pf_ee 55.8 / 53.7, tron1_sf 52.3 / 50.7, tron1_pf 43.4 / 43.4;
@@ -370,13 +382,13 @@ template <int LEGS, int JPL> static LgPlan plan(const LgEngine *h, uint32_t ph, 
             add(K::quad_pre_sim_post, qgrid);
         } else if (LEGS == 4 && pre && rest == PR) {
             const int prof = task_profile(h, false);
-            add(prof == 0 ? K::quad_all : rs(prof) ? K::quad_prof_rs[prof - 1] : K::quad_prof[prof - 1], qgrid);
+            add(prof == LG_PROF_NONE ? K::quad_all : rs(prof) ? K::quad_prof_rs[prof - 1] : K::quad_prof[prof - 1], qgrid);
         } else if (LEGS == 2 && pre && rest == PR && sw[SW_BIPED_FUSE] != 0) {
             // biped (TRON1 point foot): the whole step in one launch too -- the leg-per-lane MDP body in the tail, four replicas of the
             // wave's 16 leg-lanes (8 envs) -- unless the job-wide CaT flag has to pass between the phases (lg_step refuses that fused).
-            // LG_BIPED_FUSE=0: two launches.  PROF 6: workgroups of two waves per group of 8 envs (lg_quad.h DUO: both run the physics,
+            // LG_BIPED_FUSE=0: two launches.  TRON1_PF_EE: workgroups of two waves per group of 8 envs (lg_quad.h DUO: both run the physics,
             // then split the tail); LG_BIPED_TAIL=0: the leg-per-lane MDP body in the tail even where the component-layout tail applies
-            if (hfb && task_profile(h, false) == 6 && sw[SW_BIPED_TAIL] != 0) add(K::biped_all_ee, qgrid);
+            if (hfb && task_profile(h, false) == LG_PROF_TRON1_PF_EE && sw[SW_BIPED_TAIL] != 0) add(K::biped_all_ee, qgrid);
             else add(hfb ? K::biped_all_hf : K::biped_all, qgrid);
         } else {   // physics, then the MDP phases as a second launch (84.7 vs 90.6 us for tron1_pf_ee: 8 envs per wave there)
             add(K::phys[pre][hfb], qgrid);
@@ -388,12 +400,12 @@ template <int LEGS, int JPL> static LgPlan plan(const LgEngine *h, uint32_t ph, 
         // golden replays through the benchmarked tails (tests/test_gpu_mdp.py, tail = "fused-profile"): the component-layout tail of the task's
         // profile on injected read-backs and uniforms (lg_quad.h INJ); a task outside every profile takes the leg-per-lane launch below
         const int prof = task_profile(h, true);
-        if (LEGS == 4 && prof != 0) { add(rs(prof) ? K::inj_rs[prof - 1] : K::inj[prof - 1], qgrid); return pl; }
-        if (LEGS == 2 && prof == 6) { add(K::inj_biped, qgrid); return pl; }
+        if (LEGS == 4 && prof != LG_PROF_NONE) { add(rs(prof) ? K::inj_rs[prof - 1] : K::inj[prof - 1], qgrid); return pl; }
+        if (LEGS == 2 && prof == LG_PROF_TRON1_PF_EE) { add(K::inj_biped, qgrid); return pl; }
     }
     switch (ph) {
     case LG_PHASE_ALL:
-        if (LEGS == 4 && JPL == 3 && task_profile(h, false) == 1) add(K::all_flat, grid);   // large go2 batches: same FLAT constants
+        if (LEGS == 4 && JPL == 3 && task_profile(h, false) == LG_PROF_GO2_FLAT) add(K::all_flat, grid);   // large go2 batches: same FLAT constants
         else add(K::all, grid);
         break;
     case LG_PHASE_SIM: add(K::sim, grid); break;

@@ -4,7 +4,7 @@
 // leg-per-lane ones (lg_kernel.h) and do not include lg_quad.h, so an edit there leaves their objects valid.
 //
 // The host side (lg_host.hip) calls the launchers declared in lg_shared.h; every instantiation it names must appear in exactly
-// one group below (a missing one is a link error, not a run-time surprise).
+// one group below (a missing one is a link error, not a run-time surprise).  PROF literals: the comments name them (lg_shared.h).
 #ifndef LG_GROUP
 #error "compile with -DLG_GROUP=<0..21> (hcr_genesis_lr_cl_amd/build.py)"
 #endif
@@ -14,20 +14,21 @@
 
 template <int LEGS, bool PRE, unsigned MPH, int PROF, int JPL>
 void lg_launch_quad(dim3 grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const KParams &p) {
-    const dim3 block(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET) ? 2 * BLOCK : BLOCK);   // PROF 6: two waves per group of envs (lg_quad.h DUO)
+    const dim3 block(quad_block(PROF, MPH));
     if (e0 || e1) hipExtLaunchKernelGGL((quad_sim_kernel<LEGS, PRE, MPH, PROF, JPL>), grid, block, 0, st, e0, e1, 0, p);
     else hipLaunchKernelGGL((quad_sim_kernel<LEGS, PRE, MPH, PROF, JPL>), grid, block, 0, st, p);
 }
 #define QUAD(...) template void lg_launch_quad<__VA_ARGS__>(dim3, hipStream_t, hipEvent_t, hipEvent_t, const KParams &);
 template <int LEGS, int PROF>
 void lg_launch_quad_inj(dim3 grid, hipStream_t st, const KParams &p) {
-    hipLaunchKernelGGL((quad_sim_kernel<LEGS, true, LG_PHASE_POST | LG_PHASE_RESET, PROF, 3, true>), grid, dim3(PROF == 6 ? 2 * BLOCK : BLOCK), 0, st, p);
+    constexpr unsigned PR = LG_PHASE_POST | LG_PHASE_RESET;
+    hipLaunchKernelGGL((quad_sim_kernel<LEGS, true, PR, PROF, 3, true>), grid, dim3(quad_block(PROF, PR)), 0, st, p);
 }
 #define QUAD_INJ(...) template void lg_launch_quad_inj<__VA_ARGS__>(dim3, hipStream_t, const KParams &);
 template <int LEGS, int PROF, bool INJ>
 void lg_launch_quad_rs(dim3 grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const KParams &p) {
     constexpr unsigned PR = LG_PHASE_POST | LG_PHASE_RESET;
-    const dim3 block(PROF == 6 ? 2 * BLOCK : BLOCK);
+    const dim3 block(quad_block(PROF, PR));
     if (e0 || e1) hipExtLaunchKernelGGL((quad_sim_kernel<LEGS, true, PR, PROF, 3, INJ, true>), grid, block, 0, st, e0, e1, 0, p);
     else hipLaunchKernelGGL((quad_sim_kernel<LEGS, true, PR, PROF, 3, INJ, true>), grid, block, 0, st, p);
 }
@@ -45,26 +46,26 @@ void lg_launch_env(dim3 grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1, cons
 #endif
 
 // ---- component per lane: quad_sim_kernel<LEGS, PRE, MDP phases in the tail, PROF, JPL> ----
-#if LG_GROUP == 0      // go2 on the plane, whole step in one launch (the headline kernel); PRE | SIM | POST of the generic tail
+#if LG_GROUP == 0      // go2 on the plane, whole step in one launch (GO2_FLAT, the headline kernel); PRE | SIM | POST of the generic tail (NONE)
 QUAD(4, true, 12u, 1, 3) QUAD(4, true, 4u, 0, 3)
-#elif LG_GROUP == 1    // go2_wtw, whole step
+#elif LG_GROUP == 1    // go2_wtw, whole step (GO2_WTW)
 QUAD(4, true, 12u, 2, 3)
-#elif LG_GROUP == 2    // go2_ee, whole step
+#elif LG_GROUP == 2    // go2_ee, whole step (GO2_EE)
 QUAD(4, true, 12u, 3, 3)
-#elif LG_GROUP == 3    // go2_ts / go2_cts / go2_dreamwaq (observation programs), whole step
+#elif LG_GROUP == 3    // go2_ts / go2_cts / go2_dreamwaq, whole step (GO2_PROGRAM)
 QUAD(4, true, 12u, 4, 3)
-#elif LG_GROUP == 4    // any other quadruped task, whole step (leg-per-lane MDP body in the tail)
+#elif LG_GROUP == 4    // any other quadruped task, whole step (NONE: leg-per-lane MDP body in the tail)
 QUAD(4, true, 12u, 0, 3)
-#elif LG_GROUP == 5    // quadruped physics only (go2_cat, split launches of the tests)
-QUAD(4, true, 0u, 0, 3) QUAD(4, true, 0u, 3, 3) QUAD(4, false, 0u, 0, 3) QUAD(4, false, 0u, 3, 3)
-#elif LG_GROUP == 6    // biped physics (three joints per leg)
-QUAD(2, true, 0u, 0, 3) QUAD(2, true, 0u, 3, 3) QUAD(2, false, 0u, 0, 3) QUAD(2, false, 0u, 3, 3)
-#elif LG_GROUP == 7    // biped physics (four joints per leg: TRON1 sole foot)
+#elif LG_GROUP == 5    // quadruped physics only (go2_cat, split launches of the tests): NONE, NONE_HF (heightfield bound)
+QUAD(4, true, 0u, 0, 3) QUAD(4, true, 0u, 5, 3) QUAD(4, false, 0u, 0, 3) QUAD(4, false, 0u, 5, 3)
+#elif LG_GROUP == 6    // biped physics (three joints per leg): NONE, NONE_HF
+QUAD(2, true, 0u, 0, 3) QUAD(2, true, 0u, 5, 3) QUAD(2, false, 0u, 0, 3) QUAD(2, false, 0u, 5, 3)
+#elif LG_GROUP == 7    // biped physics (four joints per leg: TRON1 sole foot): NONE
 QUAD(2, true, 0u, 0, 4) QUAD(2, false, 0u, 0, 4)
-#elif LG_GROUP == 8    // biped, whole step in one launch (TRON1 point foot): leg-per-lane MDP body in the tail (0, 5: heightfield bound); tron1_pf_ee's component-layout tail (6)
+#elif LG_GROUP == 8    // biped, whole step in one launch (TRON1 point foot): leg-per-lane MDP body in the tail (NONE, NONE_HF); tron1_pf_ee's tail (TRON1_PF_EE)
 QUAD(2, true, 12u, 0, 3) QUAD(2, true, 12u, 5, 3) QUAD(2, true, 12u, 6, 3)
-// ---- leg per lane: env_step_kernel<LEGS, PHASES, PROF, JPL, REPL> ----
-#elif LG_GROUP == 9    // whole step, quadruped (large batches)
+// ---- leg per lane: env_step_kernel<LEGS, PHASES, PROF, JPL, REPL>, PROF NONE unless noted ----
+#elif LG_GROUP == 9    // whole step, quadruped (large batches): NONE, GO2_FLAT
 ENV(4, 15u, 0, 3, false) ENV(4, 15u, 1, 3, false)
 #elif LG_GROUP == 10    // whole step, biped
 ENV(2, 15u, 0, 3, false) ENV(2, 15u, 0, 4, false)
@@ -80,14 +81,14 @@ ENV_PHASES(4, 3)
 ENV_PHASES(2, 3)
 #elif LG_GROUP == 16   // ... sole-foot biped
 ENV_PHASES(2, 4)
-#elif LG_GROUP == 17   // the component-layout tails on injected read-backs and uniforms (golden replays through the benchmarked tails)
+#elif LG_GROUP == 17   // the component-layout tails (GO2_FLAT .. GO2_PROGRAM, TRON1_PF_EE) on injected read-backs and uniforms (golden replays)
 QUAD_INJ(4, 1) QUAD_INJ(4, 2) QUAD_INJ(4, 3) QUAD_INJ(4, 4) QUAD_INJ(2, 6)
 // ---- the whole step / the golden-replay form with the profile's default reward set as a compile-time constant (lg_quad.h RS) ----
-#elif LG_GROUP == 18   // go2 (the headline kernel of the default task), go2_wtw
+#elif LG_GROUP == 18   // go2 (GO2_FLAT, the headline kernel of the default task), go2_wtw (GO2_WTW)
 QUAD_RS(4, 1, false) QUAD_RS(4, 2, false)
 #elif LG_GROUP == 19   // ... on injected read-backs (golden replays)
 QUAD_RS(4, 1, true) QUAD_RS(4, 2, true)
-#elif LG_GROUP == 20   // go2_ee, the go2 rough heads
+#elif LG_GROUP == 20   // go2_ee (GO2_EE), the go2 rough heads (GO2_PROGRAM)
 QUAD_RS(4, 3, false) QUAD_RS(4, 4, false)
 #elif LG_GROUP == 21   // ... on injected read-backs
 QUAD_RS(4, 3, true) QUAD_RS(4, 4, true)

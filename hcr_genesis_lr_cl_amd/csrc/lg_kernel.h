@@ -222,15 +222,15 @@ enum { XA = 0, XLA = 3, XLLA = 6, XQ = 9, XQD = 12, XLQD = 15, XTQ = 18, XFL = 2
 // The body of the leg-per-lane step.  FUSED = called from the tail of quad_sim_kernel (lg_quad.h) by the first 16 lanes of
 // the wave, one per leg of the wave's envs: the model table, the hot constants and the command ranges are already in
 // LDS, `vtid` is the leg-lane index and nothing is staged here.
-// FLAT: the launch is known (host-checked, `flat_profile`) to be the plain go2-on-a-plane task -- one unstacked 45-wide
-// observation, no privileged output, no gait clock, no terrain, no task extras: those switches become compile-time constants
-// and every other task's code drops out of the instantiation (fewer scalar registers, a shorter tail).
-// PROF 2 (host-checked, `wtw_profile`): the go2_wtw task on the plane -- gait clock and 5-frame stacks stay, terrain and the other
-// tasks' packaging drop out.
+// PROF: LG_PROF_NONE, or LG_PROF_GO2_FLAT (FLAT) where the launch is known (host-checked, lg_host.hip flat_profile) to be the plain
+// go2-on-a-plane task -- one unstacked 45-wide observation, no privileged output, no gait clock, no terrain, no task extras: those
+// switches become compile-time constants and every other task's code drops out of the instantiation (fewer scalar registers, a
+// shorter tail).  The other profiles' tails are quad_sim_kernel's own (lg_quad.h); its generic tail calls this body with NONE.
 // JPL: joints per leg of the serial chains (3: go2, TRON1 point foot; 4: TRON1 sole foot, whose last body is the foot itself).
 template <int LEGS, unsigned PH, bool FUSED, int PROF = 0, int JPL = 3, bool REPL = false>
 LG_DEV void env_step_body(const KParams &p, uint4 *sMraw, int *sHot, float *sStF, const float *sX, const int vtid, const int vlane) {
-    constexpr bool FLAT = PROF == 1, WTWP = PROF == 2, PLANE = FLAT || WTWP, EEP = PROF == 3, PRGP = PROF == 4, ROUGHQ = EEP || PRGP;
+    static_assert(PROF == LG_PROF_NONE || PROF == LG_PROF_GO2_FLAT, "the leg-per-lane body: no profile, or go2 on the plane");
+    constexpr bool FLAT = PROF == LG_PROF_GO2_FLAT;
     constexpr bool DO_PRE = (PH & LG_PHASE_PRE) != 0, DO_SIM = (PH & LG_PHASE_SIM) != 0;
     constexpr bool DO_POST = (PH & LG_PHASE_POST) != 0, DO_RESET = (PH & LG_PHASE_RESET) != 0;
     constexpr int A = LEGS * JPL;
@@ -369,7 +369,7 @@ LG_DEV void env_step_body(const KParams &p, uint4 *sMraw, int *sHot, float *sStF
             rdof_lo[j] = T->reset_dof_lo[d0 + j]; rdof_span[j] = T->reset_dof_span[d0 + j];
             nv_q[j] = T->noise_vec[9 + d0 + j]; nv_qd[j] = T->noise_vec[9 + A + d0 + j]; nv_act[j] = T->noise_vec[9 + 2 * A + d0 + j];
         }
-        if (!PLANE && !ROUGHQ && p.k.obs_layout == LG_OBS_TRON1_EE) { nv_clk[0] = T->noise_vec[9 + 3 * A + foot_slot]; nv_clk[1] = T->noise_vec[9 + 3 * A + LEGS + foot_slot]; }
+        if (!FLAT && p.k.obs_layout == LG_OBS_TRON1_EE) { nv_clk[0] = T->noise_vec[9 + 3 * A + foot_slot]; nv_clk[1] = T->noise_vec[9 + 3 * A + LEGS + foot_slot]; }
         cmd0 = B.commands[4 * e]; cmd1 = B.commands[4 * e + 1]; cmd2 = B.commands[4 * e + 2]; cmd3 = B.commands[4 * e + 3];
         ep_len = B.episode_length_buf[e];
         fail_buf = B.fail_buf[e];
@@ -378,7 +378,7 @@ LG_DEV void env_step_body(const KParams &p, uint4 *sMraw, int *sHot, float *sStF
         if (DO_RESET && B.obs_dirty) dirty_prev = B.obs_dirty[e];
         origin_pre = ld3(B.env_origins + 3 * e);
         if (!FUSED) crv = reinterpret_cast<const int *>(B.command_ranges)[min(vlane, LG_CMD_RANGE_FLOATS - 1)];
-        if (!FUSED && DO_RESET && !PLANE && !EEP && p.k.obs_layout == LG_OBS_PROGRAM)
+        if (!FUSED && DO_RESET && !FLAT && p.k.obs_layout == LG_OBS_PROGRAM)
             prw = reinterpret_cast<const int *>(vlane < 26 ? &T->priv_prog : &T->labels_prog)[vlane < 26 ? vlane : min(vlane - 26, 25)];
         if (lead) {
 #pragma unroll
@@ -400,7 +400,7 @@ LG_DEV void env_step_body(const KParams &p, uint4 *sMraw, int *sHot, float *sStF
     float hts[HMAX];
 #pragma unroll
     for (int i = 0; i < HMAX; i++) hts[i] = 0.f;
-    const int P = PLANE ? 0 : p.k.o_n_height_points;
+    const int P = FLAT ? 0 : p.k.o_n_height_points;
     const bool hreg = P <= HMAX * LEGS;
     float foot_hmean = 0.f, foot_hmax = 0.f;  // mean / max of the 9 terrain heights around this lane's foot (a8)
     float mean_height = 0.f;         // mean over the height-sample grid of (base_z - h) is formed from this (a7)
@@ -594,7 +594,7 @@ LG_DEV void env_step_body(const KParams &p, uint4 *sMraw, int *sHot, float *sStF
                 const V3 r = P + mul(R, sp.p);
                 const float rad = sp.r;
                 float h; V3 n;
-                if (PLANE) { h = 0.f; n = v3(0.f, 0.f, 1.f); } else terrain_at(O, p.hf, pos.x + r.x, pos.y + r.y, h, n);
+                if (FLAT) { h = 0.f; n = v3(0.f, 0.f, 1.f); } else terrain_at(O, p.hf, pos.x + r.x, pos.y + r.y, h, n);
                 const float depth = rad - (pos.z + r.z - h) * n.z - dref;
                 if (depth > -margin) {
                     const V3 v = V.l + cross(V.a, r);
@@ -665,7 +665,7 @@ LG_DEV void env_step_body(const KParams &p, uint4 *sMraw, int *sHot, float *sStF
                         {
                             const V3 rc = K[j].P + mul(K[j].R, foot_c_loc);
                             float hc; V3 nc;
-                            if (PLANE) { hc = 0.f; nc = v3(0.f, 0.f, 1.f); } else terrain_at(O, p.hf, pos.x + rc.x, pos.y + rc.y, hc, nc);
+                            if (FLAT) { hc = 0.f; nc = v3(0.f, 0.f, 1.f); } else terrain_at(O, p.hf, pos.x + rc.x, pos.y + rc.y, hc, nc);
                             const float dc = foot_r - (pos.z + rc.z - hc) * nc.z;
                             if (dc > 0.f) { dref = dc; vref = dot(K[j].V.l + cross(K[j].V.a, rc), nc); }
                         }
@@ -739,7 +739,7 @@ LG_DEV void env_step_body(const KParams &p, uint4 *sMraw, int *sHot, float *sStF
             {
                 const V3 r = K[JPL - 1].P + mul(K[JPL - 1].R, foot_c_loc);
                 float h;
-                if (PLANE) { h = 0.f; cn = v3(0.f, 0.f, 1.f); } else terrain_at(O, p.hf, pos.x + r.x, pos.y + r.y, h, cn);
+                if (FLAT) { h = 0.f; cn = v3(0.f, 0.f, 1.f); } else terrain_at(O, p.hf, pos.x + r.x, pos.y + r.y, h, cn);
                 depth = foot_r - (pos.z + r.z - h) * cn.z;
                 fact = depth > -margin;
                 cp = r - cn * foot_r;
@@ -882,7 +882,7 @@ LG_DEV void env_step_body(const KParams &p, uint4 *sMraw, int *sHot, float *sStF
 
         STAMP(4);
         __builtin_amdgcn_s_waitcnt(0x0F70);   // vmcnt(0): the start-of-kernel loads have landed; nothing queues behind the read-back stores (see lg_quad.h)
-        if (!PLANE && p.k.cat_enable) {   // go2_cat's job-wide "some joint faster than 4 rad/s" flag (LG_CR_ANY_FAST): every wave that sees one raises it
+        if (!FLAT && p.k.cat_enable) {   // go2_cat's job-wide "some joint faster than 4 rad/s" flag (LG_CR_ANY_FAST): every wave that sees one raises it
             bool fast = false;
 #pragma unroll
             for (int j = 0; j < JPL; j++) fast = fast || fabsf(qd[j]) > 4.0f;
@@ -1123,10 +1123,10 @@ LG_DEV void env_step_body(const KParams &p, uint4 *sMraw, int *sHot, float *sStF
     const auto hc_resample_steps = HOT(resample_steps);
     const auto hc_heading_command = HOT(heading_command);
     const auto hc_push_interval = HOT(push_interval);
-    const auto hc_obs_layout = FLAT ? (HOT_T(obs_layout))(LG_OBS_GO2) : (WTWP ? (HOT_T(obs_layout))(LG_OBS_GO2_WTW) : (EEP ? (HOT_T(obs_layout))(LG_OBS_GO2_EE) : (PRGP ? (HOT_T(obs_layout))(LG_OBS_PROGRAM) : HOT(obs_layout))));
-    const auto hc_gait_mode = (FLAT || ROUGHQ) ? (HOT_T(gait_mode))(0) : (WTWP ? (HOT_T(gait_mode))(1) : HOT(gait_mode));
+    const auto hc_obs_layout = FLAT ? (HOT_T(obs_layout))(LG_OBS_GO2) : HOT(obs_layout);
+    const auto hc_gait_mode = FLAT ? (HOT_T(gait_mode))(0) : HOT(gait_mode);
     const auto hc_add_noise = HOT(add_noise);
-    const auto hc_double_shift = (FLAT || EEP) ? (HOT_T(double_shift))(0) : (WTWP ? (HOT_T(double_shift))(1) : HOT(double_shift));
+    const auto hc_double_shift = FLAT ? (HOT_T(double_shift))(0) : HOT(double_shift);
     const auto hc_obs_frame = HOT(obs_frame);
     const auto hc_obs_stack = FLAT ? (HOT_T(obs_stack))(1) : HOT(obs_stack);
     const auto hc_obs_slack = FLAT ? (HOT_T(obs_slack))(0) : HOT(obs_slack);
@@ -1141,14 +1141,14 @@ LG_DEV void env_step_body(const KParams &p, uint4 *sMraw, int *sHot, float *sStF
     const auto hc_env_id_offset = HOT(env_id_offset);
     const auto hc_heights_offset = HOT(heights_offset);
     const auto hc_obs_scale_height = HOT(obs_scale_height);
-    const auto hc_noise_act0 = (PLANE || ROUGHQ) ? (HOT_T(noise_act0))(0) : HOT(noise_act0);
+    const auto hc_noise_act0 = FLAT ? (HOT_T(noise_act0))(0) : HOT(noise_act0);
     const auto hc_about_landing_threshold = HOT(about_landing_threshold);
-    const auto hc_terrain_curriculum = PLANE ? (HOT_T(terrain_curriculum))(0) : HOT(terrain_curriculum);
-    const auto hc_custom_origins = PLANE ? (HOT_T(custom_origins))(0) : HOT(custom_origins);
-    const auto hc_sit_percent = (PLANE || ROUGHQ) ? (HOT_T(sit_percent))(0) : HOT(sit_percent);
-    const auto hc_behavior_resample_steps = (FLAT || ROUGHQ) ? (HOT_T(behavior_resample_steps))(0) : HOT(behavior_resample_steps);
+    const auto hc_terrain_curriculum = FLAT ? (HOT_T(terrain_curriculum))(0) : HOT(terrain_curriculum);
+    const auto hc_custom_origins = FLAT ? (HOT_T(custom_origins))(0) : HOT(custom_origins);
+    const auto hc_sit_percent = FLAT ? (HOT_T(sit_percent))(0) : HOT(sit_percent);
+    const auto hc_behavior_resample_steps = FLAT ? (HOT_T(behavior_resample_steps))(0) : HOT(behavior_resample_steps);
     const auto hc_heights_clip_scale = HOT(heights_clip_scale);
-    const auto hc_num_labels = PLANE ? (HOT_T(num_labels))(0) : HOT(num_labels);
+    const auto hc_num_labels = FLAT ? (HOT_T(num_labels))(0) : HOT(num_labels);
     asm volatile("" ::: "memory");
     if (STASH || FUSED) {   // bring the MDP working set back from LDS (fused: prefetched by quad_sim_kernel's prologue)
         const int t = threadIdx.x;
@@ -1203,7 +1203,7 @@ LG_DEV void env_step_body(const KParams &p, uint4 *sMraw, int *sHot, float *sStF
     for (int j = 0; j < JPL; j++) cat_lim[j] = cat_tql[j] = 0.f;
 #pragma unroll
     for (int k = 0; k < LG_NUM_CSTR; k++) cat_cnt[k] = 0.f;
-    if (DO_POST && !PLANE && !EEP && p.k.cat_enable) {
+    if (DO_POST && !FLAT && p.k.cat_enable) {
 #pragma unroll
         for (int j = 0; j < JPL; j++) { cat_lim[j] = T->dof_vel_limits[d0 + j]; cat_tql[j] = M->effort[d0 + j]; }
         cat_ar = T->cat_action_rate; cat_minh = T->cat_min_base_height; cat_maxg = T->cat_max_projected_gravity; cat_sp = T->cat_soft_p;
@@ -1310,7 +1310,7 @@ LG_DEV void env_step_body(const KParams &p, uint4 *sMraw, int *sHot, float *sStF
         //      soft_p for a violated soft / style one (constraint_manager.py:25-74 with binary inputs), per-episode violation counts
         float cat_keep = 1.f;     // (1 - p), applied to the reward before the positive clip (go2_cat.py:219-223)
         float cstr_p = 0.f;
-        if (!PLANE && !EEP && p.k.cat_enable) {
+        if (!FLAT && p.k.cat_enable) {
             int c_tq = 0, c_qd = 0, c_ar = 0, lo_any = 0, hi_any = 0, c_fast = 0;
 #pragma unroll
             for (int j = 0; j < JPL; j++) {

@@ -395,6 +395,9 @@ LG_DEV void blank_histories(unsigned long long rm, int e, float *obs, size_t oro
 
 }  // namespace q4
 
+// Threads per workgroup of quad_sim_kernel: two waves for the tron1_pf_ee tail (DUO), one otherwise
+constexpr int quad_block(int prof, unsigned mph) { return prof == LG_PROF_TRON1_PF_EE && mph == (LG_PHASE_POST | LG_PHASE_RESET) ? 2 * BLOCK : BLOCK; }
+
 // ---------------------------------------------------------------------------------------------
 // MPH: MDP phases (LG_PHASE_POST, LG_PHASE_POST | LG_PHASE_RESET or 0) run in the tail of the same launch by the first
 // 16 lanes of each wave, one per leg of the wave's envs, through env_step_body: one launch per control step, no second
@@ -406,18 +409,28 @@ LG_DEV void blank_histories(unsigned long long rm, int e, float *obs, size_t oro
 // component-layout tails themselves -- the sub-step loop and the read-back are skipped, what they would have left in registers (twists,
 // torques, contact forces, feet, terrain samples) is loaded from the bound buffers the test filled with the reference's recorded values,
 // and every uniform comes from LgBuffers.rand_in instead of Philox.  The MDP statements are the very ones the product instantiation runs.
-// RS (host-checked: the task's reward set IS its profile's default, lg_host.hip rs_mask): the set of active reward terms is a compile-time
+// RS (host-checked: the task's reward set IS its profile's default, lg_host.hip plan()'s `rs`): the set of active reward terms is a compile-time
 // constant.  The terms are evaluated behind one scalar test each -- thirty-two branches that cut the reward section into as many basic
 // blocks, each term's reduction over the env's lanes (four dependent DPP adds with their wait states) alone in its own; with the set known
 // the unused terms are gone and the others interleave (go2: -0.5 us).  Any other set of terms runs the RS = false instantiation.
 template <int LEGS, bool DO_PRE, unsigned MPH, int PROF = 0, int JPL = 3, bool INJ = false, bool RS = false>
-__global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET) ? 2 * BLOCK : BLOCK) void quad_sim_kernel(KParams p) {
+__global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams p) {
     using namespace q4;
     const unsigned tl_ = threadIdx.x & 63u;   // lane of the wave (a workgroup is one wave, two for the DUO tail below)
-    static_assert(JPL == 3 || (JPL == 4 && LEGS == 2 && MPH == 0 && PROF == 0), "four-joint legs: biped physics only");
-    static_assert(!INJ || (DO_PRE && MPH == (LG_PHASE_POST | LG_PHASE_RESET) && (PROF == 1 || PROF == 2 || PROF == 3 || PROF == 4 || PROF == 6)),
-                  "injected read-backs: the component-layout tails only");
-    constexpr bool FLAT = PROF == 1, PLANE = PROF == 1 || PROF == 2;   // host-checked task profiles (lg_kernel.h flat_profile / wtw_profile)
+    static_assert(JPL == 3 || (JPL == 4 && LEGS == 2 && MPH == 0 && PROF == LG_PROF_NONE), "four-joint legs: biped physics only");
+    constexpr bool FLAT = PROF == LG_PROF_GO2_FLAT, PLANE = FLAT || PROF == LG_PROF_GO2_WTW;   // host-checked (lg_host.hip flat_profile / wtw_profile)
+    constexpr bool QTAIL = (PLANE || PROF == LG_PROF_GO2_EE || PROF == LG_PROF_GO2_PROGRAM) && MPH == (LG_PHASE_POST | LG_PHASE_RESET);   // MDP phases in component layout on all 64 lanes (below)
+    constexpr bool WQ = PROF == LG_PROF_GO2_WTW && QTAIL;   // ... of the go2_wtw task: gait clock, behaviour targets, 61 x 5 | 99 x 5 observation stacks
+    constexpr bool PQ = PROF == LG_PROF_GO2_PROGRAM && QTAIL;   // ... of the rough heads with observation programs (go2_ts / go2_cts / go2_dreamwaq): go2_ee's MDP, other packaging
+    constexpr bool EQ = (PROF == LG_PROF_GO2_EE || PROF == LG_PROF_GO2_PROGRAM) && QTAIL;   // ... of the go2_ee family: heightfield, terrain curriculum, 45 x 20 | critic x 5 stacks, labels
+    constexpr bool SQ = WQ || EQ;             // stacked observations, PD-gain randomisation, root twist draws
+    // TRON1_PF_EE (host-checked, lg_host.hip biped_profile): the tron1_pf_ee task -- point-foot biped on a heightfield -- with its MDP
+    // phases in component layout on the env's EIGHT lanes (two quads), the second block below
+    constexpr bool BQ = PROF == LG_PROF_TRON1_PF_EE && MPH == (LG_PHASE_POST | LG_PHASE_RESET);
+    static_assert(PROF != LG_PROF_TRON1_PF_EE || (LEGS == 2 && JPL == 3), "tron1_pf_ee is the three-joint biped's tail");
+    constexpr bool CTAIL = QTAIL || BQ;       // some component-layout tail: no leg-per-lane stash, no LDS hand-off
+    constexpr bool GTAIL = MPH != 0 && !CTAIL;   // the generic tail: env_step_body on the wave's 16 leg-lanes (the end of the kernel)
+    static_assert(!INJ || (DO_PRE && CTAIL), "injected read-backs: the component-layout tails only");
     constexpr unsigned RS_MASK = lg_default_reward_mask(PROF);
     static_assert(!RS || RS_MASK != 0u, "RS: the profile has a default reward set");
     constexpr int A = JPL * LEGS;
@@ -440,8 +453,7 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
     // by the wave, one row read per lane) instead of being derived from the staged model table on every launch (628 instructions).  The model
     // table itself is staged only where something still walks it: four-joint legs, and the generic tail (env_step_body in the same launch).
     constexpr bool USE_LT = JPL == 3;
-    constexpr bool NEED_M = !USE_LT || (MPH != 0 && !(((PROF == 1 || PROF == 2 || PROF == 3 || PROF == 4) && MPH == (LG_PHASE_POST | LG_PHASE_RESET)) ||
-                                                     (PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET))));
+    constexpr bool NEED_M = !USE_LT || GTAIL;
     const LgModelDesc GAS *Mg = KPTR(const LgModelDesc GAS *, offsetof(KParams, M));
     __shared__ __attribute__((aligned(16))) uint4 sMraw[NEED_M ? MODEL_STG * BLOCK : 1];
     __shared__ __attribute__((aligned(16))) uint4 sLT[USE_LT ? LG_LT_STG * BLOCK : 1];
@@ -472,13 +484,13 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
     unsigned long long _stamp0 = 0; (void)_stamp0;
     STAMP(0);
     STAMPB(4096);
-    // DUO (the tron1_pf_ee tail, PROF 6): a workgroup of TWO waves per group of 8 envs.  4096 biped envs are 512 waves on 1024 SIMDs; with
+    // DUO (the tron1_pf_ee tail): a workgroup of TWO waves per group of 8 envs.  4096 biped envs are 512 waves on 1024 SIMDs; with
     // two, both waves run the same physics on the same envs (role 0 owns its stores) and then SPLIT the MDP tail -- role 0: rewards,
     // episode sums, the noisy actor frames; role 1: the critic frames, labels, pushes, reset / task state -- so the serial tail of the
     // wave that ends the launch is about half as long.  Being one workgroup the two are resident together whatever else runs on the
     // chip; barriers order their accesses to the shared state: every start-of-kernel load of both has returned before either stores
     // (below), and role 0's read-back stores are out before role 1's reset stores to the same arrays.
-    constexpr bool DUO = PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET);
+    constexpr bool DUO = quad_block(PROF, MPH) == 2 * BLOCK;
     const int wg = lg_wg();   // XCD-aware (lg_kernel.h)
     const int role = DUO ? (int)(threadIdx.x >> 6) : 0;
     const int tid = wg * BLOCK + tl_;
@@ -562,7 +574,7 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
     int crv = 0;
     if (MPH != 0) crv = reinterpret_cast<const int GAS *>(k_command_ranges)[min((int)tl_, LG_CMD_RANGE_FLOATS - 1)];
     int prw = 0;   // observation programs for the MDP tail (lg_kernel.h PRG_I / PRG_F)
-    if ((MPH & LG_PHASE_RESET) != 0 && (PROF == 4 || ((PROF == 0 || PROF == 5) && KINT(k.obs_layout) == LG_OBS_PROGRAM))) {
+    if ((MPH & LG_PHASE_RESET) != 0 && (PROF == LG_PROF_GO2_PROGRAM || ((PROF == LG_PROF_NONE || PROF == LG_PROF_NONE_HF) && KINT(k.obs_layout) == LG_OBS_PROGRAM))) {
         const int tl = (int)tl_;
         prw = reinterpret_cast<const int GAS *>(tl < 26 ? &kT->priv_prog : &kT->labels_prog)[tl < 26 ? tl : min(tl - 26, 25)];
     }
@@ -570,18 +582,8 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
     // (env_step_body<.., FUSED>) reads it back after the physics instead of paying the round trips then.  Layout = the
     // stash of env_step_body (NST values x 16 lanes).
     constexpr int NST = LG_R_COUNT + 36;
-    constexpr bool QTAIL = (FLAT || PROF == 2 || PROF == 3 || PROF == 4) && MPH == (LG_PHASE_POST | LG_PHASE_RESET);   // MDP phases in component layout on all 64 lanes (below)
-    constexpr bool WQ = PROF == 2 && QTAIL;   // ... of the go2_wtw task: gait clock, behaviour targets, 61 x 5 | 99 x 5 observation stacks
-    constexpr bool PQ = PROF == 4 && QTAIL;   // ... of the rough heads with observation programs (go2_ts / go2_cts / go2_dreamwaq): go2_ee's MDP, other packaging
-    constexpr bool EQ = (PROF == 3 || PROF == 4) && QTAIL;   // ... of the go2_ee family: heightfield, terrain curriculum, 45 x 20 | critic x 5 stacks, labels
-    constexpr bool SQ = WQ || EQ;             // stacked observations, PD-gain randomisation, root twist draws
-    // PROF 6 (host-checked, lg_host.hip biped_profile): the tron1_pf_ee task -- point-foot biped on a heightfield -- with its MDP phases in
-    // component layout on the env's EIGHT lanes (two quads), the second block below
-    constexpr bool BQ = PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET);
-    static_assert(PROF != 6 || (LEGS == 2 && JPL == 3), "PROF 6 is the three-joint biped's tail");
-    constexpr bool CTAIL = QTAIL || BQ;       // some component-layout tail: no leg-per-lane stash, no LDS hand-off
-    __shared__ float sStF[(MPH != 0 && !CTAIL) ? NST * 16 : 1];
-    float wsv[(MPH != 0 && !CTAIL) ? NST : 1];
+    __shared__ float sStF[GTAIL ? NST * 16 : 1];
+    float wsv[GTAIL ? NST : 1];
     // QTAIL working set, one value per lane: command component c, the two episode sums this lane owns (terms ei and ei + 16 of its
     // env, ei = 4 leg + c), this lane's joint constants; per-env / per-leg scalars replicated
     static_assert(LG_R_COUNT <= 32, "two episode sums per lane");
@@ -633,7 +635,7 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
         const int32_t GAS *tl = KB(const int32_t GAS *, terrain_levels), *tt = KB(const int32_t GAS *, terrain_types);
         if (tl) { w_lvl = tl[e]; w_type = tt[e]; }
     }
-    if (MPH != 0 && !CTAIL && tl_ < 16) {
+    if (GTAIL && tl_ < 16) {
         const LgTaskCfg GAS *T = kT;
         const int lt = wg * 16 + (int)tl_, legL = lt % LEGS, dL = 3 * legL;
         const int eL = min(lt / LEGS, N - 1);
@@ -719,7 +721,7 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
     Terr TR;
     TR.rows = PLANE ? 0 : HOT(o_terrain_rows); TR.cols = HOT(o_terrain_cols); TR.border = HOT(o_border); TR.ihs = 1.f / HOT(o_hscale);
     TR.vscale = HOT(o_vscale); TR.hf = p.hf;
-    constexpr bool HFC = PROF == 3 || PROF == 4 || PROF == 5 || PROF == 6;   // a heightfield is bound (host-checked: the rough task profiles of lg_host.hip; 5 = that and nothing else, generic tail)
+    constexpr bool HFC = PROF == LG_PROF_GO2_EE || PROF == LG_PROF_GO2_PROGRAM || PROF == LG_PROF_NONE_HF || PROF == LG_PROF_TRON1_PF_EE;   // a heightfield is bound (host-checked)
     const bool hfmode = HFC ? true : (!PLANE && TR.rows > 0);
     float lr[LT_USED];                          // this lane's row of the lane table (three-joint legs)
 #pragma unroll
@@ -2515,7 +2517,7 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
                 }
             }
             if constexpr (EQ) {
-                // observation programs (PROF 4): where the noise-free actor frame sits in the critic frame (-1: nowhere), where the "next state"
+                // observation programs (GO2_PROGRAM): where the noise-free actor frame sits in the critic frame (-1: nowhere), where the "next state"
                 // copy sits in the labels row (-1: none), whether the critic frame is clipped
                 int pfo = 0, nxo = -1;
                 float pclip = co;
@@ -2747,7 +2749,8 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
         STAMP(11);
     }
     // ---------------- MDP phases in the same launch (every other task): leg-per-lane body on the first 16 lanes -----
-    if (MPH != 0 && !CTAIL) {
+    if constexpr (GTAIL) {
+        static_assert(PROF == LG_PROF_NONE || PROF == LG_PROF_NONE_HF, "the generic tail: no profile but the heightfield");
         // hand the results to the MDP phases through LDS (layout: lg_kernel.h, XA .. XFB): leg-lane l of the tail is quad l
         // of this wave; a quad lane writes its own component.  Nothing the tail reads then comes from the arrays stored
         // above, so those stores drain in the background instead of being waited for.
@@ -2770,7 +2773,7 @@ __global__ __launch_bounds__(PROF == 6 && MPH == (LG_PHASE_POST | LG_PHASE_RESET
         // the wave's 64 lanes run the leg-per-lane body as FOUR replicas of its 16 leg-lanes (lane = 16 replica + leg-lane): every replica
         // computes the same values, replica 0 owns the state stores, and the observation section deals its stores over the replicas
         // (the four destinations of an actor-frame entry, the two of a critic entry; blanking with 64 lanes)
-        env_step_body<LEGS, MPH, true, (PROF == 5 ? 0 : PROF)>(p, sMraw, sHot, sStF, sX, wg * 16 + ((int)tl_ & 15), (int)tl_ & 15);
+        env_step_body<LEGS, MPH, true, LG_PROF_NONE>(p, sMraw, sHot, sStF, sX, wg * 16 + ((int)tl_ & 15), (int)tl_ & 15);
     }
     STAMPB(12288);
 }

@@ -2,6 +2,7 @@
 // block, the kernel argument block and the launchers of the kernel instantiations.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <initializer_list>
 #include <stdint.h>
 #include <stdio.h>
 #include <string.h>
@@ -352,6 +353,12 @@ struct KParams {
     int obs_set;         // copy of obs_buf / priv_obs_buf / labels_buf this launch writes (LgTaskCfg.obs_sets)
 };
 
+// ---- task profiles: PROF of quad_sim_kernel (lg_quad.h) and env_step_kernel (lg_kernel.h), the task switches an instantiation hard-wires
+//      (lg_host.hip's flat_profile, wtw_profile, rough_profile and biped_profile check that a task has them).  The values are part of the
+//      lg_last_kernel strings (literals in lg_inst.hip and lg_host.hip's Kernels), which bench.py reports and profiles/*.json record: never renumber.
+enum : int { LG_PROF_NONE = 0, LG_PROF_GO2_FLAT = 1, LG_PROF_GO2_WTW = 2, LG_PROF_GO2_EE = 3, LG_PROF_GO2_PROGRAM = 4,
+             LG_PROF_NONE_HF = 5,        // a heightfield is bound, nothing else hard-wired
+             LG_PROF_TRON1_PF_EE = 6 };  // GO2_EE / GO2_PROGRAM (the go2 rough heads) / TRON1_PF_EE: on a heightfield too
 
 // ---- launchers.  The kernel templates (lg_kernel.h: env_step_kernel, lg_quad.h: quad_sim_kernel) are instantiated in lg_inst.hip, which is
 //      compiled once per instantiation GROUP (-DLG_GROUP=g, in parallel: one translation unit with every instantiation took over three
@@ -367,6 +374,17 @@ void lg_launch_quad_inj(dim3 grid, hipStream_t st, const KParams &p);
 // go2 (legged_gym/envs/go2/go2_config.py), go2_wtw, go2_ee and the go2 rough heads (one set).  A task whose set equals its profile's runs
 // the instantiation that has it as a compile-time constant (lg_quad.h RS): whole step (INJ = false) or the golden-replay form (INJ = true).
 // (tron1_pf_ee, 0x2cb38577: +-0.1 us, not kept.)
-constexpr unsigned lg_default_reward_mask(int prof) { return prof == 1 ? 0x26a2296fu : (prof == 2 ? 0x7f2c0967u : ((prof == 3 || prof == 4) ? 0x242a6567u : 0u)); }
+constexpr unsigned lg_default_reward_mask(int prof) {
+    return prof == LG_PROF_GO2_FLAT ? 0x26a2296fu : prof == LG_PROF_GO2_WTW ? 0x7f2c0967u : (prof == LG_PROF_GO2_EE || prof == LG_PROF_GO2_PROGRAM) ? 0x242a6567u : 0u;
+}
+// The reward terms a profile's component-layout tail does not carry: a task with one of them active is outside the profile (lg_host.hip).
+constexpr unsigned lg_rbits(std::initializer_list<int> terms) { unsigned m = 0; for (int k : terms) m |= 1u << k; return m; }
+constexpr unsigned lg_tail_reward_excluded(int prof) {
+    constexpr unsigned flat = lg_rbits({LG_R_BIPED_PERIODIC_GAIT, LG_R_QUAD_PERIODIC_GAIT, LG_R_FEET_DISTANCE, LG_R_TRACKING_BASE_HEIGHT,
+                                        LG_R_TRACKING_FOOT_CLEARANCE, LG_R_TRACKING_ORIENTATION});
+    return prof == LG_PROF_GO2_FLAT ? flat : prof == LG_PROF_GO2_WTW ? lg_rbits({LG_R_BIPED_PERIODIC_GAIT, LG_R_FEET_DISTANCE})
+         : (prof == LG_PROF_GO2_EE || prof == LG_PROF_GO2_PROGRAM) ? flat | lg_rbits({LG_R_BASE_HEIGHT})
+         : prof == LG_PROF_TRON1_PF_EE ? lg_rbits({LG_R_QUAD_PERIODIC_GAIT, LG_R_TRACKING_FOOT_CLEARANCE, LG_R_TRACKING_ORIENTATION}) : 0u;
+}
 template <int LEGS, int PROF, bool INJ>
 void lg_launch_quad_rs(dim3 grid, hipStream_t st, hipEvent_t e0, hipEvent_t e1, const KParams &p);
