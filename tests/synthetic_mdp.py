@@ -2,16 +2,15 @@
 numpy oracle (oracle/mdp_oracle.py, itself pinned to the reference by the golden replays of tests/test_mdp_oracle.py).
 
 synth_fixture(task, N, seed, steps) returns the inputs a golden fixture holds (init_*, script_* read-backs, last_*_in,
-actions_in, rand, counter, esum_override, reward names, terrain seed); record(task, fx) replays them through the task's oracle
-stepper and adds its outputs under the keys the task's check_* reads.  The result replays through the kernel steppers of
-tests/test_gpu_mdp.py exactly like a golden fixture.
+actions_in, rand, counter, esum_override, reward names, terrain seed); record(task, fx) replays them through the oracle stepper
+of tests/mdp_harness.py and adds its outputs under the keys the task's check reads.  The result replays through the kernel
+stepper exactly like a golden fixture.
 
 Every continuous quantity a decision of the MDP phases compares with a threshold is kept at least 1e-3 (relative, or absolute
 where the threshold is 0) away from it, so that a different f32 association order cannot flip the decision; the inputs are
 built one step at a time against a live oracle so that state-dependent quantities (distance from the env origin, commands
 after a resample, previous actions) can be placed too.  CPU only: no GPU import."""
 import functools
-import os
 
 import numpy as np
 
@@ -19,70 +18,16 @@ from hcr_genesis_lr_cl_amd import abi, builders
 from hcr_genesis_lr_cl_amd import config as cfgmod
 from hcr_genesis_lr_cl_amd.model_compiler import load_model
 from oracle import mdp_oracle as mo
-from tests import test_mdp_oracle as tmo
+from tests import mdp_harness as h
 
 f32 = np.float32
-TASKS = ("go2", "go2_wtw", "go2_ee", "go2_ts", "go2_cts", "go2_dreamwaq", "go2_cat", "tron1_pf", "tron1_pf_ee", "tron1_sf")
-ROUGH = ("go2_ee", "go2_ts", "go2_cts", "go2_dreamwaq", "go2_cat", "tron1_pf_ee")
-CFG = {"go2": "GO2Cfg", "go2_wtw": "GO2WTWCfg", "go2_ee": "GO2EECfg", "go2_ts": "GO2TSCfg", "go2_cts": "GO2CTSCfg",
-       "go2_dreamwaq": "GO2DreamwaqCfg", "go2_cat": "GO2CaTCfg", "tron1_pf": "TRON1PFCfg", "tron1_pf_ee": "TRON1PFEECfg"}
+TASKS = tuple(h.TASKS)
 MARGIN = 1e-3
-GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
-
-
-def task_cfg(task):
-    return tmo.sf_cfg() if task == "tron1_sf" else getattr(cfgmod, CFG[task])()
-
-
-def oracle_stepper(task):
-    """The task's oracle stepper class of tests/test_mdp_oracle.py."""
-    if task in ("go2_ts", "go2_cts", "go2_dreamwaq", "go2_cat"):
-        return type("Stepper_" + task, (tmo.EEOracleStepper,), {"head": task})
-    return {"go2": tmo.OracleStepper, "go2_wtw": tmo.WtwOracleStepper, "go2_ee": tmo.EEOracleStepper, "tron1_pf": tmo.PFOracleStepper,
-            "tron1_pf_ee": tmo.Tron1OracleStepper, "tron1_sf": tmo.SFOracleStepper}[task]
-
-
-def check_fn(task):
-    """(the task's check_*, the replay function that drives it) of tests/test_mdp_oracle.py."""
-    if task in ("go2_ts", "go2_cts", "go2_dreamwaq", "go2_cat"):
-        return tmo.check_head, tmo.replay_ee
-    return {"go2": (tmo.check_against_fixture, tmo.replay), "go2_wtw": (tmo.check_wtw, tmo.replay), "go2_ee": (tmo.check_ee, tmo.replay_ee),
-            "tron1_pf": (tmo.check_pf, tmo.replay), "tron1_sf": (tmo.check_sf, tmo.replay),
-            "tron1_pf_ee": (tmo.check_tron1, lambda st, chk, fx: tmo.replay_rough(fx, st, chk))}[task]
-
-
-INJ_TAIL = ("go2", "go2_wtw", "go2_ee", "go2_ts", "go2_cts", "go2_dreamwaq", "tron1_pf_ee")    # tasks with an INJ profile tail
-
-
-def synth_check(task, rtol=1e-5):
-    """The task's check_* at the kernel tolerances of its golden replay (tests/test_gpu_mdp.py): rtol 1e-5; atol 1e-5 for go2 and
-    go2_wtw except on the outputs that carry the yaw command (an atan2f on the device: 5e-5), 5e-5 for the others.  Env 0 of
-    go2_wtw / tron1_pf_ee is left out for the documented reason (reference index-flatten bug in the gait clock / indicator,
-    reproduced by the oracle); nothing else is."""
-    if task == "go2":
-        return lambda t, fx, out: tmo.check_against_fixture(t, fx, out, rtol, 1e-5, atol_yaw=5e-5)
-    if task == "go2_wtw":
-        return lambda t, fx, out: tmo.check_wtw(t, fx, out, rtol, 1e-5, skip_env0=True, atol_yaw=5e-5)
-    if task == "tron1_pf_ee":
-        return lambda t, fx, out: tmo.check_tron1(t, fx, out, rtol, 5e-5, skip_env0=True)
-    chk = check_fn(task)[0]
-    return lambda t, fx, out: chk(t, fx, out, rtol, 5e-5)
-
-
-def replay(task, fx, make_stepper, check):
-    """Drive `make_stepper` through `fx` with the task's replay function, checking every step with `check(t, fx, out)`."""
-    check_fn(task)[1](make_stepper, check, fx)
-
-
-class Fixture(dict):
-    """A fixture held in memory; `.files` as on the NpzFile of a golden fixture."""
-    @property
-    def files(self):
-        return list(self.keys())
 
 
 def min_steps(task):
-    T = builders.make_task_cfg(load_model(task_cfg(task).asset.name), task_cfg(task))
+    cfg = h.TASKS[task].cfg()
+    T = builders.make_task_cfg(load_model(cfg.asset.name), cfg)
     return 2 * max(int(T.obs_stack), int(T.priv_stack)) + 2
 
 
@@ -165,7 +110,8 @@ def _forces(rng, N, L, feet, links_on_p, T, chronic_term, term):
 def synth_fixture(task, N, seed=0, steps=None):
     """Inputs of a synthetic fixture for `task` at N envs over `steps` control steps (default: the minimum that compacts the
     smallest-slack history window twice, at least 24 so that the push step sits well inside)."""
-    cfg = task_cfg(task)
+    spec = h.TASKS[task]
+    cfg = spec.cfg()
     model = load_model(cfg.asset.name)
     T = builders.make_task_cfg(model, cfg)
     S = T.slots
@@ -178,8 +124,8 @@ def synth_fixture(task, N, seed=0, steps=None):
     feet = [int(i) for i in model.arrays["foot_link"][:F]]
     term = model.find_link_indices(cfg.asset.terminate_after_contacts_on)
     maxep = int(T.max_episode_length)
-    fx = Fixture()
-    fx["reward_names"] = np.load(os.path.join(GOLDEN, f"{task}_mdp.npz"))["reward_names"]     # the reference's reward terms, in its order
+    fx = h.Fixture()
+    fx["reward_names"] = np.load(spec.gold)["reward_names"]     # the reference's reward terms, in its order
     # ---- initial state
     ep = rng.integers(0, maxep + 1, N)
     k = rng.random(N)
@@ -192,7 +138,7 @@ def synth_fixture(task, N, seed=0, steps=None):
     cmd[rng.random(N) < 0.15, :3] = 0                                                   # dropped commands (|cmd| <= 0.2)
     fx["init_commands"] = cmd.astype(f32)
     terrain = None
-    if task in ROUGH:
+    if spec.rough:
         fx["terrain_seed"] = np.array(1000 + seed)
         np.random.seed(int(fx["terrain_seed"]))
         from hcr_genesis_lr_cl_amd.terrain import Terrain
@@ -231,7 +177,7 @@ def synth_fixture(task, N, seed=0, steps=None):
         fx["init_gait_time"] = gt[:, None].astype(f32)
         fx["init_phi"] = (fx["init_gait_time"] / gp).astype(f32)
     # ---- a live oracle: the state the next step's inputs are placed against
-    live = oracle_stepper(task)(fx, N)
+    live = h.OracleStepper(spec, fx, N)
     o = live.o
     # chronic failures: a run of consecutive failing steps ending at, one below and beyond the threshold
     thr = int(T.fail_threshold)
@@ -404,30 +350,21 @@ def synth_fixture(task, N, seed=0, steps=None):
     return fx
 
 
-STACKED_EVERY_STEP = ("feat_full", "priv_full")
-
-
 def record(task, fx):
-    """fx with the oracle's outputs added under the keys the task's check_* reads (feat_last / priv_last: the full stacks at the
-    last step).  `sim` is copied on every step: the oracle modifies it in place."""
-    out_fx = Fixture(fx)
-    T, N = fx["rand"].shape[:2]
-    st = oracle_stepper(task)(fx, N)
-    outs = []
-    for t in range(T):
-        sim_in = {k[len("script_"):]: fx[k][t].copy() for k in fx.files if k.startswith("script_")}
-        sim_in["last_dof_vel"] = fx["last_dof_vel_in"][t].copy()
-        sim_in["last_feet_vel"] = fx["last_feet_vel_in"][t].copy()
-        out = st.step(t, sim_in, fx["actions_in"][t].copy(), fx["rand"][t], int(fx["counter"][t]), float(fx["esum_override"][t]))
-        last = {k: np.array(v, copy=True) for k, v in out.items() if v is not None and k in STACKED_EVERY_STEP}
-        outs.append({k: np.array(v, copy=True) for k, v in out.items() if v is not None and k not in STACKED_EVERY_STEP})
+    """fx with the oracle's outputs added under the keys the task's check reads (feat_last / priv_last: the full stacks at the
+    last step)."""
+    spec = h.TASKS[task]
+    st = h.OracleStepper(spec, fx, fx["rand"].shape[1])
+    outs, last = [], {}
+    for step in h.fixture_steps(fx):
+        out = st.step(*step)
+        last = {k: np.array(out.pop(k), copy=True) for k in ("feat_full", "priv_full") if k in out}
+        outs.append({k: np.array(v, copy=True) for k, v in out.items()})
+    out_fx = h.Fixture(fx)
     for k in outs[0]:
         out_fx[k] = np.stack([o_[k] for o_ in outs])
-    if "feat_full" in last:
+    if last:
         out_fx["feat_last"], out_fx["priv_last"] = last["feat_full"], last["priv_full"]
-    if task in ("go2_ee", "go2_ts", "go2_cts", "go2_dreamwaq"):        # no constraints: check_head skips them on an empty axis
-        out_fx["cstr_prob"] = np.zeros((T, N), f32)
-        out_fx["cstr_sums"] = np.zeros((T, 0, N), f32)
     return out_fx
 
 

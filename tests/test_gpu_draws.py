@@ -16,6 +16,7 @@ import pytest
 from oracle import draw_map
 from oracle import mdp_oracle as mo
 from oracle.philox import philox4x32_10
+from tests import mdp_harness as h
 
 pytestmark = pytest.mark.gpu
 
@@ -42,24 +43,6 @@ def test_philox_on_chip_matches_numpy():
 
 
 # ------------------------------------------------------------------------------------------------------------------------------
-def _split_engine(N, env_id_offset):
-    import torch
-    from hcr_genesis_lr_cl_amd import builders
-    from hcr_genesis_lr_cl_amd.config import GO2Cfg
-    from hcr_genesis_lr_cl_amd.engine import Engine
-    from hcr_genesis_lr_cl_amd.model_compiler import load_model
-    from tests.test_gpu_mdp import drop_unused_joint_dr
-    cfg = GO2Cfg()
-    model = load_model(cfg.asset.name)
-    desc, opts = builders.make_model_desc(model, cfg), builders.make_sim_options(model, cfg)
-    task = builders.make_task_cfg(model, cfg, seed=0x1234_5678_9ABC, env_id_offset=env_id_offset)
-    eng = Engine(model, desc, opts, task, N, "cuda:0", inject_rand=False)
-    drop_unused_joint_dr(eng, task)
-    cr = cfg.commands.ranges
-    eng.buf["command_ranges"][:8] = torch.tensor(list(cr.lin_vel_x) + list(cr.lin_vel_y) + list(cr.ang_vel_yaw) + list(cr.heading))
-    return eng, model, cfg, task
-
-
 @pytest.mark.parametrize("N,env_id_offset", [(4096, 0), (4093, (1 << 32) + 12345)], ids=["4096", "ragged-offset"])
 def test_split_launch_philox_matches_oracle_with_draw_map(N, env_id_offset):
     """tests/test_gpu_mdp.py test_kernel_matches_numpy_oracle_at_4096_envs with the kernel drawing from Philox and the oracle fed
@@ -68,8 +51,8 @@ def test_split_launch_philox_matches_oracle_with_draw_map(N, env_id_offset):
     import torch
     from hcr_genesis_lr_cl_amd import abi
     from tests.golden_inputs import random_mdp_inputs
-    from tests.test_gpu_mdp import get, load_sim, put
-    eng, model, cfg, task = _split_engine(N, env_id_offset)
+    from tests.mdp_harness import get, load_sim, put
+    eng, model, cfg, task = h.make_engine(N, inject_rand=False, seed=0x1234_5678_9ABC, env_id_offset=env_id_offset)
     assert "rand_in" not in eng.buf
     rng = np.random.default_rng(13)
     origins = np.zeros((N, 3), np.float32); origins[:, :2] = rng.uniform(-40, 40, (N, 2))
@@ -138,8 +121,6 @@ GATE_LAUNCHES = ("lg_launch_quad<4, true, LG_PHASE_POST, 0, 3>", "lg_launch_env<
 PHYS_TOL = dict(base_pos=2e-5, base_quat=2e-5, base_lin_vel_w=2e-3, base_ang_vel_w=1e-2, dof_pos=2e-4, dof_vel=3e-2, torques=5e-3,
                 feet_pos=1e-4, feet_vel=2e-2)      # DESIGN.md section 2 (tests/test_gpu_physics.py TOL)
 MDP_ORACLE_LAYOUTS = (mo.abi.OBS_GO2, mo.abi.OBS_GO2_WTW, mo.abi.OBS_GO2_EE, mo.abi.OBS_TRON1_EE)   # go2, go2_wtw, go2_ee, tron1_pf_ee
-MDP_SIM_KEYS = ("base_pos", "base_quat", "base_lin_vel_w", "base_ang_vel_w", "dof_pos", "dof_vel", "torques", "link_contact_forces",
-                "feet_pos", "feet_vel", "last_dof_vel", "last_feet_vel")
 
 
 def _pid(case):
@@ -387,21 +368,13 @@ def _check_mdp_oracle(model, cfg, task, N, pre, post, push, actions, U, c, keep,
     orc.fail_buf[:] = pre["fail_buf"]
     orc.episode_sums[:] = pre["episode_sums"]
     orc.command_ranges[:] = pre["command_ranges"][:8]
-    ts = pre["task_state"] if task.gait_mode else None
-    if task.gait_mode == 1:           # layout LG_TASK_STATE_WTW, behaviour ranges from command_ranges[8:17]
-        orc.gait_time[:], orc.phi[:], orc.gait_period[:] = ts[:, 0:1], ts[:, 1:2], ts[:, 2:3]
-        orc.base_height_target[:], orc.foot_clearance_target[:], orc.pitch_target[:] = ts[:, 3:4], ts[:, 4:5], ts[:, 5:6]
-        orc.theta[:], orc.clock_input[:], orc.exp_C_frc[:] = ts[:, 6:10], ts[:, 10:18], ts[:, 18:22]
-        br = pre["command_ranges"][8:17]
-        orc.gait_period_range, orc.base_height_target_range = list(br[0:2]), list(br[2:4])
-        orc.foot_clearance_target_range, orc.pitch_target_range, orc.num_gaits = list(br[4:6]), list(br[6:8]), int(br[8])
-    if task.gait_mode == 2:           # layout LG_TASK_STATE_BIPED
-        orc.gait_time[:], orc.phi[:] = ts[:, 0:1], ts[:, 1:2]
-        orc.theta[:], orc.clock_input[:], orc.exp_C_frc[:] = ts[:, 4:6], ts[:, 6:10], ts[:, 10:12]
+    gait = h.GAIT[int(task.gait_mode)]
+    if gait:
+        h.set_task_state(gait, orc, pre["task_state"], pre["command_ranges"])
     if terrain is not None:
         orc.terrain_levels[:], orc.terrain_types[:] = pre["terrain_levels"], pre["terrain_types"]
         orc.terrain_origins = terrain.env_origins.astype(np.float32)
-    sim = {k: post[k].reshape(N, -1).copy() for k in MDP_SIM_KEYS}
+    sim = {k: post[k].reshape(N, -1).copy() for k in h.SIM_KEYS}
     sim["base_lin_vel_w"] -= push
     if "measured_heights" in post and post["measured_heights"].size:       # the SIM phase's terrain read-backs of this step
         sim["measured_heights"] = post["measured_heights"].reshape(N, -1).copy()
@@ -427,14 +400,9 @@ def _check_mdp_oracle(model, cfg, task, N, pre, post, push, actions, U, c, keep,
         checks.append(("priv_obs_buf", post["priv_obs_buf"].reshape(N, -1)[:, -PF:], orc.priv_obs_buf[:, -PF:], 5e-5))
     if L in (abi.OBS_GO2_EE, abi.OBS_TRON1_EE):
         checks.append(("labels_buf", post["labels_buf"].reshape(N, -1), orc.labels_buf, 1e-5))
-    if task.gait_mode == 1:
-        checks.append(("task_state", post["task_state"], np.concatenate([orc.gait_time, orc.phi, orc.gait_period, orc.base_height_target,
-                                                                         orc.foot_clearance_target, orc.pitch_target, orc.theta,
-                                                                         orc.clock_input, orc.exp_C_frc], 1), 1e-5))
-    if task.gait_mode == 2:
-        got = post["task_state"]
-        checks.append(("task_state", np.concatenate([got[:, 0:2], got[:, 4:12]], 1),
-                       np.concatenate([orc.gait_time, orc.phi, orc.theta, orc.clock_input, orc.exp_C_frc], 1), 1e-5))
+    if gait:
+        checks.append(("task_state", h.recorded_task_state(gait, post["task_state"]),
+                       h.recorded_task_state(gait, h.task_state_rows(gait, orc)), 1e-5))
     for name, got, ref, tol in checks:
         np.testing.assert_allclose(got[k], ref[k], rtol=1e-5, atol=tol, err_msg=name)
     np.testing.assert_allclose(post["episode_sums"][:, k], orc.episode_sums[:, k], rtol=1e-5, atol=1e-5, err_msg="episode_sums")

@@ -8,8 +8,9 @@ import os
 import numpy as np
 import pytest
 
-from tests.test_mdp_oracle import GOLD, replay, check_against_fixture
 from oracle import mdp_oracle as mo
+from tests import mdp_harness as h
+from tests.mdp_harness import get, load_sim, make_engine, put
 
 pytestmark = pytest.mark.gpu
 
@@ -48,106 +49,14 @@ def tail(request, monkeypatch, history_mode):
         assert all(inj) if request.param == "fused-profile" else not any(inj), (request.param, sorted(set(seen)))
 
 
-SIM_KEYS = ("base_pos", "base_quat", "base_lin_vel_w", "base_ang_vel_w", "dof_pos", "dof_vel", "torques",
-            "link_contact_forces", "feet_pos", "feet_vel", "last_dof_vel", "last_feet_vel")
-
-
-def make_engine(N, env_origins=None, cfg_cls=None):
-    import torch
-    from hcr_genesis_lr_cl_amd import builders
-    from hcr_genesis_lr_cl_amd.config import GO2Cfg
-    from hcr_genesis_lr_cl_amd.engine import Engine
-    from hcr_genesis_lr_cl_amd.model_compiler import load_model
-    cfg = (cfg_cls or GO2Cfg)()
-    model = load_model(cfg.asset.name)
-    desc, opts, task = builders.make_model_desc(model, cfg), builders.make_sim_options(model, cfg), builders.make_task_cfg(model, cfg)
-    eng = Engine(model, desc, opts, task, N, "cuda:0", inject_rand=True)
-    drop_unused_joint_dr(eng, task)
-    cr = cfg.commands.ranges
-    eng.buf["command_ranges"][:8] = torch.tensor(list(cr.lin_vel_x) + list(cr.lin_vel_y) + list(cr.ang_vel_yaw) + list(cr.heading))
-    if env_origins is not None:
-        eng.buf["env_origins"].copy_(torch.from_numpy(env_origins))
-    return eng, model, cfg, task
-
-
-def drop_unused_joint_dr(eng, task):
-    """What HipSimulator does for a task without per-env joint parameters (simulator.py:310-316): the three (N, 1) arrays are unbound, the
-    kernel takes armature / frictionloss / damping from the model -- and the task fits its profile (lg_host.hip flat_profile ...)."""
-    if not int(task.dr_joint_on):
-        for k in ("joint_armature", "joint_friction", "joint_damping"):
-            eng.buf.pop(k)
-        eng.bind()
-
-
-def put(eng, name, arr):
-    import torch
-    t = eng.buf[name]
-    t.copy_(torch.from_numpy(np.ascontiguousarray(arr)).reshape(t.shape).to(t.dtype))
-
-
-def get(eng, name):
-    return eng.buf[name].detach().cpu().numpy()
-
-
-def load_sim(eng, sim):
-    for k in SIM_KEYS:
-        put(eng, k, sim[k])
-    q = sim["base_quat"]
-    put(eng, "base_lin_vel", mo.quat_rotate_inverse(q, sim["base_lin_vel_w"]))
-    put(eng, "base_ang_vel", mo.quat_rotate_inverse(q, sim["base_ang_vel_w"]))
-    put(eng, "projected_gravity", mo.quat_rotate_inverse(q, np.tile(np.array([0, 0, -1], np.float32), (len(q), 1))))
-    put(eng, "base_euler", mo.get_euler_xyz(q))
-
-
-class KernelStepper:
-    def __init__(self, fx, N):
-        import torch
-        self.eng, self.model, self.cfg, self.task = make_engine(N, fx["init_env_origins"])
-        put(self.eng, "episode_length_buf", fx["init_episode_length_buf"])
-        put(self.eng, "commands", fx["init_commands"])
-        self.names = [str(n) for n in fx["reward_names"]]
-        self.cmd_range_x = [-0.5, 0.5]
-
-    def step(self, t, sim, actions, R, counter, override):
-        import torch
-        from hcr_genesis_lr_cl_amd import abi
-        eng = self.eng
-        k = abi.REWARD_ID["tracking_lin_vel"]
-        if override:
-            eng.buf["episode_sums"][k].fill_(override)
-            eng.buf["episode_length_buf"][:4] = 1000
-        load_sim(eng, sim)
-        put(eng, "rand_in", R)
-        act = torch.from_numpy(actions).cuda()
-        if counter % 1000 == 0:       # command-curriculum gate, same split as envs/legged_robot.py
-            eng.step(abi.PHASE_PRE | abi.PHASE_POST, act, counter)
-            ids = eng.buf["reset_buf"].nonzero().flatten()
-            if len(ids):
-                mean = torch.mean(eng.buf["episode_sums"][k][ids]) / 1000.0
-                if mean > 0.8 * (1.0 * 0.02):
-                    self.cmd_range_x = [max(self.cmd_range_x[0] - 0.5, -1.0), min(self.cmd_range_x[1] + 0.5, 1.0)]
-                    eng.buf["command_ranges"][0] = self.cmd_range_x[0]
-                    eng.buf["command_ranges"][1] = self.cmd_range_x[1]
-            eng.step(abi.PHASE_RESET, None, counter)
-        else:
-            eng.step(abi.PHASE_PRE | abi.PHASE_POST | abi.PHASE_RESET, act, counter)
-        torch.cuda.synchronize()
-        es = get(eng, "episode_sums")
-        return dict(obs=get(eng, "obs_buf"), rew=get(eng, "rew_buf"), reset=get(eng, "reset_buf"), time_out=get(eng, "time_out_buf"),
-                    commands=get(eng, "commands"), ep_len=get(eng, "episode_length_buf"), fail_buf=get(eng, "fail_buf"),
-                    feet_air_time=get(eng, "feet_air_time"), last_contacts=get(eng, "last_contacts"),
-                    episode_sums=np.stack([es[abi.REWARD_ID[n]] for n in self.names]),
-                    act_hist=np.stack([get(eng, "actions"), get(eng, "last_actions"), get(eng, "llast_actions")]),
-                    sim_dof_pos=get(eng, "dof_pos"), sim_dof_vel=get(eng, "dof_vel"), sim_base_pos=get(eng, "base_pos"),
-                    sim_base_quat=get(eng, "base_quat"), sim_base_lin_vel_w=get(eng, "base_lin_vel_w"),
-                    sim_projected_gravity=get(eng, "projected_gravity"), sim_base_lin_vel=get(eng, "base_lin_vel"),
-                    dr=np.concatenate([get(eng, "friction_values"), get(eng, "added_base_mass"), get(eng, "base_com_bias"),
-                                       get(eng, "rand_push_vels")[:, :2]], 1),
-                    cmd_range_x=np.array(self.cmd_range_x, np.float32))
+def replay_golden(task):
+    """The kernel through the task's golden fixture at the kernel tolerances of tests/mdp_harness.py TASKS."""
+    spec = h.TASKS[task]
+    h.replay(spec, h.golden(spec), h.KernelStepper, spec.golden_tol())
 
 
 def test_kernel_reproduces_reference_go2_golden_vectors(tail):
-    replay(KernelStepper, lambda t, fx, out: check_against_fixture(t, fx, out, rtol=1e-5, atol=1e-5))
+    replay_golden("go2")
 
 
 def test_kernel_matches_numpy_oracle_at_4096_envs():
@@ -192,63 +101,19 @@ def test_kernel_matches_numpy_oracle_at_4096_envs():
 
 
 # ------------------------------- go2_wtw ------------------------------------------------------
-class WtwKernelStepper:
-    def __init__(self, fx, N):
-        import torch
-        from hcr_genesis_lr_cl_amd.config import GO2WTWCfg
-        self.eng, self.model, self.cfg, self.task = make_engine(N, fx["init_env_origins"], GO2WTWCfg)
-        eng = self.eng
-        put(eng, "episode_length_buf", fx["init_episode_length_buf"])
-        put(eng, "commands", fx["init_commands"])
-        eng.buf["command_ranges"][8:17] = torch.from_numpy(fx["init_behavior_ranges"]).cuda()
-        ts = np.zeros((N, 22), np.float32)
-        ts[:, 0:1], ts[:, 1:2], ts[:, 2:3] = fx["init_gait_time"], fx["init_phi"], fx["init_gait_period"]
-        ts[:, 3], ts[:, 4], ts[:, 5] = 0.27, 0.04, 0.0          # mid / min initial targets (go2_wtw.py:337-346)
-        ts[:, 6:10] = fx["init_theta"]
-        put(eng, "task_state", ts)
-        eng.buf["friction_values"].fill_(0.0); eng.buf["added_base_mass"].fill_(1.0)    # the fake simulator's initial values
-        self.names = [str(n) for n in fx["reward_names"]]
-
-    def step(self, t, sim, actions, R, counter, override):
-        import torch
-        from hcr_genesis_lr_cl_amd import abi
-        eng = self.eng
-        load_sim(eng, sim)
-        put(eng, "rand_in", R)
-        eng.step(abi.PHASE_PRE | abi.PHASE_POST | abi.PHASE_RESET, torch.from_numpy(actions).cuda(), counter)
-        torch.cuda.synchronize()
-        es = get(eng, "episode_sums")
-        return dict(obs=get(eng, "obs_buf"), priv=get(eng, "priv_obs_buf"), rew=get(eng, "rew_buf"), reset=get(eng, "reset_buf"),
-                    time_out=get(eng, "time_out_buf"), commands=get(eng, "commands"), ep_len=get(eng, "episode_length_buf"),
-                    fail_buf=get(eng, "fail_buf"), episode_sums=np.stack([es[abi.REWARD_ID[n]] for n in self.names]),
-                    act_hist=np.stack([get(eng, "actions"), get(eng, "last_actions"), get(eng, "llast_actions")]),
-                    sim_dof_pos=get(eng, "dof_pos"), sim_base_pos=get(eng, "base_pos"), sim_base_lin_vel_w=get(eng, "base_lin_vel_w"),
-                    dr_pd=np.concatenate([get(eng, "kp_scale"), get(eng, "kd_scale")], 1), task_state=get(eng, "task_state"))
-
-
 def test_kernel_reproduces_reference_go2_wtw_golden_vectors(tail):
     """Env 0 is excluded: the reference couples it to the whole batch through two index-flatten bugs
     (go2_wtw.py:33-34, 455-462) which the kernel does not reproduce (envs/go2_wtw.py docstring)."""
-    from tests.test_mdp_oracle import GOLD_WTW
-    from tests.test_mdp_oracle import check_wtw
-    replay(WtwKernelStepper, lambda t, fx, out: check_wtw(t, fx, out, rtol=1e-5, atol=1e-5, skip_env0=True), GOLD_WTW)
+    replay_golden("go2_wtw")
 
 
 # ------------------------------- every task against the oracle on synthetic batches ---------------------------------------
-def synth_kernel_stepper(task):
-    if task in ("go2_ts", "go2_cts", "go2_dreamwaq", "go2_cat"):
-        return type("KStepper_" + task, (EEKernelStepper,), {"head": task})
-    return {"go2": KernelStepper, "go2_wtw": WtwKernelStepper, "go2_ee": EEKernelStepper, "tron1_pf_ee": Tron1KernelStepper,
-            "tron1_pf": PFKernelStepper, "tron1_sf": SFKernelStepper}[task]
-
-
 def _synth_params():
     """(task, tail, history mode): fused-profile only where the task has an INJ profile tail and only with the sliding window
     (the component-layout tails hard-wire it); go2_cat, tron1_pf and tron1_sf are split only."""
-    from tests.synthetic_mdp import TASKS, INJ_TAIL
     modes = (("64", "history-window"), ("1", "history-window-min-slack"), ("0", "history-shift"))
-    return [pytest.param(task, tail, m, id=f"{task}-{tail}-{mid}") for task in TASKS for tail in ("split", "fused-profile")
-            for m, mid in modes if tail == "split" or (task in INJ_TAIL and m != "0")]
+    return [pytest.param(task, tail, m, id=f"{task}-{tail}-{mid}") for task, spec in h.TASKS.items() for tail in ("split", "fused-profile")
+            for m, mid in modes if tail == "split" or (spec.inj_tail and m != "0")]
 
 
 @pytest.mark.parametrize("N", [4096, 4093])
@@ -257,10 +122,10 @@ def test_kernel_matches_oracle_on_synthetic_batches(task, N, tail):
     """Every task's MDP instantiations against the oracle on a synthetic batch (tests/synthetic_mdp.py): 4096 envs, and 4093 for a
     partly filled last wave / workgroup / PROF 6 group of 8 envs; long enough for two compactions of the smallest-slack history
     window; inputs that cross every decision of the MDP phases with a margin.  Expected values are the oracle's, recorded once
-    per batch; tolerances of sm.synth_check (the golden replays' kernel tolerances)."""
+    per batch; tolerances of TaskSpec.synth_tol (the golden replays' kernel tolerances)."""
     from tests import synthetic_mdp as sm
-    fx = sm.recorded(task, N)
-    sm.replay(task, fx, synth_kernel_stepper(task), sm.synth_check(task))
+    spec = h.TASKS[task]
+    h.replay(spec, sm.recorded(task, N), h.KernelStepper, spec.synth_tol())
 
 
 def test_wtw_env_runs_and_histories_shift():
@@ -285,62 +150,8 @@ def test_wtw_env_runs_and_histories_shift():
 
 
 # ------------------------------- go2_ee (rough terrain) ------------------------------------------
-class EEKernelStepper:
-    head = "go2_ee"
-
-    def __init__(self, fx, N):
-        import torch
-        from hcr_genesis_lr_cl_amd import builders
-        from hcr_genesis_lr_cl_amd.engine import Engine
-        from hcr_genesis_lr_cl_amd.model_compiler import load_model
-        from tests.test_mdp_oracle import ee_terrain
-        cfg, terrain = ee_terrain(fx, self.head)
-        self.cfg, self.terrain = cfg, terrain
-        model = load_model("go2")
-        desc, opts, task = builders.make_model_desc(model, cfg), builders.make_sim_options(model, cfg, terrain), builders.make_task_cfg(model, cfg)
-        eng = self.eng = Engine(model, desc, opts, task, N, "cuda:0", inject_rand=True)
-        drop_unused_joint_dr(eng, task)
-        eng.set_terrain(terrain.height_field_raw, terrain.env_origins, fx["init_height_points"])
-        cr = cfg.commands.ranges
-        eng.buf["command_ranges"][:8] = torch.tensor(list(cr.lin_vel_x) + list(cr.lin_vel_y) + list(cr.ang_vel_yaw) + list(cr.heading))
-        put(eng, "env_origins", fx["init_env_origins"]); put(eng, "episode_length_buf", fx["init_episode_length_buf"])
-        put(eng, "commands", fx["init_commands"])
-        put(eng, "terrain_levels", fx["init_terrain_levels"]); put(eng, "terrain_types", fx["init_terrain_types"])
-        eng.buf["friction_values"].fill_(0.0); eng.buf["added_base_mass"].fill_(1.0)
-        self.names = [str(n) for n in fx["reward_names"]]
-        self.fx = fx
-
-    def step(self, t, sim, actions, R, counter, override):
-        import torch
-        from hcr_genesis_lr_cl_amd import abi
-        eng, fx = self.eng, self.fx
-        load_sim(eng, sim)
-        # terrain read-backs of the SIM phase (checked separately against the numpy sampler): injected
-        put(eng, "measured_heights", fx["measured_heights"][t]); put(eng, "height_around_feet", fx["height_around_feet"][t])
-        put(eng, "normal_vector_around_feet", fx["normals"][t])
-        put(eng, "rand_in", R)
-        if "cstr_prob" in eng.buf:       # go2_cat: the job-wide "some env moves a joint faster than 4 rad/s" flag (envs/go2_ts.py Go2CaT._any_fast)
-            eng.buf["command_ranges"][abi.CR_ANY_FAST + (counter & 1)] = float(np.any(np.abs(sim["dof_vel"]) > 4.0))   # what the SIM phase raises
-        eng.step(abi.PHASE_PRE | abi.PHASE_POST | abi.PHASE_RESET, torch.from_numpy(actions).cuda(), counter)
-        torch.cuda.synchronize()
-        es = get(eng, "episode_sums")
-        lab = get(eng, "labels_buf")
-        from tests.test_mdp_oracle import HEADS
-        W, cols = HEADS[self.head][1], HEADS[self.head][2]
-        return dict(feat_new=get(eng, "obs_buf")[:, -45:], priv_new=get(eng, "priv_obs_buf")[:, -W:], labels=lab, rew=get(eng, "rew_buf"),
-                    reset=get(eng, "reset_buf"), time_out=get(eng, "time_out_buf"), commands=get(eng, "commands"),
-                    ep_len=get(eng, "episode_length_buf"), fail_buf=get(eng, "fail_buf"), feet_air_time=get(eng, "feet_air_time"),
-                    episode_sums=np.stack([es[abi.REWARD_ID[n]] for n in self.names]), sim_dof_pos=get(eng, "dof_pos"),
-                    sim_base_pos=get(eng, "base_pos"), terrain_levels=get(eng, "terrain_levels"), env_origins=get(eng, "env_origins"),
-                    measured_heights=fx["measured_heights"][t], height_around_feet=fx["height_around_feet"][t], normals=fx["normals"][t],
-                    contact_states=get(eng, "priv_obs_buf")[:, -W:][:, cols], feat_full=get(eng, "obs_buf"), priv_full=get(eng, "priv_obs_buf"),
-                    obs=get(eng, "obs_buf")[:, -45:], cstr_prob=get(eng, "cstr_prob") if "cstr_prob" in eng.buf else None,
-                    cstr_sums=get(eng, "cstr_sums") if "cstr_sums" in eng.buf else None)
-
-
 def test_kernel_reproduces_reference_go2_ee_golden_vectors(tail):
-    from tests.test_mdp_oracle import replay_ee, check_ee
-    replay_ee(EEKernelStepper, lambda t, fx, out: check_ee(t, fx, out, rtol=1e-5, atol=5e-5))
+    replay_golden("go2_ee")
 
 
 @pytest.mark.parametrize("head", ["go2_ts", "go2_cts", "go2_dreamwaq", "go2_cat"])
@@ -348,11 +159,9 @@ def test_kernel_reproduces_reference_head_golden_vectors(head, tail):
     """the other Go2-rough heads.  Golden vectors from the reference's own Go2TS / Go2CTS / Go2Dreamwaq classes as
     configured (tests/golden/gen_mdp_fixtures.py gen_head): actor frame, newest frames of the 20-deep actor history and the
     5-deep critic stack (full stacks at the last step), the single-frame auxiliary output, rewards, resets, curricula."""
-    from tests.test_mdp_oracle import replay_ee, check_head, head_gold
     if head == "go2_cat" and tail == "fused-profile":
         pytest.skip("go2_cat has no component-layout tail: its MDP phases are the leg-per-lane launch in the product too")
-    stepper = type("KStepper_" + head, (EEKernelStepper,), {"head": head})
-    replay_ee(stepper, lambda t, fx, out: check_head(t, fx, out, rtol=1e-5, atol=5e-5), head_gold(head))
+    replay_golden(head)
 
 
 @pytest.mark.parametrize("head", ["go2_ts", "go2_cts", "go2_dreamwaq", "go2_cat"])
@@ -442,57 +251,9 @@ def test_go2_ee_env_surface_and_terrain_curriculum():
 
 
 # ------------------------------- tron1_pf_ee (biped) ----------------------------------------------
-class Tron1KernelStepper:
-    def __init__(self, fx, N):
-        import torch
-        from hcr_genesis_lr_cl_amd import builders
-        from hcr_genesis_lr_cl_amd.engine import Engine
-        from hcr_genesis_lr_cl_amd.model_compiler import load_model
-        from tests.test_mdp_oracle import tron1_terrain
-        cfg, terrain = tron1_terrain(fx)
-        model = load_model("tron1_pf")
-        desc, opts, task = builders.make_model_desc(model, cfg), builders.make_sim_options(model, cfg, terrain), builders.make_task_cfg(model, cfg)
-        eng = self.eng = Engine(model, desc, opts, task, N, "cuda:0", inject_rand=True)
-        drop_unused_joint_dr(eng, task)
-        eng.set_terrain(terrain.height_field_raw, terrain.env_origins, fx["init_height_points"])
-        cr = cfg.commands.ranges
-        eng.buf["command_ranges"][:8] = torch.tensor(list(cr.lin_vel_x) + list(cr.lin_vel_y) + list(cr.ang_vel_yaw) + list(cr.heading))
-        for k in ("env_origins", "episode_length_buf", "commands", "terrain_levels", "terrain_types"):
-            put(eng, k, fx["init_" + k])
-        ts = np.zeros((N, 12), np.float32)
-        ts[:, 0:1], ts[:, 1:2], ts[:, 2], ts[:, 4:6] = fx["init_gait_time"], fx["init_phi"], 0.5, fx["init_theta"]
-        put(eng, "task_state", ts)
-        eng.buf["friction_values"].fill_(0.0); eng.buf["added_base_mass"].fill_(1.0)
-        self.names = [str(n) for n in fx["reward_names"]]
-        self.fx = fx
-
-    def step(self, t, sim, actions, R, counter, override):
-        import torch
-        from hcr_genesis_lr_cl_amd import abi
-        eng, fx = self.eng, self.fx
-        load_sim(eng, sim)
-        put(eng, "measured_heights", fx["measured_heights"][t]); put(eng, "height_around_feet", fx["height_around_feet"][t])
-        put(eng, "normal_vector_around_feet", fx["normals"][t])
-        put(eng, "rand_in", R)
-        eng.step(abi.PHASE_PRE | abi.PHASE_POST | abi.PHASE_RESET, torch.from_numpy(actions).cuda(), counter)
-        torch.cuda.synchronize()
-        es, tsb = get(eng, "episode_sums"), get(eng, "task_state")
-        return dict(feat_new=get(eng, "obs_buf")[:, -31:], priv_new=get(eng, "priv_obs_buf")[:, -134:], labels=get(eng, "labels_buf"),
-                    rew=get(eng, "rew_buf"), reset=get(eng, "reset_buf"), time_out=get(eng, "time_out_buf"), commands=get(eng, "commands"),
-                    ep_len=get(eng, "episode_length_buf"), fail_buf=get(eng, "fail_buf"),
-                    episode_sums=np.stack([es[abi.REWARD_ID[n]] for n in self.names]),
-                    act_hist=np.stack([get(eng, "actions"), get(eng, "last_actions"), get(eng, "llast_actions")]),
-                    sim_dof_pos=get(eng, "dof_pos"), sim_base_pos=get(eng, "base_pos"), sim_base_quat=get(eng, "base_quat"),
-                    terrain_levels=get(eng, "terrain_levels"), env_origins=get(eng, "env_origins"),
-                    measured_heights=fx["measured_heights"][t], height_around_feet=fx["height_around_feet"][t], normals=fx["normals"][t],
-                    dr_joint=np.concatenate([get(eng, "joint_armature"), get(eng, "joint_friction"), get(eng, "joint_damping")], 1),
-                    task_state=np.concatenate([tsb[:, 0:2], tsb[:, 4:12]], 1), feat_full=get(eng, "obs_buf"), priv_full=get(eng, "priv_obs_buf"))
-
-
 def test_kernel_reproduces_reference_tron1_pf_ee_golden_vectors(tail):
     """Env 0 excluded for the same reason as in the wtw test (reference index-flatten bugs on the gait clock / indicator)."""
-    from tests.test_mdp_oracle import GOLD_TRON1, replay_rough, check_tron1
-    replay_rough(GOLD_TRON1, Tron1KernelStepper, lambda t, fx, out: check_tron1(t, fx, out, rtol=1e-5, atol=5e-5, skip_env0=True))
+    replay_golden("tron1_pf_ee")
 
 
 def test_tron1_env_runs_physics_and_mdp():
@@ -517,39 +278,9 @@ def test_tron1_env_runs_physics_and_mdp():
 
 
 # ------------------------------- tron1_pf (biped on the plane) ------------------------------------
-class PFKernelStepper:
-    def __init__(self, fx, N):
-        from hcr_genesis_lr_cl_amd.config import TRON1PFCfg
-        self.eng, self.model, self.cfg, self.task = make_engine(N, fx["init_env_origins"], TRON1PFCfg)
-        eng = self.eng
-        put(eng, "episode_length_buf", fx["init_episode_length_buf"])
-        put(eng, "commands", fx["init_commands"])
-        eng.buf["friction_values"].fill_(0.0); eng.buf["added_base_mass"].fill_(1.0)    # the fake simulator's initial values
-        self.names = [str(n) for n in fx["reward_names"]]
-
-    def step(self, t, sim, actions, R, counter, override):
-        import torch
-        from hcr_genesis_lr_cl_amd import abi
-        eng = self.eng
-        load_sim(eng, sim)
-        put(eng, "rand_in", R)
-        eng.step(abi.PHASE_PRE | abi.PHASE_POST | abi.PHASE_RESET, torch.from_numpy(actions).cuda(), counter)
-        torch.cuda.synchronize()
-        es = get(eng, "episode_sums")
-        return dict(obs=get(eng, "obs_buf"), priv=get(eng, "priv_obs_buf"), rew=get(eng, "rew_buf"), reset=get(eng, "reset_buf"),
-                    time_out=get(eng, "time_out_buf"), commands=get(eng, "commands"), ep_len=get(eng, "episode_length_buf"),
-                    fail_buf=get(eng, "fail_buf"), feet_air_time=get(eng, "feet_air_time"),
-                    episode_sums=np.stack([es[abi.REWARD_ID[n]] for n in self.names]),
-                    act_hist=np.stack([get(eng, "actions"), get(eng, "last_actions"), get(eng, "llast_actions")]),
-                    sim_dof_pos=get(eng, "dof_pos"), sim_base_pos=get(eng, "base_pos"), sim_base_lin_vel_w=get(eng, "base_lin_vel_w"),
-                    dr=np.concatenate([get(eng, "friction_values"), get(eng, "added_base_mass"), get(eng, "base_com_bias"),
-                                       get(eng, "rand_push_vels")[:, :2]], 1))
-
-
 def test_kernel_reproduces_reference_tron1_pf_golden_vectors():
     """TRON1PF on the plane, golden vectors from the reference's own class (gen_mdp_fixtures.py gen_tron1_pf)."""
-    from tests.test_mdp_oracle import GOLD_PF, check_pf
-    replay(PFKernelStepper, lambda t, fx, out: check_pf(t, fx, out, rtol=1e-5, atol=5e-5), GOLD_PF)
+    replay_golden("tron1_pf")
 
 
 def test_tron1_pf_env_rollout():
@@ -600,46 +331,10 @@ def test_cat_job_wide_flag_is_raised_by_the_physics_launch():
 
 
 # ------------------------------- tron1_sf (8-DOF sole-foot biped on the plane) ---------------------
-class SFKernelStepper:
-    def __init__(self, fx, N):
-        from tests.test_mdp_oracle import sf_cfg
-        self.eng, self.model, self.cfg, self.task = make_engine(N, fx["init_env_origins"], sf_cfg)
-        eng = self.eng
-        put(eng, "episode_length_buf", fx["init_episode_length_buf"])
-        put(eng, "commands", fx["init_commands"])
-        eng.buf["friction_values"].fill_(0.0); eng.buf["added_base_mass"].fill_(1.0)    # the fake simulator's initial values
-        for k in ("joint_armature", "joint_friction", "joint_damping"):
-            eng.buf[k].fill_(0.0)
-        self.names = [str(n) for n in fx["reward_names"]]
-
-    def step(self, t, sim, actions, R, counter, override):
-        import torch
-        from hcr_genesis_lr_cl_amd import abi
-        eng = self.eng
-        sim.pop("foot_quat", None)     # the kernel derives the foot orientation from base_quat and dof_pos
-        load_sim(eng, sim)
-        put(eng, "rand_in", R)
-        eng.step(abi.PHASE_PRE | abi.PHASE_POST | abi.PHASE_RESET, torch.from_numpy(actions).cuda(), counter)
-        torch.cuda.synchronize()
-        es = get(eng, "episode_sums")
-        return dict(obs=get(eng, "obs_buf"), priv=get(eng, "priv_obs_buf"), rew=get(eng, "rew_buf"), reset=get(eng, "reset_buf"),
-                    time_out=get(eng, "time_out_buf"), commands=get(eng, "commands"), ep_len=get(eng, "episode_length_buf"),
-                    fail_buf=get(eng, "fail_buf"), feet_air_time=get(eng, "feet_air_time"),
-                    episode_sums=np.stack([es[abi.reward_id(n, 4)] for n in self.names]),
-                    act_hist=np.stack([get(eng, "actions"), get(eng, "last_actions"), get(eng, "llast_actions")]),
-                    sim_dof_pos=get(eng, "dof_pos"), sim_base_pos=get(eng, "base_pos"), sim_base_quat=get(eng, "base_quat"),
-                    sim_base_lin_vel_w=get(eng, "base_lin_vel_w"),
-                    dr=np.concatenate([get(eng, "friction_values"), get(eng, "added_base_mass"), get(eng, "base_com_bias"),
-                                       get(eng, "rand_push_vels")[:, :2]], 1),
-                    dr_pd=np.concatenate([get(eng, "kp_scale"), get(eng, "kd_scale")], 1),
-                    dr_joint=np.concatenate([get(eng, "joint_armature"), get(eng, "joint_friction"), get(eng, "joint_damping")], 1))
-
-
 def test_kernel_reproduces_reference_tron1_sf_golden_vectors():
     """TRON1SF, golden vectors from the reference's own class (gen_mdp_fixtures.py gen_tron1_sf): four-joint legs in the
     MDP phases, the sole-foot reward terms, the sit-pose coin, the 10-frame stacks with the kp / kd blocks in the critic frame."""
-    from tests.test_mdp_oracle import GOLD_SF, check_sf
-    replay(SFKernelStepper, lambda t, fx, out: check_sf(t, fx, out, rtol=1e-5, atol=5e-5), GOLD_SF)
+    replay_golden("tron1_sf")
 
 
 def test_tron1_sf_env_rollout():

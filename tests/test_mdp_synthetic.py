@@ -1,11 +1,12 @@
 """The synthetic MDP fixtures (tests/synthetic_mdp.py) on the CPU: every task's recorded batch reaches the branches the GPU replays
-rely on (tests/test_gpu_mdp.py test_kernel_matches_oracle_on_synthetic_batches), record() is deterministic, and the check_*
-comparators fail on an oracle perturbed by one part in 1e4 or by one step of one env's episode length."""
+rely on (tests/test_gpu_mdp.py test_kernel_matches_oracle_on_synthetic_batches), record() is deterministic, and the harness's
+check fails on an oracle perturbed by one part in 1e4 or by one step of one env's episode length."""
 import numpy as np
 import pytest
 
 from hcr_genesis_lr_cl_amd import abi, builders
 from hcr_genesis_lr_cl_amd.model_compiler import load_model
+from tests import mdp_harness as h
 from tests import synthetic_mdp as sm
 
 GAIT_QUAD = ("go2_wtw",)
@@ -13,7 +14,7 @@ SIT = ("tron1_pf_ee", "tron1_sf")
 
 
 def _task(task):
-    cfg = sm.task_cfg(task)
+    cfg = h.TASKS[task].cfg()
     model = load_model(cfg.asset.name)
     return cfg, model, builders.make_task_cfg(model, cfg)
 
@@ -83,7 +84,7 @@ def test_synthetic_fixture_exercises_the_branches(task, N):
         assert clipped, "no observation reached clip_obs"
     if task == "go2":                                                                                # command curriculum fired
         assert fx["cmd_range_x"][0][1] == 0.5 and fx["cmd_range_x"][-1][1] == 1.0
-    if task in sm.ROUGH:                                                                             # terrain curriculum
+    if h.TASKS[task].rough:                                                                             # terrain curriculum
         lv = np.concatenate([fx["init_terrain_levels"][None], fx["terrain_levels"]])
         d, ml = np.diff(lv, axis=0), int(T.max_terrain_level)
         assert (d == 1).sum() >= 50 and (d == -1).sum() >= 50 and ((d != 0) & (np.abs(d) != 1)).sum() >= 10
@@ -121,12 +122,10 @@ def test_record_is_deterministic(task):
     assert not np.array_equal(a["actions_in"], c["actions_in"])
 
 
-def _perturbed(task, how, name=None):
-    base = sm.oracle_stepper(task)
-
-    class Perturbed(base):
-        def __init__(self, fx, N):
-            super().__init__(fx, N)
+def _perturbed(how, name=None):
+    class Perturbed(h.OracleStepper):
+        def __init__(self, spec, fx, N):
+            super().__init__(spec, fx, N)
             o = self.o
             if how == "scale":                   # one reward scale of the task, one part in 1e4
                 k = abi.reward_id(name, o.model.joints_per_leg)
@@ -140,12 +139,13 @@ def _perturbed(task, how, name=None):
 @pytest.mark.parametrize("task", sm.TASKS)
 @pytest.mark.parametrize("tolerances", ["check-default", "gpu-synthetic"])
 def test_check_catches_a_perturbed_oracle(task, how, tolerances):
-    """At each check_*'s own tolerances and at the ones the GPU comparison applies (sm.synth_check).  The perturbed scale is the
-    one of the reward term with the largest episode sum of the batch, every term's sum changes by 1e-4 of itself."""
+    """At the oracle's tolerances and at the ones the GPU comparison applies (TaskSpec.synth_tol).  The perturbed scale is the one
+    of the reward term with the largest episode sum of the batch, every term's sum changes by 1e-4 of itself."""
+    spec = h.TASKS[task]
     fx = sm.recorded(task, 256)
-    check = sm.check_fn(task)[0] if tolerances == "check-default" else sm.synth_check(task)
-    sm.replay(task, fx, sm.oracle_stepper(task), check)                                 # the unperturbed oracle passes
+    tol = h.ORACLE_TOL if tolerances == "check-default" else spec.synth_tol()
+    h.replay(spec, fx, h.OracleStepper, tol)                                           # the unperturbed oracle passes
     names = [str(n) for n in fx["reward_names"]]
     name = names[int(np.argmax(np.abs(fx["episode_sums"][-1]).max(axis=1)))]
     with pytest.raises(AssertionError):
-        sm.replay(task, fx, _perturbed(task, how, name), check)
+        h.replay(spec, fx, _perturbed(how, name), tol)
