@@ -268,6 +268,13 @@ def load_lib():
     lib.lg_rollout_gae.argtypes = [i32, i32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, f32, f32, C.c_void_p, C.c_void_p,
                                    C.c_void_p, C.c_void_p]
     lib.lg_rollout_record.restype = lib.lg_rollout_gae.restype = C.c_int
+    vp = C.c_void_p
+    lib.lg_rollout_traj_index.argtypes = [i32, i32, vp, vp, vp, i32, vp, vp]
+    lib.lg_rollout_mask_index.argtypes = [i32, i32, vp, vp, i32, vp, vp]
+    lib.lg_rollout_pad.argtypes = [i32, i32, vp, i32, i32, i32, C.POINTER(LgRowCopy), i32, C.POINTER(LgRowCopy), C.POINTER(i32), i32, vp, vp]
+    lib.lg_rollout_unpad.argtypes = [i32, i32, vp, i32, i32, i32, vp, vp, i32, vp]
+    for f in ROLLOUT_EXPORTS[2:]:
+        getattr(lib, f).restype = C.c_int
     lib.lg_last_error.restype = C.c_char_p
     lib.lg_last_kernel.argtypes = [H]
     lib.lg_last_kernel.restype = C.c_char_p
@@ -282,7 +289,8 @@ def load_lib():
 EXPORTS = ["lg_create", "lg_destroy", "lg_set_task", "lg_set_terrain", "lg_bind", "lg_step",
            "lg_time_steps", "lg_obs_window", "lg_obs_set", "lg_obs_set_select", "lg_obs_window_select", "lg_profile", "lg_profile_read", "lg_philox", "lg_dpp_kat", "lg_dpp_kat_cases", "lg_dpp_kat_run", "lg_stream_copy", "lg_terrain_generate", "lg_terrain_max_kind", "lg_last_kernel", "lg_last_error",
            "lg_abi_version"]
-ROLLOUT_EXPORTS = ["lg_rollout_record", "lg_rollout_gae"]          # include/lgrollout.h
+ROLLOUT_EXPORTS = ["lg_rollout_record", "lg_rollout_gae", "lg_rollout_traj_index", "lg_rollout_mask_index", "lg_rollout_pad",
+                   "lg_rollout_unpad"]          # include/lgrollout.h
 ROLLOUT_MAX_COPIES = 8
 
 

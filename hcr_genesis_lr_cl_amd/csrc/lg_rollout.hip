@@ -133,3 +133,291 @@ extern "C" int lg_rollout_gae(int32_t n_steps, int32_t n_envs, const float *valu
     if (e != hipSuccess) return lg_fail_msg(std::string("lg_rollout_gae: ") + hipGetErrorString(e));
     return 0;
 }
+
+// ---- recurrent policies: trajectory index, padded trajectories / masks / start hidden states, un-padding ------------------------
+// Reference call sites replaced: rsl_rl/utils/utils.py:33-65 (split_and_pad_trajectories: every trajectory length to the host, one tensor
+// per trajectory, pad_sequence), utils.py:67-71 (unpad_trajectories) and rollout_storage.py:203-228 (a torch.sum used as a slice bound and
+// a boolean-mask gather over the whole hidden-state tensor, per mini-batch).  A trajectory starts at t = 0 and behind every done, ends at
+// a done or at t = T-1; trajectories are numbered env-major, then by time.  The index is (3, capacity) int32: env, t_start, length.
+#define LG_TRAJ_BLOCK 1024
+#define LG_TRAJ_WAVES (LG_TRAJ_BLOCK / 64)
+
+// exclusive prefix sum of v over the 1024-thread block (wave scan by shuffles, the 16 wave totals by the first wave); *total = block sum
+__device__ inline int block_exclusive_scan(int v, int *sh, int *total) {
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int inc = v;
+    for (int off = 1; off < 64; off <<= 1) { const int o = __shfl_up(inc, off, 64); if (lane >= off) inc += o; }
+    if (lane == 63) sh[w] = inc;
+    __syncthreads();
+    if (w == 0) {
+        const int x = lane < LG_TRAJ_WAVES ? sh[lane] : 0;
+        int xi = x;
+        for (int off = 1; off < LG_TRAJ_WAVES; off <<= 1) { const int o = __shfl_up(xi, off, 64); if (lane >= off) xi += o; }
+        if (lane < LG_TRAJ_WAVES) sh[lane] = xi - x;
+        if (lane == LG_TRAJ_WAVES - 1) sh[LG_TRAJ_WAVES] = xi;
+    }
+    __syncthreads();
+    const int ex = sh[w] + inc - v;
+    *total = sh[LG_TRAJ_WAVES];
+    __syncthreads();                                   // sh is written again by the next tile
+    return ex;
+}
+
+__device__ inline int block_max(int v, int *sh) {
+    for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(v, off, 64); v = o > v ? o : v; }
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    int m = 0;
+    for (int k = 0; k < LG_TRAJ_WAVES; k++) m = sh[k] > m ? sh[k] : m;
+    return m;
+}
+
+// One workgroup; one lane per env walks its T flags (consecutive lanes on consecutive envs: coalesced, as in gae_kernel), env tiles of 1024
+// with a carry.  No atomics: the numbering is the scan's, so it is the same on every call.  Latency-bound and tiny (T * N bytes in, a
+// few hundred KB out): one launch that replaces a host round trip, not something to tune.
+__global__ __launch_bounds__(LG_TRAJ_BLOCK) void traj_index_kernel(int T, int N, const uint8_t *__restrict__ dones, int *__restrict__ traj_offset,
+                                                                   int *__restrict__ traj, int cap, int *__restrict__ header) {
+    __shared__ int sh[LG_TRAJ_WAVES + 1];
+    int carry = 0, longest = 0;
+    for (int base = 0; base < N; base += LG_TRAJ_BLOCK) {
+        const int e = base + (int)threadIdx.x;
+        int cnt = 0;
+        if (e < N) {
+            cnt = 1;
+            for (int t = 0; t < T - 1; t++) cnt += dones[(size_t)t * N + e] != 0;
+        }
+        int total;
+        const int ex = block_exclusive_scan(cnt, sh, &total);
+        if (e < N) {
+            int j = carry + ex, start = 0;
+            traj_offset[e] = j;
+            for (int t = 0; t < T; t++) {
+                if (t == T - 1 || dones[(size_t)t * N + e]) {
+                    const int len = t - start + 1;
+                    if (j < cap) { traj[j] = e; traj[(size_t)cap + j] = start; traj[2 * (size_t)cap + j] = len; }
+                    longest = len > longest ? len : longest;
+                    j++;
+                    start = t + 1;
+                }
+            }
+        }
+        carry += total;
+    }
+    longest = block_max(longest, sh);
+    if (threadIdx.x == 0) { traj_offset[N] = carry; header[0] = carry; header[1] = longest; }
+}
+
+// The same index from a (T, n_traj) mask alone (what unpad_trajectories is given): length = the column's count, and because the
+// trajectories of one env fill its T steps in order, the running sum of the lengths is env * T + t_start.  header = (steps covered, longest);
+// a trajectory that would run past its env's last step (a mask no rollout produces) reports INT32_MAX as the longest, so the caller sees it.
+__global__ __launch_bounds__(LG_TRAJ_BLOCK) void mask_index_kernel(int T, int n_traj, const uint8_t *__restrict__ masks, int *__restrict__ traj,
+                                                                   int cap, int *__restrict__ header) {
+    __shared__ int sh[LG_TRAJ_WAVES + 1];
+    int carry = 0, longest = 0;
+    for (int base = 0; base < n_traj; base += LG_TRAJ_BLOCK) {
+        const int j = base + (int)threadIdx.x;
+        int len = 0;
+        if (j < n_traj)
+            for (int t = 0; t < T; t++) len += masks[(size_t)t * n_traj + j] != 0;
+        int total;
+        const int p = carry + block_exclusive_scan(len, sh, &total);
+        if (j < n_traj && j < cap) { traj[j] = p / T; traj[(size_t)cap + j] = p % T; traj[2 * (size_t)cap + j] = len; }
+        const int seen = p % T + len > T ? INT32_MAX : len;
+        longest = seen > longest ? seen : longest;
+        carry += total;
+    }
+    longest = block_max(longest, sh);
+    if (threadIdx.x == 0) { header[0] = carry; header[1] = longest; }
+}
+
+// Division of a flat index below 2^31 by a divisor fixed per launch: q = (n * m) >> sh with m = ceil(2^sh / d), sh = 31 + ceil(log2 d).
+// Exact: m = (2^sh + e) / d with 0 <= e < d <= 2^(sh - 31), so n * m / 2^sh = n / d + n * e / (d * 2^sh) and the excess is below 1 / d for
+// n < 2^31.  The gathers split every flat index twice, and two of the hardware's ~20-instruction u32 divisions per 4-byte element bind
+// the scalar path by arithmetic instead of HBM.
+struct FastDiv { unsigned m, sh; };
+static FastDiv fast_div(unsigned d) {
+    unsigned s = 0;
+    while ((1ull << s) < d) s++;
+    FastDiv f;
+    f.sh = 31 + s;
+    f.m = (unsigned)(((1ull << f.sh) + d - 1) / d);
+    return f;
+}
+__device__ inline unsigned div_by(unsigned n, FastDiv f) { return (unsigned)(((unsigned long long)n * f.m) >> f.sh); }
+
+struct PadArgs {
+    int T, N, n_traj, rows, cap; const int *traj; uint8_t *masks;
+    LgRowCopy src[LG_ROLLOUT_MAX_COPIES]; int ns; unsigned src_vec;          // bit i: source i moves float4
+    LgRowCopy hid[LG_ROLLOUT_MAX_COPIES]; int hl[LG_ROLLOUT_MAX_COPIES]; int nh; unsigned hid_vec;
+    FastDiv src_row[LG_ROLLOUT_MAX_COPIES], src_w[LG_ROLLOUT_MAX_COPIES], hid_row[LG_ROLLOUT_MAX_COPIES], hid_w[LG_ROLLOUT_MAX_COPIES], by_traj;   // per element type
+};
+
+__device__ inline void zero_of(float &v) { v = 0.f; }
+__device__ inline void zero_of(float4 &v) { v = make_float4(0.f, 0.f, 0.f, 0.f); }
+
+// padded[t', j, :] = src[t_start_j + t', env_j, :] for t' < length_j, else 0.  Gather: the flat index runs over the destination, every
+// element is written once (zeros included), consecutive lanes on consecutive elements of a row.  Sizes < 2^31 (checked by the caller).
+template <typename V> __device__ inline void pad_segment(const PadArgs &a, const LgRowCopy &c, FastDiv by_row, FastDiv by_w, unsigned tid, unsigned stride) {
+    constexpr unsigned W = sizeof(V) / sizeof(float);
+    const unsigned dv = (unsigned)c.width / W, sv = (unsigned)c.src_stride / W, row = (unsigned)a.n_traj * dv, tot = (unsigned)a.rows * row;
+    const V *__restrict__ src = (const V *)c.src;
+    V *__restrict__ dst = (V *)c.dst;
+    const int *env = a.traj, *start = a.traj + a.cap, *len = a.traj + 2 * (size_t)a.cap;
+    for (unsigned i = tid; i < tot; i += stride) {
+        const unsigned tp = div_by(i, by_row), r = i - tp * row, j = div_by(r, by_w), k = r - j * dv;
+        V v;
+        zero_of(v);
+        const int t = start[j] + (int)tp, e = env[j];
+        if ((int)tp < len[j] && t < a.T && e < a.N) v = src[((size_t)t * a.N + e) * sv + k];
+        dst[i] = v;
+    }
+}
+
+// hid[l, j, :] = saved[t_start_j, l, env_j, :]: the state the policy held when trajectory j began; saved is (T, L, N, H)
+template <typename V> __device__ inline void hidden_segment(const PadArgs &a, const LgRowCopy &c, int L, FastDiv by_row, FastDiv by_w, unsigned tid, unsigned stride) {
+    constexpr unsigned W = sizeof(V) / sizeof(float);
+    const unsigned hv = (unsigned)c.width / W, row = (unsigned)a.n_traj * hv, tot = (unsigned)L * row;
+    const V *__restrict__ src = (const V *)c.src;
+    V *__restrict__ dst = (V *)c.dst;
+    const int *env = a.traj, *start = a.traj + a.cap;
+    for (unsigned i = tid; i < tot; i += stride) {
+        const unsigned l = div_by(i, by_row), r = i - l * row, j = div_by(r, by_w), k = r - j * hv;
+        V v;
+        zero_of(v);
+        const int t = start[j], e = env[j];
+        if (t < a.T && e < a.N) v = src[(((size_t)t * L + l) * a.N + e) * hv + k];
+        dst[i] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void rollout_pad_kernel(PadArgs a) {
+    const unsigned stride = gridDim.x * blockDim.x, tid = blockIdx.x * blockDim.x + threadIdx.x;
+    for (int s = 0; s < a.ns; s++) {
+        if (a.src_vec >> s & 1) pad_segment<float4>(a, a.src[s], a.src_row[s], a.src_w[s], tid, stride);
+        else pad_segment<float>(a, a.src[s], a.src_row[s], a.src_w[s], tid, stride);
+    }
+    for (int s = 0; s < a.nh; s++) {
+        if (a.hid_vec >> s & 1) hidden_segment<float4>(a, a.hid[s], a.hl[s], a.hid_row[s], a.hid_w[s], tid, stride);
+        else hidden_segment<float>(a, a.hid[s], a.hl[s], a.hid_row[s], a.hid_w[s], tid, stride);
+    }
+    if (a.masks) {                                      // (T, n_traj) even where the longest trajectory is shorter than T (utils.py:64)
+        const int *len = a.traj + 2 * (size_t)a.cap;
+        const unsigned tot = (unsigned)a.T * (unsigned)a.n_traj;
+        for (unsigned i = tid; i < tot; i += stride) {
+            const unsigned t = div_by(i, a.by_traj), j = i - t * (unsigned)a.n_traj;
+            a.masks[i] = (int)t < len[j];
+        }
+    }
+}
+
+// the inverse: dst[t_start_j + t', env_j, :] = padded[t', j, :] for t' < length_j.  The trajectories tile the (T, N) grid, so this
+// scatter writes every destination element exactly once; the bounds test keeps a malformed mask from writing outside dst.
+template <typename V> __global__ __launch_bounds__(256) void rollout_unpad_kernel(int T, int N, int n_traj, int rows, int cap,
+                                                                                  const int *__restrict__ traj, const V *__restrict__ src,
+                                                                                  V *__restrict__ dst, unsigned dv, FastDiv by_row, FastDiv by_w) {
+    const unsigned stride = gridDim.x * blockDim.x, row = (unsigned)n_traj * dv, tot = (unsigned)rows * row;
+    const int *env = traj, *start = traj + cap, *len = traj + 2 * (size_t)cap;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += stride) {
+        const unsigned tp = div_by(i, by_row), r = i - tp * row, j = div_by(r, by_w), k = r - j * dv;
+        const int t = start[j] + (int)tp, e = env[j];
+        if ((int)tp < len[j] && t < T && e < N) dst[((size_t)t * N + e) * dv + k] = src[i];
+    }
+}
+
+static bool aligned16(const void *p) { return ((uintptr_t)p & 15) == 0; }
+static unsigned grid_for(long long most) {
+    long long blocks = (most + 255) / 256;
+    return (unsigned)(blocks > 4096 ? 4096 : (blocks < 1 ? 1 : blocks));
+}
+static const long long kMaxFlat = 0x7fffffffLL;          // the kernels index each tensor with 32 bits
+
+extern "C" int lg_rollout_traj_index(int32_t n_steps, int32_t n_envs, const uint8_t *dones, int32_t *traj_offset, int32_t *traj,
+                                     int32_t capacity, int32_t *header, void *stream) {
+    if (n_steps < 1 || n_envs < 1 || !dones || !traj_offset || !traj || !header) return lg_fail_msg("lg_rollout_traj_index: null / empty argument");
+    if ((long long)n_steps * n_envs > kMaxFlat) return lg_fail_msg("lg_rollout_traj_index: n_steps * n_envs overflows 32 bits");
+    if (capacity < n_envs) return lg_fail_msg("lg_rollout_traj_index: capacity below n_envs (every env has at least one trajectory)");
+    hipLaunchKernelGGL(traj_index_kernel, dim3(1), dim3(LG_TRAJ_BLOCK), 0, (hipStream_t)stream, n_steps, n_envs, dones, traj_offset, traj, capacity,
+                       header);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return lg_fail_msg(std::string("lg_rollout_traj_index: ") + hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int lg_rollout_mask_index(int32_t n_steps, int32_t n_traj, const uint8_t *masks, int32_t *traj, int32_t capacity, int32_t *header,
+                                     void *stream) {
+    if (n_steps < 1 || n_traj < 1 || !masks || !traj || !header) return lg_fail_msg("lg_rollout_mask_index: null / empty argument");
+    if ((long long)n_steps * n_traj > kMaxFlat) return lg_fail_msg("lg_rollout_mask_index: n_steps * n_traj overflows 32 bits");
+    if (capacity < n_traj) return lg_fail_msg("lg_rollout_mask_index: capacity below n_traj");
+    hipLaunchKernelGGL(mask_index_kernel, dim3(1), dim3(LG_TRAJ_BLOCK), 0, (hipStream_t)stream, n_steps, n_traj, masks, traj, capacity, header);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return lg_fail_msg(std::string("lg_rollout_mask_index: ") + hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int lg_rollout_pad(int32_t n_steps, int32_t n_envs, const int32_t *traj, int32_t capacity, int32_t n_traj, int32_t rows,
+                              const LgRowCopy *sources, int32_t n_sources, const LgRowCopy *hidden, const int32_t *hidden_layers,
+                              int32_t n_hidden, uint8_t *masks, void *stream) {
+    if (n_steps < 1 || n_envs < 1 || !traj || n_traj < 1 || rows < 1) return lg_fail_msg("lg_rollout_pad: null / empty argument");
+    if ((long long)n_steps * n_envs > kMaxFlat) return lg_fail_msg("lg_rollout_pad: n_steps * n_envs overflows 32 bits");
+    if (capacity < n_traj) return lg_fail_msg("lg_rollout_pad: index capacity below n_traj");
+    if (rows > n_steps) return lg_fail_msg("lg_rollout_pad: more padded rows than steps");
+    if (n_sources < 0 || n_sources > LG_ROLLOUT_MAX_COPIES || (n_sources && !sources)) return lg_fail_msg("lg_rollout_pad: bad source list");
+    if (n_hidden < 0 || n_hidden > LG_ROLLOUT_MAX_COPIES || (n_hidden && (!hidden || !hidden_layers))) return lg_fail_msg("lg_rollout_pad: bad hidden-state list");
+    if (!n_sources && !n_hidden && !masks) return lg_fail_msg("lg_rollout_pad: nothing to write");
+    PadArgs a;
+    a.T = n_steps; a.N = n_envs; a.n_traj = n_traj; a.rows = rows; a.cap = capacity; a.traj = traj; a.masks = masks;
+    a.ns = n_sources; a.nh = n_hidden; a.src_vec = a.hid_vec = 0; a.by_traj = fast_div((unsigned)n_traj);
+    long long most = masks ? (long long)n_steps * n_traj : 1;
+    if (most > kMaxFlat) return lg_fail_msg("lg_rollout_pad: mask larger than 2^31 entries");
+    for (int i = 0; i < n_sources; i++) {
+        const LgRowCopy &c = sources[i];
+        if (!c.src || !c.dst || c.width < 1 || c.src_stride < c.width) return lg_fail_msg("lg_rollout_pad: bad source (null pointer, width < 1 or stride < width)");
+        if ((long long)rows * n_traj * c.width > kMaxFlat)
+            return lg_fail_msg("lg_rollout_pad: tensor larger than 2^31 entries");
+        a.src[i] = c;
+        const bool vec = c.width % 4 == 0 && c.src_stride % 4 == 0 && aligned16(c.src) && aligned16(c.dst);
+        if (vec) a.src_vec |= 1u << i;
+        a.src_w[i] = fast_div((unsigned)c.width / (vec ? 4 : 1));
+        a.src_row[i] = fast_div((unsigned)n_traj * ((unsigned)c.width / (vec ? 4 : 1)));
+        const long long tot = (long long)rows * n_traj * c.width / (vec ? 4 : 1);
+        if (tot > most) most = tot;
+    }
+    for (int i = 0; i < n_hidden; i++) {
+        const LgRowCopy &c = hidden[i];
+        if (!c.src || !c.dst || c.width < 1 || c.src_stride != c.width || hidden_layers[i] < 1)
+            return lg_fail_msg("lg_rollout_pad: bad hidden state (null pointer, width < 1, layers < 1 or rows not contiguous)");
+        if ((long long)hidden_layers[i] * n_traj * c.width > kMaxFlat) return lg_fail_msg("lg_rollout_pad: tensor larger than 2^31 entries");
+        a.hid[i] = c; a.hl[i] = hidden_layers[i];
+        const bool vec = c.width % 4 == 0 && aligned16(c.src) && aligned16(c.dst);
+        if (vec) a.hid_vec |= 1u << i;
+        a.hid_w[i] = fast_div((unsigned)c.width / (vec ? 4 : 1));
+        a.hid_row[i] = fast_div((unsigned)n_traj * ((unsigned)c.width / (vec ? 4 : 1)));
+        const long long tot = (long long)hidden_layers[i] * n_traj * c.width / (vec ? 4 : 1);
+        if (tot > most) most = tot;
+    }
+    hipLaunchKernelGGL(rollout_pad_kernel, dim3(grid_for(most)), dim3(256), 0, (hipStream_t)stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return lg_fail_msg(std::string("lg_rollout_pad: ") + hipGetErrorString(e));
+    return 0;
+}
+
+extern "C" int lg_rollout_unpad(int32_t n_steps, int32_t n_envs, const int32_t *traj, int32_t capacity, int32_t n_traj, int32_t rows,
+                                const float *padded, float *dst, int32_t width, void *stream) {
+    if (n_steps < 1 || n_envs < 1 || !traj || n_traj < 1 || rows < 1 || !padded || !dst) return lg_fail_msg("lg_rollout_unpad: null / empty argument");
+    if (width < 1) return lg_fail_msg("lg_rollout_unpad: width < 1");
+    if (capacity < n_traj) return lg_fail_msg("lg_rollout_unpad: index capacity below n_traj");
+    if ((long long)n_steps * n_envs > kMaxFlat || (long long)rows * n_traj * width > kMaxFlat)
+        return lg_fail_msg("lg_rollout_unpad: tensor larger than 2^31 entries");
+    const bool vec = width % 4 == 0 && aligned16(padded) && aligned16(dst);
+    const long long tot = (long long)rows * n_traj * width / (vec ? 4 : 1);
+    const unsigned dv = (unsigned)width / (vec ? 4 : 1);
+    const FastDiv by_row = fast_div((unsigned)n_traj * dv), by_w = fast_div(dv);
+    hipStream_t st = (hipStream_t)stream;
+    if (vec) hipLaunchKernelGGL(rollout_unpad_kernel<float4>, dim3(grid_for(tot)), dim3(256), 0, st, n_steps, n_envs, n_traj, rows, capacity, traj,
+                                (const float4 *)padded, (float4 *)dst, dv, by_row, by_w);
+    else hipLaunchKernelGGL(rollout_unpad_kernel<float>, dim3(grid_for(tot)), dim3(256), 0, st, n_steps, n_envs, n_traj, rows, capacity, traj, padded, dst,
+                            dv, by_row, by_w);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return lg_fail_msg(std::string("lg_rollout_unpad: ") + hipGetErrorString(e));
+    return 0;
+}

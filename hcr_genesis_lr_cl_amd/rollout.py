@@ -2,15 +2,20 @@
 
 Mirrors the reference's rsl_rl/storage/rollout_storage.py: same constructor, same tensors under the same names and shapes
 ((T, N, width) float32; dones (T, N, 1) uint8), `add_transitions`, `clear`, `compute_returns`, `get_statistics`,
-`mini_batch_generator` -- so rsl_rl's PPO with a feed-forward ActorCritic takes it in place of its own (recurrent policies are refused:
-hidden states are not stored).  What changes is how the rows are filled:
+`mini_batch_generator`, `reccurent_mini_batch_generator` -- so rsl_rl's PPO takes it in place of its own, with a feed-forward ActorCritic
+or with ActorCriticRecurrent (LSTM / GRU: hidden states are stored per step under the reference's names).  What changes is how the rows
+are filled and how the recurrent mini-batches are cut:
 
   * `record(t-less API: add_step)`: reward (with the time-out bootstrap of rsl_rl/algorithms/ppo.py:106-113), done flag and any
     observation rows in ONE launch (`lg_rollout_record`) instead of nine `copy_` launches (rollout_storage.py:92-100);
   * `compute_returns`: GAE over the whole rollout plus the advantage normalisation in two launches (`lg_rollout_gae`) instead
     of a 24-iteration Python loop of elementwise ops (rollout_storage.py:124-138);
   * with `attach_env(env)` on a task with unstacked observations the storage's observation rows ARE the env's observation
-    copies (LgTaskCfg.obs_sets = T + 1): step() writes each observation straight into its row and nothing is copied.
+    copies (LgTaskCfg.obs_sets = T + 1): step() writes each observation straight into its row and nothing is copied;
+  * `reccurent_mini_batch_generator`: the trajectory split of rsl_rl/utils/utils.py:33-65 (every length to the host, one tensor per
+    trajectory, pad_sequence) and the per-mini-batch sum / boolean gather of rollout_storage.py:203-228 become one index launch
+    (`lg_rollout_traj_index`), one small read-back and one launch (`lg_rollout_pad`) that writes the padded observations, the masks and
+    the start hidden states of every trajectory; `unpad_trajectories` is the inverse (`lg_rollout_mask_index` + `lg_rollout_unpad`).
 
 There is no CPU path: the kernels live in csrc/liblgsim.so (include/lgrollout.h)."""
 from __future__ import annotations
@@ -23,6 +28,13 @@ from . import abi
 
 
 class RolloutStorage:
+    """The reference's constructor plus two keywords: `env` (zero-copy observation rows, see `attach_env`) and `lstm_critic_hidden`.
+
+    `lstm_critic_hidden` decides what `reccurent_mini_batch_generator` hands the critic of an LSTM policy.  The reference's line
+    rollout_storage.py:231 reads `hid_c_batch = hid_c_batch[0] if len(hid_c_batch)==1 else hid_a_batch`: with an LSTM (two tensors per
+    network) the critic is given the ACTOR's start states.  "reference" (the default) reproduces that, so PPO.update computes what it
+    computes on rsl_rl's own storage; "own" yields the critic's own (h, c).  A GRU is unaffected: its critic always gets its own."""
+
     class Transition:                      # rollout_storage.py:37-52
         def __init__(self):
             self.observations = None
@@ -39,7 +51,11 @@ class RolloutStorage:
         def clear(self):
             self.__init__()
 
-    def __init__(self, num_envs, num_transitions_per_env, obs_shape, privileged_obs_shape, actions_shape, device="cuda:0", env=None):
+    def __init__(self, num_envs, num_transitions_per_env, obs_shape, privileged_obs_shape, actions_shape, device="cuda:0", env=None,
+                 lstm_critic_hidden="reference"):
+        if lstm_critic_hidden not in ("reference", "own"):
+            raise ValueError(f"lstm_critic_hidden={lstm_critic_hidden!r}: expected 'reference' or 'own'")
+        self.lstm_critic_hidden = lstm_critic_hidden
         self.lib = abi.load_lib()
         self.device = torch.device(device)
         if self.device.type != "cuda":
@@ -66,6 +82,7 @@ class RolloutStorage:
         self.sigma = z(T, N, *actions_shape)
         self._scratch = z(2, dtype=torch.float64)
         self.saved_hidden_states_a = self.saved_hidden_states_c = None
+        self._traj = self._traj_head = None                 # trajectory index buffers, allocated by the first recurrent generator call
         self.step = 0
 
     # ---- zero-copy observation rows -----------------------------------------------------------------------------------
@@ -98,15 +115,16 @@ class RolloutStorage:
         return self._env is not None
 
     # ---- filling rows -------------------------------------------------------------------------------------------------
-    def add_step(self, rew, reset, time_outs, gamma, observations=None, critic_observations=None, extra_copies=()):
+    def add_step(self, rew, reset, time_outs, gamma, observations=None, critic_observations=None, extra_copies=(), hidden_states=None):
         """One launch for everything the env contributes to row `self.step`: rewards (+ gamma * value * time_out), dones and
         the observation rows (skipped when they are zero-copy).  `values[self.step]` must already hold the critic's output for
         this step (the bootstrap reads it).  Policy-side rows (actions, values, log-prob, mean, std) are written by the caller
-        straight into `self.actions[self.step]` ... as outputs of its own ops."""
+        straight into `self.actions[self.step]` ... as outputs of its own ops.  `hidden_states` is what a recurrent policy held BEFORE it acted
+        on this step, as `add_transitions` takes it; its rows go out in the same launch."""
         t = self.step
         if t >= self.num_transitions_per_env:
             raise AssertionError("Rollout buffer overflow")
-        copies = []
+        copies = self._hidden_copies(t, hidden_states)
         if observations is not None and not self.zero_copy:
             copies.append((observations, self.observations[t]))
         if critic_observations is not None and self.privileged_observations is not None:
@@ -131,10 +149,6 @@ class RolloutStorage:
         t = self.step
         if t >= self.num_transitions_per_env:
             raise AssertionError("Rollout buffer overflow")
-        hs = getattr(transition, "hidden_states", None)
-        if hs is not None and tuple(hs) != (None, None):
-            raise NotImplementedError("hidden states (recurrent ActorCritic, rollout_storage.py:101-122) are not stored here: "
-                                      "use rsl_rl's own RolloutStorage for recurrent policies")
         self.actions[t].copy_(transition.actions)
         self.values[t].copy_(transition.values)
         self.actions_log_prob[t].copy_(transition.actions_log_prob.view(-1, 1))
@@ -142,7 +156,36 @@ class RolloutStorage:
         self.sigma[t].copy_(transition.action_sigma)
         crit = transition.critic_observations if self.privileged_observations is not None else None
         self.add_step(transition.rewards.reshape(-1).contiguous(), transition.dones.reshape(-1), None, 0.0,
-                      observations=transition.observations, critic_observations=crit)
+                      observations=transition.observations, critic_observations=crit,
+                      hidden_states=getattr(transition, "hidden_states", None))
+
+    def _hidden_copies(self, t, hidden_states):
+        """Row copies that store a recurrent policy's hidden states at step t (rollout_storage.py:104-119).  None or (None, None): nothing
+        (the first act of a fresh policy, so row 0 of the first rollout stays zero).  A GRU gives one (L, N, H) tensor per network, an LSTM
+        an (h, c) tuple; `saved_hidden_states_a` / `_c` are lists of (T, L, N, H) tensors allocated on first use."""
+        if hidden_states is None:
+            return []
+        hid_a, hid_c = hidden_states
+        if hid_a is None and hid_c is None:
+            return []
+        hid_a = tuple(hid_a) if isinstance(hid_a, (tuple, list)) else (hid_a,)
+        hid_c = tuple(hid_c) if isinstance(hid_c, (tuple, list)) else (hid_c,)
+        T, N = self.num_transitions_per_env, self.num_envs
+        if self.saved_hidden_states_a is None:
+            for h in hid_a + hid_c:
+                if h.dim() != 3 or h.shape[1] != N:
+                    raise ValueError(f"hidden states are (layers, {N}, hidden) tensors, got {tuple(h.shape)}")
+            self.saved_hidden_states_a = [torch.zeros(T, *h.shape, device=self.device) for h in hid_a]
+            self.saved_hidden_states_c = [torch.zeros(T, *h.shape, device=self.device) for h in hid_c]
+        if len(hid_a) != len(self.saved_hidden_states_a) or len(hid_c) != len(self.saved_hidden_states_c):
+            raise ValueError("the number of hidden-state tensors changed within a storage")
+        copies = []
+        for h, saved in zip(hid_a + hid_c, self.saved_hidden_states_a + self.saved_hidden_states_c):
+            if h.shape != saved.shape[1:] or h.dtype != torch.float32 or h.device != saved.device:
+                raise ValueError(f"hidden state {tuple(h.shape)} {h.dtype} on {h.device} does not fit the stored {tuple(saved.shape[1:])} float32")
+            # a contiguous (L, N, H) block is copied flat; the record kernel's copies are N rows, so the block is viewed as (N, L * H)
+            copies.append((h.contiguous().view(N, -1), saved[t].view(N, -1)))
+        return copies
 
     def clear(self):
         self.step = 0
@@ -180,5 +223,137 @@ class RolloutStorage:
             for b in blocks:
                 yield (*(flat[k][b] for k in order), (None, None), None)
 
+    # ---- recurrent policies ---------------------------------------------------------------------------------------------
+    def trajectory_index(self):
+        """Trajectories of the stored rollout, env-major then by time (a trajectory starts at t = 0 and behind every done and ends at a
+        done or at the last step): (index, n_traj, max_len, traj_offset).  `index` is a (3, T * N) int32 device tensor whose first n_traj
+        columns hold env, t_start and length; `traj_offset` is a host list of N + 1 ints, the first trajectory of every env.  One launch
+        and ONE device-to-host copy (header + offsets); nothing else in the recurrent generator waits for the device."""
+        T, N = self.num_transitions_per_env, self.num_envs
+        if self._traj is None:
+            self._traj = torch.empty(3, T * N, dtype=torch.int32, device=self.device)
+            self._traj_head = torch.empty(2 + N + 1, dtype=torch.int32, device=self.device)      # n_traj, max_len, traj_offset[N + 1]
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        abi.check(self.lib.lg_rollout_traj_index(T, N, self.dones.data_ptr(), self._traj_head[2:].data_ptr(), self._traj.data_ptr(), T * N,
+                                                 self._traj_head.data_ptr(), stream), self.lib)
+        host = self._traj_head.cpu().tolist()
+        return self._traj, host[0], host[1], host[2:]
+
+    def pad_trajectories(self, tensors, index=None, hidden=(), masks=True):
+        """split_and_pad_trajectories (rsl_rl/utils/utils.py:33-65) of up to eight contiguous (T, N, ...) float32 tensors in one launch that
+        shares one trajectory index: ([padded (max_len, n_traj, ...)], [start states (L, n_traj, H) of every (T, L, N, H) tensor in
+        `hidden`], masks (T, n_traj) bool or None).  The masks keep T rows where max_len < T, as the reference's do."""
+        T, N = self.num_transitions_per_env, self.num_envs
+        traj, n_traj, max_len, _ = index if index is not None else self.trajectory_index()
+        dev = self.device
+
+        def row_copies(items, what):
+            arr = (abi.LgRowCopy * max(len(items), 1))()
+            for i, (src, dst, width) in enumerate(items):
+                if not src.is_contiguous() or src.dtype != torch.float32 or src.device != dst.device:
+                    raise ValueError(f"{what} must be contiguous float32 tensors on {dev}")
+                arr[i].src, arr[i].dst, arr[i].width, arr[i].src_stride = src.data_ptr(), dst.data_ptr(), width, width
+            return arr
+
+        src_items, hid_items, layers = [], [], []
+        for x in tensors:
+            if x.dim() < 2 or x.shape[0] != T or x.shape[1] != N:
+                raise ValueError(f"padded tensors are ({T}, {N}, ...), got {tuple(x.shape)}")
+            out = torch.empty(max_len, n_traj, *x.shape[2:], device=dev)
+            src_items.append((x, out, x[0, 0].numel()))
+        for h in hidden:
+            if h.dim() != 4 or h.shape[0] != T or h.shape[2] != N:
+                raise ValueError(f"saved hidden states are ({T}, layers, {N}, hidden), got {tuple(h.shape)}")
+            hid_items.append((h, torch.empty(h.shape[1], n_traj, h.shape[3], device=dev), h.shape[3]))
+            layers.append(h.shape[1])
+        mask = torch.empty(T, n_traj, dtype=torch.bool, device=dev) if masks else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        abi.check(self.lib.lg_rollout_pad(T, N, traj.data_ptr(), traj.shape[1], n_traj, max_len, row_copies(src_items, "padded tensors"),
+                                          len(src_items), row_copies(hid_items, "saved hidden states"), (C.c_int32 * max(len(layers), 1))(*layers),
+                                          len(hid_items), 0 if mask is None else mask.data_ptr(), stream), self.lib)
+        return [o for _, o, _ in src_items], [o for _, o, _ in hid_items], mask
+
     def reccurent_mini_batch_generator(self, num_mini_batches, num_epochs=8):
-        raise NotImplementedError("recurrent policies are outside the hot path (SURVEY 8): use rsl_rl's own RolloutStorage for them")
+        """Mini-batches for a recurrent policy in the tuple order rsl_rl's PPO.update unpacks (rollout_storage.py:187-236; the spelling is
+        the reference's): padded obs, padded critic obs (the actor's when there are no privileged observations), actions, values, advantages,
+        returns, old log-prob, old mean, old std, (hid_a, hid_c), masks.  Mini-batch i is envs [i * N // num_mini_batches, (i + 1) * ...)
+        in order, not shuffled; the (T, start:stop, .) tensors are views of the storage; the padded tensors and masks are views of one
+        padded set built per call (index launch, one read-back, pad launch: no other host sync, whatever the number of mini-batches and
+        epochs).  Start hidden states are gathered once for all trajectories as (L, n_traj, H); each mini-batch gets a contiguous copy
+        of its slice (one small copy per tensor per mini-batch, made in the first epoch and yielded again in the later ones: treat them
+        as read-only, as PPO.update does).  A GRU yields tensors for hid_a / hid_c, an LSTM lists of two; see the class docstring for
+        `lstm_critic_hidden`."""
+        if self.saved_hidden_states_a is None:
+            raise RuntimeError("reccurent_mini_batch_generator: no hidden states were stored (add_transitions / add_step with hidden_states)")
+        index = self.trajectory_index()
+        offsets = index[3]
+        tensors = [self.observations] + ([self.privileged_observations] if self.privileged_observations is not None else [])
+        n_a = len(self.saved_hidden_states_a)
+        # an LSTM's critic is handed the actor's start states unless asked otherwise (rollout_storage.py:231): its own are then not gathered
+        own_critic = len(self.saved_hidden_states_c) == 1 or self.lstm_critic_hidden == "own"
+        padded, hid, masks = self.pad_trajectories(tensors, index, self.saved_hidden_states_a + (self.saved_hidden_states_c if own_critic else []))
+        padded_obs, padded_critic = padded[0], padded[-1]
+        per = self.num_envs // num_mini_batches
+        hid_batches = []
+        for epoch in range(num_epochs):
+            for i in range(num_mini_batches):
+                start, stop = i * per, (i + 1) * per
+                first, last = offsets[start], offsets[stop]
+                if epoch == 0:
+                    hid_a = [h[:, first:last].contiguous() for h in hid[:n_a]]
+                    hid_c = [h[:, first:last].contiguous() for h in hid[n_a:]] if own_critic else hid_a
+                    hid_batches.append((hid_a[0] if len(hid_a) == 1 else hid_a, hid_c[0] if len(hid_c) == 1 else hid_c))
+                hid_a, hid_c = hid_batches[i]
+                yield (padded_obs[:, first:last], padded_critic[:, first:last], self.actions[:, start:stop], self.values[:, start:stop],
+                       self.advantages[:, start:stop], self.returns[:, start:stop], self.actions_log_prob[:, start:stop],
+                       self.mu[:, start:stop], self.sigma[:, start:stop], (hid_a, hid_c), masks[:, first:last])
+
+
+class _Unpad(torch.autograd.Function):
+    """unpad_trajectories with its gradient: forward scatters the valid rows back to (T, envs, width), backward is the pad gather."""
+
+    @staticmethod
+    def forward(ctx, trajectories, masks):
+        lib = abi.load_lib()
+        dev = trajectories.device
+        if dev.type != "cuda" or trajectories.dtype != torch.float32 or trajectories.dim() < 2:
+            raise ValueError("unpad_trajectories takes a (rows, n_traj, ...) float32 tensor on a HIP device (no CPU fallback)")
+        rows, n_traj = trajectories.shape[:2]
+        if masks.dim() != 2 or masks.shape[1] != n_traj or masks.dtype not in (torch.bool, torch.uint8) or masks.device != dev:
+            raise ValueError(f"masks are (T, {n_traj}) bool on {dev}, got {tuple(masks.shape)} {masks.dtype}")
+        T = masks.shape[0]
+        x, m = trajectories.contiguous(), masks.contiguous()
+        width = x[0, 0].numel()
+        index = torch.empty(3, n_traj, dtype=torch.int32, device=dev)
+        head = torch.empty(2, dtype=torch.int32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        abi.check(lib.lg_rollout_mask_index(T, n_traj, m.data_ptr(), index.data_ptr(), n_traj, head.data_ptr(), stream), lib)
+        steps, longest = head.cpu().tolist()                           # the one read-back: the env count sizes the output
+        if steps % T or longest > rows:
+            raise ValueError(f"masks cover {steps} steps with a longest trajectory of {longest}: not whole envs of {T} steps within {rows} rows")
+        n = steps // T
+        out = torch.empty(T, n, *x.shape[2:], device=dev)              # the trajectories tile (T, n): every element is written
+        abi.check(lib.lg_rollout_unpad(T, n, index.data_ptr(), n_traj, n_traj, rows, x.data_ptr(), out.data_ptr(), width, stream), lib)
+        ctx.index, ctx.dims = index, (T, n, n_traj, rows, width, tuple(x.shape))
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        lib = abi.load_lib()
+        T, n, n_traj, rows, width, shape = ctx.dims
+        g = grad.contiguous()
+        out = torch.empty(shape, device=g.device)
+        arr = (abi.LgRowCopy * 1)()
+        arr[0].src, arr[0].dst, arr[0].width, arr[0].src_stride = g.data_ptr(), out.data_ptr(), width, width
+        stream = torch.cuda.current_stream(g.device).cuda_stream
+        abi.check(lib.lg_rollout_pad(T, n, ctx.index.data_ptr(), n_traj, n_traj, rows, arr, 1, None, None, 0, 0, stream), lib)
+        return out, None
+
+
+def unpad_trajectories(trajectories, masks):
+    """The inverse of split_and_pad_trajectories (rsl_rl/utils/utils.py:67-71, what Memory.forward applies to the RNN's output on every
+    update): trajectories (rows, n_traj, ...) float32, masks (T, n_traj) bool as the recurrent generator yields them -> (T, envs, ...),
+    contiguous, differentiable (the gradient is the pad gather).  The trajectory index is rebuilt from the masks on the device; the env
+    count is read back from it (one small copy; the reference's boolean indexing waits for the device as well) and the masks are checked
+    to cover whole envs."""
+    return _Unpad.apply(trajectories, masks)

@@ -42,6 +42,38 @@ int lg_rollout_record(int32_t n_envs, const float *rew, const uint8_t *reset, co
 int lg_rollout_gae(int32_t n_steps, int32_t n_envs, const float *values, const float *rewards, const uint8_t *dones,
                    const float *last_values, float gamma, float lam, float *returns, float *advantages, double *scratch, void *stream);
 
+/* ---- recurrent policies (rollout_storage.py:187-236, rsl_rl/utils/utils.py:33-71) -------------------------------------------------
+ * A trajectory starts at t = 0 and behind every done, and ends at a done or at t = T-1; trajectories are numbered env-major, then by
+ * time (the reference's transpose(1, 0) flattening).  The trajectory index `traj` is (3, capacity) int32: row 0 the env, row 1 t_start,
+ * row 2 the length of each trajectory. */
+
+/* dones (T, N, 1) uint8 -> traj_offset[N + 1] (first trajectory of every env; [N] = n_traj), traj (entries at or beyond capacity are
+ * not written), header = (n_traj, longest length).  capacity >= N; T * N always suffices.  One workgroup, no atomics: the numbering
+ * is the same on every call. */
+int lg_rollout_traj_index(int32_t n_steps, int32_t n_envs, const uint8_t *dones, int32_t *traj_offset, int32_t *traj, int32_t capacity,
+                          int32_t *header, void *stream);
+
+/* The same index from a trajectory mask (T, n_traj) uint8 / bool alone: the trajectories of one env fill its T steps in order, so the
+ * running sum of the lengths is env * T + t_start.  header = (steps covered = T * envs, longest length; INT32_MAX if a trajectory would
+ * run past its env's last step, which no mask of a rollout does). */
+int lg_rollout_mask_index(int32_t n_steps, int32_t n_traj, const uint8_t *masks, int32_t *traj, int32_t capacity, int32_t *header,
+                          void *stream);
+
+/* One launch, every destination element written exactly once (no memset needed):
+ *   sources[i]: src (T, N, width) with src_stride floats between envs (rows of T are N * src_stride apart), dst (rows, n_traj, width):
+ *               dst[t', j, :] = src[t_start_j + t', env_j, :] if t' < length_j else 0         (rows = the longest length, <= T)
+ *   hidden[i]:  src (T, hidden_layers[i], N, width) contiguous, dst (hidden_layers[i], n_traj, width): dst[l, j, :] = src[t_start_j, l, env_j, :]
+ *   masks:      (T, n_traj) uint8, masks[t, j] = t < length_j; may be NULL
+ * float4 moves where width, stride and the pointers allow, scalar otherwise.  Each destination must stay below 2^31 elements. */
+int lg_rollout_pad(int32_t n_steps, int32_t n_envs, const int32_t *traj, int32_t capacity, int32_t n_traj, int32_t rows,
+                   const LgRowCopy *sources, int32_t n_sources, const LgRowCopy *hidden, const int32_t *hidden_layers, int32_t n_hidden,
+                   uint8_t *masks, void *stream);
+
+/* The inverse of one source of lg_rollout_pad: dst[t_start_j + t', env_j, :] = padded[t', j, :] for t' < length_j; padded (rows, n_traj,
+ * width), dst (T, N, width), both contiguous.  With an index that tiles the (T, N) grid every element of dst is written exactly once. */
+int lg_rollout_unpad(int32_t n_steps, int32_t n_envs, const int32_t *traj, int32_t capacity, int32_t n_traj, int32_t rows,
+                     const float *padded, float *dst, int32_t width, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
