@@ -1,8 +1,10 @@
 """Generates golden vectors for the MDP part of the hot path by RUNNING THE REFERENCE'S OWN
 env classes (legged_gym/envs/...) on CPU against a fake simulator that feeds scripted physics
-read-backs.  Output: tests/golden/<task>_mdp.npz (inputs + expected outputs per step).
+read-backs.  Output: tests/golden/<task>_mdp.npz (inputs + expected outputs per step), one per task of mdp_harness.TASKS.
 
-Run in the build container only:   PYTHONDONTWRITEBYTECODE=1 python tests/golden/gen_mdp_fixtures.py
+Needs the reference checkout:   PYTHONDONTWRITEBYTECODE=1 python tests/golden/gen_mdp_fixtures.py [task ...]      (default: all)
+generate(name) is the one generator; GEN holds what differs between the tasks and READ where every recorded array comes from.
+tests/golden/check_fixtures.py checks that this and the other generators still reproduce the committed files byte for byte.
 
 What is pinned: everything LeggedRobot.step does around the physics -- action clip/history
 (legged_robot.py:230-239), command resampling + heading command + push schedule (:300-334),
@@ -12,8 +14,12 @@ and observation layout/noise/clip (go2.py:17-134, legged_robot.py:48-49).
 Uniform draws of the reference are intercepted (DrawRecorder) and stored per env in the slot
 layout of include/lgsim.h's LgRandSlots, so the kernel can be fed the very same numbers.
 """
+import contextlib
+import dataclasses
+import importlib
 import os
 import sys
+import types
 
 import numpy as np
 
@@ -28,6 +34,7 @@ import torch  # noqa: E402
 
 from hcr_genesis_lr_cl_amd import builders  # noqa: E402
 from hcr_genesis_lr_cl_amd.model_compiler import load_model  # noqa: E402
+from tests.mdp_harness import TASKS, TASK_STATE, recorded_task_state  # noqa: E402
 
 torch.set_num_threads(2)
 
@@ -235,8 +242,8 @@ def make_script(rng, model, cfg, N, T):
     q0 = np.array([cfg.init_state.default_joint_angles[n] for n in cfg.asset.dof_names], np.float32)
     s = {}
     s["base_pos"] = (rng.normal(size=(T, N, 3)) * [2, 2, 0.03] + [0, 0, 0.32]).astype(np.float32)
-    tilt = np.where(rng.random((T, N)) < 0.08, 1.2, 0.15)
-    s["base_quat"] = np.stack([rand_quat(rng, N, tilt[t][:, None] * np.ones((N, 1)))[:, :] if False else rand_quat(rng, N, 0.15) for t in range(T)])
+    rng.random((T, N))           # unused, but part of the stream every fixture was drawn from
+    s["base_quat"] = np.stack([rand_quat(rng, N, 0.15) for t in range(T)])
     big = rng.random((T, N)) < 0.08
     for t in range(T):
         if big[t].any():
@@ -316,427 +323,40 @@ def slots_from_calls(calls, slots, N, A, policy_dof_groups):
     return R
 
 
-def gen_go2(N=24, T=64, seed=7):
-    import legged_gym.envs.base.base_task as base_task
-    import legged_gym.envs.base.legged_robot as lr_mod
-    import legged_gym.envs.go2.go2 as go2_mod
-    from legged_gym.envs.go2.go2_config import GO2Cfg
-    from legged_gym.utils.helpers import class_to_dict
-    from hcr_genesis_lr_cl_amd.config import GO2Cfg as MyCfg
-
-    rec = rh.DrawRecorder(seed)
-    base_task.GenesisSimulator = FakeSimulator
-    lr_mod.torch_rand_float = rec.rand_float
-    go2_mod.torch_rand_float = rec.rand_float
-    orig_rand_like = torch.rand_like
-    torch.rand_like = rec.rand_like
-    try:
-        cfg = GO2Cfg()
-        cfg.env.num_envs = N
-        env = go2_mod.GO2(cfg, class_to_dict(cfg.sim), "cpu", True)
-        sim = env.simulator
-        sim.rec = rec
-        rng = np.random.default_rng(seed + 1)
-        model = sim.model
-        sim.script = make_script(rng, model, cfg, N, T)
-        mycfg = MyCfg()
-        task = builders.make_task_cfg(model, mycfg)
-        slots = task.slots
-        groups = [[0, 3, 6, 9], [1, 4, 7, 10], [2, 5, 8, 11]]      # go2.py:30-35
-        # initial MDP state: as after construction, with episode clocks spread so that resampling
-        # (ep_len % 500 == 0) and time-outs (ep_len > 1000) occur inside the window
-        env.episode_length_buf[:] = torch.from_numpy(rng.choice(
-            [3, 120, 470, 480, 495, 498, 499, 960, 985, 995, 998, 999, 1000], N).astype(np.int32))
-        env.commands[:] = torch.from_numpy((rng.normal(size=(N, 4)) * [0.4, 0.4, 0.5, 1.5]).astype(np.float32))
-        env.common_step_counter = 745                                   # push at 750
-        env.reset_buf[:] = 0
-        rec.take()
-        init = dict(episode_length_buf=env.episode_length_buf.numpy().copy(), commands=env.commands.numpy().copy(),
-                    env_origins=sim._env_origins.numpy().copy(), default_dof_pos=sim._default_dof_pos.numpy().copy())
-        out = {k: [] for k in ("actions_in", "rand", "counter", "obs", "rew", "reset", "time_out", "commands", "ep_len",
-                               "fail_buf", "feet_air_time", "last_contacts", "episode_sums", "act_hist", "sim_dof_pos",
-                               "sim_dof_vel", "sim_base_pos", "sim_base_quat", "sim_base_lin_vel_w", "sim_projected_gravity",
-                               "sim_base_lin_vel", "dr", "cmd_range_x", "last_dof_vel_in", "last_feet_vel_in", "esum_override")}
-        names = env.reward_names
-        for t in range(T):
-            override = 0.0
-            if t == 30:
-                env.common_step_counter = 995                            # command curriculum gate at 1000
-            if env.common_step_counter + 1 == 1000:
-                override = 18.5                                          # > 0.8 * scale * max_len = 16
-                env.episode_sums["tracking_lin_vel"][:] = override
-                # make sure somebody resets at this step
-                env.episode_length_buf[:4] = 1000
-            act = torch.from_numpy((rng.normal(size=(N, 12)) * (1.0 if t % 7 else 60.0)).astype(np.float32))
-            # what the kernel is given as "last" values for this step
-            out["last_dof_vel_in"].append(sim._dof_vel.numpy().copy())
-            out["last_feet_vel_in"].append(sim._feet_vel.numpy().copy())
-            obs, priv, rew, reset, extras = env.step(act)
-            calls = rec.take()
-            out["actions_in"].append(act.numpy().copy())
-            out["rand"].append(slots_from_calls(calls, slots, N, 12, groups))
-            out["counter"].append(env.common_step_counter)
-            out["esum_override"].append(override)
-            out["obs"].append(obs.numpy().copy()); out["rew"].append(rew.numpy().copy())
-            out["reset"].append(reset.numpy().astype(np.uint8)); out["time_out"].append(env.time_out_buf.numpy().astype(np.uint8))
-            out["commands"].append(env.commands.numpy().copy()); out["ep_len"].append(env.episode_length_buf.numpy().copy())
-            out["fail_buf"].append(env.fail_buf.numpy().copy()); out["feet_air_time"].append(env.feet_air_time.numpy().copy())
-            out["last_contacts"].append(env.last_contacts.numpy().astype(np.uint8))
-            out["episode_sums"].append(np.stack([env.episode_sums[n].numpy().copy() for n in names]))
-            out["act_hist"].append(np.stack([env.actions.numpy(), env.last_actions.numpy(), env.llast_actions.numpy()]).copy())
-            out["sim_dof_pos"].append(sim._dof_pos.numpy().copy()); out["sim_dof_vel"].append(sim._dof_vel.numpy().copy())
-            out["sim_base_pos"].append(sim._base_pos.numpy().copy()); out["sim_base_quat"].append(sim._base_quat.numpy().copy())
-            out["sim_base_lin_vel_w"].append(sim._base_lin_vel_w.numpy().copy())
-            out["sim_projected_gravity"].append(sim._projected_gravity.numpy().copy())
-            out["sim_base_lin_vel"].append(sim._base_lin_vel.numpy().copy())
-            out["dr"].append(np.concatenate([sim._friction_values.numpy(), sim._added_base_mass.numpy(), sim._base_com_bias.numpy(),
-                                             sim._rand_push_vels.numpy()[:, :2]], 1).copy())
-            out["cmd_range_x"].append(np.array(env.command_ranges["lin_vel_x"], np.float32))
-        arrays = {k: np.stack(v) for k, v in out.items()}
-        arrays.update({"script_" + k: v for k, v in sim.script.items()})
-        arrays.update({"init_" + k: v for k, v in init.items()})
-        arrays["reward_names"] = np.array(names)
-        path = os.path.join(HERE, "go2_mdp.npz")
-        np.savez_compressed(path, **arrays)
-        print("wrote", path, {k: v.shape for k, v in arrays.items() if k in ("obs", "rand", "episode_sums")},
-              "resets/step", arrays["reset"].sum(1)[:40], "cmd_range_x", arrays["cmd_range_x"][-1])
-    finally:
-        torch.rand_like = orig_rand_like
+# ------------------------------------------------------------------------------------------------------------------------------
+# What differs between the tasks.  mdp_harness.TASKS[name] already states the config class and reward scales, rough / gait / cstr /
+# stacks and the frame widths; a Gen adds what only the generator needs.  Hooks that draw from `rng` are called at fixed points of
+# generate(): make_script, place, episode clocks, commands, gait state, then one action draw per step.
+def _onto_tiles(script, sim, rng):
+    """Base xy around each env's origin, some far enough to be promoted (> 4 m); returns the origins."""
+    org = sim._env_origins.numpy()
+    T, N = script["base_pos"].shape[:2]
+    off = rng.normal(size=(T, N, 2)) * 1.5 + np.where(rng.random((T, N, 1)) < 0.3, 4.5, 0.0)
+    script["base_pos"][:, :, :2] = (org[None, :, :2] + off).astype(np.float32)
+    return org
 
 
-def gen_wtw(N=24, T=64, seed=11):
-    """GO2WTW (go2_wtw.py): periodic-gait rewards, behaviour parameters, 5-frame histories.
-    The command-curriculum gate step is NOT crossed: the reference calls a method that does not
-    exist there (`self.update_command_curriculum`, go2_wtw.py:121) and would raise."""
-    import legged_gym.envs.base.base_task as base_task
-    import legged_gym.envs.base.legged_robot as lr_mod
-    import legged_gym.envs.go2.go2_wtw.go2_wtw as wtw_mod
-    from legged_gym.envs.go2.go2_wtw.go2_wtw_config import GO2WTWCfg
-    from legged_gym.utils.helpers import class_to_dict
-    from hcr_genesis_lr_cl_amd.config import GO2WTWCfg as MyCfg
-
-    rec = rh.DrawRecorder(seed)
-    base_task.GenesisSimulator = FakeSimulator
-    lr_mod.torch_rand_float = rec.rand_float
-    wtw_mod.torch_rand_float = rec.rand_float
-    orig_rand_like, orig_randint = torch.rand_like, torch.randint
-    torch.rand_like, torch.randint = rec.rand_like, rec.randint
-    try:
-        cfg = GO2WTWCfg()
-        cfg.env.num_envs = N
-        env = wtw_mod.GO2WTW(cfg, class_to_dict(cfg.sim), "cpu", True)
-        sim = env.simulator
-        sim.rec = rec
-        rng = np.random.default_rng(seed + 1)
-        model = sim.model
-        sim.script = make_script(rng, model, cfg, N, T)
-        task = builders.make_task_cfg(model, MyCfg())
-        slots = task.slots
-        groups = [list(range(12))]                                        # legged_robot.py:279-280: one (n,12) draw
-        env.episode_length_buf[:] = torch.from_numpy(rng.choice(
-            [3, 120, 245, 248, 249, 395, 398, 399, 498, 499, 748, 960, 985, 995, 998, 999, 1000], N).astype(np.int32))
-        env.commands[:] = torch.from_numpy((rng.normal(size=(N, 4)) * [0.4, 0.4, 0.5, 1.5]).astype(np.float32))
-        env.common_step_counter = 745
-        env.reset_buf[:] = 0
-        # widen the behaviour ranges / gait set as the curriculum would, so every table entry is exercised
-        env.num_gaits = 4
-        env.gait_period_range = [0.3, 0.6]
-        env.base_height_target_range = [0.2, 0.34]
-        env.foot_clearance_target_range = [0.04, 0.12]
-        env.pitch_target_range = [-0.3, 0.3]
-        env.theta[:] = torch.from_numpy(rng.choice([0.0, 0.5], (N, 4)).astype(np.float32))
-        env.gait_period[:] = torch.from_numpy(rng.uniform(0.3, 0.6, (N, 1)).astype(np.float32))
-        env.gait_time[:] = torch.from_numpy(rng.uniform(0.0, 0.3, (N, 1)).astype(np.float32))
-        env.phi[:] = env.gait_time / env.gait_period
-        rec.take()
-        init = dict(episode_length_buf=env.episode_length_buf.numpy().copy(), commands=env.commands.numpy().copy(),
-                    env_origins=sim._env_origins.numpy().copy(), theta=env.theta.numpy().copy(),
-                    gait_period=env.gait_period.numpy().copy(), gait_time=env.gait_time.numpy().copy(), phi=env.phi.numpy().copy(),
-                    behavior_ranges=np.array(env.gait_period_range + env.base_height_target_range +
-                                             env.foot_clearance_target_range + env.pitch_target_range + [env.num_gaits], np.float32))
-        keys = ("actions_in", "rand", "counter", "obs", "priv", "rew", "reset", "time_out", "commands", "ep_len", "fail_buf",
-                "episode_sums", "act_hist", "sim_dof_pos", "sim_base_pos", "sim_base_lin_vel_w", "dr_pd", "task_state",
-                "last_dof_vel_in", "last_feet_vel_in", "esum_override")
-        out = {k: [] for k in keys}
-        names = env.reward_names
-        for t in range(T):
-            act = torch.from_numpy((rng.normal(size=(N, 12)) * (1.0 if t % 7 else 60.0)).astype(np.float32))
-            out["last_dof_vel_in"].append(sim._dof_vel.numpy().copy())
-            out["last_feet_vel_in"].append(sim._feet_vel.numpy().copy())
-            obs, priv, rew, reset, extras = env.step(act)
-            calls = rec.take()
-            out["actions_in"].append(act.numpy().copy())
-            out["rand"].append(slots_from_calls(calls, slots, N, 12, groups))
-            out["counter"].append(env.common_step_counter); out["esum_override"].append(0.0)
-            out["obs"].append(obs.numpy().copy()); out["priv"].append(priv.numpy().copy()); out["rew"].append(rew.numpy().copy())
-            out["reset"].append(reset.numpy().astype(np.uint8)); out["time_out"].append(env.time_out_buf.numpy().astype(np.uint8))
-            out["commands"].append(env.commands.numpy().copy()); out["ep_len"].append(env.episode_length_buf.numpy().copy())
-            out["fail_buf"].append(env.fail_buf.numpy().copy())
-            out["episode_sums"].append(np.stack([env.episode_sums[n].numpy().copy() for n in names]))
-            out["act_hist"].append(np.stack([env.actions.numpy(), env.last_actions.numpy(), env.llast_actions.numpy()]).copy())
-            out["sim_dof_pos"].append(sim._dof_pos.numpy().copy()); out["sim_base_pos"].append(sim._base_pos.numpy().copy())
-            out["sim_base_lin_vel_w"].append(sim._base_lin_vel_w.numpy().copy())
-            out["dr_pd"].append(np.concatenate([sim._kp_scale.numpy(), sim._kd_scale.numpy()], 1).copy())
-            out["task_state"].append(np.concatenate([env.gait_time.numpy(), env.phi.numpy(), env.gait_period.numpy(),
-                                                     env.base_height_target.numpy(), env.foot_clearance_target.numpy(),
-                                                     env.pitch_target.numpy(), env.theta.numpy(), env.clock_input.numpy(),
-                                                     env.exp_C_frc_fl.numpy(), env.exp_C_frc_fr.numpy(), env.exp_C_frc_rl.numpy(),
-                                                     env.exp_C_frc_rr.numpy()], 1).copy())
-        arrays = {k: np.stack(v) for k, v in out.items()}
-        arrays.update({"script_" + k: v for k, v in sim.script.items()})
-        arrays.update({"init_" + k: v for k, v in init.items()})
-        arrays["reward_names"] = np.array(names)
-        path = os.path.join(HERE, "go2_wtw_mdp.npz")
-        np.savez_compressed(path, **arrays)
-        print("wrote", path, arrays["obs"].shape, arrays["priv"].shape, "resets/step", arrays["reset"].sum(1)[:40])
-    finally:
-        torch.rand_like, torch.randint = orig_rand_like, orig_randint
+def _biped_feet(script):
+    script["feet_pos"][:, :, :, :2] = script["feet_pos"][:, :, :, :2] * 0.4 + script["base_pos"][:, :, None, :2]
 
 
-def gen_ee(N=24, T=48, seed=21):
-    """Go2EE (go2_ee.py, legged_robot_ee.py): heightfield terrain, terrain curriculum, estimator features /
-    labels / critic stacks.  Only the newest frame of each stack is stored per step (plus the full
-    stacks at the last step) to keep the fixture small; the stacking itself is checked on those."""
-    import legged_gym.envs.base.base_task as base_task
-    import legged_gym.envs.base.legged_robot as lr_mod
-    import legged_gym.envs.go2.go2_ee.go2_ee as ee_mod
-    from legged_gym.envs.go2.go2_ee.go2_ee_config import Go2EECfg
-    from legged_gym.utils.helpers import class_to_dict
-    from hcr_genesis_lr_cl_amd.config import GO2EECfg as MyCfg
-
-    rec = rh.DrawRecorder(seed)
-    base_task.GenesisSimulator = RoughFakeSimulator
-    lr_mod.torch_rand_float = rec.rand_float
-    ee_mod.torch_rand_float = rec.rand_float
-    orig_rand_like = torch.rand_like
-    torch.rand_like = rec.rand_like
-    try:
-        cfg = Go2EECfg()
-        cfg.env.num_envs = N
-        env = ee_mod.Go2EE(cfg, class_to_dict(cfg.sim), "cpu", True)
-        sim = env.simulator
-        sim.rec = rec
-        rng = np.random.default_rng(seed + 1)
-        model = sim.model
-        script = make_script(rng, model, cfg, N, T)
-        # place the robots on their tiles: around the env origin, some far enough to be promoted (> 4 m)
-        org = sim._env_origins.numpy()
-        off = rng.normal(size=(T, N, 2)) * 1.5 + np.where(rng.random((T, N, 1)) < 0.3, 4.5, 0.0)
-        script["base_pos"][:, :, :2] = (org[None, :, :2] + off).astype(np.float32)
-        script["base_pos"][:, :, 2] += org[None, :, 2]
-        script["feet_pos"][:, :, :, :2] += script["base_pos"][:, :, None, :2]
-        script["feet_pos"][:, :, :, 2] += org[None, :, None, 2]
-        sim.script = script
-        task = builders.make_task_cfg(model, MyCfg())
-        slots = task.slots
-        groups = [[0, 3, 6, 9], [1, 4, 7, 10], [2, 5, 8, 11]]
-        env.episode_length_buf[:] = torch.from_numpy(rng.choice([3, 120, 470, 495, 498, 499, 960, 985, 995, 998, 999, 1000], N).astype(np.int32))
-        env.commands[:] = torch.from_numpy((rng.normal(size=(N, 4)) * [0.4, 0.4, 0.5, 1.5]).astype(np.float32))
-        env.common_step_counter = 495                                   # push interval 10 s = 500 steps
-        env.reset_buf[:] = 0
-        rec.take()
-        init = dict(episode_length_buf=env.episode_length_buf.numpy().copy(), commands=env.commands.numpy().copy(),
-                    env_origins=sim._env_origins.numpy().copy(), terrain_levels=sim._terrain_levels.numpy().copy(),
-                    terrain_types=sim._terrain_types.numpy().copy(), height_points=sim._height_points[0, :, :2].numpy().copy())
-        keys = ("actions_in", "rand", "counter", "feat_new", "priv_new", "labels", "rew", "reset", "time_out", "commands", "ep_len",
-                "fail_buf", "feet_air_time", "episode_sums", "sim_dof_pos", "sim_base_pos", "terrain_levels", "env_origins",
-                "measured_heights", "height_around_feet", "normals", "contact_states", "last_dof_vel_in", "last_feet_vel_in", "esum_override")
-        out = {k: [] for k in keys}
-        names = env.reward_names
-        for t in range(T):
-            act = torch.from_numpy((rng.normal(size=(N, 12)) * (1.0 if t % 7 else 60.0)).astype(np.float32))
-            out["last_dof_vel_in"].append(sim._dof_vel.numpy().copy()); out["last_feet_vel_in"].append(sim._feet_vel.numpy().copy())
-            feat, labels, priv, rew, reset, extras = env.step(act)
-            calls = rec.take()
-            out["actions_in"].append(act.numpy().copy()); out["rand"].append(slots_from_calls(calls, slots, N, 12, groups))
-            out["counter"].append(env.common_step_counter); out["esum_override"].append(0.0)
-            out["feat_new"].append(feat.numpy()[:, -45:].copy()); out["priv_new"].append(priv.numpy()[:, -174:].copy())
-            out["labels"].append(labels.numpy().copy()); out["rew"].append(rew.numpy().copy())
-            out["reset"].append(reset.numpy().astype(np.uint8)); out["time_out"].append(env.time_out_buf.numpy().astype(np.uint8))
-            out["commands"].append(env.commands.numpy().copy()); out["ep_len"].append(env.episode_length_buf.numpy().copy())
-            out["fail_buf"].append(env.fail_buf.numpy().copy()); out["feet_air_time"].append(env.feet_air_time.numpy().copy())
-            out["episode_sums"].append(np.stack([env.episode_sums[n].numpy().copy() for n in names]))
-            out["sim_dof_pos"].append(sim._dof_pos.numpy().copy()); out["sim_base_pos"].append(sim._base_pos.numpy().copy())
-            out["terrain_levels"].append(sim._terrain_levels.numpy().copy()); out["env_origins"].append(sim._env_origins.numpy().copy())
-            out["measured_heights"].append(sim._measured_heights.numpy().copy())
-            out["height_around_feet"].append(sim._height_around_feet.numpy().copy())
-            out["normals"].append(sim._normal_vector_around_feet.numpy().copy())
-            out["contact_states"].append(sim._link_contact_states.numpy().copy())
-        arrays = {k: np.stack(v) for k, v in out.items()}
-        arrays["feat_last"], arrays["priv_last"] = feat.numpy().copy(), priv.numpy().copy()
-        arrays.update({"script_" + k: v for k, v in sim.script.items()})
-        arrays.update({"init_" + k: v for k, v in init.items()})
-        arrays["reward_names"] = np.array(names)
-        arrays["terrain_seed"] = RoughFakeSimulator.TERRAIN_SEED
-        path = os.path.join(HERE, "go2_ee_mdp.npz")
-        np.savez_compressed(path, **arrays)
-        print("wrote", path, os.path.getsize(path), "resets/step", arrays["reset"].sum(1), "levels moved",
-              int((arrays["terrain_levels"][-1] != init["terrain_levels"]).sum()))
-    finally:
-        torch.rand_like = orig_rand_like
+def place_go2_rough(script, sim, rng):
+    org = _onto_tiles(script, sim, rng)
+    script["base_pos"][:, :, 2] += org[None, :, 2]
+    script["feet_pos"][:, :, :, :2] += script["base_pos"][:, :, None, :2]
+    script["feet_pos"][:, :, :, 2] += org[None, :, None, 2]
 
 
-def gen_tron1(N=24, T=48, seed=31):
-    """TRON1PF_EE (tron1_pf_ee.py): 6-DOF biped, heightfield + curriculum, biped periodic gait, sit-pose resets,
-    all domain randomisation incl. joint armature / friction / damping.  The command-curriculum gate step is not
-    crossed (the reference calls the non-existent `update_command_curriculum`, tron1_pf_ee.py:201)."""
-    import legged_gym.envs.base.base_task as base_task
-    import legged_gym.envs.base.legged_robot as lr_mod
-    import legged_gym.envs.tron1_pf.tron1_pf_ee.tron1_pf_ee as tr_mod
-    from legged_gym.envs.tron1_pf.tron1_pf_ee.tron1_pf_ee_config import TRON1PF_EECfg
-    from legged_gym.utils.helpers import class_to_dict
-    from hcr_genesis_lr_cl_amd.config import TRON1PFEECfg as MyCfg
-
-    rec = rh.DrawRecorder(seed)
-    base_task.GenesisSimulator = RoughFakeSimulator
-    lr_mod.torch_rand_float = rec.rand_float
-    tr_mod.torch_rand_float = rec.rand_float
-    orig = (torch.rand_like, torch.rand, np.random.random)
-    torch.rand_like, torch.rand, np.random.random = rec.rand_like, rec.torch_rand, rec.np_random
-    try:
-        cfg = TRON1PF_EECfg()
-        cfg.env.num_envs = N
-        torch.rand = orig[1]                      # construction uses torch.rand-free paths; keep the original until stepping
-        env = tr_mod.TRON1PF_EE(cfg, class_to_dict(cfg.sim), "cpu", True)
-        torch.rand = rec.torch_rand
-        sim = env.simulator
-        sim.rec = rec
-        rng = np.random.default_rng(seed + 1)
-        model = sim.model
-        script = make_script(rng, model, cfg, N, T)
-        org = sim._env_origins.numpy()
-        off = rng.normal(size=(T, N, 2)) * 1.5 + np.where(rng.random((T, N, 1)) < 0.3, 4.5, 0.0)
-        script["base_pos"][:, :, :2] = (org[None, :, :2] + off).astype(np.float32)
-        script["base_pos"][:, :, 2] += org[None, :, 2] + 0.4
-        script["feet_pos"][:, :, :, :2] = script["feet_pos"][:, :, :, :2] * 0.4 + script["base_pos"][:, :, None, :2]
-        script["feet_pos"][:, :, :, 2] += org[None, :, None, 2]
-        sim.script = script
-        task = builders.make_task_cfg(model, MyCfg())
-        slots = task.slots
-        groups = [[0, 3], [1, 4], [2, 5]]                                # tron1_pf_ee.py:268-273
-        env.episode_length_buf[:] = torch.from_numpy(rng.choice([3, 120, 470, 495, 498, 499, 960, 985, 995, 998, 999, 1000], N).astype(np.int32))
-        env.commands[:] = torch.from_numpy((rng.normal(size=(N, 4)) * [0.4, 0.4, 0.5, 1.5]).astype(np.float32))
-        env.common_step_counter = 495
-        env.reset_buf[:] = 0
-        env.theta[:, 0] = torch.from_numpy(rng.uniform(0, 1, N).astype(np.float32)); env.theta[:, 1] = env.theta[:, 0] + 0.5
-        env.gait_time[:] = torch.from_numpy(rng.uniform(0.0, 0.45, (N, 1)).astype(np.float32))
-        env.phi[:] = env.gait_time / env.gait_period
-        rec.take()
-        init = dict(episode_length_buf=env.episode_length_buf.numpy().copy(), commands=env.commands.numpy().copy(),
-                    env_origins=sim._env_origins.numpy().copy(), terrain_levels=sim._terrain_levels.numpy().copy(),
-                    terrain_types=sim._terrain_types.numpy().copy(), height_points=sim._height_points[0, :, :2].numpy().copy(),
-                    theta=env.theta.numpy().copy(), gait_time=env.gait_time.numpy().copy(), phi=env.phi.numpy().copy())
-        keys = ("actions_in", "rand", "counter", "feat_new", "priv_new", "labels", "rew", "reset", "time_out", "commands", "ep_len",
-                "fail_buf", "episode_sums", "act_hist", "sim_dof_pos", "sim_base_pos", "sim_base_quat", "terrain_levels", "env_origins",
-                "measured_heights", "height_around_feet", "normals", "dr_joint", "task_state", "last_dof_vel_in", "last_feet_vel_in", "esum_override")
-        out = {k: [] for k in keys}
-        names = env.reward_names
-        for t in range(T):
-            act = torch.from_numpy((rng.normal(size=(N, 6)) * (1.0 if t % 7 else 30.0)).astype(np.float32))
-            out["last_dof_vel_in"].append(sim._dof_vel.numpy().copy()); out["last_feet_vel_in"].append(sim._feet_vel.numpy().copy())
-            feat, labels, priv, rew, reset, extras = env.step(act)
-            calls = rec.take()
-            out["actions_in"].append(act.numpy().copy()); out["rand"].append(slots_from_calls(calls, slots, N, 6, groups))
-            out["counter"].append(env.common_step_counter); out["esum_override"].append(0.0)
-            out["feat_new"].append(feat.numpy()[:, -31:].copy()); out["priv_new"].append(priv.numpy()[:, -134:].copy())
-            out["labels"].append(labels.numpy().copy()); out["rew"].append(rew.numpy().copy())
-            out["reset"].append(reset.numpy().astype(np.uint8)); out["time_out"].append(env.time_out_buf.numpy().astype(np.uint8))
-            out["commands"].append(env.commands.numpy().copy()); out["ep_len"].append(env.episode_length_buf.numpy().copy())
-            out["fail_buf"].append(env.fail_buf.numpy().copy())
-            out["episode_sums"].append(np.stack([env.episode_sums[n].numpy().copy() for n in names]))
-            out["act_hist"].append(np.stack([env.actions.numpy(), env.last_actions.numpy(), env.llast_actions.numpy()]).copy())
-            out["sim_dof_pos"].append(sim._dof_pos.numpy().copy()); out["sim_base_pos"].append(sim._base_pos.numpy().copy())
-            out["sim_base_quat"].append(sim._base_quat.numpy().copy())
-            out["terrain_levels"].append(sim._terrain_levels.numpy().copy()); out["env_origins"].append(sim._env_origins.numpy().copy())
-            out["measured_heights"].append(sim._measured_heights.numpy().copy())
-            out["height_around_feet"].append(sim._height_around_feet.numpy().copy())
-            out["normals"].append(sim._normal_vector_around_feet.numpy().copy())
-            out["dr_joint"].append(np.concatenate([sim._joint_armature.numpy(), sim._joint_friction.numpy(), sim._joint_damping.numpy()], 1).copy())
-            out["task_state"].append(np.concatenate([env.gait_time.numpy(), env.phi.numpy(), env.theta.numpy(), env.clock_input.numpy(),
-                                                     env.exp_C_frc_left.numpy(), env.exp_C_frc_right.numpy()], 1).copy())
-        arrays = {k: np.stack(v) for k, v in out.items()}
-        arrays["feat_last"], arrays["priv_last"] = feat.numpy().copy(), priv.numpy().copy()
-        arrays.update({"script_" + k: v for k, v in sim.script.items()})
-        arrays.update({"init_" + k: v for k, v in init.items()})
-        arrays["reward_names"] = np.array(names)
-        arrays["terrain_seed"] = RoughFakeSimulator.TERRAIN_SEED
-        path = os.path.join(HERE, "tron1_pf_ee_mdp.npz")
-        np.savez_compressed(path, **arrays)
-        sit = (np.abs(arrays["sim_base_quat"][:, :, 1]) > 0.05) & arrays["reset"].astype(bool)
-        print("wrote", path, os.path.getsize(path), "resets/step", arrays["reset"].sum(1), "sit resets", int(sit.sum()),
-              "levels moved", int((arrays["terrain_levels"][-1] != init["terrain_levels"]).sum()))
-    finally:
-        torch.rand_like, torch.rand, np.random.random = orig
+def place_tron1_rough(script, sim, rng):
+    org = _onto_tiles(script, sim, rng)
+    script["base_pos"][:, :, 2] += org[None, :, 2] + 0.4
+    _biped_feet(script)
+    script["feet_pos"][:, :, :, 2] += org[None, :, None, 2]
 
 
-def gen_tron1_pf(N=16, T=40, seed=51):
-    """TRON1PF (tron1_pf.py, experiment "tron1_pf"): the point-foot biped on the plane; base-class resets, 5-frame actor /
-    critic stacks, `no_fly` reward.  Stored like gen_wtw: full stacked obs / privileged obs per step."""
-    import legged_gym.envs.base.base_task as base_task
-    import legged_gym.envs.base.legged_robot as lr_mod
-    import legged_gym.envs.tron1_pf.tron1_pf as pf_mod
-    from legged_gym.envs.tron1_pf.tron1_pf_config import TRON1PFCfg
-    from legged_gym.utils.helpers import class_to_dict
-    from hcr_genesis_lr_cl_amd.config import TRON1PFCfg as MyCfg
-
-    rec = rh.DrawRecorder(seed)
-    base_task.GenesisSimulator = FakeSimulator
-    lr_mod.torch_rand_float = rec.rand_float
-    orig_rand_like = torch.rand_like
-    torch.rand_like = rec.rand_like
-    try:
-        cfg = TRON1PFCfg()
-        cfg.env.num_envs = N
-        env = pf_mod.TRON1PF(cfg, class_to_dict(cfg.sim), "cpu", True)
-        sim = env.simulator
-        sim.rec = rec
-        rng = np.random.default_rng(seed + 1)
-        model = sim.model
-        script = make_script(rng, model, cfg, N, T)
-        script["base_pos"][:, :, 2] += 0.36                       # nominal base height 0.68
-        script["feet_pos"][:, :, :, :2] = script["feet_pos"][:, :, :, :2] * 0.4 + script["base_pos"][:, :, None, :2]
-        sim.script = script
-        task = builders.make_task_cfg(model, MyCfg())
-        slots = task.slots
-        groups = [list(range(6))]                                  # legged_robot.py:279-280: one (n, 6) draw
-        env.episode_length_buf[:] = torch.from_numpy(rng.choice([3, 120, 470, 495, 498, 499, 968, 977, 985, 992, 995, 998, 999, 1000], N).astype(np.int32))
-        env.commands[:] = torch.from_numpy((rng.normal(size=(N, 4)) * [0.4, 0.4, 0.5, 1.5]).astype(np.float32))
-        env.common_step_counter = 495                              # push interval 10 s = 500 steps
-        env.reset_buf[:] = 0
-        rec.take()
-        init = dict(episode_length_buf=env.episode_length_buf.numpy().copy(), commands=env.commands.numpy().copy(),
-                    env_origins=sim._env_origins.numpy().copy())
-        keys = ("actions_in", "rand", "counter", "obs", "priv", "rew", "reset", "time_out", "commands", "ep_len", "fail_buf", "feet_air_time",
-                "episode_sums", "act_hist", "sim_dof_pos", "sim_base_pos", "sim_base_lin_vel_w", "dr", "last_dof_vel_in", "last_feet_vel_in",
-                "esum_override")
-        out = {k: [] for k in keys}
-        names = env.reward_names
-        for t in range(T):
-            act = torch.from_numpy((rng.normal(size=(N, 6)) * (1.0 if t % 7 else 60.0)).astype(np.float32))
-            out["last_dof_vel_in"].append(sim._dof_vel.numpy().copy()); out["last_feet_vel_in"].append(sim._feet_vel.numpy().copy())
-            obs, priv, rew, reset, extras = env.step(act)
-            calls = rec.take()
-            out["actions_in"].append(act.numpy().copy()); out["rand"].append(slots_from_calls(calls, slots, N, 6, groups))
-            out["counter"].append(env.common_step_counter); out["esum_override"].append(0.0)
-            out["obs"].append(obs.numpy().copy()); out["priv"].append(priv.numpy().copy()); out["rew"].append(rew.numpy().copy())
-            out["reset"].append(reset.numpy().astype(np.uint8)); out["time_out"].append(env.time_out_buf.numpy().astype(np.uint8))
-            out["commands"].append(env.commands.numpy().copy()); out["ep_len"].append(env.episode_length_buf.numpy().copy())
-            out["fail_buf"].append(env.fail_buf.numpy().copy()); out["feet_air_time"].append(env.feet_air_time.numpy().copy())
-            out["episode_sums"].append(np.stack([env.episode_sums[n].numpy().copy() for n in names]))
-            out["act_hist"].append(np.stack([env.actions.numpy(), env.last_actions.numpy(), env.llast_actions.numpy()]).copy())
-            out["sim_dof_pos"].append(sim._dof_pos.numpy().copy()); out["sim_base_pos"].append(sim._base_pos.numpy().copy())
-            out["sim_base_lin_vel_w"].append(sim._base_lin_vel_w.numpy().copy())
-            out["dr"].append(np.concatenate([sim._friction_values.numpy(), sim._added_base_mass.numpy(), sim._base_com_bias.numpy(),
-                                             sim._rand_push_vels.numpy()[:, :2]], 1).copy())
-        arrays = {k: np.stack(v) for k, v in out.items()}
-        arrays.update({"script_" + k: v for k, v in sim.script.items()})
-        arrays.update({"init_" + k: v for k, v in init.items()})
-        arrays["reward_names"] = np.array(names)
-        path = os.path.join(HERE, "tron1_pf_mdp.npz")
-        np.savez_compressed(path, **arrays)
-        print("wrote", path, os.path.getsize(path), arrays["obs"].shape, arrays["priv"].shape, "resets/step", arrays["reset"].sum(1), list(names))
-    finally:
-        torch.rand_like = orig_rand_like
+def place_tron1_pf(script, sim, rng):
+    script["base_pos"][:, :, 2] += 0.36                       # nominal base height 0.68
+    _biped_feet(script)
 
 
 def _mat_to_quat(R):
@@ -749,217 +369,326 @@ def _mat_to_quat(R):
     return (q / np.linalg.norm(q, axis=-1, keepdims=True)).astype(np.float32)
 
 
-def gen_tron1_sf(N=16, T=44, seed=61):
-    """TRON1SF (tron1_sf.py, experiment "tron1_sf"): the 8-DOF sole-foot biped on the plane: 10-frame actor / critic stacks, the
-    6-DOF index pairs of its `_reset_dofs`, the batch-wide sit-pose coin, `hip_pos_zero_command` / `foot_flat` rewards (and
-    `keep_ankle_pitch_zero_in_air`, given a scale here so that it is pinned too).  The foot orientation the class reads from
-    rigid_body_states is scripted consistently with the scripted base orientation and joint angles (oracle.mdp_oracle.foot_rotations)."""
-    import legged_gym.envs.base.base_task as base_task
-    import legged_gym.envs.base.legged_robot as lr_mod
-    import legged_gym.envs.tron1_sf.tron1_sf as sf_mod
-    from legged_gym.envs.tron1_sf.tron1_sf_config import TRON1SFCfg
-    from legged_gym.utils.helpers import class_to_dict
-    from hcr_genesis_lr_cl_amd.config import TRON1SFCfg as MyCfg
+def place_tron1_sf(script, sim, rng):
+    """The foot orientation the class reads from rigid_body_states (tron1_sf.py:300) is scripted consistently with the scripted
+    base orientation and joint angles."""
     from oracle.mdp_oracle import foot_rotations
+    script["base_pos"][:, :, 2] += 0.43                       # nominal base height 0.75
+    _biped_feet(script)
+    script["foot_quat"] = np.stack([_mat_to_quat(foot_rotations(sim.model, q, p)) for q, p in zip(script["base_quat"], script["dof_pos"])])
 
-    rec = rh.DrawRecorder(seed)
-    base_task.GenesisSimulator = FakeSimulator
-    lr_mod.torch_rand_float = rec.rand_float
-    sf_mod.torch_rand_float = rec.rand_float
-    orig = (torch.rand_like, np.random.random)
-    torch.rand_like, np.random.random = rec.rand_like, rec.np_random
+
+def gait_wtw(env, rng, N):
+    """Widen the behaviour ranges / gait set as the curriculum would, so every table entry is exercised."""
+    env.num_gaits = 4
+    env.gait_period_range = [0.3, 0.6]
+    env.base_height_target_range = [0.2, 0.34]
+    env.foot_clearance_target_range = [0.04, 0.12]
+    env.pitch_target_range = [-0.3, 0.3]
+    env.theta[:] = torch.from_numpy(rng.choice([0.0, 0.5], (N, 4)).astype(np.float32))
+    env.gait_period[:] = torch.from_numpy(rng.uniform(0.3, 0.6, (N, 1)).astype(np.float32))
+    env.gait_time[:] = torch.from_numpy(rng.uniform(0.0, 0.3, (N, 1)).astype(np.float32))
+    env.phi[:] = env.gait_time / env.gait_period
+
+
+def gait_biped(env, rng, N):
+    env.theta[:, 0] = torch.from_numpy(rng.uniform(0, 1, N).astype(np.float32))
+    env.theta[:, 1] = env.theta[:, 0] + 0.5
+    env.gait_time[:] = torch.from_numpy(rng.uniform(0.0, 0.45, (N, 1)).astype(np.float32))
+    env.phi[:] = env.gait_time / env.gait_period
+
+
+# TaskSpec.gait -> (initial-state hook, the init_* keys it adds, the reference's per-foot exp_C_frc_<foot> attributes)
+GAIT = {"wtw": (gait_wtw, ("theta", "gait_period", "gait_time", "phi"), ("fl", "fr", "rl", "rr")),
+        "biped": (gait_biped, ("theta", "gait_time", "phi"), ("left", "right"))}
+
+
+def go2_gate(env, t):
+    """Cross the command-curriculum gate (counter 1000) soon after step 30, with episode sums above it; returns the value written.  Not
+    done for go2_wtw / tron1_pf_ee: the reference calls a method that does not exist there (`self.update_command_curriculum`,
+    go2_wtw.py:121, tron1_pf_ee.py:201) and would raise."""
+    if t == 30:
+        env.common_step_counter = 995
+    if env.common_step_counter + 1 != 1000:
+        return 0.0
+    env.episode_sums["tracking_lin_vel"][:] = 18.5               # > 0.8 * scale * max_len = 16
+    env.episode_length_buf[:4] = 1000                            # make sure somebody resets at this step
+    return 18.5
+
+
+def cat_limits(sim):
+    """Properties of the Simulator ABC that CaT's constraints read (simulator.py: torque_limits, dof_vel_limits)."""
+    type(sim).torque_limits = property(lambda s_: torch.tensor(s_.model.arrays["effort"], dtype=torch.float))
+    type(sim).dof_vel_limits = property(lambda s_: torch.tensor(s_._cfg.asset.dof_vel_limits, dtype=torch.float).unsqueeze(0))
+
+
+def still_commands(env):
+    env.commands[:3] = 0.0            # standing-still envs (feet_contact_stand_still, CaT's style constraint)
+
+
+def near_zero_commands(env):
+    env.commands[::3, :3] *= 0.05     # hip_pos_zero_command, the air-time gate
+
+
+@dataclasses.dataclass(frozen=True)
+class Gen:
+    module: str                       # the reference's task module; its config class lives in <module>_config
+    cls: str
+    cfg: str
+    N: int
+    T: int
+    seed: int                         # of the recorder's stream; the script, initial state and actions draw from seed + 1
+    returns: tuple                    # names for the tuple env.step() returns: obs / feat = actor side, priv = critic side
+    keys: tuple                       # per-step arrays in the fixture's order (READ)
+    groups: tuple                     # policy dofs of each _reset_dofs draw
+    clocks: tuple                     # episode lengths to start from, so that resampling (commands: ep_len % 500 == 0) and time-outs
+    #                                   (ep_len > 1000) occur inside the window
+    counter: int = 495                # common_step_counter to start from: a push at the next multiple of the push interval
+    patch: tuple = ()                 # PATCHABLE globals the task draws from, besides torch.rand_like
+    patch_late: tuple = ()            # the same, installed only once the env is constructed
+    place: object = None              # (script, sim, rng): put the scripted robots where the task's terrain / height terms expect them
+    commands: object = None           # (env): command tweaks after the common draw
+    big_action: float = 60.0          # action scale on every 7th step (clipping)
+
+
+_LEGS3 = ((0, 3, 6, 9), (1, 4, 7, 10), (2, 5, 8, 11))                    # go2.py:30-35
+_PLANE = ("obs", "priv", "rew", "reset", "extras")
+_EE = ("feat", "labels", "priv", "rew", "reset", "extras")
+_CLOCKS = (3, 120, 470, 495, 498, 499, 960, 985, 995, 998, 999, 1000)
+_BIPED_CLOCKS = (3, 120, 470, 495, 498, 499, 968, 977, 985, 992, 995, 998, 999, 1000)
+_TAIL = ("last_dof_vel_in", "last_feet_vel_in", "esum_override")
+_ROUGH_KEYS = ("terrain_levels", "env_origins", "measured_heights", "height_around_feet", "normals")
+_BIPED_KEYS = ("actions_in", "rand", "counter", "obs", "priv", "rew", "reset", "time_out", "commands", "ep_len", "fail_buf", "feet_air_time",
+               "episode_sums", "act_hist", "sim_dof_pos", "sim_base_pos")
+
+
+def _head(name, cls, returns=("obs", "labels", "feat", "priv", "rew", "reset", "extras")):
+    """go2_ts / go2_cts / go2_dreamwaq / go2_cat (legged_gym/envs/__init__.py:82-86) AS CONFIGURED, recorded like go2_ee plus the
+    clipped actor frame; `labels` is the single-frame auxiliary output (TS / CTS / CaT: privileged encoder input; Dreamwaq: explicit
+    labels | next state).  As configured the asset selects 17 contact-state links while the size fields assume 12
+    (go2_ts_config.py:8-14): what the class EMITS is pinned."""
+    return Gen(f"legged_gym.envs.go2.{name}.{name}", cls, cls + "Cfg", 16, 36, 41, returns,
+               ("actions_in", "rand", "counter", "obs", "feat_new", "priv_new", "labels", "rew", "reset", "time_out", "commands", "ep_len",
+                "fail_buf", "feet_air_time", "episode_sums", "sim_dof_pos", "sim_base_pos") + _ROUGH_KEYS + ("contact_states",) + _TAIL
+               + ("cstr_prob", "cstr_sums"),
+               _LEGS3, (3, 470, 495, 498, 499, 968, 972, 977, 981, 985, 989, 992, 995, 998, 999, 1000),
+               place=place_go2_rough, commands=still_commands)
+
+
+# Rough tasks store only the newest frame of each stack per step (feat_new / priv_new) plus the full stacks at the last step
+# (feat_last / priv_last) to keep the fixtures small; the stacking itself is checked on those.
+GEN = {
+    "go2": Gen("legged_gym.envs.go2.go2", "GO2", "GO2Cfg", 24, 64, 7, _PLANE,
+               ("actions_in", "rand", "counter", "obs", "rew", "reset", "time_out", "commands", "ep_len", "fail_buf", "feet_air_time",
+                "last_contacts", "episode_sums", "act_hist", "sim_dof_pos", "sim_dof_vel", "sim_base_pos", "sim_base_quat",
+                "sim_base_lin_vel_w", "sim_projected_gravity", "sim_base_lin_vel", "dr", "cmd_range_x") + _TAIL,
+               _LEGS3, (3, 120, 470, 480, 495, 498, 499, 960, 985, 995, 998, 999, 1000), counter=745),
+    # periodic-gait rewards, behaviour parameters, 5-frame histories
+    "go2_wtw": Gen("legged_gym.envs.go2.go2_wtw.go2_wtw", "GO2WTW", "GO2WTWCfg", 24, 64, 11, _PLANE,
+                   ("actions_in", "rand", "counter", "obs", "priv", "rew", "reset", "time_out", "commands", "ep_len", "fail_buf",
+                    "episode_sums", "act_hist", "sim_dof_pos", "sim_base_pos", "sim_base_lin_vel_w", "dr_pd", "task_state") + _TAIL,
+                   (tuple(range(12)),),                                   # legged_robot.py:279-280: one (n, 12) draw
+                   (3, 120, 245, 248, 249, 395, 398, 399, 498, 499, 748, 960, 985, 995, 998, 999, 1000), counter=745,
+                   patch=("torch.randint",)),
+    # heightfield terrain, terrain curriculum, estimator features / labels / critic stacks (go2_ee.py, legged_robot_ee.py)
+    "go2_ee": Gen("legged_gym.envs.go2.go2_ee.go2_ee", "Go2EE", "Go2EECfg", 24, 48, 21, _EE,
+                  ("actions_in", "rand", "counter", "feat_new", "priv_new", "labels", "rew", "reset", "time_out", "commands", "ep_len",
+                   "fail_buf", "feet_air_time", "episode_sums", "sim_dof_pos", "sim_base_pos") + _ROUGH_KEYS + ("contact_states",) + _TAIL,
+                  _LEGS3, _CLOCKS, place=place_go2_rough),
+    "go2_ts": _head("go2_ts", "Go2TS"),
+    "go2_cts": _head("go2_cts", "Go2CTS"),
+    "go2_dreamwaq": _head("go2_dreamwaq", "Go2Dreamwaq", ("obs", "priv", "feat", "explicit", "next_state", "rew", "reset", "extras")),
+    "go2_cat": _head("go2_cat", "Go2CaT"),
+    # the point-foot biped on the plane: base-class resets, 5-frame actor / critic stacks, `no_fly`.  Its module draws nothing itself.
+    "tron1_pf": Gen("legged_gym.envs.tron1_pf.tron1_pf", "TRON1PF", "TRON1PFCfg", 16, 40, 51, _PLANE,
+                    _BIPED_KEYS + ("sim_base_lin_vel_w", "dr") + _TAIL,
+                    (tuple(range(6)),), _BIPED_CLOCKS, place=place_tron1_pf),     # legged_robot.py:279-280: one (n, 6) draw
+    # 6-DOF biped, heightfield + curriculum, biped periodic gait, sit-pose resets (theta offset, gait time: torch.rand; the coin:
+    # np.random.random), all domain randomisation incl. joint armature / friction / damping.  The env is constructed with the
+    # original torch.rand.
+    "tron1_pf_ee": Gen("legged_gym.envs.tron1_pf.tron1_pf_ee.tron1_pf_ee", "TRON1PF_EE", "TRON1PF_EECfg", 24, 48, 31, _EE,
+                       ("actions_in", "rand", "counter", "feat_new", "priv_new", "labels", "rew", "reset", "time_out", "commands",
+                        "ep_len", "fail_buf", "episode_sums", "act_hist", "sim_dof_pos", "sim_base_pos", "sim_base_quat") + _ROUGH_KEYS
+                       + ("dr_joint", "task_state") + _TAIL,
+                       ((0, 3), (1, 4), (2, 5)), _CLOCKS,                 # tron1_pf_ee.py:268-273
+                       patch=("np.random.random",), patch_late=("torch.rand",), place=place_tron1_rough, big_action=30.0),
+    # the 8-DOF sole-foot biped on the plane: 10-frame stacks, the batch-wide sit-pose coin, `hip_pos_zero_command` / `foot_flat`
+    # (and `keep_ankle_pitch_zero_in_air`, which TaskSpec.reward_scales gives a scale so that it is pinned too)
+    "tron1_sf": Gen("legged_gym.envs.tron1_sf.tron1_sf", "TRON1SF", "TRON1SFCfg", 16, 44, 61, _PLANE,
+                    _BIPED_KEYS + ("sim_base_quat", "sim_base_lin_vel_w", "dr", "dr_pd", "dr_joint") + _TAIL,
+                    ((0, 3), (1, 4), (2, 5), (3, 6)), _BIPED_CLOCKS,      # tron1_sf.py:224-231: the 6-DOF index pairs on the 8-DOF vector
+                    patch=("np.random.random",), place=place_tron1_sf, commands=near_zero_commands),
+}
+assert list(GEN) == list(TASKS)
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+def _np(x):
+    return x.numpy().copy()
+
+
+def _u8(x):
+    return x.numpy().astype(np.uint8)
+
+
+def _cat(*xs):
+    return np.concatenate([x.numpy() for x in xs], 1).copy()
+
+
+def _task_state(s):
+    """mdp_harness.TASK_STATE's columns from the env's attributes (the reference keeps exp_C_frc per foot), as the fixtures record them."""
+    feet = GAIT[s.spec.gait][2]
+    cols = [torch.zeros(s.N, w) if a is None else
+            torch.cat([getattr(s.env, f"exp_C_frc_{f}") for f in feet], 1) if a == "exp_C_frc" else getattr(s.env, a)
+            for a, w in TASK_STATE[s.spec.gait]]
+    return recorded_task_state(s.spec.gait, _cat(*cols))
+
+
+_CSTR = ("torque", "dof_vel", "action_rate", "base_height", "collision", "feet_stumble", "dof_pos", "base_orientation", "stand_still")
+
+# fixture key -> its value for one step, from s: spec, g, env, sim, N, slots, names, and per step act, override, r (env.step()'s
+# results by name) and calls.  sim_<x> is the fake simulator's _<x>.  last_*_in are read before the step, everything else after.
+BEFORE_STEP = ("last_dof_vel_in", "last_feet_vel_in")       # what the kernel is given as "last" values for this step
+READ = {
+    "last_dof_vel_in": lambda s: _np(s.sim._dof_vel),
+    "last_feet_vel_in": lambda s: _np(s.sim._feet_vel),
+    "actions_in": lambda s: _np(s.act),
+    "rand": lambda s: slots_from_calls(s.calls, s.slots, s.N, s.act.shape[1], s.g.groups),
+    "counter": lambda s: s.env.common_step_counter,
+    "esum_override": lambda s: s.override,
+    "obs": lambda s: _np(s.r["obs"]),
+    "priv": lambda s: _np(s.r["priv"]),
+    "feat_new": lambda s: _np(s.r["feat"][:, -s.spec.frames[0]:]),
+    "priv_new": lambda s: _np(s.r["priv"][:, -s.spec.frames[1]:]),
+    "labels": lambda s: _np(s.r["labels"]),
+    "rew": lambda s: _np(s.r["rew"]),
+    "reset": lambda s: _u8(s.r["reset"]),
+    "time_out": lambda s: _u8(s.env.time_out_buf),
+    "commands": lambda s: _np(s.env.commands),
+    "ep_len": lambda s: _np(s.env.episode_length_buf),
+    "fail_buf": lambda s: _np(s.env.fail_buf),
+    "feet_air_time": lambda s: _np(s.env.feet_air_time),
+    "last_contacts": lambda s: _u8(s.env.last_contacts),
+    "episode_sums": lambda s: np.stack([_np(s.env.episode_sums[n]) for n in s.names]),
+    "act_hist": lambda s: np.stack([_np(s.env.actions), _np(s.env.last_actions), _np(s.env.llast_actions)]),
+    "dr": lambda s: _cat(s.sim._friction_values, s.sim._added_base_mass, s.sim._base_com_bias, s.sim._rand_push_vels[:, :2]),
+    "dr_pd": lambda s: _cat(s.sim._kp_scale, s.sim._kd_scale),
+    "dr_joint": lambda s: _cat(s.sim._joint_armature, s.sim._joint_friction, s.sim._joint_damping),
+    "cmd_range_x": lambda s: np.array(s.env.command_ranges["lin_vel_x"], np.float32),
+    "task_state": _task_state,
+    "terrain_levels": lambda s: _np(s.sim._terrain_levels),
+    "env_origins": lambda s: _np(s.sim._env_origins),
+    "measured_heights": lambda s: _np(s.sim._measured_heights),
+    "height_around_feet": lambda s: _np(s.sim._height_around_feet),
+    "normals": lambda s: _np(s.sim._normal_vector_around_feet),
+    "contact_states": lambda s: _np(s.sim._link_contact_states),
+    "cstr_prob": lambda s: _np(s.env.cstr_prob) if s.spec.cstr else np.zeros(s.N, np.float32),
+    "cstr_sums": lambda s: np.stack([_np(s.env.episode_sums["cstr_" + n]) for n in _CSTR]) if s.spec.cstr else np.zeros((0, s.N), np.float32),
+}
+
+
+def read(s, key):
+    return _np(getattr(s.sim, "_" + key[len("sim_"):])) if key.startswith("sim_") else READ[key](s)
+
+
+PATCHABLE = {"torch.rand_like": (torch, "rand_like", "rand_like"), "torch.randint": (torch, "randint", "randint"),
+             "torch.rand": (torch, "rand", "torch_rand"), "np.random.random": (np.random, "random", "np_random")}
+
+
+@contextlib.contextmanager
+def patched(rec, names, others=()):
+    """Serve the PATCHABLE globals `names` from the recorder and set `others` ((object, attribute, value)); restore all on exit."""
+    targets = [(obj, attr, getattr(rec, method)) for obj, attr, method in map(PATCHABLE.get, names)] + list(others)
+    saved = [(obj, attr, getattr(obj, attr)) for obj, attr, _ in targets]
+    for obj, attr, value in targets:
+        setattr(obj, attr, value)
     try:
-        cfg = TRON1SFCfg()
-        cfg.env.num_envs = N
-        cfg.rewards.scales.keep_ankle_pitch_zero_in_air = 0.2     # defined by the class, unscaled in the shipped config
-        env = sf_mod.TRON1SF(cfg, class_to_dict(cfg.sim), "cpu", True)
-        sim = env.simulator
-        sim.rec = rec
-        rng = np.random.default_rng(seed + 1)
-        model = sim.model
-        script = make_script(rng, model, cfg, N, T)
-        script["base_pos"][:, :, 2] += 0.43                       # nominal base height 0.75
-        script["feet_pos"][:, :, :, :2] = script["feet_pos"][:, :, :, :2] * 0.4 + script["base_pos"][:, :, None, :2]
-        script["foot_quat"] = np.stack([_mat_to_quat(foot_rotations(model, script["base_quat"][t], script["dof_pos"][t])) for t in range(T)])
-        sim.script = script
-        mycfg = MyCfg()
-        mycfg.rewards.scales.keep_ankle_pitch_zero_in_air = 0.2
-        task = builders.make_task_cfg(model, mycfg)
-        slots = task.slots
-        groups = [[0, 3], [1, 4], [2, 5], [3, 6]]                  # tron1_sf.py:224-231: the 6-DOF index pairs on the 8-DOF vector
-        env.episode_length_buf[:] = torch.from_numpy(rng.choice([3, 120, 470, 495, 498, 499, 968, 977, 985, 992, 995, 998, 999, 1000], N).astype(np.int32))
-        env.commands[:] = torch.from_numpy((rng.normal(size=(N, 4)) * [0.4, 0.4, 0.5, 1.5]).astype(np.float32))
-        env.commands[::3, :3] *= 0.05                              # ~zero commands: hip_pos_zero_command, the air-time gate
-        env.common_step_counter = 495                              # push interval 10 s = 500 steps
-        env.reset_buf[:] = 0
-        rec.take()
-        init = dict(episode_length_buf=env.episode_length_buf.numpy().copy(), commands=env.commands.numpy().copy(),
-                    env_origins=sim._env_origins.numpy().copy())
-        keys = ("actions_in", "rand", "counter", "obs", "priv", "rew", "reset", "time_out", "commands", "ep_len", "fail_buf", "feet_air_time",
-                "episode_sums", "act_hist", "sim_dof_pos", "sim_base_pos", "sim_base_quat", "sim_base_lin_vel_w", "dr", "dr_pd", "dr_joint",
-                "last_dof_vel_in", "last_feet_vel_in", "esum_override")
-        out = {k: [] for k in keys}
-        names = env.reward_names
-        for t in range(T):
-            act = torch.from_numpy((rng.normal(size=(N, 8)) * (1.0 if t % 7 else 60.0)).astype(np.float32))
-            out["last_dof_vel_in"].append(sim._dof_vel.numpy().copy()); out["last_feet_vel_in"].append(sim._feet_vel.numpy().copy())
-            obs, priv, rew, reset, extras = env.step(act)
-            calls = rec.take()
-            out["actions_in"].append(act.numpy().copy()); out["rand"].append(slots_from_calls(calls, slots, N, 8, groups))
-            out["counter"].append(env.common_step_counter); out["esum_override"].append(0.0)
-            out["obs"].append(obs.numpy().copy()); out["priv"].append(priv.numpy().copy()); out["rew"].append(rew.numpy().copy())
-            out["reset"].append(reset.numpy().astype(np.uint8)); out["time_out"].append(env.time_out_buf.numpy().astype(np.uint8))
-            out["commands"].append(env.commands.numpy().copy()); out["ep_len"].append(env.episode_length_buf.numpy().copy())
-            out["fail_buf"].append(env.fail_buf.numpy().copy()); out["feet_air_time"].append(env.feet_air_time.numpy().copy())
-            out["episode_sums"].append(np.stack([env.episode_sums[n].numpy().copy() for n in names]))
-            out["act_hist"].append(np.stack([env.actions.numpy(), env.last_actions.numpy(), env.llast_actions.numpy()]).copy())
-            out["sim_dof_pos"].append(sim._dof_pos.numpy().copy()); out["sim_base_pos"].append(sim._base_pos.numpy().copy())
-            out["sim_base_quat"].append(sim._base_quat.numpy().copy()); out["sim_base_lin_vel_w"].append(sim._base_lin_vel_w.numpy().copy())
-            out["dr"].append(np.concatenate([sim._friction_values.numpy(), sim._added_base_mass.numpy(), sim._base_com_bias.numpy(),
-                                             sim._rand_push_vels.numpy()[:, :2]], 1).copy())
-            out["dr_pd"].append(np.concatenate([sim._kp_scale.numpy(), sim._kd_scale.numpy()], 1).copy())
-            out["dr_joint"].append(np.concatenate([sim._joint_armature.numpy(), sim._joint_friction.numpy(), sim._joint_damping.numpy()], 1).copy())
-        arrays = {k: np.stack(v) for k, v in out.items()}
-        arrays.update({"script_" + k: v for k, v in sim.script.items()})
-        arrays.update({"init_" + k: v for k, v in init.items()})
-        arrays["reward_names"] = np.array(names)
-        path = os.path.join(HERE, "tron1_sf_mdp.npz")
-        np.savez_compressed(path, **arrays)
-        sit = arrays["reset"].astype(bool) & (np.abs(arrays["sim_dof_pos"][:, :, 2] - 1.35) < 1e-6)
-        print("wrote", path, os.path.getsize(path), arrays["obs"].shape, arrays["priv"].shape, "resets/step", arrays["reset"].sum(1),
-              "sit resets", int(sit.sum()), list(names))
+        yield
     finally:
-        torch.rand_like, np.random.random = orig
+        for obj, attr, value in saved:
+            setattr(obj, attr, value)
 
 
-def gen_head(name, N=16, T=36, seed=41):
-    """The other Go2-rough heads -- Go2TS, Go2CTS, Go2Dreamwaq, Go2CaT (legged_gym/envs/__init__.py:82-86) -- run AS CONFIGURED
-    on the rough fake simulator: same recording as gen_ee.  Stored per step: the clipped actor frame, the newest frame of the
-    20-deep actor history and of the 5-deep critic stack, and the single-frame auxiliary output (TS / CTS / CaT: privileged
-    encoder input; Dreamwaq: explicit labels | next state), plus the full stacks at the last step.  As configured the asset
-    selects 17 contact-state links while the size fields assume 12 (go2_ts_config.py:8-14): what the class EMITS is pinned."""
-    import importlib
+def generate(name):
+    """Run the reference's task class for TASKS[name] / GEN[name] on the fake simulator and save <name>_mdp.npz."""
     import legged_gym.envs.base.base_task as base_task
     import legged_gym.envs.base.legged_robot as lr_mod
     from legged_gym.utils.helpers import class_to_dict
-    from hcr_genesis_lr_cl_amd import config as mycfg
-    mod_name, cls_name, cfg_mod, cfg_name, my_name = {
-        "go2_ts": ("legged_gym.envs.go2.go2_ts.go2_ts", "Go2TS", "legged_gym.envs.go2.go2_ts.go2_ts_config", "Go2TSCfg", "GO2TSCfg"),
-        "go2_cts": ("legged_gym.envs.go2.go2_cts.go2_cts", "Go2CTS", "legged_gym.envs.go2.go2_cts.go2_cts_config", "Go2CTSCfg", "GO2CTSCfg"),
-        "go2_dreamwaq": ("legged_gym.envs.go2.go2_dreamwaq.go2_dreamwaq", "Go2Dreamwaq", "legged_gym.envs.go2.go2_dreamwaq.go2_dreamwaq_config",
-                         "Go2DreamwaqCfg", "GO2DreamwaqCfg"),
-        "go2_cat": ("legged_gym.envs.go2.go2_cat.go2_cat", "Go2CaT", "legged_gym.envs.go2.go2_cat.go2_cat_config", "Go2CaTCfg", "GO2CaTCfg"),
-    }[name]
-    env_mod = importlib.import_module(mod_name)
-    ref_cfg_cls = getattr(importlib.import_module(cfg_mod), cfg_name)
-    rec = rh.DrawRecorder(seed)
-    base_task.GenesisSimulator = RoughFakeSimulator
-    lr_mod.torch_rand_float = rec.rand_float
-    env_mod.torch_rand_float = rec.rand_float
-    orig_rand_like = torch.rand_like
-    torch.rand_like = rec.rand_like
-    try:
-        cfg = ref_cfg_cls()
+    spec, g = TASKS[name], GEN[name]
+    N, T = g.N, g.T
+    mod = importlib.import_module(g.module)
+    rec = rh.DrawRecorder(g.seed)
+    # the base class's uniform source, and the task module's own copy of the name where it has one
+    draws = [(m, "torch_rand_float", rec.rand_float) for m in (lr_mod, mod) if hasattr(m, "torch_rand_float")]
+    with contextlib.ExitStack() as stack:
+        stack.enter_context(patched(rec, ("torch.rand_like",) + g.patch,
+                                    [(base_task, "GenesisSimulator", RoughFakeSimulator if spec.rough else FakeSimulator)] + draws))
+        cfg = getattr(importlib.import_module(g.module + "_config"), g.cfg)()
         cfg.env.num_envs = N
         if hasattr(cfg.env, "num_teacher"):
             cfg.env.num_teacher = N // 4 * 3
-        env = getattr(env_mod, cls_name)(cfg, class_to_dict(cfg.sim), "cpu", True)
+        for k, v in spec.reward_scales:
+            setattr(cfg.rewards.scales, k, v)
+        env = getattr(mod, g.cls)(cfg, class_to_dict(cfg.sim), "cpu", True)
+        stack.enter_context(patched(rec, g.patch_late))
         sim = env.simulator
         sim.rec = rec
-        if name == "go2_cat":          # properties of the Simulator ABC the constraints read (simulator.py: torque_limits, dof_vel_limits)
-            type(sim).torque_limits = property(lambda s_: torch.tensor(s_.model.arrays["effort"], dtype=torch.float))
-            type(sim).dof_vel_limits = property(lambda s_: torch.tensor(s_._cfg.asset.dof_vel_limits, dtype=torch.float).unsqueeze(0))
-        rng = np.random.default_rng(seed + 1)
-        model = sim.model
-        script = make_script(rng, model, cfg, N, T)
-        org = sim._env_origins.numpy()
-        off = rng.normal(size=(T, N, 2)) * 1.5 + np.where(rng.random((T, N, 1)) < 0.3, 4.5, 0.0)
-        script["base_pos"][:, :, :2] = (org[None, :, :2] + off).astype(np.float32)
-        script["base_pos"][:, :, 2] += org[None, :, 2]
-        script["feet_pos"][:, :, :, :2] += script["base_pos"][:, :, None, :2]
-        script["feet_pos"][:, :, :, 2] += org[None, :, None, 2]
+        if spec.cstr:
+            cat_limits(sim)
+        rng = np.random.default_rng(g.seed + 1)
+        script = make_script(rng, sim.model, cfg, N, T)
+        if g.place:
+            g.place(script, sim, rng)
         sim.script = script
-        task = builders.make_task_cfg(model, getattr(mycfg, my_name)())
-        slots = task.slots
-        groups = [[0, 3, 6, 9], [1, 4, 7, 10], [2, 5, 8, 11]]
-        env.episode_length_buf[:] = torch.from_numpy(rng.choice([3, 470, 495, 498, 499, 968, 972, 977, 981, 985, 989, 992, 995, 998, 999, 1000], N).astype(np.int32))
+        # initial MDP state: as after construction, with the episode clocks spread
+        env.episode_length_buf[:] = torch.from_numpy(rng.choice(g.clocks, N).astype(np.int32))
         env.commands[:] = torch.from_numpy((rng.normal(size=(N, 4)) * [0.4, 0.4, 0.5, 1.5]).astype(np.float32))
-        env.commands[:3] = 0.0                                   # standing-still envs (feet_contact_stand_still, CaT's style constraint)
-        env.common_step_counter = 495
+        if g.commands:
+            g.commands(env)
+        env.common_step_counter = g.counter
         env.reset_buf[:] = 0
         env.extras.setdefault("episode", {})      # exists after the runner's env.reset(); go2_cts.py:96 / go2_cat.py:101 index it on every step
+        init = dict(episode_length_buf=env.episode_length_buf, commands=env.commands, env_origins=sim._env_origins)
+        if spec.go2:
+            init["default_dof_pos"] = sim._default_dof_pos
+        if spec.rough:
+            init.update(terrain_levels=sim._terrain_levels, terrain_types=sim._terrain_types, height_points=sim._height_points[0, :, :2])
+        if spec.gait:
+            set_gait, gait_keys, _ = GAIT[spec.gait]
+            set_gait(env, rng, N)
+            init.update({k: getattr(env, k) for k in gait_keys})
+        init = {k: _np(v) for k, v in init.items()}
+        if spec.gait == "wtw":
+            init["behavior_ranges"] = np.array(env.gait_period_range + env.base_height_target_range + env.foot_clearance_target_range +
+                                               env.pitch_target_range + [env.num_gaits], np.float32)
         rec.take()
-        init = dict(episode_length_buf=env.episode_length_buf.numpy().copy(), commands=env.commands.numpy().copy(),
-                    env_origins=sim._env_origins.numpy().copy(), terrain_levels=sim._terrain_levels.numpy().copy(),
-                    terrain_types=sim._terrain_types.numpy().copy(), height_points=sim._height_points[0, :, :2].numpy().copy())
-        keys = ("actions_in", "rand", "counter", "obs", "feat_new", "priv_new", "labels", "rew", "reset", "time_out", "commands", "ep_len",
-                "fail_buf", "feet_air_time", "episode_sums", "sim_dof_pos", "sim_base_pos", "terrain_levels", "env_origins",
-                "measured_heights", "height_around_feet", "normals", "contact_states", "last_dof_vel_in", "last_feet_vel_in", "esum_override",
-                "cstr_prob", "cstr_sums")
-        out = {k: [] for k in keys}
-        names = env.reward_names
-        cstr_names = ["torque", "dof_vel", "action_rate", "base_height", "collision", "feet_stumble", "dof_pos", "base_orientation", "stand_still"]
+        s = types.SimpleNamespace(spec=spec, g=g, env=env, sim=sim, N=N, names=env.reward_names,
+                                  slots=builders.make_task_cfg(sim.model, spec.cfg()).slots)
+        out = {k: [] for k in g.keys}
         for t in range(T):
-            act = torch.from_numpy((rng.normal(size=(N, 12)) * (1.0 if t % 7 else 60.0)).astype(np.float32))
-            out["last_dof_vel_in"].append(sim._dof_vel.numpy().copy()); out["last_feet_vel_in"].append(sim._feet_vel.numpy().copy())
-            res = env.step(act)
-            if name == "go2_dreamwaq":
-                obs, critic, hist, explicit, nxt, rew, reset, extras = res
-                aux = torch.cat([explicit, nxt], dim=-1)
-            else:
-                obs, aux, hist, critic, rew, reset, extras = res
-            calls = rec.take()
-            FW = critic.shape[1] - 4 * cfg.env.single_critic_obs_len if t < 4 else critic.shape[1] // 5   # newest frame width
-            out["actions_in"].append(act.numpy().copy()); out["rand"].append(slots_from_calls(calls, slots, N, 12, groups))
-            out["counter"].append(env.common_step_counter); out["esum_override"].append(0.0)
-            out["obs"].append(obs.numpy().copy())
-            out["feat_new"].append(hist.numpy()[:, -45:].copy()); out["priv_new"].append(critic.numpy()[:, -177:].copy())
-            assert critic.shape[1] in (4 * cfg.env.single_critic_obs_len + 177, 3 * cfg.env.single_critic_obs_len + 2 * 177,
-                                       2 * cfg.env.single_critic_obs_len + 3 * 177, cfg.env.single_critic_obs_len + 4 * 177, 5 * 177), critic.shape
-            out["labels"].append(aux.numpy().copy()); out["rew"].append(rew.numpy().copy())
-            out["reset"].append(reset.numpy().astype(np.uint8)); out["time_out"].append(env.time_out_buf.numpy().astype(np.uint8))
-            out["commands"].append(env.commands.numpy().copy()); out["ep_len"].append(env.episode_length_buf.numpy().copy())
-            out["fail_buf"].append(env.fail_buf.numpy().copy()); out["feet_air_time"].append(env.feet_air_time.numpy().copy())
-            out["episode_sums"].append(np.stack([env.episode_sums[n].numpy().copy() for n in names]))
-            out["sim_dof_pos"].append(sim._dof_pos.numpy().copy()); out["sim_base_pos"].append(sim._base_pos.numpy().copy())
-            out["terrain_levels"].append(sim._terrain_levels.numpy().copy()); out["env_origins"].append(sim._env_origins.numpy().copy())
-            out["measured_heights"].append(sim._measured_heights.numpy().copy())
-            out["height_around_feet"].append(sim._height_around_feet.numpy().copy())
-            out["normals"].append(sim._normal_vector_around_feet.numpy().copy())
-            out["contact_states"].append(sim._link_contact_states.numpy().copy())
-            if name == "go2_cat":
-                out["cstr_prob"].append(env.cstr_prob.numpy().copy())
-                out["cstr_sums"].append(np.stack([env.episode_sums["cstr_" + n].numpy().copy() for n in cstr_names]))
-            else:
-                out["cstr_prob"].append(np.zeros(N, np.float32)); out["cstr_sums"].append(np.zeros((0, N), np.float32))
+            s.override = go2_gate(env, t) if spec.go2 else 0.0
+            s.act = torch.from_numpy((rng.normal(size=(N, cfg.env.num_actions)) * (1.0 if t % 7 else g.big_action)).astype(np.float32))
+            for k in BEFORE_STEP:
+                out[k].append(read(s, k))
+            s.r = dict(zip(g.returns, env.step(s.act), strict=True))
+            s.calls = rec.take()
+            if "explicit" in s.r:                                         # go2_dreamwaq
+                s.r["labels"] = torch.cat([s.r["explicit"], s.r["next_state"]], dim=-1)
+            for k in g.keys:
+                if k not in BEFORE_STEP:
+                    out[k].append(read(s, k))
         arrays = {k: np.stack(v) for k, v in out.items()}
-        arrays["feat_last"], arrays["priv_last"] = hist.numpy().copy(), critic.numpy().copy()
+        if spec.stacks:
+            arrays["feat_last"], arrays["priv_last"] = _np(s.r["feat"]), _np(s.r["priv"])
         arrays.update({"script_" + k: v for k, v in sim.script.items()})
         arrays.update({"init_" + k: v for k, v in init.items()})
-        arrays["reward_names"] = np.array(names)
-        arrays["terrain_seed"] = RoughFakeSimulator.TERRAIN_SEED
-        path = os.path.join(HERE, f"{name}_mdp.npz")
-        np.savez_compressed(path, **arrays)
-        print("wrote", path, os.path.getsize(path), "aux width", arrays["labels"].shape[-1], "critic stack", arrays["priv_last"].shape,
-              "resets/step", arrays["reset"].sum(1), "levels moved", int((arrays["terrain_levels"][-1] != init["terrain_levels"]).sum()))
-    finally:
-        torch.rand_like = orig_rand_like
+        arrays["reward_names"] = np.array(s.names)
+        if spec.rough:
+            arrays["terrain_seed"] = RoughFakeSimulator.TERRAIN_SEED
+        moved = ("levels moved", int((arrays["terrain_levels"][-1] != init["terrain_levels"]).sum())) if spec.rough else ()
+        rh.save(f"{name}_mdp", arrays, "resets/step", arrays["reset"].sum(1), *moved)
 
 
 if __name__ == "__main__":
-    which = sys.argv[1:] or ["go2", "wtw", "ee", "tron1", "go2_ts", "go2_cts", "go2_dreamwaq", "go2_cat", "tron1_pf", "tron1_sf"]
-    if "tron1_sf" in which:
-        gen_tron1_sf()
-    if "tron1_pf" in which:
-        gen_tron1_pf()
-    for h in ("go2_ts", "go2_cts", "go2_dreamwaq", "go2_cat"):
-        if h in which:
-            gen_head(h)
-    if "tron1" in which:
-        gen_tron1()
-    if "ee" in which:
-        gen_ee()
-    if "go2" in which:
-        gen_go2()
-    if "wtw" in which:
-        gen_wtw()
+    for task in sys.argv[1:] or TASKS:
+        generate(task)

@@ -3,7 +3,8 @@
 (rsl_rl/storage/rollout_storage.py:89-102) and compute_returns (:124-138: GAE + advantage normalisation).
 
 Build-container only:   PYTHONDONTWRITEBYTECODE=1 python tests/golden/gen_rollout_fixtures.py
-Output: tests/golden/rollout_gae.npz (inputs per step + every storage tensor afterwards)."""
+Output: tests/golden/rollout_gae.npz (inputs per step + every storage tensor afterwards).
+Written through ref_harness.save; `python tests/golden/check_fixtures.py` checks that the output still equals the committed files."""
 import os
 import sys
 
@@ -55,10 +56,8 @@ def main(N=48, T=24, seed=5):
     assert np.array_equal(st.values.numpy(), arrays["values"]) and np.array_equal(st.actions_log_prob.numpy()[..., 0], arrays["logp"])
     for k in ("rewards", "dones", "returns", "advantages"):
         arrays["st_" + k] = getattr(st, k).numpy().copy()
-    path = os.path.join(HERE, "rollout_gae.npz")
-    np.savez_compressed(path, **arrays)
-    print("wrote", path, os.path.getsize(path), "dones", int(arrays["dones"].sum()), "time_outs", int(arrays["time_outs"].sum()),
-          "adv mean/std", float(st.advantages.mean()), float(st.advantages.std()))
+    rh.save("rollout_gae", arrays, "dones", int(arrays["dones"].sum()), "time_outs", int(arrays["time_outs"].sum()),
+            "adv mean/std", float(st.advantages.mean()), float(st.advantages.std()))
 
 
 if __name__ == "__main__":

@@ -9,7 +9,8 @@ Output: tests/golden/rollout_recurrent_<rnn>_r<k>_<part>.npz for rnn in lstm / g
 file stays under the committed-file limit (steps: per-step inputs and the storage's value-derived tensors; hidden_a / hidden_c: the
 full saved_hidden_states_a / _c; batches_obs / batches_rest: every yielded tensor of every mini-batch, plus the LSTM critic's own start
 states that the reference does not yield), and tests/golden/rollout_recurrent_short.npz (every env done at the same step, so that the
-longest trajectory is shorter than the rollout)."""
+longest trajectory is shorter than the rollout).
+Written through ref_harness.save; `python tests/golden/check_fixtures.py` checks that the output still equals the committed files."""
 import os
 import sys
 
@@ -27,11 +28,8 @@ YIELD = ("obs", "critic_obs", "actions", "values", "advantages", "returns", "log
 
 
 def save(name, arrays):
-    path = os.path.join(HERE, name)
-    np.savez_compressed(path, **arrays)
-    size = os.path.getsize(path)
-    assert size < LIMIT, (name, size)
-    print("wrote", name, size)
+    path = rh.save(name, arrays)
+    assert os.path.getsize(path) < LIMIT, path
 
 
 def as_lists(hidden_states):
@@ -135,11 +133,11 @@ def run(rnn, N=48, T=24, seed=5):
                 assert np.array_equal(rest[f"b{b}_own_c0"], rest[f"b{b}_hid_c0"])
             first = last
         assert first == len(starts)
-        save(f"rollout_recurrent_{rnn}_r{k}_steps.npz", steps)
-        save(f"rollout_recurrent_{rnn}_r{k}_hidden_a.npz", {f"saved_a{i}": x for i, x in enumerate(saved_a)})
-        save(f"rollout_recurrent_{rnn}_r{k}_hidden_c.npz", {f"saved_c{i}": x for i, x in enumerate(saved_c)})
-        save(f"rollout_recurrent_{rnn}_r{k}_batches_obs.npz", obs_part)
-        save(f"rollout_recurrent_{rnn}_r{k}_batches_rest.npz", rest)
+        save(f"rollout_recurrent_{rnn}_r{k}_steps", steps)
+        save(f"rollout_recurrent_{rnn}_r{k}_hidden_a", {f"saved_a{i}": x for i, x in enumerate(saved_a)})
+        save(f"rollout_recurrent_{rnn}_r{k}_hidden_c", {f"saved_c{i}": x for i, x in enumerate(saved_c)})
+        save(f"rollout_recurrent_{rnn}_r{k}_batches_obs", obs_part)
+        save(f"rollout_recurrent_{rnn}_r{k}_batches_rest", rest)
         st.clear()
     print(rnn, "trajectories per rollout", n_traj)
 
@@ -153,7 +151,7 @@ def short():
     dones[2] = 1
     padded, masks = split_and_pad_trajectories(x, dones)
     assert padded.shape == (3, 6, 5) and masks.shape == (6, 6)
-    save("rollout_recurrent_short.npz", dict(x=x.numpy(), dones=dones.numpy(), padded=padded.numpy().copy(), masks=masks.numpy().copy()))
+    save("rollout_recurrent_short", dict(x=x.numpy(), dones=dones.numpy(), padded=padded.numpy().copy(), masks=masks.numpy().copy()))
 
 
 if __name__ == "__main__":

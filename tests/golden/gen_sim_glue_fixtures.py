@@ -4,6 +4,7 @@ RUNNING THE REFERENCE'S OWN METHODS UNBOUND on a stand-in object whose `_robot` 
 
 Build-container only:   PYTHONDONTWRITEBYTECODE=1 python tests/golden/gen_sim_glue_fixtures.py
 Output: tests/golden/sim_glue_<task>.npz and tests/golden/math_utils_kat.npz (data only).
+Written through ref_harness.save; `python tests/golden/check_fixtures.py` checks that the output still equals the committed files.
 
 What is pinned (reference file:line):
   * GenesisSimulator.step            genesis_simulator.py:20-33   "last" snapshots, one _compute_torques per sub-step
@@ -342,10 +343,8 @@ def gen_task(name, ref_cfg_cls, N=16, T=6, seed=101):
             GS.update_terrain_curriculum(g, ids, up, down)
             arrays["tc_levels"] = g._terrain_levels.numpy().copy()
             arrays["tc_env_origins"] = g._env_origins.numpy().copy()
-        path = os.path.join(HERE, f"sim_glue_{name}.npz")
-        np.savez_compressed(path, **arrays)
-        print("wrote", path, os.path.getsize(path), "oob/step", arrays["oob_ids"].sum(1), "reset draws", list(arrays["reset_draw_tags"]),
-              "setters", list(arrays["reset_setter_names"]))
+        rh.save(f"sim_glue_{name}", arrays, "oob/step", arrays["oob_ids"].sum(1), "reset draws", list(arrays["reset_draw_tags"]),
+                "setters", list(arrays["reset_setter_names"]))
     finally:
         torch.rand, torch.randint_like = orig_rand, orig_randint_like
 
@@ -369,9 +368,7 @@ def gen_math_kat(seed=301, n=64):
                   quat_from_euler_xyz=mu.quat_from_euler_xyz(torch.from_numpy(rpy[:, 0]), torch.from_numpy(rpy[:, 1]), torch.from_numpy(rpy[:, 2])).numpy(),
                   quat_mul=mu.quat_mul(tq, torch.from_numpy(np.roll(q, 1, 0).copy())).numpy(),
                   normalize=mu.normalize(tv).numpy())
-    path = os.path.join(HERE, "math_utils_kat.npz")
-    np.savez_compressed(path, **arrays)
-    print("wrote", path, os.path.getsize(path))
+    rh.save("math_utils_kat", arrays)
 
 
 if __name__ == "__main__":

@@ -1,5 +1,6 @@
 """Golden heightfields from the reference's own Terrain class (build container only).
-Stores the int16 grids (compressed) + env origins for the two rough-terrain configs in scope."""
+Stores the int16 grids (compressed) + env origins for the two rough-terrain configs in scope.
+Written through ref_harness.save; `python tests/golden/check_fixtures.py` checks that the output still equals the committed files."""
 import os
 import sys
 
@@ -20,7 +21,5 @@ for name, cfg_cls, curriculum in (("go2_ee", Go2EECfg, True), ("tron1_pf_ee", TR
     cfg.terrain.curriculum = curriculum
     np.random.seed(3)
     t = Terrain(cfg.terrain)
-    np.savez_compressed(os.path.join(HERE, f"terrain_{name}.npz"), height_field_raw=t.height_field_raw,
-                        env_origins=t.env_origins, seed=3, curriculum=curriculum)
-    print(name, t.height_field_raw.shape, t.height_field_raw.min(), t.height_field_raw.max(),
-          os.path.getsize(os.path.join(HERE, f"terrain_{name}.npz")))
+    rh.save(f"terrain_{name}", dict(height_field_raw=t.height_field_raw, env_origins=t.env_origins, seed=3, curriculum=curriculum),
+            t.height_field_raw.shape, t.height_field_raw.min(), t.height_field_raw.max())

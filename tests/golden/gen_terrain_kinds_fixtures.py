@@ -9,6 +9,7 @@ tests rebuild the same config from the file:
   selected_<generator>             legged_gym/scripts/play.py:26-64 overrides (2 x 2 tiles, 5 m border, selected) with each of its
                                    eight terrain_kwargs sets;
   nav_six                          a six-entry go2_nav-style proportions list (legged_gym/envs/go2/go2_nav/go2_nav_config.py:30).
+Written through ref_harness.save; `python tests/golden/check_fixtures.py` checks that the output still equals the committed files.
 """
 import copy
 import json
@@ -54,10 +55,9 @@ def main():
         np.random.seed(SEED)
         t = Terrain(cfg.terrain)
         after = np.random.random()
-        path = os.path.join(HERE, f"terrain_kinds_{name}.npz")
-        np.savez_compressed(path, height_field_raw=t.height_field_raw, env_origins=t.env_origins, seed=SEED, after=after,
-                            overrides=json.dumps(over, sort_keys=True))
-        print(name, t.height_field_raw.shape, t.height_field_raw.min(), t.height_field_raw.max(), os.path.getsize(path))
+        rh.save(f"terrain_kinds_{name}", dict(height_field_raw=t.height_field_raw, env_origins=t.env_origins, seed=SEED, after=after,
+                                              overrides=json.dumps(over, sort_keys=True)),
+                t.height_field_raw.shape, t.height_field_raw.min(), t.height_field_raw.max())
 
 
 if __name__ == "__main__":

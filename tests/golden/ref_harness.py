@@ -17,6 +17,17 @@ import types
 sys.dont_write_bytecode = True
 os.environ["SIMULATOR"] = "genesis"
 REF = os.environ.get("LG_REFERENCE", "/root/reference")
+GOLDEN = os.path.dirname(os.path.abspath(__file__))
+OUT_ENV = "LG_GOLDEN_OUT"          # a directory for the generators to write to instead of tests/golden/ (check_fixtures.py)
+
+
+def save(name, arrays, *info):
+    """Every generator's way out: <name>.npz, arrays in the order given, and one line saying so.  Returns the path."""
+    import numpy as np
+    path = os.path.join(os.environ.get(OUT_ENV) or GOLDEN, name + ".npz")
+    np.savez_compressed(path, **arrays)
+    print("wrote", path, os.path.getsize(path), *info)
+    return path
 
 
 class _Anything:

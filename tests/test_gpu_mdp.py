@@ -157,7 +157,7 @@ def test_kernel_reproduces_reference_go2_ee_golden_vectors(tail):
 @pytest.mark.parametrize("head", ["go2_ts", "go2_cts", "go2_dreamwaq", "go2_cat"])
 def test_kernel_reproduces_reference_head_golden_vectors(head, tail):
     """the other Go2-rough heads.  Golden vectors from the reference's own Go2TS / Go2CTS / Go2Dreamwaq classes as
-    configured (tests/golden/gen_mdp_fixtures.py gen_head): actor frame, newest frames of the 20-deep actor history and the
+    configured (tests/golden/gen_mdp_fixtures.py, GEN["go2_ts"] ...): actor frame, newest frames of the 20-deep actor history and the
     5-deep critic stack (full stacks at the last step), the single-frame auxiliary output, rewards, resets, curricula."""
     if head == "go2_cat" and tail == "fused-profile":
         pytest.skip("go2_cat has no component-layout tail: its MDP phases are the leg-per-lane launch in the product too")
@@ -279,7 +279,7 @@ def test_tron1_env_runs_physics_and_mdp():
 
 # ------------------------------- tron1_pf (biped on the plane) ------------------------------------
 def test_kernel_reproduces_reference_tron1_pf_golden_vectors():
-    """TRON1PF on the plane, golden vectors from the reference's own class (gen_mdp_fixtures.py gen_tron1_pf)."""
+    """TRON1PF on the plane, golden vectors from the reference's own class (gen_mdp_fixtures.py, GEN["tron1_pf"])."""
     replay_golden("tron1_pf")
 
 
@@ -332,7 +332,7 @@ def test_cat_job_wide_flag_is_raised_by_the_physics_launch():
 
 # ------------------------------- tron1_sf (8-DOF sole-foot biped on the plane) ---------------------
 def test_kernel_reproduces_reference_tron1_sf_golden_vectors():
-    """TRON1SF, golden vectors from the reference's own class (gen_mdp_fixtures.py gen_tron1_sf): four-joint legs in the
+    """TRON1SF, golden vectors from the reference's own class (gen_mdp_fixtures.py, GEN["tron1_sf"]): four-joint legs in the
     MDP phases, the sole-foot reward terms, the sit-pose coin, the 10-frame stacks with the kp / kd blocks in the critic frame."""
     replay_golden("tron1_sf")
 
