@@ -124,6 +124,9 @@ class RolloutStorage:
         t = self.step
         if t >= self.num_transitions_per_env:
             raise AssertionError("Rollout buffer overflow")
+        rew = self._env_row("rew", rew, (torch.float32,))
+        rst = self._env_row("reset", reset, (torch.bool, torch.uint8))
+        to = None if time_outs is None else self._env_row("time_outs", time_outs, (torch.bool, torch.uint8))
         copies = self._hidden_copies(t, hidden_states)
         if observations is not None and not self.zero_copy:
             copies.append((observations, self.observations[t]))
@@ -132,30 +135,49 @@ class RolloutStorage:
         copies += list(extra_copies)
         arr = (abi.LgRowCopy * max(len(copies), 1))()
         for i, (src, dst) in enumerate(copies):
-            if src.dim() != 2 or src.stride(1) != 1 or not dst.is_contiguous() or src.shape != dst.shape or src.dtype != torch.float32:
+            if (src.dim() != 2 or src.stride(1) != 1 or not dst.is_contiguous() or src.shape != dst.shape or src.dtype != torch.float32
+                    or dst.dtype != torch.float32 or src.shape[0] != self.num_envs or src.device != dst.device):
                 raise ValueError("row copies take (N, width) float32 views with unit inner stride")
             arr[i].src, arr[i].dst, arr[i].width, arr[i].src_stride = src.data_ptr(), dst.data_ptr(), src.shape[1], src.stride(0)
-        rst = reset.view(torch.uint8) if reset.dtype == torch.bool else reset
-        to = None if time_outs is None else (time_outs.view(torch.uint8) if time_outs.dtype == torch.bool else time_outs)
         stream = torch.cuda.current_stream(self.device).cuda_stream
         abi.check(self.lib.lg_rollout_record(self.num_envs, rew.data_ptr(), rst.data_ptr(), 0 if to is None else to.data_ptr(),
                                              self.values[t].data_ptr(), float(gamma), self.rewards[t].data_ptr(), self.dones[t].data_ptr(),
                                              arr, len(copies), stream), self.lib)
         self.step += 1
 
+    def _env_row(self, name, x, dtypes):
+        """One of add_step's per-env inputs as the record kernel reads it: N elements of one of `dtypes`, consecutive in memory, on the
+        storage's device.  The kernel takes a bare pointer, so anything else would be read as the wrong bytes: it is refused here, before
+        any launch, and never converted (a conversion is a hidden launch; `add_transitions` is the entry point that converts).  A bool
+        tensor is re-viewed as uint8, which costs nothing."""
+        if (not torch.is_tensor(x) or x.dtype not in dtypes or x.numel() != self.num_envs or not x.is_contiguous()
+                or x.device != self.rewards.device):
+            got = f"{tuple(x.shape)} {x.dtype} strides {x.stride()} on {x.device}" if torch.is_tensor(x) else type(x).__name__
+            raise ValueError(f"add_step: {name} must hold {self.num_envs} contiguous elements of {' / '.join(str(d) for d in dtypes)} on "
+                             f"{self.rewards.device}, got {got}")
+        return x.view(torch.uint8) if x.dtype == torch.bool else x
+
     def add_transitions(self, transition):
         """rollout_storage.py:89-102, the reference's entry point (rsl_rl's PPO.process_env_step has already bootstrapped
-        `transition.rewards`): policy-side rows by copy_, env-side rows by the record kernel."""
+        `transition.rewards`): policy-side rows by copy_, env-side rows by the record kernel.  The reference's `copy_` converts whatever
+        dtype it is given (its BaseTask.reset_buf is torch.int), so rewards and dones that are not already what the kernel reads are
+        converted the same way first: dones to the uint8 of the stored row, rewards to float32."""
         t = self.step
         if t >= self.num_transitions_per_env:
             raise AssertionError("Rollout buffer overflow")
+        rew, dones = transition.rewards.reshape(-1), transition.dones.reshape(-1)
+        if rew.dtype != torch.float32 or not rew.is_contiguous():
+            rew = rew.to(torch.float32).contiguous()
+        if dones.dtype not in (torch.bool, torch.uint8) or not dones.is_contiguous():
+            dones = dones.to(torch.uint8).contiguous()
+        self._env_row("rewards", rew, (torch.float32,)), self._env_row("dones", dones, (torch.bool, torch.uint8))   # before any row is written
         self.actions[t].copy_(transition.actions)
         self.values[t].copy_(transition.values)
         self.actions_log_prob[t].copy_(transition.actions_log_prob.view(-1, 1))
         self.mu[t].copy_(transition.action_mean)
         self.sigma[t].copy_(transition.action_sigma)
         crit = transition.critic_observations if self.privileged_observations is not None else None
-        self.add_step(transition.rewards.reshape(-1).contiguous(), transition.dones.reshape(-1), None, 0.0,
+        self.add_step(rew, dones, None, 0.0,
                       observations=transition.observations, critic_observations=crit,
                       hidden_states=getattr(transition, "hidden_states", None))
 

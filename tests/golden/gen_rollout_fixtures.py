@@ -3,7 +3,8 @@
 (rsl_rl/storage/rollout_storage.py:89-102) and compute_returns (:124-138: GAE + advantage normalisation).
 
 Build-container only:   PYTHONDONTWRITEBYTECODE=1 python tests/golden/gen_rollout_fixtures.py
-Output: tests/golden/rollout_gae.npz (inputs per step + every storage tensor afterwards).
+Output: tests/golden/rollout_gae.npz (inputs per step + every storage tensor afterwards) and tests/golden/rollout_stats.npz
+(get_statistics of small hand-made done patterns, written afterwards so that the first file does not depend on it).
 Written through ref_harness.save; `python tests/golden/check_fixtures.py` checks that the output still equals the committed files."""
 import os
 import sys
@@ -58,6 +59,28 @@ def main(N=48, T=24, seed=5):
         arrays["st_" + k] = getattr(st, k).numpy().copy()
     rh.save("rollout_gae", arrays, "dones", int(arrays["dones"].sum()), "time_outs", int(arrays["time_outs"].sum()),
             "adv mean/std", float(st.advantages.mean()), float(st.advantages.std()))
+    stats(seed)
+
+
+def stats(seed, T=6, N=5):
+    """rollout_stats.npz: what the reference's RolloutStorage.get_statistics (rollout_storage.py:140-146) returns for a handful of done
+    patterns; per pattern the dones and rewards put in and the (mean trajectory length, mean reward) that came out, both float32."""
+    from rsl_rl.storage import RolloutStorage
+    rng = np.random.default_rng(seed + 1)
+    patterns = dict(none=np.zeros((T, N, 1), np.uint8), all=np.ones((T, N, 1), np.uint8), last=np.zeros((T, N, 1), np.uint8),
+                    first=np.zeros((T, N, 1), np.uint8), random=(rng.random((T, N, 1)) < 0.3).astype(np.uint8))
+    patterns["last"][-1, 1::2] = 1
+    patterns["first"][0, ::2] = 1
+    arrays = {}
+    for name, dones in patterns.items():
+        rewards = (rng.normal(size=(T, N, 1)) * 0.05 + 0.02).astype(np.float32)
+        st = RolloutStorage(N, T, [3], [None], [2])
+        st.dones.copy_(torch.from_numpy(dones)); st.rewards.copy_(torch.from_numpy(rewards))
+        length, reward = st.get_statistics()
+        assert length.dtype == reward.dtype == torch.float32
+        arrays.update({f"{name}_dones": dones, f"{name}_rewards": rewards, f"{name}_length": length.numpy().copy(),
+                       f"{name}_reward": reward.numpy().copy()})
+    rh.save("rollout_stats", arrays, "mean lengths", *(float(arrays[f"{n}_length"]) for n in patterns))
 
 
 if __name__ == "__main__":
