@@ -17,6 +17,7 @@ from oracle import draw_map
 from oracle import mdp_oracle as mo
 from oracle.philox import philox4x32_10
 from tests import mdp_harness as h
+from tests import physics_harness as ph
 
 pytestmark = pytest.mark.gpu
 
@@ -118,8 +119,7 @@ PRODUCT = [
     ("go2_cat", {"LG_MDP_REPLICAS": "1"}, "lg_launch_env<LEGS, PR, 0, JPL, true>"),
 ]
 GATE_LAUNCHES = ("lg_launch_quad<4, true, LG_PHASE_POST, 0, 3>", "lg_launch_env<LEGS, LG_PHASE_RESET, 0, JPL, false>")
-PHYS_TOL = dict(base_pos=2e-5, base_quat=2e-5, base_lin_vel_w=2e-3, base_ang_vel_w=1e-2, dof_pos=2e-4, dof_vel=3e-2, torques=5e-3,
-                feet_pos=1e-4, feet_vel=2e-2)      # DESIGN.md section 2 (tests/test_gpu_physics.py TOL)
+PHYS_KEYS = ("base_pos", "base_quat", "base_lin_vel_w", "base_ang_vel_w", "dof_pos", "dof_vel", "torques", "feet_pos", "feet_vel")   # of ph.TOL
 MDP_ORACLE_LAYOUTS = (mo.abi.OBS_GO2, mo.abi.OBS_GO2_WTW, mo.abi.OBS_GO2_EE, mo.abi.OBS_TRON1_EE)   # go2, go2_wtw, go2_ee, tron1_pf_ee
 
 
@@ -251,16 +251,12 @@ def test_product_launch_draws_follow_the_map(case, monkeypatch):
         # ---- physics of the envs that did not reset against the f64 oracle from the same pre-step state
         orc.sim_step(eng.desc, eng.opts, hs, np.clip(act.cpu().numpy(), -ca, ca), "f64", threads=16, heightfield=hf)
         hs.arr["base_lin_vel_w"] += push                       # the push lands on the physics result (MdpOracle.step does the same)
-        bad = np.zeros(N, bool)
-        for k, tol in PHYS_TOL.items():
-            err = np.abs(post[k].reshape(N, -1) - hs.arr[k].reshape(N, -1)) > tol + 1e-4 * np.abs(hs.arr[k].reshape(N, -1))
-            bad |= err.any(1) & keep
         # on a heightfield a sample within round-off of a cell edge may fall in the neighbouring cell (0.5 % of
         # envs); on the plane one env per step may flip a contact or limit branch between f32 and f64 (deeply penetrating random states)
-        assert bad.sum() <= (0.005 * keep.sum() if hf is not None else 1), (name, int(bad.sum()), [
-            (k, float(np.abs(post[k].reshape(N, -1) - hs.arr[k].reshape(N, -1))[keep].max())) for k in PHYS_TOL])
+        rule, cap = (ph.ENV_SHARE, 0.005) if hf is not None else (ph.ENV_COUNT, 1)
+        off = ph.compare(post, hs.arr, PHYS_KEYS, rule=rule, cap=cap, envs=keep, joint=True, label=name)[ph.ANY]
         seen["phys"] += int(keep.sum())
-        seen["phys_off"] = seen.get("phys_off", 0) + int(bad.sum())
+        seen["phys_off"] = seen.get("phys_off", 0) + int(round(off * keep.sum()))
         # ---- callback command resampling (legged_robot.py:300-315) of envs that did not reset
         cb = keep & (post["episode_length_buf"] % task.resample_steps == 0) & (post["episode_length_buf"] > 0)
         seen["cb"] += int(cb.sum())

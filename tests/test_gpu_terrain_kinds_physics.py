@@ -6,12 +6,11 @@ import os
 import numpy as np
 import pytest
 
-from tests.test_gpu_physics import SIM_OUT, TOL
+from tests import physics_harness as ph
 
 pytestmark = pytest.mark.gpu
 
-G = os.path.join(os.path.dirname(__file__), "golden")
-EIGHT = [0.2, 0.1, 0.1, 0.1, 0.1, 0.2, 0.1, 0.1]
+G = ph.GOLDEN
 
 
 def _play_kwargs():
@@ -24,69 +23,11 @@ def _play_kwargs():
     return out
 
 
-def _eight_kind_map(cfg):
-    """Map (a): the go2_ee terrain with every kind in its own column, generated on the host and checked against its fixture."""
-    from hcr_genesis_lr_cl_amd.terrain import Terrain
-    g = np.load(os.path.join(G, "terrain_kinds_eight_curriculum.npz"))
-    cfg.terrain.terrain_proportions, cfg.terrain.curriculum, cfg.terrain.border_size = list(EIGHT), True, 20.0
-    np.random.seed(int(g["seed"]))
-    terrain = Terrain(cfg.terrain)
-    np.testing.assert_array_equal(terrain.height_field_raw, g["height_field_raw"])
-    return terrain
-
-
 @pytest.mark.parametrize("robot,layout", [("go2", 1), ("go2", 2), ("tron1_pf", 1), ("tron1_pf", 2)])
 def test_one_control_step_on_eight_kind_map_matches_oracle(robot, layout):
     """The heightfield contact on the new tiles against the unchanged f64 oracle, robots scattered over all 100 tiles and dropped onto
-    the local ground (into the holes and gaps as well); the same tolerance and outlier contract as
-    tests/test_gpu_physics.py::test_one_control_step_matches_oracle_other_configs."""
-    import torch
-    from hcr_genesis_lr_cl_amd import abi, builders
-    from hcr_genesis_lr_cl_amd.config import GO2EECfg, TRON1PFEECfg
-    from hcr_genesis_lr_cl_amd.engine import Engine
-    from hcr_genesis_lr_cl_amd.model_compiler import load_model
-    from oracle import oracle as orc
-    from oracle import mdp_oracle as mo
-    from tests.util import random_sim_state, load_state_into_engine, engine_arrays
-    cfg = {"go2": GO2EECfg, "tron1_pf": TRON1PFEECfg}[robot]()
-    cfg.hip.sim_layout = layout
-    terrain = _eight_kind_map(cfg)
-    model = load_model(robot)
-    desc, opts, task = builders.make_model_desc(model, cfg), builders.make_sim_options(model, cfg, terrain), builders.make_task_cfg(model, cfg)
-    eng = Engine(model, desc, opts, task, 512, "cuda:0")
-    hx, hy = np.meshgrid(cfg.terrain.measured_points_x, cfg.terrain.measured_points_y, indexing="ij")
-    eng.set_terrain(terrain.height_field_raw, terrain.env_origins, np.stack([hx.ravel(), hy.ravel()], 1).astype(np.float32))
-    st, actions = random_sim_state(model, cfg, eng.n, 4)
-    rng = np.random.default_rng(8)
-    tiles = terrain.env_origins.reshape(-1, 3)
-    pick = tiles[rng.permutation(np.arange(eng.n) % len(tiles))]            # every tile gets robots
-    st.arr["base_pos"][:, :2] = pick[:, :2] + rng.uniform(-3, 3, (eng.n, 2))
-    st.arr["env_origins"][:] = pick
-    h = mo.sample_heights(st.arr["base_pos"], np.tile([0, 0, 0, 1.0], (eng.n, 1)).astype(np.float32), np.zeros((1, 2), np.float32),
-                          terrain.height_field_raw, cfg.terrain.border_size, cfg.terrain.horizontal_scale, cfg.terrain.vertical_scale)
-    st.arr["base_pos"][:, 2] += h[:, 0]
-    assert (h[:, 0] < -9.0).any()                                            # some robots really stand in the stepping-stone holes
-    if robot == "tron1_pf":
-        st.arr["joint_armature"] = np.random.default_rng(1).uniform(0.11, 0.13, (eng.n, 1)).astype(np.float32)
-        st.arr["joint_friction"] = np.random.default_rng(2).uniform(0.0, 0.01, (eng.n, 1)).astype(np.float32)
-        st.arr["joint_damping"] = np.random.default_rng(3).uniform(1.4, 1.45, (eng.n, 1)).astype(np.float32)
-    load_state_into_engine(eng, st)
-    eng.step(abi.PHASE_SIM, torch.from_numpy(actions).cuda(), 0)
-    orc.sim_step(desc, opts, st, actions, "f64", threads=8, heightfield=terrain.height_field_raw)
-    got = engine_arrays(eng, SIM_OUT)
-    shares = {}
-    for k in SIM_OUT:
-        ref = st.arr[k].reshape(eng.n, -1)
-        assert np.all(np.isfinite(got[k])), k
-        if k == "link_contact_forces":
-            err = np.abs(got[k] - ref)
-            ok = err <= 0.3 + 0.01 * np.abs(ref)
-            shares[k] = 1.0 - ok.mean()
-            assert ok.mean() > 0.995, (k, (~ok).sum(), err.max())
-        else:
-            bad = ~np.isclose(got[k], ref, atol=TOL[k] * 3, rtol=1e-4)
-            shares[k] = bad.mean()
-            assert bad.mean() <= 5e-3, (k, bad.sum(), np.abs(got[k] - ref).max())
+    the local ground (into the holes and gaps as well); the tolerance and outlier contract of the rough-terrain cases."""
+    shares = ph.run_case(ph.CASES[f"{robot}-eight-kind"], layout, ph.EngineStepper)
     print(f"{robot} layout {layout}: worst outlier share {max(shares.values()):.4%} ({max(shares, key=shares.get)})")
 
 
@@ -114,7 +55,7 @@ def test_random_rollout_on_eight_kind_map_stays_sane(task):
     """4096 envs, 150 control steps of random actions on map (a)'s proportions: nothing non-finite, nobody thrown upward (falling
     into a 10 m hole legitimately reaches about 14 m/s downward)."""
     import torch
-    env, cfg = _make(task, 4096, terrain_proportions=list(EIGHT))
+    env, cfg = _make(task, 4096, terrain_proportions=list(ph.EIGHT))
     t = env.simulator._terrain
     assert t.heightsamples_dev is not None and int(t.height_field_raw.min()) == -2000 and (t.height_field_raw == -1000).any()
     env.reset()

@@ -8,6 +8,7 @@ import pytest
 
 from oracle import oracle as orc
 from hcr_genesis_lr_cl_amd import config as cfgmod
+from tests.physics_harness import momentum
 
 
 def _state(go2, n=1, h=0.42):
@@ -49,40 +50,6 @@ def test_free_fall_closed_form(go2):
     np.testing.assert_allclose(st.arr["base_ang_vel_w"], 0, atol=1e-5)
 
 
-def _momentum(model, st, e=0):
-    """Linear + angular momentum about the world origin from the state (independent FK in numpy)."""
-    a = model.arrays
-    from hcr_genesis_lr_cl_amd.model_compiler import _sym
-    def qmat(q):
-        x, y, z, w = q
-        return np.array([[1-2*(y*y+z*z), 2*(x*y-z*w), 2*(x*z+y*w)], [2*(x*y+z*w), 1-2*(x*x+z*z), 2*(y*z-x*w)],
-                         [2*(x*z-y*w), 2*(y*z+x*w), 1-2*(x*x+y*y)]])
-    def rod(u, t):
-        K = np.array([[0, -u[2], u[1]], [u[2], 0, -u[0]], [-u[1], u[0], 0]])
-        return np.eye(3) + np.sin(t) * K + (1 - np.cos(t)) * K @ K
-    s = {k: v[e].astype(np.float64) for k, v in st.arr.items()}
-    R, P = [qmat(s["base_quat"])], [s["base_pos"]]
-    W, V = [s["base_ang_vel_w"]], [s["base_lin_vel_w"]]
-    nb = int(a["mass"].shape[0])
-    for i in range(1, nb):
-        p = int(a["parent"][i])
-        Rpc = a["jrot"][i].reshape(3, 3) @ rod(a["axis"][i], s["dof_pos"][i - 1])
-        R.append(R[p] @ Rpc)
-        Pi = P[p] + R[p] @ a["jpos"][i]
-        P.append(Pi)
-        V.append(V[p] + np.cross(W[p], Pi - P[p]))
-        W.append(W[p] + R[i] @ a["axis"][i] * s["dof_vel"][i - 1])
-    lin, ang, mtot, com = np.zeros(3), np.zeros(3), 0.0, np.zeros(3)
-    for i in range(nb):
-        c = P[i] + R[i] @ a["com"][i]
-        vc = V[i] + np.cross(W[i], c - P[i])
-        Iw = R[i] @ _sym(a["inertia"][i]) @ R[i].T
-        lin += a["mass"][i] * vc
-        ang += Iw @ W[i] + a["mass"][i] * np.cross(c, vc)
-        mtot += a["mass"][i]; com += a["mass"][i] * c
-    return lin, ang, com / mtot
-
-
 def test_zero_gravity_momentum_conserved_under_internal_torques(go2):
     """Internal torques cannot change total momentum: d/dt(p, h) = 0 instantaneously.  A first-order
     integrator keeps that to O(dt^2) per step, so the one-step drift must fall ~100x when dt
@@ -99,9 +66,9 @@ def test_zero_gravity_momentum_conserved_under_internal_torques(go2):
         st.arr["dof_vel"][:] = r2.normal(size=12)
         st.arr["base_pos"][:, :2] = 0
         act = r2.normal(size=(1, 12)).astype(np.float32)
-        l0, a0, c0 = _momentum(go2["model"], st)
+        l0, a0, c0 = momentum(go2["model"], st)
         orc.sim_step(go2["desc"], opts, st, act, "f64")
-        l1, a1, c1 = _momentum(go2["model"], st)
+        l1, a1, c1 = momentum(go2["model"], st)
         drift.append((np.linalg.norm(l1 - l0), np.linalg.norm(a1 - a0)))
     assert drift[0][0] < 5e-3 and drift[0][1] < 5e-3
     # f32 state I/O floors the smaller-dt drift at ~1e-6

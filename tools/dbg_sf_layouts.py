@@ -1,30 +1,23 @@
 """Diagnostic: tron1_sf physics, component-per-lane vs leg-per-lane kernel on the same states (airborne, then with contacts)."""
 import os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
-import copy
-import numpy as np, torch
-from hcr_genesis_lr_cl_amd import builders, abi
-from hcr_genesis_lr_cl_amd.config import TRON1SFCfg
-from hcr_genesis_lr_cl_amd.engine import Engine
-from hcr_genesis_lr_cl_amd.model_compiler import load_model
-from tests.util import random_sim_state, load_state_into_engine, engine_arrays
-OUT = ["base_pos", "base_quat", "base_lin_vel_w", "base_ang_vel_w", "dof_pos", "dof_vel", "torques", "link_contact_forces", "feet_pos", "feet_vel"]
-model, cfg = load_model("tron1_sf"), TRON1SFCfg()
-desc, task = builders.make_model_desc(model, cfg), builders.make_task_cfg(model, cfg)
-engs = []
-for lay in (1, 2):
-    c = TRON1SFCfg(); c.hip.sim_layout = lay
-    engs.append(Engine(model, desc, builders.make_sim_options(model, c), task, 256, "cuda:0"))
-for name, zoff, dec in (("airborne", 2.0, None), ("contacts", 0.0, None)):
-    st, actions = random_sim_state(model, cfg, 256, 4, z_offset=zoff)
+import dataclasses
+import numpy as np
+from tests import physics_harness as ph
+OUT = ph.SIM_OUT[:10]          # up to feet_vel
+case = ph.PhysicsCase("tron1_sf", "TRON1SFCfg", n=256)
+builts = [ph.build(case, lay) for lay in ph.LAYOUTS]
+engs = [ph.EngineStepper(b, case.n) for b in builts]
+for name, zoff in (("airborne", 2.0), ("contacts", 0.0)):
+    st, actions = ph.initial_state(dataclasses.replace(case, z_offset=zoff), builts[0])
     st.arr["joint_armature"] = np.full((256, 1), 0.12, np.float32)
     st.arr["joint_friction"] = np.full((256, 1), 0.005, np.float32)
     st.arr["joint_damping"] = np.full((256, 1), 1.4, np.float32)
     res = []
     for e in engs:
-        load_state_into_engine(e, st)
-        e.step(abi.PHASE_SIM, torch.from_numpy(actions).cuda(), 0)
-        res.append(engine_arrays(e, OUT))
+        e.load(st)
+        e.step(actions)
+        res.append(e.arrays(OUT))
     print("==", name)
     for k in OUT:
         d = np.abs(res[0][k] - res[1][k])
