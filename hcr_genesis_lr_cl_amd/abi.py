@@ -273,6 +273,8 @@ def load_lib():
     lib.lg_rollout_mask_index.argtypes = [i32, i32, vp, vp, i32, vp, vp]
     lib.lg_rollout_pad.argtypes = [i32, i32, vp, i32, i32, i32, C.POINTER(LgRowCopy), i32, C.POINTER(LgRowCopy), C.POINTER(i32), i32, vp, vp]
     lib.lg_rollout_unpad.argtypes = [i32, i32, vp, i32, i32, i32, vp, vp, i32, vp]
+    lib.lg_rollout_gather.argtypes = [C.POINTER(LgGatherItem), i32, vp]
+    lib.lg_rollout_gae_groups.argtypes = [i32, i32, i32, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp]
     for f in ROLLOUT_EXPORTS[2:]:
         getattr(lib, f).restype = C.c_int
     lib.lg_last_error.restype = C.c_char_p
@@ -290,8 +292,10 @@ EXPORTS = ["lg_create", "lg_destroy", "lg_set_task", "lg_set_terrain", "lg_bind"
            "lg_time_steps", "lg_obs_window", "lg_obs_set", "lg_obs_set_select", "lg_obs_window_select", "lg_profile", "lg_profile_read", "lg_philox", "lg_dpp_kat", "lg_dpp_kat_cases", "lg_dpp_kat_run", "lg_stream_copy", "lg_terrain_generate", "lg_terrain_max_kind", "lg_last_kernel", "lg_last_error",
            "lg_abi_version"]
 ROLLOUT_EXPORTS = ["lg_rollout_record", "lg_rollout_gae", "lg_rollout_traj_index", "lg_rollout_mask_index", "lg_rollout_pad",
-                   "lg_rollout_unpad"]          # include/lgrollout.h
+                   "lg_rollout_unpad", "lg_rollout_gather", "lg_rollout_gae_groups"]          # include/lgrollout.h
 ROLLOUT_MAX_COPIES = 8
+ROLLOUT_MAX_GATHER = 16
+GATHER_F32, GATHER_NOT_U8 = 0, 1
 
 
 TILE_SLOPE, TILE_UNIFORM, TILE_STAIRS, TILE_OBSTACLES = 0, 1, 2, 3
@@ -305,6 +309,11 @@ class LgTerrainTile(C.Structure):
 
 class LgRowCopy(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("width", i32), ("src_stride", i32)]
+
+
+class LgGatherItem(C.Structure):
+    _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("index", C.c_void_p), ("rows", i32), ("width", i32), ("src_stride", i32),
+                ("kind", i32), ("group", i32), ("env_offset", i32), ("n_envs", i32)]
 
 
 def check(rc, lib=None):

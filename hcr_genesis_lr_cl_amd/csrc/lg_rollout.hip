@@ -421,3 +421,145 @@ extern "C" int lg_rollout_unpad(int32_t n_steps, int32_t n_envs, const int32_t *
     if (e != hipSuccess) return lg_fail_msg(std::string("lg_rollout_unpad: ") + hipGetErrorString(e));
     return 0;
 }
+
+// ---- mini-batches: every tensor of one mini-batch gathered in one launch -------------------------------------------------------------
+// Reference call sites replaced: the 9 index gathers per mini-batch of rollout_storage.py:170-186 and the 11 to 16 of rollout_storage_ee.py:
+// 141-151, _ts.py:103-114, _dreamwaq.py:108-120 and _cts.py:160-177 (with the `[:, a:b].flatten(0, 1)` copies of _cts.py:126-140, made on
+// every call).  blockIdx.y is the item; within an item the flat index runs over the destination, consecutive lanes on consecutive floats
+// of a row, so every destination element is written once and a row of the source is read by neighbouring lanes.
+struct GatherArgs {
+    LgGatherItem it[LG_ROLLOUT_MAX_GATHER];
+    FastDiv by_w[LG_ROLLOUT_MAX_GATHER], by_group[LG_ROLLOUT_MAX_GATHER];    // by_w per element type (float or float4)
+    unsigned vec;                                                            // bit i: item i moves float4
+};
+
+__device__ inline void load_of(float &v, const float *src, size_t at) { v = src[at]; }
+__device__ inline void load_of(float4 &v, const float4 *src, size_t at) { v = src[at]; }
+__device__ inline void load_of(float &v, const uint8_t *src, size_t at) { v = 1.0f - (float)src[at]; }
+
+// S: the source's element type, V: what moves (float4 only with S = float4)
+template <typename S, typename V> __device__ inline void gather_item(const LgGatherItem &c, FastDiv by_w, FastDiv by_group) {
+    constexpr unsigned W = sizeof(V) / sizeof(float);
+    const unsigned dv = (unsigned)c.width / W, sv = (unsigned)c.src_stride / W, tot = (unsigned)c.rows * dv;
+    const unsigned stride = gridDim.x * blockDim.x, group = (unsigned)c.group;
+    const bool plain = c.group == c.n_envs;                                   // env_offset is 0 then: the index is the source row
+    const S *__restrict__ src = (const S *)c.src;
+    V *__restrict__ dst = (V *)c.dst;
+    const int64_t *__restrict__ index = c.index;
+    for (unsigned i = blockIdx.x * blockDim.x + threadIdx.x; i < tot; i += stride) {
+        const unsigned j = div_by(i, by_w), k = i - j * dv;
+        unsigned r = (unsigned)index[j];
+        if (!plain) { const unsigned t = div_by(r, by_group); r = t * (unsigned)c.n_envs + (unsigned)c.env_offset + (r - t * group); }
+        V v;
+        load_of(v, src, (size_t)r * sv + k);
+        dst[i] = v;
+    }
+}
+
+__global__ __launch_bounds__(256) void rollout_gather_kernel(GatherArgs a) {
+    const int s = blockIdx.y;
+    const LgGatherItem &c = a.it[s];
+    if (c.kind == LG_GATHER_NOT_U8) gather_item<uint8_t, float>(c, a.by_w[s], a.by_group[s]);
+    else if (a.vec >> s & 1) gather_item<float4, float4>(c, a.by_w[s], a.by_group[s]);
+    else gather_item<float, float>(c, a.by_w[s], a.by_group[s]);
+}
+
+extern "C" int lg_rollout_gather(const LgGatherItem *items, int32_t n_items, void *stream) {
+    if (!items || n_items < 1 || n_items > LG_ROLLOUT_MAX_GATHER) return lg_fail_msg("lg_rollout_gather: bad item list (null, empty or more than 16 items)");
+    GatherArgs a;
+    a.vec = 0;
+    long long most = 0;
+    for (int i = 0; i < n_items; i++) {
+        const LgGatherItem &c = items[i];
+        const std::string at = "lg_rollout_gather: item " + std::to_string(i) + ": ";
+        if (c.rows > 0 && (!c.src || !c.dst || !c.index)) return lg_fail_msg(at + "null pointer");
+        if (c.width < 1 || c.src_stride < c.width) return lg_fail_msg(at + "width < 1 or stride < width");
+        if (c.kind != LG_GATHER_F32 && c.kind != LG_GATHER_NOT_U8) return lg_fail_msg(at + "unknown kind");
+        if (c.group < 1 || c.env_offset < 0 || (long long)c.env_offset + c.group > c.n_envs) return lg_fail_msg(at + "env window outside the envs (group < 1 or env_offset + group > n_envs)");
+        if (c.rows < 0) return lg_fail_msg(at + "rows < 0");
+        if ((long long)c.rows * c.width > kMaxFlat) return lg_fail_msg(at + "destination of 2^31 elements or more");
+        a.it[i] = c;
+        const bool vec = c.kind == LG_GATHER_F32 && c.width % 4 == 0 && c.src_stride % 4 == 0 && aligned16(c.src) && aligned16(c.dst);
+        if (vec) a.vec |= 1u << i;
+        a.by_w[i] = fast_div((unsigned)c.width / (vec ? 4 : 1));
+        a.by_group[i] = fast_div((unsigned)c.group);
+        const long long tot = (long long)c.rows * c.width / (vec ? 4 : 1);
+        if (tot > most) most = tot;
+    }
+    if (most == 0) return 0;                              // every item empty: nothing to write
+    unsigned blocks = grid_for(most);
+    if (blocks > 1024) blocks = 1024;                     // x 16 items: enough lanes in flight to cover the gathers' latency
+    hipLaunchKernelGGL(rollout_gather_kernel, dim3(blocks, (unsigned)n_items), dim3(256), 0, (hipStream_t)stream, a);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return lg_fail_msg(std::string("lg_rollout_gather: ") + hipGetErrorString(e));
+    return 0;
+}
+
+// ---- GAE for two groups of envs (rollout_storage_cts.py:81-114): gae_kernel with the raw advantages split and a (sum, sum of squares)
+// pair per group; a block may hold envs of both groups, so every lane carries both pairs (one of them zero) through the reduction.
+__global__ __launch_bounds__(256) void gae_groups_kernel(int T, int N, int n_first, const float *__restrict__ values, const float *__restrict__ rewards,
+                                                         const uint8_t *__restrict__ dones, const float *__restrict__ last_values, float gamma,
+                                                         float lam, float *__restrict__ returns, float *__restrict__ adv_first,
+                                                         float *__restrict__ adv_rest, double *scratch) {
+    const int e = blockIdx.x * blockDim.x + threadIdx.x;
+    double s[4] = {0.0, 0.0, 0.0, 0.0};
+    if (e < N) {
+        const bool first = e < n_first;
+        float *__restrict__ out = first ? adv_first : adv_rest;
+        const int n = first ? n_first : N - n_first, col = first ? e : e - n_first;
+        double s1 = 0.0, s2 = 0.0;
+        float adv = 0.f, next_v = last_values[e];
+        for (int t = T - 1; t >= 0; t--) {
+            const size_t i = (size_t)t * N + e;
+            const float v = values[i];
+            const float nt = 1.0f - (float)dones[i];
+            const float delta = rewards[i] + nt * gamma * next_v - v;
+            adv = delta + nt * gamma * lam * adv;
+            const float ret = adv + v;
+            returns[i] = ret;
+            const float a = ret - v;                       // rollout_storage_cts.py:96 / :113: returns - values, as in gae_kernel
+            out[(size_t)t * n + col] = a;
+            s1 += (double)a; s2 += (double)a * (double)a;
+            next_v = v;
+        }
+        s[0] = first ? s1 : 0.0; s[1] = first ? s2 : 0.0; s[2] = first ? 0.0 : s1; s[3] = first ? 0.0 : s2;
+    }
+    for (int off = 32; off > 0; off >>= 1)
+        for (int q = 0; q < 4; q++) s[q] += __shfl_down(s[q], off, 64);
+    __shared__ double sh[4][4];
+    const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
+    if (l == 0)
+        for (int q = 0; q < 4; q++) sh[q][w] = s[q];
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        double acc = 0.0;
+        for (int k = 0; k < (int)(blockDim.x >> 6); k++) acc += sh[threadIdx.x][k];
+        atomicAdd(&scratch[threadIdx.x], acc);
+    }
+}
+
+extern "C" int lg_rollout_gae_groups(int32_t n_steps, int32_t n_envs, int32_t n_first, const float *values, const float *rewards, const uint8_t *dones,
+                                     const float *last_values, float gamma, float lam, float *returns, float *adv_first, float *adv_rest,
+                                     double *scratch, void *stream) {
+    if (n_steps < 1 || n_envs < 1 || !values || !rewards || !dones || !last_values || !returns || !adv_first || !adv_rest || !scratch)
+        return lg_fail_msg("lg_rollout_gae_groups: null / empty argument");
+    if (n_first < 1 || n_first >= n_envs) return lg_fail_msg("lg_rollout_gae_groups: n_first outside [1, n_envs - 1]");
+    const long long tot_first = (long long)n_steps * n_first, tot_rest = (long long)n_steps * (n_envs - n_first);
+    if (tot_first < 2 || tot_rest < 2) return lg_fail_msg("lg_rollout_gae_groups: the normalisation needs at least two entries per group");
+    hipStream_t st = (hipStream_t)stream;
+    hipError_t e = hipMemsetAsync(scratch, 0, 4 * sizeof(double), st);
+    if (e != hipSuccess) return lg_fail_msg(std::string("lg_rollout_gae_groups: ") + hipGetErrorString(e));
+    const int block = 256;
+    hipLaunchKernelGGL(gae_groups_kernel, dim3((n_envs + block - 1) / block), dim3(block), 0, st, n_steps, n_envs, n_first, values, rewards, dones,
+                       last_values, gamma, lam, returns, adv_first, adv_rest, scratch);
+    const long long tots[2] = {tot_first, tot_rest};
+    float *const advs[2] = {adv_first, adv_rest};
+    for (int g = 0; g < 2; g++) {
+        long long blocks = (tots[g] + block - 1) / block;
+        if (blocks > 2048) blocks = 2048;
+        hipLaunchKernelGGL(adv_normalize_kernel, dim3((unsigned)blocks), dim3(block), 0, st, tots[g], advs[g], scratch + 2 * g);
+    }
+    e = hipGetLastError();
+    if (e != hipSuccess) return lg_fail_msg(std::string("lg_rollout_gae_groups: ") + hipGetErrorString(e));
+    return 0;
+}

@@ -15,7 +15,17 @@ are filled and how the recurrent mini-batches are cut:
   * `reccurent_mini_batch_generator`: the trajectory split of rsl_rl/utils/utils.py:33-65 (every length to the host, one tensor per
     trajectory, pad_sequence) and the per-mini-batch sum / boolean gather of rollout_storage.py:203-228 become one index launch
     (`lg_rollout_traj_index`), one small read-back and one launch (`lg_rollout_pad`) that writes the padded observations, the masks and
-    the start hidden states of every trajectory; `unpad_trajectories` is the inverse (`lg_rollout_mask_index` + `lg_rollout_unpad`).
+    the start hidden states of every trajectory; `unpad_trajectories` is the inverse (`lg_rollout_mask_index` + `lg_rollout_unpad`);
+  * `mini_batch_generator`: the nine index gathers per mini-batch of rollout_storage.py:170-186 are ONE launch (`lg_rollout_gather`) that
+    writes every tensor of the mini-batch, indexed by the int64 permutation as torch.randperm gives it.
+
+`RolloutStorageEE`, `RolloutStorageTS`, `RolloutStorageCTS` and `RolloutStorageDreamWaQ` mirror the storages that the reference's PPO_EE,
+PPO_TS, PPO_CTS and PPO_DreamWaQ build (rsl_rl/storage/rollout_storage_ee.py, _ts.py, _cts.py, _dreamwaq.py): the reference's constructor
+arguments in its order, its tensors and Transition attributes, and generators that yield its tuples of 13 / 14 / 18 / 15 entries -- each
+from one gather launch, `terminated = 1 - dones` formed by the kernel, CTS's teacher and student halves read in place from the
+(T, N, width) rows through an env window and its three index sets served together.  Their env-side rows go out with reward and done in the
+one record launch, through `add_transitions` or through `add_step` with the rows as keywords; CTS computes its returns and the two
+separately normalised advantage tensors with `lg_rollout_gae_groups`.
 
 There is no CPU path: the kernels live in csrc/liblgsim.so (include/lgrollout.h)."""
 from __future__ import annotations
@@ -68,7 +78,7 @@ class RolloutStorage:
         self.observations = None
         if env is not None:
             self.attach_env(env)
-        if self.observations is None:
+        if self.observations is None and obs_shape is not None:          # RolloutStorageEE stores no actor observations
             self.observations = z(T, N, *obs_shape)
         self.privileged_observations = z(T, N, *privileged_obs_shape) if privileged_obs_shape[0] is not None else None
         self.rewards = z(T, N, 1)
@@ -171,15 +181,18 @@ class RolloutStorage:
         if dones.dtype not in (torch.bool, torch.uint8) or not dones.is_contiguous():
             dones = dones.to(torch.uint8).contiguous()
         self._env_row("rewards", rew, (torch.float32,)), self._env_row("dones", dones, (torch.bool, torch.uint8))   # before any row is written
+        rows = self._transition_rows(transition)
         self.actions[t].copy_(transition.actions)
         self.values[t].copy_(transition.values)
         self.actions_log_prob[t].copy_(transition.actions_log_prob.view(-1, 1))
         self.mu[t].copy_(transition.action_mean)
         self.sigma[t].copy_(transition.action_sigma)
+        self.add_step(rew, dones, None, 0.0, hidden_states=getattr(transition, "hidden_states", None), **rows)
+
+    def _transition_rows(self, transition):
+        """The env-side rows of `transition` as keywords of `add_step`; the storages of the other learners name their own rows here."""
         crit = transition.critic_observations if self.privileged_observations is not None else None
-        self.add_step(rew, dones, None, 0.0,
-                      observations=transition.observations, critic_observations=crit,
-                      hidden_states=getattr(transition, "hidden_states", None))
+        return dict(observations=transition.observations, critic_observations=crit)
 
     def _hidden_copies(self, t, hidden_states):
         """Row copies that store a recurrent policy's hidden states at step t (rollout_storage.py:104-119).  None or (None, None): nothing
@@ -235,15 +248,54 @@ class RolloutStorage:
         """Mini-batches in the tuple order rsl_rl's PPO.update unpacks (rollout_storage.py:148-186): obs, critic obs, actions, target
         values, advantages, returns, old log-prob, old mean, old std, hidden states (None, None), masks None.  One random permutation of
         the T x N samples per call, cut into `num_mini_batches` equal index blocks and replayed every epoch."""
-        flat = {k: getattr(self, k).flatten(0, 1) for k in
-                ("observations", "actions", "values", "advantages", "returns", "actions_log_prob", "mu", "sigma")}
-        flat["critic"] = self.privileged_observations.flatten(0, 1) if self.privileged_observations is not None else flat["observations"]
-        order = ("observations", "critic", "actions", "values", "advantages", "returns", "actions_log_prob", "mu", "sigma")
+        critic = "privileged_observations" if self.privileged_observations is not None else "observations"
+        names = ("observations", critic, "actions", "values", "advantages", "returns", "actions_log_prob", "mu", "sigma")
         per = (self.num_envs * self.num_transitions_per_env) // num_mini_batches
-        blocks = torch.randperm(num_mini_batches * per, device=self.device).view(num_mini_batches, per)
+        perm = torch.randperm(num_mini_batches * per, device=self.device)
+        for batch in self._gather_batches([(getattr(self, k), abi.GATHER_F32, 0, None) for k in names], [(perm, per)], num_mini_batches, num_epochs):
+            yield (*batch, (None, None), None)
+
+    def _gather_batches(self, entries, index_sets, num_mini_batches, num_epochs):
+        """The tensors of every mini-batch, one `lg_rollout_gather` launch per mini-batch.  `entries`: (source, kind, index set, window) per
+        yielded tensor; the source is a (T, n, ...) tensor with contiguous rows, `window` is None (index r is row r of source.flatten(0, 1))
+        or (first env, envs): index r is row r of source[:, first:first + envs].flatten(0, 1), read in place.  `index_sets`: (permutation
+        int64, rows per mini-batch); mini-batch i takes entries [i * rows, (i + 1) * rows) of each, and every epoch replays them.  Yields
+        lists of freshly allocated contiguous float32 tensors (rows, ...): nothing is shared between yields."""
+        if len(entries) > abi.ROLLOUT_MAX_GATHER:
+            raise ValueError(f"a mini-batch of {len(entries)} tensors: one gather launch takes {abi.ROLLOUT_MAX_GATHER}")
+        dev = self.device
+        arr = (abi.LgGatherItem * len(entries))()
+        shapes = []
+        for it, (x, kind, k, window) in zip(arr, entries):
+            want = torch.uint8 if kind == abi.GATHER_NOT_U8 else torch.float32
+            n = x.shape[1] if x.dim() >= 2 else 0
+            stride = 0 if n == 0 else (x.stride(1) if n > 1 else x.stride(0))
+            width = x[0, 0].numel() if n else 0
+            if (n == 0 or x.dtype != want or x.device != dev or width < 1 or not x[0, 0].is_contiguous() or stride < width
+                    or (x.shape[0] > 1 and n > 1 and x.stride(0) != n * stride)):
+                raise ValueError(f"mini-batch sources are (T, envs, ...) {want} tensors on {dev} with contiguous rows and one row stride, got "
+                                 f"{tuple(x.shape)} {x.dtype} strides {x.stride()} on {x.device}")
+            first, group = (0, n) if window is None else window
+            perm, rows = index_sets[k]
+            if perm.dtype != torch.int64 or not perm.is_contiguous() or perm.device != dev or perm.numel() < num_mini_batches * rows:
+                raise ValueError("mini-batch index sets are contiguous int64 tensors on the storage's device")
+            it.src, it.rows, it.width, it.src_stride, it.kind = x.data_ptr(), rows, width, stride, kind
+            it.group, it.env_offset, it.n_envs = group, first, n
+            shapes.append((rows, *x.shape[2:]))
+        if all(rows == 0 for _, rows in index_sets):                  # more mini-batches than samples: empty batches, as indexing gives
+            for _ in range(num_epochs * num_mini_batches):
+                yield [torch.empty(sh, device=dev) for sh in shapes]
+            return
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        gather, lib, n_items = self.lib.lg_rollout_gather, self.lib, len(entries)
+        bases = [index_sets[k][0].data_ptr() for _, _, k, _ in entries]
         for _ in range(num_epochs):
-            for b in blocks:
-                yield (*(flat[k][b] for k in order), (None, None), None)
+            for i in range(num_mini_batches):
+                out = [torch.empty(sh, device=dev) for sh in shapes]
+                for it, o, base in zip(arr, out, bases):
+                    it.dst, it.index = o.data_ptr(), base + 8 * i * it.rows
+                abi.check(gather(arr, n_items, stream), lib)
+                yield out
 
     # ---- recurrent policies ---------------------------------------------------------------------------------------------
     def trajectory_index(self):
@@ -329,6 +381,198 @@ class RolloutStorage:
                 yield (padded_obs[:, first:last], padded_critic[:, first:last], self.actions[:, start:stop], self.values[:, start:stop],
                        self.advantages[:, start:stop], self.returns[:, start:stop], self.actions_log_prob[:, start:stop],
                        self.mu[:, start:stop], self.sigma[:, start:stop], (hid_a, hid_c), masks[:, first:last])
+
+
+class _LearnerStorage(RolloutStorage):
+    """What the storages of the explicit-estimator, teacher-student, CTS and DreamWaQ learners share: their env-side rows named in a table,
+    a fused `add_step` that takes them as keywords, and a mini-batch generator that is one gather launch per yield."""
+
+    STEP_ROWS = ()          # (add_step keyword = Transition attribute, storage tensor), in the order of the reference's add_transitions
+    BATCH = ()              # (storage tensor, gather kind) in the order the learner's update() unpacks, before `(None, None), None`
+
+    def add_step(self, rew, reset, time_outs, gamma, extra_copies=(), hidden_states=None, **rows):
+        """RolloutStorage.add_step with this learner's rows as keywords (the names in STEP_ROWS, each an (N, width) float32 tensor): reward,
+        done and every row in the one record launch.  More rows than the launch takes is a ValueError before anything is enqueued."""
+        t = self.step
+        if t >= self.num_transitions_per_env:
+            raise AssertionError("Rollout buffer overflow")
+        known = dict(self.STEP_ROWS)
+        copies = []
+        for k, src in rows.items():
+            if k not in known:
+                raise TypeError(f"{type(self).__name__}.add_step: unknown row {k!r}; expected one of {', '.join(known)}")
+            dst = getattr(self, known[k])
+            if src is not None and dst is not None:
+                copies.append((src, dst[t]))
+        copies += list(extra_copies)
+        n = len(copies) + self._hidden_count(hidden_states)
+        if n > abi.ROLLOUT_MAX_COPIES:
+            raise ValueError(f"{type(self).__name__}.add_step: {n} row copies in one step, the record launch takes {abi.ROLLOUT_MAX_COPIES}")
+        RolloutStorage.add_step(self, rew, reset, time_outs, gamma, extra_copies=copies, hidden_states=hidden_states)
+
+    @staticmethod
+    def _hidden_count(hidden_states):
+        """How many row copies `_hidden_copies` will ask for, without allocating anything."""
+        if hidden_states is None or (hidden_states[0] is None and hidden_states[1] is None):
+            return 0
+        return sum(len(h) if isinstance(h, (tuple, list)) else 1 for h in hidden_states)
+
+    def _transition_rows(self, transition):
+        rows = {k: getattr(transition, k) for k, _ in self.STEP_ROWS}
+        n = sum(v is not None and getattr(self, dst) is not None for (_, dst), v in zip(self.STEP_ROWS, rows.values()))
+        n += self._hidden_count(getattr(transition, "hidden_states", None))
+        if n > abi.ROLLOUT_MAX_COPIES:
+            raise ValueError(f"{type(self).__name__}.add_transitions: {n} row copies in one step, the record launch takes {abi.ROLLOUT_MAX_COPIES}")
+        return rows
+
+    def _batch_source(self, name):
+        return getattr(self, name)
+
+    def mini_batch_generator(self, num_mini_batches, num_epochs=8):
+        """The learner's tuple (BATCH, then `(None, None), None`): one random permutation of the T x N samples per call, cut into
+        `num_mini_batches` equal index blocks and replayed every epoch; each yield is one gather launch into fresh tensors."""
+        per = (self.num_envs * self.num_transitions_per_env) // num_mini_batches
+        perm = torch.randperm(num_mini_batches * per, device=self.device)
+        entries = [(self._batch_source(name), kind, 0, None) for name, kind in self.BATCH]
+        for batch in self._gather_batches(entries, [(perm, per)], num_mini_batches, num_epochs):
+            yield (*batch, (None, None), None)
+
+
+_F32, _NOT = abi.GATHER_F32, abi.GATHER_NOT_U8
+_PPO_BATCH = (("actions", _F32), ("values", _F32), ("advantages", _F32), ("returns", _F32), ("actions_log_prob", _F32), ("mu", _F32), ("sigma", _F32))
+
+
+class RolloutStorageEE(_LearnerStorage):
+    """rsl_rl/storage/rollout_storage_ee.py (PPO_EE, the explicit estimator): no actor observations are stored; the actor's input is the
+    estimator features and labels.  `add_step` keywords: critic_observations, estimator_features, estimator_labels.  Mini-batches are the
+    13 entries of rollout_storage_ee.py:152-154; `terminated` is float32 1 - dones, formed by the gather."""
+
+    class Transition(RolloutStorage.Transition):
+        def __init__(self):
+            super().__init__()
+            self.estimator_features = None
+            self.estimator_labels = None
+
+    STEP_ROWS = (("critic_observations", "privileged_observations"), ("estimator_features", "estimator_features"), ("estimator_labels", "estimator_labels"))
+    BATCH = (("critic", _F32), ("estimator_features", _F32), ("estimator_labels", _F32), ("dones", _NOT)) + _PPO_BATCH
+
+    def __init__(self, num_envs, num_transitions_per_env, privileged_obs_shape, estimator_feature_shape, estimator_label_shape, actions_shape,
+                 device="cuda:0"):
+        super().__init__(num_envs, num_transitions_per_env, None, privileged_obs_shape, actions_shape, device)
+        del self.observations, self.obs_shape
+        self.estimator_feature_shape, self.estimator_label_shape = estimator_feature_shape, estimator_label_shape
+        T, N = self.num_transitions_per_env, self.num_envs
+        self.estimator_features = torch.zeros(T, N, *estimator_feature_shape, device=self.device)
+        self.estimator_labels = torch.zeros(T, N, *estimator_label_shape, device=self.device)
+
+    def _batch_source(self, name):
+        if name != "critic":
+            return getattr(self, name)
+        if self.privileged_observations is not None:
+            return self.privileged_observations
+        return torch.cat((self.estimator_features, self.estimator_labels), dim=-1)       # rollout_storage_ee.py:116-123, once per call
+
+
+class RolloutStorageTS(_LearnerStorage):
+    """rsl_rl/storage/rollout_storage_ts.py (PPO_TS, teacher-student): privileged observations feed the privilege encoder, critic
+    observations the critic.  `add_step` keywords: observations, privileged_observations, observation_histories, critic_observations.
+    Mini-batches are the 14 entries of rollout_storage_ts.py:115-117."""
+
+    class Transition(RolloutStorage.Transition):
+        def __init__(self):
+            super().__init__()
+            self.privileged_observations = None
+            self.observation_histories = None
+
+    STEP_ROWS = (("observations", "observations"), ("privileged_observations", "privileged_observations"),
+                 ("observation_histories", "observation_histories"), ("critic_observations", "critic_observations"))
+    BATCH = (("observations", _F32), ("privileged_observations", _F32), ("observation_histories", _F32), ("critic_observations", _F32),
+             ("dones", _NOT)) + _PPO_BATCH
+
+    def __init__(self, num_envs, num_transitions_per_env, obs_shape, privileged_obs_shape, obs_history_shape, critic_obs_shape, actions_shape,
+                 device="cuda:0"):
+        if privileged_obs_shape[0] is None:
+            raise ValueError(f"Privileged observations are required for {type(self).__name__}")
+        super().__init__(num_envs, num_transitions_per_env, obs_shape, privileged_obs_shape, actions_shape, device)
+        self.obs_history_shape, self.critic_obs_shape = obs_history_shape, critic_obs_shape
+        T, N = self.num_transitions_per_env, self.num_envs
+        self.observation_histories = torch.zeros(T, N, *obs_history_shape, device=self.device)
+        self.critic_observations = torch.zeros(T, N, *critic_obs_shape, device=self.device)
+
+
+class RolloutStorageDreamWaQ(_LearnerStorage):
+    """rsl_rl/storage/rollout_storage_dreamwaq.py (PPO_DreamWaQ).  `add_step` keywords: observations, privileged_observations,
+    observation_histories, explicit_info_labels, next_states -- five rows, so a recurrent policy's hidden states on top (an LSTM has four
+    tensors) do not fit one record launch and are refused.  Mini-batches are the 15 entries of rollout_storage_dreamwaq.py:121-123."""
+
+    class Transition(RolloutStorage.Transition):
+        def __init__(self):
+            super().__init__()
+            self.privileged_observations = None
+            self.observation_histories = None
+            self.explicit_info_labels = None
+            self.next_states = None
+
+    STEP_ROWS = (("observations", "observations"), ("privileged_observations", "privileged_observations"),
+                 ("observation_histories", "observation_histories"), ("explicit_info_labels", "explicit_info_labels"), ("next_states", "next_states"))
+    BATCH = (("observations", _F32), ("privileged_observations", _F32), ("observation_histories", _F32), ("explicit_info_labels", _F32),
+             ("next_states", _F32), ("dones", _NOT)) + _PPO_BATCH
+
+    def __init__(self, num_envs, num_transitions_per_env, obs_shape, privileged_obs_shape, obs_history_shape, explicit_info_shape,
+                 next_states_shape, actions_shape, device="cuda:0"):
+        if privileged_obs_shape[0] is None:
+            raise ValueError("privileged_observations is necessary for DreamWaQ RolloutStorage")
+        super().__init__(num_envs, num_transitions_per_env, obs_shape, privileged_obs_shape, actions_shape, device)
+        self.obs_history_shape = obs_history_shape
+        T, N = self.num_transitions_per_env, self.num_envs
+        self.observation_histories = torch.zeros(T, N, *obs_history_shape, device=self.device)
+        self.explicit_info_labels = torch.zeros(T, N, *explicit_info_shape, device=self.device)
+        self.next_states = torch.zeros(T, N, *next_states_shape, device=self.device)
+
+
+class RolloutStorageCTS(RolloutStorageTS):
+    """rsl_rl/storage/rollout_storage_cts.py (PPO_CTS, concurrent teacher-student): envs [0, num_teacher) are the teacher's, the rest the
+    student's.  `compute_returns` is one GAE pass whose advantages are split into `teacher_advantages` (T, num_teacher, 1) and
+    `student_advantages` (T, N - num_teacher, 1), each normalised by its own mean and std (`lg_rollout_gae_groups`); `advantages` is left
+    alone, as in the reference.  Mini-batches are the 18 entries of rollout_storage_cts.py:179-184: seven gathered by a permutation of
+    the teacher's samples, six by one of the student's, three by one of all samples, in one launch; the teacher / student tensors are
+    read from the (T, N, width) rows in place (the reference flattens a copy of each on every call)."""
+
+    def __init__(self, num_envs, num_teacher, num_transitions_per_env, obs_shape, privileged_obs_shape, obs_history_shape, critic_obs_shape,
+                 actions_shape, device="cuda:0"):
+        if not 1 <= int(num_teacher) <= int(num_envs) - 1:
+            raise ValueError(f"num_teacher={num_teacher}: both groups need an env, expected 1 .. {int(num_envs) - 1}")
+        super().__init__(num_envs, num_transitions_per_env, obs_shape, privileged_obs_shape, obs_history_shape, critic_obs_shape, actions_shape, device)
+        self.num_teacher = int(num_teacher)
+        T, N = self.num_transitions_per_env, self.num_envs
+        self.teacher_advantages = torch.zeros(T, self.num_teacher, 1, device=self.device)
+        self.student_advantages = torch.zeros(T, N - self.num_teacher, 1, device=self.device)
+        self._scratch = torch.zeros(4, dtype=torch.float64, device=self.device)
+
+    def compute_returns(self, last_values, gamma, lam):
+        """rollout_storage_cts.py:81-114 in four launches (memset, GAE, one normalisation per group)."""
+        lv = last_values.reshape(-1).contiguous().float()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        abi.check(self.lib.lg_rollout_gae_groups(self.num_transitions_per_env, self.num_envs, self.num_teacher, self.values.data_ptr(),
+                                                 self.rewards.data_ptr(), self.dones.data_ptr(), lv.data_ptr(), float(gamma), float(lam),
+                                                 self.returns.data_ptr(), self.teacher_advantages.data_ptr(), self.student_advantages.data_ptr(),
+                                                 self._scratch.data_ptr(), stream), self.lib)
+
+    def mini_batch_generator(self, num_mini_batches, num_epochs=8):
+        """Mini-batch sizes are the reference's: num_teacher * T // n for the teacher, (N - num_teacher) * T // n for the student, their sum
+        for the critic's three tensors (not N * T // n).  Three permutations per call, drawn in the reference's order."""
+        T, N, nt, dev = self.num_transitions_per_env, self.num_envs, self.num_teacher, self.device
+        per_t, per_s = nt * T // num_mini_batches, (N - nt) * T // num_mini_batches
+        sets = [(torch.randperm(num_mini_batches * per, device=dev), per) for per in (per_t, per_s, per_t + per_s)]
+        teacher, student = (0, nt), (nt, N - nt)
+        entries = [(getattr(self, k), _F32, 0, teacher) for k in ("observations", "privileged_observations", "actions", "actions_log_prob")]
+        entries += [(self.teacher_advantages, _F32, 0, None), (self.mu, _F32, 0, teacher), (self.sigma, _F32, 0, teacher)]
+        entries += [(getattr(self, k), _F32, 1, student) for k in ("observations", "privileged_observations", "observation_histories", "actions",
+                                                                   "actions_log_prob")]
+        entries += [(self.student_advantages, _F32, 1, None)]
+        entries += [(getattr(self, k), _F32, 2, None) for k in ("critic_observations", "values", "returns")]
+        for batch in self._gather_batches(entries, sets, num_mini_batches, num_epochs):
+            yield (*batch, (None, None), None)
 
 
 class _Unpad(torch.autograd.Function):

@@ -74,6 +74,47 @@ int lg_rollout_pad(int32_t n_steps, int32_t n_envs, const int32_t *traj, int32_t
 int lg_rollout_unpad(int32_t n_steps, int32_t n_envs, const int32_t *traj, int32_t capacity, int32_t n_traj, int32_t rows,
                      const float *padded, float *dst, int32_t width, void *stream);
 
+/* ---- mini-batches (rollout_storage.py:148-186 and the generators of rollout_storage_ee / _ts / _cts / _dreamwaq.py) -----------------
+ * One item of lg_rollout_gather: dst (rows, width) float32 contiguous, dst[j, :] = f(src[row(index[j]), :]) with
+ *   row(r) = (r / group) * n_envs + env_offset + r % group
+ * so that index r addresses x[:, env_offset : env_offset + group].flatten(0, 1)[r] of a (T, n_envs, width) tensor without the flattened
+ * copy; a plain gather is group = n_envs, env_offset = 0.  src_stride is the distance between consecutive source rows, in elements.
+ * kind LG_GATHER_F32: src float32, f(x) = x.  kind LG_GATHER_NOT_U8: src uint8, f(x) = 1.0f - x (the `terminated_batch` of the
+ * explicit-estimator, teacher-student and DreamWaQ generators).  index is int64 (what torch.randperm yields); its values must address
+ * rows inside src and stay below 2^31: they are NOT checked on the device. */
+#define LG_ROLLOUT_MAX_GATHER 16
+#define LG_GATHER_F32 0
+#define LG_GATHER_NOT_U8 1
+
+typedef struct LgGatherItem {
+    const void *src;
+    float *dst;
+    const int64_t *index;
+    int32_t rows;         /* entries of index = rows of dst; 0 skips the item, whose pointers are then not looked at */
+    int32_t width;
+    int32_t src_stride;
+    int32_t kind;
+    int32_t group;
+    int32_t env_offset;
+    int32_t n_envs;
+} LgGatherItem;
+
+/* Every tensor of one mini-batch in ONE launch: up to LG_ROLLOUT_MAX_GATHER items, each with its own index pointer and row count.
+ * Consecutive lanes on consecutive floats of a row; float4 moves where kind, width, stride and both pointers allow, scalar otherwise.
+ * Every destination element is written exactly once.  Refused before the launch: a null pointer, width < 1, src_stride < width,
+ * group < 1, env_offset < 0, env_offset + group > n_envs, rows < 0, an unknown kind, n_items outside [1, LG_ROLLOUT_MAX_GATHER], a
+ * destination of 2^31 elements or more. */
+int lg_rollout_gather(const LgGatherItem *items, int32_t n_items, void *stream);
+
+/* lg_rollout_gae for two groups of envs (rollout_storage_cts.py:81-114): one pass of the recurrence over all N envs into returns
+ * (T, N, 1); the raw advantages returns - values of envs [0, n_first) go to adv_first (T, n_first, 1) and those of [n_first, N) to
+ * adv_rest (T, N - n_first, 1), both contiguous, and each group is normalised by its own mean and unbiased std.
+ * scratch: device buffer of at least 4 doubles (sum, sum of squares per group).  Refused: n_first < 1, n_first >= N, a group with
+ * fewer than two entries. */
+int lg_rollout_gae_groups(int32_t n_steps, int32_t n_envs, int32_t n_first, const float *values, const float *rewards, const uint8_t *dones,
+                          const float *last_values, float gamma, float lam, float *returns, float *adv_first, float *adv_rest,
+                          double *scratch, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,540 @@
+"""The storages of the explicit-estimator (EE), teacher-student (TS), concurrent teacher-student (CTS) and DreamWaQ learners in
+hcr_genesis_lr_cl_amd.rollout, the gather kernel behind every mini-batch (`lg_rollout_gather`) and the grouped return computation of CTS
+(`lg_rollout_gae_groups`), against tests/golden/rollout_algos.npz (the reference's own four classes on the CPU, N = 12, T = 5, 5 teacher
+envs; tests/golden/gen_rollout_algos_fixtures.py) and against float64 restatements (tests/rollout_algos_harness.py).
+
+  * CPU: the restatement and the expected tuple layouts reproduce the fixture; header, ctypes mirror and export list agree;
+  * fixture replay per class, filled by `add_transitions` and by `add_step`: stored tensors bit-equal, returns / advantages at the
+    tolerances of test_rollout_storage_matches_rsl_rl, the yielded tuple's arity, order, shapes and dtypes equal to the reference's;
+  * gather contents at N in {1, 65, 257}, T in {3, 24}, 1 / 4 / 7 mini-batches, widths 1, 3 (scalar), 12, 48 (float4), 45 (scalar, odd)
+    and a float4-wide tensor whose base is not 16-byte aligned: every entry of every yield equals the host copy at the sample ids read
+    from a tagged entry of the same index set, `terminated == 1 - dones` there, every epoch is a permutation of its index range;
+  * the kernel through its C entry point with every destination inside a sentinel-filled allocation that is compared whole;
+  * grouped GAE, GROUP_CASES: returns within 4 * err_ref + 1 ulp(max |returns|) of the float64 recurrence (err_ref: the error of the
+    float32 restatement, oracle/rollout_oracle.py, on the same inputs), each group's normalised advantages within 4 ulp of its scale of
+    the float64 normalisation of that group's own float32 returns - values;
+  * refusals before any launch.
+
+Measured on an MI355X (gfx950) over GROUP_CASES (gamma 0.99, lam 0.95; first / rest: the two groups' normalised advantages): the returns'
+error is at most 3.230e-06 and at most 1.24 x err_ref of its case; the normalised advantages of either group are within 1.63 ulp of the
+group's scale (bound 4).  Per case:
+
+      N  first    T  done | max|ret|   err_ref    kernel     bound | first: max|adv|  err   in ulp | rest: max|adv|   err   in ulp
+      2      1   24   0.0 |    4.135 9.272e-07 1.154e-06 4.186e-06 |    2.673 1.780e-07   0.75 |    1.644 1.464e-07   1.23
+      2      1   24  0.08 |    3.543 5.552e-07 5.552e-07 2.459e-06 |    2.311 8.866e-08   0.37 |    1.866 8.857e-08   0.74
+      2      1   24   1.0 |    0.384 1.192e-07 1.192e-07 5.066e-07 |    2.536 3.090e-07   1.30 |    2.084 1.285e-07   0.54
+     65      1   24   0.0 |    4.503 1.664e-06 1.556e-06 7.134e-06 |    2.405 1.427e-07   0.60 |    2.870 1.782e-07   0.75
+     65      1   24  0.08 |    3.989 1.664e-06 1.556e-06 6.896e-06 |    2.476 2.157e-07   0.90 |    3.473 1.713e-07   0.72
+     65      1   24   1.0 |    0.424 1.192e-07 1.192e-07 5.066e-07 |    1.840 9.605e-08   0.81 |    3.491 2.295e-07   0.96
+    130     65    1   0.0 |    2.801 1.973e-07 1.973e-07 1.028e-06 |    2.738 2.602e-07   1.09 |    2.255 1.664e-07   0.70
+    130     65    1  0.08 |    2.801 1.973e-07 1.973e-07 1.028e-06 |    2.819 1.400e-07   0.59 |    2.256 1.820e-07   0.76
+    130     65    1   1.0 |    0.643 1.192e-07 1.192e-07 5.364e-07 |    2.478 1.297e-07   0.54 |    3.042 2.219e-07   0.93
+    130     65   24   0.0 |    7.714 2.844e-06 2.356e-06 1.185e-05 |    2.996 3.099e-07   1.30 |    2.939 1.934e-07   0.81
+    130     65   24  0.08 |    7.714 2.690e-06 2.328e-06 1.124e-05 |    3.700 3.035e-07   1.27 |    3.160 1.920e-07   0.81
+    130     65   24   1.0 |    0.684 1.192e-07 1.192e-07 5.364e-07 |    4.007 2.006e-07   0.42 |    3.881 3.403e-07   1.43
+    257    256   24   0.0 |    8.260 3.235e-06 3.230e-06 1.390e-05 |    3.204 2.751e-07   1.15 |    2.335 1.787e-07   0.75
+    257    256   24  0.08 |    8.260 2.676e-06 2.598e-06 1.166e-05 |    4.370 4.033e-07   0.85 |    2.146 6.116e-08   0.26
+    257    256   24   1.0 |    0.743 1.192e-07 1.192e-07 5.364e-07 |    3.909 2.348e-07   0.98 |    1.859 6.446e-08   0.54
+   4097   1024    1   0.0 |    3.939 4.376e-07 3.468e-07 1.989e-06 |    3.513 2.611e-07   1.10 |    3.983 1.808e-07   0.76
+   4097   1024    1  0.08 |    3.939 4.376e-07 3.468e-07 1.989e-06 |    3.589 3.681e-07   1.54 |    4.108 5.124e-07   1.07
+   4097   1024    1   1.0 |    0.713 1.192e-07 1.192e-07 5.364e-07 |    2.981 1.760e-07   0.74 |    3.831 2.072e-07   0.87
+   4097   1024   24   0.0 |    8.154 3.370e-06 2.818e-06 1.443e-05 |    3.221 2.889e-07   1.21 |    3.379 3.881e-07   1.63
+   4097   1024   24  0.08 |    8.154 3.233e-06 2.569e-06 1.389e-05 |    4.351 3.097e-07   0.65 |    3.929 2.660e-07   1.12
+   4097   1024   24   1.0 |    0.762 1.788e-07 1.788e-07 7.749e-07 |    4.361 3.966e-07   0.83 |    4.631 2.917e-07   0.61
+"""
+import ctypes as C
+import os
+import re
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+from tests import rollout_algos_harness as ah
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+GOLD = os.path.join(HERE, "golden", "rollout_algos.npz")
+HEADER = os.path.join(os.path.dirname(HERE), "include", "lgrollout.h")
+NAMES = {"EE": "RolloutStorageEE", "TS": "RolloutStorageTS", "CTS": "RolloutStorageCTS", "DreamWaQ": "RolloutStorageDreamWaQ"}
+SENTINEL, MARGIN = -7777.25, 37
+
+
+def storage_class(cls):
+    from hcr_genesis_lr_cl_amd import rollout
+    return getattr(rollout, NAMES[cls])
+
+
+# ---- CPU ----------------------------------------------------------------------------------------------------------------------------------
+def test_the_four_classes_import():
+    from hcr_genesis_lr_cl_amd import rollout
+    for cls, name in NAMES.items():
+        k = getattr(rollout, name)
+        assert issubclass(k, rollout.RolloutStorage) and issubclass(k.Transition, rollout.RolloutStorage.Transition)
+        tr = k.Transition()
+        for attr, _ in ah.ROWS[cls] + ah.POLICY_ROWS:
+            assert hasattr(tr, attr) and getattr(tr, attr) is None, (cls, attr)
+    assert issubclass(rollout.RolloutStorageCTS, rollout.RolloutStorageTS)
+
+
+def test_layouts_match_the_fixture():
+    """What the reference's generators yielded (read off the tags by the fixture's generator) is what LAYOUTS says, with the reference's
+    mini-batch sizes: 12 * 5 // 3 = 20, and for CTS 5 * 5 // 3 = 8, 7 * 5 // 3 = 11 and their sum 19 (not 20)."""
+    fx = np.load(GOLD)
+    T, N, nt = int(fx["num_steps"]), int(fx["num_envs"]), int(fx["num_teacher"])
+    assert (T, N, nt) == (ah.T, ah.N, ah.NUM_TEACHER)
+    for cls in ah.CLASSES:
+        names, sets = fx[f"{cls}_layout_names"].tolist(), fx[f"{cls}_layout_sets"].tolist()
+        assert list(zip(names, sets)) == ah.LAYOUTS[cls], cls
+        assert len(names) + 2 == ah.ARITY[cls]
+        assert fx[f"{cls}_layout_widths"].tolist() == [ah.width_of(n) for n in names]
+        assert set(fx[f"{cls}_layout_dtypes"].tolist()) == {"float32"}
+        per = {"CTS": [nt * T // 3, (N - nt) * T // 3, nt * T // 3 + (N - nt) * T // 3]}.get(cls, [N * T // 3])
+        assert fx[f"{cls}_layout_rows"].tolist() == [per[s] for s in sets] and (cls != "CTS" or per == [8, 11, 19])
+        if "dones" in names:
+            term, dones = fx[f"{cls}_terminated"], fx[f"{cls}_terminated_dones"]
+            assert term.dtype == np.float32 and term.shape == (6, per[0]) and np.array_equal(term, 1.0 - dones.astype(np.float32))
+            assert 0 < dones.sum() < dones.size
+        for attr, stored in ah.ROWS[cls] + ah.POLICY_ROWS:                    # add_transitions copies every row verbatim
+            want = fx[f"{cls}_in_{attr}"]
+            np.testing.assert_array_equal(fx[f"{cls}_st_{stored}"], want.reshape(T, N, -1), err_msg=f"{cls}.{stored}")
+        np.testing.assert_array_equal(fx[f"{cls}_st_rewards"][..., 0], fx[f"{cls}_in_rewards"])
+        np.testing.assert_array_equal(fx[f"{cls}_st_dones"][..., 0], fx[f"{cls}_in_dones"])
+    assert "EE_st_observations" not in fx.files and fx["CTS_st_teacher_advantages"].shape == (T, nt, 1)
+
+
+def test_grouped_gae_restatement_reproduces_the_fixture():
+    """gae_groups_f64 against the reference's RolloutStorageCTS.compute_returns, at the tolerances test_rollout_oracle_reproduces_rsl_rl
+    uses; the other three classes inherit the base compute_returns, which is the one-group case."""
+    from oracle import rollout_oracle as ro
+    fx = np.load(GOLD)
+    g = lambda k: fx["CTS_st_" + k]
+    ret, raw, first, rest = ah.gae_groups_f64(g("values"), g("rewards"), g("dones"), fx["CTS_last_values"], fx["gamma"], fx["lam"], ah.NUM_TEACHER)
+    np.testing.assert_allclose(ret, g("returns"), rtol=1e-5, atol=1e-6)
+    np.testing.assert_allclose(first, g("teacher_advantages"), rtol=1e-5, atol=2e-6)
+    np.testing.assert_allclose(rest, g("student_advantages"), rtol=1e-5, atol=2e-6)
+    assert np.array_equal(g("advantages"), np.zeros_like(g("advantages")))             # the reference leaves the base tensor alone
+    assert abs(first.mean()) < 1e-12 and abs(rest.std(ddof=1) - 1.0) < 1e-7
+    both = ro.normalise_f64(raw)                                                         # one normalisation over all envs is something else
+    assert np.abs(both[:, :ah.NUM_TEACHER] - first).max() > 1e-2
+    for cls in ("EE", "TS", "DreamWaQ"):
+        g = lambda k: fx[f"{cls}_st_{k}"]
+        ret, _, adv = ro.compute_returns_f64(g("values"), g("rewards"), g("dones"), fx[f"{cls}_last_values"], fx["gamma"], fx["lam"])
+        np.testing.assert_allclose(ret, g("returns"), rtol=1e-5, atol=1e-6)
+        np.testing.assert_allclose(adv, g("advantages"), rtol=1e-5, atol=2e-6)
+
+
+def test_gather_abi_matches_header():
+    from hcr_genesis_lr_cl_amd import abi
+    cls = abi.LgGatherItem
+    lines = ['#include <stdio.h>', '#include <stddef.h>', f'#include "{HEADER}"', "int main(void){", 'printf("size %zu\\n", sizeof(LgGatherItem));',
+             'printf("max %d\\n", LG_ROLLOUT_MAX_GATHER);', 'printf("f32 %d\\n", LG_GATHER_F32);', 'printf("not_u8 %d\\n", LG_GATHER_NOT_U8);']
+    lines += [f'printf("{f} %zu\\n", offsetof(LgGatherItem, {f}));' for f, _ in cls._fields_] + ["return 0;}"]
+    with tempfile.TemporaryDirectory() as d:
+        src, exe = os.path.join(d, "p.c"), os.path.join(d, "p")
+        open(src, "w").write("\n".join(lines))
+        subprocess.run(["gcc", "-o", exe, src], check=True)
+        got = dict(l.split() for l in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.strip().splitlines())
+    assert int(got["size"]) == C.sizeof(cls)
+    for f, _ in cls._fields_:
+        assert int(got[f]) == getattr(cls, f).offset, f
+    assert (int(got["max"]), int(got["f32"]), int(got["not_u8"])) == (abi.ROLLOUT_MAX_GATHER, abi.GATHER_F32, abi.GATHER_NOT_U8)
+    assert {"lg_rollout_gather", "lg_rollout_gae_groups"} <= set(abi.ROLLOUT_EXPORTS)
+    if not os.path.exists(abi.lib_path()):
+        from hcr_genesis_lr_cl_amd import build
+        build.build()
+    lib = abi.load_lib()                                                                 # loads without a GPU; nothing is called
+    text = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    for name in ("lg_rollout_gather", "lg_rollout_gae_groups"):
+        params = re.search(name + r"\s*\((.*?)\)\s*;", text, re.S).group(1)
+        assert len(getattr(lib, name).argtypes) == len(params.split(",")), name
+        assert getattr(lib, name).restype is C.c_int
+
+
+# ---- GPU: fixture replay --------------------------------------------------------------------------------------------------------------
+def fill(st, cls, x, path, T):
+    """T steps of the inputs `x` ({Transition attribute: (T, N, ...) host array}) by the reference's entry point or by the fused one."""
+    import torch
+    dev = st.device
+    g = lambda k, t: torch.from_numpy(np.ascontiguousarray(x[k][t])).to(dev)
+    for t in range(T):
+        if path == "add_transitions":
+            tr = type(st).Transition()
+            for attr in x:
+                setattr(tr, attr, g(attr, t))
+            st.add_transitions(tr)
+        else:
+            for attr, stored in ah.POLICY_ROWS:
+                getattr(st, stored)[t].copy_(g(attr, t).view(st.num_envs, -1))
+            st.add_step(g("rewards", t), g("dones", t), None, 0.0, **{attr: g(attr, t) for attr, _ in ah.ROWS[cls]})
+    assert st.step == T
+
+
+def decode_batch(batch, T, N):
+    """(names, widths, dtypes, rows, sets, ids per set) of one yielded tuple, as the fixture's generator reads them."""
+    names, widths, dtypes, rows, sets, ids_of_set = [], [], [], [], [], []
+    for item in batch[:-2]:
+        a = item.cpu().numpy()
+        name, ids = ah.decode(a[:, 0], T, N) if a.shape[0] else ("empty", None)
+        if ids is not None:
+            key = ids.tolist()
+            if key not in ids_of_set:
+                ids_of_set.append(key)
+            sets.append(ids_of_set.index(key))
+        else:
+            sets.append(-1)
+        names.append(name); widths.append(a.shape[1]); dtypes.append(str(a.dtype)); rows.append(a.shape[0])
+    for i, name in enumerate(names):
+        if name == "dones":
+            match = [k for k, ids in enumerate(ids_of_set) if len(ids) == rows[i]]
+            assert len(match) == 1
+            sets[i] = match[0]
+    return names, widths, dtypes, rows, sets, ids_of_set
+
+
+def tag_computed(st, T, N):
+    import torch
+    nt = getattr(st, "num_teacher", 0)
+    for n in ah.COMPUTED:
+        x = getattr(st, n, None)
+        if x is not None:
+            first, group = {"teacher_advantages": (0, nt), "student_advantages": (nt, N - nt)}.get(n, (0, N))
+            x[..., 0] = torch.from_numpy(ah.tag_base(n, T, N) + ah.tag_ids(T, N, first, group)).to(st.device)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("path", ["add_transitions", "add_step"])
+@pytest.mark.parametrize("cls", ah.CLASSES)
+def test_fixture_replay(cls, path):
+    import torch
+    fx = np.load(GOLD)
+    T, N, nt = ah.T, ah.N, ah.NUM_TEACHER
+    st = storage_class(cls)(*ah.ctor_args(cls, N, T, nt), "cuda:0")
+    x = {k[len(cls) + 4:]: fx[k] for k in fx.files if k.startswith(cls + "_in_")}
+    fill(st, cls, x, path, T)
+    with pytest.raises(AssertionError, match="overflow"):
+        fill(st, cls, x, path, 1)
+    st.compute_returns(torch.from_numpy(fx[f"{cls}_last_values"]).to(st.device), float(fx["gamma"]), float(fx["lam"]))
+    torch.cuda.synchronize()
+    if cls == "EE":
+        assert not hasattr(st, "observations") and not hasattr(st, "obs_shape")
+    stored = [k[len(cls) + 4:] for k in fx.files if k.startswith(cls + "_st_")]
+    approx = {"returns": 2e-6, "advantages": 5e-6, "teacher_advantages": 5e-6, "student_advantages": 5e-6}
+    for n in stored:
+        got, want = getattr(st, n).cpu().numpy(), fx[f"{cls}_st_{n}"]
+        assert got.shape == want.shape and got.dtype == want.dtype, n
+        if n in approx and not (cls == "CTS" and n == "advantages"):
+            np.testing.assert_allclose(got, want, rtol=1e-5, atol=approx[n], err_msg=n)
+        else:
+            np.testing.assert_array_equal(got, want, err_msg=n)                          # CTS leaves `advantages` zero, as the reference does
+    tag_computed(st, T, N)
+    batches = list(st.mini_batch_generator(3, 2))
+    torch.cuda.synchronize()
+    assert len(batches) == 6
+    want = tuple(fx[f"{cls}_layout_{k}"].tolist() for k in ("names", "widths", "dtypes", "rows", "sets"))
+    for batch in batches:
+        assert len(batch) == ah.ARITY[cls] and batch[-2] == (None, None) and batch[-1] is None
+        assert all(b.is_contiguous() and b.dim() == 2 for b in batch[:-2])
+        assert decode_batch(batch, T, N)[:5] == want
+
+
+# ---- GPU: what the mini-batches hold, whatever the permutation ------------------------------------------------------------------------
+# 45: scalar and odd; 48, 12: float4; 3, 1: scalar; `mu` (12 wide) is re-pointed at a view one float into its allocation: float4-wide, but
+# its base is not 16-byte aligned, so it must go the scalar way
+GATHER_WIDTHS = dict(observations=45, privileged_observations=48, observation_histories=12, critic_observations=16, estimator_features=12,
+                     estimator_labels=3, explicit_info_labels=5, next_states=48, actions=12)
+GATHER_CASES = [(cls, N, T, nt) for cls in ("EE", "TS", "DreamWaQ") for N in (1, 65, 257) for T in (3, 24) for nt in (0,)]
+GATHER_CASES += [("CTS", N, T, nt) for N in (65, 257) for T in (3, 24) for nt in (1, 64, N - 1)]
+
+
+def tagged_storage(cls, N, T, nt, seed):
+    """A storage of GATHER_WIDTHS with random contents, a tag in column 0 of every float tensor, dones at a rate near 0.3 and `mu`
+    off 16-byte alignment.  Returns (storage, {tensor name: host copy, (T, envs, width)})."""
+    import torch
+    st = storage_class(cls)(*ah.ctor_args(cls, N, T, nt, GATHER_WIDTHS), "cuda:0")
+    pool = torch.zeros(T * N * 12 + 8, device=st.device)
+    st.mu = pool[1:1 + T * N * 12].view(T, N, 12)
+    assert st.mu.data_ptr() % 16 == 4 and st.actions.data_ptr() % 16 == 0
+    rng = np.random.default_rng(seed)
+    host = {}
+    for n in ah.TAGGED:
+        x = getattr(st, n, None)
+        if x is None:
+            continue
+        first, group = {"teacher_advantages": (0, nt), "student_advantages": (nt, N - nt)}.get(n, (0, N))
+        h = rng.normal(size=tuple(x.shape)).astype(np.float32)
+        h[..., 0] = ah.tag_base(n, T, N) + ah.tag_ids(T, N, first, group)
+        x.copy_(torch.from_numpy(h))
+        host[n] = h
+    d = (rng.random((T, N, 1)) < 0.3).astype(np.uint8)
+    st.dones.copy_(torch.from_numpy(d))
+    host["dones"] = d
+    return st, host
+
+
+def rows_at(host, name, ids, N, nt):
+    """Host rows of tensor `name` at the global sample ids t * N + e (the groups' advantage tensors hold their own envs only)."""
+    h = host[name]
+    t, e = ids // N, ids % N
+    if name == "teacher_advantages":
+        assert (e < nt).all()
+    if name == "student_advantages":
+        e = e - nt
+        assert (e >= 0).all()
+    return h[t, e]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("cls,N,T,nt", GATHER_CASES, ids=[f"{c}-N{n}-T{t}-nt{k}" for c, n, t, k in GATHER_CASES])
+def test_mini_batches_hold_the_samples_their_tags_name(cls, N, T, nt):
+    import torch
+    st, host = tagged_storage(cls, N, T, nt, seed=N * 31 + T)
+    layout = ah.LAYOUTS[cls]
+    windows = {"CTS": [(0, nt), (nt, N - nt), (0, N)]}.get(cls, [(0, N)])
+    for nmb, epochs in ((1, 1), (4, 2), (7, 2)):
+        pers = [g * T // nmb for _, g in windows[:2]]
+        pers = pers + [sum(pers)] if cls == "CTS" else pers[:1]
+        batches = list(st.mini_batch_generator(nmb, epochs))
+        torch.cuda.synchronize()
+        assert len(batches) == nmb * epochs
+        blocks = []
+        for b, batch in enumerate(batches):
+            assert len(batch) == ah.ARITY[cls] and batch[-2] == (None, None) and batch[-1] is None
+            items = [x.cpu().numpy() for x in batch[:-2]]
+            ids = {}
+            for (name, s), a in zip(layout, items):                                     # sample ids per index set, from its first tagged entry
+                if s not in ids and name != "dones" and a.shape[0]:
+                    got, ids[s] = ah.decode(a[:, 0], T, N)
+                    assert got == name
+            for k, ((name, s), a, x) in enumerate(zip(layout, items, batch)):
+                assert x.dtype == torch.float32 and x.is_contiguous() and a.shape == (pers[s], ah.width_of(name, GATHER_WIDTHS)), (b, k, name)
+                if pers[s] == 0:
+                    continue
+                want = rows_at(host, name, ids[s], N, nt)
+                if name == "dones":
+                    want = 1.0 - want.astype(np.float32)
+                    assert set(np.unique(want)) <= {0.0, 1.0}
+                np.testing.assert_array_equal(a, want, err_msg=f"{nmb} mini-batches, yield {b}: entry {k} is not {name} at the sample ids of its set")
+            blocks.append(ids)
+        for s, (first, group) in enumerate(windows):
+            if pers[s] == 0:
+                continue
+            local = [(i[s] // N) * group + (i[s] % N - first) for i in blocks]           # index into x[:, first:first + group].flatten(0, 1)
+            env = np.concatenate([i[s] % N for i in blocks])
+            assert (env >= first).all() and (env < first + group).all(), f"set {s} holds envs outside [{first}, {first + group})"
+            epoch = np.concatenate(local[:nmb])
+            assert len(epoch) == nmb * pers[s] and len(np.unique(epoch)) == len(epoch) and epoch.min() >= 0 and epoch.max() < nmb * pers[s]
+            if nmb * pers[s] > 64:
+                assert not np.array_equal(epoch, np.sort(epoch))                         # a permutation, not the identity
+            for b in range(nmb, len(local)):
+                np.testing.assert_array_equal(local[b], local[b % nmb], err_msg="later epochs replay the blocks of the first")
+    assert T * N < 24 or set(np.unique(host["dones"])) == {0, 1}                         # both values of `terminated` occur
+
+
+def test_gather_cases_cover_the_issue():
+    assert {c[1] for c in GATHER_CASES} == {1, 65, 257} and {c[2] for c in GATHER_CASES} == {3, 24} and {c[0] for c in GATHER_CASES} == set(ah.CLASSES)
+    assert {(c[1], c[3]) for c in GATHER_CASES if c[0] == "CTS"} == {(65, 1), (65, 64), (257, 1), (257, 64), (257, 256)}
+    assert {1, 3, 12, 45, 48} <= set(GATHER_WIDTHS.values()) | {1}
+    assert all(n * t % 7 for _, n, t, _ in GATHER_CASES)                                 # seven mini-batches always drop a tail
+
+
+# ---- GPU: the kernel through its C entry point, destinations inside sentinel-filled allocations ------------------------------------------
+# (width, columns before / behind the window in the source row, kind, (first env, envs) or None, index set)
+ITEMS = [(1, 0, 0, 0, None, 0), (3, 0, 0, 0, None, 0), (12, 0, 0, 0, None, 0), (48, 0, 0, 0, None, 0), (45, 0, 0, 0, None, 0),
+         (12, 1, 3, 0, None, 0), (48, 4, 12, 0, None, 0), (1, 0, 0, 1, None, 0), (3, 2, 0, 1, None, 1), (48, 0, 0, 0, "first", 1),
+         (45, 0, 0, 0, "rest", 2), (12, 0, 0, 0, "first", 1), (1, 0, 0, 1, "rest", 2), (16, 0, 0, 0, None, 2), (5, 0, 3, 0, "first", 1),
+         (64, 0, 0, 0, None, 0)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N,T", [(1, 3), (2, 3), (65, 3), (65, 24), (257, 24)])
+def test_gather_kernel_writes_its_rows_and_nothing_else(N, T):
+    """All 16 items in one launch: plain and windowed, both kinds, strided sources (a source whose rows start 1 float into a 16-float
+    stride is float4-wide but unaligned), three index sets of different lengths with repeated and out-of-order rows.  The destinations
+    are cut from one pool, an odd number of floats apart, and the pool is compared whole."""
+    import torch
+    from hcr_genesis_lr_cl_amd import abi
+    lib, dev = abi.load_lib(), "cuda:0"
+    rng = np.random.default_rng(N * 100 + T)
+    n_first = max(N // 3, 1)
+    win = {None: (0, N), "first": (0, n_first), "rest": (n_first, N - n_first)}
+    rows = [max(T * N * 2 // 3, 1), max(T * n_first // 2, 1), T * (N - n_first) + 3]
+    index_host = {s: rng.integers(0, T * group, size=rows[s]).astype(np.int64) for s, group in enumerate((N, n_first, N - n_first)) if group > 0}
+    items = [it for it in ITEMS if win[it[4]][1] > 0 and it[5] in index_host]
+    offs, at = [], MARGIN
+    for k, it in enumerate(items):
+        if k % 3 == 0:
+            at = (at + 3) // 4 * 4                                                       # every third destination is 16-byte aligned
+        offs.append(at)
+        at += rows[it[5]] * it[0] + MARGIN
+    total = at
+    pool_host = np.full(total, SENTINEL, np.float32)
+    pool = torch.from_numpy(pool_host.copy()).to(dev)
+    assert pool.data_ptr() % 16 == 0
+    arr = (abi.LgGatherItem * len(items))()
+    keep, want_parts = [], []
+    for it, at, (w, before, behind, kind, window, s) in zip(arr, offs, items):
+        first, group = win[window]
+        stride = before + w + behind
+        if kind == abi.GATHER_NOT_U8:
+            src_host = (rng.random((T, N, stride)) < 0.3).astype(np.uint8)
+        else:
+            src_host = rng.normal(size=(T, N, stride)).astype(np.float32)
+        src = torch.from_numpy(src_host).to(dev)
+        idx = torch.from_numpy(index_host[s]).to(dev)
+        r = index_host[s]
+        picked = src_host[r // group, first + r % group, before:before + w]
+        want_parts.append((at, (1.0 - picked.astype(np.float32)) if kind == abi.GATHER_NOT_U8 else picked))
+        it.src, it.dst, it.index = src.data_ptr() + before * src.element_size(), pool.data_ptr() + 4 * at, idx.data_ptr()
+        it.rows, it.width, it.src_stride, it.kind = rows[s], w, stride, kind
+        it.group, it.env_offset, it.n_envs = group, first, N
+        keep += [src, idx]
+    abi.check(lib.lg_rollout_gather(arr, len(items), torch.cuda.current_stream().cuda_stream), lib)
+    torch.cuda.synchronize()
+    for o, part in want_parts:
+        pool_host[o:o + part.size] = part.reshape(-1)
+    np.testing.assert_array_equal(pool.cpu().numpy(), pool_host)
+
+
+# ---- GPU: GAE for two groups ------------------------------------------------------------------------------------------------------------
+GROUP_SIZES = [(2, 1), (65, 1), (130, 65), (257, 256), (4097, 1024)]
+GROUP_CASES = [(N, nf, T, rate) for N, nf in GROUP_SIZES for T in (1, 24) if T * min(nf, N - nf) >= 2 for rate in (0.0, 0.08, 1.0)]
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("N,n_first,T,rate", GROUP_CASES, ids=[f"N{n}-first{f}-T{t}-d{r}" for n, f, t, r in GROUP_CASES])
+def test_grouped_gae_matches_f64(N, n_first, T, rate):
+    import torch
+    from oracle import rollout_oracle as ro
+    from tests.test_rollout import gae_inputs, ulp32
+    gamma, lam = ah.GAMMA, ah.LAM
+    host = gae_inputs(N, T, rate, seed=N * 131 + T)
+    host["rewards"][:, :n_first] += np.float32(0.25)                                     # a sample counted in the wrong group moves both means
+    st = storage_class("CTS")(N, n_first, T, [1], [1], [1], [1], [1], "cuda:0")
+    for k in ("values", "rewards", "dones"):
+        getattr(st, k).copy_(torch.from_numpy(host[k]))
+    st.advantages.fill_(SENTINEL)
+    st.compute_returns(torch.from_numpy(host["last_values"]).to(st.device), gamma, lam)
+    torch.cuda.synchronize()
+    c = lambda x: x.cpu().numpy()
+    for k in ("values", "rewards", "dones"):
+        np.testing.assert_array_equal(c(getattr(st, k)), host[k], err_msg=k)
+    assert (c(st.advantages) == np.float32(SENTINEL)).all()                              # the base tensor stays untouched
+    ret64 = ah.gae_groups_f64(host["values"], host["rewards"], host["dones"], host["last_values"], gamma, lam, n_first)[0]
+    ret32, _ = ro.compute_returns(host["values"], host["rewards"], host["dones"], host["last_values"], gamma, lam)
+    returns = c(st.returns)
+    assert returns.dtype == np.float32 and returns.shape == (T, N, 1) and np.isfinite(returns).all()
+    err_ref, err = float(np.abs(ret32 - ret64).max()), float(np.abs(returns - ret64).max())
+    bound = 4.0 * err_ref + ulp32(np.abs(ret64).max())
+    raw = returns - host["values"]                                                       # float32, as the kernel forms it
+    figures, ok = [], err <= bound
+    for name, got, part in (("first", c(st.teacher_advantages), raw[:, :n_first]), ("rest", c(st.student_advantages), raw[:, n_first:])):
+        assert got.dtype == np.float32 and got.shape == part.shape and np.isfinite(got).all()
+        want = ah.normalise_f64(part)
+        scale = ulp32(np.abs(want).max())
+        e = float(np.abs(got.astype(np.float64) - want).max())
+        mean, std = got.mean(dtype=np.float64), got.std(ddof=1, dtype=np.float64)
+        figures.append(f"{name} max|adv| {np.abs(want).max():.3f} err {e:.3e} = {e / scale:.2f} ulp")
+        ok = ok and e <= 4.0 * scale and abs(mean) < 1e-6 and abs(std - 1.0) < 1e-5
+    print(f"N={N} first={n_first} T={T} done={rate}: max|returns| {np.abs(ret64).max():.3f} err_ref {err_ref:.3e} kernel {err:.3e} bound {bound:.3e} | "
+          + " | ".join(figures))
+    assert ok, (err, bound, figures)
+
+
+def test_group_cases_cover_the_issue():
+    assert {(c[0], c[1]) for c in GROUP_CASES} == set(GROUP_SIZES) and {c[3] for c in GROUP_CASES} == {0.0, 0.08, 1.0}
+    assert {(c[0], c[1]) for c in GROUP_CASES if c[2] == 1} == {(130, 65), (4097, 1024)} and len(GROUP_CASES) == 21
+
+
+# ---- GPU: refusals, all before any launch --------------------------------------------------------------------------------------------------
+@pytest.mark.gpu
+def test_refusals_before_any_launch():
+    import torch
+    from hcr_genesis_lr_cl_amd import abi
+    from hcr_genesis_lr_cl_amd.rollout import RolloutStorageCTS, RolloutStorageDreamWaQ, RolloutStorageEE, RolloutStorageTS
+    N, T, dev = 8, 3, "cuda:0"
+    for nt in (0, N, N + 1, -1):
+        with pytest.raises(ValueError, match="num_teacher"):
+            RolloutStorageCTS(N, nt, T, [5], [7], [9], [6], [2], dev)
+    for make in (lambda: RolloutStorageTS(N, T, [5], [None], [9], [6], [2], dev), lambda: RolloutStorageCTS(N, 3, T, [5], [None], [9], [6], [2], dev),
+                 lambda: RolloutStorageDreamWaQ(N, T, [5], [None], [9], [4], [3], [2], dev)):
+        with pytest.raises(ValueError, match="(?i)privileged"):
+            make()
+    assert RolloutStorageEE(N, T, [None], [6], [4], [2], dev).privileged_observations is None      # the explicit estimator may go without
+
+    st = RolloutStorageDreamWaQ(N, T, [5], [7], [9], [4], [3], [2], dev)
+    tensors = ("observations", "privileged_observations", "observation_histories", "explicit_info_labels", "next_states", "rewards")
+    for n in tensors:
+        getattr(st, n).fill_(SENTINEL)
+    st.dones.fill_(0xAB)
+    st.step = 1
+    rew, flag = torch.ones(N, device=dev), torch.ones(N, dtype=torch.bool, device=dev)
+    rows = {n: torch.ones(N, getattr(st, n).shape[2], device=dev) for n in tensors[:5]}
+    lstm = ((torch.ones(1, N, 4, device=dev),) * 2, (torch.ones(1, N, 4, device=dev),) * 2)
+    with pytest.raises(ValueError, match="9 row copies"):                                # five rows and an LSTM's four hidden tensors
+        st.add_step(rew, flag, None, 0.0, hidden_states=lstm, **rows)
+    tr = RolloutStorageDreamWaQ.Transition()
+    for k, v in rows.items():
+        setattr(tr, k, v)
+    tr.actions = tr.action_mean = tr.action_sigma = torch.ones(N, 2, device=dev)
+    tr.values, tr.actions_log_prob, tr.rewards, tr.dones, tr.hidden_states = torch.ones(N, 1, device=dev), rew, rew, flag, lstm
+    st.actions.fill_(SENTINEL)
+    with pytest.raises(ValueError, match="9 row copies"):
+        st.add_transitions(tr)
+    with pytest.raises(ValueError, match="rew"):
+        st.add_step(rew.double(), flag, None, 0.0, **rows)
+    with pytest.raises(ValueError, match="reset"):
+        st.add_step(rew, flag.cpu(), None, 0.0, **rows)
+    with pytest.raises(ValueError, match="row copies"):
+        st.add_step(rew, flag, None, 0.0, **dict(rows, next_states=rows["next_states"].double()))
+    with pytest.raises(ValueError, match="row copies"):
+        st.add_step(rew, flag, None, 0.0, **dict(rows, observations=rows["observations"].cpu()))
+    with pytest.raises(TypeError, match="unknown row"):
+        st.add_step(rew, flag, None, 0.0, estimator_labels=rows["observations"])
+    torch.cuda.synchronize()
+    assert st.step == 1 and st.saved_hidden_states_a is None and (st.dones == 0xAB).all() and (st.actions == SENTINEL).all()
+    assert all((getattr(st, n) == SENTINEL).all() for n in tensors)
+    st.step = T
+    with pytest.raises(AssertionError, match="overflow"):
+        st.add_step(rew.double(), flag, None, 0.0, **rows)                               # the overflow is reported first, as in the base class
+    tr.hidden_states = None
+    with pytest.raises(AssertionError, match="overflow"):
+        st.add_transitions(tr)
+
+    # the C entry point: one good item, then one field wrong at a time
+    lib = abi.load_lib()
+    src, dst = torch.zeros(6, 4, device=dev), torch.full((5, 4), SENTINEL, device=dev)
+    idx = torch.zeros(5, dtype=torch.int64, device=dev)
+
+    def item(**over):
+        a = (abi.LgGatherItem * 17)()
+        for it in a:
+            it.src, it.dst, it.index, it.rows, it.width, it.src_stride = src.data_ptr(), dst.data_ptr(), idx.data_ptr(), 5, 4, 4
+            it.kind, it.group, it.env_offset, it.n_envs = abi.GATHER_F32, 2, 0, 2
+        for k, v in over.items():
+            setattr(a[0], k, v)
+        return a
+    bad = [(dict(src=None), "null pointer"), (dict(dst=None), "null pointer"), (dict(index=None), "null pointer"), (dict(width=0), "width < 1"),
+           (dict(src_stride=3), "stride < width"), (dict(group=0), "group < 1"), (dict(group=2, env_offset=1), "env_offset \\+ group > n_envs"),
+           (dict(env_offset=-1, group=1), "env window"), (dict(rows=-1), "rows < 0"), (dict(kind=2), "unknown kind"),
+           (dict(rows=1 << 30, width=2, src_stride=2), "2\\^31 elements")]
+    stream = torch.cuda.current_stream().cuda_stream
+    for over, msg in bad:
+        with pytest.raises(RuntimeError, match="lg_rollout_gather: item 0: .*" + msg):
+            abi.check(lib.lg_rollout_gather(item(**over), 1, stream), lib)
+    for n in (0, 17):
+        with pytest.raises(RuntimeError, match="lg_rollout_gather: bad item list"):
+            abi.check(lib.lg_rollout_gather(item(), n, stream), lib)
+    with pytest.raises(RuntimeError, match="lg_rollout_gather: bad item list"):
+        abi.check(lib.lg_rollout_gather(None, 1, stream), lib)
+    z = torch.zeros(4, device=dev)
+    gg = lambda T_, N_, nf: lib.lg_rollout_gae_groups(T_, N_, nf, z.data_ptr(), z.data_ptr(), z.data_ptr(), z.data_ptr(), 0.99, 0.95, z.data_ptr(),
+                                                      z.data_ptr(), z.data_ptr(), z.data_ptr(), stream)
+    for T_, N_, nf, msg in ((2, 2, 0, "n_first"), (2, 2, 2, "n_first"), (1, 2, 1, "two entries per group"), (1, 3, 1, "two entries per group")):
+        with pytest.raises(RuntimeError, match="lg_rollout_gae_groups: .*" + msg):
+            abi.check(gg(T_, N_, nf), lib)
+    torch.cuda.synchronize()
+    assert (dst == SENTINEL).all() and (z == 0).all()
+    assert lib.lg_rollout_gather(item(), 16, stream) == 0                                # sixteen are taken
+    torch.cuda.synchronize()
+    assert (dst == 0).all()
