@@ -1,4 +1,4 @@
-"""ctypes mirror of include/lgsim.h (the C ABI) and the loader of the HIP library.
+"""ctypes mirror of include/lgsim.h, include/lgrollout.h and include/lgsensor.h (the C ABI) and the loader of the HIP library.
 
 Field order and types must match the header exactly; tests/test_abi.py compiles a C
 probe that prints sizeof/offsetof for every struct and compares them with these classes.
@@ -277,6 +277,8 @@ def load_lib():
     lib.lg_rollout_gae_groups.argtypes = [i32, i32, i32, vp, vp, vp, vp, f32, f32, vp, vp, vp, vp, vp]
     for f in ROLLOUT_EXPORTS[2:]:
         getattr(lib, f).restype = C.c_int
+    lib.lg_depth_render.argtypes = [C.POINTER(LgDepthCam), C.POINTER(LgDepthScene), vp, vp, vp]
+    lib.lg_depth_render.restype = C.c_int
     lib.lg_last_error.restype = C.c_char_p
     lib.lg_last_kernel.argtypes = [H]
     lib.lg_last_kernel.restype = C.c_char_p
@@ -293,6 +295,8 @@ EXPORTS = ["lg_create", "lg_destroy", "lg_set_task", "lg_set_terrain", "lg_bind"
            "lg_abi_version"]
 ROLLOUT_EXPORTS = ["lg_rollout_record", "lg_rollout_gae", "lg_rollout_traj_index", "lg_rollout_mask_index", "lg_rollout_pad",
                    "lg_rollout_unpad", "lg_rollout_gather", "lg_rollout_gae_groups"]          # include/lgrollout.h
+SENSOR_EXPORTS = ["lg_depth_render"]                                                          # include/lgsensor.h
+DEPTH_MAX_CELLS = 4096
 ROLLOUT_MAX_COPIES = 8
 ROLLOUT_MAX_GATHER = 16
 GATHER_F32, GATHER_NOT_U8 = 0, 1
@@ -314,6 +318,16 @@ class LgRowCopy(C.Structure):
 class LgGatherItem(C.Structure):
     _fields_ = [("src", C.c_void_p), ("dst", C.c_void_p), ("index", C.c_void_p), ("rows", i32), ("width", i32), ("src_stride", i32),
                 ("kind", i32), ("group", i32), ("env_offset", i32), ("n_envs", i32)]
+
+
+class LgDepthCam(C.Structure):
+    _fields_ = [("width", i32), ("height", i32), ("mount_pos", f32 * 3), ("mount_quat", f32 * 4), ("min_range", f32), ("max_range", f32),
+                ("near_clip", f32), ("far_clip", f32), ("normalize", i32)]
+
+
+class LgDepthScene(C.Structure):
+    _fields_ = [("n_envs", i32), ("base_pos", C.c_void_p), ("base_quat", C.c_void_p), ("heightfield", C.c_void_p), ("rows", i32), ("cols", i32),
+                ("hscale", f32), ("vscale", f32), ("border", f32)]
 
 
 def check(rc, lib=None):

@@ -102,7 +102,14 @@ class LeggedRobotCfg(Section):
     noise = section(
         add_noise=True, noise_level=1.0,
         noise_scales=section(dof_pos=0.01, dof_vel=0.5, lin_vel=0.1, ang_vel=0.2, gravity=0.05, height_measurements=0.1))
-    sensor = section(add_depth=False)
+    # legged_robot_config.py:224-244; `fov_horizontal` is the field the Genesis glue reads (genesis_simulator.py:808), set by the depth
+    # task's config only (go2_ts_depth_config.py:163): None here falls back to horizontal_fov_deg (depth_hfov_deg below)
+    sensor = section(
+        add_depth=False, use_warp=False,
+        depth_camera_config=section(
+            num_sensors=1, num_history=1, near_clip=0.1, far_clip=10.0, near_plane=0.1, far_plane=10.0, resolution=(80, 60),
+            horizontal_fov_deg=75, fov_horizontal=None, pos=(0.3, 0.0, 0.1), euler=(0.0, 0.0, 0.0), decimation=5,
+            calculate_depth=True, segmentation_camera=False, return_pointcloud=False, pointcloud_in_world_frame=False))
     viewer = section(ref_env=0, pos=[4.0, 4.0, 2.0], lookat=[0.0, 0.0, 0.0])
     sim = section(dt=0.005, substeps=1, max_collision_pairs=100, IK_max_targets=2, gravity=[0.0, 0.0, -9.81])
     # engine constants of this backend (no counterpart in the reference: Genesis' soft-constraint
@@ -190,6 +197,13 @@ def pd_gains(cfg):
 
 def default_dof_pos(cfg):
     return np.array([cfg.init_state.default_joint_angles[n] for n in cfg.asset.dof_names], np.float32)
+
+
+def depth_hfov_deg(cfg):
+    """Horizontal field of view of the depth camera, degrees: `fov_horizontal` when the config sets it, else `horizontal_fov_deg`."""
+    c = cfg.sensor.depth_camera_config
+    v = getattr(c, "fov_horizontal", None)
+    return float(v if v is not None else c.horizontal_fov_deg)
 
 
 def terrain_bounds(cfg):

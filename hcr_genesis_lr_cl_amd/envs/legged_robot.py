@@ -23,6 +23,7 @@ import torch
 
 from .. import abi
 from .. import config as cfgmod
+from ..sensor import depth_cadence_tick
 from ..simulator import HipSimulator
 
 
@@ -168,6 +169,11 @@ class LeggedRobot:
         self.common_step_counter += 1
         c = self.common_step_counter
         self._engine_step(actions, c)
+        if self._add_depth:
+            # go2_ts_depth.py:223-226, 238-239: the render follows the step launch on the same stream, so it sees the pose after resets
+            render, self.depth_image_update_counter = depth_cadence_tick(self.depth_image_update_counter, self.depth_image_update_decimation)
+            if render:
+                self.simulator.update_depth_images()
         self.extras["episode"] = _EpisodeExtras(self, c)
         return self.obs_buf, self.privileged_obs_buf, self.rew_buf, self.reset_buf, self.extras
 
@@ -203,6 +209,11 @@ class LeggedRobot:
     def get_observations(self):
         return self.obs_buf
 
+    @property
+    def depth_images(self):
+        """The simulator's (N, num_history, H, W) normalised range images; None without a depth camera."""
+        return self.simulator.depth_images
+
     # ---- checkpoint / resume (SURVEY 8(f)4) ---------------------------------------------------------------------------
     _HOST_STATE = ("common_step_counter", "command_ranges")
 
@@ -211,8 +222,11 @@ class LeggedRobot:
         observation histories, DR parameters, terrain levels / origins), the step counter that keys the Philox draws, and the
         host-side curriculum state (command ranges; task classes add theirs through `_HOST_STATE`)."""
         import copy
-        return {"engine": self._engine.state_dict(), "host": {k: copy.deepcopy(getattr(self, k)) for k in self._HOST_STATE},
-                "task": type(self).__name__, "seed": int(self._engine.task.seed), "env_id_offset": int(self._engine.task.env_id_offset)}
+        sd = {"engine": self._engine.state_dict(), "host": {k: copy.deepcopy(getattr(self, k)) for k in self._HOST_STATE},
+              "task": type(self).__name__, "seed": int(self._engine.task.seed), "env_id_offset": int(self._engine.task.env_id_offset)}
+        if self.cfg.sensor.add_depth:      # the image is only re-rendered every decimation + 1 steps: it and the counter are state
+            sd["depth"] = {"images": self.simulator.depth_images.detach().clone(), "counter": int(self.depth_image_update_counter)}
+        return sd
 
     def load_state_dict(self, sd):
         import copy
@@ -220,7 +234,14 @@ class LeggedRobot:
             raise ValueError(f"checkpoint of task {sd['task']} loaded into {type(self).__name__}")
         if int(sd["seed"]) != int(self._engine.task.seed) or int(sd["env_id_offset"]) != int(self._engine.task.env_id_offset):
             raise ValueError("checkpoint seed / env shard differ from this env's: the random streams would not continue")
+        if ("depth" in sd) != bool(self.cfg.sensor.add_depth):
+            raise ValueError("checkpoint and env differ in sensor.add_depth")
         self._engine.load_state_dict(sd["engine"])
+        if "depth" in sd:
+            if sd["depth"]["images"].shape != self.simulator.depth_images.shape:
+                raise ValueError(f"checkpoint depth images {tuple(sd['depth']['images'].shape)} != {tuple(self.simulator.depth_images.shape)}")
+            self.simulator.depth_images.copy_(sd["depth"]["images"])
+            self.depth_image_update_counter = int(sd["depth"]["counter"])
         for k, v in sd["host"].items():
             setattr(self, k, copy.deepcopy(v))
         self._upload_command_ranges()          # also rebinds nothing: the device copy is part of the buffers, this keeps host and device equal
@@ -293,6 +314,9 @@ class LeggedRobot:
         """legged_robot.py:380-409: aliases onto the engine's device buffers."""
         b = self._engine.buf
         self.common_step_counter = 0
+        self._add_depth = bool(self.cfg.sensor.add_depth)
+        self.depth_image_update_counter = 0                # go2_ts_depth.py:157-158, 195-196
+        self.depth_image_update_decimation = int(self.cfg.sensor.depth_camera_config.decimation)
         self.commands = b["commands"]
         self.actions, self.last_actions, self.llast_actions = b["actions"], b["last_actions"], b["llast_actions"]
         self.feet_air_time = b["feet_air_time"]

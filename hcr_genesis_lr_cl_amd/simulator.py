@@ -16,7 +16,7 @@ import os
 import numpy as np
 import torch
 
-from . import abi, builders
+from . import abi, builders, sensor
 from . import config as cfgmod
 from .engine import Engine
 from .model_compiler import compile_urdf, load_model
@@ -100,8 +100,20 @@ class HipSimulator:
         self._base_ang_vel_w[env_ids] = base_ang_vel[:]
 
     def update_sensors(self):
+        """genesis_simulator.py:135-138."""
         if self._cfg.sensor.add_depth:
-            raise NotImplementedError("depth cameras are outside this backend's scope (SURVEY.md row 23)")
+            self.update_depth_images()
+
+    def update_depth_images(self):
+        """genesis_simulator.py:741-750 in one launch on the current stream: ray-cast the terrain from the live base poses into
+        depth_images[:, 0], clipped and normalised in the kernel.  Without a depth camera there is nothing to do."""
+        if self.depth_images is None:
+            return None
+        stream = torch.cuda.current_stream(self._engine.device).cuda_stream
+        sensor.render(self._engine.lib, self._depth_cam, self._depth_scene, self._depth_ray_dirs, self.depth_images, stream)
+
+    def draw_debug_depth_images(self):
+        return None  # headless backend: nothing is drawn or saved
 
     def update_terrain_curriculum(self, env_ids, move_up, move_down):
         """genesis_simulator.py:140-148."""
@@ -129,8 +141,9 @@ class HipSimulator:
         self._control_dt = self._cfg.sim.dt * self._cfg.control.decimation
         d = self._cfg.domain_rand
         self._batch_dofs_links_info = d.randomize_joint_armature or d.randomize_joint_friction or d.randomize_joint_damping
+        self.depth_images = None
         if self._cfg.sensor.add_depth:
-            raise NotImplementedError("depth cameras are outside this backend's scope")
+            self._depth_cam = sensor.make_depth_cam(self._cfg)      # refuses num_history != 1 before anything is allocated
 
     def _load_model(self):
         a = self._cfg.asset
@@ -241,10 +254,23 @@ class HipSimulator:
             self._measured_heights = b["measured_heights"]
         else:  # genesis_simulator.py:494: zeros, never refreshed on a plane
             self._measured_heights = torch.zeros(self._num_envs, self._num_height_points, device=dev)
+        if cfg.sensor.add_depth:
+            self._init_depth_camera()
         # engine state starts at the nominal pose (the env resets everything before stepping)
         self._dof_pos[:] = self._default_dof_pos
         self._base_pos[:] = self._base_init_pos + self._env_origins
         self._base_quat[:] = self._base_init_quat
+
+    def _init_depth_camera(self):
+        """genesis_simulator.py:446-453, 803-819: the image buffer (N, num_history, H, W), the per-pixel direction table (float64 on
+        the host, float32 on the device) and the scene over the engine's live pose buffers and registered heightfield."""
+        c, dev = self._cfg.sensor.depth_camera_config, self._device
+        W, H = int(c.resolution[0]), int(c.resolution[1])
+        dirs = sensor.ray_directions(W, H, cfgmod.depth_hfov_deg(self._cfg))
+        self._depth_ray_dirs = torch.from_numpy(dirs.astype(np.float32)).to(dev).contiguous()
+        self.depth_images = torch.zeros((self._num_envs, int(c.num_history), H, W), device=dev)
+        hs = getattr(self._engine, "height_samples", None) if self._terrain is not None else None
+        self._depth_scene = sensor.make_depth_scene(self._num_envs, self._base_pos, self._base_quat, self._opts, hs)
 
     def _init_height_points(self):
         """genesis_simulator.py:496-507."""
