@@ -29,6 +29,8 @@ def configs():
             ("go2-allterms", "go2", False, {}, True)]
     # go2's single frame has no history to shift; these two run the generic tail (lg_launch_quad<4, true, PR, 0, 3>) without slack
     out += [(t + "-slack0", t, False, {"LG_OBS_SLACK": "0"}, False) for t in ("go2_wtw", "go2_ee")]
+    # the whole step in one leg-per-lane launch (lg_launch_env<LEGS, LG_PHASE_ALL, 0, JPL, false>): the instantiations that spill
+    out += [(t + "-layout1", t, False, {"LG_SIM_LAYOUT": "1"}, False) for t in ("go2_ee", "tron1_pf_ee", "tron1_sf")]
     return out
 
 

@@ -88,8 +88,6 @@ def test_fused_launch_equals_split_launches(task, monkeypatch):
     go2_ts / go2_cts / go2_dreamwaq (the same kind of tail again: terrain curriculum, terrain samples kept in the lanes that took them,
     20 / 5-frame stacks, labels / observation programs interpreted in component layout).  For the bipeds path (a) is what their env.step() issues -- component-per-lane physics launch, then the
     leg-per-lane MDP launch (tron1_sf: four-joint legs in both)."""
-    import torch
-    from hcr_genesis_lr_cl_amd import abi
     from hcr_genesis_lr_cl_amd.envs import make_env
     N = 256
     start = 480                                                      # crosses the push step (500) for go2_ee
@@ -116,6 +114,15 @@ def test_fused_launch_equals_split_launches(task, monkeypatch):
         assert len(e1.reward_scales) >= 26
     else:
         e1, e2 = make_env(task, N, "cuda:0")[0], make_env(task, N, "cuda:0")[0]
+    _one_step_routes_agree(e1, e2, N, start, want)
+
+
+def _one_step_routes_agree(e1, e2, N, start, want=None, want_sim=None):
+    """40 control steps, each from the same state: e1.step() (lg_last_kernel naming `want`) against SIM (naming `want_sim`), then
+    PRE | POST | RESET on e2 -- identical integers, floats to 1e-5 or the `loose` table (round-off of a stiff contact solve between two
+    instantiations of the same source)."""
+    import torch
+    from hcr_genesis_lr_cl_amd import abi
     e1.reset(); e2.reset()
     g = torch.Generator(device="cuda"); g.manual_seed(5)
     # spread the episode clocks so that time-outs, command and behaviour resampling fall inside the window
@@ -136,6 +143,8 @@ def test_fused_launch_equals_split_launches(task, monkeypatch):
         e2.common_step_counter += 1
         ca = float(e2.cfg.normalization.clip_actions)
         e2._engine.step(abi.PHASE_SIM, torch.clip(act, -ca, ca), e2.common_step_counter)       # Simulator.step: pre-clipped actions
+        if want_sim is not None:
+            assert want_sim in e2._engine.last_kernel(), e2._engine.last_kernel()
         e2._engine.step(abi.PHASE_PRE | abi.PHASE_POST | abi.PHASE_RESET, act, e2.common_step_counter)
         torch.cuda.synchronize()
         assert e1._engine.obs_window() == e2._engine.obs_window()
@@ -150,6 +159,71 @@ def test_fused_launch_equals_split_launches(task, monkeypatch):
                 assert torch.equal(a, b), f"{k} @ {t}"
         n_reset += int(e1.reset_buf.sum())
     assert n_reset > 0
+
+
+ALL_LEG_PER_LANE = "lg_launch_env<LEGS, LG_PHASE_ALL, 0, JPL, false>"      # lg_host.hip Kernels<>::all, ::all_flat (go2 on the plane)
+ALL_LEG_PER_LANE_FLAT = "lg_launch_env<4, LG_PHASE_ALL, 1, 3, false>"
+
+
+@pytest.mark.parametrize("task", ["go2", "go2_wtw", "go2_ee", "go2_ts", "go2_cts", "go2_dreamwaq", "tron1_pf_ee", "tron1_pf", "tron1_sf", "go2_wtw-shift"])
+def test_one_launch_leg_per_lane_step_equals_split_launches(task, monkeypatch):
+    """The large-batch route (LG_SIM_LAYOUT=1; automatic above 8192 quadruped / 16384 biped envs): (a) env.step(), ONE launch of
+    env_step_kernel<.., LG_PHASE_ALL> -- the only instantiation that parks the MDP working set (episode sums, soft limits, noise
+    vector, commands, episode clock, fail count, air time, origin, obs_dirty) in LDS across the physics and hands the read-backs,
+    guard_bad, the last_* snapshots and the terrain samples to the MDP phases in registers -- against (b) SIM in
+    env_step_kernel<.., LG_PHASE_SIM>, then PRE | POST | RESET, which pass all of that through memory.  Same loop, tolerances and
+    re-sync as test_fused_launch_equals_split_launches.  250 envs: a leg-per-lane wave carries 16 quadruped / 32 biped envs, so the
+    last workgroup is partly dead for both robot shapes.  Every registered task but go2_cat, whose env.step() already is (b)'s two
+    calls (envs/go2_ts.py Go2CaT: PRE | SIM, then POST | RESET), so (a) and (b) would coincide; go2_wtw-shift is go2_wtw with the
+    in-place history shift (LG_OBS_SLACK=0)."""
+    from hcr_genesis_lr_cl_amd.envs import make_env
+    monkeypatch.setenv("LG_SIM_LAYOUT", "1")
+    if task.endswith("-shift"):
+        task = task[:-6]
+        monkeypatch.setenv("LG_OBS_SLACK", "0")
+    N = 250
+    e1, e2 = make_env(task, N, "cuda:0")[0], make_env(task, N, "cuda:0")[0]
+    _one_step_routes_agree(e1, e2, N, 480, ALL_LEG_PER_LANE_FLAT if task == "go2" else ALL_LEG_PER_LANE, "lg_launch_env<LEGS, LG_PHASE_SIM, 0, JPL, false>")
+
+
+def test_automatic_layout_switch_over_and_last_partial_workgroup(monkeypatch):
+    """lg_host.hip plan() without LG_SIM_LAYOUT: component-per-lane while threads * 4 <= 2048 * 64, i.e. up to 8192 quadruped / 16384
+    biped envs, the one-launch leg-per-lane step from the next env on.  go2 at 8193 envs is 513 workgroups of 16 envs, the last one
+    with a single live env: 30 seeded steps, then envs [0, 64) and env 8192 equal, bit for bit, a 64-env and a 1-env shard of the same
+    8193-env job run in layout 1 (obs, rew, done of every step)."""
+    import torch
+    from hcr_genesis_lr_cl_amd.envs import make_env
+    monkeypatch.delenv("LG_SIM_LAYOUT", raising=False)
+    for task, n, want in (("go2", 8192, "lg_launch_quad"), ("tron1_pf", 16384, "lg_launch_quad<2"), ("tron1_pf", 16385, "lg_launch_env<LEGS, LG_PHASE_ALL")):
+        env = make_env(task, n, "cuda:0")[0]
+        env.reset()
+        assert int(env._engine.opts.sim_layout) == 0
+        env.step(torch.zeros(n, env.num_actions, device="cuda"))
+        assert want in env._engine.last_kernel() and " + " not in env._engine.last_kernel(), (task, n, env._engine.last_kernel())
+        del env
+    N = 8193
+    g = torch.Generator(device="cuda"); g.manual_seed(3)
+    acts = [torch.randn(N, 12, generator=g, device="cuda") for _ in range(30)]
+    shards = ((0, 64), (8192, 1))        # (first env, envs): a whole leading workgroup's worth, and the lone live env of workgroup 512
+
+    def run(env, lo, keep):
+        """obs, rew, done of every step, cut to the `keep` ranges of the job's env ids."""
+        env.reset()
+        outs = []
+        for a in acts:
+            obs, _, rew, done, _ = env.step(a[lo:lo + env.num_envs].contiguous())
+            assert ALL_LEG_PER_LANE_FLAT in env._engine.last_kernel(), env._engine.last_kernel()
+            outs.append([[x[o - lo:o - lo + m].clone() for x in (obs, rew, done)] for o, m in keep])
+        torch.cuda.synchronize()
+        return outs
+    env = _mk(N)
+    assert int(env._engine.opts.sim_layout) == 0
+    full = run(env, 0, shards)
+    monkeypatch.setenv("LG_SIM_LAYOUT", "1")
+    for i, (lo, n) in enumerate(shards):
+        part = run(_mk(n, env_id_offset=lo, global_num_envs=N), lo, [(lo, n)])
+        for t, (f, p_) in enumerate(zip(full, part)):
+            assert all(torch.equal(x, y) for x, y in zip(f[i], p_[0])), (lo, n, t)
 
 
 def test_long_random_rollout_is_sane():
@@ -250,6 +324,18 @@ def test_full_size_batch_properties():
 def test_long_rollout_stays_sane(task):
     """1500 control steps of aggressive random actions (sigma 2) on every BASELINE task at 1024 envs: state and outputs
     stay finite and bounded, resets keep happening (robots fall) and robots never leave the terrain bounds."""
+    _long_rollout(task, 1500)
+
+
+@pytest.mark.parametrize("task", ["go2_ee", "tron1_pf_ee", "tron1_sf"])
+def test_long_rollout_stays_sane_leg_per_lane(task, monkeypatch):
+    """The same bounds over 300 steps through the one-launch leg-per-lane step (LG_SIM_LAYOUT=1): the heightfield quadruped, the biped
+    and the four-joint legs, whose whole-step instantiations are the ones that spill (profiles/r03_register_table.md)."""
+    monkeypatch.setenv("LG_SIM_LAYOUT", "1")
+    _long_rollout(task, 300, ALL_LEG_PER_LANE)
+
+
+def _long_rollout(task, steps, want=None):
     import torch
     from hcr_genesis_lr_cl_amd.envs import make_env
     env, cfg = make_env(task, 1024, "cuda:0")
@@ -257,12 +343,13 @@ def test_long_rollout_stays_sane(task):
     g = torch.Generator(device="cuda"); g.manual_seed(7)
     A = env.num_actions
     resets = 0
-    for t in range(1500):
+    for t in range(steps):
         out = env.step(2.0 * torch.randn(1024, A, generator=g, device="cuda"))
         if t % 100 == 99:
             obs, rew, done = out[0], out[-3], out[-2]
             assert torch.isfinite(obs).all() and torch.isfinite(rew).all(), (task, t)
             resets += int(done.sum())
+    assert want is None or want in env._engine.last_kernel(), env._engine.last_kernel()
     b = env._engine.buf
     for k in ("dof_pos", "dof_vel", "base_pos", "base_quat", "base_lin_vel_w", "base_ang_vel_w", "link_contact_forces", "torques"):
         assert torch.isfinite(b[k]).all(), (task, k)

@@ -97,12 +97,18 @@ def test_reused_contact_w_matches_oracle(layout, every):
     assert np.abs(refs[1].st.arr["dof_vel"] - refs[0].st.arr["dof_vel"]).max() > 1e-4
 
 
-def test_nonfinite_state_is_counted_and_ends_the_episode():
+@pytest.mark.parametrize("layout", [None, 1], ids=["auto", "leg-per-lane"])
+def test_nonfinite_state_is_counted_and_ends_the_episode(layout, monkeypatch):
     """the non-finite guard re-seats the robot, and it is never silent -- LgBuffers.nonfinite_count goes up and the env
-    terminates in the same step (reset_buf = 1, not a time-out), in the fused launch and in the split launches."""
+    terminates in the same step (reset_buf = 1, not a time-out), in the fused launch and in the split launches; in the one-launch
+    leg-per-lane step (LG_SIM_LAYOUT=1) too, where the guard's flag reaches the MDP phases in a register."""
     import torch
     from hcr_genesis_lr_cl_amd.envs import make_env
-    for task in ("go2", "tron1_pf_ee", "go2_cat"):
+    if layout is None:
+        monkeypatch.delenv("LG_SIM_LAYOUT", raising=False)
+    else:
+        monkeypatch.setenv("LG_SIM_LAYOUT", str(layout))
+    for task in ("go2", "tron1_pf_ee", "go2_cat", "tron1_sf"):      # tron1_sf: four joints per leg
         env, cfg = make_env(task, 64)
         env.reset()
         g = torch.Generator(device="cuda"); g.manual_seed(3)
@@ -121,6 +127,8 @@ def test_nonfinite_state_is_counted_and_ends_the_episode():
         assert int(eng.buf["fail_buf"][5]) == 0 and int(eng.buf["episode_length_buf"][5]) == 0     # the reset went through
         env.step(torch.randn(64, env.num_actions, generator=g, device="cuda"))
         assert eng.nonfinite_count() == 2, task
+        if layout == 1 and task != "go2_cat":
+            assert "LG_PHASE_ALL" in eng.last_kernel(), eng.last_kernel()
 
 
 @pytest.mark.parametrize("task", ["go2_ee", "tron1_pf_ee", "tron1_sf"])
