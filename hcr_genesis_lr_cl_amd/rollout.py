@@ -36,6 +36,28 @@ import torch
 
 from . import abi
 
+_F32, _NOT = abi.GATHER_F32, abi.GATHER_NOT_U8
+_PPO_BATCH = (("actions", _F32), ("values", _F32), ("advantages", _F32), ("returns", _F32), ("actions_log_prob", _F32), ("mu", _F32), ("sigma", _F32))
+
+
+def _call(dev, name, *args):
+    """Entry point `name` of include/lgrollout.h on the current stream of `dev` (each takes the stream last); a refusal is a RuntimeError."""
+    lib = abi.load_lib()
+    abi.check(getattr(lib, name)(*args, torch.cuda.current_stream(dev).cuda_stream), lib)
+
+
+def _row_copies(items, refusal):
+    """An LgRowCopy array from (src, dst, width, stride) items: rows of `width` floats, `stride` floats apart in src and packed in dst.
+    ValueError(refusal) for anything but float32 tensors on one device, a dst that is not contiguous, or a src that is neither contiguous
+    nor (where stride != width) a view with unit inner stride."""
+    arr = (abi.LgRowCopy * max(len(items), 1))()
+    for c, (src, dst, width, stride) in zip(arr, items):
+        if (src.dtype != torch.float32 or dst.dtype != torch.float32 or src.device != dst.device or not dst.is_contiguous()
+                or not (src.is_contiguous() or (stride != width and src.stride(-1) == 1))):
+            raise ValueError(refusal)
+        c.src, c.dst, c.width, c.src_stride = src.data_ptr(), dst.data_ptr(), width, stride
+    return arr
+
 
 class RolloutStorage:
     """The reference's constructor plus two keywords: `env` (zero-copy observation rows, see `attach_env`) and `lstm_critic_hidden`.
@@ -43,9 +65,16 @@ class RolloutStorage:
     `lstm_critic_hidden` decides what `reccurent_mini_batch_generator` hands the critic of an LSTM policy.  The reference's line
     rollout_storage.py:231 reads `hid_c_batch = hid_c_batch[0] if len(hid_c_batch)==1 else hid_a_batch`: with an LSTM (two tensors per
     network) the critic is given the ACTOR's start states.  "reference" (the default) reproduces that, so PPO.update computes what it
-    computes on rsl_rl's own storage; "own" yields the critic's own (h, c).  A GRU is unaffected: its critic always gets its own."""
+    computes on rsl_rl's own storage; "own" yields the critic's own (h, c).  A GRU is unaffected: its critic always gets its own.
 
-    class Transition:                      # rollout_storage.py:37-52
+    The storages of the other learners are this class with their own two tables and the tensors those name."""
+
+    # (add_step keyword = Transition attribute, storage tensor), in the order of the reference's add_transitions
+    STEP_ROWS = (("observations", "observations"), ("critic_observations", "privileged_observations"))
+    # (storage tensor or "critic", gather kind) in the order the learner's update() unpacks, before `(None, None), None`
+    BATCH = (("observations", _F32), ("critic", _F32)) + _PPO_BATCH
+
+    class Transition:                     # rollout_storage.py:37-52
         def __init__(self):
             self.observations = None
             self.critic_observations = None
@@ -90,7 +119,7 @@ class RolloutStorage:
         self.advantages = z(T, N, 1)
         self.mu = z(T, N, *actions_shape)
         self.sigma = z(T, N, *actions_shape)
-        self._scratch = z(2, dtype=torch.float64)
+        self._scratch = z(4, dtype=torch.float64)            # (sum, sum of squares) of the raw advantages, per group of envs
         self.saved_hidden_states_a = self.saved_hidden_states_c = None
         self._traj = self._traj_head = None                 # trajectory index buffers, allocated by the first recurrent generator call
         self.step = 0
@@ -125,34 +154,41 @@ class RolloutStorage:
         return self._env is not None
 
     # ---- filling rows -------------------------------------------------------------------------------------------------
-    def add_step(self, rew, reset, time_outs, gamma, observations=None, critic_observations=None, extra_copies=(), hidden_states=None):
-        """One launch for everything the env contributes to row `self.step`: rewards (+ gamma * value * time_out), dones and
-        the observation rows (skipped when they are zero-copy).  `values[self.step]` must already hold the critic's output for
-        this step (the bootstrap reads it).  Policy-side rows (actions, values, log-prob, mean, std) are written by the caller
-        straight into `self.actions[self.step]` ... as outputs of its own ops.  `hidden_states` is what a recurrent policy held BEFORE it acted
-        on this step, as `add_transitions` takes it; its rows go out in the same launch."""
+    def add_step(self, rew, reset, time_outs, gamma, extra_copies=(), hidden_states=None, **rows):
+        """One launch for everything the env contributes to row `self.step`: rewards (+ gamma * value * time_out), dones and the rows
+        named in STEP_ROWS, given as keywords (each an (N, width) float32 tensor; `observations` is skipped when it is zero-copy, and so is
+        a row the storage does not hold).  `values[self.step]` must already hold the critic's output for this step (the bootstrap reads
+        it).  Policy-side rows (actions, values, log-prob, mean, std) are written by the caller straight into `self.actions[self.step]`
+        ... as outputs of its own ops.  `hidden_states` is what a recurrent policy held BEFORE it acted on this step, as `add_transitions`
+        takes it; its rows go out in the same launch."""
+        self._record(gamma, *self._step_args(rew, reset, time_outs, extra_copies, hidden_states, rows))
+
+    def _step_args(self, rew, reset, time_outs, extra_copies, hidden_states, rows):
+        """What the record launch of step `self.step` takes, with every refusal of `add_step`: nothing is enqueued or written here."""
         t = self.step
         if t >= self.num_transitions_per_env:
             raise AssertionError("Rollout buffer overflow")
+        known, copies = dict(self.STEP_ROWS), []
+        for k, src in rows.items():
+            if k not in known:
+                raise TypeError(f"{type(self).__name__}.add_step: unknown row {k!r}; expected one of {', '.join(known)}")
+            dst = getattr(self, known[k])
+            if src is not None and dst is not None and not (k == "observations" and self.zero_copy):
+                copies.append((src, dst[t]))
+        copies += list(extra_copies)
         rew = self._env_row("rew", rew, (torch.float32,))
         rst = self._env_row("reset", reset, (torch.bool, torch.uint8))
         to = None if time_outs is None else self._env_row("time_outs", time_outs, (torch.bool, torch.uint8))
-        copies = self._hidden_copies(t, hidden_states)
-        if observations is not None and not self.zero_copy:
-            copies.append((observations, self.observations[t]))
-        if critic_observations is not None and self.privileged_observations is not None:
-            copies.append((critic_observations, self.privileged_observations[t]))
-        copies += list(extra_copies)
-        arr = (abi.LgRowCopy * max(len(copies), 1))()
-        for i, (src, dst) in enumerate(copies):
-            if (src.dim() != 2 or src.stride(1) != 1 or not dst.is_contiguous() or src.shape != dst.shape or src.dtype != torch.float32
-                    or dst.dtype != torch.float32 or src.shape[0] != self.num_envs or src.device != dst.device):
-                raise ValueError("row copies take (N, width) float32 views with unit inner stride")
-            arr[i].src, arr[i].dst, arr[i].width, arr[i].src_stride = src.data_ptr(), dst.data_ptr(), src.shape[1], src.stride(0)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        abi.check(self.lib.lg_rollout_record(self.num_envs, rew.data_ptr(), rst.data_ptr(), 0 if to is None else to.data_ptr(),
-                                             self.values[t].data_ptr(), float(gamma), self.rewards[t].data_ptr(), self.dones[t].data_ptr(),
-                                             arr, len(copies), stream), self.lib)
+        copies = self._hidden_copies(t, hidden_states, len(copies)) + copies
+        refusal = "row copies take (N, width) float32 views with unit inner stride"
+        if any(src.dim() != 2 or src.shape != dst.shape or src.shape[0] != self.num_envs for src, dst in copies):
+            raise ValueError(refusal)
+        return rew, rst, to, _row_copies([(src, dst, src.shape[1], src.stride(0)) for src, dst in copies], refusal), len(copies)
+
+    def _record(self, gamma, rew, rst, to, arr, n_copies):
+        t = self.step
+        _call(self.device, "lg_rollout_record", self.num_envs, rew.data_ptr(), rst.data_ptr(), 0 if to is None else to.data_ptr(),
+              self.values[t].data_ptr(), float(gamma), self.rewards[t].data_ptr(), self.dones[t].data_ptr(), arr, n_copies)
         self.step += 1
 
     def _env_row(self, name, x, dtypes):
@@ -172,39 +208,32 @@ class RolloutStorage:
         `transition.rewards`): policy-side rows by copy_, env-side rows by the record kernel.  The reference's `copy_` converts whatever
         dtype it is given (its BaseTask.reset_buf is torch.int), so rewards and dones that are not already what the kernel reads are
         converted the same way first: dones to the uint8 of the stored row, rewards to float32."""
-        t = self.step
-        if t >= self.num_transitions_per_env:
-            raise AssertionError("Rollout buffer overflow")
         rew, dones = transition.rewards.reshape(-1), transition.dones.reshape(-1)
         if rew.dtype != torch.float32 or not rew.is_contiguous():
             rew = rew.to(torch.float32).contiguous()
         if dones.dtype not in (torch.bool, torch.uint8) or not dones.is_contiguous():
             dones = dones.to(torch.uint8).contiguous()
-        self._env_row("rewards", rew, (torch.float32,)), self._env_row("dones", dones, (torch.bool, torch.uint8))   # before any row is written
-        rows = self._transition_rows(transition)
+        rows = {k: getattr(transition, k, None) for k, _ in self.STEP_ROWS}
+        args = self._step_args(rew, dones, None, (), getattr(transition, "hidden_states", None), rows)      # refuses before any row is written
+        t = self.step
         self.actions[t].copy_(transition.actions)
         self.values[t].copy_(transition.values)
         self.actions_log_prob[t].copy_(transition.actions_log_prob.view(-1, 1))
         self.mu[t].copy_(transition.action_mean)
         self.sigma[t].copy_(transition.action_sigma)
-        self.add_step(rew, dones, None, 0.0, hidden_states=getattr(transition, "hidden_states", None), **rows)
+        self._record(0.0, *args)
 
-    def _transition_rows(self, transition):
-        """The env-side rows of `transition` as keywords of `add_step`; the storages of the other learners name their own rows here."""
-        crit = transition.critic_observations if self.privileged_observations is not None else None
-        return dict(observations=transition.observations, critic_observations=crit)
-
-    def _hidden_copies(self, t, hidden_states):
+    def _hidden_copies(self, t, hidden_states, n_other):
         """Row copies that store a recurrent policy's hidden states at step t (rollout_storage.py:104-119).  None or (None, None): nothing
         (the first act of a fresh policy, so row 0 of the first rollout stays zero).  A GRU gives one (L, N, H) tensor per network, an LSTM
-        an (h, c) tuple; `saved_hidden_states_a` / `_c` are lists of (T, L, N, H) tensors allocated on first use."""
-        if hidden_states is None:
+        an (h, c) tuple; `saved_hidden_states_a` / `_c` are lists of (T, L, N, H) tensors allocated on first use -- which is why states that
+        do not fit the record launch next to the step's `n_other` copies are refused here, before that allocation, and not by the launch."""
+        if hidden_states is None or (hidden_states[0] is None and hidden_states[1] is None):
             return []
-        hid_a, hid_c = hidden_states
-        if hid_a is None and hid_c is None:
-            return []
-        hid_a = tuple(hid_a) if isinstance(hid_a, (tuple, list)) else (hid_a,)
-        hid_c = tuple(hid_c) if isinstance(hid_c, (tuple, list)) else (hid_c,)
+        hid_a, hid_c = (tuple(h) if isinstance(h, (tuple, list)) else (h,) for h in hidden_states)
+        n = n_other + len(hid_a) + len(hid_c)
+        if n > abi.ROLLOUT_MAX_COPIES:
+            raise ValueError(f"{type(self).__name__}: {n} row copies in one step, the record launch takes {abi.ROLLOUT_MAX_COPIES}")
         T, N = self.num_transitions_per_env, self.num_envs
         if self.saved_hidden_states_a is None:
             for h in hid_a + hid_c:
@@ -229,11 +258,13 @@ class RolloutStorage:
 
     def compute_returns(self, last_values, gamma, lam):
         """rollout_storage.py:124-138 in two launches."""
+        self._gae("lg_rollout_gae", (), last_values, gamma, lam, self.advantages)
+
+    def _gae(self, name, groups, last_values, gamma, lam, *advantages):
         lv = last_values.reshape(-1).contiguous().float()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        abi.check(self.lib.lg_rollout_gae(self.num_transitions_per_env, self.num_envs, self.values.data_ptr(), self.rewards.data_ptr(),
-                                          self.dones.data_ptr(), lv.data_ptr(), float(gamma), float(lam), self.returns.data_ptr(),
-                                          self.advantages.data_ptr(), self._scratch.data_ptr(), stream), self.lib)
+        _call(self.device, name, self.num_transitions_per_env, self.num_envs, *groups, self.values.data_ptr(), self.rewards.data_ptr(),
+              self.dones.data_ptr(), lv.data_ptr(), float(gamma), float(lam), self.returns.data_ptr(), *(a.data_ptr() for a in advantages),
+              self._scratch.data_ptr())
 
     def get_statistics(self):
         """(mean trajectory length, mean reward) of the stored rollout -- what rollout_storage.py:140-146 reports: a trajectory ends at
@@ -245,15 +276,25 @@ class RolloutStorage:
         return lengths.float().mean(), self.rewards.mean()
 
     def mini_batch_generator(self, num_mini_batches, num_epochs=8):
-        """Mini-batches in the tuple order rsl_rl's PPO.update unpacks (rollout_storage.py:148-186): obs, critic obs, actions, target
-        values, advantages, returns, old log-prob, old mean, old std, hidden states (None, None), masks None.  One random permutation of
-        the T x N samples per call, cut into `num_mini_batches` equal index blocks and replayed every epoch."""
-        critic = "privileged_observations" if self.privileged_observations is not None else "observations"
-        names = ("observations", critic, "actions", "values", "advantages", "returns", "actions_log_prob", "mu", "sigma")
+        """Mini-batches in the tuple order the learner's update() unpacks: BATCH, then hidden states (None, None) and masks None; for this
+        class (rollout_storage.py:148-186) obs, critic obs, actions, target values, advantages, returns, old log-prob, old mean, old std.
+        One random permutation of the T x N samples per call, cut into `num_mini_batches` equal index blocks and replayed every epoch;
+        each yield is one gather launch into fresh tensors."""
         per = (self.num_envs * self.num_transitions_per_env) // num_mini_batches
         perm = torch.randperm(num_mini_batches * per, device=self.device)
-        for batch in self._gather_batches([(getattr(self, k), abi.GATHER_F32, 0, None) for k in names], [(perm, per)], num_mini_batches, num_epochs):
+        entries = [(self._batch_source(name), kind, 0, None) for name, kind in self.BATCH]
+        for batch in self._gather_batches(entries, [(perm, per)], num_mini_batches, num_epochs):
             yield (*batch, (None, None), None)
+
+    def _batch_source(self, name):
+        """The tensor behind an entry of BATCH.  "critic" is what the critic reads: the privileged observations if they are stored, else the
+        actor's input -- the observations, or where none are stored (the explicit estimator, rollout_storage_ee.py:116-123) the estimator
+        features and labels side by side, concatenated once per generator call."""
+        if name != "critic":
+            return getattr(self, name)
+        if self.privileged_observations is not None:
+            return self.privileged_observations
+        return self.observations if hasattr(self, "observations") else torch.cat((self.estimator_features, self.estimator_labels), dim=-1)
 
     def _gather_batches(self, entries, index_sets, num_mini_batches, num_epochs):
         """The tensors of every mini-batch, one `lg_rollout_gather` launch per mini-batch.  `entries`: (source, kind, index set, window) per
@@ -307,9 +348,8 @@ class RolloutStorage:
         if self._traj is None:
             self._traj = torch.empty(3, T * N, dtype=torch.int32, device=self.device)
             self._traj_head = torch.empty(2 + N + 1, dtype=torch.int32, device=self.device)      # n_traj, max_len, traj_offset[N + 1]
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        abi.check(self.lib.lg_rollout_traj_index(T, N, self.dones.data_ptr(), self._traj_head[2:].data_ptr(), self._traj.data_ptr(), T * N,
-                                                 self._traj_head.data_ptr(), stream), self.lib)
+        _call(self.device, "lg_rollout_traj_index", T, N, self.dones.data_ptr(), self._traj_head[2:].data_ptr(), self._traj.data_ptr(), T * N,
+              self._traj_head.data_ptr())
         host = self._traj_head.cpu().tolist()
         return self._traj, host[0], host[1], host[2:]
 
@@ -321,31 +361,23 @@ class RolloutStorage:
         traj, n_traj, max_len, _ = index if index is not None else self.trajectory_index()
         dev = self.device
 
-        def row_copies(items, what):
-            arr = (abi.LgRowCopy * max(len(items), 1))()
-            for i, (src, dst, width) in enumerate(items):
-                if not src.is_contiguous() or src.dtype != torch.float32 or src.device != dst.device:
-                    raise ValueError(f"{what} must be contiguous float32 tensors on {dev}")
-                arr[i].src, arr[i].dst, arr[i].width, arr[i].src_stride = src.data_ptr(), dst.data_ptr(), width, width
-            return arr
-
-        src_items, hid_items, layers = [], [], []
+        src_items, hid_items = [], []
         for x in tensors:
             if x.dim() < 2 or x.shape[0] != T or x.shape[1] != N:
                 raise ValueError(f"padded tensors are ({T}, {N}, ...), got {tuple(x.shape)}")
-            out = torch.empty(max_len, n_traj, *x.shape[2:], device=dev)
-            src_items.append((x, out, x[0, 0].numel()))
+            width = x[0, 0].numel()
+            src_items.append((x, torch.empty(max_len, n_traj, *x.shape[2:], device=dev), width, width))
         for h in hidden:
             if h.dim() != 4 or h.shape[0] != T or h.shape[2] != N:
                 raise ValueError(f"saved hidden states are ({T}, layers, {N}, hidden), got {tuple(h.shape)}")
-            hid_items.append((h, torch.empty(h.shape[1], n_traj, h.shape[3], device=dev), h.shape[3]))
-            layers.append(h.shape[1])
+            hid_items.append((h, torch.empty(h.shape[1], n_traj, h.shape[3], device=dev), h.shape[3], h.shape[3]))
+        layers = [h.shape[1] for h in hidden]
         mask = torch.empty(T, n_traj, dtype=torch.bool, device=dev) if masks else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        abi.check(self.lib.lg_rollout_pad(T, N, traj.data_ptr(), traj.shape[1], n_traj, max_len, row_copies(src_items, "padded tensors"),
-                                          len(src_items), row_copies(hid_items, "saved hidden states"), (C.c_int32 * max(len(layers), 1))(*layers),
-                                          len(hid_items), 0 if mask is None else mask.data_ptr(), stream), self.lib)
-        return [o for _, o, _ in src_items], [o for _, o, _ in hid_items], mask
+        _call(dev, "lg_rollout_pad", T, N, traj.data_ptr(), traj.shape[1], n_traj, max_len,
+              _row_copies(src_items, f"padded tensors must be contiguous float32 tensors on {dev}"), len(src_items),
+              _row_copies(hid_items, f"saved hidden states must be contiguous float32 tensors on {dev}"), (C.c_int32 * max(len(layers), 1))(*layers),
+              len(hid_items), 0 if mask is None else mask.data_ptr())
+        return [it[1] for it in src_items], [it[1] for it in hid_items], mask
 
     def reccurent_mini_batch_generator(self, num_mini_batches, num_epochs=8):
         """Mini-batches for a recurrent policy in the tuple order rsl_rl's PPO.update unpacks (rollout_storage.py:187-236; the spelling is
@@ -383,66 +415,7 @@ class RolloutStorage:
                        self.mu[:, start:stop], self.sigma[:, start:stop], (hid_a, hid_c), masks[:, first:last])
 
 
-class _LearnerStorage(RolloutStorage):
-    """What the storages of the explicit-estimator, teacher-student, CTS and DreamWaQ learners share: their env-side rows named in a table,
-    a fused `add_step` that takes them as keywords, and a mini-batch generator that is one gather launch per yield."""
-
-    STEP_ROWS = ()          # (add_step keyword = Transition attribute, storage tensor), in the order of the reference's add_transitions
-    BATCH = ()              # (storage tensor, gather kind) in the order the learner's update() unpacks, before `(None, None), None`
-
-    def add_step(self, rew, reset, time_outs, gamma, extra_copies=(), hidden_states=None, **rows):
-        """RolloutStorage.add_step with this learner's rows as keywords (the names in STEP_ROWS, each an (N, width) float32 tensor): reward,
-        done and every row in the one record launch.  More rows than the launch takes is a ValueError before anything is enqueued."""
-        t = self.step
-        if t >= self.num_transitions_per_env:
-            raise AssertionError("Rollout buffer overflow")
-        known = dict(self.STEP_ROWS)
-        copies = []
-        for k, src in rows.items():
-            if k not in known:
-                raise TypeError(f"{type(self).__name__}.add_step: unknown row {k!r}; expected one of {', '.join(known)}")
-            dst = getattr(self, known[k])
-            if src is not None and dst is not None:
-                copies.append((src, dst[t]))
-        copies += list(extra_copies)
-        n = len(copies) + self._hidden_count(hidden_states)
-        if n > abi.ROLLOUT_MAX_COPIES:
-            raise ValueError(f"{type(self).__name__}.add_step: {n} row copies in one step, the record launch takes {abi.ROLLOUT_MAX_COPIES}")
-        RolloutStorage.add_step(self, rew, reset, time_outs, gamma, extra_copies=copies, hidden_states=hidden_states)
-
-    @staticmethod
-    def _hidden_count(hidden_states):
-        """How many row copies `_hidden_copies` will ask for, without allocating anything."""
-        if hidden_states is None or (hidden_states[0] is None and hidden_states[1] is None):
-            return 0
-        return sum(len(h) if isinstance(h, (tuple, list)) else 1 for h in hidden_states)
-
-    def _transition_rows(self, transition):
-        rows = {k: getattr(transition, k) for k, _ in self.STEP_ROWS}
-        n = sum(v is not None and getattr(self, dst) is not None for (_, dst), v in zip(self.STEP_ROWS, rows.values()))
-        n += self._hidden_count(getattr(transition, "hidden_states", None))
-        if n > abi.ROLLOUT_MAX_COPIES:
-            raise ValueError(f"{type(self).__name__}.add_transitions: {n} row copies in one step, the record launch takes {abi.ROLLOUT_MAX_COPIES}")
-        return rows
-
-    def _batch_source(self, name):
-        return getattr(self, name)
-
-    def mini_batch_generator(self, num_mini_batches, num_epochs=8):
-        """The learner's tuple (BATCH, then `(None, None), None`): one random permutation of the T x N samples per call, cut into
-        `num_mini_batches` equal index blocks and replayed every epoch; each yield is one gather launch into fresh tensors."""
-        per = (self.num_envs * self.num_transitions_per_env) // num_mini_batches
-        perm = torch.randperm(num_mini_batches * per, device=self.device)
-        entries = [(self._batch_source(name), kind, 0, None) for name, kind in self.BATCH]
-        for batch in self._gather_batches(entries, [(perm, per)], num_mini_batches, num_epochs):
-            yield (*batch, (None, None), None)
-
-
-_F32, _NOT = abi.GATHER_F32, abi.GATHER_NOT_U8
-_PPO_BATCH = (("actions", _F32), ("values", _F32), ("advantages", _F32), ("returns", _F32), ("actions_log_prob", _F32), ("mu", _F32), ("sigma", _F32))
-
-
-class RolloutStorageEE(_LearnerStorage):
+class RolloutStorageEE(RolloutStorage):
     """rsl_rl/storage/rollout_storage_ee.py (PPO_EE, the explicit estimator): no actor observations are stored; the actor's input is the
     estimator features and labels.  `add_step` keywords: critic_observations, estimator_features, estimator_labels.  Mini-batches are the
     13 entries of rollout_storage_ee.py:152-154; `terminated` is float32 1 - dones, formed by the gather."""
@@ -465,15 +438,8 @@ class RolloutStorageEE(_LearnerStorage):
         self.estimator_features = torch.zeros(T, N, *estimator_feature_shape, device=self.device)
         self.estimator_labels = torch.zeros(T, N, *estimator_label_shape, device=self.device)
 
-    def _batch_source(self, name):
-        if name != "critic":
-            return getattr(self, name)
-        if self.privileged_observations is not None:
-            return self.privileged_observations
-        return torch.cat((self.estimator_features, self.estimator_labels), dim=-1)       # rollout_storage_ee.py:116-123, once per call
 
-
-class RolloutStorageTS(_LearnerStorage):
+class RolloutStorageTS(RolloutStorage):
     """rsl_rl/storage/rollout_storage_ts.py (PPO_TS, teacher-student): privileged observations feed the privilege encoder, critic
     observations the critic.  `add_step` keywords: observations, privileged_observations, observation_histories, critic_observations.
     Mini-batches are the 14 entries of rollout_storage_ts.py:115-117."""
@@ -500,7 +466,7 @@ class RolloutStorageTS(_LearnerStorage):
         self.critic_observations = torch.zeros(T, N, *critic_obs_shape, device=self.device)
 
 
-class RolloutStorageDreamWaQ(_LearnerStorage):
+class RolloutStorageDreamWaQ(RolloutStorage):
     """rsl_rl/storage/rollout_storage_dreamwaq.py (PPO_DreamWaQ).  `add_step` keywords: observations, privileged_observations,
     observation_histories, explicit_info_labels, next_states -- five rows, so a recurrent policy's hidden states on top (an LSTM has four
     tensors) do not fit one record launch and are refused.  Mini-batches are the 15 entries of rollout_storage_dreamwaq.py:121-123."""
@@ -547,16 +513,10 @@ class RolloutStorageCTS(RolloutStorageTS):
         T, N = self.num_transitions_per_env, self.num_envs
         self.teacher_advantages = torch.zeros(T, self.num_teacher, 1, device=self.device)
         self.student_advantages = torch.zeros(T, N - self.num_teacher, 1, device=self.device)
-        self._scratch = torch.zeros(4, dtype=torch.float64, device=self.device)
 
     def compute_returns(self, last_values, gamma, lam):
         """rollout_storage_cts.py:81-114 in four launches (memset, GAE, one normalisation per group)."""
-        lv = last_values.reshape(-1).contiguous().float()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        abi.check(self.lib.lg_rollout_gae_groups(self.num_transitions_per_env, self.num_envs, self.num_teacher, self.values.data_ptr(),
-                                                 self.rewards.data_ptr(), self.dones.data_ptr(), lv.data_ptr(), float(gamma), float(lam),
-                                                 self.returns.data_ptr(), self.teacher_advantages.data_ptr(), self.student_advantages.data_ptr(),
-                                                 self._scratch.data_ptr(), stream), self.lib)
+        self._gae("lg_rollout_gae_groups", (self.num_teacher,), last_values, gamma, lam, self.teacher_advantages, self.student_advantages)
 
     def mini_batch_generator(self, num_mini_batches, num_epochs=8):
         """Mini-batch sizes are the reference's: num_teacher * T // n for the teacher, (N - num_teacher) * T // n for the student, their sum
@@ -580,7 +540,6 @@ class _Unpad(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, trajectories, masks):
-        lib = abi.load_lib()
         dev = trajectories.device
         if dev.type != "cuda" or trajectories.dtype != torch.float32 or trajectories.dim() < 2:
             raise ValueError("unpad_trajectories takes a (rows, n_traj, ...) float32 tensor on a HIP device (no CPU fallback)")
@@ -592,27 +551,23 @@ class _Unpad(torch.autograd.Function):
         width = x[0, 0].numel()
         index = torch.empty(3, n_traj, dtype=torch.int32, device=dev)
         head = torch.empty(2, dtype=torch.int32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        abi.check(lib.lg_rollout_mask_index(T, n_traj, m.data_ptr(), index.data_ptr(), n_traj, head.data_ptr(), stream), lib)
+        _call(dev, "lg_rollout_mask_index", T, n_traj, m.data_ptr(), index.data_ptr(), n_traj, head.data_ptr())
         steps, longest = head.cpu().tolist()                           # the one read-back: the env count sizes the output
         if steps % T or longest > rows:
             raise ValueError(f"masks cover {steps} steps with a longest trajectory of {longest}: not whole envs of {T} steps within {rows} rows")
         n = steps // T
         out = torch.empty(T, n, *x.shape[2:], device=dev)              # the trajectories tile (T, n): every element is written
-        abi.check(lib.lg_rollout_unpad(T, n, index.data_ptr(), n_traj, n_traj, rows, x.data_ptr(), out.data_ptr(), width, stream), lib)
+        _call(dev, "lg_rollout_unpad", T, n, index.data_ptr(), n_traj, n_traj, rows, x.data_ptr(), out.data_ptr(), width)
         ctx.index, ctx.dims = index, (T, n, n_traj, rows, width, tuple(x.shape))
         return out
 
     @staticmethod
     def backward(ctx, grad):
-        lib = abi.load_lib()
         T, n, n_traj, rows, width, shape = ctx.dims
         g = grad.contiguous()
         out = torch.empty(shape, device=g.device)
-        arr = (abi.LgRowCopy * 1)()
-        arr[0].src, arr[0].dst, arr[0].width, arr[0].src_stride = g.data_ptr(), out.data_ptr(), width, width
-        stream = torch.cuda.current_stream(g.device).cuda_stream
-        abi.check(lib.lg_rollout_pad(T, n, ctx.index.data_ptr(), n_traj, n_traj, rows, arr, 1, None, None, 0, 0, stream), lib)
+        arr = _row_copies([(g, out, width, width)], "the gradient of unpad_trajectories is a float32 tensor")
+        _call(g.device, "lg_rollout_pad", T, n, ctx.index.data_ptr(), n_traj, n_traj, rows, arr, 1, None, None, 0, 0)
         return out, None
 
 

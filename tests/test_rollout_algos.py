@@ -13,6 +13,7 @@ envs; tests/golden/gen_rollout_algos_fixtures.py) and against float64 restatemen
   * grouped GAE, GROUP_CASES: returns within 4 * err_ref + 1 ulp(max |returns|) of the float64 recurrence (err_ref: the error of the
     float32 restatement, oracle/rollout_oracle.py, on the same inputs), each group's normalised advantages within 4 ulp of its scale of
     the float64 normalisation of that group's own float32 returns - values;
+  * `lg_rollout_gae` and `lg_rollout_gae_groups` on one input (N = 257, n_first in {1, 128, 256}): the same returns bit for bit;
   * refusals before any launch.
 
 Measured on an MI355X (gfx950) over GROUP_CASES (gamma 0.99, lam 0.95; first / rest: the two groups' normalised advantages): the returns'
@@ -444,6 +445,43 @@ def test_grouped_gae_matches_f64(N, n_first, T, rate):
 def test_group_cases_cover_the_issue():
     assert {(c[0], c[1]) for c in GROUP_CASES} == set(GROUP_SIZES) and {c[3] for c in GROUP_CASES} == {0.0, 0.08, 1.0}
     assert {(c[0], c[1]) for c in GROUP_CASES if c[2] == 1} == {(130, 65), (4097, 1024)} and len(GROUP_CASES) == 21
+
+
+@pytest.mark.gpu
+def test_both_gae_entry_points_are_one_recurrence():
+    """`lg_rollout_gae` and `lg_rollout_gae_groups` instantiate one kernel body: on one input (N = 257: envs of both groups in the first
+    256-lane block, one env in a second block) they write the same `returns` bit for bit, and every normalised advantage tensor, taken back
+    through its own mean and std, is `returns - values` at the tolerance of test_grouped_gae_matches_f64 (4 ulp of the largest normalised
+    advantage, here scaled by the std the values were divided by)."""
+    import torch
+    from tests.test_rollout import gae_inputs, gae_storage, ulp32
+    N, T, gamma, lam = 257, 24, ah.GAMMA, ah.LAM
+    host = gae_inputs(N, T, 0.05, seed=257)
+    last = torch.from_numpy(host["last_values"]).to("cuda:0")
+    c = lambda x: x.cpu().numpy()
+
+    def unnormalised_matches(got, raw, what):
+        a = raw.astype(np.float64)
+        mean, std = a.mean(), a.std(ddof=1) + 1e-8
+        tol = 4.0 * ulp32(np.abs((a - mean) / std).max()) * std
+        err = float(np.abs(got.astype(np.float64) * std + mean - a).max())
+        print(f"{what}: std {std:.4f} err {err:.3e} tol {tol:.3e}")
+        assert got.shape == raw.shape and err <= tol, (what, err, tol)
+
+    one = gae_storage(N, T, host)
+    one.compute_returns(last, gamma, lam)
+    returns = c(one.returns)
+    raw = returns - host["values"]                                                       # float32, as the kernel forms it
+    assert np.isfinite(returns).all()
+    unnormalised_matches(c(one.advantages), raw, "one group")
+    for n_first in (1, 128, 256):
+        st = storage_class("CTS")(N, n_first, T, [1], [1], [1], [1], [1], "cuda:0")
+        for k in ("values", "rewards", "dones"):
+            getattr(st, k).copy_(torch.from_numpy(host[k]))
+        st.compute_returns(last, gamma, lam)
+        np.testing.assert_array_equal(c(st.returns).view(np.uint32), returns.view(np.uint32), err_msg=f"n_first={n_first}")
+        unnormalised_matches(c(st.teacher_advantages), raw[:, :n_first], f"n_first={n_first} first")
+        unnormalised_matches(c(st.student_advantages), raw[:, n_first:], f"n_first={n_first} rest")
 
 
 # ---- GPU: refusals, all before any launch --------------------------------------------------------------------------------------------------
