@@ -1,4 +1,4 @@
-"""ctypes mirror of include/lgsim.h, include/lgrollout.h and include/lgsensor.h (the C ABI) and the loader of the HIP library.
+"""ctypes mirror of include/lgsim.h, include/lgrollout.h, include/lgsensor.h and include/lgpolicy.h (the C ABI) and the loader of the HIP library.
 
 Field order and types must match the header exactly; tests/test_abi.py compiles a C
 probe that prints sizeof/offsetof for every struct and compares them with these classes.
@@ -279,6 +279,9 @@ def load_lib():
         getattr(lib, f).restype = C.c_int
     lib.lg_depth_render.argtypes = [C.POINTER(LgDepthCam), C.POINTER(LgDepthScene), vp, vp, vp]
     lib.lg_depth_render.restype = C.c_int
+    lib.lg_policy_act.argtypes = [C.POINTER(LgPolicyArgs), vp]
+    lib.lg_policy_row_tile.argtypes = [C.POINTER(LgPolicyArgs)]
+    lib.lg_policy_act.restype = lib.lg_policy_row_tile.restype = C.c_int
     lib.lg_last_error.restype = C.c_char_p
     lib.lg_last_kernel.argtypes = [H]
     lib.lg_last_kernel.restype = C.c_char_p
@@ -296,6 +299,10 @@ EXPORTS = ["lg_create", "lg_destroy", "lg_set_task", "lg_set_terrain", "lg_bind"
 ROLLOUT_EXPORTS = ["lg_rollout_record", "lg_rollout_gae", "lg_rollout_traj_index", "lg_rollout_mask_index", "lg_rollout_pad",
                    "lg_rollout_unpad", "lg_rollout_gather", "lg_rollout_gae_groups"]          # include/lgrollout.h
 SENSOR_EXPORTS = ["lg_depth_render"]                                                          # include/lgsensor.h
+POLICY_EXPORTS = ["lg_policy_act", "lg_policy_row_tile"]                                      # include/lgpolicy.h
+POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 2048
+POLICY_DETERMINISTIC, POLICY_VALUES_ONLY = 1, 2
+POLICY_STREAM_TAG = 0x504F4C49
 DEPTH_MAX_CELLS = 4096
 ROLLOUT_MAX_COPIES = 8
 ROLLOUT_MAX_GATHER = 16
@@ -328,6 +335,23 @@ class LgDepthCam(C.Structure):
 class LgDepthScene(C.Structure):
     _fields_ = [("n_envs", i32), ("base_pos", C.c_void_p), ("base_quat", C.c_void_p), ("heightfield", C.c_void_p), ("rows", i32), ("cols", i32),
                 ("hscale", f32), ("vscale", f32), ("border", f32)]
+
+
+class LgPolicyLayer(C.Structure):
+    _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p), ("n_in", i32), ("n_out", i32), ("elu", i32), ("reserved", i32)]
+
+
+class LgPolicyChain(C.Structure):
+    _fields_ = [("input", C.c_void_p), ("out", C.c_void_p), ("n_layers", i32), ("in_width", i32), ("in_stride", i32), ("out_stride", i32),
+                ("layer", LgPolicyLayer * POLICY_MAX_LAYERS)]
+
+
+class LgPolicyArgs(C.Structure):
+    _fields_ = [("n_envs", i32), ("flags", u32), ("estimator", LgPolicyChain), ("actor", LgPolicyChain), ("critic", LgPolicyChain),
+                ("clip_actions", f32), ("clip_on", i32), ("std", C.c_void_p), ("noise", C.c_void_p),
+                ("noise_stride", i32), ("actions_stride", i32), ("mu_stride", i32), ("sigma_stride", i32),
+                ("actions", C.c_void_p), ("mu", C.c_void_p), ("sigma", C.c_void_p), ("log_prob", C.c_void_p),
+                ("log_prob_stride", i32), ("reserved", i32), ("seed", u64), ("counter", C.c_void_p), ("dbg_uniform", C.c_void_p)]
 
 
 def check(rc, lib=None):

@@ -1,0 +1,220 @@
+"""Developer tool (GPU only, never read by bench.py): time of the policy half of one rollout step at N = 4096 envs for three net sets (dims:
+bench.py::ppo_rollout) -- go2 (actor 45-512-256-128-12, critic 45-512-256-128-1), go2_ee (estimator 900-256-128-24, actor 924-..-12,
+critic 870-1024-256-128-1) and tron1_pf_ee (310 / 327 / 1340, 17 labels, 6 actions) -- produced three ways into the same storage row:
+
+  (i)   the fused launch, `FusedPolicy.act(obs, critic_obs, storage=st)` (Philox draw, so with its one-lane counter launch);
+  (ii)  the torch ops of bench.py::policy_row (f32 GEMMs, ELUs, randn, log-prob arithmetic, five copy_) captured once and replayed as one
+        HIP graph;
+  (iii) the same ops dispatched eagerly;
+  (iv)  go2 only: the loop act -> env.step -> add_step for 24 steps on zero-copy observation rows, with (i) and with (ii), in env-steps/s.
+
+(i)-(iii): each sample is the device-event time around a burst of launches divided by the burst length, so it is the time per step on the
+device queue with launches back to back; the sides alternate in one process after a warm-up, median and p10-p90 over the repeats are
+printed.  (iv): host clock around whole 24-step loops ending in a synchronise.  Before anything is timed the fused launch's mu and values are
+compared with the torch ops' on the same inputs.  FLOP are counted from the shapes: 2 * in * out per layer and env.
+
+    python tools/policy_act_time.py [--repeats 30] [--burst 50] [--envs 4096]
+
+Prints a table and one JSON line."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+import torch  # noqa: E402
+import torch.nn as nn  # noqa: E402
+
+F32_MFMA_FLOPS = 157e12          # exact-f32 MFMA rate, MI355X_MICROARCH.md
+SETS = {"go2": dict(obs=45, est=None, actor=[512, 256, 128], A=12, cobs=45, critic=[512, 256, 128]),
+        "go2_ee": dict(obs=900, est=([256, 128], 24), actor=[512, 256, 128], A=12, cobs=870, critic=[1024, 256, 128]),
+        "tron1_pf_ee": dict(obs=310, est=([256, 128], 17), actor=[512, 256, 128], A=6, cobs=1340, critic=[1024, 256, 128])}
+
+
+def mlp(i, hidden, o, tail=None):
+    layers, d = [], i
+    for h in hidden:
+        layers += [nn.Linear(d, h), nn.ELU()]
+        d = h
+    layers.append(nn.Linear(d, o))
+    if tail is not None:
+        layers.append(tail)
+    return nn.Sequential(*layers)
+
+
+class Nets(nn.Module):
+    is_recurrent = False
+
+    def __init__(self, d):
+        super().__init__()
+        E = d["est"][1] if d["est"] else 0
+        if d["est"]:
+            self.estimator = mlp(d["obs"], d["est"][0], E)
+        self.actor = mlp(d["obs"] + E, d["actor"], d["A"], nn.Hardtanh(-100.0, 100.0))
+        self.critic = mlp(d["cobs"], d["critic"], 1)
+        self.std = nn.Parameter(torch.ones(d["A"]))
+
+
+def flops_per_env(m):
+    return sum(2 * l.in_features * l.out_features for l in m.modules() if isinstance(l, nn.Linear))
+
+
+def weight_bytes(m):
+    return sum(4 * (l.in_features + 1) * l.out_features for l in m.modules() if isinstance(l, nn.Linear))
+
+
+def torch_row(m, obs, cobs, st, t, lab_row):
+    """bench.py::policy_row on the rows it is given."""
+    if hasattr(m, "estimator"):
+        lab = m.estimator(obs)
+        lab_row.copy_(lab)
+        mu = m.actor(torch.cat((obs, lab), dim=-1))
+    else:
+        mu = m.actor(obs)
+    st.mu[t].copy_(mu)
+    std = m.std.expand_as(mu)
+    st.sigma[t].copy_(std)
+    act = mu + std * torch.randn_like(mu)
+    st.actions[t].copy_(act)
+    st.actions_log_prob[t, :, 0].copy_((-0.5 * ((act - mu) / std) ** 2 - m.std.log() - 0.9189385332046727).sum(-1))
+    st.values[t].copy_(m.critic(cobs))
+
+
+def capture(fn):
+    s = torch.cuda.Stream()
+    s.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(s):
+        for _ in range(3):
+            fn()
+    torch.cuda.current_stream().wait_stream(s)
+    g = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(g):
+        fn()
+    return g
+
+
+def stat(v):
+    s = sorted(v)
+    return dict(median=statistics.median(v), min=s[0], max=s[-1], p10=s[len(s) // 10], p90=s[(9 * len(s)) // 10])
+
+
+def burst_us(fn, burst):
+    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    a.record()
+    for _ in range(burst):
+        fn()
+    b.record()
+    b.synchronize()
+    return a.elapsed_time(b) * 1e3 / burst
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--repeats", type=int, default=30)
+    ap.add_argument("--burst", type=int, default=50)
+    ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--loops", type=int, default=20, help="24-step loops per sample of (iv)")
+    args = ap.parse_args()
+    if not torch.cuda.is_available():
+        sys.exit("policy_act_time.py: no GPU -- a time is only measured on the device")
+    from hcr_genesis_lr_cl_amd import build as b
+    from hcr_genesis_lr_cl_amd.policy import FusedPolicy
+    from hcr_genesis_lr_cl_amd.rollout import RolloutStorage
+    N, dev, T = args.envs, "cuda:0", 24
+    res = dict(tool="policy_act_time", envs=N, repeats=args.repeats, burst=args.burst, f32_mfma_flops=F32_MFMA_FLOPS, source_hash=b.source_hash(),
+               device=torch.cuda.get_device_name(0), sets={})
+    torch.manual_seed(1)
+    with torch.inference_mode():
+        for name, d in SETS.items():
+            m = Nets(d).to(dev)
+            fp = FusedPolicy(m, seed=1)
+            st = RolloutStorage(N, 2, [d["obs"]], [d["cobs"]], [d["A"]], dev)
+            obs, cobs = torch.randn(N, d["obs"], device=dev), torch.randn(N, d["cobs"], device=dev)
+            lab_row = torch.zeros(N, d["est"][1], device=dev) if d["est"] else None
+            st.step = 0
+            fp.act(obs, cobs, storage=st, labels=lab_row)
+            torch_row(m, obs, cobs, st, 1, lab_row)
+            torch.cuda.synchronize()
+            agree = {k: float((getattr(st, k)[0] - getattr(st, k)[1]).abs().max()) for k in ("mu", "values", "sigma")}
+            if agree["mu"] > 1e-4 or agree["values"] > 1e-4 or agree["sigma"] != 0.0:
+                sys.exit(f"policy_act_time.py: {name}: the fused launch and the torch ops disagree ({agree}) -- nothing timed")
+            graph = capture(lambda: torch_row(m, obs, cobs, st, 1, lab_row))
+            sides = {"fused": lambda: fp.act(obs, cobs, storage=st, labels=lab_row), "torch_graph": graph.replay,
+                     "torch_eager": lambda: torch_row(m, obs, cobs, st, 1, lab_row)}
+            for _ in range(args.warmup):
+                for f in sides.values():
+                    burst_us(f, args.burst)
+            times = {k: [] for k in sides}
+            for _ in range(args.repeats):
+                for k, f in sides.items():
+                    times[k].append(burst_us(f, args.burst))
+            flop = flops_per_env(m) * N
+            out = dict(flop_per_step=flop, weight_bytes=weight_bytes(m), row_tile=fp.row_tile(), step_us={k: stat(v) for k, v in times.items()},
+                       max_abs_diff_vs_torch=agree)
+            out["fused_flops"] = flop / (out["step_us"]["fused"]["median"] * 1e-6)
+            out["fraction_of_f32_mfma_rate"] = out["fused_flops"] / F32_MFMA_FLOPS
+            res["sets"][name] = out
+            print(f"{name}: {flop / 1e9:.2f} GFLOP per step, {out['weight_bytes'] / 1e6:.2f} MB of weights, row tile {out['row_tile']}, "
+                  f"|mu - torch| {agree['mu']:.1e}, |values - torch| {agree['values']:.1e}")
+            for k, v in out["step_us"].items():
+                print(f"  {k:12s}: median {v['median']:8.1f} us   min {v['min']:8.1f}   p10-p90 {v['p10']:8.1f} - {v['p90']:8.1f}   max {v['max']:8.1f}")
+            print(f"  fused: {out['fused_flops'] / 1e12:.1f} TFLOP/s = {100 * out['fraction_of_f32_mfma_rate']:.1f} % of the {F32_MFMA_FLOPS / 1e12:.0f} TFLOP/s f32-MFMA rate")
+            del fp, st, graph, sides
+        res["loop_go2"] = loop_go2(N, T, dev, args)
+    lp = res["loop_go2"]
+    for k in ("fused", "torch_graph"):
+        v = lp["env_steps_per_s"][k]
+        print(f"go2 loop act -> step -> add_step, {T} steps, {k:12s}: median {v['median'] / 1e6:6.2f} M env-steps/s   p10-p90 {v['p10'] / 1e6:6.2f} - {v['p90'] / 1e6:6.2f}")
+    print(json.dumps(res))
+
+
+def loop_go2(N, T, dev, args):
+    from hcr_genesis_lr_cl_amd.config import GO2Cfg
+    from hcr_genesis_lr_cl_amd.envs import GO2, set_seed
+    from hcr_genesis_lr_cl_amd.policy import FusedPolicy
+    from hcr_genesis_lr_cl_amd.rollout import RolloutStorage
+    cfg = GO2Cfg()
+    cfg.env.num_envs = N
+    cfg.hip.obs_sets = T + 1
+    set_seed(int(cfg.seed))
+    env = GO2(cfg, None, dev, True)
+    env.reset()
+    m = Nets(SETS["go2"]).to(dev)
+    fp = FusedPolicy(m, seed=1)
+    st = RolloutStorage(N, T, [45], [None], [12], dev, env=env)
+    graphs = [capture(lambda t=t: torch_row(m, st.observations[t], st.observations[t], st, t, None)) for t in range(T)]
+
+    def loop(kind):
+        for t in range(T):
+            if kind == "fused":
+                fp.act(st.observations[t], st.observations[t], storage=st)
+            else:
+                graphs[t].replay()
+            out = env.step(st.actions[t])
+            st.add_step(out[-3], out[-2], out[-1]["time_outs"], 0.99)
+        st.clear()
+
+    def sample(kind):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(args.loops):
+            loop(kind)
+        torch.cuda.synchronize()
+        return N * T * args.loops / (time.perf_counter() - t0)
+
+    kinds = ("fused", "torch_graph")
+    for _ in range(args.warmup):
+        for k in kinds:
+            sample(k)
+    rates = {k: [] for k in kinds}
+    for _ in range(args.repeats):
+        for k in kinds:
+            rates[k].append(sample(k))
+    return dict(steps=T, loops_per_sample=args.loops, zero_copy=bool(st.zero_copy), env_steps_per_s={k: stat(v) for k, v in rates.items()})
+
+
+if __name__ == "__main__":
+    main()
