@@ -303,6 +303,7 @@ POLICY_EXPORTS = ["lg_policy_act", "lg_policy_row_tile"]                        
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 2048
 POLICY_DETERMINISTIC, POLICY_VALUES_ONLY = 1, 2
 POLICY_STREAM_TAG = 0x504F4C49
+POLICY_LATENT_TAG = 0x4C41544E
 DEPTH_MAX_CELLS = 4096
 ROLLOUT_MAX_COPIES = 8
 ROLLOUT_MAX_GATHER = 16
@@ -346,12 +347,20 @@ class LgPolicyChain(C.Structure):
                 ("layer", LgPolicyLayer * POLICY_MAX_LAYERS)]
 
 
+class LgPolicyHead(C.Structure):
+    _fields_ = [(f"{h}_{k}", C.c_void_p) for h in ("latent_mu", "latent_var", "vel_mu", "vel_var") for k in ("w", "b")] + [
+        ("H", i32), ("L", i32), ("E", i32), ("logvar_clip", f32), ("noise", C.c_void_p), ("latent_out", C.c_void_p),
+        ("params_out", C.c_void_p), ("dbg_latent_uniform", C.c_void_p), ("noise_stride", i32), ("latent_stride", i32),
+        ("params_stride", i32), ("reserved", i32)]
+
+
 class LgPolicyArgs(C.Structure):
     _fields_ = [("n_envs", i32), ("flags", u32), ("estimator", LgPolicyChain), ("actor", LgPolicyChain), ("critic", LgPolicyChain),
                 ("clip_actions", f32), ("clip_on", i32), ("std", C.c_void_p), ("noise", C.c_void_p),
                 ("noise_stride", i32), ("actions_stride", i32), ("mu_stride", i32), ("sigma_stride", i32),
                 ("actions", C.c_void_p), ("mu", C.c_void_p), ("sigma", C.c_void_p), ("log_prob", C.c_void_p),
-                ("log_prob_stride", i32), ("reserved", i32), ("seed", u64), ("counter", C.c_void_p), ("dbg_uniform", C.c_void_p)]
+                ("log_prob_stride", i32), ("reserved", i32), ("seed", u64), ("counter", C.c_void_p), ("dbg_uniform", C.c_void_p),
+                ("encoder_b", LgPolicyChain), ("n_split", i32), ("has_split", i32), ("head", LgPolicyHead)]
 
 
 def check(rc, lib=None):

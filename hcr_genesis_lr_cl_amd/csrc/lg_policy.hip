@@ -17,6 +17,16 @@
 // row blocks of accumulators, NT * RB >= 2 independent chains wherever the layer is wide enough to matter.  No width is assumed to be a
 // tile multiple: the K tail is loaded element by element with zeros behind K on BOTH operands, neurons >= out and rows >= N are computed
 // on clamped addresses and never stored.
+//
+// Row groups (CTS, rsl_rl/algorithms/ppo_cts.py:110-135).  With `encoder_b` / `n_split` the policy tiles (blockIdx.y = 0) are two runs: tiles
+// [0, tiles_a) carry env rows [0, n_split) through seq[0] (estimator -> actor), the rest carry [n_split, N) through seq[1] (encoder_b -> the
+// same actor layers).  A tile never straddles the split: it knows its sequence's [row_begin, row_end), rows behind row_end are staged as
+// zeros and never stored, and every global row address is row0 + row < row_end.  The critic (blockIdx.y = 1) stays one run over [0, N).
+//
+// VAE head (DreamWaQ, rsl_rl/modules/vae.py:65-101).  The four heads are FOUR LAYERS that read the same activation (the encoder's output)
+// and write disjoint columns of the next one, [latent_mu | latent_logvar | vel_mu | vel_logvar] (a layer names its source and destination
+// activation; the clip of the two log-variances is the layer clip the actor's end already has).  `reparam` then forms the actor's input
+// [obs | z | vel] in the other buffer: sample = eps * exp(0.5 logvar) + mu, or the means in deterministic mode.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string>
@@ -30,7 +40,7 @@ typedef float f4u __attribute__((ext_vector_type(4), aligned(4)));   // weight r
 typedef __attribute__((address_space(3))) float lds_f;               // activations: explicit LDS pointers (ds_* instead of flat_*)
 typedef __attribute__((address_space(3))) f4 lds_f4;
 
-static const int kThreads = 256, kWaves = 4, kMaxSeqLayers = 2 * LG_POLICY_MAX_LAYERS;
+static const int kThreads = 256, kWaves = 4, kMaxSeqLayers = 3 * LG_POLICY_MAX_LAYERS;   // leading chain, four heads, actor
 static const size_t kLdsBytes = 160u * 1024u;      // gfx950: 160 KB per workgroup
 
 struct KLayer {
@@ -40,22 +50,38 @@ struct KLayer {
     int K, M, elu, clip_on;
     float clip;
     int out_col, gstride, cat_w, cat_stride;
+    int src, dst;           // activation read and written; activation i lives in buffer i & 1 with row stride PSeq::stride[i] ...
+    int sa, so;             // ... which `plan` copies here (stride[src], stride[dst]) so that a layer's operands are one read of its KLayer
 };
-struct KSeq {
+struct KSeq {                            // one sequence as the kernel walks it: its layers are l[first .. first + n_layers) of KArgs
     const float *in;
-    int in_w, in_stride, n_layers, epilogue;
-    int stride[kMaxSeqLayers + 1];      // LDS row stride of activation i; activation i lives in buffer i & 1
-    KLayer l[kMaxSeqLayers];
+    int in_w, in_stride, stride0;       // the staged input and its LDS row stride
+    int first, n_layers, epilogue;
+    int row_begin, row_end;             // the env rows this sequence serves
+    int reparam_after;                  // index of the last head layer (the reparameterisation follows it), or -1
 };
+struct KHead {                           // the reparameterisation behind the four head layers
+    const float *obs, *noise;           // the actor's features (N, F); eps (N, L + E) or NULL: Philox
+    float *latent_out, *dbg_uniform;
+    int F, L, E, obs_stride, noise_stride, latent_stride, determ;
+    int sx;                             // LDS row stride of the activation [obs | z | vel]
+};
+// every layer of the launch, packed: two group sequences of leading chain + actor and the critic (CTS, 20), or leading chain + four
+// heads + actor and the critic (DreamWaQ, 16).  A sequence takes only the slots it uses, so the block stays near the size it had.
+static const int kMaxLayers = 5 * LG_POLICY_MAX_LAYERS;
 struct KArgs {
-    KSeq seq[2];
+    KSeq seq[3];
+    KLayer l[kMaxLayers];
+    KHead head;
     int N, R, q_off, A;
+    int tiles_a, seq_y1;                // policy tiles below tiles_a run seq[0], the others seq[1]; blockIdx.y = 1 runs seq[seq_y1]
     const float *std, *noise;
     float *actions, *mu, *sigma, *log_prob, *dbg_uniform;
     const unsigned *counter;
     int noise_stride, actions_stride, mu_stride, sigma_stride, log_prob_stride;
     unsigned seed_lo, seed_hi;
 };
+static_assert(sizeof(KArgs) <= 4096, "KArgs is passed by value: the kernel-argument segment is 4 KB");
 
 // one layer for the workgroup's row tile: nxt[row][out_col + n] = act(b[n] + sum_k W[n][k] cur[row][k])
 template <int RB, int NT>
@@ -140,24 +166,86 @@ __device__ __forceinline__ void stage_rows(const float *src, int w, int stride, 
     }
 }
 
+// four uniforms of one Philox block and the four normals Box-Muller makes of them: (x, y) and (z, w) give two each
+__device__ __forceinline__ void draw4(unsigned env, unsigned quad, unsigned counter, unsigned tag, unsigned seed_lo, unsigned seed_hi, float *u, float *z) {
+    const U4 c = {env, quad, counter, tag};
+    const U4 x = philox4x32_10(c, seed_lo, seed_hi);
+    u[0] = u01(x.x); u[1] = u01(x.y); u[2] = u01(x.z); u[3] = u01(x.w);
+#pragma unroll
+    for (int p = 0; p < 2; p++) {
+        const float rad = sqrtf(-2.0f * logf(1.0f - u[2 * p])), th = 6.283185307179586f * u[2 * p + 1];
+        z[2 * p] = rad * cosf(th);
+        z[2 * p + 1] = rad * sinf(th);
+    }
+}
+
+// par[row] = [latent_mu (L) | latent_logvar (L) | vel_mu (E) | vel_logvar (E)] -> x[row] = [obs (F) | z (L) | vel (E)]: one lane per
+// (env row, quad of the L + E sampled columns); vae.py:84-92, or the means alone (vae.py:98-101) in deterministic mode
+__device__ __forceinline__ void reparam(const KArgs &a, const lds_f *par, int sp, lds_f *x, int sx, int R, int rows, int row0) {
+    const KHead &hd = a.head;
+    const int L = hd.L, E = hd.E, W = L + E, Q = (W + 3) >> 2;
+    stage_rows(hd.obs, hd.F, hd.obs_stride, x, sx, R, rows, row0);
+    for (int t = threadIdx.x; t < R * Q; t += kThreads) {
+        const int row = t / Q, q = t - row * Q;
+        const size_t env = (size_t)row0 + row;
+        float eps[4] = {0.f, 0.f, 0.f, 0.f};
+        if (row < rows && !hd.determ) {
+            if (hd.noise) {
+#pragma unroll
+                for (int e = 0; e < 4; e++)
+                    if (4 * q + e < W) eps[e] = hd.noise[env * hd.noise_stride + 4 * q + e];
+            } else {
+                float u[4];
+                draw4((unsigned)env, (unsigned)q, a.counter[0], LG_POLICY_LATENT_TAG, a.seed_lo, a.seed_hi, u, eps);
+                if (hd.dbg_uniform)
+#pragma unroll
+                    for (int e = 0; e < 4; e++) hd.dbg_uniform[env * (4 * Q) + 4 * q + e] = u[e];
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            const int c = 4 * q + e;
+            if (c < W) {
+                const int im = c < L ? c : 2 * L + (c - L), iv = c < L ? L + c : 2 * L + E + (c - L);
+                const float mu = par[row * sp + im];
+                const float v = hd.determ ? mu : eps[e] * expf(0.5f * par[row * sp + iv]) + mu;
+                x[row * sx + hd.F + c] = v;
+                if (hd.latent_out && row < rows) hd.latent_out[env * hd.latent_stride + c] = v;
+            }
+        }
+    }
+}
+
 template <int RB> __global__ __launch_bounds__(256) void policy_act_kernel(KArgs a) {
     extern __shared__ __align__(16) float lds[];
-    const KSeq &s = a.seq[blockIdx.y];
-    const int R = a.R, row0 = blockIdx.x * R, rows = min(R, a.N - row0);
+    int tile = blockIdx.x, si = a.seq_y1;
+    if (blockIdx.y == 0) {
+        si = tile >= a.tiles_a;
+        if (si) tile -= a.tiles_a;
+    }
+    const KSeq &s = a.seq[si];
+    const int R = a.R, row0 = s.row_begin + tile * R;
+    if (row0 >= s.row_end) return;                       // the whole workgroup: the critic's run can be a tile shorter than the policy's two
+    const int rows = min(R, s.row_end - row0);
     lds_f *buf[2] = {(lds_f *)lds, (lds_f *)lds + a.q_off};
-    stage_rows(s.in, s.in_w, s.in_stride, buf[0], s.stride[0], R, rows, row0);
+    stage_rows(s.in, s.in_w, s.in_stride, buf[0], s.stride0, R, rows, row0);
     __syncthreads();
     for (int li = 0; li < s.n_layers; li++) {
-        const KLayer &L = s.l[li];
-        lds_f *nxt = buf[(li + 1) & 1];
-        layer<RB>(L, buf[li & 1], s.stride[li], nxt, s.stride[li + 1], R, rows, row0);
-        if (L.cat_src) stage_rows(L.cat_src, L.cat_w, L.cat_stride, nxt, s.stride[li + 1], R, rows, row0);
+        const KLayer &L = a.l[s.first + li];
+        lds_f *nxt = buf[L.dst & 1];
+        layer<RB>(L, buf[L.src & 1], L.sa, nxt, L.so, R, rows, row0);
+        if (L.cat_src) stage_rows(L.cat_src, L.cat_w, L.cat_stride, nxt, L.so, R, rows, row0);
         __syncthreads();
+        if (li == s.reparam_after) {
+            reparam(a, nxt, L.so, buf[(L.dst + 1) & 1], a.head.sx, R, rows, row0);
+            __syncthreads();
+        }
     }
     if (!s.epilogue) return;
     // sampling epilogue: one lane per (env row, action quad); the log-prob terms replace mu in LDS, then one lane per row sums them in order
-    lds_f *m = buf[s.n_layers & 1];
-    const int sm = s.stride[s.n_layers], A = a.A, Q = (A + 3) >> 2;
+    const KLayer &last = a.l[s.first + s.n_layers - 1];
+    lds_f *m = buf[last.dst & 1];
+    const int sm = last.so, A = a.A, Q = (A + 3) >> 2;
     for (int t = threadIdx.x; t < R * Q; t += kThreads) {
         const int row = t / Q, q = t - row * Q;
         if (row >= rows) continue;
@@ -167,15 +255,8 @@ template <int RB> __global__ __launch_bounds__(256) void policy_act_kernel(KArgs
 #pragma unroll
             for (int e = 0; e < 4; e++) z[e] = 4 * q + e < A ? a.noise[env * a.noise_stride + 4 * q + e] : 0.f;
         } else {
-            const U4 c = {(unsigned)env, (unsigned)q, a.counter[0], LG_POLICY_STREAM_TAG};
-            const U4 x = philox4x32_10(c, a.seed_lo, a.seed_hi);
-            const float u[4] = {u01(x.x), u01(x.y), u01(x.z), u01(x.w)};
-#pragma unroll
-            for (int p = 0; p < 2; p++) {
-                const float rad = sqrtf(-2.0f * logf(1.0f - u[2 * p])), th = 6.283185307179586f * u[2 * p + 1];
-                z[2 * p] = rad * cosf(th);
-                z[2 * p + 1] = rad * sinf(th);
-            }
+            float u[4];
+            draw4((unsigned)env, (unsigned)q, a.counter[0], LG_POLICY_STREAM_TAG, a.seed_lo, a.seed_hi, u, z);
             if (a.dbg_uniform)
 #pragma unroll
                 for (int e = 0; e < 4; e++) a.dbg_uniform[env * (4 * Q) + 4 * q + e] = u[e];
@@ -227,35 +308,96 @@ static bool check_chain(const LgPolicyChain &c, const char *name, int first_in, 
     return true;
 }
 
-static void put_chain(KSeq &s, const LgPolicyChain &c, float *gout, int gstride) {
+// a sequence while `plan` builds it (host only): `pack` copies what the kernel needs into KArgs
+struct PSeq {
+    const float *in;
+    int in_w, in_stride, n_layers, epilogue, n_act, row_begin, row_end, reparam_after;
+    int stride[kMaxSeqLayers + 1];      // LDS row stride of activation i; activation i lives in buffer i & 1
+    KLayer l[kMaxSeqLayers];
+};
+
+static void start_seq(PSeq &s, const LgPolicyChain &first, int row_begin, int row_end) {
+    s.in = first.input; s.in_w = first.in_width; s.in_stride = first.in_stride;
+    s.stride[0] = lds_stride(s.in_w);
+    s.n_act = 1; s.row_begin = row_begin; s.row_end = row_end; s.reparam_after = -1;
+}
+
+// one more layer reading the newest activation; `new_act`: it opens a new activation of width `act_w` (otherwise it shares the newest
+// one with the layer before it, at column `out_col`)
+static KLayer &put_layer(PSeq &s, const float *W, const float *b, int K, int M, int elu, bool new_act, int act_w, int out_col) {
+    KLayer &L = s.l[s.n_layers++];
+    L = KLayer{};
+    L.W = W; L.b = b; L.K = K; L.M = M; L.elu = elu; L.out_col = out_col;
+    if (new_act) { s.stride[s.n_act] = lds_stride(act_w); s.n_act++; }
+    L.src = s.n_act - 2; L.dst = s.n_act - 1;
+    return L;
+}
+
+static void put_chain(PSeq &s, const LgPolicyChain &c, float *gout, int gstride) {
     for (int i = 0; i < c.n_layers; i++) {
-        KLayer &L = s.l[s.n_layers];
-        L = KLayer{};
-        L.W = c.layer[i].weight; L.b = c.layer[i].bias; L.K = c.layer[i].n_in; L.M = c.layer[i].n_out; L.elu = c.layer[i].elu;
+        KLayer &L = put_layer(s, c.layer[i].weight, c.layer[i].bias, c.layer[i].n_in, c.layer[i].n_out, c.layer[i].elu, true, c.layer[i].n_out, 0);
         if (i == c.n_layers - 1) { L.gout = gout; L.gstride = gstride; }
-        s.stride[s.n_layers + 1] = lds_stride(L.M);
-        s.n_layers++;
     }
 }
 
-// the launch plan of one call: which sequences run, their LDS strides, the row tile.  Returns 0 and fills k / n_seq / lds_bytes, or the refusal.
-static int plan(const LgPolicyArgs *p, KArgs &k, int &n_seq, size_t &lds_bytes) {
+// a leading chain whose output lands behind the features in the actor's input activation (the EE / TS concatenation)
+static void put_leading(PSeq &s, const LgPolicyChain &e, const LgPolicyChain &ac, int actor_in) {
+    put_chain(s, e, e.out, e.out_stride);
+    KLayer &L = s.l[s.n_layers - 1];
+    L.out_col = ac.in_width; L.cat_src = ac.input; L.cat_w = ac.in_width; L.cat_stride = ac.in_stride;
+    s.stride[s.n_act - 1] = lds_stride(actor_in);
+}
+
+// the launch plan of one call: which sequences run, their LDS strides, the row tile.  Returns 0 and fills k / n_y / lds_bytes, or the refusal.
+static int plan(const LgPolicyArgs *p, KArgs &k, int &n_y, size_t &lds_bytes) {
     if (!p) return lg_fail_msg("lg_policy_act: null descriptor");
     if (p->n_envs < 1) return lg_fail_msg("lg_policy_act: n_envs < 1");
     const bool values_only = p->flags & LG_POLICY_VALUES_ONLY, determ = p->flags & LG_POLICY_DETERMINISTIC;
     if ((p->flags & ~3u) || (values_only && determ)) return lg_fail_msg("lg_policy_act: bad flags");
     const bool has_est = p->estimator.n_layers != 0, has_critic = p->critic.n_layers != 0;
+    const bool has_b = p->encoder_b.n_layers != 0;
+    const LgPolicyHead &h = p->head;
+    const bool has_head = h.H != 0 || h.L != 0 || h.E != 0;
+    const int N = p->n_envs;
     std::string err;
     k = KArgs{};
-    n_seq = 0;
+    PSeq seq[3] = {};
+    int n_seq = 0, n_policy = 0;
     if (!values_only) {
-        const LgPolicyChain &e = p->estimator, &ac = p->actor;
+        const LgPolicyChain &e = p->estimator, &ac = p->actor, &eb = p->encoder_b;
+        if (p->n_split < 0 || p->n_split > N) return lg_fail_msg("lg_policy_act: n_split outside [0, n_envs]");
+        if (has_b && !p->has_split) return lg_fail_msg("lg_policy_act: encoder_b without n_split (has_split is not set)");
+        if (!has_b && (p->has_split || p->n_split)) return lg_fail_msg("lg_policy_act: n_split without encoder_b");
+        if (has_b && !has_est) return lg_fail_msg("lg_policy_act: encoder_b without an estimator chain for the rows below the split");
+        if (has_b && has_head) return lg_fail_msg("lg_policy_act: the VAE head and encoder_b exclude each other");
+        if (has_head && !has_est) return lg_fail_msg("lg_policy_act: the VAE head needs the estimator chain as its encoder");
         int actor_in = ac.in_width;
         if (has_est) {
             if (!check_chain(e, "lg_policy_act: estimator", e.in_width, err)) return lg_fail_msg(err);
-            if (e.out && e.out_stride < e.layer[e.n_layers - 1].n_out) return lg_fail_msg("lg_policy_act: estimator out_stride < width");
-            actor_in += e.layer[e.n_layers - 1].n_out;
-            if (actor_in > LG_POLICY_MAX_WIDTH) return lg_fail_msg("lg_policy_act: actor input (features, estimator output) wider than 2048");
+            const int e_out = e.layer[e.n_layers - 1].n_out;
+            if (e.out && e.out_stride < e_out) return lg_fail_msg("lg_policy_act: estimator out_stride < width");
+            if (has_head) {
+                if (h.L < 1 || h.E < 1) return lg_fail_msg("lg_policy_act: head widths L and E must be >= 1");
+                if (h.H != e_out) return lg_fail_msg("lg_policy_act: head takes H = " + std::to_string(h.H) + " inputs, the estimator chain gives " + std::to_string(e_out));
+                if (!h.latent_mu_w || !h.latent_mu_b || !h.latent_var_w || !h.latent_var_b || !h.vel_mu_w || !h.vel_mu_b || !h.vel_var_w || !h.vel_var_b)
+                    return lg_fail_msg("lg_policy_act: null head weight or bias");
+                if (!(h.logvar_clip >= 0.f)) return lg_fail_msg("lg_policy_act: logvar_clip must be >= 0");
+                if ((long long)ac.in_width + h.L + h.E > LG_POLICY_MAX_WIDTH) return lg_fail_msg("lg_policy_act: actor input (obs, latent) wider than 2048");
+                actor_in += h.L + h.E;
+                if (h.latent_out && h.latent_stride < h.L + h.E) return lg_fail_msg("lg_policy_act: latent_stride < L + E");
+                if (h.params_out && h.params_stride < 2 * (h.L + h.E)) return lg_fail_msg("lg_policy_act: params_stride < 2 L + 2 E");
+                if (!determ && (h.noise ? h.noise_stride < h.L + h.E : !p->counter))
+                    return lg_fail_msg("lg_policy_act: head noise_stride < L + E, or neither latent noise nor a Philox counter");
+            } else {
+                actor_in += e_out;
+                if (actor_in > LG_POLICY_MAX_WIDTH) return lg_fail_msg("lg_policy_act: actor input (features, estimator output) wider than 2048");
+            }
+        }
+        if (has_b) {
+            if (!check_chain(eb, "lg_policy_act: encoder_b", eb.in_width, err)) return lg_fail_msg(err);
+            const int b_out = eb.layer[eb.n_layers - 1].n_out, e_out = e.layer[e.n_layers - 1].n_out;
+            if (b_out != e_out) return lg_fail_msg("lg_policy_act: the group chains end at different widths (" + std::to_string(e_out) + ", " + std::to_string(b_out) + ")");
+            if (eb.out && eb.out_stride < b_out) return lg_fail_msg("lg_policy_act: encoder_b out_stride < width");
         }
         if (!check_chain(ac, "lg_policy_act: actor", actor_in, err)) return lg_fail_msg(err);
         const int A = ac.layer[ac.n_layers - 1].n_out;
@@ -265,63 +407,103 @@ static int plan(const LgPolicyArgs *p, KArgs &k, int &n_seq, size_t &lds_bytes) 
             if (p->actions_stride < A || p->sigma_stride < A || p->log_prob_stride < 1) return lg_fail_msg("lg_policy_act: a destination stride below its width");
             if (p->noise ? p->noise_stride < A : !p->counter) return lg_fail_msg("lg_policy_act: noise_stride < actions, or neither noise nor a Philox counter");
         }
-        KSeq &s = k.seq[n_seq++];
-        const LgPolicyChain &first = has_est ? e : ac;
-        s.in = first.input; s.in_w = first.in_width; s.in_stride = first.in_stride;
-        s.stride[0] = lds_stride(s.in_w);
-        if (has_est) {
-            put_chain(s, e, e.out, e.out_stride);
-            KLayer &L = s.l[s.n_layers - 1];             // its output lands behind the features in the actor's input activation
-            L.out_col = ac.in_width; L.cat_src = ac.input; L.cat_w = ac.in_width; L.cat_stride = ac.in_stride;
-            s.stride[s.n_layers] = lds_stride(actor_in);
+        if (p->clip_on && !(p->clip_actions >= 0.f)) return lg_fail_msg("lg_policy_act: clip_actions must be >= 0");
+        const int split = has_b ? p->n_split : N;
+        for (int g = 0; g < (has_b ? 2 : 1); g++) {
+            PSeq &s = seq[n_seq++];
+            const LgPolicyChain &lead = g ? eb : e;
+            start_seq(s, has_est ? lead : ac, g ? split : 0, g ? N : split);
+            if (has_head) {
+                put_chain(s, e, e.out, e.out_stride);
+                const int L = h.L, E = h.E, PW = 2 * (L + E);
+                const float *W[4] = {h.latent_mu_w, h.latent_var_w, h.vel_mu_w, h.vel_var_w}, *B[4] = {h.latent_mu_b, h.latent_var_b, h.vel_mu_b, h.vel_var_b};
+                const int M[4] = {L, L, E, E}, col[4] = {0, L, 2 * L, 2 * L + E};
+                for (int i = 0; i < 4; i++) {
+                    KLayer &hl = put_layer(s, W[i], B[i], h.H, M[i], 0, i == 0, PW, col[i]);
+                    if (i & 1) { hl.clip_on = 1; hl.clip = h.logvar_clip; }
+                    if (h.params_out) { hl.gout = h.params_out + col[i]; hl.gstride = h.params_stride; }
+                }
+                s.reparam_after = s.n_layers - 1;
+                s.stride[s.n_act] = k.head.sx = lds_stride(actor_in);       // [obs | z | vel], formed by `reparam` in the other buffer
+                s.n_act++;
+            } else if (has_est) {
+                put_leading(s, lead, ac, actor_in);
+            }
+            put_chain(s, ac, determ ? p->mu : nullptr, p->mu_stride);
+            KLayer &last = s.l[s.n_layers - 1];
+            last.clip_on = p->clip_on != 0; last.clip = p->clip_actions;
+            s.epilogue = !determ;
         }
-        put_chain(s, ac, determ ? p->mu : nullptr, p->mu_stride);
-        KLayer &last = s.l[s.n_layers - 1];
-        last.clip_on = p->clip_on != 0; last.clip = p->clip_actions;
-        if (last.clip_on && !(p->clip_actions >= 0.f)) return lg_fail_msg("lg_policy_act: clip_actions must be >= 0");
-        s.epilogue = !determ;
+        n_policy = n_seq;
         k.A = A;
+        if (has_head) {
+            KHead &d = k.head;
+            d.obs = ac.input; d.obs_stride = ac.in_stride; d.F = ac.in_width; d.L = h.L; d.E = h.E; d.determ = determ;
+            d.noise = determ ? nullptr : h.noise; d.noise_stride = h.noise_stride;
+            d.latent_out = h.latent_out; d.latent_stride = h.latent_stride;
+            d.dbg_uniform = (determ || h.noise) ? nullptr : h.dbg_latent_uniform;
+        }
     }
     if (has_critic && !determ) {
         const LgPolicyChain &c = p->critic;
         if (!check_chain(c, "lg_policy_act: critic", c.in_width, err)) return lg_fail_msg(err);
         if (!c.out || c.out_stride < c.layer[c.n_layers - 1].n_out) return lg_fail_msg("lg_policy_act: null values or stride < width");
-        KSeq &s = k.seq[n_seq++];
-        s.in = c.input; s.in_w = c.in_width; s.in_stride = c.in_stride;
-        s.stride[0] = lds_stride(s.in_w);
+        PSeq &s = seq[n_seq++];
+        start_seq(s, c, 0, N);
         put_chain(s, c, c.out, c.out_stride);
     } else if (values_only) {
         return lg_fail_msg("lg_policy_act: values_only without a critic");
     }
-    k.N = p->n_envs;
+    if (values_only) n_policy = 1;                       // the critic alone: it is the blockIdx.y = 0 run
+    k.N = N;
     k.std = p->std; k.noise = p->noise; k.actions = p->actions; k.mu = p->mu; k.sigma = p->sigma; k.log_prob = p->log_prob;
     k.dbg_uniform = p->dbg_uniform; k.counter = p->counter;
     k.noise_stride = p->noise_stride; k.actions_stride = p->actions_stride; k.mu_stride = p->mu_stride; k.sigma_stride = p->sigma_stride;
     k.log_prob_stride = p->log_prob_stride;
     k.seed_lo = (unsigned)p->seed; k.seed_hi = (unsigned)(p->seed >> 32);
+    k.seq_y1 = n_policy;
+    n_y = n_seq > n_policy ? 2 : 1;
+    int n_l = 0;                                         // pack: each sequence's layers, with their two LDS strides, into the shared array
+    for (int q = 0; q < n_seq; q++) {
+        const PSeq &s = seq[q];
+        k.seq[q] = KSeq{s.in, s.in_w, s.in_stride, s.stride[0], n_l, s.n_layers, s.epilogue, s.row_begin, s.row_end, s.reparam_after};
+        for (int i = 0; i < s.n_layers; i++) {
+            KLayer &L = k.l[n_l++] = s.l[i];
+            L.sa = s.stride[L.src]; L.so = s.stride[L.dst];
+        }
+    }
     // buffer 0 holds the even activations, buffer 1 the odd ones: each as wide as its widest
     int w[2] = {0, 0};
     for (int q = 0; q < n_seq; q++)
-        for (int i = 0; i <= k.seq[q].n_layers; i++)
-            if (k.seq[q].stride[i] > w[i & 1]) w[i & 1] = k.seq[q].stride[i];
+        for (int i = 0; i < seq[q].n_act; i++)
+            if (seq[q].stride[i] > w[i & 1]) w[i & 1] = seq[q].stride[i];
     for (int R = 32; R >= 8; R >>= 1) {
         lds_bytes = (size_t)R * (w[0] + w[1]) * sizeof(float);
         if (lds_bytes <= kLdsBytes) {
             k.R = R; k.q_off = R * w[0];
+            k.tiles_a = (k.seq[0].row_end - k.seq[0].row_begin + R - 1) / R;
             return 0;
         }
     }
     return lg_fail_msg("lg_policy_act: an 8-row tile of these widths does not fit the LDS");
 }
 
+// tiles along x: the policy's one or two runs, or the critic's if that is longer
+static unsigned grid_x(const KArgs &k) {
+    int t = k.tiles_a;
+    if (k.seq_y1 == 2) t += (k.seq[1].row_end - k.seq[1].row_begin + k.R - 1) / k.R;
+    const int all = (k.N + k.R - 1) / k.R;
+    return (unsigned)(t > all ? t : all);
+}
+
 extern "C" int lg_policy_row_tile(const LgPolicyArgs *args) {
-    KArgs k; int n_seq; size_t lds;
-    return plan(args, k, n_seq, lds) ? 0 : k.R;
+    KArgs k; int n_y; size_t lds;
+    return plan(args, k, n_y, lds) ? 0 : k.R;
 }
 
 extern "C" int lg_policy_act(const LgPolicyArgs *args, void *stream) {
-    KArgs k; int n_seq; size_t lds;
-    if (plan(args, k, n_seq, lds)) return 1;
+    KArgs k; int n_y; size_t lds;
+    if (plan(args, k, n_y, lds)) return 1;
     // once per device and kernel: dynamic LDS above 64 KB has to be asked for.  Not synchronised on purpose: two threads racing here
     // both set the same attribute to the same value, which is harmless.
     static bool lds_raised[64][2];
@@ -334,10 +516,10 @@ extern "C" int lg_policy_act(const LgPolicyArgs *args, void *stream) {
         if (e != hipSuccess) return lg_fail_msg(std::string("lg_policy_act: hipFuncSetAttribute: ") + hipGetErrorString(e));
         lds_raised[dev][rb] = true;
     }
-    const dim3 grid((unsigned)((k.N + k.R - 1) / k.R), (unsigned)n_seq);
+    const dim3 grid(grid_x(k), (unsigned)n_y);
     if (rb) hipLaunchKernelGGL(policy_act_kernel<2>, grid, dim3(kThreads), lds, (hipStream_t)stream, k);
     else hipLaunchKernelGGL(policy_act_kernel<1>, grid, dim3(kThreads), lds, (hipStream_t)stream, k);
-    if (k.seq[0].epilogue && !k.noise) hipLaunchKernelGGL(policy_counter_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, args->counter);
+    if (k.seq[0].epilogue && (!k.noise || (k.seq[0].reparam_after >= 0 && !k.head.noise))) hipLaunchKernelGGL(policy_counter_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, args->counter);
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? 0 : lg_fail_msg(std::string("lg_policy_act: ") + hipGetErrorString(e));
 }

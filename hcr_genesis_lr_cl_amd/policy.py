@@ -6,17 +6,31 @@ action_mean, action_std: about 25 torch launches) is one call of `FusedPolicy.ac
 `storage.step` of a `RolloutStorage`.  The module is wrapped by duck typing: `.actor` and `.critic` (and optionally `.estimator`) are
 `nn.Sequential`s of `Linear`, `ELU` and -- only at the actor's end -- `Hardtanh`; `.std` is the per-action standard deviation.  Weights,
 biases and std are read IN PLACE on every call (no packed copy that an optimizer step could leave stale).  The class serves the rollout
-only: everything runs on `.data` without autograd, and `update()` keeps using the module itself.  Recurrent policies, the TS / CTS /
-DreamWaQ families and activations other than ELU are refused, with a message that names the layer.
+only: everything runs on `.data` without autograd, and `update()` keeps using the module itself.
+
+Three more module shapes are recognised, each still one launch per step (the keywords are in `FusedPolicy.act`'s docstring):
+  TS / CTS   `.privilege_encoder` and `.history_encoder` (Linear / ELU) beside `.actor`, `.critic`, `.std` (`ActorCriticTS`, `ActorCriticCTS`):
+             the actor reads (obs, latent) with the latent of whichever encoder the call wants; with `num_teacher=k` env rows [0, k) take
+             the privilege encoder and the others the history encoder in the same launch (ppo_cts.py:110-135: two actor passes and four
+             torch.cat otherwise).
+  DreamWaQ   `.vae` with `.encoder` (Linear / ELU, may end in ELU), `.latent_mu`, `.vel_mu` (Linear), `.latent_var`, `.vel_var`
+             (Sequential(Linear, Hardtanh(-c, c)), one c): the four heads, the clip, the reparameterised draw and the concatenation
+             [obs | z | vel] of vae.py:65-101 / actor_critic_dreamwaq.py:145-171 run in the launch.  `.vae.decoder` is the learner's.
+Recurrent policies, a history encoder with Conv1d / Flatten (the "TCN" option) and activations other than ELU are refused, with a message
+that names the layer.
 
 The draw is torch's when `noise` is given, otherwise the project's Philox4x32-10: counter (env, action quad, call counter, stream tag),
 key = seed, Box-Muller on the uniforms; the call counter is a device cell that a one-lane launch behind the act launch increments, so a
-captured call draws fresh numbers on every replay.
+captured call draws fresh numbers on every replay.  DreamWaQ's latent draw is the same with its own tag (`LG_POLICY_LATENT_TAG`) and the
+quads of the L + E sampled columns, or `latent_noise`; both draws of a call read the same counter value and it advances once.
 
 Measured at 4096 envs against the same rows from torch ops replayed as one HIP graph (tools/policy_act_time.py):
 go2 nets 68 us against 158 us per step, and the act -> step -> add_step loop 45.6 M against 22.8 M env-steps/s.  For the explicit-estimator
 sets the fused launch does NOT beat the graph replay: go2_ee 406 us against 300 us, tron1_pf_ee 395 us against 299 us (16-row tiles
-re-read 2 GB of weights from L2 per step); a rollout that only wants speed keeps the torch path for those.
+re-read 2 GB of weights from L2 per step); a rollout that only wants speed keeps the torch path for those.  The families, same tool,
+go2 sizes: go2_ts 294 us against 260 us and go2_dreamwaq 355 us against 323 us -- the fused launch loses there as well, for the same
+reason (16-row tiles, 1.5 / 1.7 GB of weights per step) -- while go2_cts (3072 teachers of 4096) WINS, 295 us against 369 us: the torch
+side runs the reference's two actor passes and four cats, the fused launch serves both row groups at the cost of the TS step.
 
 There is no CPU path: the kernel lives in csrc/liblgsim.so."""
 from __future__ import annotations
@@ -42,16 +56,39 @@ class ChainSpec:
 class PolicySpec:
     """`describe`'s result: the chains, whether the actor reads (features, estimator output), the clip value, the action count."""
 
-    def __init__(self, estimator, actor, critic, std):
+    def __init__(self, estimator, actor, critic, std, privilege_encoder=None, history_encoder=None, vae_encoder=None, head=None):
         self.estimator, self.actor, self.critic, self.std = estimator, actor, critic, std
+        self.privilege_encoder, self.history_encoder, self.vae_encoder, self.head = privilege_encoder, history_encoder, vae_encoder, head
+        self.family = "ts" if privilege_encoder is not None else "dreamwaq" if head is not None else "ee" if estimator is not None else "plain"
         self.concat = estimator is not None
         self.clip_actions = actor.clip
         self.num_actions = actor.widths[-1]
+        # what rides behind the observations in the actor's input: the encoders' latent (TS / CTS), (z, vel) (DreamWaQ)
+        if self.family == "ts":
+            self.latent_width = privilege_encoder.widths[-1]
+        elif self.family == "dreamwaq":
+            self.latent_width = head.L + head.E
+        else:
+            self.latent_width = 0
+        self.obs_width = (estimator.widths[0] if self.concat else actor.widths[0]) - self.latent_width
 
     @property
     def chain_order(self):
-        """The order a workgroup walks: the estimator precedes its actor; the critic runs in workgroups of its own."""
-        return [c.name for c in (self.estimator, self.actor, self.critic) if c is not None]
+        """The order a workgroup walks: a leading chain precedes its actor; the critic runs in workgroups of its own."""
+        return [c.name for c in (self.estimator, self.privilege_encoder, self.history_encoder, self.vae_encoder, self.actor, self.critic)
+                if c is not None]
+
+
+class HeadSpec:
+    """The four Linear heads of a DreamWaQ VAE (rsl_rl/modules/vae.py:40-50) and the symmetric clip of the two log-variances."""
+
+    def __init__(self, latent_mu, latent_var, vel_mu, vel_var, clip):
+        self.latent_mu, self.latent_var, self.vel_mu, self.vel_var, self.clip = latent_mu, latent_var, vel_mu, vel_var, clip
+        self.H, self.L, self.E = latent_mu.in_features, latent_mu.out_features, vel_mu.out_features
+
+    @property
+    def linears(self):
+        return (self.latent_mu, self.latent_var, self.vel_mu, self.vel_var)
 
 
 def _check_tensor(t, what, device):
@@ -63,7 +100,7 @@ def _check_tensor(t, what, device):
         raise ValueError(f"FusedPolicy: {what} is on {t.device}, not on the HIP device {device}")
 
 
-def _describe_chain(name, seq, device, allow_clip):
+def _describe_chain(name, seq, device, allow_clip, allow_trailing_elu=False):
     if not isinstance(seq, nn.Sequential):
         raise ValueError(f"FusedPolicy: {name} is {type(seq).__name__}, expected an nn.Sequential of Linear / ELU"
                          + (" / Hardtanh" if allow_clip else "") + " (recurrent and encoder policies keep the torch path)")
@@ -101,9 +138,40 @@ def _describe_chain(name, seq, device, allow_clip):
         raise ValueError(f"FusedPolicy: {name} has no Linear layer")
     if len(linears) > abi.POLICY_MAX_LAYERS:
         raise ValueError(f"FusedPolicy: {name} has {len(linears)} Linear layers, the kernel takes {abi.POLICY_MAX_LAYERS}")
-    if elu[-1]:
+    if elu[-1] and not allow_trailing_elu:
         raise ValueError(f"FusedPolicy: {name} ends in an ELU, expected a Linear output layer")
     return ChainSpec(name, linears, elu, clip)
+
+
+def _describe_head(vae, device):
+    lin, clips = {}, {}
+    for name in ("latent_mu", "latent_var", "vel_mu", "vel_var"):
+        m = getattr(vae, name, None)
+        where = f"vae.{name}"
+        if name.endswith("_var"):
+            if not isinstance(m, nn.Sequential) or len(m) != 2 or not isinstance(m[0], nn.Linear) or not isinstance(m[1], nn.Hardtanh):
+                raise ValueError(f"FusedPolicy: {where} is not Sequential(Linear, Hardtanh): the log-variance head of the VAE")
+            if m[1].min_val != -m[1].max_val or not m[1].max_val >= 0:
+                raise ValueError(f"FusedPolicy: {where}[1] (Hardtanh({m[1].min_val}, {m[1].max_val})) must be a symmetric clip")
+            clips[name] = float(m[1].max_val)
+            m, where = m[0], where + "[0]"
+        if not isinstance(m, nn.Linear):
+            raise ValueError(f"FusedPolicy: {where} is {type(m).__name__}, expected a Linear")
+        if m.bias is None:
+            raise ValueError(f"FusedPolicy: {where} has no bias")
+        _check_tensor(m.weight.data, f"{where}.weight", device)
+        _check_tensor(m.bias.data, f"{where}.bias", device)
+        lin[name] = m
+    if clips["latent_var"] != clips["vel_var"]:
+        raise ValueError(f"FusedPolicy: vae.latent_var clips to {clips['latent_var']}, vae.vel_var to {clips['vel_var']}; the kernel takes one clip")
+    H = lin["latent_mu"].in_features
+    for name, m in lin.items():
+        if m.in_features != H or m.in_features > abi.POLICY_MAX_WIDTH:
+            raise ValueError(f"FusedPolicy: vae.{name} takes {m.in_features} inputs, vae.latent_mu {H} (limit {abi.POLICY_MAX_WIDTH})")
+    for a, b in (("latent_mu", "latent_var"), ("vel_mu", "vel_var")):
+        if lin[a].out_features != lin[b].out_features:
+            raise ValueError(f"FusedPolicy: vae.{a} has {lin[a].out_features} outputs, vae.{b} {lin[b].out_features}")
+    return HeadSpec(lin["latent_mu"], lin["latent_var"], lin["vel_mu"], lin["vel_var"], clips["latent_var"])
 
 
 def describe(actor_critic, device=None):
@@ -122,6 +190,29 @@ def describe(actor_critic, device=None):
     _check_tensor(std.data, "std", device)
     if tuple(std.shape) != (actor.widths[-1],):
         raise ValueError(f"FusedPolicy: std has shape {tuple(std.shape)}, the actor has {actor.widths[-1]} outputs")
+    ts = hasattr(actor_critic, "privilege_encoder") or hasattr(actor_critic, "history_encoder")
+    vae = getattr(actor_critic, "vae", None)
+    if (ts or vae is not None) and (estimator is not None or (ts and vae is not None)):
+        raise ValueError("FusedPolicy: the module mixes .estimator, .privilege_encoder / .history_encoder and .vae; one family at a time")
+    if ts:
+        for need in ("privilege_encoder", "history_encoder"):
+            if not hasattr(actor_critic, need):
+                raise ValueError(f"FusedPolicy: the module has no .{need}")
+        pe = _describe_chain("privilege_encoder", actor_critic.privilege_encoder, device, False)
+        he = _describe_chain("history_encoder", actor_critic.history_encoder, device, False)
+        if pe.widths[-1] != he.widths[-1]:
+            raise ValueError(f"FusedPolicy: privilege_encoder gives {pe.widths[-1]} latent dims, history_encoder {he.widths[-1]}")
+        if actor.widths[0] <= pe.widths[-1]:
+            raise ValueError(f"FusedPolicy: actor[0] takes {actor.widths[0]} inputs, the latent alone has {pe.widths[-1]}")
+        return PolicySpec(None, actor, critic, std, privilege_encoder=pe, history_encoder=he)
+    if vae is not None:
+        enc = _describe_chain("vae.encoder", getattr(vae, "encoder", None), device, False, allow_trailing_elu=True)
+        head = _describe_head(vae, device)
+        if head.H != enc.widths[-1]:
+            raise ValueError(f"FusedPolicy: vae.latent_mu takes {head.H} inputs, vae.encoder gives {enc.widths[-1]}")
+        if actor.widths[0] <= head.L + head.E:
+            raise ValueError(f"FusedPolicy: actor[0] takes {actor.widths[0]} inputs, (z, vel) alone has {head.L} + {head.E}")
+        return PolicySpec(None, actor, critic, std, vae_encoder=enc, head=head)
     if estimator is not None and actor.widths[0] != estimator.widths[0] + estimator.widths[-1]:
         raise ValueError(f"FusedPolicy: actor[0] takes {actor.widths[0]} inputs, (features, estimator output) has "
                          f"{estimator.widths[0]} + {estimator.widths[-1]}")
@@ -147,8 +238,45 @@ def _fill_chain(dst, spec, inp, in_width, out):
         l.weight, l.bias, l.n_in, l.n_out, l.elu = m.weight.data.data_ptr(), m.bias.data.data_ptr(), m.in_features, m.out_features, int(e)
 
 
+def _family_inputs(spec, n, privileged_obs, obs_history, num_teacher, student, latent_noise, latent, latent_params, dbg_latent_uniform):
+    """Which keyword arguments the module's family takes; every refusal names the argument.  Returns (leading chain, its rows,
+    second chain or None, its rows) for the TS family, None otherwise."""
+    fam = spec.family
+    if fam != "dreamwaq":
+        for k, v in (("latent_noise", latent_noise), ("latent", latent), ("latent_params", latent_params), ("dbg_latent_uniform", dbg_latent_uniform)):
+            if v is not None:
+                raise ValueError(f"FusedPolicy: {k} was given, the module has no .vae")
+    if fam != "ts":
+        for k, v in (("privileged_obs", privileged_obs), ("num_teacher", num_teacher), ("student", student or None)):
+            if v is not None:
+                raise ValueError(f"FusedPolicy: {k} was given, the module has no .privilege_encoder / .history_encoder")
+    if fam in ("plain", "ee") and obs_history is not None:
+        raise ValueError("FusedPolicy: obs_history was given, the module has neither a .history_encoder nor a .vae")
+    if fam == "dreamwaq" and obs_history is None:
+        raise ValueError("FusedPolicy: obs_history is missing: the VAE's encoder reads it")
+    if fam != "ts":
+        return None
+    if num_teacher is not None:
+        if student:
+            raise ValueError("FusedPolicy: num_teacher and the student call exclude each other")
+        if isinstance(num_teacher, bool) or int(num_teacher) != num_teacher or not 0 <= int(num_teacher) <= n:
+            raise ValueError(f"FusedPolicy: num_teacher={num_teacher} is outside [0, {n}]")
+        for k, v in (("privileged_obs", privileged_obs), ("obs_history", obs_history)):
+            if v is None:
+                raise ValueError(f"FusedPolicy: {k} is missing: with num_teacher both encoders run, each on its rows")
+        return spec.privilege_encoder, privileged_obs, spec.history_encoder, obs_history
+    if student:
+        if obs_history is None:
+            raise ValueError("FusedPolicy: obs_history is missing: the history encoder reads it")
+        return spec.history_encoder, obs_history, None, None
+    if privileged_obs is None:
+        raise ValueError("FusedPolicy: privileged_obs is missing: the privilege encoder reads it")
+    return spec.privilege_encoder, privileged_obs, None, None
+
+
 def policy_args(spec, obs, critic_obs=None, actions=None, mu=None, sigma=None, log_prob=None, values=None, labels=None, noise=None,
-                counter=None, seed=0, flags=0, dbg_uniform=None, device=None):
+                counter=None, seed=0, flags=0, dbg_uniform=None, device=None, privileged_obs=None, obs_history=None, num_teacher=None,
+                student=False, latent_noise=None, latent=None, latent_params=None, dbg_latent_uniform=None):
     """The LgPolicyArgs of one call.  Every tensor is addressed in place; nothing is copied and the library is not touched."""
     a = abi.LgPolicyArgs()
     A = spec.num_actions
@@ -157,11 +285,42 @@ def policy_args(spec, obs, critic_obs=None, actions=None, mu=None, sigma=None, l
     n = int((critic_obs if values_only else obs).shape[0])
     a.n_envs = n
     if not values_only:
-        F = spec.estimator.widths[0] if spec.concat else spec.actor.widths[0]
+        ts = _family_inputs(spec, n, privileged_obs, obs_history, num_teacher, student, latent_noise, latent, latent_params, dbg_latent_uniform)
+        F = spec.obs_width
+        if spec.family in ("ts", "dreamwaq") and torch.is_tensor(obs) and obs.dim() == 2 and obs.shape[1] != F:
+            raise ValueError(f"FusedPolicy: actor[0] takes {spec.actor.widths[0]} inputs, (obs, latent) has {obs.shape[1]} + {spec.latent_width}")
         src = _rows(obs, F, "obs", None, device)
         if spec.concat:
             E = spec.estimator.widths[-1]
             _fill_chain(a.estimator, spec.estimator, src, F, None if labels is None else _rows(labels, E, "labels", n, device))
+        elif labels is not None:
+            raise ValueError("FusedPolicy: a labels row was given, the module has no estimator")
+        if ts is not None:
+            lead, rows, lead_b, rows_b = ts
+            _fill_chain(a.estimator, lead, _rows(rows, lead.widths[0], "privileged_obs" if lead is spec.privilege_encoder else "obs_history", n, device),
+                        lead.widths[0], None)
+            if lead_b is not None:
+                _fill_chain(a.encoder_b, lead_b, _rows(rows_b, lead_b.widths[0], "obs_history", n, device), lead_b.widths[0], None)
+                a.n_split, a.has_split = int(num_teacher), 1
+        if spec.family == "dreamwaq":
+            enc, h = spec.vae_encoder, spec.head
+            _fill_chain(a.estimator, enc, _rows(obs_history, enc.widths[0], "obs_history", n, device), enc.widths[0], None)
+            hd = a.head
+            for name, m in zip(("latent_mu", "latent_var", "vel_mu", "vel_var"), h.linears):
+                setattr(hd, name + "_w", m.weight.data.data_ptr())
+                setattr(hd, name + "_b", m.bias.data.data_ptr())
+            hd.H, hd.L, hd.E, hd.logvar_clip = h.H, h.L, h.E, h.clip
+            if latent is not None:
+                hd.latent_out, hd.latent_stride = _rows(latent, h.L + h.E, "latent", n, device)
+            if latent_params is not None:
+                hd.params_out, hd.params_stride = _rows(latent_params, 2 * (h.L + h.E), "latent_params", n, device)
+            if not determ:
+                if latent_noise is not None:
+                    hd.noise, hd.noise_stride = _rows(latent_noise, h.L + h.E, "latent_noise", n, device)
+                elif dbg_latent_uniform is not None:
+                    if not dbg_latent_uniform.is_contiguous():
+                        raise ValueError("FusedPolicy: the debug uniforms must be a contiguous (N, 4 * ceil((L + E) / 4)) float32 tensor")
+                    hd.dbg_latent_uniform = _rows(dbg_latent_uniform, 4 * ((h.L + h.E + 3) // 4), "dbg_latent_uniform", n, device)[0]
         _fill_chain(a.actor, spec.actor, src, F, None)
         a.mu, a.mu_stride = _rows(mu, A, "mu", n, device)
         if spec.clip_actions is not None:
@@ -173,12 +332,12 @@ def policy_args(spec, obs, critic_obs=None, actions=None, mu=None, sigma=None, l
             a.log_prob, a.log_prob_stride = _rows(log_prob, 1, "log_prob", n, device)
             if noise is not None:
                 a.noise, a.noise_stride = _rows(noise, A, "noise", n, device)
-            else:
+            if noise is None or (spec.family == "dreamwaq" and latent_noise is None):
                 a.counter, a.seed = counter.data_ptr(), int(seed) & (2 ** 64 - 1)
-                if dbg_uniform is not None:                  # the kernel writes it densely: no stride is carried
-                    if not dbg_uniform.is_contiguous():
-                        raise ValueError("FusedPolicy: the debug uniforms must be a contiguous (N, 4 * ceil(A / 4)) float32 tensor")
-                    a.dbg_uniform = _rows(dbg_uniform, 4 * ((A + 3) // 4), "dbg_uniform", n, device)[0]
+            if noise is None and dbg_uniform is not None:    # the kernel writes it densely: no stride is carried
+                if not dbg_uniform.is_contiguous():
+                    raise ValueError("FusedPolicy: the debug uniforms must be a contiguous (N, 4 * ceil(A / 4)) float32 tensor")
+                a.dbg_uniform = _rows(dbg_uniform, 4 * ((A + 3) // 4), "dbg_uniform", n, device)[0]
     if critic_obs is not None and not determ:
         _fill_chain(a.critic, spec.critic, _rows(critic_obs, spec.critic.widths[0], "critic_obs", n, device), spec.critic.widths[0],
                     _rows(values, 1, "values", n, device))
@@ -186,7 +345,8 @@ def policy_args(spec, obs, critic_obs=None, actions=None, mu=None, sigma=None, l
 
 
 class FusedPolicy:
-    """`FusedPolicy(actor_critic, seed=...)`; `act`, `act_inference`, `evaluate`, `fill_transition`.  See the module docstring."""
+    """`FusedPolicy(actor_critic, seed=...)`; `act`, `act_inference`, `act_teacher`, `act_student`, `evaluate`, `fill_transition`.  See the
+    module docstring."""
 
     def __init__(self, actor_critic, seed=0, device=None):
         std = getattr(actor_critic, "std", None)
@@ -204,27 +364,31 @@ class FusedPolicy:
         self._own = {}
         self._args = {}
         self.last_actions = self.last_mu = self.last_sigma = self.last_log_prob = self.last_values = self.last_labels = None
+        self.last_latent = self.last_latent_params = None
 
     # ---- launches ------------------------------------------------------------------------------------------------------
     def _param_key(self):
         """Identity of every layer object of the LIVE module and the address of every parameter: a replaced layer
         (`module.actor[0] = nn.Linear(...)`), a moved parameter or a reassigned `.data` all miss the descriptor cache."""
         key = []
-        for name in ("estimator", "actor", "critic"):
-            seq = getattr(self.module, name, None)
+        vae = getattr(self.module, "vae", None)
+        subs = [getattr(self.module, name, None) for name in ("estimator", "actor", "critic", "privilege_encoder", "history_encoder")]
+        subs += [vae] + [getattr(vae, name, None) for name in ("encoder", "latent_mu", "latent_var", "vel_mu", "vel_var")]
+        for seq in subs:
             key.append(id(seq))
-            for m in (seq if isinstance(seq, nn.Sequential) else ()):
+            for m in (seq if isinstance(seq, nn.Sequential) else (seq,) if isinstance(seq, nn.Linear) else ()):
                 key.append(id(m))
                 if isinstance(m, nn.Linear):
                     key += [m.weight.data.data_ptr(), 0 if m.bias is None else m.bias.data.data_ptr()]
         key.append(self.module.std.data.data_ptr())
         return tuple(key)
 
-    def _launch(self, flags, **t):
+    def _launch(self, flags, num_teacher=None, student=False, **t):
         """Build (or reuse) the descriptor of this call and enqueue it on the current stream.  The descriptor is keyed by every address
         and stride it holds and by the module's layer objects, so a parameter that moved or a layer that was replaced is seen (the module
         is then described again, with every refusal); the parameters' CONTENTS are read by the kernel each call."""
-        key = (flags, self._param_key()) + tuple((k, v.data_ptr(), v.stride(0), v.shape[0]) for k, v in sorted(t.items()) if v is not None)
+        key = (flags, num_teacher, student, self._param_key()) + tuple((k, v.data_ptr(), v.stride(0), v.shape[0]) for k, v in sorted(t.items())
+                                                                         if torch.is_tensor(v))
         a = self._args.get(key)
         if a is None:
             self.spec = describe(self.module, self.device)
@@ -232,26 +396,40 @@ class FusedPolicy:
                 self._args.clear()
             a = self._args[key] = policy_args(self.spec, t.get("obs"), t.get("critic_obs"), t.get("actions"), t.get("mu"), t.get("sigma"),
                                               t.get("log_prob"), t.get("values"), t.get("labels"), t.get("noise"), self.counter, self.seed, flags,
-                                              t.get("dbg_uniform"), self.device)
+                                              t.get("dbg_uniform"), self.device, t.get("privileged_obs"), t.get("obs_history"), num_teacher, student,
+                                              t.get("latent_noise"), t.get("latent"), t.get("latent_params"), t.get("dbg_latent_uniform"))
         abi.check(self.lib.lg_policy_act(C.byref(a), torch.cuda.current_stream(self.device).cuda_stream), self.lib)
 
     def _buffers(self, n):
         b = self._own.get(n)
         if b is None:
             A, z = self.spec.num_actions, lambda w: torch.zeros(n, w, device=self.device)
-            b = self._own[n] = dict(actions=z(A), mu=z(A), sigma=z(A), log_prob=z(1), values=z(1), inference=z(A), evaluate=z(1),
+            b = self._own[n] = dict(actions=z(A), mu=z(A), sigma=z(A), log_prob=z(1), values=z(1), inference=z(A), student=z(A), evaluate=z(1),
                                     labels=z(self.spec.estimator.widths[-1]) if self.spec.concat else None)
         return b
 
-    def act(self, obs, critic_obs, storage=None, noise=None, labels=None, _dbg_uniform=None):
+    def act(self, obs, critic_obs, storage=None, noise=None, labels=None, _dbg_uniform=None, privileged_obs=None, obs_history=None,
+            num_teacher=None, latent_noise=None, latent=None, latent_params=None, _dbg_latent_uniform=None):
         """Sample actions for `obs` ((N, F): the actor's input, or the estimator features of an explicit-estimator module) and evaluate the
-        critic on `critic_obs` (None: no critic launch, no values written).  With a `RolloutStorage` / `RolloutStorageEE` the five results
+        critic on `critic_obs` (None: no critic launch, no values written).  With a `RolloutStorage` (any of the family's) the five results
         go straight into row `storage.step` -- actions, mu, sigma, actions_log_prob, values: the rows `add_step` leaves to the caller --
         and the returned actions ARE that row; with zero-copy observation rows `obs` already is `storage.observations[storage.step]`, so
         nothing is copied at all.  Without a storage the results land in buffers this object owns (`last_mu`, `last_sigma`,
         `last_log_prob`, `last_values`; overwritten by the next call of the same N).  `noise` ((N, A), e.g. torch.randn) replaces the Philox
-        draw.  `labels` ((N, E), e.g. `storage.estimator_labels[t]`-shaped) receives the estimator's output.  (`_dbg_uniform`, for the
-        tests: a contiguous (N, 4 * ceil(A / 4)) tensor that receives the uniforms of the Philox draw.)"""
+        draw.  `labels` ((N, E), e.g. `storage.estimator_labels[t]`-shaped) receives the estimator's output.
+
+        By family (a keyword of another family, or a missing one, is a ValueError that names it):
+          TS        act(obs, critic_obs, privileged_obs=...): latent = privilege_encoder(privileged_obs), as PPO_TS.act.
+          CTS       act(obs, critic_obs, privileged_obs=..., obs_history=..., num_teacher=k): full-N tensors; env rows [0, k) take the
+                    privilege encoder, the others the history encoder, in the one launch (ppo_cts.py:115-127).  With a
+                    `RolloutStorageCTS`, `num_teacher` defaults to the storage's.  WITHOUT `num_teacher` (and without such a storage)
+                    the call is the TS one: every row takes the privilege encoder and a given `obs_history` is IGNORED -- it is
+                    accepted only because PPO_TS.act is handed one (and stores it); nothing here reads it.
+          DreamWaQ  act(obs, critic_obs, obs_history=..., latent_noise=None, latent=None, latent_params=None): `latent_noise` ((N, L + E),
+                    columns (z, vel)) replaces the Philox draw of the reparameterisation; `latent` ((N, L + E)) receives the samples
+                    (z, vel) and `latent_params` ((N, 2L + 2E)) latent_mu, latent_logvar, vel_mu, vel_logvar (clipped).
+        (`_dbg_uniform` / `_dbg_latent_uniform`, for the tests: contiguous (N, 4 * ceil(A / 4)) / (N, 4 * ceil((L + E) / 4)) tensors that
+        receive the uniforms of the Philox draws.)"""
         n = int(obs.shape[0])
         if storage is not None:
             t = storage.step
@@ -259,21 +437,40 @@ class FusedPolicy:
                 raise AssertionError("Rollout buffer overflow")
             d = dict(actions=storage.actions[t], mu=storage.mu[t], sigma=storage.sigma[t], log_prob=storage.actions_log_prob[t],
                      values=storage.values[t])
+            if num_teacher is None and self.spec.family == "ts":
+                num_teacher = getattr(storage, "num_teacher", None)
         else:
             d = self._buffers(n)
         if labels is not None and not self.spec.concat:
             raise ValueError("FusedPolicy: a labels row was given, the module has no estimator")
+        if num_teacher is None and self.spec.family == "ts":
+            obs_history = None                               # the teacher's call: the history is the learner's, nothing here reads it
         values = d["values"] if critic_obs is not None else None
-        self._launch(0, obs=obs, critic_obs=critic_obs, actions=d["actions"], mu=d["mu"], sigma=d["sigma"], log_prob=d["log_prob"], values=values,
-                     labels=labels, noise=noise, dbg_uniform=_dbg_uniform)
+        self._launch(0, num_teacher, obs=obs, critic_obs=critic_obs, actions=d["actions"], mu=d["mu"], sigma=d["sigma"], log_prob=d["log_prob"],
+                     values=values, labels=labels, noise=noise, dbg_uniform=_dbg_uniform, privileged_obs=privileged_obs, obs_history=obs_history,
+                     latent_noise=latent_noise, latent=latent, latent_params=latent_params, dbg_latent_uniform=_dbg_latent_uniform)
         self.last_actions, self.last_mu, self.last_sigma, self.last_log_prob = d["actions"], d["mu"], d["sigma"], d["log_prob"]
         self.last_values, self.last_labels = values, labels
+        self.last_latent, self.last_latent_params = latent, latent_params
         return d["actions"]
 
-    def act_inference(self, obs):
-        """The clipped mean alone (actor_critic.py act_inference): no draw, no critic."""
+    def act_inference(self, obs, obs_history=None, latent=None):
+        """The clipped mean alone (actor_critic.py act_inference): no draw, no critic.  DreamWaQ: `act_inference(obs, obs_history)`, the
+        actor on [obs | latent_mu | vel_mu] (actor_critic_dreamwaq.py:165-171); `latent` ((N, L + E)) receives those means."""
         mu = self._buffers(int(obs.shape[0]))["inference"]
-        self._launch(abi.POLICY_DETERMINISTIC, obs=obs, mu=mu)
+        self._launch(abi.POLICY_DETERMINISTIC, obs=obs, mu=mu, obs_history=obs_history, latent=latent)
+        return mu
+
+    def act_teacher(self, obs, privileged_obs):
+        """TS / CTS: the mean with the privilege encoder's latent (actor_critic_ts.py:178-184)."""
+        mu = self._buffers(int(obs.shape[0]))["inference"]
+        self._launch(abi.POLICY_DETERMINISTIC, obs=obs, mu=mu, privileged_obs=privileged_obs)
+        return mu
+
+    def act_student(self, obs, obs_history):
+        """TS / CTS: the mean with the history encoder's latent (actor_critic_ts.py:186-195)."""
+        mu = self._buffers(int(obs.shape[0]))["student"]
+        self._launch(abi.POLICY_DETERMINISTIC, None, True, obs=obs, mu=mu, obs_history=obs_history)
         return mu
 
     def evaluate(self, critic_obs):
@@ -282,25 +479,43 @@ class FusedPolicy:
         self._launch(abi.POLICY_VALUES_ONLY, critic_obs=critic_obs, values=v)
         return v
 
-    def fill_transition(self, transition, obs, critic_obs, noise=None):
-        """What rsl_rl's PPO.act (ppo.py:97-104) does to `self.transition`, from one launch; returns the actions."""
-        transition.actions = self.act(obs, critic_obs, noise=noise)
+    def fill_transition(self, transition, obs, critic_obs, noise=None, privileged_obs=None, obs_history=None, num_teacher=None,
+                        latent_noise=None, latent=None, latent_params=None, explicit_info_labels=None):
+        """What rsl_rl's PPO.act (ppo.py:97-104) does to `self.transition`, from one launch; returns the actions.  The TS family fills what
+        PPO_TS / PPO_CTS.act fill (ppo_ts.py:81-92: also privileged_observations and observation_histories), DreamWaQ what PPO_DreamWaQ.act
+        fills (ppo_dreamwaq.py:127-137: `critic_obs` is its privileged observations; explicit_info_labels is passed through)."""
+        transition.actions = self.act(obs, critic_obs, noise=noise, privileged_obs=privileged_obs, obs_history=obs_history, num_teacher=num_teacher,
+                                      latent_noise=latent_noise, latent=latent, latent_params=latent_params)
         transition.values = self.last_values
         transition.actions_log_prob = self.last_log_prob.view(-1)
         transition.action_mean = self.last_mu
         transition.action_sigma = self.last_sigma
         transition.observations = obs
+        if self.spec.family == "dreamwaq":
+            transition.privileged_observations = critic_obs
+            transition.observation_histories = obs_history
+            transition.explicit_info_labels = explicit_info_labels
+            return transition.actions
         transition.critic_observations = critic_obs
+        if self.spec.family == "ts":
+            transition.privileged_observations = privileged_obs
+            transition.observation_histories = obs_history
         return transition.actions
 
-    def row_tile(self, n=1):
+    def row_tile(self, n=1, num_teacher=None):
         """Env rows one workgroup carries for this module (32, 16 or 8): the kernel's choice, for documentation and tools."""
         b = self._buffers(n)
-        F = (self.spec.estimator or self.spec.actor).widths[0]
-        a = policy_args(self.spec, torch.zeros(n, F, device=self.device), torch.zeros(n, self.spec.critic.widths[0], device=self.device),
-                        b["actions"], b["mu"], b["sigma"], b["log_prob"], b["values"], counter=self.counter, device=self.device)
+        sp, z = self.spec, lambda w: torch.zeros(n, w, device=self.device)
+        kw = {}
+        if sp.family == "ts":
+            kw = dict(privileged_obs=z(sp.privilege_encoder.widths[0]), num_teacher=num_teacher)
+            if num_teacher is not None:
+                kw["obs_history"] = z(sp.history_encoder.widths[0])
+        elif sp.family == "dreamwaq":
+            kw = dict(obs_history=z(sp.vae_encoder.widths[0]))
+        a = policy_args(sp, z(sp.obs_width), z(sp.critic.widths[0]), b["actions"], b["mu"], b["sigma"], b["log_prob"], b["values"],
+                        counter=self.counter, device=self.device, **kw)
         r = self.lib.lg_policy_row_tile(C.byref(a))
         if r == 0:
             abi.check(1, self.lib)
         return r
-

@@ -1,5 +1,8 @@
 /* lgpolicy.h -- C ABI of the fused policy step: what rsl_rl/algorithms/ppo.py:93-105 asks of ActorCritic / ActorCriticEE during a
- * rollout (act, evaluate, get_actions_log_prob, action_mean, action_std) in ONE launch.  Same conventions as lgrollout.h: plain device
+ * rollout (act, evaluate, get_actions_log_prob, action_mean, action_std) in ONE launch; likewise PPO_TS / PPO_CTS / PPO_DreamWaQ.act of
+ * ActorCriticTS / ActorCriticCTS / ActorCriticDreamWaQ.  For the TS family the `estimator` slot carries whichever encoder the call wants
+ * (the privilege encoder on the privileged observations for act / act_teacher, the history encoder on the history for act_student); CTS
+ * adds `encoder_b` for the rows from `n_split` on; DreamWaQ puts the VAE's encoder into `estimator` and its four heads into `head`.  Same conventions as lgrollout.h: plain device
  * pointers, sizes, the caller's HIP stream as void*; 0 on success, otherwise non-zero with the message in lgsim.h's last-error call.
  * Everything is float32.  Weights are read where torch keeps them (nn.Linear.weight is (out, in) row-major) on every call: nothing is
  * packed or cached, so an optimizer step between two calls is seen by the second.
@@ -18,6 +21,7 @@ extern "C" {
 #define LG_POLICY_DETERMINISTIC 1u   /* actor (and estimator) only; writes `mu` (and `chain.out` of the estimator): act_inference */
 #define LG_POLICY_VALUES_ONLY 2u     /* critic only: evaluate */
 #define LG_POLICY_STREAM_TAG 0x504F4C49u   /* fourth Philox counter word of the action draw */
+#define LG_POLICY_LATENT_TAG 0x4C41544Eu   /* ... and of the VAE head's latent draw */
 
 /* y = W x + b, then ELU(alpha = 1) where `elu` is set */
 typedef struct LgPolicyLayer {
@@ -39,6 +43,29 @@ typedef struct LgPolicyChain {
     int32_t out_stride;
     LgPolicyLayer layer[LG_POLICY_MAX_LAYERS];
 } LgPolicyChain;
+
+/* The VAE head of rsl_rl/modules/vae.py:65-101 behind the `estimator` chain (the VAE's encoder, whose last Linear may carry an ELU): four
+ * Linear heads on the encoded vector (H), each (out, H) row-major and read in place; the two log-variances are clipped to +-logvar_clip.
+ * Sampling: sample = eps * exp(0.5 logvar) + mu, and the actor reads [actor.input[:, :in_width] (F) | z (L) | vel (E)], formed in LDS, so
+ * actor.layer[0].n_in = F + L + E.  LG_POLICY_DETERMINISTIC: no draw, the actor reads [obs | latent_mu | vel_mu].  eps is `noise`
+ * ((N, L + E), columns in (z, vel) order) or, when NULL, Philox4x32-10 with counter (env, quad over the L + E columns, *counter,
+ * LG_POLICY_LATENT_TAG), key = seed, Box-Muller as the action draw.  H == L == E == 0: no head. */
+typedef struct LgPolicyHead {
+    const float *latent_mu_w, *latent_mu_b;     /* (L, H), (L) */
+    const float *latent_var_w, *latent_var_b;   /* (L, H), (L): the log-variance */
+    const float *vel_mu_w, *vel_mu_b;           /* (E, H), (E) */
+    const float *vel_var_w, *vel_var_b;         /* (E, H), (E) */
+    int32_t H, L, E;
+    float logvar_clip;
+    const float *noise;            /* (N, L + E) with noise_stride, or NULL: Philox */
+    float *latent_out;             /* optional (N, L + E): the samples (z, vel), or the means in deterministic mode */
+    float *params_out;             /* optional (N, 2L + 2E): latent_mu, latent_logvar, vel_mu, vel_logvar; log-variances after the clip */
+    float *dbg_latent_uniform;     /* optional (N, 4 * ceil((L + E) / 4)), dense: the uniforms the latent draw used */
+    int32_t noise_stride;
+    int32_t latent_stride;
+    int32_t params_stride;
+    int32_t reserved;
+} LgPolicyHead;
 
 typedef struct LgPolicyArgs {
     int32_t n_envs;
@@ -67,11 +94,23 @@ typedef struct LgPolicyArgs {
     uint64_t seed;
     uint32_t *counter;
     float *dbg_uniform;        /* optional (N, 4 * ceil(A / 4)): the uniforms the draw used */
+    /* Row groups (PPO_CTS, ppo_cts.py:110-135) when has_split: env rows [0, n_split) run `estimator` on estimator.input, rows
+     * [n_split, n_envs) run `encoder_b` on encoder_b.input; both inputs (and both optional `out`s) are full-N matrices addressed by the
+     * global env row, the first read only below the split, the second only from it on.  Both chains end at the same width and feed the
+     * same actor layers and epilogue; the Philox counter keeps the global env index, and the critic stays one pass over all rows.  n_split
+     * of 0 or n_envs leaves one group empty.  *counter is incremented once per call whichever draws use it. */
+    LgPolicyChain encoder_b;
+    int32_t n_split;
+    int32_t has_split;         /* encoder_b and has_split come together */
+    LgPolicyHead head;
 } LgPolicyArgs;
 
 /* One act launch (plus the one-lane counter launch on the Philox path).  Allocates nothing and never synchronises.  Refused before any
  * launch: a null or inconsistent descriptor, more than LG_POLICY_MAX_LAYERS layers, a width outside [1, LG_POLICY_MAX_WIDTH], a stride
- * below its width, layer widths that do not chain, a row tile that does not fit the LDS. */
+ * below its width, layer widths that do not chain, a row tile that does not fit the LDS; n_split outside [0, n_envs], encoder_b without
+ * has_split or the reverse, group chains ending at different widths, head widths that do not chain (H against the estimator chain's
+ * output, actor.layer[0].n_in against in_width + L + E), head together with encoder_b, neither latent noise nor a counter in sampling
+ * mode, an (obs | latent) width above LG_POLICY_MAX_WIDTH. */
 int lg_policy_act(const LgPolicyArgs *args, void *stream);
 
 /* rows of envs one workgroup carries for this descriptor (32, 16 or 8), or 0 with the last error set: what lg_policy_act would choose */
