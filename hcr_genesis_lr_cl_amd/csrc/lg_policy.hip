@@ -142,7 +142,7 @@ __device__ __forceinline__ void layer_tile(const KLayer &L, const lds_f *cur, in
                         const int row = j * 16 + r;
                         float v = acc[j][i][e] + bias;
                         if (L.elu) v = v > 0.f ? v : expm1f(v);
-                        if (L.clip_on) v = fminf(fmaxf(v, -L.clip), L.clip);
+                        if (L.clip_on) v = v < -L.clip ? -L.clip : (v > L.clip ? L.clip : v);     // compares, not fminf / fmaxf: a NaN stays a NaN, as with torch's Hardtanh
                         if (row < R) nxt[row * so + L.out_col + n] = v;
                         if (L.gout && row < rows) L.gout[(size_t)(row0 + row) * L.gstride + n] = v;
                     }

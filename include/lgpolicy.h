@@ -6,6 +6,9 @@
  * pointers, sizes, the caller's HIP stream as void*; 0 on success, otherwise non-zero with the message in lgsim.h's last-error call.
  * Everything is float32.  Weights are read where torch keeps them (nn.Linear.weight is (out, in) row-major) on every call: nothing is
  * packed or cached, so an optimizer step between two calls is seen by the second.
+ * NaN is not silent: a NaN in a row of an input reaches `mu`, `sigma`, `actions` and `log_prob` of that env row (and the head's `latent_out`
+ * / `params_out` when it entered through the estimator chain), as with torch -- both clips (`clip_actions`, `logvar_clip`) are compares
+ * that pass a NaN on, like torch.nn.Hardtanh; no other row and no output of a chain that did not read it changes a bit.
  */
 #ifndef LGPOLICY_H
 #define LGPOLICY_H
