@@ -281,7 +281,11 @@ def load_lib():
     lib.lg_depth_render.restype = C.c_int
     lib.lg_policy_act.argtypes = [C.POINTER(LgPolicyArgs), vp]
     lib.lg_policy_row_tile.argtypes = [C.POINTER(LgPolicyArgs)]
-    lib.lg_policy_act.restype = lib.lg_policy_row_tile.restype = C.c_int
+    lib.lg_policy_act_recurrent.argtypes = [C.POINTER(LgPolicyRecurrentArgs), vp]
+    lib.lg_policy_row_tile_recurrent.argtypes = [C.POINTER(LgPolicyRecurrentArgs)]
+    lib.lg_policy_reset.argtypes = [C.POINTER(LgPolicyRecurrentArgs), vp, vp]
+    for f in POLICY_EXPORTS:
+        getattr(lib, f).restype = C.c_int
     lib.lg_last_error.restype = C.c_char_p
     lib.lg_last_kernel.argtypes = [H]
     lib.lg_last_kernel.restype = C.c_char_p
@@ -299,8 +303,10 @@ EXPORTS = ["lg_create", "lg_destroy", "lg_set_task", "lg_set_terrain", "lg_bind"
 ROLLOUT_EXPORTS = ["lg_rollout_record", "lg_rollout_gae", "lg_rollout_traj_index", "lg_rollout_mask_index", "lg_rollout_pad",
                    "lg_rollout_unpad", "lg_rollout_gather", "lg_rollout_gae_groups"]          # include/lgrollout.h
 SENSOR_EXPORTS = ["lg_depth_render"]                                                          # include/lgsensor.h
-POLICY_EXPORTS = ["lg_policy_act", "lg_policy_row_tile"]                                      # include/lgpolicy.h
+POLICY_EXPORTS = ["lg_policy_act", "lg_policy_row_tile", "lg_policy_act_recurrent", "lg_policy_row_tile_recurrent", "lg_policy_reset"]   # include/lgpolicy.h
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 2048
+POLICY_MAX_RNN_LAYERS, POLICY_MAX_RNN_HIDDEN = 2, 512
+POLICY_LSTM, POLICY_GRU = 1, 2
 POLICY_DETERMINISTIC, POLICY_VALUES_ONLY = 1, 2
 POLICY_STREAM_TAG = 0x504F4C49
 POLICY_LATENT_TAG = 0x4C41544E
@@ -354,6 +360,16 @@ class LgPolicyHead(C.Structure):
         ("params_stride", i32), ("reserved", i32)]
 
 
+class LgPolicyRnnLayer(C.Structure):
+    _fields_ = [("weight_ih", C.c_void_p), ("weight_hh", C.c_void_p), ("bias_ih", C.c_void_p), ("bias_hh", C.c_void_p)]
+
+
+class LgPolicyMemory(C.Structure):
+    _fields_ = [("kind", i32), ("n_layers", i32), ("hidden", i32), ("in_width", i32), ("in_stride", i32), ("reserved", i32),
+                ("input", C.c_void_p), ("layer", LgPolicyRnnLayer * POLICY_MAX_RNN_LAYERS), ("h", C.c_void_p), ("c", C.c_void_p),
+                ("h_prev_out", C.c_void_p), ("c_prev_out", C.c_void_p), ("reset_mask", C.c_void_p)]
+
+
 class LgPolicyArgs(C.Structure):
     _fields_ = [("n_envs", i32), ("flags", u32), ("estimator", LgPolicyChain), ("actor", LgPolicyChain), ("critic", LgPolicyChain),
                 ("clip_actions", f32), ("clip_on", i32), ("std", C.c_void_p), ("noise", C.c_void_p),
@@ -361,6 +377,12 @@ class LgPolicyArgs(C.Structure):
                 ("actions", C.c_void_p), ("mu", C.c_void_p), ("sigma", C.c_void_p), ("log_prob", C.c_void_p),
                 ("log_prob_stride", i32), ("reserved", i32), ("seed", u64), ("counter", C.c_void_p), ("dbg_uniform", C.c_void_p),
                 ("encoder_b", LgPolicyChain), ("n_split", i32), ("has_split", i32), ("head", LgPolicyHead)]
+
+
+class LgPolicyRecurrentArgs(LgPolicyArgs):
+    """struct { LgPolicyArgs args; LgPolicyMemory memory_a, memory_c; }: a ctypes subclass lays its own fields out behind the base's, so
+    the members of `args` are attributes of this object as they are of a plain LgPolicyArgs."""
+    _fields_ = [("memory_a", LgPolicyMemory), ("memory_c", LgPolicyMemory)]
 
 
 def check(rc, lib=None):

@@ -234,6 +234,13 @@ class RolloutStorage:
         n = n_other + len(hid_a) + len(hid_c)
         if n > abi.ROLLOUT_MAX_COPIES:
             raise ValueError(f"{type(self).__name__}: {n} row copies in one step, the record launch takes {abi.ROLLOUT_MAX_COPIES}")
+        self._hidden_saved(hid_a, hid_c)
+        # a contiguous (L, N, H) block is copied flat; the record kernel's copies are N rows, so the block is viewed as (N, L * H)
+        return [(h.contiguous().view(self.num_envs, -1), saved[t].view(self.num_envs, -1))
+                for h, saved in zip(hid_a + hid_c, self.saved_hidden_states_a + self.saved_hidden_states_c)]
+
+    def _hidden_saved(self, hid_a, hid_c):
+        """`saved_hidden_states_a` / `_c` for states of these shapes: allocated on first use, checked against them afterwards."""
         T, N = self.num_transitions_per_env, self.num_envs
         if self.saved_hidden_states_a is None:
             for h in hid_a + hid_c:
@@ -243,13 +250,21 @@ class RolloutStorage:
             self.saved_hidden_states_c = [torch.zeros(T, *h.shape, device=self.device) for h in hid_c]
         if len(hid_a) != len(self.saved_hidden_states_a) or len(hid_c) != len(self.saved_hidden_states_c):
             raise ValueError("the number of hidden-state tensors changed within a storage")
-        copies = []
         for h, saved in zip(hid_a + hid_c, self.saved_hidden_states_a + self.saved_hidden_states_c):
             if h.shape != saved.shape[1:] or h.dtype != torch.float32 or h.device != saved.device:
                 raise ValueError(f"hidden state {tuple(h.shape)} {h.dtype} on {h.device} does not fit the stored {tuple(saved.shape[1:])} float32")
-            # a contiguous (L, N, H) block is copied flat; the record kernel's copies are N rows, so the block is viewed as (N, L * H)
-            copies.append((h.contiguous().view(N, -1), saved[t].view(N, -1)))
-        return copies
+
+    def hidden_state_rows(self, hidden_states):
+        """Row `self.step` of the saved hidden states, as ((L, N, H) views for the actor's memory, likewise the critic's), for a producer
+        that writes the pre-step states there itself (`FusedPolicy.act(storage=...)`: the launch fills them, and `add_step` is then
+        called without `hidden_states`).  `hidden_states` is the policy's `get_hidden_states()`, read for its shapes only: the saved
+        lists are allocated on first use and checked exactly as `add_step(hidden_states=...)` does."""
+        t = self.step
+        if t >= self.num_transitions_per_env:
+            raise AssertionError("Rollout buffer overflow")
+        hid_a, hid_c = (tuple(h) if isinstance(h, (tuple, list)) else (h,) for h in hidden_states)
+        self._hidden_saved(hid_a, hid_c)
+        return [s[t] for s in self.saved_hidden_states_a], [s[t] for s in self.saved_hidden_states_c]
 
     def clear(self):
         self.step = 0

@@ -8,7 +8,11 @@
  * packed or cached, so an optimizer step between two calls is seen by the second.
  * NaN is not silent: a NaN in a row of an input reaches `mu`, `sigma`, `actions` and `log_prob` of that env row (and the head's `latent_out`
  * / `params_out` when it entered through the estimator chain), as with torch -- both clips (`clip_actions`, `logvar_clip`) are compares
- * that pass a NaN on, like torch.nn.Hardtanh; no other row and no output of a chain that did not read it changes a bit.
+ * that pass a NaN on, like torch.nn.Hardtanh; no other row and no output of a chain that did not read it changes a bit.  The same holds
+ * for the states of a memory (below): a NaN in a row's observation or incoming state reaches that row's outputs and new state only.
+ * A recurrent policy (rsl_rl/modules/actor_critic_recurrent.py: an LSTM or GRU in front of the actor and of the critic) passes
+ * LgPolicyRecurrentArgs -- LgPolicyArgs with the two memories behind it -- to the _recurrent entry points; the memories run in the same
+ * launch, ahead of the MLP they feed.
  */
 #ifndef LGPOLICY_H
 #define LGPOLICY_H
@@ -21,6 +25,10 @@ extern "C" {
 
 #define LG_POLICY_MAX_LAYERS 4
 #define LG_POLICY_MAX_WIDTH 2048
+#define LG_POLICY_MAX_RNN_LAYERS 2
+#define LG_POLICY_MAX_RNN_HIDDEN (LG_POLICY_MAX_WIDTH / 4)   /* the gates of one cell, 4 H wide for both kinds, are one activation */
+#define LG_POLICY_LSTM 1
+#define LG_POLICY_GRU 2
 #define LG_POLICY_DETERMINISTIC 1u   /* actor (and estimator) only; writes `mu` (and `chain.out` of the estimator): act_inference */
 #define LG_POLICY_VALUES_ONLY 2u     /* critic only: evaluate */
 #define LG_POLICY_STREAM_TAG 0x504F4C49u   /* fourth Philox counter word of the action draw */
@@ -70,6 +78,39 @@ typedef struct LgPolicyHead {
     int32_t reserved;
 } LgPolicyHead;
 
+/* One layer of a torch nn.LSTM / nn.GRU, read in place: weight_ih_l{k} (G H, in) and weight_hh_l{k} (G H, H) row-major, bias_ih_l{k} and
+ * bias_hh_l{k} (G H); G = 4 with gate rows (i, f, g, o) for an LSTM, G = 3 with (r, z, n) for a GRU; `in` is in_width for layer 0, H behind. */
+typedef struct LgPolicyRnnLayer {
+    const float *weight_ih, *weight_hh, *bias_ih, *bias_hh;
+} LgPolicyRnnLayer;
+
+/* The memory in front of a chain (Memory of actor_critic_recurrent.py:92-116 in inference mode): one time step of an LSTM or GRU on rows
+ * of `input`; the top layer's new h (N, H) is the chain's input, so the chain's own input / in_width / in_stride are not read and its
+ * layer[0].n_in is H.  The cell is torch's:
+ *   LSTM  gates = W_ih x + b_ih + W_hh h + b_hh;  c' = s(f) c + s(i) tanh(g);  h' = s(o) tanh(c')
+ *   GRU   r = s(W_ir x + b_ir + W_hr h + b_hr), z likewise;  n = tanh(W_in x + b_in + r (W_hn h + b_hn));  h' = (1 - z) n + z h
+ * and layer k > 0 reads the new h' of layer k - 1.  `h` (and `c`) are the live states, (n_layers, N, H) contiguous, UPDATED IN PLACE: a
+ * workgroup reads and writes the state rows of its own env rows only, and has read a layer's previous state before it writes the new one.
+ * reset_mask (N bytes, optional): a non-zero byte means that row's incoming state is read as zero (the reset(dones) of the step before).
+ * h_prev_out / c_prev_out (optional, same layout): the state the call started from, after the mask -- what PPO.act stores with the
+ * transition.  kind == 0 (an all-zero struct): no memory.  LG_POLICY_DETERMINISTIC runs memory_a only, LG_POLICY_VALUES_ONLY memory_c
+ * only; a memory whose chain does not run is not touched. */
+typedef struct LgPolicyMemory {
+    int32_t kind;              /* 0 none, LG_POLICY_LSTM, LG_POLICY_GRU */
+    int32_t n_layers;          /* 1 .. LG_POLICY_MAX_RNN_LAYERS */
+    int32_t hidden;            /* H, 1 .. LG_POLICY_MAX_RNN_HIDDEN */
+    int32_t in_width;
+    int32_t in_stride;
+    int32_t reserved;
+    const float *input;        /* (N, in_width), in_stride floats between rows */
+    LgPolicyRnnLayer layer[LG_POLICY_MAX_RNN_LAYERS];
+    float *h;                  /* (n_layers, N, H) */
+    float *c;                  /* (n_layers, N, H) for an LSTM, NULL for a GRU */
+    float *h_prev_out;         /* optional (n_layers, N, H) */
+    float *c_prev_out;         /* optional (n_layers, N, H), LSTM only */
+    const uint8_t *reset_mask; /* optional (N) */
+} LgPolicyMemory;
+
 typedef struct LgPolicyArgs {
     int32_t n_envs;
     uint32_t flags;
@@ -108,6 +149,15 @@ typedef struct LgPolicyArgs {
     LgPolicyHead head;
 } LgPolicyArgs;
 
+/* LgPolicyArgs grown by the two memories, which lie directly behind its last member: every member of `args` is where it is in a plain
+ * LgPolicyArgs and keeps its meaning, and an all-zero memory means "no memory", so a zero-filled tail describes the same call as `args`
+ * alone.  No flag bit was added: flags & ~3u is refused as before. */
+typedef struct LgPolicyRecurrentArgs {
+    LgPolicyArgs args;
+    LgPolicyMemory memory_a;   /* in front of the actor; excludes estimator, encoder_b and head */
+    LgPolicyMemory memory_c;   /* in front of the critic */
+} LgPolicyRecurrentArgs;
+
 /* One act launch (plus the one-lane counter launch on the Philox path).  Allocates nothing and never synchronises.  Refused before any
  * launch: a null or inconsistent descriptor, more than LG_POLICY_MAX_LAYERS layers, a width outside [1, LG_POLICY_MAX_WIDTH], a stride
  * below its width, layer widths that do not chain, a row tile that does not fit the LDS; n_split outside [0, n_envs], encoder_b without
@@ -116,8 +166,20 @@ typedef struct LgPolicyArgs {
  * mode, an (obs | latent) width above LG_POLICY_MAX_WIDTH. */
 int lg_policy_act(const LgPolicyArgs *args, void *stream);
 
+/* lg_policy_act with the memories: the same launch (and counter launch), the same refusals, and for a memory also an unknown kind, a layer
+ * count outside [1, LG_POLICY_MAX_RNN_LAYERS], H outside [1, LG_POLICY_MAX_RNN_HIDDEN], a null parameter, input or state pointer, `c`
+ * missing for an LSTM or given for a GRU, a chain whose layer[0].n_in is not H, a memory together with the estimator, encoder_b or the
+ * head.  With both memories absent it is lg_policy_act on `args`. */
+int lg_policy_act_recurrent(const LgPolicyRecurrentArgs *args, void *stream);
+
+/* The stand-alone reset(dones) of actor_critic_recurrent.py:72-74: one launch that zeroes the rows of `h` (and `c`) of both memories whose
+ * byte in `mask` ((N) bytes on the device) is non-zero; mask == NULL zeroes every row.  Only the memories' kind, n_layers, hidden, h and c
+ * and args.n_envs are read.  Refused: no memory at all, or a memory that the act call would refuse for those members. */
+int lg_policy_reset(const LgPolicyRecurrentArgs *args, const uint8_t *mask, void *stream);
+
 /* rows of envs one workgroup carries for this descriptor (32, 16 or 8), or 0 with the last error set: what lg_policy_act would choose */
 int lg_policy_row_tile(const LgPolicyArgs *args);
+int lg_policy_row_tile_recurrent(const LgPolicyRecurrentArgs *args);
 
 #ifdef __cplusplus
 }

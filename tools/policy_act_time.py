@@ -1,16 +1,26 @@
-"""Developer tool (GPU only, never read by bench.py): time of the policy half of one rollout step at N = 4096 envs for six net sets -- go2
+"""Developer tool (GPU only, never read by bench.py): time of the policy half of one rollout step at N = 4096 envs for eight net sets -- go2
 (actor 45-512-256-128-12, critic 45-512-256-128-1), go2_ee (estimator 900-256-128-24, actor 924-..-12, critic 870-1024-256-128-1),
 tron1_pf_ee (310 / 327 / 1340, 17 labels, 6 actions) (dims: bench.py::ppo_rollout), and the go2 sizes of config.py for the other learner
 families: go2_ts (privilege encoder 99-256-128-99, actor 144-512-256-128-12, critic 885-1024-256-128-1; the teacher's step, as PPO_TS.act),
 go2_cts (the same plus the history encoder 900-256-128-99 on the 1024 student rows behind 3072 teachers; the torch side is the
 reference's two passes and four cats, ppo_cts.py:115-127) and go2_dreamwaq (VAE encoder 900-256-128-80 with the trailing ELU, heads
-16 / 16 / 24 / 24, actor 85-..-12, critic 885-..-1) -- produced three ways into the same storage row:
+16 / 16 / 24 / 24, actor 85-..-12, critic 885-..-1), and two recurrent sets (ActorCriticRecurrent, obs 45 for both memories): go2_lstm256
+(LSTM 256 x 1, actor and critic 256-256-256-256-out) and go2_lstm512 (LSTM 512 x 1, actor and critic 512-512-256-128-out) -- produced three
+ways into the same storage row:
 
   (i)   the fused launch, `FusedPolicy.act(obs, critic_obs, storage=st)` (Philox draw, so with its one-lane counter launch);
   (ii)  the torch ops of bench.py::policy_row (f32 GEMMs, ELUs, randn, log-prob arithmetic, five copy_) captured once and replayed as one
         HIP graph;
   (iii) the same ops dispatched eagerly;
   (iv)  go2 only: the loop act -> env.step -> add_step for 24 steps on zero-copy observation rows, with (i) and with (ii), in env-steps/s.
+
+Recurrent sets: (i) is `act(obs, critic_obs, storage=st, reset=mask)` (about 2 % of the rows done): cells, MLPs, draw, reset and the
+pre-step hidden-state rows in the one launch; (ii) / (iii) are the module's ops for the same rows: the masked reset of the four state
+tensors, their copies into the storage's saved hidden states (two per memory), nn.LSTM of both memories, the MLPs, sampling and the five
+copies; the states are kept at fixed addresses (the new ones copied back), which the graph needs.  Measured on one MI355X at 4096 envs
+(DESIGN.md section 10b): go2_lstm256 fused 266 us against 410 us for the graph replay (667 us eager) -- the fused launch wins; go2_lstm512
+fused 1133 us against 622 us (678 us eager) -- it loses by 1.8 x, because only the 8-row tile fits the LDS and 512 tiles per chain each
+re-read 6.3 MB of weights from L2.  A rollout that only wants speed keeps H = 512 (and any size whose row tile is 8) on the torch ops.
 
 (i)-(iii): each sample is the device-event time around a burst of launches divided by the burst length, so it is the time per step on the
 device queue with launches back to back; the sides alternate in one process after a warm-up, median and p10-p90 over the repeats are
@@ -39,6 +49,8 @@ _GO2_FAMILY = dict(obs=45, est=None, actor=[512, 256, 128], A=12, cobs=885, crit
 SETS["go2_ts"] = dict(_GO2_FAMILY, family="ts", priv=99, latent=99, enc=[256, 128])
 SETS["go2_cts"] = dict(SETS["go2_ts"], teachers=3072)                 # of 4096: scaled with --envs
 SETS["go2_dreamwaq"] = dict(_GO2_FAMILY, family="dreamwaq", enc=[256, 128], H=80, L=16, E=24)
+SETS["go2_lstm256"] = dict(obs=45, est=None, actor=[256, 256, 256], A=12, cobs=45, critic=[256, 256, 256], family="recurrent", rnn=nn.LSTM, H=256, layers=1)
+SETS["go2_lstm512"] = dict(obs=45, est=None, actor=[512, 256, 128], A=12, cobs=45, critic=[512, 256, 128], family="recurrent", rnn=nn.LSTM, H=512, layers=1)
 
 
 def mlp(i, hidden, o, tail=None):
@@ -70,6 +82,13 @@ class Nets(nn.Module):
             self.vae.latent_mu, self.vae.vel_mu = nn.Linear(d["H"], d["L"]), nn.Linear(d["H"], d["E"])
             self.vae.latent_var = nn.Sequential(nn.Linear(d["H"], d["L"]), nn.Hardtanh(-5.0, 5.0))
             self.vae.vel_var = nn.Sequential(nn.Linear(d["H"], d["E"]), nn.Hardtanh(-5.0, 5.0))
+        if d.get("family") == "recurrent":           # actor_critic_recurrent.py: the MLPs read the memories' top h
+            self.is_recurrent = True
+            self.memory_a, self.memory_c = nn.Module(), nn.Module()
+            self.memory_a.rnn, self.memory_c.rnn = d["rnn"](d["obs"], d["H"], d["layers"]), d["rnn"](d["cobs"], d["H"], d["layers"])
+            self.actor, self.critic = mlp(d["H"], d["actor"], d["A"], nn.Hardtanh(-100.0, 100.0)), mlp(d["H"], d["critic"], 1)
+            self.std = nn.Parameter(torch.ones(d["A"]))
+            return
         self.actor = mlp(d["obs"] + E, d["actor"], d["A"], nn.Hardtanh(-100.0, 100.0))
         self.critic = mlp(d["cobs"], d["critic"], 1)
         self.std = nn.Parameter(torch.ones(d["A"]))
@@ -84,6 +103,9 @@ def work(m, d, N, k):
     fl = lambda *mods: sum(2 * l.in_features * l.out_features for l in _linears(*mods))
     by = lambda *mods: sum(4 * (l.in_features + 1) * l.out_features for l in _linears(*mods))
     fam = d.get("family")
+    if fam == "recurrent":
+        rnn = [p for mem in (m.memory_a, m.memory_c) for n, p in mem.rnn.named_parameters() if n.startswith("weight")]
+        return N * (fl(m.actor, m.critic) + sum(2 * p.numel() for p in rnn)), by(m.actor, m.critic) + sum(4 * (p.shape[1] + 1) * p.shape[0] for p in rnn)
     if fam == "ts":
         lead = [m.privilege_encoder] + ([m.history_encoder] if k is not None else [])
         flop = N * fl(m.actor, m.critic) + (N if k is None else k) * fl(m.privilege_encoder) + (0 if k is None else (N - k) * fl(m.history_encoder))
@@ -131,6 +153,24 @@ def torch_row(m, x, st, t, lab_row, k=None, z=None, eps=None):
     else:
         out = _sample(m, m.actor(obs), z)
     _store(st, t, *out, m.critic(x["cobs"]))
+
+
+def recurrent_row(m, x, st, t, state, mask, z=None):
+    """What PPO.act / process_env_step ask of an ActorCriticRecurrent for one step, on states kept at fixed addresses: reset(dones) of the
+    step before as a masked fill, the pre-step states into the storage (ppo.py:94-95, rollout_storage.py:104-119), both memories, the
+    MLPs, the draw and the five copies."""
+    keep = mask.view(1, -1, 1)
+    for s in state["a"] + state["c"]:
+        s.masked_fill_(keep, 0.0)
+    for saved, s in zip(st.saved_hidden_states_a + st.saved_hidden_states_c, state["a"] + state["c"]):
+        saved[t].copy_(s)
+    top = {}
+    for w, mem, inp in (("a", m.memory_a, x["obs"]), ("c", m.memory_c, x["cobs"])):
+        out, new = mem.rnn(inp.unsqueeze(0), tuple(state[w]))
+        top[w] = out.squeeze(0)
+        for s, n in zip(state[w], new):
+            s.copy_(n)
+    _store(st, t, *_sample(m, m.actor(top["a"]), z), m.critic(top["c"]))
 
 
 def make_storage(d, N, k, dev):
@@ -202,6 +242,10 @@ def main():
             x = {key: torch.randn(N, d[w], device=dev) for key, w in (("obs", "obs"), ("cobs", "cobs"), ("priv", "priv"), ("hist", "hist")) if w in d}
             lab_row = torch.zeros(N, d["est"][1], device=dev) if d["est"] else None
             fam = d.get("family")
+            if fam == "recurrent":
+                res["sets"][name] = time_recurrent(name, d, m, fp, st, x, N, args)
+                del fp, st
+                continue
             if fam == "ts":
                 kw = dict(privileged_obs=x["priv"])
             elif fam == "dreamwaq":
@@ -251,6 +295,52 @@ def main():
         v = res["loop_go2"]["env_steps_per_s"][k]
         print(f"go2 loop act -> step -> add_step, {T} steps, {k:12s}: median {v['median'] / 1e6:6.2f} M env-steps/s   p10-p90 {v['p10'] / 1e6:6.2f} - {v['p90'] / 1e6:6.2f}")
     print(json.dumps(res))
+
+
+def time_sides(sides, args):
+    for _ in range(args.warmup):
+        for f in sides.values():
+            burst_us(f, args.burst)
+    times = {q: [] for q in sides}
+    for _ in range(args.repeats):
+        for q, f in sides.items():
+            times[q].append(burst_us(f, args.burst))
+    return times
+
+
+def time_recurrent(name, d, m, fp, st, x, N, args):
+    dev = x["obs"].device
+    z = torch.randn(N, d["A"], device=dev)
+    mask = torch.zeros(N, dtype=torch.bool, device=dev)
+    state = {w: [torch.zeros(d["layers"], N, d["H"], device=dev) for _ in range(2)] for w in "ac"}
+    st.step = 0
+    for _ in range(2):                                           # two steps from zero states, so that the second reads computed ones
+        fp.act(x["obs"], x["cobs"], storage=st, noise=z, reset=mask)
+    for _ in range(2):
+        recurrent_row(m, x, st, 1, state, mask, z)
+    torch.cuda.synchronize()
+    agree = {q: float((getattr(st, q)[0] - getattr(st, q)[1]).abs().max()) for q in ("mu", "values", "sigma")}
+    agree["saved_h_a"] = float((st.saved_hidden_states_a[0][0] - st.saved_hidden_states_a[0][1]).abs().max())
+    if agree["mu"] > 1e-4 or agree["values"] > 1e-4 or agree["saved_h_a"] > 1e-4 or agree["sigma"] != 0.0:
+        sys.exit(f"policy_act_time.py: {name}: the fused launch and the torch ops disagree ({agree}) -- nothing timed")
+    mask.copy_(torch.rand(N, device=dev) < 0.02)
+    want = args.sides.split(",")
+    graph = capture(lambda: recurrent_row(m, x, st, 1, state, mask)) if "torch_graph" in want else None
+    sides = {"fused": lambda: fp.act(x["obs"], x["cobs"], storage=st, reset=mask), "torch_graph": graph and graph.replay,
+             "torch_eager": lambda: recurrent_row(m, x, st, 1, state, mask)}
+    times = time_sides({q: f for q, f in sides.items() if q in want}, args)
+    flop, wbytes = work(m, d, N, None)
+    out = dict(flop_per_step=flop, weight_bytes=wbytes, row_tile=fp.row_tile(N), step_us={k: stat(v) for k, v in times.items()},
+               max_abs_diff_vs_torch=agree)
+    print(f"{name}: {flop / 1e9:.2f} GFLOP per step, {wbytes / 1e6:.2f} MB of weights, row tile {out['row_tile']}, "
+          f"|mu - torch| {agree['mu']:.1e}, |values - torch| {agree['values']:.1e}, |saved h_a - torch| {agree['saved_h_a']:.1e}")
+    for k, v in out["step_us"].items():
+        print(f"  {k:12s}: median {v['median']:8.1f} us   min {v['min']:8.1f}   p10-p90 {v['p10']:8.1f} - {v['p90']:8.1f}   max {v['max']:8.1f}")
+    if "fused" in times:
+        out["fused_flops"] = flop / (out["step_us"]["fused"]["median"] * 1e-6)
+        out["fraction_of_f32_mfma_rate"] = out["fused_flops"] / F32_MFMA_FLOPS
+        print(f"  fused: {out['fused_flops'] / 1e12:.1f} TFLOP/s = {100 * out['fraction_of_f32_mfma_rate']:.1f} % of the {F32_MFMA_FLOPS / 1e12:.0f} TFLOP/s f32-MFMA rate")
+    return out
 
 
 def loop_go2(N, T, dev, args):
