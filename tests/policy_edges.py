@@ -68,13 +68,23 @@ def sequences(d):
     return [[d["obs"], *d["actor"], d["A"]], critic]
 
 
-def planned_tile(d):
-    """The largest R of 32, 16, 8 at which two buffers, each as wide as the widest activation it holds, fit the LDS; 0: none does."""
+def buffer_strides(seqs):
+    """Row strides of the two LDS buffers for these sequences of activation widths: each as wide as the widest activation it holds."""
     w = [0, 0]
-    for seq in sequences(d):
+    for seq in seqs:
         for i, width in enumerate(seq):
             w[i & 1] = max(w[i & 1], lds_stride(width))
+    return w
+
+
+def tile_of(seqs):
+    """The largest R of 32, 16, 8 at which the two buffers fit the LDS; 0: none does."""
+    w = buffer_strides(seqs)
     return next((R for R in (32, 16, 8) if R * (w[0] + w[1]) * 4 <= LDS_BYTES), 0)
+
+
+def planned_tile(d):
+    return tile_of(sequences(d))
 
 
 def layers(d):

@@ -13,7 +13,7 @@ import torch
 import torch.nn as nn
 
 from tests.test_policy_host import max_err, parity_bound
-from tests.test_policy_recurrent_host import RESET_BEFORE, RNETS, STEPS, load_states, make_inputs, make_rnet, shared, state_keys
+from tests.test_policy_recurrent_host import RESET_BEFORE, RNETS, STEPS, load_states, make_inputs, make_rnet, net, net_key, shared, state_keys
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -23,9 +23,10 @@ _GPU = {}
 
 
 def gpu_module(name):
-    if name not in _GPU:
-        _GPU[name] = copy.deepcopy(make_rnet(name)).to(DEV)
-    return _GPU[name]
+    """The module of net set `name` (an RNETS name, or a row of another table: see `net`) on the device, moved once."""
+    if net_key(name) not in _GPU:
+        _GPU[net_key(name)] = copy.deepcopy(make_rnet(name)).to(DEV)
+    return _GPU[net_key(name)]
 
 
 def fused(name, module=None):
@@ -54,7 +55,7 @@ def started(name, n):
     """A FusedPolicy whose states of batch size n hold the case's incoming states."""
     s = shared(name, n)
     fp = fused(name)
-    fp.set_hidden_states(to_reference(s["inp"]["start"], RNETS[name]["kind"]), n=n)
+    fp.set_hidden_states(to_reference(s["inp"]["start"], net(name)["kind"]), n=n)
     return fp, s
 
 
@@ -64,7 +65,7 @@ def step(fp, inp, t, **kw):
 
 def check_step(name, n, fp, s, t):
     """Outputs and states after step t against the float64 oracle, each within the parity rule on the float32 yardstick of the same step."""
-    kind = RNETS[name]["kind"]
+    kind, name = net(name)["kind"], net_key(name)
     torch.cuda.synchronize()
     got = dict(mu=fp.last_mu, values=fp.last_values, actions=fp.last_actions, log_prob=fp.last_log_prob, **live(fp, kind))
     ref, f32 = s["ref"][t], s["f32"][t]

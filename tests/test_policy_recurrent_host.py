@@ -34,6 +34,20 @@ STEPS = 5
 RESET_BEFORE = (2, 4)         # a reset mask is applied before these steps of the five
 
 
+def net(name):
+    """A net set: its RNETS name, or the dict itself (tests/policy_recurrent_edges.py has a table of its own, whose rows carry "name")."""
+    return RNETS[name] if isinstance(name, str) else name
+
+
+def net_key(name):
+    return name if isinstance(name, str) else name["name"]
+
+
+def mem_dims(d, w):
+    """(input width, rnn layers, H) of memory_a (w = "a") or memory_c ("c"): the critic's takes the optional keys `layers_c` and `H_c`."""
+    return (d["obs"], d["layers"], d["H"]) if w == "a" else (d["cobs"], d.get("layers_c", d["layers"]), d.get("H_c", d["H"]))
+
+
 class Memory(nn.Module):
     """One time step of an rnn on its own hidden states (None: zeros), as the reference's Memory in inference mode."""
 
@@ -52,14 +66,17 @@ class Memory(nn.Module):
 
 
 class RecurrentStandIn(nn.Module):
+    """memory_a -> actor, memory_c -> critic from a net-set dict.  The optional keys `H_c`, `layers_c` and `mlp_c` give the critic's
+    memory and MLP sizes of their own (default: `H`, `layers`, `mlp`, as in every RNETS row)."""
     is_recurrent = True
 
     def __init__(self, d, clip=None):
         super().__init__()
-        self.memory_a = Memory(d["obs"], d["kind"], d["layers"], d["H"])
-        self.memory_c = Memory(d["cobs"], d["kind"], d["layers"], d["H"])
-        self.actor = mlp(d["H"], d["mlp"], d["A"], nn.Hardtanh(-clip, clip) if clip is not None else None)
-        self.critic = mlp(d["H"], d["mlp"], 1)
+        (in_a, layers_a, H_a), (in_c, layers_c, H_c) = mem_dims(d, "a"), mem_dims(d, "c")
+        self.memory_a = Memory(in_a, d["kind"], layers_a, H_a)
+        self.memory_c = Memory(in_c, d["kind"], layers_c, H_c)
+        self.actor = mlp(H_a, d["mlp"], d["A"], nn.Hardtanh(-clip, clip) if clip is not None else None)
+        self.critic = mlp(H_c, d.get("mlp_c", d["mlp"]), 1)
         self.std = nn.Parameter(torch.ones(d["A"]))
 
     def mean(self, obs):
@@ -80,7 +97,7 @@ def make_rnet(name, clip=None, seed=3):
     """The recurrent net set `name`, seeded in the style of `make_net`: every weight matrix uniform +-1.5 / sqrt(in) (for the rnn `in` is the
     matrix's own column count), biases +-0.5, std in [0.5, 1.5).  No Hardtanh by default, so that every actor output carries the whole
     chain's error instead of saturating at the clip."""
-    d = RNETS[name]
+    d = net(name)
     m = RecurrentStandIn(d, clip)
     g = torch.Generator().manual_seed(seed)
     with torch.no_grad():
@@ -100,11 +117,11 @@ def state_keys(kind):
 def make_inputs(name, n, seed=11):
     """Seeded inputs of STEPS steps at batch size n: observations, injected noise, incoming states uniform +-1 and the two reset masks
     (row 0 is done in the first and alive in the second, so that N = 1 sees both)."""
-    d = RNETS[name]
+    d = net(name)
     g = torch.Generator().manual_seed(seed)
     obs, cobs = torch.randn(STEPS, n, d["obs"], generator=g), torch.randn(STEPS, n, d["cobs"], generator=g)
     noise = torch.randn(STEPS, n, d["A"], generator=g)
-    start = {k: torch.rand(d["layers"], n, d["H"], generator=g) * 2 - 1 for k in state_keys(d["kind"])}
+    start = {k: torch.rand(mem_dims(d, k[-1])[1], n, mem_dims(d, k[-1])[2], generator=g) * 2 - 1 for k in state_keys(d["kind"])}
     masks = {t: torch.rand(n, generator=g) < 0.3 for t in RESET_BEFORE}
     masks[RESET_BEFORE[0]][0], masks[RESET_BEFORE[1]][0] = True, False
     return dict(obs=obs, cobs=cobs, noise=noise, start=start, masks=masks)
@@ -153,6 +170,9 @@ def torch_steps(m, inp, dtype, steps=STEPS):
 
 # ---- float32 numpy restatement of the cells, with the deliberately wrong variants --------------------------------------------------------
 VARIANTS = {"ifog": "lstm", "r_whole": "gru", "z_swapped": "gru", "no_bhh": None, "stale_layer": None}      # which kind a variant applies to
+# what the state handling could get wrong (tests/test_policy_recurrent_edges_host.py runs them): a reset that zeroes h and leaves c; rnn
+# layer 1 staged from layer 0's incoming h; the critic's run reading the actor's states (only where both have one shape)
+STATE_VARIANTS = {"c_not_reset": "lstm", "prev_of_layer0": None, "swapped_memories": None}
 
 
 def _sig(x):
@@ -162,7 +182,7 @@ def _sig(x):
 def np_memory_step(rnn, x, h, c, variant=None):
     """One time step of `rnn` (nn.LSTM / nn.GRU) on x (N, in) from states h (and c) (layers, N, H), all float32; returns (top h', h', c').
     `variant`: None, or one of VARIANTS -- gate order (i, f, o, g); r applied to the whole sum; z and 1 - z swapped; b_hh dropped; layer 2
-    reading the OLD h of layer 1."""
+    reading the OLD h of layer 1 -- or `prev_of_layer0` of STATE_VARIANTS: layer 1 starts from layer 0's incoming h."""
     lstm = isinstance(rnn, nn.LSTM)
     H = rnn.hidden_size
     f32 = lambda t: t.detach().numpy().astype(np.float32)
@@ -172,7 +192,8 @@ def np_memory_step(rnn, x, h, c, variant=None):
         w_ih, w_hh, b_ih, b_hh = (f32(getattr(rnn, f"{n}_l{k}")) for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"))
         if variant == "no_bhh":
             b_hh = np.zeros_like(b_hh)
-        gx, gh = (x @ w_ih.T + b_ih).astype(np.float32), (h[k] @ w_hh.T + b_hh).astype(np.float32)
+        hk = h[0] if variant == "prev_of_layer0" else h[k]
+        gx, gh = (x @ w_ih.T + b_ih).astype(np.float32), (hk @ w_hh.T + b_hh).astype(np.float32)
         if lstm:
             g = gx + gh
             order = (0, 1, 3, 2) if variant == "ifog" else (0, 1, 2, 3)
@@ -182,21 +203,24 @@ def np_memory_step(rnn, x, h, c, variant=None):
         else:
             r, z = _sig(gx[:, :H] + gh[:, :H]), _sig(gx[:, H:2 * H] + gh[:, H:2 * H])
             n = np.tanh(r * (gx[:, 2 * H:] + gh[:, 2 * H:]) if variant == "r_whole" else gx[:, 2 * H:] + r * gh[:, 2 * H:])
-            h_new[k] = z * n + (1 - z) * h[k] if variant == "z_swapped" else (1 - z) * n + z * h[k]
+            h_new[k] = z * n + (1 - z) * hk if variant == "z_swapped" else (1 - z) * n + z * hk
         x = h[k] if variant == "stale_layer" else h_new[k]
     return h_new[-1], h_new, c_new
 
 
 def np_steps(m, inp, variant=None, steps=STEPS):
-    """The numpy restatement of `torch_steps`' last step: mu, values and the states after `steps` steps."""
+    """The numpy restatement of `torch_steps`' last step: mu, values and the states after `steps` steps.  `variant`: one of VARIANTS, or of
+    STATE_VARIANTS."""
     st = {k: v.numpy().astype(np.float32).copy() for k, v in inp["start"].items()}
     for t in range(steps):
         if t in inp["masks"]:
-            for v in st.values():
-                v[:, inp["masks"][t].numpy()] = 0
-        top = {}
+            for k, v in st.items():
+                if not (variant == "c_not_reset" and k.startswith("c_")):
+                    v[:, inp["masks"][t].numpy()] = 0
+        top, pre = {}, dict(st)                                  # the states this step starts from: a cell returns new arrays
         for w, mem, x in (("a", m.memory_a, inp["obs"][t]), ("c", m.memory_c, inp["cobs"][t])):
-            top[w], st["h_" + w], c = np_memory_step(mem.rnn, x.numpy(), st["h_" + w], st.get("c_" + w), variant)
+            src = "a" if variant == "swapped_memories" else w
+            top[w], st["h_" + w], c = np_memory_step(mem.rnn, x.numpy(), pre["h_" + src], pre.get("c_" + src), variant)
             if c is not None:
                 st["c_" + w] = c
     return dict(mu=np_forward(m.actor, top["a"]), values=np_forward(m.critic, top["c"]), **st)
@@ -207,10 +231,11 @@ _SHARED = {}
 
 def shared(name, n):
     """Per (net set, N), computed once and left unchanged: the module, the inputs, the float64 oracle and the float32 yardstick."""
-    if (name, n) not in _SHARED:
+    key = (net_key(name), n)
+    if key not in _SHARED:
         m, inp = make_rnet(name), make_inputs(name, n)
-        _SHARED[name, n] = dict(module=m, inp=inp, ref=torch_steps(m, inp, torch.float64), f32=torch_steps(m, inp, torch.float32))
-    return _SHARED[name, n]
+        _SHARED[key] = dict(module=m, inp=inp, ref=torch_steps(m, inp, torch.float64), f32=torch_steps(m, inp, torch.float32))
+    return _SHARED[key]
 
 
 # ---- the struct ---------------------------------------------------------------------------------------------------------------------------
@@ -255,9 +280,10 @@ def test_header_declares_the_reset_entry_point():
 
 # ---- the descriptor -----------------------------------------------------------------------------------------------------------------------
 def _memory_tensors(d, n, prev=False, mask=False):
-    t = {k: torch.zeros(d["layers"], n, d["H"]) for k in state_keys(d["kind"])}
+    z = lambda k: torch.zeros(mem_dims(d, k[-1])[1], n, mem_dims(d, k[-1])[2])
+    t = {k: z(k) for k in state_keys(d["kind"])}
     if prev:
-        t.update({k.replace("_", "_prev_"): torch.zeros(d["layers"], n, d["H"]) for k in state_keys(d["kind"])})
+        t.update({k.replace("_", "_prev_"): z(k) for k in state_keys(d["kind"])})
     if mask:
         t["reset"] = torch.zeros(n, dtype=torch.uint8)
     return t
