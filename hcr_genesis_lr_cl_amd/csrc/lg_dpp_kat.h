@@ -318,4 +318,6 @@
     X("src1", "dpp", 0, "v_mul_f32_dpp %[r], %[x], %[y] quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf\n\t" "v_sub_f32_dpp %[d], %[z], %[r] quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t") \
     X("src1", "dpp", 0, "v_mul_f32_dpp %[r], %[x], %[y] quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf\n\t" "v_sub_f32_dpp %[d], %[z], %[r] quad_perm:[1,1,1,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t") \
     X("src1", "dpp", 0, "v_mul_f32_dpp %[r], %[x], %[y] quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf\n\t" "v_sub_f32_dpp %[d], %[z], %[r] quad_perm:[2,2,2,2] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t") \
-    X("src1", "dpp", 0, "v_mul_f32_dpp %[r], %[x], %[y] quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf\n\t" "v_sub_f32_dpp %[d], %[z], %[r] quad_perm:[3,3,3,3] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t")
+    X("src1", "dpp", 0, "v_mul_f32_dpp %[r], %[x], %[y] quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf\n\t" "v_sub_f32_dpp %[d], %[z], %[r] quad_perm:[3,3,3,3] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t") \
+    X("src1", "dpp", 1, "v_mul_f32_dpp %[r], %[x], %[y] quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf\n\t" "v_mov_b32_e32 %[t], %[x]\n\t" "v_sub_f32_dpp %[d], %[z], %[r] quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t") \
+    X("src1", "dpp", 1, "v_mul_f32_dpp %[r], %[x], %[y] quad_perm:[0,0,0,0] row_mask:0xf bank_mask:0xf\n\t" "v_mov_b32_e32 %[t], %[x]\n\t" "v_add_f32_dpp %[d], %[z], %[r] quad_perm:[1,1,1,1] row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t")

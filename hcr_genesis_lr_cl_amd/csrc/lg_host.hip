@@ -364,8 +364,11 @@ template <int LEGS, int JPL> static LgPlan plan(const LgEngine *h, uint32_t ph, 
     const bool repl = sw[SW_MDP_REPLICAS] >= 0 ? sw[SW_MDP_REPLICAS] != 0 : (LEGS == 2 && (long long)threads * 4 <= 1024LL * BLOCK);
     const auto mdp = [&](uint32_t m) {   // POST | RESET or POST leg per lane, behind a physics launch or on its own
         if (m == PR) add(repl ? K::post_reset_repl : K::post_reset, repl ? rgrid : grid); else add(K::post, grid); };
-    // rs(P): the task's reward set is profile P's default one -> the instantiation with it as a constant (lg_quad.h RS; LG_REWARD_SET_CONST=0: off)
-    const auto rs = [&](int prof) { return (unsigned)h->hot.reward_mask == lg_default_reward_mask(prof) && sw[SW_REWARD_SET_CONST] != 0; };
+    // rs(P): the task's reward set is profile P's default one and the solver options are the configs' defaults -> the instantiation with
+    // them as constants (lg_quad.h RS; LG_REWARD_SET_CONST=0: off)
+    const auto rs = [&](int prof) {
+        return (unsigned)h->hot.reward_mask == lg_default_reward_mask(prof) && h->hot.o_contact_iters == LG_DEFAULT_CONTACT_ITERS &&
+               h->hot.o_contact_w_every == LG_DEFAULT_CONTACT_W_EVERY && sw[SW_REWARD_SET_CONST] != 0; };
     // physics layout (lg_quad.h): one vector component per lane while the batch cannot fill the SIMDs with one leg per
     // lane; the MDP phases then follow in a second launch on the same stream
     // auto: component-per-lane while that needs at most two waves per SIMD (1024 SIMDs).  Measured go2, us per step,

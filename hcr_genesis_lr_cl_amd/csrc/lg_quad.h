@@ -413,6 +413,10 @@ constexpr int quad_block(int prof, unsigned mph) { return prof == LG_PROF_TRON1_
 // constant.  The terms are evaluated behind one scalar test each -- thirty-two branches that cut the reward section into as many basic
 // blocks, each term's reduction over the env's lanes (four dependent DPP adds with their wait states) alone in its own; with the set known
 // the unused terms are gone and the others interleave (go2: -0.5 us).  Any other set of terms runs the RS = false instantiation.
+// RS also makes the solver options of the task configs constants (lg_shared.h LG_DEFAULT_CONTACT_ITERS / _W_EVERY, host-checked the same way):
+// the two contact sweeps are straight-line code and W is recomputed on every sub-step, so nothing of it is carried between sub-steps and the
+// test around the contact stage is gone (go2: -0.7 us).  Other options run the RS = false instantiation; tests/test_gpu_profile_constants.py
+// compares what the two forms leave in the buffers bit for bit.
 template <int LEGS, bool DO_PRE, unsigned MPH, int PROF = 0, int JPL = 3, bool INJ = false, bool RS = false>
 __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams p) {
     using namespace q4;
@@ -826,7 +830,9 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
     float f_link[4] = {0.f, 0.f, 0.f, 0.f};   // net contact force on hip, thigh, calf, foot links (component)
     float f_base = 0.f;
 
-    const int decim = INJ ? 0 : HOT(o_decimation), iters = HOT(o_contact_iters), w_every = HOT(o_contact_w_every);
+    // RS: the solver options are the configs' defaults, host-checked like the reward set (the same statements in the same order either way)
+    const int decim = INJ ? 0 : HOT(o_decimation), iters = RS ? LG_DEFAULT_CONTACT_ITERS : HOT(o_contact_iters);
+    const int w_every = RS ? LG_DEFAULT_CONTACT_W_EVERY : HOT(o_contact_w_every);
     QM Ac_keep = {0.f, 0.f, 0.f};             // dt * W of this leg's foot as of its latest refresh (LgSimOptions.contact_w_every)
     const float mv = HOT(o_max_base_lin_vel), mw = HOT(o_max_base_ang_vel);
 
@@ -1315,12 +1321,16 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
             }
             if (sub == 0) STAMP(18);
             float resp_c = 0.f;
-            for (int it = 0; it < iters; it++) {
+            const auto sweep = [&](const int it) {
                 // foot: velocity it would have without its own force, then the local law
                 {
                     const float vo = vfree + resp_c * dt - mulv(Ac, fc);
                     const float vo0 = bc<0>(vo);
-                    const float rn = kc * depth - kappa * vo0;
+                    // Which product of a sum of two rides on the add is the compiler's choice, and it goes by what else uses them: a product
+                    // that is the same in every sweep (kc depth here, kl lim_e below) is hoisted out of a loop but stands next to its sum in
+                    // straight-line code, and the sum then rounds the other way.  Spelled out (as the loop form has always been compiled),
+                    // both forms of the sweeps round alike.
+                    const float rn = fmaf(-kappa, vo0, kc * depth);
                     // stick trial: rows of [1 + kappa A00, kappa A01, kappa A02; A1.; A2.]
                     QM m;
                     m.c0 = L.is0 ? 1.f + kappa * Ac.c0 : Ac.c0;
@@ -1347,8 +1357,8 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
                 {   // limit stops of the three joints (joint lanes)
                     float C = dinvv;
                     if (it > 0 && lim_T > 0.f) C = fminf(fmaxf(lim_s * dqdd * rcp(lim_T), C), 8.f * C);
-                    const float vin = -lim_s * (qd + dt * (qdd + dqdd)) + dt * lim_T * C;
-                    const float Tn = (kl * lim_e + kapl * vin) * rcp(1.f + kapl * dt * C);
+                    const float vin = fmaf(dt * lim_T, C, -(lim_s * (qd + dt * (qdd + dqdd))));
+                    const float Tn = fmaf(kapl, vin, kl * lim_e) * rcp(1.f + kapl * dt * C);
                     lim_T = lim_s != 0.f ? fmaxf(Tn, 0.f) : 0.f;
                     tl = lim_s * lim_T;
                 }
@@ -1362,7 +1372,9 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
                 const QV6 ac = resp_down(L, J, da0, du, dqdd);
                 const float ra = ac.l + cross(ac.a, cpr);
                 resp_c = mulv(E, ra);
-            }
+            };
+            if constexpr (RS) { static_assert(LG_DEFAULT_CONTACT_ITERS == 2); sweep(0); sweep(1); }   // straight-line code
+            else for (int it = 0; it < iters; it++) sweep(it);
             if (JPL == 4) f_link[3] += mulv(ET, fc);   // the foot is the last body's own link: on top of its sole corners
             else f_link[3] = mulv(ET, fc);
         } else if (JPL != 4) {
@@ -2007,7 +2019,12 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
         float total = 0.f;
         auto add = [&](int id, float r) {            // `id` is a compile-time constant at every call
             const float rew = r * scl[id];
-            total += rew;
+            {   // the rounded product is added, never fused into the sum: that is what the constant reward set (RS: the terms in one basic
+                // block, `rew` kept for the episode sum next to it) has always compiled to, while a term alone in its block got a
+                // multiply-add -- the last bit of rew_buf differed between the two forms.  Said here, both round alike.
+#pragma clang fp contract(off)
+                total = total + rew;
+            }
             if constexpr (BQ) es[id >> 3] = ei == (id & 7) ? es[id >> 3] + rew : es[id >> 3];
             else if (id < 16) es0 = ei == id ? es0 + rew : es0;
             else es1 = ei == id - 16 ? es1 + rew : es1;

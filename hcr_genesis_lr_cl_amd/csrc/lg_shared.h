@@ -377,6 +377,9 @@ void lg_launch_quad_inj(dim3 grid, hipStream_t st, const KParams &p);
 constexpr unsigned lg_default_reward_mask(int prof) {
     return prof == LG_PROF_GO2_FLAT ? 0x26a2296fu : prof == LG_PROF_GO2_WTW ? 0x7f2c0967u : (prof == LG_PROF_GO2_EE || prof == LG_PROF_GO2_PROGRAM) ? 0x242a6567u : 0u;
 }
+// The solver options of the task configs (config.py HipCfg defaults): the RS instantiations have them as constants too -- two contact sweeps
+// as straight-line code, W of every foot recomputed on every sub-step (nothing kept between sub-steps).  plan() checks the engine's options.
+constexpr int LG_DEFAULT_CONTACT_ITERS = 2, LG_DEFAULT_CONTACT_W_EVERY = 1;
 // The reward terms a profile's component-layout tail does not carry: a task with one of them active is outside the profile (lg_host.hip).
 constexpr unsigned lg_rbits(std::initializer_list<int> terms) { unsigned m = 0; for (int k : terms) m |= 1u << k; return m; }
 constexpr unsigned lg_tail_reward_excluded(int prof) {
