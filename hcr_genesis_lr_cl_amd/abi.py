@@ -1,4 +1,4 @@
-"""ctypes mirror of include/lgsim.h, include/lgrollout.h, include/lgsensor.h and include/lgpolicy.h (the C ABI) and the loader of the HIP library.
+"""ctypes mirror of include/lgsim.h, include/lgrollout.h, include/lgsensor.h, include/lgpolicy.h and include/lgppo.h (the C ABI) and the loader of the HIP library.
 
 Field order and types must match the header exactly; tests/test_abi.py compiles a C
 probe that prints sizeof/offsetof for every struct and compares them with these classes.
@@ -286,6 +286,11 @@ def load_lib():
     lib.lg_policy_reset.argtypes = [C.POINTER(LgPolicyRecurrentArgs), vp, vp]
     for f in POLICY_EXPORTS:
         getattr(lib, f).restype = C.c_int
+    if hasattr(lib, "lg_ppo_loss"):              # absent from libraries older than the fused PPO loss head
+        lib.lg_ppo_loss.argtypes = [C.POINTER(LgPpoLossArgs), vp]
+        lib.lg_ppo_loss_workspace.argtypes = [C.POINTER(LgPpoLossArgs)]
+        for f in PPO_EXPORTS:
+            getattr(lib, f).restype = C.c_int
     lib.lg_last_error.restype = C.c_char_p
     lib.lg_last_kernel.argtypes = [H]
     lib.lg_last_kernel.restype = C.c_char_p
@@ -304,6 +309,11 @@ ROLLOUT_EXPORTS = ["lg_rollout_record", "lg_rollout_gae", "lg_rollout_traj_index
                    "lg_rollout_unpad", "lg_rollout_gather", "lg_rollout_gae_groups"]          # include/lgrollout.h
 SENSOR_EXPORTS = ["lg_depth_render"]                                                          # include/lgsensor.h
 POLICY_EXPORTS = ["lg_policy_act", "lg_policy_row_tile", "lg_policy_act_recurrent", "lg_policy_row_tile_recurrent", "lg_policy_reset"]   # include/lgpolicy.h
+PPO_EXPORTS = ["lg_ppo_loss", "lg_ppo_loss_workspace"]                                        # include/lgppo.h
+PPO_MAX_ACTIONS, PPO_MAX_GROUPS = 64, 2
+PPO_CLIPPED_VALUE, PPO_SPO = 1, 2
+PPO_THREADS, PPO_MAX_BLOCKS, PPO_PARTIAL_SLOTS = 256, 512, 6
+PPO_R_LOSS, PPO_R_SURROGATE, PPO_R_VALUE, PPO_R_ENTROPY, PPO_R_KL, PPO_RESULT_FLOATS = 0, 1, 3, 4, 5, 8
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 2048
 POLICY_MAX_RNN_LAYERS, POLICY_MAX_RNN_HIDDEN = 2, 512
 POLICY_LSTM, POLICY_GRU = 1, 2
@@ -383,6 +393,20 @@ class LgPolicyRecurrentArgs(LgPolicyArgs):
     """struct { LgPolicyArgs args; LgPolicyMemory memory_a, memory_c; }: a ctypes subclass lays its own fields out behind the base's, so
     the members of `args` are attributes of this object as they are of a plain LgPolicyArgs."""
     _fields_ = [("memory_a", LgPolicyMemory), ("memory_c", LgPolicyMemory)]
+
+
+class LgPpoGroup(C.Structure):
+    _fields_ = [("n_rows", i32)] + [(f"{n}_stride", i32) for n in ("mu", "sigma", "actions", "old_mu", "old_sigma", "old_log_prob", "advantages",
+                                                                    "grad_mu", "grad_sigma")] + [
+        (n, C.c_void_p) for n in ("mu", "sigma", "actions", "old_mu", "old_sigma", "old_log_prob", "advantages", "grad_mu", "grad_sigma")]
+
+
+class LgPpoLossArgs(C.Structure):
+    _fields_ = [("n_groups", i32), ("n_actions", i32), ("flags", u32), ("n_value_rows", i32), ("group", LgPpoGroup * PPO_MAX_GROUPS),
+                ("values", C.c_void_p), ("returns", C.c_void_p), ("target_values", C.c_void_p), ("grad_values", C.c_void_p),
+                ("values_stride", i32), ("returns_stride", i32), ("target_values_stride", i32), ("grad_values_stride", i32),
+                ("clip_param", C.c_double), ("value_loss_coef", C.c_double), ("entropy_coef", C.c_double),
+                ("partials", C.c_void_p), ("partials_capacity", i64), ("result", C.c_void_p)]
 
 
 def check(rc, lib=None):
