@@ -95,16 +95,15 @@ __device__ __forceinline__ void policy_tile(const KPpo &k, const KGroup &G, int 
     const float old_lp = valid ? G.old_log_prob[r * G.old_log_prob_stride] : 0.f;
     const float adv = valid ? G.advantages[r * G.advantages_stride] : 0.f;
     double lp = 0.0, ent = 0.0, kl = 0.0;
-    float dmu[4], dsg[4], inv_s[4];      // d logp / d mu, d logp / d sigma, 1 / sigma
+    float dmu[4], dsg[4], inv_s[4];      // d logp / d mu, the (a - mu)^2 / sigma^3 part of d logp / d sigma, 1 / sigma
     for (int j = 0; j < 4; j++) {
         const bool col = on && c0 + j < A;
         const float d = ac[j] - mu[j], s = sg[j], var = s * s, ls = logf(s);
-        const float t_lp = -(d * d) / (2.f * var) - ls - 0.918938533204672742f;
-        const float t_ent = 1.418938533204672742f + ls;
+        const float t_lp = -(d * d) / (2.f * var) - ls;
         inv_s[j] = 1.f / s;
         dmu[j] = d / var;
-        dsg[j] = (d * d) / (var * s) - inv_s[j];
-        if (col) { lp += (double)t_lp; ent += (double)t_ent; }
+        dsg[j] = (d * d) / (var * s);
+        if (col) { lp += (double)t_lp; ent += (double)ls; }
         if (col && has_kl) {
             const float dm = omu[j] - mu[j];
             kl += (double)(logf(s / osg[j] + 1.e-5f) + (osg[j] * osg[j] + dm * dm) / (2.f * var) - 0.5f);
@@ -115,20 +114,27 @@ __device__ __forceinline__ void policy_tile(const KPpo &k, const KGroup &G, int 
         ent += __shfl_xor(ent, m);
         kl += __shfl_xor(kl, m);
     }
+    // the per-column constants once per row and in float64: as a float in every column term, 0.5 log 2 pi is off by 1.6e-8, the same way
+    // in every column, and A of those shift the row's log-prob (1e-6 at A = 64) instead of averaging out
+    lp -= (double)A * 0.918938533204672742;
+    ent += (double)A * 1.418938533204672742;
     const float ratio = expf((float)(lp - (double)old_lp));
-    float term, g;                               // the row's surrogate term and d term / d ratio
+    // the row's surrogate term and d loss / d ratio.  The 1 / B of the mean goes into the advantage first, as in autograd's backward:
+    // |Adv| near FLT_MAX then overflows where the gradient itself does and not in a factor that 1 / B would have brought back.
+    const float adv_b = adv * G.inv_rows;
+    float term, g;
     if (k.spo) {
-        const float e = ratio - 1.f, aa = fabsf(adv);
-        term = -(adv * ratio - aa * (e * e) / k.two_clip);
-        g = -(adv - aa * (2.f * e) / k.two_clip);
+        const float e = ratio - 1.f;
+        term = -(adv * ratio - fabsf(adv) * (e * e) / k.two_clip);
+        g = -(adv_b - fabsf(adv_b) * (2.f * e) / k.two_clip);
     } else {
         const float rc = nan_clamp(ratio, k.ratio_lo, k.ratio_hi);
         const float s1 = -adv * ratio, s2 = -adv * rc;
         const bool inside = ratio >= k.ratio_lo && ratio <= k.ratio_hi;      // clamp's closed interval
         term = nan_max(s1, s2);
-        g = s1 > s2 ? -adv : (s2 > s1 ? 0.f : (s1 == s2 ? (inside ? -adv : -0.5f * adv) : NAN));
+        g = s1 > s2 ? -adv_b : (s2 > s1 ? 0.f : (s1 == s2 ? (inside ? -adv_b : -0.5f * adv_b) : NAN));
     }
-    const float dlp = g * ratio * G.inv_rows;    // d loss / d logp of this row
+    const float dlp = g * ratio;                 // d loss / d logp of this row
     if (valid && q == 0) {
         acc[S_SUR0 + gi] += (double)term;
         acc[S_ENT] += ent;
@@ -138,7 +144,8 @@ __device__ __forceinline__ void policy_tile(const KPpo &k, const KGroup &G, int 
         float gm[4], gs[4];
         for (int j = 0; j < 4; j++) {
             gm[j] = dlp * dmu[j];
-            gs[j] = dlp * dsg[j] - k.entropy_scale * inv_s[j];
+            // the two partials of sigma apart, as autograd adds them: a row whose d loss / d logp is infinite gives inf - inf = NaN
+            gs[j] = dlp * dsg[j] - dlp * inv_s[j] - k.entropy_scale * inv_s[j];
         }
         store_quad(G.grad_mu + r * G.grad_mu_stride, c0, A, gm);
         store_quad(G.grad_sigma + r * G.grad_sigma_stride, c0, A, gs);

@@ -21,7 +21,15 @@
  * conventions where branches meet: equal operands of a max share the gradient in halves (inside the clip range the halves add up to
  * the unclipped gradient), a clipped branch that wins contributes zero, clamp passes the gradient on its closed interval.
  * NaN is not silent: max and clamp are compares that pass a NaN on, so a NaN in a row reaches that row's gradients and every scalar the
- * row feeds, and nothing else.
+ * row feeds, and nothing else.  What a row feeds: mu and sigma feed the surrogate, the KL and grad_mu / grad_sigma, sigma also the
+ * entropy; actions, old_log_prob and advantages the surrogate and grad_mu / grad_sigma; old_mu and old_sigma the KL alone; values and
+ * returns the value loss and grad_values, target_values too under LG_PPO_CLIPPED_VALUE and nothing otherwise (the column is not read).
+ * This is torch autograd's reach of a NaN with one exception: for a NaN target value autograd returns the finite 2 (v - R) coef / B_v
+ * in grad_values (max's backward hands the gradient to both operands when neither compare holds, clamp's zeroes the clipped one); here
+ * that element is NaN, by the rule above.
+ * Where float32 overflows (exp to inf, |Adv| infinite or near FLT_MAX) the gradients have the NaN / inf pattern of torch's float32
+ * autograd: the two partials of sigma are added apart, so a row with an infinite d loss / d logp has NaN in grad_sigma (inf - inf), and
+ * the 1 / B of the mean is applied to the advantage first.  sigma > 0 is the caller's contract: nothing checks it.
  */
 #ifndef LGPPO_H
 #define LGPPO_H

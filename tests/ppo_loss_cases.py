@@ -57,23 +57,41 @@ def old_log_prob_for(mu, sigma, actions, ratio):
 def make_inputs(case):
     """float32 numpy inputs of a table case: dict(groups=[{mu, sigma, actions, old_log_prob, advantages, old_mu, old_sigma}], values,
     returns, target_values).  The old log-prob and the target values are free input columns, so they are chosen to put the ratio and the
-    value step where gap_ratio / gap_step drew them: both sides of every branch, never on one."""
+    value step where gap_ratio / gap_step drew them: both sides of every branch, never on one.  A case given as a dict may carry `clip`
+    (default CLIP), the boundaries the ratios and steps are placed around; the draws of a case do not depend on it."""
     c = CASES[case] if isinstance(case, str) else case
-    rng = np.random.default_rng(c["seed"])
+    rng, clip = np.random.default_rng(c["seed"]), c.get("clip", CLIP)      # gap_ratio / gap_step draw the same numbers at every clip
     f = lambda x: np.ascontiguousarray(x, dtype=np.float32)
     A, groups = c["A"], []
     for B, kl in zip(c["rows"], c["kl"]):
         mu, sigma = f(rng.normal(size=(B, A)) * 0.5), f(0.3 + 0.9 * rng.random((B, A)))
         old_mu, old_sigma = f(mu + 0.1 * sigma * rng.normal(size=(B, A))), f(sigma * np.exp(0.05 * rng.normal(size=(B, A))))
         actions = f(old_mu + old_sigma * rng.normal(size=(B, A)))
-        g = dict(mu=mu, sigma=sigma, actions=actions, old_log_prob=old_log_prob_for(mu, sigma, actions, gap_ratio(rng, B)).reshape(B, 1),
+        g = dict(mu=mu, sigma=sigma, actions=actions, old_log_prob=old_log_prob_for(mu, sigma, actions, gap_ratio(rng, B, clip)).reshape(B, 1),
                  advantages=f(rng.normal(size=(B, 1))), old_mu=old_mu if kl else None, old_sigma=old_sigma if kl else None)
         groups.append(g)
     Bv = c["vrows"]
     values = f(rng.normal(size=(Bv, 1)))
-    target_values = f(values.astype(np.float64) - gap_step(rng, Bv).reshape(Bv, 1))
+    target_values = f(values.astype(np.float64) - gap_step(rng, Bv, clip).reshape(Bv, 1))
     returns = f(target_values + 0.5 * rng.normal(size=(Bv, 1)))
     return dict(groups=groups, values=values, returns=returns, target_values=target_values)
+
+
+def assert_both_sides(name, inp, clip=CLIP):
+    """In float64: at B >= 63 between 10 % and 60 % of the rows have the ratio outside [1 - clip, 1 + clip], likewise |v - v_t| > clip, both
+    sides and both signs of the advantage occur, and no row lies within 1e-4 of a boundary.  No row is excluded."""
+    for g in inp["groups"]:
+        r = np.exp(log_prob64(g["mu"], g["sigma"], g["actions"]) - g["old_log_prob"].astype(np.float64).reshape(-1))
+        assert np.minimum(np.abs(r - (1 - clip)), np.abs(r - (1 + clip))).min() > 1e-4, name
+        share = np.mean((r < 1 - clip) | (r > 1 + clip))
+        if len(r) >= 63:
+            assert 0.10 <= share <= 0.60, (name, share)
+            assert (r < 1 - clip).any() and (r > 1 + clip).any() and (g["advantages"] > 0).any() and (g["advantages"] < 0).any()
+    d = inp["values"].astype(np.float64) - inp["target_values"].astype(np.float64)
+    assert np.abs(np.abs(d) - clip).min() > 1e-4, name
+    if len(d) >= 63:
+        assert 0.10 <= np.mean(np.abs(d) > clip) <= 0.60, name
+        assert (d > clip).any() and (d < -clip).any()
 
 
 def restate(inp, clipped, spo, ent, clip=CLIP, value_loss_coef=1.0, dtype=torch.float64, break_tie=False, drop_kl_eps=False):

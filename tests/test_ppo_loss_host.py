@@ -325,18 +325,7 @@ def test_inputs_sit_on_both_sides_of_every_branch(table_inputs):
     """In float64, for the fixed seeds: at B >= 63 between 10 % and 60 % of the rows have the ratio outside [1 - eps, 1 + eps], likewise
     |v - v_t| > eps, and no row of any case lies within 1e-4 of a boundary.  No row is excluded."""
     for name, inp in table_inputs.items():
-        for g in inp["groups"]:
-            r = np.exp(pc.log_prob64(g["mu"], g["sigma"], g["actions"]) - g["old_log_prob"].astype(np.float64).reshape(-1))
-            assert np.minimum(np.abs(r - (1 - pc.CLIP)), np.abs(r - (1 + pc.CLIP))).min() > 1e-4, name
-            share = np.mean((r < 1 - pc.CLIP) | (r > 1 + pc.CLIP))
-            if len(r) >= 63:
-                assert 0.10 <= share <= 0.60, (name, share)
-                assert (r < 1 - pc.CLIP).any() and (r > 1 + pc.CLIP).any() and (g["advantages"] > 0).any() and (g["advantages"] < 0).any()
-        d = inp["values"].astype(np.float64) - inp["target_values"].astype(np.float64)
-        assert np.abs(np.abs(d) - pc.CLIP).min() > 1e-4, name
-        if len(d) >= 63:
-            assert 0.10 <= np.mean(np.abs(d) > pc.CLIP) <= 0.60, name
-            assert (d > pc.CLIP).any() and (d < -pc.CLIP).any()
+        pc.assert_both_sides(name, inp)
     for c in pc.load_fixture(FIXTURE).values():                                                       # the fixture's rows likewise
         for g in c["inp"]["groups"]:
             r = np.exp(pc.log_prob64(g["mu"], g["sigma"], g["actions"]) - g["old_log_prob"].astype(np.float64).reshape(-1))
