@@ -1,4 +1,4 @@
-"""ctypes mirror of include/lgsim.h, include/lgrollout.h, include/lgsensor.h, include/lgpolicy.h and include/lgppo.h (the C ABI) and the loader of the HIP library.
+"""ctypes mirror of include/lgsim.h, include/lgrollout.h, include/lgsensor.h, include/lgpolicy.h, include/lgppo.h and include/lgoptim.h (the C ABI) and the loader of the HIP library.
 
 Field order and types must match the header exactly; tests/test_abi.py compiles a C
 probe that prints sizeof/offsetof for every struct and compares them with these classes.
@@ -291,6 +291,11 @@ def load_lib():
         lib.lg_ppo_loss_workspace.argtypes = [C.POINTER(LgPpoLossArgs)]
         for f in PPO_EXPORTS:
             getattr(lib, f).restype = C.c_int
+    if hasattr(lib, "lg_adam_step"):             # absent from libraries older than the fused optimizer step
+        lib.lg_adam_step.argtypes = [C.POINTER(LgAdamArgs), vp]
+        lib.lg_adam_workspace.argtypes = [C.POINTER(LgAdamArgs)]
+        for f in OPTIM_EXPORTS:
+            getattr(lib, f).restype = C.c_int
     lib.lg_last_error.restype = C.c_char_p
     lib.lg_last_kernel.argtypes = [H]
     lib.lg_last_kernel.restype = C.c_char_p
@@ -314,6 +319,12 @@ PPO_MAX_ACTIONS, PPO_MAX_GROUPS = 64, 2
 PPO_CLIPPED_VALUE, PPO_SPO = 1, 2
 PPO_THREADS, PPO_MAX_BLOCKS, PPO_PARTIAL_SLOTS = 256, 512, 6
 PPO_R_LOSS, PPO_R_SURROGATE, PPO_R_VALUE, PPO_R_ENTROPY, PPO_R_KL, PPO_RESULT_FLOATS = 0, 1, 3, 4, 5, 8
+OPTIM_EXPORTS = ["lg_adam_step", "lg_adam_workspace"]                                         # include/lgoptim.h
+ADAM_MAX_TENSORS = 64
+ADAM_CLIP, ADAM_KL_RULE = 1, 2
+ADAM_CHUNK, ADAM_THREADS, ADAM_MAX_BLOCKS = 1024, 256, 512
+ADAM_STATE_DOUBLES, ADAM_S_LR, ADAM_S_STEP = 2, 0, 1
+ADAM_RESULT_FLOATS, ADAM_R_GRAD_NORM, ADAM_R_CLIP_COEF, ADAM_R_LR, ADAM_R_STEP = 4, 0, 1, 2, 3
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 2048
 POLICY_MAX_RNN_LAYERS, POLICY_MAX_RNN_HIDDEN = 2, 512
 POLICY_LSTM, POLICY_GRU = 1, 2
@@ -407,6 +418,16 @@ class LgPpoLossArgs(C.Structure):
                 ("values_stride", i32), ("returns_stride", i32), ("target_values_stride", i32), ("grad_values_stride", i32),
                 ("clip_param", C.c_double), ("value_loss_coef", C.c_double), ("entropy_coef", C.c_double),
                 ("partials", C.c_void_p), ("partials_capacity", i64), ("result", C.c_void_p)]
+
+
+class LgAdamTensor(C.Structure):
+    _fields_ = [("param", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p), ("grad", C.c_void_p), ("numel", i64)]
+
+
+class LgAdamArgs(C.Structure):
+    _fields_ = [("n_tensors", i32), ("flags", u32), ("tensor", LgAdamTensor * ADAM_MAX_TENSORS),
+                ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("max_grad_norm", C.c_double), ("desired_kl", C.c_double),
+                ("kl", C.c_void_p), ("state", C.c_void_p), ("partials", C.c_void_p), ("partials_capacity", i64), ("result", C.c_void_p)]
 
 
 def check(rc, lib=None):
