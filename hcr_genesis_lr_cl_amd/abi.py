@@ -1,4 +1,4 @@
-"""ctypes mirror of include/lgsim.h, include/lgrollout.h, include/lgsensor.h, include/lgpolicy.h, include/lgppo.h and include/lgoptim.h (the C ABI) and the loader of the HIP library.
+"""ctypes mirror of include/lgsim.h, include/lgrollout.h, include/lgsensor.h, include/lgpolicy.h, include/lgppo.h, include/lgoptim.h and include/lgtrain.h (the C ABI) and the loader of the HIP library.
 
 Field order and types must match the header exactly; tests/test_abi.py compiles a C
 probe that prints sizeof/offsetof for every struct and compares them with these classes.
@@ -296,6 +296,12 @@ def load_lib():
         lib.lg_adam_workspace.argtypes = [C.POINTER(LgAdamArgs)]
         for f in OPTIM_EXPORTS:
             getattr(lib, f).restype = C.c_int
+    if hasattr(lib, "lg_train_forward"):         # absent from libraries older than the fused learner pass
+        lib.lg_train_plan.argtypes = [C.POINTER(LgTrainArgs), C.POINTER(LgTrainPlan)]
+        lib.lg_train_forward.argtypes = [C.POINTER(LgTrainArgs), vp]
+        lib.lg_train_backward.argtypes = [C.POINTER(LgTrainArgs), vp]
+        for f in TRAIN_EXPORTS:
+            getattr(lib, f).restype = C.c_int
     lib.lg_last_error.restype = C.c_char_p
     lib.lg_last_kernel.argtypes = [H]
     lib.lg_last_kernel.restype = C.c_char_p
@@ -325,6 +331,9 @@ ADAM_CLIP, ADAM_KL_RULE = 1, 2
 ADAM_CHUNK, ADAM_THREADS, ADAM_MAX_BLOCKS = 1024, 256, 512
 ADAM_STATE_DOUBLES, ADAM_S_LR, ADAM_S_STEP = 2, 0, 1
 ADAM_RESULT_FLOATS, ADAM_R_GRAD_NORM, ADAM_R_CLIP_COEF, ADAM_R_LR, ADAM_R_STEP = 4, 0, 1, 2, 3
+TRAIN_EXPORTS = ["lg_train_plan", "lg_train_forward", "lg_train_backward"]                    # include/lgtrain.h
+TRAIN_CHAINS, TRAIN_ACTOR, TRAIN_CRITIC = 2, 0, 1
+TRAIN_WG_TILE, TRAIN_MIN_SLICE_ROWS, TRAIN_TARGET_JOBS, TRAIN_MAX_SLICES = 64, 64, 512, 32
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 2048
 POLICY_MAX_RNN_LAYERS, POLICY_MAX_RNN_HIDDEN = 2, 512
 POLICY_LSTM, POLICY_GRU = 1, 2
@@ -428,6 +437,32 @@ class LgAdamArgs(C.Structure):
     _fields_ = [("n_tensors", i32), ("flags", u32), ("tensor", LgAdamTensor * ADAM_MAX_TENSORS),
                 ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double), ("max_grad_norm", C.c_double), ("desired_kl", C.c_double),
                 ("kl", C.c_void_p), ("state", C.c_void_p), ("partials", C.c_void_p), ("partials_capacity", i64), ("result", C.c_void_p)]
+
+
+class LgTrainLayer(C.Structure):
+    _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p), ("grad_weight", C.c_void_p), ("grad_bias", C.c_void_p),
+                ("n_in", i32), ("n_out", i32), ("elu", i32), ("reserved", i32)]
+
+
+class LgTrainChain(C.Structure):
+    _fields_ = [("input", C.c_void_p), ("in_stride", i32), ("n_layers", i32), ("layer", LgTrainLayer * POLICY_MAX_LAYERS)]
+
+
+class LgTrainArgs(C.Structure):
+    _fields_ = [("n_rows", i32), ("clip_on", i32), ("clip_actions", f32), ("reserved", i32), ("chain", LgTrainChain * TRAIN_CHAINS),
+                ("std", C.c_void_p), ("grad_std", C.c_void_p), ("mu", C.c_void_p), ("sigma", C.c_void_p), ("values", C.c_void_p),
+                ("grad_mu", C.c_void_p), ("grad_sigma", C.c_void_p), ("grad_values", C.c_void_p),
+                ("mu_stride", i32), ("sigma_stride", i32), ("values_stride", i32),
+                ("grad_mu_stride", i32), ("grad_sigma_stride", i32), ("grad_values_stride", i32),
+                ("workspace", C.c_void_p), ("workspace_capacity", i64)]
+
+
+class LgTrainPlan(C.Structure):
+    _fields_ = [("row_tile", i32), ("lds_bytes", i32), ("slices", i32 * POLICY_MAX_LAYERS * TRAIN_CHAINS),
+                ("slice_rows", i32 * POLICY_MAX_LAYERS * TRAIN_CHAINS), ("std_slices", i32), ("std_slice_rows", i32),
+                ("weight_jobs", i32), ("reserved", i32), ("h_off", i64 * POLICY_MAX_LAYERS * TRAIN_CHAINS),
+                ("g_off", i64 * POLICY_MAX_LAYERS * TRAIN_CHAINS), ("p_off", i64 * POLICY_MAX_LAYERS * TRAIN_CHAINS),
+                ("std_p_off", i64), ("workspace_floats", i64)]
 
 
 def check(rc, lib=None):
