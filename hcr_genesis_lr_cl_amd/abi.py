@@ -1,4 +1,4 @@
-"""ctypes mirror of include/lgsim.h, include/lgrollout.h, include/lgsensor.h, include/lgpolicy.h, include/lgppo.h, include/lgoptim.h and include/lgtrain.h (the C ABI) and the loader of the HIP library.
+"""ctypes mirror of include/lgsim.h, include/lgrollout.h, include/lgsensor.h, include/lgpolicy.h, include/lgppo.h, include/lgoptim.h, include/lgtrain.h and include/lgtrainee.h (the C ABI) and the loader of the HIP library.
 
 Field order and types must match the header exactly; tests/test_abi.py compiles a C
 probe that prints sizeof/offsetof for every struct and compares them with these classes.
@@ -302,6 +302,15 @@ def load_lib():
         lib.lg_train_backward.argtypes = [C.POINTER(LgTrainArgs), vp]
         for f in TRAIN_EXPORTS:
             getattr(lib, f).restype = C.c_int
+    if hasattr(lib, "lg_train_ee_forward"):      # absent from libraries older than the explicit-estimator learner passes
+        lib.lg_train_ee_plan.argtypes = [C.POINTER(LgTrainEEArgs), C.POINTER(LgTrainEEPlan)]
+        lib.lg_train_ee_forward.argtypes = [C.POINTER(LgTrainEEArgs), vp]
+        lib.lg_train_ee_backward.argtypes = [C.POINTER(LgTrainEEArgs), vp]
+        lib.lg_train_est_plan.argtypes = [C.POINTER(LgTrainEstArgs), C.POINTER(LgTrainEEPlan)]
+        lib.lg_train_est_forward.argtypes = [C.POINTER(LgTrainEstArgs), vp]
+        lib.lg_train_est_backward.argtypes = [C.POINTER(LgTrainEstArgs), vp]
+        for f in TRAIN_EE_EXPORTS:
+            getattr(lib, f).restype = C.c_int
     lib.lg_last_error.restype = C.c_char_p
     lib.lg_last_kernel.argtypes = [H]
     lib.lg_last_kernel.restype = C.c_char_p
@@ -334,6 +343,10 @@ ADAM_RESULT_FLOATS, ADAM_R_GRAD_NORM, ADAM_R_CLIP_COEF, ADAM_R_LR, ADAM_R_STEP =
 TRAIN_EXPORTS = ["lg_train_plan", "lg_train_forward", "lg_train_backward"]                    # include/lgtrain.h
 TRAIN_CHAINS, TRAIN_ACTOR, TRAIN_CRITIC = 2, 0, 1
 TRAIN_WG_TILE, TRAIN_MIN_SLICE_ROWS, TRAIN_TARGET_JOBS, TRAIN_MAX_SLICES = 64, 64, 512, 32
+TRAIN_EE_EXPORTS = ["lg_train_ee_plan", "lg_train_est_plan", "lg_train_ee_forward", "lg_train_ee_backward", "lg_train_est_forward",
+                    "lg_train_est_backward"]                                                  # include/lgtrainee.h
+TRAIN_EE_CHAINS, TRAIN_EE_ESTIMATOR, TRAIN_EE_ACTOR, TRAIN_EE_CRITIC, TRAIN_EE_THREADS = 3, 0, 1, 2, 256
+TRAIN_EE_TARGET_JOBS = 2048
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 2048
 POLICY_MAX_RNN_LAYERS, POLICY_MAX_RNN_HIDDEN = 2, 512
 POLICY_LSTM, POLICY_GRU = 1, 2
@@ -463,6 +476,30 @@ class LgTrainPlan(C.Structure):
                 ("weight_jobs", i32), ("reserved", i32), ("h_off", i64 * POLICY_MAX_LAYERS * TRAIN_CHAINS),
                 ("g_off", i64 * POLICY_MAX_LAYERS * TRAIN_CHAINS), ("p_off", i64 * POLICY_MAX_LAYERS * TRAIN_CHAINS),
                 ("std_p_off", i64), ("workspace_floats", i64)]
+
+
+class LgTrainEEArgs(C.Structure):
+    _fields_ = [("n_rows", i32), ("clip_on", i32), ("clip_actions", f32), ("reserved", i32), ("chain", LgTrainChain * TRAIN_EE_CHAINS),
+                ("std", C.c_void_p), ("grad_std", C.c_void_p), ("mu", C.c_void_p), ("sigma", C.c_void_p), ("values", C.c_void_p),
+                ("grad_mu", C.c_void_p), ("grad_sigma", C.c_void_p), ("grad_values", C.c_void_p),
+                ("mu_stride", i32), ("sigma_stride", i32), ("values_stride", i32),
+                ("grad_mu_stride", i32), ("grad_sigma_stride", i32), ("grad_values_stride", i32),
+                ("workspace", C.c_void_p), ("workspace_capacity", i64)]
+
+
+class LgTrainEstArgs(C.Structure):
+    _fields_ = [("n_rows", i32), ("labels_stride", i32), ("mask_stride", i32), ("reserved", i32), ("chain", LgTrainChain),
+                ("labels", C.c_void_p), ("mask", C.c_void_p), ("loss", C.c_void_p), ("upstream", C.c_void_p),
+                ("workspace", C.c_void_p), ("workspace_capacity", i64)]
+
+
+class LgTrainEEPlan(C.Structure):
+    _fields_ = [("row_tile", i32), ("lds_bytes", i32), ("slices", i32 * POLICY_MAX_LAYERS * TRAIN_EE_CHAINS),
+                ("slice_rows", i32 * POLICY_MAX_LAYERS * TRAIN_EE_CHAINS), ("std_slices", i32), ("std_slice_rows", i32),
+                ("weight_jobs", i32), ("loss_tiles", i32), ("est_first_buffer", i32), ("reserved", i32),
+                ("h_off", i64 * POLICY_MAX_LAYERS * TRAIN_EE_CHAINS), ("g_off", i64 * POLICY_MAX_LAYERS * TRAIN_EE_CHAINS),
+                ("p_off", i64 * POLICY_MAX_LAYERS * TRAIN_EE_CHAINS), ("std_p_off", i64), ("cat_off", i64), ("gl_off", i64),
+                ("partial_off", i64), ("workspace_floats", i64)]
 
 
 def check(rc, lib=None):

@@ -12,7 +12,10 @@ tensors and returns them for the parameters; autograd sets or accumulates .grad 
 activations, the layer gradients, the slice partials) belongs to `tp`, grows to the largest batch seen and is reused, so a backward
 whose forward has been overwritten by a later forward raises instead of using stale activations.  Weights are read where torch keeps
 them on every call.  The gradient that reaches mu through sigma = mu * 0 + std is taken as exactly zero (include/lgtrain.h); there is no
-gradient for the observations and no double backward.  There is no CPU path: the module lives on a HIP device."""
+gradient for the observations and no double backward.  There is no CPU path: the module lives on a HIP device.
+
+FusedTrainPassEE (below; include/lgtrainee.h, csrc/lg_train_ee.hip) is the same for ActorCriticEE under PPO_EE: the RL pass and the
+supervised estimator pass."""
 from __future__ import annotations
 
 import ctypes as C
@@ -278,3 +281,280 @@ class FusedTrainPass:
     def __call__(self, obs, critic_obs):
         """(mu, sigma, values) of the mini-batch: (B, A), (B, A), (B, 1).  One launch on the current stream."""
         return _Pass.apply(self, obs, critic_obs, *self.spec.parameters())
+
+
+# ---- the explicit-estimator family (include/lgtrainee.h, csrc/lg_train_ee.hip) ----------------------------------------------------------------
+class TrainSpecEE:
+    """ActorCriticEE as the kernels take it: the estimator, the actor (whose input is [features | estimator output]) and the critic."""
+
+    def __init__(self, estimator, actor, critic, std):
+        self.estimator, self.actor, self.critic, self.std = estimator, actor, critic, std
+        self.chains = (estimator, actor, critic)
+        self.num_actions, self.clip_actions = actor.widths[-1], actor.clip
+        self.num_features, self.num_labels = estimator.widths[0], estimator.widths[-1]
+
+    def rl_parameters(self):
+        """Actor, critic, then std: the order of PPO_EE.rl_parameters and of the RL pass's gradients."""
+        return [p for c in (self.actor, self.critic) for l in c.linears for p in (l.weight, l.bias)] + [self.std]
+
+    def rl_parameter_names(self):
+        return [f"{c.name}.{i}.{n}" for c in (self.actor, self.critic) for i in range(len(c.linears)) for n in ("weight", "bias")] + ["std"]
+
+    def estimator_parameters(self):
+        return [p for l in self.estimator.linears for p in (l.weight, l.bias)]
+
+    def estimator_parameter_names(self):
+        return [f"estimator.{i}.{n}" for i in range(len(self.estimator.linears)) for n in ("weight", "bias")]
+
+
+def describe_ee(actor_critic, device=None):
+    """ActorCriticEE as the kernels take it (duck-typed: .estimator, .actor, .critic, .std), by the rules of `describe` for each chain.
+    Refusals are ValueErrors that name the layer or the member."""
+    if getattr(actor_critic, "estimator", None) is None:
+        raise ValueError("FusedTrainPassEE: the module has no .estimator; the plain ActorCritic is FusedTrainPass's")
+    for attr, family in _OTHER_FAMILIES:
+        if attr != "estimator" and getattr(actor_critic, attr, None) is not None:
+            raise ValueError(f"FusedTrainPassEE: the module has .{attr} ({family}) beside .estimator; only ActorCriticEE is built")
+    if getattr(actor_critic, "is_recurrent", False):
+        raise ValueError("FusedTrainPassEE: the module is recurrent (is_recurrent); the recurrent update keeps the torch path")
+    for need in ("actor", "critic", "std"):
+        if getattr(actor_critic, need, None) is None:
+            raise ValueError(f"FusedTrainPassEE: the module has no .{need}")
+    estimator = _describe_chain("estimator", actor_critic.estimator, device, False)
+    actor = _describe_chain("actor", actor_critic.actor, device, True)
+    critic = _describe_chain("critic", actor_critic.critic, device, False)
+    if actor.widths[0] != estimator.widths[0] + estimator.widths[-1]:
+        raise ValueError(f"FusedTrainPassEE: actor[0] takes {actor.widths[0]} inputs, but [features | estimator output] has "
+                         f"{estimator.widths[0]} + {estimator.widths[-1]} columns")
+    std = actor_critic.std
+    _check_param(std, "std", device)
+    if tuple(std.shape) != (actor.widths[-1],):
+        raise ValueError(f"FusedTrainPassEE: std has shape {tuple(std.shape)}, the actor has {actor.widths[-1]} outputs")
+    return TrainSpecEE(estimator, actor, critic, std)
+
+
+def _fill_chain(ch, c, device, grads=None):
+    """Widths, flags and weight pointers of one LgTrainChain; `grads`: [weight, bias, weight, bias, ...] tensors of its layers."""
+    ch.n_layers = len(c.linears)
+    for li, (lin, elu) in enumerate(zip(c.linears, c.elu)):
+        L = ch.layer[li]
+        _check_param(lin.weight, f"{c.name} layer {li} weight", device)
+        _check_param(lin.bias, f"{c.name} layer {li} bias", device)
+        L.weight, L.bias, L.n_in, L.n_out, L.elu = lin.weight.data_ptr(), lin.bias.data_ptr(), lin.in_features, lin.out_features, int(elu)
+        if grads is not None:
+            L.grad_weight, L.grad_bias = grads[2 * li].data_ptr(), grads[2 * li + 1].data_ptr()
+
+
+def _bind_workspace(a, workspace, device):
+    if workspace is not None:
+        if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float32 or not workspace.is_contiguous() \
+                or (device is not None and workspace.device != device):
+            raise ValueError("FusedTrainPassEE: the workspace must be a contiguous float32 tensor" + (f" on {device}" if device is not None else ""))
+        a.workspace, a.workspace_capacity = workspace.data_ptr(), workspace.numel()
+
+
+def ee_args(spec, features, critic_obs, mu, sigma, values, workspace, grads=None, grad_mu=None, grad_sigma=None, grad_values=None, device=None):
+    """LgTrainEEArgs of one call of the RL pass.  `grads` (backward): the tensors that take the gradients, in spec.rl_parameters() order."""
+    a = abi.LgTrainEEArgs()
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1:
+        raise ValueError(f"FusedTrainPassEE: estimator_features must be a (B, {spec.num_features}) float32 tensor with B >= 1")
+    n = int(features.shape[0])
+    a.n_rows = n
+    a.clip_on, a.clip_actions = (1, spec.clip_actions) if spec.clip_actions is not None else (0, 0.0)
+    na = 2 * len(spec.actor.linears)
+    est, act, cri = a.chain[abi.TRAIN_EE_ESTIMATOR], a.chain[abi.TRAIN_EE_ACTOR], a.chain[abi.TRAIN_EE_CRITIC]
+    est.input, est.in_stride = _rows(features, spec.num_features, "estimator_features", n, device)
+    cri.input, cri.in_stride = _rows(critic_obs, spec.critic.widths[0], "critic_obs", n, device)
+    _fill_chain(est, spec.estimator, device)
+    _fill_chain(act, spec.actor, device, None if grads is None else grads[:na])
+    _fill_chain(cri, spec.critic, device, None if grads is None else grads[na:-1])
+    A, V = spec.num_actions, spec.critic.widths[-1]
+    _check_param(spec.std, "std", device)
+    a.std = spec.std.data_ptr()
+    a.mu, a.mu_stride = _rows(mu, A, "mu", n, device)
+    a.sigma, a.sigma_stride = _rows(sigma, A, "sigma", n, device)
+    a.values, a.values_stride = _rows(values, V, "values", n, device)
+    if grads is not None:
+        a.grad_std = grads[-1].data_ptr()
+        a.grad_mu, a.grad_mu_stride = _rows(grad_mu, A, "grad_mu", n, device)
+        a.grad_sigma, a.grad_sigma_stride = _rows(grad_sigma, A, "grad_sigma", n, device)
+        a.grad_values, a.grad_values_stride = _rows(grad_values, V, "grad_values", n, device)
+    _bind_workspace(a, workspace, device)
+    return a
+
+
+def _scalar(t, what, device):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != 1 or (device is not None and t.device != device):
+        raise ValueError(f"FusedTrainPassEE: {what} must be one float32" + (f" on {device}" if device is not None else ""))
+    return t.data_ptr()
+
+
+def est_args(spec, features, labels, terminated, loss, workspace, grads=None, upstream=None, device=None):
+    """LgTrainEstArgs of one call of the estimator pass.  `grads` (backward): in spec.estimator_parameters() order."""
+    a = abi.LgTrainEstArgs()
+    if not isinstance(features, torch.Tensor) or features.dim() != 2 or features.shape[0] < 1:
+        raise ValueError(f"FusedTrainPassEE: estimator_features must be a (B, {spec.num_features}) float32 tensor with B >= 1")
+    n = int(features.shape[0])
+    a.n_rows = n
+    a.chain.input, a.chain.in_stride = _rows(features, spec.num_features, "estimator_features", n, device)
+    _fill_chain(a.chain, spec.estimator, device, grads)
+    a.labels, a.labels_stride = _rows(labels, spec.num_labels, "estimator_labels", n, device)
+    a.mask, a.mask_stride = _rows(terminated, 1, "terminated", n, device)
+    if loss is not None:
+        a.loss = _scalar(loss, "the loss", device)
+    if upstream is not None:
+        a.upstream = _scalar(upstream, "the upstream gradient", device)
+    _bind_workspace(a, workspace, device)
+    return a
+
+
+def _widths_into(ch, w):
+    ch.n_layers = len(w) - 1
+    for li in range(min(len(w) - 1, abi.POLICY_MAX_LAYERS)):
+        ch.layer[li].n_in, ch.layer[li].n_out = w[li], w[li + 1]
+
+
+_PLANS_EE = {}
+
+
+def plan_ee(n_rows, estimator_widths, actor_widths, critic_widths):
+    """LgTrainEEPlan of the RL pass (lg_train_ee_plan) for chains of these widths."""
+    key = (int(n_rows),) + tuple(tuple(int(x) for x in w) for w in (estimator_widths, actor_widths, critic_widths))
+    if key not in _PLANS_EE:
+        lib, a, p = abi.load_lib(), abi.LgTrainEEArgs(), abi.LgTrainEEPlan()
+        a.n_rows = key[0]
+        for ci, w in enumerate(key[1:]):
+            _widths_into(a.chain[ci], w)
+        abi.check(lib.lg_train_ee_plan(C.byref(a), C.byref(p)), lib)
+        _PLANS_EE[key] = p
+    return _PLANS_EE[key]
+
+
+def plan_est(n_rows, estimator_widths):
+    """LgTrainEEPlan of the estimator pass (lg_train_est_plan)."""
+    key = (int(n_rows), tuple(int(x) for x in estimator_widths))
+    if key not in _PLANS_EE:
+        lib, a, p = abi.load_lib(), abi.LgTrainEstArgs(), abi.LgTrainEEPlan()
+        a.n_rows = key[0]
+        _widths_into(a.chain, key[1])
+        abi.check(lib.lg_train_est_plan(C.byref(a), C.byref(p)), lib)
+        _PLANS_EE[key] = p
+    return _PLANS_EE[key]
+
+
+def _call(name, args, device):
+    lib = abi.load_lib()
+    abi.check(getattr(lib, name)(C.byref(args), torch.cuda.current_stream(device).cuda_stream), lib)
+
+
+class _PassEE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tp, features, critic_obs, *params):
+        spec, device, n = tp.spec, tp.device, int(features.shape[0])
+        mu = torch.empty((n, spec.num_actions), dtype=torch.float32, device=device)
+        sigma = torch.empty_like(mu)
+        values = torch.empty((n, spec.critic.widths[-1]), dtype=torch.float32, device=device)
+        args = ee_args(spec, features, critic_obs, mu, sigma, values, None, device=device)      # every refusal before anything grows
+        _bind_workspace(args, tp._rl_workspace_for(n), device)
+        _call("lg_train_ee_forward", args, device)
+        tp._rl_calls += 1
+        ctx.tp, ctx.call, ctx.features, ctx.critic_obs = tp, tp._rl_calls, features, critic_obs
+        ctx.save_for_backward(mu, sigma, values)
+        return mu, sigma, values
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_mu, grad_sigma, grad_values):
+        tp = ctx.tp
+        if tp._rl_calls != ctx.call:
+            raise RuntimeError(f"FusedTrainPassEE: backward of RL forward call {ctx.call}, but RL forward call {tp._rl_calls} has overwritten "
+                               f"its activations in the workspace since; run each backward before the next forward of the same pass")
+        mu, sigma, values = ctx.saved_tensors
+        spec, device = tp.spec, tp.device
+        grads = [torch.empty_like(p) for p in spec.rl_parameters()]
+        gm, gs, gv = _grad_rows(grad_mu, mu), _grad_rows(grad_sigma, sigma), _grad_rows(grad_values, values)
+        args = ee_args(spec, ctx.features, ctx.critic_obs, mu, sigma, values, tp._rl_workspace, grads, gm, gs, gv, device=device)
+        _call("lg_train_ee_backward", args, device)
+        return (None, None, None) + tuple(grads)          # nothing for the estimator's parameters: they are no input of this pass
+
+
+class _EstLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tp, features, labels, terminated, *params):
+        spec, device, n = tp.spec, tp.device, int(features.shape[0])
+        loss = torch.empty((), dtype=torch.float32, device=device)
+        args = est_args(spec, features, labels, terminated, loss, None, device=device)
+        _bind_workspace(args, tp._est_workspace_for(n), device)
+        _call("lg_train_est_forward", args, device)
+        tp._est_calls += 1
+        ctx.tp, ctx.call, ctx.inputs = tp, tp._est_calls, (features, labels, terminated)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        tp = ctx.tp
+        if tp._est_calls != ctx.call:
+            raise RuntimeError(f"FusedTrainPassEE: backward of estimator forward call {ctx.call}, but estimator forward call {tp._est_calls} has "
+                               f"overwritten its activations in the workspace since; run each backward before the next forward of the same pass")
+        spec, device = tp.spec, tp.device
+        up = grad_loss.to(torch.float32).reshape(1).contiguous()        # stays on the device: the kernel reads it there
+        grads = [torch.empty_like(p) for p in spec.estimator_parameters()]
+        args = est_args(spec, *ctx.inputs, None, tp._est_workspace, grads, up, device=device)
+        _call("lg_train_est_backward", args, device)
+        return (None, None, None, None) + tuple(grads)
+
+
+class FusedTrainPassEE:
+    """The two network passes of PPO_EE.update() on an ActorCriticEE (include/lgtrainee.h):
+
+        tp = FusedTrainPassEE(actor_critic_ee)
+        mu, sigma, values = tp(estimator_features, critic_obs)                        # RL step: one launch; backward three
+        est_loss = tp.estimator_loss(estimator_features, estimator_labels, terminated)       # estimator step: two launches; backward three
+
+    Optimise tp.rl_parameters() (actor, critic, std: the reference's order) and tp.estimator_parameters() apart.  The RL pass gives the
+    estimator's parameters no gradient (their .grad is left as it was): the reference discards that gradient unread, and there is no
+    end-to-end estimator gradient from the RL loss.  Each pass has its own workspace and call counter: a forward of one does not
+    invalidate a pending backward of the other; within a pass a backward whose forward has been overwritten raises."""
+
+    def __init__(self, actor_critic):
+        dev = getattr(getattr(actor_critic, "std", None), "device", None)
+        if isinstance(dev, torch.device) and dev.type != "cuda":
+            raise ValueError(f"FusedTrainPassEE: the module is on {dev}, not on a HIP device (there is no CPU path)")
+        self.spec = describe_ee(actor_critic, dev)
+        self.device = dev
+        self._rl_workspace = self._est_workspace = None
+        self._rl_calls = self._est_calls = 0
+
+    def rl_parameters(self):
+        return self.spec.rl_parameters()
+
+    def estimator_parameters(self):
+        return self.spec.estimator_parameters()
+
+    def plan(self, n_rows):
+        s = self.spec
+        return plan_ee(n_rows, s.estimator.widths, s.actor.widths, s.critic.widths)
+
+    def estimator_plan(self, n_rows):
+        return plan_est(n_rows, self.spec.estimator.widths)
+
+    def _rl_workspace_for(self, n):
+        need = int(self.plan(n).workspace_floats)
+        if self._rl_workspace is None or self._rl_workspace.numel() < need:
+            self._rl_workspace = torch.empty(need, dtype=torch.float32, device=self.device)
+        return self._rl_workspace
+
+    def _est_workspace_for(self, n):
+        need = int(self.estimator_plan(n).workspace_floats)
+        if self._est_workspace is None or self._est_workspace.numel() < need:
+            self._est_workspace = torch.empty(need, dtype=torch.float32, device=self.device)
+        return self._est_workspace
+
+    def __call__(self, estimator_features, critic_obs):
+        """(mu, sigma, values) of the mini-batch: (B, A), (B, A), (B, 1).  One launch on the current stream."""
+        return _PassEE.apply(self, estimator_features, critic_obs, *self.spec.rl_parameters())
+
+    def estimator_loss(self, estimator_features, estimator_labels, terminated):
+        """mse_loss(estimator(features) * terminated, labels * terminated) as a 0-dim tensor with autograd.  Two launches."""
+        return _EstLoss.apply(self, estimator_features, estimator_labels, terminated, *self.spec.estimator_parameters())
