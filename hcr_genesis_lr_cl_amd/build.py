@@ -31,7 +31,7 @@ if PASS_MODE not in ("default", "strict"):
     raise ValueError(f"LG_DPP_PASS_MODE={PASS_MODE!r}: expected 'default' or 'strict'")
 N_GROUPS = 22
 QUAD_GROUPS = list(range(0, 9)) + list(range(17, 22))   # lg_inst.hip: groups that include lg_quad.h
-COMMON = ["lg_shared.h", "lg_math.h", os.path.join(INC, "lgsim.h")]
+COMMON = ["lg_shared.h", "lg_math.h", "lg_lane_ints.h", os.path.join(INC, "lgsim.h")]
 # -fno-slp-vectorize: packing scalars into v_pk_* costs more v_mov / AGPR shuffles than it saves here.
 # iterative-ilp scheduling: the kernels run one wave per SIMD, so occupancy is irrelevant and the scheduler should fill DPP /
 # VALU->SGPR hazard slots with independent work (measured -3 % on the physics launch, neutral elsewhere).

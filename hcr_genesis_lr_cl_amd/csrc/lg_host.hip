@@ -242,6 +242,7 @@ static bool flat_profile(const LgEngine *h, bool inj) {
            h->model.n_bodies == 1 + 3 * h->model.n_legs &&
            o.n_height_points == 0 && o.terrain_rows == 0 && o.feet_terrain_info == 0 && !b.link_contact_states && !b.task_state && !h->hf &&
            uniforms_ok(h, inj) && !b.joint_armature && !t.dr_joint_on && !t.dr_pd_on && t.reset_lin_vel_span == 0.f && t.reset_ang_vel_span == 0.f && flat_noise_ok(h) &&
+           (double)b.n_envs * (9 + 9 * h->model.n_legs) * 4.0 < 4.0e9 &&      // 32-bit byte offsets into one set of the observation rows (lg_quad.h)
            rewards_ok(h, LG_PROF_GO2_FLAT);
 }
 // wtw_profile: go2_wtw on the plane (GO2_WTW): sliding-window stacks of 61 | 99-wide frames, Philox draws, no per-env joint parameters,
@@ -365,10 +366,12 @@ template <int LEGS, int JPL> static LgPlan plan(const LgEngine *h, uint32_t ph, 
     const auto mdp = [&](uint32_t m) {   // POST | RESET or POST leg per lane, behind a physics launch or on its own
         if (m == PR) add(repl ? K::post_reset_repl : K::post_reset, repl ? rgrid : grid); else add(K::post, grid); };
     // rs(P): the task's reward set is profile P's default one and the solver options are the configs' defaults -> the instantiation with
-    // them as constants (lg_quad.h RS; LG_REWARD_SET_CONST=0: off)
+    // them as constants (lg_quad.h RS; LG_REWARD_SET_CONST=0: off).  The same instantiation takes the configs' branch switches, the bound /
+    // unbound optional buffers as given (lg_shared.h lg_rs_constants_hold): anything else runs the general form
     const auto rs = [&](int prof) {
         return (unsigned)h->hot.reward_mask == lg_default_reward_mask(prof) && h->hot.o_contact_iters == LG_DEFAULT_CONTACT_ITERS &&
-               h->hot.o_contact_w_every == LG_DEFAULT_CONTACT_W_EVERY && sw[SW_REWARD_SET_CONST] != 0; };
+               h->hot.o_contact_w_every == LG_DEFAULT_CONTACT_W_EVERY && lg_rs_constants_hold(prof, h->task, h->bufs) &&
+               sw[SW_REWARD_SET_CONST] != 0; };
     // physics layout (lg_quad.h): one vector component per lane while the batch cannot fill the SIMDs with one leg per
     // lane; the MDP phases then follow in a second launch on the same stream
     // auto: component-per-lane while that needs at most two waves per SIMD (1024 SIMDs).  Measured go2, us per step,
@@ -432,6 +435,7 @@ static int execute(LgEngine *h, const LgPlan &pl, uint32_t ph, const float *acti
     const LgHot &hot = h->hot;   // refreshed by upload_hot
     p.k.m_n_links = hot.m_n_links;
     for (int i = 0; i < 4; i++) { p.k.m_foot_link[i] = hot.m_foot_link[i]; p.k.joint_axis[i] = h->joint_axis[i]; }
+    p.k.foot_pack = lg_foot_pack(hot.m_foot_link, h->model.n_legs);
     p.k.obs_layout = hot.obs_layout; p.k.o_n_height_points = hot.o_n_height_points; p.k.cat_enable = h->task.cat_enable;
     p.k.reward_mask = (unsigned)hot.reward_mask; p.k.clip_actions = hot.clip_actions;
     p.obs_win = 0; p.obs_set = h->obs_set;

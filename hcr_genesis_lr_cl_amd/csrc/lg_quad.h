@@ -304,6 +304,14 @@ template <int AK> LG_DEV void joint_rot(const Lane &L, const QM &Rp, float ax, f
 // store / load at base + a 32-bit BYTE offset (base wave-uniform: the saddr form of global_store / global_load)
 template <class T> LG_DEV void stq(T *base, unsigned off, T v) { *reinterpret_cast<T *>(reinterpret_cast<char *>(base) + off) = v; }
 template <class T> LG_DEV T ldq(const T *base, unsigned off) { return *reinterpret_cast<const T *>(reinterpret_cast<const char *>(base) + off); }
+// A byte offset formed earlier in the kernel, re-issued in the basic block that stores through it.  The saddr form is selected only where
+// the zero extension of the offset sits in the block of the access; for an offset computed once in the prologue it does not, and every
+// store through it would pay a 64-bit add in vector registers instead.  One call per predicate block and offset (at most one v_mov).
+LG_DEV unsigned blk(unsigned off) { asm("" : "+v"(off)); return off; }
+// the same for the global-address-space pointers of the start-of-kernel burst: wave-uniform base + 32-bit byte offset = a load in saddr form
+template <class T> LG_DEV T ldg(const T __attribute__((address_space(1))) *base, unsigned off) {
+    return *reinterpret_cast<const T __attribute__((address_space(1))) *>(reinterpret_cast<const char __attribute__((address_space(1))) *>(base) + off);
+}
 
 struct QJoint { QV6 S, U, c; float dinv, u; };
 struct QKin { QM R; float P; QV6 V; QR Wr; };   // Wr: the rotations of V.a (cross products)
@@ -485,6 +493,9 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
         for (int k = 0; k < LG_LT_STG; k++) { const u4v a = src[tl_ + k * BLOCK]; ltg[k] = make_uint4(a.x, a.y, a.z, a.w); }
     }
     const LgBuffers &B = p.B;
+    // the staging loads above go out before the lane constants and the pointers of the burst are formed (left to itself the scheduler puts
+    // the ~80 v_readlane of the pointers first: the tables then arrive after the wave needs them)
+    __builtin_amdgcn_sched_barrier(0);
     unsigned long long _stamp0 = 0; (void)_stamp0;
     STAMP(0);
     STAMPB(4096);
@@ -498,26 +509,26 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
     const int wg = lg_wg();   // XCD-aware (lg_kernel.h)
     const int role = DUO ? (int)(threadIdx.x >> 6) : 0;
     const int tid = wg * BLOCK + tl_;
-    Lane L;
-    L.c = tid & 3; L.is0 = L.c == 0; L.is1 = L.c == 1; L.is2 = L.c == 2; L.is3 = L.c == 3;
-    L.d0 = L.is0 ? 1.f : 0.f; L.d1 = L.is1 ? 1.f : 0.f; L.d2 = L.is2 ? 1.f : 0.f;
-    const int cj = min(L.c, 2);               // vector component of this lane; lane 3 shadows lane 2's addresses and never stores one
-    const int cjj = JPL == 4 ? L.c : cj;      // joint of this lane (four-joint legs: lane 3 carries the fourth)
-    const int quad = tid >> 2, leg = quad % LEGS;
-    int e = quad / LEGS;
+    // the lane's integer constants -- env, leg, component, foot link / slot, the byte offset of its element in each index pattern -- from
+    // lg_lane_ints.h (shared with the host and with tests/test_lane_constants.py).  The per-leg foot constants arrive packed in one kernel
+    // argument (KParams.k.foot_pack, built by the host): a shift and two masks per lane instead of a select tree over the four foot links
+    // and four compares for the slot.
     const int N = KINT(B.n_envs);
-    const bool alive = e < N;                 // this lane's env exists
+    const LgLaneInts LI = lg_lane_ints(tid, N, LEGS, JPL, (unsigned)KINT(k.foot_pack));
+    Lane L;
+    L.c = LI.c; L.is0 = L.c == 0; L.is1 = L.c == 1; L.is2 = L.c == 2; L.is3 = L.c == 3;
+    L.d0 = L.is0 ? 1.f : 0.f; L.d1 = L.is1 ? 1.f : 0.f; L.d2 = L.is2 ? 1.f : 0.f;
+    const int cj = LI.cj;                     // vector component of this lane; lane 3 shadows lane 2's addresses and never stores one
+    const int cjj = LI.cjj;                   // joint of this lane (four-joint legs: lane 3 carries the fourth)
+    const int leg = LI.leg, e = LI.e;         // dead lanes (past the last env) shadow the last env
+    const bool alive = LI.alive != 0;         // this lane's env exists
     const bool live = alive && role == 0;     // ... and this wave owns its physics / state stores
-    if (!alive) e = N - 1;
     const bool st = live && !L.is3;           // this lane stores vector components
     const bool stj = JPL == 4 ? live : st;    // ... joint values
     const bool lead = st && leg == 0;         // ... and the per-env ones
     const int nL = KINT(k.m_n_links), F = LEGS;
     const int b0 = 1 + JPL * leg, d0 = JPL * leg;
-    const int foot_link = leg == 0 ? KINT(k.m_foot_link[0]) : (leg == 1 ? KINT(k.m_foot_link[1]) : (leg == 2 ? KINT(k.m_foot_link[2]) : KINT(k.m_foot_link[3])));
-    int foot_slot = 0;
-#pragma unroll
-    for (int k = 0; k < LEGS; k++) foot_slot += (KINT(k.m_foot_link[k]) < foot_link) ? 1 : 0;
+    const int foot_link = LI.foot_link, foot_slot = LI.foot_slot;
 
     // ---------------- start-of-kernel loads (one burst, one wait) --------------------------------
     // pointers of the burst, rebuilt from the lane table
@@ -552,29 +563,38 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
     const float GAS *const k_actions_in = KPTR(const float GAS *, offsetof(KParams, actions));
     const LgSimOptions GAS *kO = KPTR(const LgSimOptions GAS *, offsetof(KParams, O));
     const LgTaskCfg GAS *kT = KPTR(const LgTaskCfg GAS *, offsetof(KParams, T));
-    const int ja = e * A + d0 + cjj;          // this lane's joint
+    const int ja = LI.ja;                     // this lane's joint
+    // One 32-bit byte offset per index pattern, shared by the loads of this burst and by every later store to the same arrays (prologue
+    // stores, read-back, reset, MDP state): the wave-uniform base stays in scalar registers and the access takes the saddr form, instead of
+    // a 64-bit address built in vector registers per array (sign extension, 64-bit shift and add).  Every array stays below 4 GiB (checked
+    // where the launch is chosen, lg_host.hip).
+    unsigned o_ja = LI.o_ja, o_e = LI.o_e, o_e3 = LI.o_e3, o_q4 = LI.o_q4, o_fs = LI.o_fs, o_ft = LI.o_ft;   // (tron1_pf_ee: formed again behind the sub-steps)
+    const unsigned o_dj = LI.o_dj;
+    // MB (host-checked: lg_step refuses PRE / POST / RESET without them, lg_host.hip check_mdp_bufs; env_origins: lg_bind): the per-env
+    // randomisation buffers are bound.  RS (host-checked, lg_shared.h lg_rs_constants_hold): the per-env joint parameter arrays are not.
+    constexpr bool MB = MPH != 0 || DO_PRE;
     float act, last_act = 0.f, llast_act = 0.f;
     if (DO_PRE) {
         const float ca = KFLT(k.clip_actions);
-        last_act = k_actions[ja]; llast_act = k_last_actions[ja];
-        act = clampf(k_actions_in[ja], -ca, ca);
+        last_act = ldg(k_actions, o_ja); llast_act = ldg(k_last_actions, o_ja);
+        act = clampf(ldg(k_actions_in, o_ja), -ca, ca);
     } else {
-        act = k_actions_in ? k_actions_in[ja] : k_actions[ja];
+        act = k_actions_in ? ldg(k_actions_in, o_ja) : ldg(k_actions, o_ja);
     }
-    float pos = k_base_pos[3 * e + cj], vw = k_base_lin_vel_w[3 * e + cj], ww = k_base_ang_vel_w[3 * e + cj];
-    float quat = k_base_quat[4 * e + L.c];
-    float q = k_dof_pos[ja], qd = k_dof_vel[ja];
-    const float snap_fv = k_feet_vel[(e * F + foot_slot) * 3 + cj];
-    const float snap_blv = k_base_lin_vel[3 * e + cj], snap_bav = k_base_ang_vel[3 * e + cj];
-    const float dr_mass = k_added_base_mass ? k_added_base_mass[e] : 0.f;
-    const float dr_com = k_base_com_bias ? k_base_com_bias[3 * e + cj] : 0.f;
-    const float dr_fric = k_friction_values ? k_friction_values[e] : 1.f;
-    const float dr_kp = k_kp_scale ? k_kp_scale[ja] : 1.f, dr_kd = k_kd_scale ? k_kd_scale[ja] : 1.f;
+    float pos = ldg(k_base_pos, o_e3), vw = ldg(k_base_lin_vel_w, o_e3), ww = ldg(k_base_ang_vel_w, o_e3);
+    float quat = ldg(k_base_quat, o_q4);
+    float q = ldg(k_dof_pos, o_ja), qd = ldg(k_dof_vel, o_ja);
+    const float snap_fv = ldg(k_feet_vel, o_ft);
+    const float snap_blv = ldg(k_base_lin_vel, o_e3), snap_bav = ldg(k_base_ang_vel, o_e3);
+    const float dr_mass = (MB || k_added_base_mass) ? ldg(k_added_base_mass, o_e) : 0.f;
+    const float dr_com = (MB || k_base_com_bias) ? ldg(k_base_com_bias, o_e3) : 0.f;
+    const float dr_fric = (MB || k_friction_values) ? ldg(k_friction_values, o_e) : 1.f;
+    const float dr_kp = (MB || k_kp_scale) ? ldg(k_kp_scale, o_ja) : 1.f, dr_kd = (MB || k_kd_scale) ? ldg(k_kd_scale, o_ja) : 1.f;
     float gain_p = 0.f, gain_d = 0.f, q0 = 0.f;      // three-joint legs: from the lane table, below
     if constexpr (!USE_LT) { gain_p = kO->kp[d0 + cjj]; gain_d = kO->kd[d0 + cjj]; q0 = kO->default_dof_pos[d0 + cjj]; }
     float dr_arm = 0.f, dr_jf = 0.f, dr_jd = 0.f;
-    if (k_joint_armature) { dr_arm = k_joint_armature[e]; dr_jf = k_joint_friction[e]; dr_jd = k_joint_damping[e]; }
-    const float origin = k_env_origins ? k_env_origins[3 * e + cj] : 0.f;
+    if (!RS && k_joint_armature) { dr_arm = ldg(k_joint_armature, o_e); dr_jf = ldg(k_joint_friction, o_e); dr_jd = ldg(k_joint_damping, o_e); }
+    const float origin = (MB || k_env_origins) ? ldg(k_env_origins, o_e3) : 0.f;
     int crv = 0;
     if (MPH != 0) crv = reinterpret_cast<const int GAS *>(k_command_ranges)[min((int)tl_, LG_CMD_RANGE_FLOATS - 1)];
     int prw = 0;   // observation programs for the MDP tail (lg_kernel.h PRG_I / PRG_F)
@@ -591,53 +611,56 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
     // QTAIL working set, one value per lane: command component c, the two episode sums this lane owns (terms ei and ei + 16 of its
     // env, ei = 4 leg + c), this lane's joint constants; per-env / per-leg scalars replicated
     static_assert(LG_R_COUNT <= 32, "two episode sums per lane");
-    const int ei = (leg << 2) | L.c;
+    const int ei = LI.ei;
     float m_cmd = 0.f, m_air = 0.f, m_es0 = 0.f, m_es1 = 0.f, m_slo = 0.f, m_shi = 0.f, m_rlo = 0.f, m_rsp = 0.f, m_nq = 0.f, m_nqd = 0.f;
     int m_ep = 0, m_fail = 0, m_lc = 0;
     // biped tail: four episode sums per lane (terms el + 8 k of its env, el = 4 leg + c), the action / clock noise scales of tron1_pf_ee's
     // frame, the sit pose and the gait offsets a reset needs
     float b_es[4] = {0.f, 0.f, 0.f, 0.f}, b_nact = 0.f, b_nclk0 = 0.f, b_nclk1 = 0.f, b_sitq = 0.f, b_sitp = 0.f, b_sitr = 0.f, b_th0 = 0.f, b_th1 = 0.f;
+    unsigned o_es = LI.o_es;   // this lane's element of row `ei` of a (term, N) array; row ei + k: + 4 k N
     if (BQ) {
         static_assert(LG_R_COUNT <= 32, "four episode sums per lane");
 #pragma unroll
-        for (int k = 0; k < 4; k++) if (ei + 8 * k < LG_R_COUNT) b_es[k] = k_episode_sums[(size_t)(ei + 8 * k) * N + e];
-        b_nact = kT->noise_vec[9 + 2 * A + d0 + cj];
-        b_nclk0 = kT->noise_vec[9 + 3 * A + foot_slot]; b_nclk1 = kT->noise_vec[9 + 3 * A + LEGS + foot_slot];
-        b_sitq = kT->sit_dof_pos[d0 + cj]; b_sitp = kT->sit_pos[cj]; b_sitr = kT->sit_quat[L.c];
+        for (int k = 0; k < 4; k++) if (ei + 8 * k < LG_R_COUNT) b_es[k] = ldg(k_episode_sums, o_es + 32u * (unsigned)k * (unsigned)N);
+        b_nact = ldg(&kT->noise_vec[9 + 2 * A], o_dj);
+        b_nclk0 = ldg(&kT->noise_vec[9 + 3 * A], 4u * (unsigned)foot_slot); b_nclk1 = ldg(&kT->noise_vec[9 + 3 * A + LEGS], 4u * (unsigned)foot_slot);
+        b_sitq = ldg(&kT->sit_dof_pos[0], o_dj); b_sitp = ldg(&kT->sit_pos[0], 4u * (unsigned)cj); b_sitr = ldg(&kT->sit_quat[0], 4u * (unsigned)L.c);
         b_th0 = kT->theta_table[0][0]; b_th1 = kT->theta_table[0][1];
     }
     if (CTAIL) {
-        m_cmd = k_commands[4 * e + L.c];
-        m_ep = k_episode_length_buf[e];
-        m_fail = (int)k_fail_buf[e];
-        m_air = k_feet_air_time[e * F + foot_slot];
-        m_lc = (int)k_last_contacts[e * F + foot_slot];
-        if (QTAIL) m_es0 = k_episode_sums[(size_t)ei * N + e];
-        if (QTAIL && ei + 16 < LG_R_COUNT) m_es1 = k_episode_sums[(size_t)(ei + 16) * N + e];
-        m_slo = kT->soft_dof_lo[d0 + cj]; m_shi = kT->soft_dof_hi[d0 + cj];
-        m_rlo = kT->reset_dof_lo[d0 + cj]; m_rsp = kT->reset_dof_span[d0 + cj];
-        m_nq = kT->noise_vec[9 + d0 + cj]; m_nqd = kT->noise_vec[9 + A + d0 + cj];
+        m_cmd = ldg(k_commands, o_q4);
+        m_ep = ldg(k_episode_length_buf, o_e);
+        m_fail = (int)ldg(k_fail_buf, 2u * o_e);
+        m_air = ldg(k_feet_air_time, o_fs);
+        m_lc = (int)ldg(k_last_contacts, o_fs >> 2);
+        if (QTAIL) m_es0 = ldg(k_episode_sums, o_es);
+        if (QTAIL && ei + 16 < LG_R_COUNT) m_es1 = ldg(k_episode_sums, o_es + 64u * (unsigned)N);
+        m_slo = ldg(&kT->soft_dof_lo[0], o_dj); m_shi = ldg(&kT->soft_dof_hi[0], o_dj);
+        m_rlo = ldg(&kT->reset_dof_lo[0], o_dj); m_rsp = ldg(&kT->reset_dof_span[0], o_dj);
+        m_nq = ldg(&kT->noise_vec[9], o_dj); m_nqd = ldg(&kT->noise_vec[9 + A], o_dj);
     }
     // go2_wtw: gait clock and behaviour targets (per-env scalars replicated, per-foot entries by leg), the latest push, the deferred-
     // blanking flag of the observation stacks
     float w_gt = 0.f, w_phi = 0.f, w_gp = 1.f, w_bh = 0.f, w_fc = 0.f, w_pt = 0.f, w_th = 0.f, w_ec = 0.f, w_push = 0.f;
     int w_dirty = 0, w_lvl = 0, w_type = 0;
     if (WQ) {
-        const float GAS *ts = KB(const float GAS *, task_state) + (size_t)e * LG_TASK_STATE_WTW;
-        w_gt = ts[0]; w_phi = ts[1]; w_gp = ts[2]; w_bh = ts[3]; w_fc = ts[4]; w_pt = ts[5];
-        w_th = ts[6 + foot_slot]; w_ec = ts[18 + foot_slot];
+        const float GAS *ts = KB(const float GAS *, task_state);
+        const unsigned o_ts = (unsigned)LG_TASK_STATE_WTW * o_e, o_tf = o_ts + 4u * (unsigned)foot_slot;
+        w_gt = ldg(ts, o_ts); w_phi = ldg(ts + 1, o_ts); w_gp = ldg(ts + 2, o_ts); w_bh = ldg(ts + 3, o_ts); w_fc = ldg(ts + 4, o_ts); w_pt = ldg(ts + 5, o_ts);
+        w_th = ldg(ts + 6, o_tf); w_ec = ldg(ts + 18, o_tf);
     }
     if (BQ) {   // tron1_pf_ee: gait clock (LG_TASK_STATE_BIPED, tron1_pf_ee.py:167-184)
-        const float GAS *ts = KB(const float GAS *, task_state) + (size_t)e * LG_TASK_STATE_BIPED;
-        w_gt = ts[0]; w_phi = ts[1]; w_th = ts[4 + foot_slot]; w_ec = ts[10 + foot_slot];
+        const float GAS *ts = KB(const float GAS *, task_state);
+        const unsigned o_ts = (unsigned)LG_TASK_STATE_BIPED * o_e, o_tf = o_ts + 4u * (unsigned)foot_slot;
+        w_gt = ldg(ts, o_ts); w_phi = ldg(ts + 1, o_ts); w_th = ldg(ts + 4, o_tf); w_ec = ldg(ts + 10, o_tf);
     }
     if (SQ || BQ) {
-        w_push = KB(const float GAS *, rand_push_vels)[3 * e + cj];
-        if (k_obs_dirty) w_dirty = (int)k_obs_dirty[e];
+        w_push = ldg(KB(const float GAS *, rand_push_vels), o_e3);
+        if (k_obs_dirty) w_dirty = (int)ldg(k_obs_dirty, o_e >> 2);
     }
     if (EQ || BQ) {   // go2_ee, tron1_pf_ee: terrain level / type of the env (curriculum at reset)
         const int32_t GAS *tl = KB(const int32_t GAS *, terrain_levels), *tt = KB(const int32_t GAS *, terrain_types);
-        if (tl) { w_lvl = tl[e]; w_type = tt[e]; }
+        if (tl) { w_lvl = ldg(tl, o_e); w_type = ldg(tt, o_e); }
     }
     if (GTAIL && tl_ < 16) {
         const LgTaskCfg GAS *T = kT;
@@ -692,9 +715,10 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
 
     // ---------------- prologue stores ---------------------------------------------------------------
     if (DO_PRE && stj) {
-        stq(B.llast_actions, 4u * (unsigned)ja, llast_act);
-        stq(B.last_actions, 4u * (unsigned)ja, last_act);
-        stq(B.actions, 4u * (unsigned)ja, act);
+        const unsigned oj = blk(o_ja);
+        stq(B.llast_actions, oj, llast_act);
+        stq(B.last_actions, oj, last_act);
+        stq(B.actions, oj, act);
     }
     float last_foot_v = snap_fv, qd_start = qd;   // kept for the MDP tail (dof_acc, foot_acc)
     // injected read-backs (INJ): what the physics of this step left behind, as the test put it into the buffers
@@ -708,10 +732,10 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
         inj_fp = B.feet_pos[(e * F + foot_slot) * 3 + cj];
         inj_pg = B.projected_gravity[3 * e + cj]; inj_eul = B.base_euler[3 * e + cj];
     } else {
-    if (stj) stq(B.last_dof_vel, 4u * (unsigned)ja, qd);   // "last" snapshots (genesis_simulator.py:21-24)
+    if (stj) stq(B.last_dof_vel, blk(o_ja), qd);   // "last" snapshots (genesis_simulator.py:21-24)
     if (st) {
-        stq(B.last_feet_vel, 4u * (unsigned)((e * F + foot_slot) * 3 + cj), snap_fv);
-        if (leg == 0) { stq(B.last_base_lin_vel, 4u * (unsigned)(3 * e + cj), snap_blv); stq(B.last_base_ang_vel, 4u * (unsigned)(3 * e + cj), snap_bav); }
+        stq(B.last_feet_vel, blk(o_ft), snap_fv);
+        if (leg == 0) { const unsigned oe = blk(o_e3); stq(B.last_base_lin_vel, oe, snap_blv); stq(B.last_base_ang_vel, oe, snap_bav); }
     }
     }
     (void)last_foot_v; (void)qd_start;
@@ -760,9 +784,9 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
             LIc[j] = QM{lr[LT_IC + 3 * j], lr[LT_IC + 3 * j + 1], lr[LT_IC + 3 * j + 2]};
         }
         Lqlo = lr[LT_QLO]; Lqhi = lr[LT_QHI]; Leff = lr[LT_EFF]; Lvlim = lr[LT_VLIM];
-        arm = B.joint_armature ? dr_arm : lr[LT_ARM];
-        jfric = B.joint_friction ? dr_jf : lr[LT_JFRIC];
-        jdamp = B.joint_damping ? dr_jd : lr[LT_JDAMP];
+        arm = (!RS && B.joint_armature) ? dr_arm : lr[LT_ARM];
+        jfric = (!RS && B.joint_friction) ? dr_jf : lr[LT_JFRIC];
+        jdamp = (!RS && B.joint_damping) ? dr_jd : lr[LT_JDAMP];
         foot_c_loc = lr[LT_FOOT_C]; foot_r = lr[LT_FOOT_R]; foot_link_pos = lr[LT_LINKPOS];
 #pragma unroll
         for (int k = 0; k < NSLOT; k++) {
@@ -1423,6 +1447,14 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
     }  // sub-steps
 
     STAMP(21);
+    // tron1_pf_ee (two waves per workgroup, ~390 registers): seven more values held across the sub-step loop cost it register moves in
+    // every sub-step.  Its tail forms the offsets again from the indices that are live there anyway (`blk` keeps the compiler from
+    // re-using the prologue's values): the same expressions as lg_lane_ints.h.
+    if constexpr (BQ) {
+        const unsigned e2 = blk((unsigned)e);
+        o_ja = 4u * blk((unsigned)ja); o_e = 4u * e2; o_e3 = 4u * (3u * e2 + (unsigned)cj); o_q4 = 4u * (4u * e2 + (unsigned)L.c);
+        o_fs = 4u * (e2 * (unsigned)F + (unsigned)foot_slot); o_ft = 3u * o_fs + 4u * (unsigned)cj; o_es = 4u * ((unsigned)ei * (unsigned)N + e2);
+    }
     // Every load of the start-of-kernel burst landed during the sub-steps; say so before the read-back stores go out.  vmcnt
     // retires loads and stores in issue order, and the compiler keeps a load "pending" until a wait formally covers it: the first
     // use of a prologue value behind the ~60 read-back stores (episode sums, soft limits, noise scales of the MDP tail) otherwise
@@ -1444,13 +1476,13 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
             // never silent: counted, and the env terminates at this step's check_termination (fail_buf over the threshold)
             // the start-of-step snapshots may be what was not finite: this step's rate terms (dof_acc, foot_acc) read zeros instead
             last_foot_v = 0.f; qd_start = 0.f;
-            if (stj) B.last_dof_vel[ja] = 0.f;
+            if (stj) stq(B.last_dof_vel, o_ja, 0.f);
             if (st) {
-                B.last_feet_vel[(e * F + foot_slot) * 3 + cj] = 0.f;
-                if (leg == 0) { B.last_base_lin_vel[3 * e + cj] = 0.f; B.last_base_ang_vel[3 * e + cj] = 0.f; }
+                stq(B.last_feet_vel, o_ft, 0.f);
+                if (leg == 0) { stq(B.last_base_lin_vel, o_e3, 0.f); stq(B.last_base_ang_vel, o_e3, 0.f); }
             }
             if (lead && L.is0) {
-                if (B.nonfinite_count) atomicAdd(B.nonfinite_count, 1);
+                if (RS || B.nonfinite_count) atomicAdd(B.nonfinite_count, 1);   // RS: bound (host-checked, plan()'s `rs`)
                 if (MPH == 0 && B.fail_buf) B.fail_buf[e] = LG_FAIL_NONFINITE;   // the MDP launch that follows reads it
             }
         }
@@ -1503,26 +1535,26 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
         f_link[0] = inj_fl[0]; f_link[1] = inj_fl[1]; f_link[2] = inj_fl[2]; f_link[3] = inj_fl[3]; f_base = inj_fb;
     }
     // Read-back stores: a wave-uniform base (kernel argument) + a 32-bit byte offset per lane, so that the store takes its base from scalar
-    // registers (saddr form) -- one offset per index pattern, shared by the arrays that use it -- instead of a 64-bit pointer computed in
-    // vector registers for every store (sign extension, 64-bit shift, add with carry: 3-4 VALU instructions each, ~70 stores per lane in the
-    // step).  Every array stays below 4 GiB (checked where the launch is chosen, lg_host.hip).
-    const unsigned o_ja = 4u * (unsigned)ja, o_e3 = 4u * (unsigned)(3 * e + cj), o_ft = 4u * (unsigned)((e * F + foot_slot) * 3 + cj);
-    if (!INJ && stj) { stq(B.dof_pos, o_ja, q); stq(B.dof_vel, o_ja, qd); stq(B.torques, o_ja, torque); }
+    // registers (saddr form) -- one offset per index pattern (o_ja, o_e3, o_ft, ...: formed once for the start-of-kernel loads), shared by the
+    // arrays that use it -- instead of a 64-bit pointer computed in vector registers for every store (sign extension, 64-bit shift, add with
+    // carry: 3-4 VALU instructions each, ~70 stores per lane in the step).
+    if (!INJ && stj) { const unsigned oj = blk(o_ja); stq(B.dof_pos, oj, q); stq(B.dof_vel, oj, qd); stq(B.torques, oj, torque); }
     if (!INJ && st) {
-        const unsigned o_lk = 4u * (unsigned)((e * nL + foot_link - 3) * 3 + cj);
+        const unsigned o_lk = 4u * (unsigned)((e * nL + foot_link - 3) * 3 + cj), of = blk(o_ft);
 #pragma unroll
         for (int k = 0; k < 4; k++) stq(B.link_contact_forces, o_lk + 12u * (unsigned)k, f_link[k]);
-        stq(B.feet_pos, o_ft, foot_p);
-        stq(B.feet_vel, o_ft, foot_v);
+        stq(B.feet_pos, of, foot_p);
+        stq(B.feet_vel, of, foot_v);
         if (leg == 0) {
-            stq(B.base_pos, o_e3, pos);
-            stq(B.base_lin_vel_w, o_e3, vw); stq(B.base_ang_vel_w, o_e3, ww);
-            stq(B.base_lin_vel, o_e3, blv); stq(B.base_ang_vel, o_e3, bav);
-            stq(B.projected_gravity, o_e3, pg); stq(B.base_euler, o_e3, eul);
+            const unsigned oe = blk(o_e3);
+            stq(B.base_pos, oe, pos);
+            stq(B.base_lin_vel_w, oe, vw); stq(B.base_ang_vel_w, oe, ww);
+            stq(B.base_lin_vel, oe, blv); stq(B.base_ang_vel, oe, bav);
+            stq(B.projected_gravity, oe, pg); stq(B.base_euler, oe, eul);
             stq(B.link_contact_forces, 4u * (unsigned)((e * nL) * 3 + cj), f_base);
         }
     }
-    if (!INJ && live && leg == 0) stq(B.base_quat, 4u * (unsigned)(4 * e + L.c), quat);
+    if (!INJ && live && leg == 0) stq(B.base_quat, blk(o_q4), quat);
 
     // ---------------- terrain sampling around the base and the feet (genesis_simulator.py:552-610) ------
     const int P = PLANE ? 0 : HOT(o_n_height_points);
@@ -1751,8 +1783,11 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
         const auto b_tracking_sigma = BQ ? HOT(tracking_sigma) : HOT_T(tracking_sigma)();
         const auto b_yaw_clip_0 = BQ ? HOT(yaw_clip[0]) : HOT_T(yaw_clip[0])();
         const auto b_yaw_clip_1 = BQ ? HOT(yaw_clip[1]) : HOT_T(yaw_clip[1])();
+        // RS: the configs' branch switches are constants (lg_shared.h lg_default_flags, host-checked by plan() like the reward set): the
+        // statements behind them are the same, their tests and selects are gone
+        constexpr LgProfFlags RSF = lg_default_flags(PROF);
         const auto h_about_landing_threshold = BQ ? b_about_landing_threshold : HOT(about_landing_threshold);
-        const auto h_add_noise = BQ ? b_add_noise : HOT(add_noise);
+        const auto h_add_noise = BQ ? b_add_noise : HOT(add_noise);   // not a constant of RS: see lg_shared.h LgProfFlags
         const auto h_base_height_target = BQ ? b_base_height_target : HOT(base_height_target);
         const auto h_base_init_quat_0 = BQ ? b_base_init_quat_0 : HOT(base_init_quat[0]);
         const auto h_base_init_quat_1 = BQ ? b_base_init_quat_1 : HOT(base_init_quat[1]);
@@ -1763,15 +1798,15 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
         const auto h_dr_com_lo_0 = BQ ? b_dr_com_lo_0 : HOT(dr_com_lo[0]);
         const auto h_dr_com_lo_1 = BQ ? b_dr_com_lo_1 : HOT(dr_com_lo[1]);
         const auto h_dr_com_lo_2 = BQ ? b_dr_com_lo_2 : HOT(dr_com_lo[2]);
-        const auto h_dr_com_on = BQ ? b_dr_com_on : HOT(dr_com_on);
+        const auto h_dr_com_on = RS ? RSF.dr_com_on : (BQ ? b_dr_com_on : HOT(dr_com_on));
         const auto h_dr_com_span_0 = BQ ? b_dr_com_span_0 : HOT(dr_com_span[0]);
         const auto h_dr_com_span_1 = BQ ? b_dr_com_span_1 : HOT(dr_com_span[1]);
         const auto h_dr_com_span_2 = BQ ? b_dr_com_span_2 : HOT(dr_com_span[2]);
         const auto h_dr_friction_lo = BQ ? b_dr_friction_lo : HOT(dr_friction_lo);
-        const auto h_dr_friction_on = BQ ? b_dr_friction_on : HOT(dr_friction_on);
+        const auto h_dr_friction_on = RS ? RSF.dr_friction_on : (BQ ? b_dr_friction_on : HOT(dr_friction_on));
         const auto h_dr_friction_span = BQ ? b_dr_friction_span : HOT(dr_friction_span);
         const auto h_dr_mass_lo = BQ ? b_dr_mass_lo : HOT(dr_mass_lo);
-        const auto h_dr_mass_on = BQ ? b_dr_mass_on : HOT(dr_mass_on);
+        const auto h_dr_mass_on = RS ? RSF.dr_mass_on : (BQ ? b_dr_mass_on : HOT(dr_mass_on));
         const auto h_dr_mass_span = BQ ? b_dr_mass_span : HOT(dr_mass_span);
         const auto h_env_id_offset = BQ ? b_env_id_offset : HOT(env_id_offset);
         const auto h_fail_threshold = BQ ? b_fail_threshold : HOT(fail_threshold);
@@ -1779,7 +1814,7 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
         const auto h_foot_clearance_sigma = BQ ? b_foot_clearance_sigma : HOT(foot_clearance_sigma);
         const auto h_foot_clearance_target = BQ ? b_foot_clearance_target : HOT(foot_clearance_target);
         const auto h_foot_height_offset = BQ ? b_foot_height_offset : HOT(foot_height_offset);
-        const auto h_heading_command = BQ ? b_heading_command : HOT(heading_command);
+        const auto h_heading_command = RS ? RSF.heading_command : (BQ ? b_heading_command : HOT(heading_command));
         const auto h_max_episode_length = BQ ? b_max_episode_length : HOT(max_episode_length);
         const auto h_max_projected_gravity = BQ ? b_max_projected_gravity : HOT(max_projected_gravity);
         const auto h_max_push_vel_xy = BQ ? b_max_push_vel_xy : HOT(max_push_vel_xy);
@@ -1797,7 +1832,7 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
         const auto h_obs_scale_dof_vel = BQ ? b_obs_scale_dof_vel : HOT(obs_scale_dof_vel);
         const auto h_obs_scale_lin_vel = BQ ? b_obs_scale_lin_vel : HOT(obs_scale_lin_vel);
         const auto h_obs_sets = BQ ? b_obs_sets : HOT(obs_sets);
-        const auto h_only_positive_rewards = BQ ? b_only_positive_rewards : HOT(only_positive_rewards);
+        const auto h_only_positive_rewards = RS ? RSF.only_positive_rewards : (BQ ? b_only_positive_rewards : HOT(only_positive_rewards));
         const auto h_push_interval = BQ ? b_push_interval : HOT(push_interval);
         const auto h_resample_steps = BQ ? b_resample_steps : HOT(resample_steps);
         const auto h_reset_ang_vel_lo = BQ ? b_reset_ang_vel_lo : HOT(reset_ang_vel_lo);
@@ -1819,7 +1854,7 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
         // the stacked-observation profiles: go2_wtw, the go2_ee family, tron1_pf_ee
         const auto h_slots_dr_kp = BQ ? b_slots_dr_kp : (SQ ? HOT(slots.dr_kp) : 0);
         const auto h_slots_dr_kd = BQ ? b_slots_dr_kd : (SQ ? HOT(slots.dr_kd) : 0);
-        const auto h_dr_pd_on = BQ ? b_dr_pd_on : (SQ ? HOT(dr_pd_on) : 0);
+        const auto h_dr_pd_on = RS ? RSF.dr_pd_on : (BQ ? b_dr_pd_on : (SQ ? HOT(dr_pd_on) : 0));
         const auto h_dr_kp_lo = BQ ? b_dr_kp_lo : (SQ ? HOT(dr_kp_lo) : 0.f);
         const auto h_dr_kp_span = BQ ? b_dr_kp_span : (SQ ? HOT(dr_kp_span) : 0.f);
         const auto h_dr_kd_lo = BQ ? b_dr_kd_lo : (SQ ? HOT(dr_kd_lo) : 0.f);
@@ -1843,7 +1878,7 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
         const auto h_slots_terrain_level = EQ ? HOT(slots.terrain_level) : 0;
         const auto h_reset_root_xy_lo = BQ ? b_reset_root_xy_lo : (EQ ? HOT(reset_root_xy_lo) : 0.f);
         const auto h_reset_root_xy_span = BQ ? b_reset_root_xy_span : (EQ ? HOT(reset_root_xy_span) : 0.f);
-        const auto h_custom_origins = BQ ? b_custom_origins : (EQ ? HOT(custom_origins) : 0);
+        const auto h_custom_origins = RS ? RSF.custom_origins : (BQ ? b_custom_origins : (EQ ? HOT(custom_origins) : 0));
         const auto h_heights_offset = BQ ? b_heights_offset : (EQ ? HOT(heights_offset) : 0.f);
         const auto h_heights_clip_scale = BQ ? b_heights_clip_scale : (EQ ? HOT(heights_clip_scale) : 0);
         const auto h_obs_scale_height = BQ ? b_obs_scale_height : (EQ ? HOT(obs_scale_height) : 1.f);
@@ -1933,7 +1968,7 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
                 const bool xy = L.c < 2;
                 vw = xy ? vw + pv : vw;
                 o_push = xy ? pv : o_push;
-                if (liveB && leg == 0 && xy) { B.rand_push_vels[3 * e + L.c] = pv; B.base_lin_vel_w[3 * e + L.c] = vw; }   // DUO: role 1, in program order with its reset stores
+                if (liveB && leg == 0 && xy) { const unsigned oe = blk(o_e3); stq(B.rand_push_vels, oe, pv); stq(B.base_lin_vel_w, oe, vw); }   // xy: L.c == cj   // DUO: role 1, in program order with its reset stores
             }
         }
         // ---- go2_wtw behaviour parameters (go2_wtw.py:180-218): lane c of every quad evaluates the block that holds draw `slot + c` and
@@ -2332,18 +2367,21 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
             const float npg = -L.sel(bc<2>(Rr.c0), bc<2>(Rr.c1), bc<2>(Rr.c2));
             if (reset) { blv = vw; bav = ww; pg = npg; }
             if (reset && stB) {
-                B.dof_pos[ja] = q; B.dof_vel[ja] = 0.f; B.last_dof_vel[ja] = 0.f;
-                B.actions[ja] = 0.f; B.last_actions[ja] = 0.f; B.llast_actions[ja] = 0.f;
-                if ((SQ || BQ) && h_dr_pd_on) { B.kp_scale[ja] = o_kp; B.kd_scale[ja] = o_kd; }
-                if (EQ && h_terrain_curriculum && p.counter > 0 && leg == 0) { B.env_origins[3 * e + cj] = norg; if (L.is0) B.terrain_levels[e] = nlvl; }
-                B.last_feet_vel[(e * F + foot_slot) * 3 + cj] = 0.f;
+                // the same offsets as the read-back stores (saddr form)
+                const unsigned oj = blk(o_ja);
+                stq(B.dof_pos, oj, q); stq(B.dof_vel, oj, 0.f); stq(B.last_dof_vel, oj, 0.f);
+                stq(B.actions, oj, 0.f); stq(B.last_actions, oj, 0.f); stq(B.llast_actions, oj, 0.f);
+                if ((SQ || BQ) && h_dr_pd_on) { stq(B.kp_scale, oj, o_kp); stq(B.kd_scale, oj, o_kd); }
+                if (EQ && h_terrain_curriculum && p.counter > 0 && leg == 0) { stq(B.env_origins, blk(o_e3), norg); if (L.is0) stq(B.terrain_levels, blk(o_e), (int32_t)nlvl); }
+                stq(B.last_feet_vel, blk(o_ft), 0.f);
                 if (leg == 0) {
-                    if (curr) { B.env_origins[3 * e + cj] = norg; if (L.is0) B.terrain_levels[e] = nlvl; }
-                    B.base_pos[3 * e + cj] = pos; B.base_lin_vel_w[3 * e + cj] = vw; B.base_ang_vel_w[3 * e + cj] = ww;
-                    B.base_lin_vel[3 * e + cj] = blv; B.base_ang_vel[3 * e + cj] = bav; B.projected_gravity[3 * e + cj] = pg;
-                    B.last_base_lin_vel[3 * e + cj] = 0.f; B.last_base_ang_vel[3 * e + cj] = 0.f;
-                    if (h_dr_com_on) B.base_com_bias[3 * e + cj] = BQ ? o_com : L.sel(h_dr_com_span_0, h_dr_com_span_1, h_dr_com_span_2) * v1 +
-                                                                            L.sel(h_dr_com_lo_0, h_dr_com_lo_1, h_dr_com_lo_2);
+                    const unsigned oe = blk(o_e3);
+                    if (curr) { stq(B.env_origins, oe, norg); if (L.is0) stq(B.terrain_levels, blk(o_e), (int32_t)nlvl); }
+                    stq(B.base_pos, oe, pos); stq(B.base_lin_vel_w, oe, vw); stq(B.base_ang_vel_w, oe, ww);
+                    stq(B.base_lin_vel, oe, blv); stq(B.base_ang_vel, oe, bav); stq(B.projected_gravity, oe, pg);
+                    stq(B.last_base_lin_vel, oe, 0.f); stq(B.last_base_ang_vel, oe, 0.f);
+                    if (h_dr_com_on) stq(B.base_com_bias, oe, BQ ? o_com : L.sel(h_dr_com_span_0, h_dr_com_span_1, h_dr_com_span_2) * v1 +
+                                                                            L.sel(h_dr_com_lo_0, h_dr_com_lo_1, h_dr_com_lo_2));
                 }
                 if (BQ && leg == 1 && h_dr_joint_on && B.joint_armature) {   // genesis_simulator.py:704-733: one value per env each
                     float *jp = L.is0 ? B.joint_armature : (L.is1 ? B.joint_friction : B.joint_damping);
@@ -2351,21 +2389,22 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
                 }
             }
             if (reset && liveB && leg == 0) {
-                B.base_quat[4 * e + L.c] = quat;
+                stq(B.base_quat, blk(o_q4), quat);
                 if (L.is3) {   // the lane holding the fourth element of blocks 0 / 1: friction and mass draws
-                    if (h_dr_friction_on) B.friction_values[e] = BQ ? o_fric : h_dr_friction_span * v0 + h_dr_friction_lo;
-                    if (h_dr_mass_on) B.added_base_mass[e] = BQ ? o_mass : h_dr_mass_span * v1 + h_dr_mass_lo;
-                    B.episode_done_step[e] = (int)p.counter;
+                    const unsigned oe = blk(o_e);
+                    if (h_dr_friction_on) stq(B.friction_values, oe, BQ ? o_fric : h_dr_friction_span * v0 + h_dr_friction_lo);
+                    if (h_dr_mass_on) stq(B.added_base_mass, oe, BQ ? o_mass : h_dr_mass_span * v1 + h_dr_mass_lo);
+                    stq(B.episode_done_step, oe, (int32_t)p.counter);
                 }
             }
             if (reset && live) {    // extras["episode"] snapshot (legged_robot.py:128-132), then the sums restart
                 if constexpr (BQ) {
 #pragma unroll
                     for (int k = 0; k < 4; k++)
-                        if (ei + 8 * k < LG_R_COUNT && ((rmask >> (ei + 8 * k)) & 1u)) { B.episode_done_sums[(size_t)(ei + 8 * k) * N + e] = es[k]; es[k] = 0.f; }
+                        if (ei + 8 * k < LG_R_COUNT && ((rmask >> (ei + 8 * k)) & 1u)) { stq(B.episode_done_sums, o_es + 32u * (unsigned)k * (unsigned)N, es[k]); es[k] = 0.f; }
                 } else {
-                    if ((rmask >> ei) & 1u) { B.episode_done_sums[(size_t)ei * N + e] = es0; es0 = 0.f; }
-                    if (ei + 16 < LG_R_COUNT && ((rmask >> (ei + 16)) & 1u)) { B.episode_done_sums[(size_t)(ei + 16) * N + e] = es1; es1 = 0.f; }
+                    if ((rmask >> ei) & 1u) { stq(B.episode_done_sums, blk(o_es), es0); es0 = 0.f; }
+                    if (ei + 16 < LG_R_COUNT && ((rmask >> (ei + 16)) & 1u)) { stq(B.episode_done_sums, o_es + 64u * (unsigned)N, es1); es1 = 0.f; }
                 }
             }
         }
@@ -2715,17 +2754,20 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
                     uq = rin[ns_ + 9 + d0 + cj]; uqd = rin[ns_ + 9 + A + d0 + cj]; ug = rin[ns_ + 3 + cj]; ua = rin[ns_ + 6 + cj];
                 }
             }
-            float *o = B.obs_buf + ((size_t)(h_obs_sets > 1 ? p.obs_set : 0) * N + e) * (size_t)(9 + 3 * A);
+            // destination = the set's allocation (wave-uniform) + a 32-bit byte offset per lane: stores in saddr form, as the read-back's (one set
+            // stays below 4 GiB: lg_host.hip flat_profile)
+            float *const ob = B.obs_buf + (size_t)(h_obs_sets > 1 ? p.obs_set : 0) * N * (size_t)(9 + 3 * A);
+            const unsigned oj = (unsigned)(9 + 3 * A) * o_e + 4u * (unsigned)(9 + d0 + cj), oc = (unsigned)(9 + 3 * A) * o_e + 4u * (unsigned)cj;
             auto noisy = [&](float v, float u, float ns) { if (nz) v += (2.f * u - 1.f) * ns; return clampf(v, -co, co); };
             if (st) {
-                o[9 + d0 + cj] = noisy((q - q0) * h_obs_scale_dof_pos, uq, m_nq);
-                o[9 + A + d0 + cj] = noisy(qd * h_obs_scale_dof_vel, uqd, m_nqd);
-                o[9 + 2 * A + d0 + cj] = clampf(act, -co, co);
+                stq(ob, oj, noisy((q - q0) * h_obs_scale_dof_pos, uq, m_nq));
+                stq(ob, oj + 4u * (unsigned)A, noisy(qd * h_obs_scale_dof_vel, uqd, m_nqd));
+                stq(ob, oj + 8u * (unsigned)A, clampf(act, -co, co));
                 if (leg == 0) {
                     const float cs_ = L.is2 ? h_obs_scale_ang_vel : h_obs_scale_lin_vel;
-                    o[cj] = clampf(cmdv * cs_, -co, co);
-                    o[3 + cj] = noisy(pg, ug, L.sel(h_noise_lead_0, h_noise_lead_1, h_noise_lead_2));
-                    o[6 + cj] = noisy(bav * h_obs_scale_ang_vel, ua, L.sel(h_noise_lead_3, h_noise_lead_4, h_noise_lead_5));
+                    stq(ob, oc, clampf(cmdv * cs_, -co, co));
+                    stq(ob, oc + 12u, noisy(pg, ug, L.sel(h_noise_lead_0, h_noise_lead_1, h_noise_lead_2)));
+                    stq(ob, oc + 24u, noisy(bav * h_obs_scale_ang_vel, ua, L.sel(h_noise_lead_3, h_noise_lead_4, h_noise_lead_5)));
                 }
             }
         }
@@ -2734,7 +2776,7 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
         //      host-checked) ----
         if constexpr (BQ) {
             if (live) {        // DUO: role 0, what the reward terms produced
-                const unsigned es4 = ((unsigned)ei * (unsigned)N + (unsigned)e) * 4u;
+                const unsigned es4 = blk(o_es);
 #pragma unroll
                 for (int k = 0; k < 4; k++)
                     if (ei + 8 * k < LG_R_COUNT && ((rmask >> (ei + 8 * k)) & 1u))
@@ -2750,16 +2792,15 @@ __global__ __launch_bounds__(quad_block(PROF, MPH)) void quad_sim_kernel(KParams
                 }
             }
         } else if (live) {
-            const unsigned o_es = 4u * ((unsigned)ei * (unsigned)N + (unsigned)e);
-            if ((rmask >> ei) & 1u) stq(B.episode_sums, o_es, es0);
+            if ((rmask >> ei) & 1u) stq(B.episode_sums, blk(o_es), es0);
             if (ei + 16 < LG_R_COUNT && ((rmask >> (ei + 16)) & 1u)) stq(B.episode_sums, o_es + 64u * (unsigned)N, es1);
-            if (L.is0) { stq(B.feet_air_time, 4u * (unsigned)(e * F + foot_slot), air); stq(B.last_contacts, (unsigned)(e * F + foot_slot), (uint8_t)last_contact); }
+            if (L.is0) { stq(B.feet_air_time, blk(o_fs), air); stq(B.last_contacts, o_fs >> 2, (uint8_t)last_contact); }
             if (leg == 0) {
-                stq(B.commands, 4u * (unsigned)(4 * e + L.c), cmdv);
+                stq(B.commands, blk(o_q4), cmdv);
                 if (L.is0) {
-                    const unsigned ue = (unsigned)e;
-                    stq(B.episode_length_buf, 4u * ue, (int32_t)ep_len); stq(B.fail_buf, 8u * ue, (int64_t)failb);
-                    stq(B.reset_buf, ue, (uint8_t)(reset ? 1 : 0)); stq(B.time_out_buf, ue, (uint8_t)(time_out ? 1 : 0)); stq(B.rew_buf, 4u * ue, total);
+                    const unsigned oe = blk(o_e), ue = oe >> 2;
+                    stq(B.episode_length_buf, oe, (int32_t)ep_len); stq(B.fail_buf, 2u * oe, (int64_t)failb);
+                    stq(B.reset_buf, ue, (uint8_t)(reset ? 1 : 0)); stq(B.time_out_buf, ue, (uint8_t)(time_out ? 1 : 0)); stq(B.rew_buf, oe, total);
                 }
             }
         }

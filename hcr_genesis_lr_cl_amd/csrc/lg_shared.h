@@ -10,6 +10,7 @@
 #include <type_traits>
 #include "../../include/lgsim.h"
 #include "lg_math.h"
+#include "lg_lane_ints.h"
 #include <vector>
 #include <hip/hip_ext.h>
 
@@ -348,6 +349,7 @@ struct KParams {
     struct { int m_n_links, m_foot_link[4], obs_layout, o_n_height_points; unsigned reward_mask; float clip_actions;
              int cat_enable;      // LgTaskCfg.cat_enable: tested on every step, so not behind a memory round trip
              int joint_axis[4];   // per joint index: 0/1/2 if that joint's axis is +-e_x/e_y/e_z on every leg, else -1 (lg_quad.h joint_rot)
+             unsigned foot_pack;  // foot link and foot slot of every leg, a byte each (lg_lane_ints.h lg_foot_pack)
     } k;
     int obs_win;         // first frame of the observation window this launch writes (sliding history, LgTaskCfg.obs_slack)
     int obs_set;         // copy of obs_buf / priv_obs_buf / labels_buf this launch writes (LgTaskCfg.obs_sets)
@@ -380,6 +382,24 @@ constexpr unsigned lg_default_reward_mask(int prof) {
 // The solver options of the task configs (config.py HipCfg defaults): the RS instantiations have them as constants too -- two contact sweeps
 // as straight-line code, W of every foot recomputed on every sub-step (nothing kept between sub-steps).  plan() checks the engine's options.
 constexpr int LG_DEFAULT_CONTACT_ITERS = 2, LG_DEFAULT_CONTACT_W_EVERY = 1;
+// The on / off switches of the task configs that only steer branches of the component-layout tails (heading commands, positive rewards only,
+// the domain-randomisation switches, custom origins; config.py: the same in GO2Cfg, GO2WTWCfg and GO2EECfg with its heads, but for PD-gain
+// randomisation and the heightfield's custom origins): constants of the RS instantiations too, checked by plan() against the engine's task
+// like the reward set.  (add_noise is NOT one of them: with the test gone the compiler fused the other product of go2's
+// `scale * x + noise * u` into the sum, and the observations differed in their last bits.)  Together with them plan() checks what else RS
+// takes as given: the optional buffer the kernel would test for null is bound (nonfinite_count), the per-env joint parameter arrays are not.
+struct LgProfFlags { int heading_command, only_positive_rewards, dr_friction_on, dr_mass_on, dr_com_on, dr_pd_on, custom_origins; };
+constexpr LgProfFlags lg_default_flags(int prof) {
+    return LgProfFlags{1, 1, 1, 1, 1, prof == LG_PROF_GO2_FLAT ? 0 : 1, (prof == LG_PROF_GO2_EE || prof == LG_PROF_GO2_PROGRAM) ? 1 : 0};
+}
+inline bool lg_rs_constants_hold(int prof, const LgTaskCfg &t, const LgBuffers &b) {
+    const LgProfFlags f = lg_default_flags(prof);
+    const bool ok = (t.heading_command != 0) == (f.heading_command != 0) &&
+              (t.only_positive_rewards != 0) == (f.only_positive_rewards != 0) && (t.dr_friction_on != 0) == (f.dr_friction_on != 0) &&
+              (t.dr_mass_on != 0) == (f.dr_mass_on != 0) && (t.dr_com_on != 0) == (f.dr_com_on != 0) && (t.dr_pd_on != 0) == (f.dr_pd_on != 0) &&
+              (t.custom_origins != 0) == (f.custom_origins != 0);
+    return ok && b.nonfinite_count && !b.joint_armature && !b.joint_friction && !b.joint_damping;
+}
 // The reward terms a profile's component-layout tail does not carry: a task with one of them active is outside the profile (lg_host.hip).
 constexpr unsigned lg_rbits(std::initializer_list<int> terms) { unsigned m = 0; for (int k : terms) m |= 1u << k; return m; }
 constexpr unsigned lg_tail_reward_excluded(int prof) {
