@@ -1,0 +1,198 @@
+"""The fused learner passes on the GPU (csrc/lg_train.hip, csrc/lg_train_ee.hip, csrc/lg_train_tiles.h) at the edges of
+tests/train_edges.py, which the tables of tests/test_gpu_train.py and tests/test_gpu_train_ee.py do not reach: the 16- and 8-row tiles,
+NT = 4 over ragged widths, 31 and 32 batch slices with a short last one, layers of unequal slice counts, the finalize kernel's second
+trip, and the 16-byte row accesses under a stride.  Every case runs as those two files run theirs (their `run`) against the float64
+restatement under the same factor-8 parity rule; bit-identical repeats, the independence of rows across the small tiles, and strided
+views with widths that are multiples of 4."""
+import numpy as np
+import pytest
+import torch
+
+from hcr_genesis_lr_cl_amd import train
+from tests import train_cases as tc
+from tests import train_edges as te
+from tests import train_ee_cases as ec
+from tests.test_gpu_train import dev, host, same_bits
+from tests.test_gpu_train import run as run_plain
+from tests.test_gpu_train_ee import run as run_ee
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda")
+RATIOS = []
+FILL = 7.25
+
+
+def run_case(row, B, x=None):
+    """One run of a case on a fresh module, after the plan has been held to the row tile the table states."""
+    d = te.ROWS[row]
+    x = x if x is not None else te.inputs(row, B)
+    if d["kind"] == "plain":
+        m = tc.Module(x, DEV)
+        tp = train.FusedTrainPass(m)
+        assert tp.plan(B).row_tile == d["R"]
+        return run_plain(x, m, tp)
+    m = ec.Module(x, DEV)
+    tp = train.FusedTrainPassEE(m)
+    assert (tp.plan(B).row_tile, tp.estimator_plan(B).row_tile) == d["R"]
+    return run_ee(x, m, tp)
+
+
+# ---- parity -----------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", te.CASES, ids=[te.case_id(c) for c in te.CASES])
+def test_parity_on_the_edge_table(case):
+    row, B = case
+    got, _, _ = run_case(row, B)
+    ref64, ref32 = te.references(row, B)
+    n = len(RATIOS)
+    te.check(row, got, ref64, ref32, te.case_id(case), RATIOS)
+    assert len(RATIOS) == n + 1 and RATIOS[-1][0] == te.case_id(case)
+
+
+# ---- determinism ------------------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", [("r8", 25), ("tiny", 2113), ("fixture", 8193)], ids=te.case_id)
+def test_repeats_are_bit_identical(case):
+    """The 8-row tile, the 32-slice combine and the two-trip finalize: the same pass again on its own workspace, and a fresh one."""
+    row, B = case
+    assert case in te.CASES
+    run = run_plain if te.ROWS[row]["kind"] == "plain" else run_ee
+    x = te.inputs(row, B)
+    a, m, tp = run_case(row, B)
+    b, _, _ = run(x, m, tp)
+    c, _, _ = run_case(row, B)
+    assert same_bits(a, b) and same_bits(a, c)
+
+
+# ---- rows across the small tiles --------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("case", [("r8", 25), ("r16", 49)], ids=te.case_id)
+def test_rows_are_independent_across_the_small_tiles(case):
+    """A NaN in the last row of the first tile and another in the first row of the next, in obs and in critic_obs: those two rows of mu,
+    sigma and values are NaN and every other row keeps the bits of the clean run."""
+    row, B = case
+    R = te.ROWS[row]["R"]
+    assert case in te.CASES and R in (8, 16) and B > 2 * R
+    x = te.inputs(row, B)
+    clean, _, _ = run_case(row, B)
+    y = dict(x, obs=x["obs"].copy(), critic_obs=x["critic_obs"].copy())
+    for k in ("obs", "critic_obs"):
+        y[k][R - 1, 2] = np.nan
+        y[k][R, 0] = np.nan
+    got, _, _ = run_case(row, B, y)
+    others = np.ones(B, bool)
+    others[[R - 1, R]] = False
+    for k in ("mu", "sigma", "values"):
+        assert np.isnan(got[k][~others]).all(), k
+        assert np.array_equal(got[k][others].view(np.uint32), clean[k][others].view(np.uint32)), k
+
+
+# ---- the 16-byte rows under a stride ----------------------------------------------------------------------------------------------------------
+def _place(B, w, place):
+    """(the wider filled matrix, its (B, w) view) of a placement; None: the matrix itself."""
+    if place is None:
+        t = torch.full((B, w), FILL, device=DEV)
+        return t, t
+    off, stride = place
+    wide = torch.full((B, stride), FILL, device=DEV)
+    return wide, wide[:, off:off + w]
+
+
+class _Placed:
+    """The matrices of one call, each placed alike: inputs filled from the case, outputs left at the fill."""
+
+    def __init__(self, x, B, place, inputs, outputs):
+        self.place, self.wide, self.view, self.inputs = place, {}, {}, list(inputs)
+        for k, w in list(inputs.items()) + list(outputs.items()):
+            self.wide[k], self.view[k] = _place(B, w, place)
+        for k in inputs:
+            self.view[k].copy_(dev(x[k]))
+        self.before = {k: host(v).copy() for k, v in self.wide.items()}
+
+    def check_untouched(self):
+        """Inputs and incoming gradients unchanged; every gap column of an output keeps its fill."""
+        for k, wide in self.wide.items():
+            after = host(wide)
+            if k in self.inputs:
+                assert np.array_equal(after, self.before[k]), k
+            elif self.place is not None:
+                off, w = self.place[0], self.view[k].shape[1]
+                gaps = np.ones(after.shape[1], bool)
+                gaps[off:off + w] = False
+                assert (after[:, gaps] == FILL).all(), k
+
+
+def _abi_plain(x, place):
+    B, (actor, critic) = te.VEC_B, te.VEC_PLAIN
+    m = tc.Module(x, DEV)
+    D = m.std.device
+    spec = train.describe(m, D)
+    A, V = actor[-1], critic[-1]
+    p = _Placed(x, B, place, dict(obs=actor[0], critic_obs=critic[0], grad_mu=A, grad_sigma=A, grad_values=V), dict(mu=A, sigma=A, values=V))
+    v = p.view
+    ws = torch.empty(int(train.plan(B, actor, critic).workspace_floats), device=DEV)
+    train.forward(train.train_args(spec, v["obs"], v["critic_obs"], v["mu"], v["sigma"], v["values"], ws, device=D), D)
+    grads = [torch.full_like(q, FILL) for q in spec.parameters()]
+    a = train.train_args(spec, v["obs"], v["critic_obs"], v["mu"], v["sigma"], v["values"], ws, grads, v["grad_mu"], v["grad_sigma"], v["grad_values"], device=D)
+    if place is not None:
+        assert (a.chain[0].in_stride, a.chain[1].in_stride, a.mu_stride, a.sigma_stride, a.values_stride, a.grad_mu_stride, a.grad_sigma_stride,
+                a.grad_values_stride) == (place[1],) * 8
+        assert (a.chain[0].input % 16 == 0) == (place[0] % 4 == 0) and (a.mu % 16 == 0) == (place[0] % 4 == 0)
+    train.backward(a, D)
+    torch.cuda.synchronize()
+    p.check_untouched()
+    return tc.named(x, {k: host(v[k]) for k in ("mu", "sigma", "values")}, [host(g) for g in grads])
+
+
+def _abi_ee(x, place):
+    B, (est, actor, critic) = te.VEC_B, te.VEC_EE
+    m = ec.Module(x, DEV)
+    D = m.std.device
+    spec = train.describe_ee(m, D)
+    A, V, NL = actor[-1], critic[-1], est[-1]
+    p = _Placed(x, B, place, dict(features=est[0], critic_obs=critic[0], labels=NL, terminated=1, grad_mu=A, grad_sigma=A, grad_values=V),
+                dict(mu=A, sigma=A, values=V))
+    v = p.view
+    ws = torch.empty(int(train.plan_ee(B, est, actor, critic).workspace_floats), device=DEV)
+    train._call("lg_train_ee_forward", train.ee_args(spec, v["features"], v["critic_obs"], v["mu"], v["sigma"], v["values"], ws, device=D), D)
+    rl_grads = [torch.full_like(q, FILL) for q in spec.rl_parameters()]
+    a = train.ee_args(spec, v["features"], v["critic_obs"], v["mu"], v["sigma"], v["values"], ws, rl_grads, v["grad_mu"], v["grad_sigma"], v["grad_values"], device=D)
+    train._call("lg_train_ee_backward", a, D)
+    ews = torch.empty(int(train.plan_est(B, est).workspace_floats), device=DEV)
+    loss, up = torch.full((), FILL, device=DEV), torch.full((1,), float(x["upstream"]), device=DEV)
+    train._call("lg_train_est_forward", train.est_args(spec, v["features"], v["labels"], v["terminated"], loss, ews, device=D), D)
+    est_grads = [torch.full_like(q, FILL) for q in spec.estimator_parameters()]
+    e = train.est_args(spec, v["features"], v["labels"], v["terminated"], None, ews, est_grads, up, device=D)
+    if place is not None:
+        assert (a.chain[0].in_stride, a.chain[2].in_stride, a.mu_stride, a.values_stride, a.grad_sigma_stride, e.chain.in_stride, e.labels_stride,
+                e.mask_stride) == (place[1],) * 8
+    train._call("lg_train_est_backward", e, D)
+    torch.cuda.synchronize()
+    p.check_untouched()
+    return ec.named(x, {k: host(v[k]) for k in ("mu", "sigma", "values")}, [host(g) for g in rl_grads], host(loss), [host(g) for g in est_grads])
+
+
+@pytest.mark.parametrize("kind", ["plain", "ee"])
+def test_vector_rows_under_a_stride(kind):
+    """The C ABI on column slices of wider filled matrices, every width a multiple of 4: base and stride on 16 bytes (the 16-byte accesses
+    with stride != width), a base off 16 bytes and an odd stride (the fallbacks) each give the bits of the contiguous call, which lies
+    within the parity rule; gaps, inputs and incoming gradients are untouched."""
+    plain = kind == "plain"
+    x = te.draw(kind, te.VEC_PLAIN if plain else te.VEC_EE, te.VEC_B, 977)
+    call = _abi_plain if plain else _abi_ee
+    clean = call(x, None)
+    ref64, ref32 = te.plain_references(x) if plain else ec.references(x)
+    (tc if plain else ec).check_parity(clean, ref64, ref32, f"vector rows, {kind}, contiguous", RATIOS)
+    through_autograd, _, _ = (run_plain if plain else run_ee)(x)
+    assert same_bits(clean, through_autograd)
+    for name, place in te.PLACEMENTS.items():
+        assert same_bits(call(x, place), clean), name
+
+
+def test_zz_print_the_parity_ratios():
+    """Not a check of its own: the worst |kernel - f64| / max(|torch-f32 - f64|, ulp) per tensor class over every parity check above, for
+    DESIGN.md."""
+    worst = {}
+    for _, ratios in RATIOS:
+        for k, v in ratios.items():
+            worst[k] = max(worst.get(k, 0.0), v)
+    for k, v in worst.items():
+        print(f"PARITY {k}: {v:.3f} over {len(RATIOS)} checks")

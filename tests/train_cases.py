@@ -159,36 +159,55 @@ def forward(x, dtype=np.float64):
     return dict(mu=mu, sigma=mu * 0 + std, values=c[-1], acts=(a, c))
 
 
+def slice_sum(per, g, h=None, phases=1, drop_last=False):
+    """The sum over the batch of g (or of g^T h) as the kernels form it: per slice of `per` rows, the slices added in slice order.  phases
+    = 4: a column sum of a slice is ((s0 + s1) + s2) + s3 with s_p over the rows p, p + 4, ... of the slice, as the weight-gradient wave
+    forms a bias partial; 1: row after row, as grad_std's column sums.  drop_last: without the last slice (a wrong variant)."""
+    def cols(a):
+        if phases == 1:
+            return a.sum(0)
+        s = [a[p::phases].sum(0) for p in range(phases)]
+        out = s[0]
+        for v in s[1:]:
+            out = out + v
+        return out
+    parts = [cols(g[s:s + per]) if h is None else g[s:s + per].T @ h[s:s + per] for s in range(0, g.shape[0], per)]
+    if drop_last:
+        parts = parts[:-1]
+    out = parts[0]
+    for p in parts[1:]:
+        out = out + p
+    return out
+
+
 def backward(x, dtype=np.float64, wrong=None, slices=None):
     """The hand-written backward of include/lgtrain.h in numpy `dtype`: the gradients in param_names order.  `slices` (rows per slice):
-    the batch sums are formed per slice and added in slice order, as the kernel does.  wrong = "no_mask" / "elu1" / "drop_last_slice"
-    are deliberately wrong variants for the rule's own test."""
+    the batch sums are formed per slice and added in slice order, as the kernel does; one number for every sum, or (std, [per actor
+    layer], [per critic layer]) as the plan gives each layer its own.  wrong = "no_mask" / "elu1" / "drop_last_slice" are deliberately
+    wrong variants for the rule's own test."""
     fw = forward(x, dtype)
     std, actor, critic = _chains(x, dtype)
     B = fw["mu"].shape[0]
-    per = slices or B
+    if slices is None or isinstance(slices, (int, np.integer)):
+        std_per, layer_per = int(slices or B), None
+    else:
+        std_per, layer_per = int(slices[0]), [[int(p) for p in c] for c in slices[1:]]
 
-    if wrong == "drop_last_slice" and not (slices and B > per):
+    if wrong == "drop_last_slice" and not (slices and B > max([std_per] + [p for c in layer_per or [] for p in c])):
         raise ValueError("drop_last_slice needs more than one slice")
 
-    def bsum(g, h=None):          # sum over the batch of g (or of g^T h), slice by slice
-        parts = [g[s:s + per].sum(0) if h is None else g[s:s + per].T @ h[s:s + per] for s in range(0, B, per)]
-        if wrong == "drop_last_slice":
-            parts = parts[:-1]
-        out = parts[0]
-        for p in parts[1:]:
-            out = out + p
-        return out
+    def bsum(per, g, h=None, phases=1):
+        return slice_sum(per, g, h, phases, drop_last=wrong == "drop_last_slice")
 
-    grads = [bsum(np.asarray(x["grad_sigma"]).astype(dtype))]
+    grads = [bsum(std_per, np.asarray(x["grad_sigma"]).astype(dtype))]
     g_mu = np.asarray(x["grad_mu"]).astype(dtype)
     if x["clip"] is not None and wrong != "no_mask":
         g_mu = np.where((fw["mu"] >= x["clip"]) | (fw["mu"] <= -x["clip"]), 0, g_mu).astype(dtype)
-    for layers, acts, G in ((actor, fw["acts"][0], g_mu), (critic, fw["acts"][1], np.asarray(x["grad_values"]).astype(dtype))):
+    for ci, (layers, acts, G) in enumerate(((actor, fw["acts"][0], g_mu), (critic, fw["acts"][1], np.asarray(x["grad_values"]).astype(dtype)))):
         out = []
         for li in range(len(layers) - 1, -1, -1):
-            H = acts[li]
-            out = [bsum(G, H), bsum(G)] + out
+            H, per = acts[li], layer_per[ci][li] if layer_per else std_per
+            out = [bsum(per, G, H), bsum(per, G, phases=4)] + out
             if li:
                 d = np.ones_like(H) if wrong == "elu1" else np.where(H > 0, 1, H + 1)
                 G = ((G @ layers[li][0]) * d).astype(dtype)

@@ -190,23 +190,25 @@ def rl_backward(x, dtype=np.float64, slices=None):
     return g[1:] + g[:1]
 
 
-def est_pass(x, dtype=np.float64, upstream=None):
-    """dict(loss, grads (est_names order), pred) of the estimator pass: d = (p - y) t, loss = sum d^2 / (B NL), d loss / d p = 2 d t / (B NL),
-    times `upstream` (default x["upstream"])."""
+def est_pass(x, dtype=np.float64, upstream=None, slices=None):
+    """dict(loss, grads (est_names order), pred, d) of the estimator pass: d = (p - y) t, loss = sum d^2 / (B NL), d loss / d p =
+    2 d t / (B NL), times `upstream` (default x["upstream"]).  `slices` (rows per slice, one number or one per layer): the batch sums are
+    formed per slice and added in slice order, as the kernel does."""
     layers = _pairs(x["est_params"], dtype)
     acts = tc._mlp(layers, np.asarray(x["features"]).astype(dtype), dtype)
     t, y = np.asarray(x["terminated"]).astype(dtype), np.asarray(x["labels"]).astype(dtype)
     d = (acts[-1] - y) * t
-    n = d.size
+    n, B = d.size, d.shape[0]
     up = dtype(x["upstream"] if upstream is None else upstream)
     G = (2 * d * t / n * up).astype(dtype)
     grads = []
     for li in range(len(layers) - 1, -1, -1):
         H = acts[li]
-        grads = [G.T @ H, G.sum(0)] + grads
+        per = B if slices is None else int(slices) if isinstance(slices, (int, np.integer)) else int(slices[li])
+        grads = [tc.slice_sum(per, G, H), tc.slice_sum(per, G, phases=4)] + grads
         if li:
             G = ((G @ layers[li][0]) * np.where(H > 0, 1, H + 1)).astype(dtype)
-    return dict(loss=(d * d).sum() / n, grads=grads, pred=acts[-1])
+    return dict(loss=(d * d).sum() / n, grads=grads, pred=acts[-1], d=d)
 
 
 def _mlp_t(h, ps):
