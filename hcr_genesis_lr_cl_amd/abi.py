@@ -1,4 +1,4 @@
-"""ctypes mirror of include/lgsim.h, include/lgrollout.h, include/lgsensor.h, include/lgpolicy.h, include/lgppo.h, include/lgoptim.h, include/lgtrain.h and include/lgtrainee.h (the C ABI) and the loader of the HIP library.
+"""ctypes mirror of include/lgsim.h, include/lgrollout.h, include/lgsensor.h, include/lgpolicy.h, include/lgppo.h, include/lgoptim.h, include/lgtrain.h, include/lgtrainee.h and include/lgtraints.h (the C ABI) and the loader of the HIP library.
 
 Field order and types must match the header exactly; tests/test_abi.py compiles a C
 probe that prints sizeof/offsetof for every struct and compares them with these classes.
@@ -311,6 +311,15 @@ def load_lib():
         lib.lg_train_est_backward.argtypes = [C.POINTER(LgTrainEstArgs), vp]
         for f in TRAIN_EE_EXPORTS:
             getattr(lib, f).restype = C.c_int
+    if hasattr(lib, "lg_train_ts_forward"):      # absent from libraries older than the teacher-student learner passes
+        lib.lg_train_ts_plan.argtypes = [C.POINTER(LgTrainTSArgs), C.POINTER(LgTrainTSPlan)]
+        lib.lg_train_ts_forward.argtypes = [C.POINTER(LgTrainTSArgs), vp]
+        lib.lg_train_ts_backward.argtypes = [C.POINTER(LgTrainTSArgs), vp]
+        lib.lg_train_enc_plan.argtypes = [C.POINTER(LgTrainEncArgs), C.POINTER(LgTrainTSPlan)]
+        lib.lg_train_enc_forward.argtypes = [C.POINTER(LgTrainEncArgs), vp]
+        lib.lg_train_enc_backward.argtypes = [C.POINTER(LgTrainEncArgs), vp]
+        for f in TRAIN_TS_EXPORTS:
+            getattr(lib, f).restype = C.c_int
     lib.lg_last_error.restype = C.c_char_p
     lib.lg_last_kernel.argtypes = [H]
     lib.lg_last_kernel.restype = C.c_char_p
@@ -347,6 +356,11 @@ TRAIN_EE_EXPORTS = ["lg_train_ee_plan", "lg_train_est_plan", "lg_train_ee_forwar
                     "lg_train_est_backward"]                                                  # include/lgtrainee.h
 TRAIN_EE_CHAINS, TRAIN_EE_ESTIMATOR, TRAIN_EE_ACTOR, TRAIN_EE_CRITIC, TRAIN_EE_THREADS = 3, 0, 1, 2, 256
 TRAIN_EE_TARGET_JOBS = 2048
+TRAIN_TS_EXPORTS = ["lg_train_ts_plan", "lg_train_enc_plan", "lg_train_ts_forward", "lg_train_ts_backward", "lg_train_enc_forward",
+                    "lg_train_enc_backward"]                                                  # include/lgtraints.h
+TRAIN_TS_CHAINS, TRAIN_TS_PRIVILEGE, TRAIN_TS_ACTOR, TRAIN_TS_CRITIC, TRAIN_TS_HISTORY, TRAIN_TS_RL_CHAINS = 4, 0, 1, 2, 3, 3
+TRAIN_ENC_CHAINS, TRAIN_ENC_HISTORY, TRAIN_ENC_PRIVILEGE = 2, 0, 1
+TRAIN_TS_TARGET_JOBS, TRAIN_TS_THREADS = 2048, 256
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 2048
 POLICY_MAX_RNN_LAYERS, POLICY_MAX_RNN_HIDDEN = 2, 512
 POLICY_LSTM, POLICY_GRU = 1, 2
@@ -499,6 +513,29 @@ class LgTrainEEPlan(C.Structure):
                 ("weight_jobs", i32), ("loss_tiles", i32), ("est_first_buffer", i32), ("reserved", i32),
                 ("h_off", i64 * POLICY_MAX_LAYERS * TRAIN_EE_CHAINS), ("g_off", i64 * POLICY_MAX_LAYERS * TRAIN_EE_CHAINS),
                 ("p_off", i64 * POLICY_MAX_LAYERS * TRAIN_EE_CHAINS), ("std_p_off", i64), ("cat_off", i64), ("gl_off", i64),
+                ("partial_off", i64), ("workspace_floats", i64)]
+
+
+class LgTrainTSArgs(C.Structure):
+    _fields_ = [("n_rows", i32), ("clip_on", i32), ("clip_actions", f32), ("n_obs", i32), ("chain", LgTrainChain * TRAIN_TS_RL_CHAINS),
+                ("std", C.c_void_p), ("grad_std", C.c_void_p), ("mu", C.c_void_p), ("sigma", C.c_void_p), ("values", C.c_void_p),
+                ("grad_mu", C.c_void_p), ("grad_sigma", C.c_void_p), ("grad_values", C.c_void_p),
+                ("mu_stride", i32), ("sigma_stride", i32), ("values_stride", i32),
+                ("grad_mu_stride", i32), ("grad_sigma_stride", i32), ("grad_values_stride", i32),
+                ("workspace", C.c_void_p), ("workspace_capacity", i64)]
+
+
+class LgTrainEncArgs(C.Structure):
+    _fields_ = [("n_rows", i32), ("mask_stride", i32), ("reserved", i32 * 2), ("chain", LgTrainChain * TRAIN_ENC_CHAINS),
+                ("mask", C.c_void_p), ("loss", C.c_void_p), ("upstream", C.c_void_p), ("workspace", C.c_void_p), ("workspace_capacity", i64)]
+
+
+class LgTrainTSPlan(C.Structure):
+    _fields_ = [("row_tile", i32), ("lds_bytes", i32), ("slices", i32 * POLICY_MAX_LAYERS * TRAIN_TS_CHAINS),
+                ("slice_rows", i32 * POLICY_MAX_LAYERS * TRAIN_TS_CHAINS), ("std_slices", i32), ("std_slice_rows", i32),
+                ("weight_jobs", i32), ("loss_tiles", i32), ("enc_first_buffer", i32), ("reserved", i32),
+                ("h_off", i64 * POLICY_MAX_LAYERS * TRAIN_TS_CHAINS), ("g_off", i64 * POLICY_MAX_LAYERS * TRAIN_TS_CHAINS),
+                ("p_off", i64 * POLICY_MAX_LAYERS * TRAIN_TS_CHAINS), ("std_p_off", i64), ("cat_off", i64), ("gl_off", i64), ("y_off", i64),
                 ("partial_off", i64), ("workspace_floats", i64)]
 
 

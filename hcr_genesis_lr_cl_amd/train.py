@@ -15,7 +15,8 @@ them on every call.  The gradient that reaches mu through sigma = mu * 0 + std i
 gradient for the observations and no double backward.  There is no CPU path: the module lives on a HIP device.
 
 FusedTrainPassEE (below; include/lgtrainee.h, csrc/lg_train_ee.hip) is the same for ActorCriticEE under PPO_EE: the RL pass and the
-supervised estimator pass."""
+supervised estimator pass.  FusedTrainPassTS (include/lgtraints.h, csrc/lg_train_ts.hip) is the same for ActorCriticTS under PPO_TS: the RL
+pass, whose gradient reaches the privilege encoder through the latent, and the supervised history-encoder pass."""
 from __future__ import annotations
 
 import ctypes as C
@@ -558,3 +559,281 @@ class FusedTrainPassEE:
     def estimator_loss(self, estimator_features, estimator_labels, terminated):
         """mse_loss(estimator(features) * terminated, labels * terminated) as a 0-dim tensor with autograd.  Two launches."""
         return _EstLoss.apply(self, estimator_features, estimator_labels, terminated, *self.spec.estimator_parameters())
+
+
+# ---- the teacher-student family (include/lgtraints.h, csrc/lg_train_ts.hip) -------------------------------------------------------------------
+_TS_FOREIGN = (("estimator", "ActorCriticEE"), ("vae", "ActorCriticDreamWaQ"), ("memory_a", "ActorCriticRecurrent"), ("memory_c", "ActorCriticRecurrent"))
+
+
+class TrainSpecTS:
+    """ActorCriticTS as the kernels take it: the privilege encoder, the actor (whose input is [obs | latent]), the critic and the history
+    encoder."""
+
+    def __init__(self, privilege_encoder, actor, critic, history_encoder, std):
+        self.privilege_encoder, self.actor, self.critic, self.history_encoder, self.std = privilege_encoder, actor, critic, history_encoder, std
+        self.chains = (privilege_encoder, actor, critic, history_encoder)          # abi.TRAIN_TS_* order
+        self.num_actions, self.clip_actions = actor.widths[-1], actor.clip
+        self.num_latent = privilege_encoder.widths[-1]
+        self.num_obs = actor.widths[0] - self.num_latent
+
+    def rl_parameters(self):
+        """Actor, critic, privilege encoder, then std: the order of PPO_TS.rl_parameters and of the RL pass's gradients."""
+        return [p for c in (self.actor, self.critic, self.privilege_encoder) for l in c.linears for p in (l.weight, l.bias)] + [self.std]
+
+    def rl_parameter_names(self):
+        return [f"{c.name}.{i}.{n}" for c in (self.actor, self.critic, self.privilege_encoder) for i in range(len(c.linears))
+                for n in ("weight", "bias")] + ["std"]
+
+    def encoder_parameters(self):
+        return [p for l in self.history_encoder.linears for p in (l.weight, l.bias)]
+
+    def encoder_parameter_names(self):
+        return [f"history_encoder.{i}.{n}" for i in range(len(self.history_encoder.linears)) for n in ("weight", "bias")]
+
+
+def describe_ts(actor_critic, device=None):
+    """ActorCriticTS as the kernels take it (duck-typed: .privilege_encoder, .history_encoder, .actor, .critic, .std), by the rules of
+    `describe` for each of the four chains: a Conv1d / Flatten "TCN" history encoder is refused by its layer's name.  Refusals are
+    ValueErrors that name the layer or the member."""
+    for need in ("privilege_encoder", "history_encoder"):
+        if getattr(actor_critic, need, None) is None:
+            raise ValueError(f"FusedTrainPassTS: the module has no .{need}; ActorCriticTS has a privilege encoder and a history encoder")
+    for attr, family in _TS_FOREIGN:
+        if getattr(actor_critic, attr, None) is not None:
+            raise ValueError(f"FusedTrainPassTS: the module has .{attr} ({family}) beside its encoders; only ActorCriticTS is built")
+    if getattr(actor_critic, "is_recurrent", False):
+        raise ValueError("FusedTrainPassTS: the module is recurrent (is_recurrent); the recurrent update keeps the torch path")
+    for need in ("actor", "critic", "std"):
+        if getattr(actor_critic, need, None) is None:
+            raise ValueError(f"FusedTrainPassTS: the module has no .{need}")
+
+    def chain(name, clip):
+        try:
+            return _describe_chain(name, getattr(actor_critic, name), device, clip)
+        except ValueError as e:
+            raise ValueError(str(e).replace("FusedTrainPass:", "FusedTrainPassTS:", 1)) from None
+    priv, hist = chain("privilege_encoder", False), chain("history_encoder", False)
+    actor, critic = chain("actor", True), chain("critic", False)
+    if hist.widths[-1] != priv.widths[-1]:
+        raise ValueError(f"FusedTrainPassTS: history_encoder ends at {hist.widths[-1]} columns, privilege_encoder at {priv.widths[-1]}: the "
+                         f"latent widths differ")
+    if actor.widths[0] <= priv.widths[-1]:
+        raise ValueError(f"FusedTrainPassTS: actor[0] takes {actor.widths[0]} inputs, but [obs | latent] has O + {priv.widths[-1]} columns with O >= 1")
+    std = actor_critic.std
+    _check_param(std, "std", device)
+    if tuple(std.shape) != (actor.widths[-1],):
+        raise ValueError(f"FusedTrainPassTS: std has shape {tuple(std.shape)}, the actor has {actor.widths[-1]} outputs")
+    return TrainSpecTS(priv, actor, critic, hist, std)
+
+
+def _rows_ts(t, width, what, n=None, device=None):
+    try:
+        return _rows(t, width, what, n, device)
+    except ValueError as e:
+        raise ValueError(str(e).replace("FusedTrainPass:", "FusedTrainPassTS:", 1)) from None
+
+
+def ts_args(spec, obs, privileged_obs, critic_obs, mu, sigma, values, workspace, grads=None, grad_mu=None, grad_sigma=None, grad_values=None,
+            device=None):
+    """LgTrainTSArgs of one call of the RL pass.  `grads` (backward): the tensors that take the gradients, in spec.rl_parameters() order
+    (actor, critic, privilege encoder, std)."""
+    a = abi.LgTrainTSArgs()
+    if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or obs.shape[0] < 1:
+        raise ValueError(f"FusedTrainPassTS: obs must be a (B, O) float32 tensor with B >= 1 and O = actor[0].in_features - {spec.num_latent}")
+    n = int(obs.shape[0])
+    if obs.shape[1] + spec.num_latent != spec.actor.widths[0]:
+        raise ValueError(f"FusedTrainPassTS: actor[0] takes {spec.actor.widths[0]} inputs, but [obs | latent] has {obs.shape[1]} + "
+                         f"{spec.num_latent} columns")
+    a.n_rows, a.n_obs = n, spec.num_obs
+    a.clip_on, a.clip_actions = (1, spec.clip_actions) if spec.clip_actions is not None else (0, 0.0)
+    na, nc = 2 * len(spec.actor.linears), 2 * len(spec.critic.linears)
+    pri, act, cri = a.chain[abi.TRAIN_TS_PRIVILEGE], a.chain[abi.TRAIN_TS_ACTOR], a.chain[abi.TRAIN_TS_CRITIC]
+    act.input, act.in_stride = _rows_ts(obs, spec.num_obs, "obs", n, device)
+    pri.input, pri.in_stride = _rows_ts(privileged_obs, spec.privilege_encoder.widths[0], "privileged_obs", n, device)
+    cri.input, cri.in_stride = _rows_ts(critic_obs, spec.critic.widths[0], "critic_obs", n, device)
+    _fill_chain(act, spec.actor, device, None if grads is None else grads[:na])
+    _fill_chain(cri, spec.critic, device, None if grads is None else grads[na:na + nc])
+    _fill_chain(pri, spec.privilege_encoder, device, None if grads is None else grads[na + nc:-1])
+    A, V = spec.num_actions, spec.critic.widths[-1]
+    _check_param(spec.std, "std", device)
+    a.std = spec.std.data_ptr()
+    a.mu, a.mu_stride = _rows_ts(mu, A, "mu", n, device)
+    a.sigma, a.sigma_stride = _rows_ts(sigma, A, "sigma", n, device)
+    a.values, a.values_stride = _rows_ts(values, V, "values", n, device)
+    if grads is not None:
+        a.grad_std = grads[-1].data_ptr()
+        a.grad_mu, a.grad_mu_stride = _rows_ts(grad_mu, A, "grad_mu", n, device)
+        a.grad_sigma, a.grad_sigma_stride = _rows_ts(grad_sigma, A, "grad_sigma", n, device)
+        a.grad_values, a.grad_values_stride = _rows_ts(grad_values, V, "grad_values", n, device)
+    _bind_workspace(a, workspace, device)
+    return a
+
+
+def enc_args(spec, obs_history, privileged_obs, terminated, loss, workspace, grads=None, upstream=None, device=None):
+    """LgTrainEncArgs of one call of the encoder pass.  `grads` (backward): in spec.encoder_parameters() order.  The privilege encoder's
+    gradient pointers stay null: the pass has no use for them."""
+    a = abi.LgTrainEncArgs()
+    if not isinstance(obs_history, torch.Tensor) or obs_history.dim() != 2 or obs_history.shape[0] < 1:
+        raise ValueError(f"FusedTrainPassTS: obs_history must be a (B, {spec.history_encoder.widths[0]}) float32 tensor with B >= 1")
+    n = int(obs_history.shape[0])
+    a.n_rows = n
+    his, pri = a.chain[abi.TRAIN_ENC_HISTORY], a.chain[abi.TRAIN_ENC_PRIVILEGE]
+    his.input, his.in_stride = _rows_ts(obs_history, spec.history_encoder.widths[0], "obs_history", n, device)
+    pri.input, pri.in_stride = _rows_ts(privileged_obs, spec.privilege_encoder.widths[0], "privileged_obs", n, device)
+    _fill_chain(his, spec.history_encoder, device, grads)
+    _fill_chain(pri, spec.privilege_encoder, device)
+    a.mask, a.mask_stride = _rows_ts(terminated, 1, "terminated", n, device)
+    if loss is not None:
+        a.loss = _scalar(loss, "the loss", device)
+    if upstream is not None:
+        a.upstream = _scalar(upstream, "the upstream gradient", device)
+    _bind_workspace(a, workspace, device)
+    return a
+
+
+_PLANS_TS = {}
+
+
+def plan_ts(n_rows, privilege_widths, actor_widths, critic_widths):
+    """LgTrainTSPlan of the RL pass (lg_train_ts_plan) for chains of these widths; O is actor_widths[0] less the latent width."""
+    key = (int(n_rows),) + tuple(tuple(int(x) for x in w) for w in (privilege_widths, actor_widths, critic_widths))
+    if key not in _PLANS_TS:
+        lib, a, p = abi.load_lib(), abi.LgTrainTSArgs(), abi.LgTrainTSPlan()
+        a.n_rows, a.n_obs = key[0], key[2][0] - key[1][-1]
+        for ci, w in enumerate(key[1:]):
+            _widths_into(a.chain[ci], w)
+        abi.check(lib.lg_train_ts_plan(C.byref(a), C.byref(p)), lib)
+        _PLANS_TS[key] = p
+    return _PLANS_TS[key]
+
+
+def plan_enc(n_rows, history_widths, privilege_widths):
+    """LgTrainTSPlan of the encoder pass (lg_train_enc_plan)."""
+    key = (int(n_rows), "enc", tuple(int(x) for x in history_widths), tuple(int(x) for x in privilege_widths))
+    if key not in _PLANS_TS:
+        lib, a, p = abi.load_lib(), abi.LgTrainEncArgs(), abi.LgTrainTSPlan()
+        a.n_rows = key[0]
+        _widths_into(a.chain[abi.TRAIN_ENC_HISTORY], key[2])
+        _widths_into(a.chain[abi.TRAIN_ENC_PRIVILEGE], key[3])
+        abi.check(lib.lg_train_enc_plan(C.byref(a), C.byref(p)), lib)
+        _PLANS_TS[key] = p
+    return _PLANS_TS[key]
+
+
+class _PassTS(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tp, obs, privileged_obs, critic_obs, *params):
+        spec, device, n = tp.spec, tp.device, int(obs.shape[0])
+        mu = torch.empty((n, spec.num_actions), dtype=torch.float32, device=device)
+        sigma = torch.empty_like(mu)
+        values = torch.empty((n, spec.critic.widths[-1]), dtype=torch.float32, device=device)
+        args = ts_args(spec, obs, privileged_obs, critic_obs, mu, sigma, values, None, device=device)      # every refusal before anything grows
+        _bind_workspace(args, tp._rl_workspace_for(n), device)
+        _call("lg_train_ts_forward", args, device)
+        tp._rl_calls += 1
+        ctx.tp, ctx.call, ctx.inputs = tp, tp._rl_calls, (obs, privileged_obs, critic_obs)
+        ctx.save_for_backward(mu, sigma, values)
+        return mu, sigma, values
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_mu, grad_sigma, grad_values):
+        tp = ctx.tp
+        if tp._rl_calls != ctx.call:
+            raise RuntimeError(f"FusedTrainPassTS: backward of RL forward call {ctx.call}, but RL forward call {tp._rl_calls} has overwritten "
+                               f"its activations in the workspace since; run each backward before the next forward of the same pass")
+        mu, sigma, values = ctx.saved_tensors
+        spec, device = tp.spec, tp.device
+        grads = [torch.empty_like(p) for p in spec.rl_parameters()]
+        gm, gs, gv = _grad_rows(grad_mu, mu), _grad_rows(grad_sigma, sigma), _grad_rows(grad_values, values)
+        args = ts_args(spec, *ctx.inputs, mu, sigma, values, tp._rl_workspace, grads, gm, gs, gv, device=device)
+        _call("lg_train_ts_backward", args, device)
+        return (None, None, None, None) + tuple(grads)     # nothing for the history encoder's parameters: they are no input of this pass
+
+
+class _EncLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, tp, obs_history, privileged_obs, terminated, *params):
+        spec, device, n = tp.spec, tp.device, int(obs_history.shape[0])
+        loss = torch.empty((), dtype=torch.float32, device=device)
+        args = enc_args(spec, obs_history, privileged_obs, terminated, loss, None, device=device)
+        _bind_workspace(args, tp._enc_workspace_for(n), device)
+        _call("lg_train_enc_forward", args, device)
+        tp._enc_calls += 1
+        ctx.tp, ctx.call, ctx.inputs = tp, tp._enc_calls, (obs_history, privileged_obs, terminated)
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        tp = ctx.tp
+        if tp._enc_calls != ctx.call:
+            raise RuntimeError(f"FusedTrainPassTS: backward of encoder forward call {ctx.call}, but encoder forward call {tp._enc_calls} has "
+                               f"overwritten its activations in the workspace since; run each backward before the next forward of the same pass")
+        spec, device = tp.spec, tp.device
+        up = grad_loss.to(torch.float32).reshape(1).contiguous()        # stays on the device: the kernel reads it there
+        grads = [torch.empty_like(p) for p in spec.encoder_parameters()]
+        args = enc_args(spec, *ctx.inputs, None, tp._enc_workspace, grads, up, device=device)
+        _call("lg_train_enc_backward", args, device)
+        return (None, None, None, None) + tuple(grads)     # the privilege encoder's parameters are no input: the target carries no gradient
+
+
+class FusedTrainPassTS:
+    """The two network passes of PPO_TS.update() on an ActorCriticTS (include/lgtraints.h):
+
+        tp = FusedTrainPassTS(actor_critic_ts)
+        mu, sigma, values = tp(obs, privileged_obs, critic_obs)                   # RL step: one launch; backward three
+        enc_loss = tp.encoder_loss(obs_history, privileged_obs, terminated)       # encoder step: two launches; backward three
+
+    Optimise tp.rl_parameters() (actor, critic, privilege encoder, std: the reference's order) and tp.encoder_parameters() (the history
+    encoder) apart.  The RL gradient reaches the privilege encoder through the latent columns of the actor's input; the history encoder
+    takes no part in the RL pass and its .grad is left as it was.  The encoder pass takes its targets from the privilege encoder with no
+    gradient: that encoder's .grad is left as it was.  Each pass has its own workspace and call counter: a forward of one does not
+    invalidate a pending backward of the other; within a pass a backward whose forward has been overwritten raises.  The actor may end in a
+    Hardtanh or not (ActorCriticTS has none).
+
+    This is PPO_TS's update only.  ActorCriticCTS has the same members, but PPO_CTS updates two env groups with other losses: it keeps the
+    torch path, and so does a "TCN" (Conv1d) history encoder, which is refused by layer name."""
+
+    def __init__(self, actor_critic):
+        dev = getattr(getattr(actor_critic, "std", None), "device", None)
+        if isinstance(dev, torch.device) and dev.type != "cuda":
+            raise ValueError(f"FusedTrainPassTS: the module is on {dev}, not on a HIP device (there is no CPU path)")
+        self.spec = describe_ts(actor_critic, dev)
+        self.device = dev
+        self._rl_workspace = self._enc_workspace = None
+        self._rl_calls = self._enc_calls = 0
+
+    def rl_parameters(self):
+        return self.spec.rl_parameters()
+
+    def encoder_parameters(self):
+        return self.spec.encoder_parameters()
+
+    def plan(self, n_rows):
+        s = self.spec
+        return plan_ts(n_rows, s.privilege_encoder.widths, s.actor.widths, s.critic.widths)
+
+    def encoder_plan(self, n_rows):
+        return plan_enc(n_rows, self.spec.history_encoder.widths, self.spec.privilege_encoder.widths)
+
+    def _rl_workspace_for(self, n):
+        need = int(self.plan(n).workspace_floats)
+        if self._rl_workspace is None or self._rl_workspace.numel() < need:
+            self._rl_workspace = torch.empty(need, dtype=torch.float32, device=self.device)
+        return self._rl_workspace
+
+    def _enc_workspace_for(self, n):
+        need = int(self.encoder_plan(n).workspace_floats)
+        if self._enc_workspace is None or self._enc_workspace.numel() < need:
+            self._enc_workspace = torch.empty(need, dtype=torch.float32, device=self.device)
+        return self._enc_workspace
+
+    def __call__(self, obs, privileged_obs, critic_obs):
+        """(mu, sigma, values) of the mini-batch: (B, A), (B, A), (B, 1).  One launch on the current stream."""
+        return _PassTS.apply(self, obs, privileged_obs, critic_obs, *self.spec.rl_parameters())
+
+    def encoder_loss(self, obs_history, privileged_obs, terminated):
+        """mse_loss(history_encoder(obs_history) * terminated, privilege_encoder(privileged_obs).detach() * terminated) as a 0-dim tensor
+        with autograd.  Two launches."""
+        return _EncLoss.apply(self, obs_history, privileged_obs, terminated, *self.spec.encoder_parameters())

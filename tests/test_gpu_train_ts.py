@@ -1,0 +1,465 @@
+"""The teacher-student learner passes on the GPU (hcr_genesis_lr_cl_amd/train.py's FusedTrainPassTS, csrc/lg_train_ts.hip) against the
+float64 restatement of tests/train_ts_cases.py under the project's parity rule, and their conventions: the reference's whole PPO_TS.update()
+end to end (6 RL steps, 12 encoder steps; FusedTrainPassTS, FusedPPOLoss, two FusedAdams), bit-identical repeats, one RL step plus one
+encoder step as a HIP graph, strided views, weights changed in place, the stale-forward refusal per pass, the history encoder's .grad left
+alone by the RL backward and the privilege encoder's by the encoder backward, the fully masked batch, the NaN row (through the latent into
+the privilege encoder's gradients) and the saturated Hardtanh column that passes nothing on to the actor or the encoder."""
+import copy
+import os
+
+import numpy as np
+import pytest
+import torch
+import torch.nn as nn
+
+from hcr_genesis_lr_cl_amd import optim, ppo_loss, train
+from tests import optim_cases as oc
+from tests import train_ts_cases as sc
+
+pytestmark = pytest.mark.gpu
+
+DEV = torch.device("cuda")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIXTURE = os.path.join(ROOT, "tests", "golden", "ppo_ts_train.npz")
+RATIOS = []
+COTANGENTS = ("grad_mu", "grad_sigma", "grad_values")
+
+
+def dev(a):
+    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
+
+
+def host(t):
+    return t.detach().cpu().numpy()
+
+
+def run(x, m=None, tp=None):
+    """Both passes once on a fresh module: the RL forward and the backward of the case's three cotangents, then the encoder loss and its
+    backward under the case's upstream factor.  (name -> numpy array, module, pass).  Asserts on the way that the RL backward gave the
+    history encoder nothing and that the encoder backward left the privilege encoder's gradients bit for bit."""
+    m = m if m is not None else sc.Module(x, DEV)
+    tp = tp if tp is not None else train.FusedTrainPassTS(m)
+    for p in m.parameters():
+        p.grad = None
+    mu, sigma, values = tp(dev(x["obs"]), dev(x["privileged_obs"]), dev(x["critic_obs"]))
+    torch.autograd.backward([mu, sigma, values], [dev(x[k]) for k in COTANGENTS])
+    assert all(p.grad is None for p in m.encoder_parameters())                # the RL pass gives the history encoder nothing
+    rl_grads = [host(p.grad).copy() for p in m.rl_parameters()]
+    loss = tp.encoder_loss(dev(x["obs_history"]), dev(x["privileged_obs"]), dev(x["terminated"]))
+    (loss * float(x["upstream"])).backward()
+    torch.cuda.synchronize()
+    for p, g in zip(m.rl_parameters(), rl_grads):                             # the encoder pass gives the RL parameters nothing
+        assert np.array_equal(host(p.grad).view(np.uint32), g.view(np.uint32))
+    got = sc.named(x, dict(mu=host(mu), sigma=host(sigma), values=host(values)), rl_grads, host(loss), [host(p.grad) for p in m.encoder_parameters()])
+    return got, m, tp
+
+
+def same_bits(a, b):
+    return set(a) == set(b) and all(np.array_equal(np.asarray(a[k], np.float32).view(np.uint32), np.asarray(b[k], np.float32).view(np.uint32)) for k in a)
+
+
+# ---- parity -----------------------------------------------------------------------------------------------------------------------------------
+PARITY_CASES = list(sc.CASES) + [f"{net}_ragged" for net in sc.RAGGED_SLICE_NETS]
+
+
+def case_inputs(name):
+    if name.endswith("_ragged"):                                      # the smallest batch either plan slices raggedly for that net
+        net = name[:-len("_ragged")]
+        b = sc.smallest_ragged_b(net)
+        assert b <= 257
+        return sc.make_inputs(dict(net=net, B=b, seed=1200 + len(net)))
+    return sc.make_inputs(name)
+
+
+@pytest.mark.parametrize("name", PARITY_CASES)
+def test_parity_on_the_table(name):
+    x = case_inputs(name)
+    got, _, _ = run(x)
+    ref64, ref32 = sc.references(x)
+    sc.check_parity(got, ref64, ref32, name, RATIOS)
+
+
+# ---- the whole update -------------------------------------------------------------------------------------------------------------------------
+def _init_inputs(fx):
+    return dict(sc.fixture_inputs(fx, {k: np.asarray(v, np.float32) for k, v in fx["init"].items()}))
+
+
+def _torch_update(fx, dtype):
+    """The reference's PPO_TS.update() on the fixture's columns (rounded to float32 first) in torch ops of `dtype` on the CPU.  Returns
+    (per step, RL steps then encoder steps, the parameters by name as float64 numpy; the RL rates)."""
+    cfg = fx["cfg"]
+    m = sc.Module(_init_inputs(fx), dtype=dtype)
+    t = lambda a: torch.from_numpy(np.asarray(a, np.float32)).to(dtype)
+    betas = (cfg["beta1"], cfg["beta2"])
+    opt = torch.optim.Adam(m.rl_parameters(), lr=cfg["lr0"], betas=betas, eps=cfg["eps"])
+    enc_opt = torch.optim.Adam(m.encoder_parameters(), lr=cfg["encoder_lr"], betas=betas, eps=cfg["eps"])
+    snap = lambda: {n: p.detach().double().numpy().copy() for n, p in m.named_parameters()}
+    lr, lrs, out, clip = cfg["lr0"], [], [], cfg["clip_param"]
+    for s in range(cfg["steps"]):
+        c = {k: t(fx[k][s]) for k in sc.FIXTURE_COLUMNS}
+        mu, sigma, value = m(c["obs"], c["privileged_obs"], c["critic_obs"])
+        logp = (-(c["actions"] - mu) ** 2 / (2 * sigma ** 2) - sigma.log() - 0.9189385332046727).sum(-1)
+        with torch.no_grad():
+            kl = torch.sum(torch.log(sigma / c["old_sigma"] + 1.e-5) + (c["old_sigma"] ** 2 + (c["old_mu"] - mu) ** 2) / (2.0 * sigma ** 2) - 0.5,
+                           dim=-1).mean()
+        lr = ppo_loss.adjust_learning_rate(kl, lr, cfg["desired_kl"])
+        for group in opt.param_groups:
+            group["lr"] = lr
+        ratio, adv = torch.exp(logp - c["old_log_prob"].squeeze(-1)), c["advantages"].squeeze(-1)
+        surrogate = torch.max(-adv * ratio, -adv * torch.clamp(ratio, 1.0 - clip, 1.0 + clip)).mean()
+        vc = c["target_values"] + (value - c["target_values"]).clamp(-clip, clip)
+        value_loss = torch.max((value - c["returns"]).pow(2), (vc - c["returns"]).pow(2)).mean()
+        entropy = (1.4189385332046727 + sigma.log()).sum(-1).mean()
+        loss = surrogate + cfg["value_loss_coef"] * value_loss - cfg["entropy_coef"] * entropy
+        opt.zero_grad()
+        loss.backward()
+        nn.utils.clip_grad_norm_(m.rl_parameters(), cfg["max_grad_norm"])
+        opt.step()
+        lrs.append(lr)
+        out.append(snap())
+    for s in range(cfg["enc_steps"]):
+        loss = m.encoder_loss(t(fx["enc_history"][s]), t(fx["enc_privileged"][s]), t(fx["enc_terminated"][s]))
+        enc_opt.zero_grad()
+        loss.backward()
+        nn.utils.clip_grad_norm_(m.encoder_parameters(), cfg["max_grad_norm"])
+        enc_opt.step()
+        out.append(snap())
+    return out, lrs
+
+
+class _Learner:
+    """FusedTrainPassTS + FusedPPOLoss + two FusedAdams on a module: the fused PPO_TS mini-batch steps."""
+
+    def __init__(self, m, cfg):
+        self.tp = train.FusedTrainPassTS(m)
+        self.loss_fn = ppo_loss.FusedPPOLoss(clip_param=cfg["clip_param"], value_loss_coef=cfg["value_loss_coef"], entropy_coef=cfg["entropy_coef"])
+        betas = (cfg["beta1"], cfg["beta2"])
+        self.rl_opt = optim.FusedAdam(list(zip(self.tp.spec.rl_parameter_names(), self.tp.rl_parameters())), lr=cfg["lr0"], betas=betas, eps=cfg["eps"],
+                                      max_grad_norm=cfg["max_grad_norm"], desired_kl=cfg["desired_kl"])
+        self.enc_opt = optim.FusedAdam(list(zip(self.tp.spec.encoder_parameter_names(), self.tp.encoder_parameters())), lr=cfg["encoder_lr"],
+                                       betas=betas, eps=cfg["eps"], max_grad_norm=cfg["max_grad_norm"])
+
+    def rl_step(self, c):
+        mu, sigma, values = self.tp(c["obs"], c["privileged_obs"], c["critic_obs"])
+        out = self.loss_fn(mu, sigma, values, c["actions"], c["old_log_prob"], c["advantages"], c["returns"], c["target_values"], c["old_mu"], c["old_sigma"])
+        self.rl_opt.zero_grad()
+        out.loss.backward()
+        self.rl_opt.step(kl_mean=out.kl_mean)
+        return out
+
+    def enc_step(self, e):
+        loss = self.tp.encoder_loss(e["enc_history"], e["enc_privileged"], e["enc_terminated"])
+        self.enc_opt.zero_grad()
+        loss.backward()
+        self.enc_opt.step()
+        return loss
+
+
+def _rl_batches(fx):
+    return [{k: dev(fx[k][s]) for k in sc.FIXTURE_COLUMNS} for s in range(fx["cfg"]["steps"])]
+
+
+def _enc_batches(fx):
+    return [{k: dev(fx[k][s]) for k in sc.ENC_COLUMNS} for s in range(fx["cfg"]["enc_steps"])]
+
+
+def test_fixture_update_end_to_end():
+    """The reference's PPO_TS.update(), 6 RL steps then 12 encoder steps, through FusedTrainPassTS, FusedPPOLoss and two FusedAdams: the
+    learning rates are the fixture's and every parameter after each of the 18 steps lies within the parity rule of the float64 run of the
+    same torch code on the float32 inputs (its float32 side: that code in float32 on the CPU); that float64 run is the fixture up to the
+    rounding of its inputs."""
+    fx = sc.load_fixture(FIXTURE)
+    cfg = fx["cfg"]
+    ref64, lrs64 = _torch_update(fx, torch.float64)
+    ref32, lrs32 = _torch_update(fx, torch.float32)
+    assert lrs64 == lrs32 == [float(v) for v in fx["lr"]]
+    assert max(np.abs(ref64[-1][n] - fx["enc_params"][-1][n]).max() for n in fx["names"]) < 1e-5
+    assert max(np.abs(ref64[cfg["steps"] - 1][n] - fx["params"][-1][n]).max() for n in fx["names"]) < 1e-5
+    m = sc.Module(_init_inputs(fx), DEV)
+    learner = _Learner(m, cfg)
+    rl, enc = _rl_batches(fx), _enc_batches(fx)
+    for s in range(cfg["steps"] + cfg["enc_steps"]):
+        if s < cfg["steps"]:
+            learner.rl_step(rl[s])
+            assert learner.rl_opt.lr == float(fx["lr"][s]), (s, learner.rl_opt.lr, fx["lr"][s])
+        else:
+            loss = learner.enc_step(enc[s - cfg["steps"]])
+            assert abs(float(loss.detach()) - fx["enc_loss"][s - cfg["steps"]]) < 1e-4
+        got = {n: host(p) for n, p in m.named_parameters()}
+        worst, bad = 0.0, []
+        for name in fx["names"]:
+            r64, r32 = ref64[s][name], ref32[s][name]
+            err, bound = oc.max_err(got[name], r64), oc.parity_bound(oc.max_err(r32, r64), r64)
+            worst = max(worst, err / (bound / oc.PARITY_FACTOR))
+            if not err <= bound:
+                bad.append((name, err, bound))
+        print(f"fixture step {s}: worst parameter ratio {worst:.3f} (allowed {oc.PARITY_FACTOR:g})")
+        RATIOS.append((f"fixture step {s}", dict(parameters=worst)))
+        assert not bad, (s, bad)
+    assert learner.rl_opt.step_count == cfg["steps"] and learner.enc_opt.step_count == cfg["enc_steps"]
+
+
+def test_captured_steps_replay_like_eager_steps():
+    """One RL step plus one encoder step captured on one stream as a HIP graph and replayed three times with the mini-batches rewritten in
+    place in between: every parameter, the rate and the step counts are those of three eager pairs of steps, bit for bit."""
+    fx = sc.load_fixture(FIXTURE)
+    cfg = fx["cfg"]
+    rl, enc = _rl_batches(fx)[:3], _enc_batches(fx)[:3]
+    x = _init_inputs(fx)
+    eager = sc.Module(x, DEV)
+    le = _Learner(eager, cfg)
+    for c, e in zip(rl, enc):
+        le.rl_step(c)
+        le.enc_step(e)
+    torch.cuda.synchronize()
+
+    m = sc.Module(x, DEV)
+    static = {k: torch.zeros_like(v) for k, v in {**rl[0], **enc[0]}.items()}
+    stream = torch.cuda.Stream()
+    stream.wait_stream(torch.cuda.current_stream())
+    with torch.cuda.stream(stream):                                   # warm-up on the side stream, on a module of its own
+        lw = _Learner(copy.deepcopy(m), cfg)
+        lw.rl_step(rl[0])
+        lw.enc_step(enc[0])
+    torch.cuda.current_stream().wait_stream(stream)
+    torch.cuda.synchronize()
+    lg = _Learner(m, cfg)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph, stream=stream):
+        lg.rl_step(static)
+        lg.enc_step(static)
+    torch.cuda.synchronize()
+    assert lg.rl_opt.step_count == 0 and lg.enc_opt.step_count == 0   # capturing runs nothing
+    for c, e in zip(rl, enc):
+        for k, v in {**c, **e}.items():
+            static[k].copy_(v)
+        graph.replay()
+    torch.cuda.synchronize()
+    assert lg.rl_opt.step_count == 3 and lg.enc_opt.step_count == 3 and lg.rl_opt.lr == le.rl_opt.lr
+    for (n, a), b in zip(m.named_parameters(), eager.parameters()):
+        assert np.array_equal(host(a).view(np.uint32), host(b).view(np.uint32)), n
+
+
+# ---- determinism, addressing, state -----------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("name", ["fixture_b257", "go2_ts_b257"])
+def test_repeats_are_bit_identical(name):
+    x = sc.make_inputs(name)
+    a, m, tp = run(x)
+    b, _, _ = run(x, m, tp)                                           # the same pass again: its workspaces are reused
+    c, _, _ = run(x)                                                  # a fresh module and pass
+    assert same_bits(a, b) and same_bits(a, c)
+
+
+def test_strided_views_of_every_matrix_leave_the_gaps_untouched():
+    """The C ABI through train.ts_args / enc_args on column slices of wider matrices: the same bits as the contiguous call, and every gap
+    column keeps its fill."""
+    x = sc.make_inputs("fixture_b33")
+    x["upstream"] = np.float32(1.0)
+    clean, _, _ = run(x)
+    m = sc.Module(x, DEV)
+    D = m.std.device
+    spec = train.describe_ts(m, D)
+    f = sc.NETS["fixture"]
+    B, FILL = 33, 7.25
+    wide = {k: torch.full((B, w), FILL, device=DEV) for k, w in (("in", 48), ("out", 16), ("grad", 19))}
+    obs, pobs, cobs, hist, term = wide["in"][:, 1:8], wide["in"][:, 10:15], wide["in"][:, 17:26], wide["in"][:, 29:43], wide["in"][:, 45:46]
+    mu, sigma, values = wide["out"][:, 1:4], wide["out"][:, 6:9], wide["out"][:, 13:14]
+    gm, gs, gv = wide["grad"][:, 2:5], wide["grad"][:, 9:12], wide["grad"][:, 17:18]
+    for view, k in ((obs, "obs"), (pobs, "privileged_obs"), (cobs, "critic_obs"), (hist, "obs_history"), (term, "terminated"), (gm, "grad_mu"),
+                    (gs, "grad_sigma"), (gv, "grad_values")):
+        view.copy_(dev(x[k]))
+    before = {k: host(v).copy() for k, v in wide.items()}
+    ws = torch.empty(int(train.plan_ts(B, *f[:3]).workspace_floats), device=DEV)
+    train._call("lg_train_ts_forward", train.ts_args(spec, obs, pobs, cobs, mu, sigma, values, ws, device=D), D)
+    rl_grads = [torch.full_like(p, FILL) for p in spec.rl_parameters()]
+    a = train.ts_args(spec, obs, pobs, cobs, mu, sigma, values, ws, rl_grads, gm, gs, gv, device=D)
+    assert (a.chain[0].in_stride, a.chain[1].in_stride, a.chain[2].in_stride, a.mu_stride, a.grad_sigma_stride) == (48, 48, 48, 16, 19)
+    train._call("lg_train_ts_backward", a, D)
+    ews = torch.empty(int(train.plan_enc(B, f[3], f[0]).workspace_floats), device=DEV)
+    loss, up = torch.full((), FILL, device=DEV), torch.ones(1, device=DEV)
+    train._call("lg_train_enc_forward", train.enc_args(spec, hist, pobs, term, loss, ews, device=D), D)
+    enc_grads = [torch.full_like(p, FILL) for p in spec.encoder_parameters()]
+    e = train.enc_args(spec, hist, pobs, term, None, ews, enc_grads, up, device=D)
+    assert (e.chain[0].in_stride, e.chain[1].in_stride, e.mask_stride) == (48, 48, 48)
+    train._call("lg_train_enc_backward", e, D)
+    torch.cuda.synchronize()
+    got = sc.named(x, dict(mu=host(mu), sigma=host(sigma), values=host(values)), [host(g) for g in rl_grads], host(loss), [host(g) for g in enc_grads])
+    assert same_bits(got, clean)
+    after = {k: host(v) for k, v in wide.items()}
+    assert np.array_equal(after["in"], before["in"]) and np.array_equal(after["grad"], before["grad"])
+    gaps = np.ones(16, bool)
+    gaps[[1, 2, 3, 6, 7, 8, 13]] = False
+    assert (after["out"][:, gaps] == FILL).all()
+
+
+def test_weights_changed_in_place_are_seen():
+    x = sc.make_inputs("fixture_b33")
+    _, m, tp = run(x)
+    with torch.no_grad():
+        for p in m.parameters():
+            p.mul_(0.5)
+    y = dict(x, rl_params=[host(p).copy() for p in m.rl_parameters()], enc_params=[host(p).copy() for p in m.encoder_parameters()])
+    again, _, _ = run(y, m, tp)
+    fresh, _, _ = run(y)
+    assert same_bits(again, fresh)
+    sc.check_parity(again, *sc.references(y), "weights halved in place", RATIOS)
+
+
+def test_each_pass_refuses_a_backward_after_its_own_later_forward_only():
+    x = sc.make_inputs("fixture_b33")
+    m = sc.Module(x, DEV)
+    tp = train.FusedTrainPassTS(m)
+    o, p, c, h, t = (dev(x[k]) for k in ("obs", "privileged_obs", "critic_obs", "obs_history", "terminated"))
+    mu1, _, _ = tp(o, p, c)
+    mu2, _, values2 = tp(o, p, c)
+    with pytest.raises(RuntimeError, match=r"FusedTrainPassTS: backward of RL forward call 1, but RL forward call 2 has overwritten"):
+        mu1.sum().backward()
+    assert all(q.grad is None for q in m.parameters())
+    l1 = tp.encoder_loss(h, p, t)
+    l2 = tp.encoder_loss(h, p, t)
+    with pytest.raises(RuntimeError, match=r"FusedTrainPassTS: backward of encoder forward call 1, but encoder forward call 2 has overwritten"):
+        l1.backward()
+    assert all(q.grad is None for q in m.parameters())
+    # the passes do not invalidate each other: an RL forward behind the encoder forward, then both backwards, newest first or not
+    mu3, _, values3 = tp(o, p, c)
+    l2.backward()
+    (mu3.sum() + values3.sum()).backward()
+    assert all(q.grad is not None for q in m.parameters())
+    l4 = tp.encoder_loss(h, p, t)
+    with pytest.raises(RuntimeError, match=r"RL forward call 2, but RL forward call 3"):
+        (mu2.sum() + values2.sum()).backward()
+    mu5, _, _ = tp(o[:9], p[:9], c[:9])
+    l4.backward()                                                      # the RL forward in between left the encoder's workspace alone
+    mu5.sum().backward()
+    # and the interleaved results are those of the passes run apart
+    apart, _, _ = run(x, m, tp)
+    for q in m.parameters():
+        q.grad = None
+    loss = tp.encoder_loss(h, p, t)
+    mu, sigma, values = tp(o, p, c)
+    (loss * float(x["upstream"])).backward()
+    torch.autograd.backward([mu, sigma, values], [dev(x[k]) for k in COTANGENTS])
+    torch.cuda.synchronize()
+    got = sc.named(x, dict(mu=host(mu), sigma=host(sigma), values=host(values)), [host(q.grad) for q in m.rl_parameters()], host(loss),
+                   [host(q.grad) for q in m.encoder_parameters()])
+    assert same_bits(got, apart)
+
+
+def test_each_backward_leaves_the_other_encoders_grad_untouched():
+    x = sc.make_inputs("fixture_b257")
+    m = sc.Module(x, DEV)
+    tp = train.FusedTrainPassTS(m)
+
+    def mark(params):
+        out = []
+        for i, p in enumerate(params):
+            p.grad = torch.full_like(p, 3.5 + i)
+            out.append((p, p.grad, host(p.grad).copy()))
+        return out
+    marks = mark(m.encoder_parameters())
+    mu, sigma, values = tp(dev(x["obs"]), dev(x["privileged_obs"]), dev(x["critic_obs"]))
+    torch.autograd.backward([mu, sigma, values], [dev(x[k]) for k in COTANGENTS])
+    torch.cuda.synchronize()
+    for p, g, before in marks:                                        # the RL backward: the history encoder's .grad is the same tensor, same bits
+        assert p.grad is g and np.array_equal(host(p.grad), before)
+    assert all(p.grad is not None and np.abs(host(p.grad)).max() > 0 for p in m.privilege_encoder.parameters())      # through the latent
+    for p in m.parameters():
+        p.grad = None
+    marks = mark(m.privilege_encoder.parameters())
+    tp.encoder_loss(dev(x["obs_history"]), dev(x["privileged_obs"]), dev(x["terminated"])).backward()
+    torch.cuda.synchronize()
+    for p, g, before in marks:                                        # the encoder backward: the privilege encoder's .grad likewise
+        assert p.grad is g and np.array_equal(host(p.grad), before)
+    assert all(p.grad is not None for p in m.encoder_parameters())
+    assert all(p.grad is None for p in list(m.actor.parameters()) + list(m.critic.parameters()) + [m.std])
+
+
+def test_a_fully_masked_batch_gives_zero_loss_and_zero_gradients():
+    x = sc.make_inputs("fixture_b257")
+    x["terminated"] = np.zeros_like(x["terminated"])
+    got, _, _ = run(x)
+    assert got["loss"][0] == 0.0
+    assert all((got[n] == 0).all() for n in sc.enc_names(x["hist"]))
+
+
+def test_a_saturated_hardtanh_column_passes_nothing_to_the_actor_or_the_encoder():
+    """A duck-typed TS module whose actor ends in a Hardtanh: with column 0 of mu saturated in every row and cotangents in that column
+    only, the actor's and, through the latent, the privilege encoder's gradients are exactly zero; with the Hardtanh removed they are not."""
+    x = sc.make_inputs("fixture_b33")
+    na = 2 * (len(x["actor"]) - 1)
+    x["rl_params"] = [p.copy() for p in x["rl_params"]]
+    x["rl_params"][na - 1][0] = 50.0                                  # the last actor bias: mu[:, 0] far above the clip
+    x["grad_mu"] = np.zeros_like(x["grad_mu"])
+    x["grad_mu"][:, 0] = 1.0 + np.arange(33, dtype=np.float32)
+    x["grad_sigma"], x["grad_values"] = np.zeros_like(x["grad_sigma"]), np.zeros_like(x["grad_values"])
+    got, m, _ = run(x)
+    assert isinstance(m.actor[-1], nn.Hardtanh) and (got["mu"][:, 0] == np.float32(x["clip"])).all()
+    names = sc.rl_names(x["actor"], x["critic"], x["priv"])
+    for n in names:
+        if n.startswith("actor") or n.startswith("privilege_encoder"):
+            assert (got[n] == 0).all(), n
+    free, _, _ = run(dict(x, clip=None))
+    for n in names:
+        if n.startswith("actor") or n.startswith("privilege_encoder"):
+            assert np.abs(free[n]).max() > 0, n
+    sc.check_parity(got, *sc.references(x), "a saturated column", RATIOS)
+
+
+# ---- non-finite values ------------------------------------------------------------------------------------------------------------------------
+def test_a_nan_row_stays_in_its_row_and_reaches_what_torch_reaches():
+    x = sc.make_inputs("fixture_b257")
+    clean, _, _ = run(x)
+    rl, enc = sc.rl_names(x["actor"], x["critic"], x["priv"]), sc.enc_names(x["hist"])
+    row = int(np.flatnonzero(x["terminated"][:, 0] == 1)[5])                 # an unmasked row
+    y = dict(x, privileged_obs=x["privileged_obs"].copy())
+    y["privileged_obs"][row, 2] = np.nan                                     # through the privilege encoder into the latent
+    got, _, _ = run(y)
+    others = np.arange(257) != row
+    assert np.isnan(got["mu"][row]).all() and np.isnan(got["sigma"][row]).all()
+    for k in ("mu", "sigma"):
+        assert np.array_equal(got[k][others].view(np.uint32), clean[k][others].view(np.uint32))
+    for n in ["values"] + [n for n in rl if n.startswith("critic")]:         # the critic read another matrix: not a bit changes
+        assert np.array_equal(got[n].view(np.uint32), clean[n].view(np.uint32)), n
+    assert np.array_equal(got["std"].view(np.uint32), clean["std"].view(np.uint32))
+    theirs = sc.torch_passes(y)
+    assert np.isnan(theirs["loss"]) and np.isnan(got["loss"][0])             # the target of that row is NaN
+    for n, g in list(zip(rl, theirs["rl_grads"])) + list(zip(enc, theirs["enc_grads"])):
+        assert (np.isnan(got[n]) | ~np.isnan(g)).all(), n                      # wherever torch's gradient is NaN, so is the kernel's
+    assert np.isnan(got["privilege_encoder.0.weight"][:, 2]).all()           # the NaN row reaches the privilege encoder's gradients
+    assert np.isnan(theirs["rl_grads"][rl.index("privilege_encoder.0.weight")][:, 2]).all()
+    # a NaN observation: the actor's first layer, and through the latent columns of its input gradient the privilege encoder too
+    y = dict(x, obs=x["obs"].copy())
+    y["obs"][row, 1] = np.nan
+    got, _, _ = run(y)
+    theirs = sc.torch_passes(y)
+    assert np.isnan(got["mu"][row]).all() and np.array_equal(got["mu"][others].view(np.uint32), clean["mu"][others].view(np.uint32))
+    for n, g in zip(rl, theirs["rl_grads"]):
+        assert (np.isnan(got[n]) | ~np.isnan(g)).all(), n
+    assert np.isnan(got["actor.0.weight"][:, 1]).all() and np.isnan(theirs["rl_grads"][rl.index("privilege_encoder.2.weight")]).any()
+    assert np.isfinite(got["loss"][0]) and same_bits({n: got[n] for n in enc}, {n: clean[n] for n in enc})      # the encoder pass read neither
+    # in a masked row of the history the loss is still NaN (the mask is a multiplication)
+    masked = int(np.flatnonzero(x["terminated"][:, 0] == 0)[2])
+    z = dict(x, obs_history=x["obs_history"].copy())
+    z["obs_history"][masked, 0] = np.nan
+    got, _, _ = run(z)
+    assert np.isnan(got["loss"][0]) and np.isnan(sc.torch_passes(z)["loss"])
+    for n in ["mu", "sigma", "values"] + rl:                                 # the RL pass never reads the history
+        assert np.array_equal(got[n].view(np.uint32), clean[n].view(np.uint32)), n
+    # the same through the critic: values of that row only
+    w = dict(x, critic_obs=x["critic_obs"].copy())
+    w["critic_obs"][256, 0] = np.inf
+    got, _, _ = run(w)
+    assert not np.isfinite(got["values"][256]).any() and np.array_equal(got["values"][:256].view(np.uint32), clean["values"][:256].view(np.uint32))
+    for n in ["mu", "sigma", "std", "loss"] + [n for n in rl if not n.startswith("critic")] + enc:
+        assert np.array_equal(np.asarray(got[n], np.float32).view(np.uint32), np.asarray(clean[n], np.float32).view(np.uint32)), n
+
+
+def test_zz_print_the_parity_ratios():
+    """Not a check of its own: the worst |kernel - f64| / max(|torch-f32 - f64|, ulp) per tensor class over every parity check above, for
+    DESIGN.md's table."""
+    worst = {}
+    for _, ratios in RATIOS:
+        for k, v in ratios.items():
+            worst[k] = max(worst.get(k, 0.0), v)
+    for k, v in worst.items():
+        print(f"PARITY {k}: {v:.3f} over {len(RATIOS)} checks")
