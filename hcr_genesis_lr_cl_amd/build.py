@@ -47,11 +47,11 @@ def units():
          ("lg_policy", "lg_policy.hip", [], ["lg_math.h", os.path.join(INC, "lgpolicy.h")]),
          ("lg_ppo", "lg_ppo.hip", [], [os.path.join(INC, "lgppo.h")]),
          ("lg_optim", "lg_optim.hip", [], [os.path.join(INC, "lgoptim.h")]),
-         ("lg_train", "lg_train.hip", [], [os.path.join(INC, "lgtrain.h"), os.path.join(INC, "lgpolicy.h"), "lg_train_tiles.h"]),
+         ("lg_train", "lg_train.hip", [], [os.path.join(INC, "lgtrain.h"), os.path.join(INC, "lgpolicy.h"), "lg_train_tiles.h", "lg_train_pass.h"]),
          ("lg_train_ee", "lg_train_ee.hip", [], [os.path.join(INC, "lgtrainee.h"), os.path.join(INC, "lgtrain.h"), os.path.join(INC, "lgpolicy.h"),
-                                                 "lg_train_tiles.h"]),
+                                                 "lg_train_tiles.h", "lg_train_pass.h"]),
          ("lg_train_ts", "lg_train_ts.hip", [], [os.path.join(INC, "lgtraints.h"), os.path.join(INC, "lgtrain.h"), os.path.join(INC, "lgpolicy.h"),
-                                                 "lg_train_tiles.h"])]
+                                                 "lg_train_tiles.h", "lg_train_pass.h"])]
     for g in range(N_GROUPS):
         deps = COMMON + ["lg_kernel.h"] + (["lg_quad.h"] if g in QUAD_GROUPS else []) + ([os.path.join(HERE, "dpp_hazard_pass.py")] if DPP_PASS else [])
         u.append((f"lg_inst_{g}", "lg_inst.hip", [f"-DLG_GROUP={g}"], deps))

@@ -6,7 +6,8 @@
 // share of the two loss.backward() calls of PPO_EE.update() (ppo_ee.py:108-131) that runs through the three MLPs of
 // rsl_rl/modules/actor_critic_ee.py:39-79,115-133.
 //
-// The layer routines are lg_train_tiles.h's (shared with lg_train.hip, where the MFMA layouts are described).  What is new here:
+// The layer routines are lg_train_tiles.h's (the MFMA layouts are described in lg_train.hip), the chain, loss, plan and launch routines
+// lg_train_pass.h's.  What is this family's own:
 //   RL forward        grid (row tiles, 2).  y = 0: features -> LDS, the estimator chain ping-pongs so that its output ends in activation 1,
 //                     the features are staged again (L2-resident) into activation 0 at the actor's stride with the estimator's output
 //                     copied behind them, the concatenation goes to the workspace while the actor's first layer reads it.  y = 1: the critic.
@@ -15,11 +16,8 @@
 //   backward          the three launches of lg_train.hip over the chains [c0, c1) of the pass: actor and critic, or the estimator alone
 //                     (whose staged gl is scaled by the upstream scalar, read on the device).
 // Plain stores only; two calls on the same inputs give the same bits.
-#include <string>
-#include "lg_train_tiles.h"
+#include "lg_train_pass.h"
 #include "../../include/lgtrainee.h"
-
-int lg_fail_msg(const std::string &m);   // lg_host.hip: sets the thread-local message, returns 1
 
 #define EST LG_TRAIN_EE_ESTIMATOR
 #define ACT LG_TRAIN_EE_ACTOR
@@ -27,40 +25,15 @@ int lg_fail_msg(const std::string &m);   // lg_host.hip: sets the thread-local m
 static const int kRedBytes = LG_TRAIN_EE_THREADS * (int)sizeof(double);
 static_assert(LG_TRAIN_EE_THREADS == kThreads, "the loss tree has one leaf per thread of the row-tile workgroup");
 
-struct EArgs {
+struct EArgs : PArgs {
     TChain c[LG_TRAIN_EE_CHAINS];
-    float *ws;
-    const float *std, *grad_sigma;
-    float *grad_std, *sigma;
     const float *labels, *mask, *upstream;
     float *loss;
-    int N, R, q_off, red_off, A, clip_on;
-    float clip;
-    int sigma_stride, grad_sigma_stride, labels_stride, mask_stride;
-    int std_S, std_rps, std_job0, n_jobs;
-    int c0, c1;                 // the chains of the backward launches
-    int est_start, n_tiles, est_pass;
-    long long std_p_off, cat_off, gl_off, part_off;
+    int labels_stride, mask_stride;
+    int est_start, est_pass;
+    long long cat_off, gl_off, part_off;
 };
 static_assert(sizeof(EArgs) <= 4096, "EArgs is passed by value: the kernel-argument segment is 4 KB");
-
-// the chain over the row tile; its input is staged in b0 and a barrier has passed.  Returns the activation that holds the last layer's
-// output (a barrier has passed behind it).  store_h: every hidden activation to the workspace while the next layer reads it.
-template <int RB>
-__device__ __forceinline__ lds_f *chain_forward(const EArgs &a, const TChain &c, lds_f *b0, lds_f *b1, bool store_h, bool clip_last, int rows, int row0) {
-    lds_f *buf[2] = {b0, b1};
-    for (int li = 0; li < c.n_layers; li++) {
-        const TLayer &L = c.l[li];
-        const bool clip_on = clip_last && li == c.n_layers - 1;
-        const int per_wave = (((L.M + 15) >> 4) + kWaves - 1) / kWaves;
-        if (li && store_h) copy_out(buf[li & 1], L.sa, a.ws + c.l[li - 1].h_off, L.K, L.K, rows, row0);
-        if (per_wave >= 4) fwd_tile<RB, 4>(L, buf[li & 1], buf[(li + 1) & 1], clip_on, a.clip, a.R);
-        else if (per_wave >= 2) fwd_tile<RB, 2>(L, buf[li & 1], buf[(li + 1) & 1], clip_on, a.clip, a.R);
-        else fwd_tile<RB, 1>(L, buf[li & 1], buf[(li + 1) & 1], clip_on, a.clip, a.R);
-        __syncthreads();
-    }
-    return buf[c.n_layers & 1];
-}
 
 template <int RB> __global__ __launch_bounds__(256) void train_ee_forward_kernel(EArgs a) {
     extern __shared__ __align__(16) float lds[];
@@ -69,18 +42,13 @@ template <int RB> __global__ __launch_bounds__(256) void train_ee_forward_kernel
     lds_f *b0 = (lds_f *)lds, *b1 = (lds_f *)lds + a.q_off;
     if (blockIdx.y == 1) {
         const TChain &c = a.c[CRI];
-        stage_rows(c.in, c.l[0].K, c.in_stride, b0, c.l[0].sa, R, rows, row0);
-        __syncthreads();
-        const lds_f *v = chain_forward<RB>(a, c, b0, b1, true, false, rows, row0);
+        const lds_f *v = chain_from_rows<RB>(a.ws, c, b0, b1, true, false, a.clip, R, rows, row0);
         copy_out(v, c.l[c.n_layers - 1].so, c.out, c.l[c.n_layers - 1].M, c.out_stride, rows, row0);
         return;
     }
     const TChain &e = a.c[EST], &c = a.c[ACT];
     const int F = e.l[0].K, NL = e.l[e.n_layers - 1].M;
-    lds_f *s0 = a.est_start ? b1 : b0, *s1 = a.est_start ? b0 : b1;
-    stage_rows(e.in, F, e.in_stride, s0, e.l[0].sa, R, rows, row0);
-    __syncthreads();
-    const lds_f *p = chain_forward<RB>(a, e, s0, s1, false, false, rows, row0);       // ends in b1: est_start is chosen so
+    const lds_f *p = chain_from_rows<RB>(a.ws, e, a.est_start ? b1 : b0, a.est_start ? b0 : b1, false, false, a.clip, R, rows, row0);       // ends in b1: est_start is chosen so
     const int sa = c.l[0].sa, sp = e.l[e.n_layers - 1].so;
     stage_rows(e.in, F, e.in_stride, b0, sa, R, rows, row0);                           // [features | est] in b0, at the actor's stride
     for (int i = threadIdx.x; i < R * NL; i += kThreads) {
@@ -89,13 +57,10 @@ template <int RB> __global__ __launch_bounds__(256) void train_ee_forward_kernel
     }
     __syncthreads();
     copy_out(b0, sa, a.ws + a.cat_off, F + NL, F + NL, rows, row0);
-    const lds_f *m = chain_forward<RB>(a, c, b0, b1, true, a.clip_on != 0, rows, row0);
-    const int sm = c.l[c.n_layers - 1].so, A = a.A;
-    copy_out(m, sm, c.out, A, c.out_stride, rows, row0);
-    for (int t = threadIdx.x; t < rows * A; t += kThreads) {
-        const int row = t / A, ai = t - row * A;
-        a.sigma[(size_t)(row0 + row) * a.sigma_stride + ai] = m[row * sm + ai] * 0.f + a.std[ai];
-    }
+    const lds_f *m = chain_forward<RB>(a.ws, c, b0, b1, true, a.clip_on != 0, a.clip, R, rows, row0);
+    const int sm = c.l[c.n_layers - 1].so;
+    copy_out(m, sm, c.out, a.A, c.out_stride, rows, row0);
+    store_sigma(m, sm, a.A, a.std, a.sigma, a.sigma_stride, rows, row0);
 }
 
 template <int RB> __global__ __launch_bounds__(256) void train_est_forward_kernel(EArgs a) {
@@ -103,197 +68,53 @@ template <int RB> __global__ __launch_bounds__(256) void train_est_forward_kerne
     const TChain &c = a.c[EST];
     const int R = a.R, row0 = blockIdx.x * R;
     const int rows = min(R, a.N - row0);
-    lds_f *b0 = (lds_f *)lds, *b1 = (lds_f *)lds + a.q_off;
-    stage_rows(c.in, c.l[0].K, c.in_stride, b0, c.l[0].sa, R, rows, row0);
-    __syncthreads();
-    const lds_f *p = chain_forward<RB>(a, c, b0, b1, true, false, rows, row0);
-    const int NL = c.l[c.n_layers - 1].M, sp = c.l[c.n_layers - 1].so;
-    const float scale = 2.0f / ((float)a.N * (float)NL);
-    float *gl = a.ws + a.gl_off;
-    double acc = 0.0;
-    for (int i = threadIdx.x; i < rows * NL; i += kThreads) {
-        const int row = i / NL, col = i - row * NL;
-        const float t = a.mask[(size_t)(row0 + row) * a.mask_stride];
-        const float d = (p[row * sp + col] - a.labels[(size_t)(row0 + row) * a.labels_stride + col]) * t;       // NaN * 0 stays NaN, as in torch
-        gl[(size_t)(row0 + row) * NL + col] = d * t * scale;
-        acc += (double)d * (double)d;
-    }
-    volatile double *red = (volatile double *)(lds + a.red_off);
-    red[threadIdx.x] = acc;
-    __syncthreads();
-    for (int s = kThreads / 2; s > 0; s >>= 1) {                                         // a fixed tree over the 256 thread sums
-        if ((int)threadIdx.x < s) red[threadIdx.x] = red[threadIdx.x] + red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) ((double *)(a.ws + a.part_off))[blockIdx.x] = red[0];
+    const lds_f *p = chain_from_rows<RB>(a.ws, c, (lds_f *)lds, (lds_f *)lds + a.q_off, true, false, a.clip, R, rows, row0);
+    const int NL = c.l[c.n_layers - 1].M;
+    mse_tile(p, c.l[c.n_layers - 1].so, NL, a.labels, a.labels_stride, a.mask, a.mask_stride, a.ws + a.gl_off, 2.0f / ((float)a.N * (float)NL),
+             (volatile double *)(lds + a.red_off), (double *)(a.ws + a.part_off), rows, row0);
 }
 
-// one workgroup: the tile partials in tile order.  256 of them at a time reach LDS through parallel loads; thread 0 adds them in order.
 __global__ __launch_bounds__(256) void train_est_finalize_kernel(EArgs a) {
-    __shared__ double part[kThreads];
-    const double *P = (const double *)(a.ws + a.part_off);
-    double sum = 0.0;
-    for (int t0 = 0; t0 < a.n_tiles; t0 += kThreads) {
-        const int n = min(kThreads, a.n_tiles - t0);
-        if ((int)threadIdx.x < n) part[threadIdx.x] = P[t0 + threadIdx.x];
-        __syncthreads();
-        if (threadIdx.x == 0)
-            for (int i = 0; i < n; i++) sum += part[i];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) a.loss[0] = (float)(sum / ((double)a.N * (double)a.c[EST].l[a.c[EST].n_layers - 1].M));
+    loss_finalize((const double *)(a.ws + a.part_off), a.n_tiles, a.N, a.c[EST].l[a.c[EST].n_layers - 1].M, a.loss);
 }
 
 template <int RB> __global__ __launch_bounds__(256) void train_ee_input_grad_kernel(EArgs a) {
     extern __shared__ __align__(16) float lds[];
     const int ci = a.c0 + blockIdx.y;
     const TChain &c = a.c[ci];
-    const int R = a.R, row0 = blockIdx.x * R, nl = c.n_layers;
+    const int R = a.R, row0 = blockIdx.x * R;
     const int rows = min(R, a.N - row0);
-    lds_f *buf[2] = {(lds_f *)lds, (lds_f *)lds + a.q_off};
-    {   // G of the last layer: gl times the upstream scalar (estimator pass), or the incoming gradient, behind the Hardtanh's mask for the actor
-        const TLayer &L = c.l[nl - 1];
-        lds_f *g = buf[nl & 1];
-        float *gws = a.ws + L.g_off;
-        const bool mask = ci == ACT && a.clip_on;
-        const int w = L.M;
-        const float up = a.est_pass ? a.upstream[0] : 1.f;
-        for (int i = threadIdx.x; i < R * w; i += kThreads) {
-            const int row = i / w, col = i - row * w;
-            float v = 0.f;
-            if (row < rows) {
-                if (a.est_pass) v = a.ws[a.gl_off + (size_t)(row0 + row) * w + col] * up;
-                else {
-                    v = c.gin[(size_t)(row0 + row) * c.gin_stride + col];
-                    if (mask) {
-                        const float m = c.out[(size_t)(row0 + row) * c.out_stride + col];
-                        if (m >= a.clip || m <= -a.clip) v = 0.f;             // hardtanh_backward: a NaN mean passes the gradient on
-                    }
-                }
-                gws[(size_t)(row0 + row) * w + col] = v;
-            }
-            g[row * L.so + col] = v;
-        }
-    }
+    lds_f *b0 = (lds_f *)lds, *b1 = (lds_f *)lds + a.q_off;
+    seed_last_g(a.ws, c, (c.n_layers & 1) ? b1 : b0, a.est_pass ? a.ws + a.gl_off : nullptr, a.upstream, ci == ACT && a.clip_on, a.clip, R, rows, row0);
     __syncthreads();
-    for (int li = nl - 1; li >= 1; li--) {
-        const TLayer &L = c.l[li], &P = c.l[li - 1];
-        lds_f *cur = buf[(li + 1) & 1], *nxt = buf[li & 1];
-        if (P.elu) {                                                   // H_(l-1) into the destination tile: the epilogue turns it into G_(l-1) in place
-            stage_rows(a.ws + P.h_off, L.K, L.K, nxt, L.sa, R, rows, row0);
-            __syncthreads();
-        }
-        const int per_wave = (((L.K + 15) >> 4) + kWaves - 1) / kWaves;
-        if (per_wave >= 4) bwd_tile<RB, 4>(L, cur, nxt, P.elu != 0, R);
-        else if (per_wave >= 2) bwd_tile<RB, 2>(L, cur, nxt, P.elu != 0, R);
-        else bwd_tile<RB, 1>(L, cur, nxt, P.elu != 0, R);
-        __syncthreads();
-        copy_out(nxt, L.sa, a.ws + P.g_off, L.K, L.K, rows, row0);     // read-only until the barrier behind the next layer's stage
-    }
+    chain_backward<RB>(a.ws, c, b0, b1, R, rows, row0);
 }
 
-// one wave per job: (layer, 64 x 64 tile of its gradient, batch slice) of the chains [c0, c1), or a slice of grad_std's column sums
-__global__ __launch_bounds__(64) void train_ee_weight_grad_kernel(EArgs a) {
-    const int job = blockIdx.x;
-    if (job >= a.std_job0) {
-        colsum_wave(a.grad_sigma, a.grad_sigma_stride, a.A, a.ws + a.std_p_off, job - a.std_job0, a.std_rps, a.N);
-        return;
-    }
-    int ci = a.c0, li = 0;
-    for (int c = a.c0; c < a.c1; c++)
-        for (int l = 0; l < a.c[c].n_layers; l++)
-            if (job >= a.c[c].l[l].job0) { ci = c; li = l; }          // job0 rises with (c, l)
-    const TChain &c = a.c[ci];
-    const TLayer &L = c.l[li];
-    wgrad_wave(L, a.ws + L.g_off, li ? a.ws + c.l[li - 1].h_off : c.in, li ? L.K : c.in_stride, a.ws, job - L.job0, a.N);
-}
+__global__ __launch_bounds__(64) void train_ee_weight_grad_kernel(EArgs a) { wgrad_job(a, a.c, a.c0, a.c1); }
 
-__global__ __launch_bounds__(256) void train_ee_combine_kernel(EArgs a) {
-    const long long stride = (long long)gridDim.x * blockDim.x, first = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    for (int ci = a.c0; ci < a.c1; ci++)
-        for (int li = 0; li < a.c[ci].n_layers; li++) combine_layer(a.c[ci].l[li], a.ws, first, stride);
-    if (a.std_S) combine_cols(a.ws + a.std_p_off, a.A, a.std_S, a.grad_std, first, stride);
-}
+__global__ __launch_bounds__(256) void train_ee_combine_kernel(EArgs a) { combine_all(a, a.c, a.c0, a.c1); }
 
 // ---- host ----------------------------------------------------------------------------------------------------------------------------
 static const char *kChainEE[LG_TRAIN_EE_CHAINS] = {"chain[0] (estimator)", "chain[1] (actor)", "chain[2] (critic)"};
 static const char *kChainEst = "chain (estimator)";
+static void (*const kForward[2])(EArgs) = {train_ee_forward_kernel<1>, train_ee_forward_kernel<2>};
+static void (*const kEstForward[2])(EArgs) = {train_est_forward_kernel<1>, train_est_forward_kernel<2>};
+static void (*const kInputGrad[2])(EArgs) = {train_ee_input_grad_kernel<1>, train_ee_input_grad_kernel<2>};
+static bool raised_forward[2][64], raised_est_forward[2][64], raised_input_grad[2][64];
 
-// widths and layer count of one chain into k; `first`: the LDS activation its input sits in
-static int plan_chain(const std::string &cn, const LgTrainChain &c, TChain &t, int first, int w[2]) {
-    if (c.n_layers < 1 || c.n_layers > kMaxL) return lg_fail_msg(cn + ".n_layers = " + std::to_string(c.n_layers) + " is outside [1, " + std::to_string(kMaxL) + "]");
-    int width = c.layer[0].n_in;
-    for (int li = 0; li < c.n_layers; li++) {
-        const LgTrainLayer &l = c.layer[li];
-        const std::string ln = cn + ".layer[" + std::to_string(li) + "]";
-        if (l.n_in < 1 || l.n_in > LG_POLICY_MAX_WIDTH) return lg_fail_msg(ln + ".n_in = " + std::to_string(l.n_in) + " is outside [1, " + std::to_string(LG_POLICY_MAX_WIDTH) + "]");
-        if (l.n_out < 1 || l.n_out > LG_POLICY_MAX_WIDTH) return lg_fail_msg(ln + ".n_out = " + std::to_string(l.n_out) + " is outside [1, " + std::to_string(LG_POLICY_MAX_WIDTH) + "]");
-        if (l.n_in != width) return lg_fail_msg(ln + ".n_in = " + std::to_string(l.n_in) + ", but its input has " + std::to_string(width) + " columns");
-        width = l.n_out;
-        TLayer &L = t.l[li];
-        L.K = l.n_in; L.M = l.n_out; L.elu = l.elu != 0;
-        L.sa = lds_stride(l.n_in); L.so = lds_stride(l.n_out);
-        if (L.sa > w[(li + first) & 1]) w[(li + first) & 1] = L.sa;
-        if (L.so > w[(li + first + 1) & 1]) w[(li + first + 1) & 1] = L.so;
-    }
-    t.n_layers = c.n_layers;
+// offsets, slices and jobs of the chains [c0, c1) behind `off`, the LDS tile, and with extra_lds the estimator pass's loss regions
+static int layout_ee(const std::string &f, int N, int c0, int c1, bool std_on, const int w[2], int extra_lds, long long off, LgTrainEEPlan &pl, EArgs &k) {
+    PassLayout lay;
+    if (plan_layout(f, k, k.c, N, c0, c1, std_on ? ACT : -1, LG_TRAIN_EE_TARGET_JOBS, w, extra_lds, false, off, lay)) return 1;
+    plan_out(pl, k, k.c, lay);
+    k.gl_off = pl.gl_off = lay.gl_off; k.part_off = pl.partial_off = lay.part_off;
+    pl.loss_tiles = extra_lds ? k.n_tiles : 0;
     return 0;
-}
-
-// offsets, slices and jobs of the chains [c0, c1) behind `off`; the LDS tile
-static int plan_rest(const std::string &f, int N, int c0, int c1, bool std_on, const int w[2], int extra_lds, long long off, LgTrainEEPlan &pl, EArgs &k) {
-    int jobs = 0;
-    for (int ci = 0; ci < LG_TRAIN_EE_CHAINS; ci++)
-        for (int li = 0; li < LG_POLICY_MAX_LAYERS; li++) pl.h_off[ci][li] = pl.g_off[ci][li] = pl.p_off[ci][li] = -1;
-    for (int ci = c0; ci < c1; ci++)
-        for (int li = 0; li < k.c[ci].n_layers; li++) {
-            TLayer &L = k.c[ci].l[li];
-            if (li < k.c[ci].n_layers - 1) { L.h_off = pl.h_off[ci][li] = off; off += (long long)N * L.M; }
-            L.g_off = pl.g_off[ci][li] = off; off += (long long)N * L.M;
-        }
-    for (int ci = c0; ci < c1; ci++)
-        for (int li = 0; li < k.c[ci].n_layers; li++) {
-            TLayer &L = k.c[ci].l[li];
-            const int tn = (L.M + LG_TRAIN_WG_TILE - 1) / LG_TRAIN_WG_TILE;
-            L.tiles_k = (L.K + LG_TRAIN_WG_TILE - 1) / LG_TRAIN_WG_TILE;
-            slice_rule(N, (long long)tn * L.tiles_k, L.S, L.rps, LG_TRAIN_EE_TARGET_JOBS);
-            pl.slices[ci][li] = L.S; pl.slice_rows[ci][li] = L.rps;
-            L.p_off = pl.p_off[ci][li] = off; off += (long long)L.S * ((long long)L.M * L.K + L.M);
-            L.job0 = jobs; jobs += L.S * tn * L.tiles_k;
-        }
-    pl.std_p_off = -1;
-    if (std_on) {
-        k.A = k.c[ACT].l[k.c[ACT].n_layers - 1].M;
-        slice_rule(N, 1, k.std_S, k.std_rps, LG_TRAIN_EE_TARGET_JOBS);
-        pl.std_slices = k.std_S; pl.std_slice_rows = k.std_rps;
-        k.std_p_off = pl.std_p_off = off; off += (long long)k.std_S * k.A;
-    }
-    k.std_job0 = jobs; jobs += k.std_S;
-    k.n_jobs = pl.weight_jobs = jobs;
-    k.N = N; k.c0 = c0; k.c1 = c1;
-    for (int R = 32; R >= 8; R >>= 1) {
-        const size_t bytes = (size_t)R * (w[0] + w[1]) * sizeof(float) + extra_lds;
-        if (bytes <= kLdsBytes) {
-            k.R = pl.row_tile = R; k.q_off = R * w[0]; k.red_off = R * (w[0] + w[1]); pl.lds_bytes = (int)bytes;
-            k.n_tiles = (N + R - 1) / R;
-            if (extra_lds) {                                         // the estimator pass: gl and the float64 tile partials
-                const int NL = k.c[EST].l[k.c[EST].n_layers - 1].M;
-                k.gl_off = pl.gl_off = off; off += (long long)N * NL;
-                off += off & 1;
-                k.part_off = pl.partial_off = off; off += 2LL * k.n_tiles;
-                pl.loss_tiles = k.n_tiles;
-            }
-            pl.workspace_floats = off;
-            return 0;
-        }
-    }
-    return lg_fail_msg(f + ": an 8-row tile of these widths (" + std::to_string(w[0] + w[1]) + " floats per row) does not fit the 160 KB of LDS");
 }
 
 static int make_plan_ee(const char *fn, const LgTrainEEArgs *p, LgTrainEEPlan &pl, EArgs &k) {
     const std::string f(fn);
-    if (!p) return lg_fail_msg(f + ": null descriptor");
-    if (p->n_rows < 1) return lg_fail_msg(f + ": n_rows = " + std::to_string(p->n_rows) + " < 1");
+    if (check_desc(f, p)) return 1;
     pl = LgTrainEEPlan{};
     k = EArgs{};
     int w[2] = {0, 0};
@@ -306,88 +127,33 @@ static int make_plan_ee(const char *fn, const LgTrainEEArgs *p, LgTrainEEPlan &p
         return lg_fail_msg(f + ": " + kChainEE[ACT] + ".layer[0].n_in = " + std::to_string(k.c[ACT].l[0].K) + ", but [features | estimator output] has " +
                            std::to_string(F) + " + " + std::to_string(NL) + " columns");
     pl.cat_off = k.cat_off = 0;
-    pl.gl_off = pl.partial_off = -1;
-    return plan_rest(f, p->n_rows, ACT, CRI + 1, true, w, 0, (long long)p->n_rows * (F + NL), pl, k);
+    return layout_ee(f, p->n_rows, ACT, CRI + 1, true, w, 0, (long long)p->n_rows * (F + NL), pl, k);
 }
 
 static int make_plan_est(const char *fn, const LgTrainEstArgs *p, LgTrainEEPlan &pl, EArgs &k) {
     const std::string f(fn);
-    if (!p) return lg_fail_msg(f + ": null descriptor");
-    if (p->n_rows < 1) return lg_fail_msg(f + ": n_rows = " + std::to_string(p->n_rows) + " < 1");
+    if (check_desc(f, p)) return 1;
     pl = LgTrainEEPlan{};
     k = EArgs{};
     int w[2] = {0, 0};
     if (plan_chain(f + ": " + kChainEst, p->chain, k.c[EST], 0, w)) return 1;
     pl.cat_off = -1;
     k.est_pass = 1;
-    return plan_rest(f, p->n_rows, EST, EST + 1, false, w, kRedBytes, 0, pl, k);
-}
-
-static int bind_chain(const std::string &cn, const LgTrainChain &c, TChain &t, bool input, bool grads) {
-    if (input) {
-        if (!c.input) return lg_fail_msg(cn + ".input is null");
-        if (c.in_stride < c.layer[0].n_in) return lg_fail_msg(cn + ".in_stride = " + std::to_string(c.in_stride) + " is below its width " + std::to_string(c.layer[0].n_in));
-        t.in = c.input; t.in_stride = c.in_stride;
-    }
-    for (int li = 0; li < c.n_layers; li++) {
-        const LgTrainLayer &l = c.layer[li];
-        const std::string ln = cn + ".layer[" + std::to_string(li) + "]";
-        if (!l.weight) return lg_fail_msg(ln + ".weight is null");
-        if (!l.bias) return lg_fail_msg(ln + ".bias is null");
-        if (grads && !l.grad_weight) return lg_fail_msg(ln + ".grad_weight is null");
-        if (grads && !l.grad_bias) return lg_fail_msg(ln + ".grad_bias is null");
-        TLayer &L = t.l[li];
-        L.W = l.weight; L.b = l.bias; L.gW = l.grad_weight; L.gb = l.grad_bias;
-    }
-    return 0;
-}
-
-static int check_ws(const std::string &f, const float *ws, long long cap, const LgTrainEEPlan &pl, bool align8) {
-    if (!ws) return lg_fail_msg(f + ": workspace is null");
-    if (align8 && ((uintptr_t)ws & 7)) return lg_fail_msg(f + ": workspace is not 8-byte aligned (it holds the float64 partials)");
-    if (cap < pl.workspace_floats)
-        return lg_fail_msg(f + ": workspace_capacity = " + std::to_string(cap) + " floats is below the plan's " + std::to_string((long long)pl.workspace_floats));
-    return 0;
+    return layout_ee(f, p->n_rows, EST, EST + 1, false, w, kRedBytes, 0, pl, k);
 }
 
 static int bind_ee(const char *fn, const LgTrainEEArgs *p, const LgTrainEEPlan &pl, EArgs &k, bool backward) {
     const std::string f(fn);
-    for (int ci = 0; ci < LG_TRAIN_EE_CHAINS; ci++)
-        if (bind_chain(f + ": " + kChainEE[ci], p->chain[ci], k.c[ci], ci != ACT, backward && ci != EST)) return 1;
-    const int A = k.A, V = k.c[CRI].l[k.c[CRI].n_layers - 1].M;
-    if (p->clip_on && !(p->clip_actions >= 0.f)) return lg_fail_msg(f + ": clip_actions must be >= 0 under clip_on");
-    if (!p->std) return lg_fail_msg(f + ": std is null");
-    if (!p->mu) return lg_fail_msg(f + ": mu is null");
-    if (!p->sigma) return lg_fail_msg(f + ": sigma is null");
-    if (!p->values) return lg_fail_msg(f + ": values is null");
-    if (p->mu_stride < A) return lg_fail_msg(f + ": mu_stride = " + std::to_string(p->mu_stride) + " is below its width " + std::to_string(A));
-    if (p->sigma_stride < A) return lg_fail_msg(f + ": sigma_stride = " + std::to_string(p->sigma_stride) + " is below its width " + std::to_string(A));
-    if (p->values_stride < V) return lg_fail_msg(f + ": values_stride = " + std::to_string(p->values_stride) + " is below its width " + std::to_string(V));
-    if (backward) {
-        if (!p->grad_std) return lg_fail_msg(f + ": grad_std is null");
-        if (!p->grad_mu) return lg_fail_msg(f + ": grad_mu is null");
-        if (!p->grad_sigma) return lg_fail_msg(f + ": grad_sigma is null");
-        if (!p->grad_values) return lg_fail_msg(f + ": grad_values is null");
-        if (p->grad_mu_stride < A) return lg_fail_msg(f + ": grad_mu_stride = " + std::to_string(p->grad_mu_stride) + " is below its width " + std::to_string(A));
-        if (p->grad_sigma_stride < A) return lg_fail_msg(f + ": grad_sigma_stride = " + std::to_string(p->grad_sigma_stride) + " is below its width " + std::to_string(A));
-        if (p->grad_values_stride < V) return lg_fail_msg(f + ": grad_values_stride = " + std::to_string(p->grad_values_stride) + " is below its width " + std::to_string(V));
-    }
-    if (check_ws(f, p->workspace, p->workspace_capacity, pl, false)) return 1;
-    k.ws = p->workspace;
+    for (int ci = 0; ci < LG_TRAIN_EE_CHAINS; ci++)      // the actor has no input of its own
+        if (bind_chain(f + ": " + kChainEE[ci], p->chain[ci], k.c[ci], ci == ACT ? 0 : p->chain[ci].layer[0].n_in, backward && ci != EST)) return 1;
+    if (bind_heads(f, p, k, k.c[ACT], k.c[CRI], pl.workspace_floats, backward)) return 1;
     k.c[ACT].in = p->workspace + pl.cat_off; k.c[ACT].in_stride = k.c[ACT].l[0].K;       // the stored concatenation
-    k.c[ACT].out = p->mu; k.c[ACT].out_stride = p->mu_stride;
-    k.c[CRI].out = p->values; k.c[CRI].out_stride = p->values_stride;
-    k.c[ACT].gin = p->grad_mu; k.c[ACT].gin_stride = p->grad_mu_stride;
-    k.c[CRI].gin = p->grad_values; k.c[CRI].gin_stride = p->grad_values_stride;
-    k.std = p->std; k.grad_std = p->grad_std; k.sigma = p->sigma; k.sigma_stride = p->sigma_stride;
-    k.grad_sigma = p->grad_sigma; k.grad_sigma_stride = p->grad_sigma_stride;
-    k.clip_on = p->clip_on != 0; k.clip = p->clip_actions;
     return 0;
 }
 
 static int bind_est(const char *fn, const LgTrainEstArgs *p, const LgTrainEEPlan &pl, EArgs &k, bool backward) {
     const std::string f(fn);
-    if (bind_chain(f + ": " + kChainEst, p->chain, k.c[EST], true, backward)) return 1;
+    if (bind_chain(f + ": " + kChainEst, p->chain, k.c[EST], p->chain.layer[0].n_in, backward)) return 1;
     const int NL = k.c[EST].l[k.c[EST].n_layers - 1].M;
     if (!p->labels) return lg_fail_msg(f + ": labels is null");
     if (!p->mask) return lg_fail_msg(f + ": mask is null");
@@ -395,7 +161,7 @@ static int bind_est(const char *fn, const LgTrainEstArgs *p, const LgTrainEEPlan
     if (p->mask_stride < 1) return lg_fail_msg(f + ": mask_stride = " + std::to_string(p->mask_stride) + " is below its width 1");
     if (!backward && !p->loss) return lg_fail_msg(f + ": loss is null");
     if (backward && !p->upstream) return lg_fail_msg(f + ": upstream is null");
-    if (check_ws(f, p->workspace, p->workspace_capacity, pl, true)) return 1;
+    if (check_ws(f, p->workspace, p->workspace_capacity, pl.workspace_floats, true)) return 1;
     k.ws = p->workspace;
     k.labels = p->labels; k.labels_stride = p->labels_stride; k.mask = p->mask; k.mask_stride = p->mask_stride;
     k.loss = p->loss; k.upstream = p->upstream;
@@ -414,73 +180,25 @@ extern "C" int lg_train_est_plan(const LgTrainEstArgs *args, LgTrainEEPlan *out)
     return make_plan_est("lg_train_est_plan", args, *out, k);
 }
 
-// once per device and kernel: dynamic LDS above 64 KB has to be asked for (an unsynchronised race sets the same value twice: harmless)
-static int raise_lds(const char *fn, int which, int rb) {
-    static bool raised[64][3][2];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return lg_fail_msg(std::string(fn) + ": no current HIP device");
-    if (raised[dev][which][rb]) return 0;
-    const void *fp[3][2] = {{(const void *)train_ee_forward_kernel<1>, (const void *)train_ee_forward_kernel<2>},
-                            {(const void *)train_est_forward_kernel<1>, (const void *)train_est_forward_kernel<2>},
-                            {(const void *)train_ee_input_grad_kernel<1>, (const void *)train_ee_input_grad_kernel<2>}};
-    const hipError_t e = hipFuncSetAttribute(fp[which][rb], hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsBytes);
-    if (e != hipSuccess) return lg_fail_msg(std::string(fn) + ": hipFuncSetAttribute: " + hipGetErrorString(e));
-    raised[dev][which][rb] = true;
-    return 0;
-}
-
-static int done(const char *fn) {
-    const hipError_t e = hipGetLastError();
-    return e == hipSuccess ? 0 : lg_fail_msg(std::string(fn) + ": " + hipGetErrorString(e));
-}
-
-// the three launches of a backward over the chains [c0, c1) of k
-static int launch_backward(const char *fn, const LgTrainEEPlan &pl, const EArgs &k, hipStream_t stream) {
-    const int rb = k.R == 32;
-    if (raise_lds(fn, 2, rb)) return 1;
-    const dim3 grid((unsigned)k.n_tiles, (unsigned)(k.c1 - k.c0));
-    if (rb) hipLaunchKernelGGL(train_ee_input_grad_kernel<2>, grid, dim3(kThreads), (size_t)pl.lds_bytes, stream, k);
-    else hipLaunchKernelGGL(train_ee_input_grad_kernel<1>, grid, dim3(kThreads), (size_t)pl.lds_bytes, stream, k);
-    hipLaunchKernelGGL(train_ee_weight_grad_kernel, dim3((unsigned)k.n_jobs), dim3(64), 0, stream, k);
-    long long elems = k.A;
-    for (int ci = k.c0; ci < k.c1; ci++)
-        for (int li = 0; li < k.c[ci].n_layers; li++) {
-            const long long n = (long long)k.c[ci].l[li].M * k.c[ci].l[li].K + k.c[ci].l[li].M;
-            if (n > elems) elems = n;
-        }
-    long long blocks = (elems + 255) / 256;
-    if (blocks > 1024) blocks = 1024;                    // grid-stride behind that
-    hipLaunchKernelGGL(train_ee_combine_kernel, dim3((unsigned)blocks), dim3(256), 0, stream, k);
-    return done(fn);
-}
-
 extern "C" int lg_train_ee_forward(const LgTrainEEArgs *args, void *stream) {
     static const char *fn = "lg_train_ee_forward";
     LgTrainEEPlan pl; EArgs k;
     if (make_plan_ee(fn, args, pl, k) || bind_ee(fn, args, pl, k, false)) return 1;
-    const int rb = k.R == 32;
-    if (raise_lds(fn, 0, rb)) return 1;
-    const dim3 grid((unsigned)k.n_tiles, 2);
-    if (rb) hipLaunchKernelGGL(train_ee_forward_kernel<2>, grid, dim3(kThreads), (size_t)pl.lds_bytes, (hipStream_t)stream, k);
-    else hipLaunchKernelGGL(train_ee_forward_kernel<1>, grid, dim3(kThreads), (size_t)pl.lds_bytes, (hipStream_t)stream, k);
-    return done(fn);
+    return launch_tile(fn, kForward, raised_forward, 2, pl.lds_bytes, (hipStream_t)stream, k) || done(fn);
 }
 
 extern "C" int lg_train_ee_backward(const LgTrainEEArgs *args, void *stream) {
     static const char *fn = "lg_train_ee_backward";
     LgTrainEEPlan pl; EArgs k;
     if (make_plan_ee(fn, args, pl, k) || bind_ee(fn, args, pl, k, true)) return 1;
-    return launch_backward(fn, pl, k, (hipStream_t)stream);
+    return launch_backward(fn, kInputGrad, raised_input_grad, train_ee_weight_grad_kernel, train_ee_combine_kernel, k.c1 - k.c0, pl.lds_bytes, (hipStream_t)stream, k);
 }
 
 extern "C" int lg_train_est_forward(const LgTrainEstArgs *args, void *stream) {
     static const char *fn = "lg_train_est_forward";
     LgTrainEEPlan pl; EArgs k;
     if (make_plan_est(fn, args, pl, k) || bind_est(fn, args, pl, k, false)) return 1;
-    const int rb = k.R == 32;
-    if (raise_lds(fn, 1, rb)) return 1;
-    if (rb) hipLaunchKernelGGL(train_est_forward_kernel<2>, dim3((unsigned)k.n_tiles), dim3(kThreads), (size_t)pl.lds_bytes, (hipStream_t)stream, k);
-    else hipLaunchKernelGGL(train_est_forward_kernel<1>, dim3((unsigned)k.n_tiles), dim3(kThreads), (size_t)pl.lds_bytes, (hipStream_t)stream, k);
+    if (launch_tile(fn, kEstForward, raised_est_forward, 1, pl.lds_bytes, (hipStream_t)stream, k)) return 1;
     hipLaunchKernelGGL(train_est_finalize_kernel, dim3(1), dim3(kThreads), 0, (hipStream_t)stream, k);
     return done(fn);
 }
@@ -489,5 +207,5 @@ extern "C" int lg_train_est_backward(const LgTrainEstArgs *args, void *stream) {
     static const char *fn = "lg_train_est_backward";
     LgTrainEEPlan pl; EArgs k;
     if (make_plan_est(fn, args, pl, k) || bind_est(fn, args, pl, k, true)) return 1;
-    return launch_backward(fn, pl, k, (hipStream_t)stream);
+    return launch_backward(fn, kInputGrad, raised_input_grad, train_ee_weight_grad_kernel, train_ee_combine_kernel, k.c1 - k.c0, pl.lds_bytes, (hipStream_t)stream, k);
 }

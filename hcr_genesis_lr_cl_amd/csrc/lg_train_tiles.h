@@ -1,7 +1,8 @@
-// lg_train_tiles.h -- the layer routines of the fused learner passes, shared by lg_train.hip (the plain ActorCritic, include/lgtrain.h) and
-// lg_train_ee.hip (ActorCriticEE, include/lgtrainee.h): the row-tile forward and input-gradient layers, the weight-gradient wave, the
-// combine of the slice partials, and the host's LDS stride and slice rules.  The MFMA operand layouts are described at the top of
-// lg_train.hip.  Everything here is inlined into the kernels of the including unit; nothing is exported.
+// lg_train_tiles.h -- the layer routines of the fused learner passes, shared by lg_train.hip (the plain ActorCritic, include/lgtrain.h),
+// lg_train_ee.hip (ActorCriticEE, include/lgtrainee.h) and lg_train_ts.hip (ActorCriticTS, include/lgtraints.h): the row-tile forward and
+// input-gradient layers, the weight-gradient wave, the combine of the slice partials, and the host's LDS stride and slice rules.  What a
+// pass builds from them (chains, loss, plan, bind, launch) is lg_train_pass.h, which includes this header.  The MFMA operand layouts are
+// described at the top of lg_train.hip.  Everything here is inlined into the kernels of the including unit; nothing is exported.
 #ifndef LG_TRAIN_TILES_H
 #define LG_TRAIN_TILES_H
 #include <hip/hip_runtime.h>

@@ -16,7 +16,11 @@ gradient for the observations and no double backward.  There is no CPU path: the
 
 FusedTrainPassEE (below; include/lgtrainee.h, csrc/lg_train_ee.hip) is the same for ActorCriticEE under PPO_EE: the RL pass and the
 supervised estimator pass.  FusedTrainPassTS (include/lgtraints.h, csrc/lg_train_ts.hip) is the same for ActorCriticTS under PPO_TS: the RL
-pass, whose gradient reaches the privilege encoder through the latent, and the supervised history-encoder pass."""
+pass, whose gradient reaches the privilege encoder through the latent, and the supervised history-encoder pass.
+
+The three families share what is below `_Pass`: one record per pass (workspace, call counter, entry points, descriptor builder), one
+autograd.Function for an RL pass and one for a loss pass, driven by that record.  A refusal carries the name of the surface that first
+raised it, which is why the helpers take an `owner`."""
 from __future__ import annotations
 
 import ctypes as C
@@ -29,6 +33,7 @@ from . import abi
 _OTHER_FAMILIES = (("estimator", "ActorCriticEE"), ("privilege_encoder", "ActorCriticTS / ActorCriticCTS"),
                    ("history_encoder", "ActorCriticTS / ActorCriticCTS"), ("vae", "ActorCriticDreamWaQ"),
                    ("memory_a", "ActorCriticRecurrent"), ("memory_c", "ActorCriticRecurrent"))
+_PLAIN, _EE, _TS = "FusedTrainPass", "FusedTrainPassEE", "FusedTrainPassTS"
 
 
 class TrainChainSpec:
@@ -56,88 +61,139 @@ class TrainSpec:
         return ["std"] + [f"{c.name}.{i}.{n}" for c in self.chains for i in range(len(c.linears)) for n in ("weight", "bias")]
 
 
-def _check_param(t, what, device):
+def _check_param(t, what, device, owner=_PLAIN):
     if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise ValueError(f"FusedTrainPass: {what} is {getattr(t, 'dtype', type(t).__name__)}, the kernel reads float32")
+        raise ValueError(f"{owner}: {what} is {getattr(t, 'dtype', type(t).__name__)}, the kernel reads float32")
     if not t.is_contiguous():
-        raise ValueError(f"FusedTrainPass: {what} is not contiguous")
+        raise ValueError(f"{owner}: {what} is not contiguous")
     if device is not None and t.device != device:
-        raise ValueError(f"FusedTrainPass: {what} is on {t.device}, not on {device}")
+        raise ValueError(f"{owner}: {what} is on {t.device}, not on {device}")
 
 
-def _describe_chain(name, seq, device, allow_clip):
+def _describe_chain(name, seq, device, allow_clip, owner=_PLAIN):
     if not isinstance(seq, nn.Sequential):
-        raise ValueError(f"FusedTrainPass: {name} is {type(seq).__name__}, expected an nn.Sequential of Linear / ELU"
+        raise ValueError(f"{owner}: {name} is {type(seq).__name__}, expected an nn.Sequential of Linear / ELU"
                          + (" / Hardtanh" if allow_clip else ""))
     linears, elu, clip = [], [], None
     mods = list(seq)
     for i, m in enumerate(mods):
         where = f"{name}[{i}]"
         if clip is not None:
-            raise ValueError(f"FusedTrainPass: {where} ({type(m).__name__}) follows the Hardtanh, which must end the actor")
+            raise ValueError(f"{owner}: {where} ({type(m).__name__}) follows the Hardtanh, which must end the actor")
         if isinstance(m, nn.Linear):
             if m.bias is None:
-                raise ValueError(f"FusedTrainPass: {where} has no bias")
+                raise ValueError(f"{owner}: {where} has no bias")
             if m.in_features > abi.POLICY_MAX_WIDTH or m.out_features > abi.POLICY_MAX_WIDTH:
-                raise ValueError(f"FusedTrainPass: {where} is {m.in_features} -> {m.out_features}, widths are limited to {abi.POLICY_MAX_WIDTH}")
+                raise ValueError(f"{owner}: {where} is {m.in_features} -> {m.out_features}, widths are limited to {abi.POLICY_MAX_WIDTH}")
             if linears and linears[-1].out_features != m.in_features:
-                raise ValueError(f"FusedTrainPass: {where} takes {m.in_features} inputs, the layer before it gives {linears[-1].out_features}")
-            _check_param(m.weight, f"{where}.weight", device)
-            _check_param(m.bias, f"{where}.bias", device)
+                raise ValueError(f"{owner}: {where} takes {m.in_features} inputs, the layer before it gives {linears[-1].out_features}")
+            _check_param(m.weight, f"{where}.weight", device, owner)
+            _check_param(m.bias, f"{where}.bias", device, owner)
             linears.append(m)
             elu.append(False)
         elif isinstance(m, nn.ELU):
             if not linears or elu[-1]:
-                raise ValueError(f"FusedTrainPass: {where} (ELU) does not follow a Linear")
+                raise ValueError(f"{owner}: {where} (ELU) does not follow a Linear")
             if m.alpha != 1.0:
-                raise ValueError(f"FusedTrainPass: {where} is ELU(alpha={m.alpha}), only alpha = 1 is built")
+                raise ValueError(f"{owner}: {where} is ELU(alpha={m.alpha}), only alpha = 1 is built")
             elu[-1] = True
         elif isinstance(m, nn.Hardtanh) and allow_clip:
             if i != len(mods) - 1 or not linears or elu[-1] or m.min_val != -m.max_val or not m.max_val >= 0:
-                raise ValueError(f"FusedTrainPass: {where} (Hardtanh({m.min_val}, {m.max_val})) must be the symmetric clip behind the actor's last Linear")
+                raise ValueError(f"{owner}: {where} (Hardtanh({m.min_val}, {m.max_val})) must be the symmetric clip behind the actor's last Linear")
             clip = float(m.max_val)
         else:
-            raise ValueError(f"FusedTrainPass: {where} is {type(m).__name__}; only Linear and ELU"
+            raise ValueError(f"{owner}: {where} is {type(m).__name__}; only Linear and ELU"
                              + (" (and a final Hardtanh)" if allow_clip else "") + " are built into the kernel")
     if not linears:
-        raise ValueError(f"FusedTrainPass: {name} has no Linear layer")
+        raise ValueError(f"{owner}: {name} has no Linear layer")
     if len(linears) > abi.POLICY_MAX_LAYERS:
-        raise ValueError(f"FusedTrainPass: {name} has {len(linears)} Linear layers, the kernel takes {abi.POLICY_MAX_LAYERS}")
+        raise ValueError(f"{owner}: {name} has {len(linears)} Linear layers, the kernel takes {abi.POLICY_MAX_LAYERS}")
     if elu[-1]:
-        raise ValueError(f"FusedTrainPass: {name} ends in an ELU, expected a Linear output layer")
+        raise ValueError(f"{owner}: {name} ends in an ELU, expected a Linear output layer")
     return TrainChainSpec(name, linears, elu, clip)
+
+
+def _describe(actor_critic, device, owner, foreign, beside, chains, chain_owner, between=None):
+    """What describe, describe_ee and describe_ts share: no member of another family (`foreign`; `beside` ends that refusal), not
+    recurrent, .actor / .critic / .std there, the chains of `chains` ((name, may end in a Hardtanh) pairs) by _describe_chain, the
+    family's own checks across them (`between`) and the shape of std.  Returns the chain specs by name, and std."""
+    for attr, family in foreign:
+        if getattr(actor_critic, attr, None) is not None:
+            raise ValueError(f"{owner}: the module has .{attr} ({family}){beside}")
+    if getattr(actor_critic, "is_recurrent", False):
+        raise ValueError(f"{owner}: the module is recurrent (is_recurrent); the recurrent update keeps the torch path")
+    for need in ("actor", "critic", "std"):
+        if getattr(actor_critic, need, None) is None:
+            raise ValueError(f"{owner}: the module has no .{need}")
+    c = {name: _describe_chain(name, getattr(actor_critic, name), device, clip, chain_owner) for name, clip in chains}
+    if between is not None:
+        between(c)
+    std = actor_critic.std
+    _check_param(std, "std", device)
+    if tuple(std.shape) != (c["actor"].widths[-1],):
+        raise ValueError(f"{owner}: std has shape {tuple(std.shape)}, the actor has {c['actor'].widths[-1]} outputs")
+    return c, std
 
 
 def describe(actor_critic, device=None):
     """The plain ActorCritic as the kernel takes it (duck-typed: .actor, .critic, .std).  Refusals are ValueErrors that name the layer or
     the member; with `device` every parameter must live there."""
-    for attr, family in _OTHER_FAMILIES:
-        if getattr(actor_critic, attr, None) is not None:
-            raise ValueError(f"FusedTrainPass: the module has .{attr} ({family}); only the plain ActorCritic is built, the other learners "
-                             f"keep the torch path")
-    if getattr(actor_critic, "is_recurrent", False):
-        raise ValueError("FusedTrainPass: the module is recurrent (is_recurrent); the recurrent update keeps the torch path")
-    for need in ("actor", "critic", "std"):
-        if getattr(actor_critic, need, None) is None:
-            raise ValueError(f"FusedTrainPass: the module has no .{need}")
-    actor = _describe_chain("actor", actor_critic.actor, device, True)
-    critic = _describe_chain("critic", actor_critic.critic, device, False)
-    std = actor_critic.std
-    _check_param(std, "std", device)
-    if tuple(std.shape) != (actor.widths[-1],):
-        raise ValueError(f"FusedTrainPass: std has shape {tuple(std.shape)}, the actor has {actor.widths[-1]} outputs")
-    return TrainSpec(actor, critic, std)
+    c, std = _describe(actor_critic, device, _PLAIN, _OTHER_FAMILIES, "; only the plain ActorCritic is built, the other learners keep the torch path",
+                       (("actor", True), ("critic", False)), _PLAIN)
+    return TrainSpec(c["actor"], c["critic"], std)
 
 
-def _rows(t, width, what, n=None, device=None):
+def _rows(t, width, what, n=None, device=None, owner=_PLAIN):
     """(n, width) float32 with unit inner stride: (pointer, row stride)."""
     ok = isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == width and (n is None or t.shape[0] == n) \
         and (t.shape[1] == 1 or t.stride(1) == 1) and (t.shape[0] == 1 or t.stride(0) >= width) and (device is None or t.device == device)
     if not ok:
         got = f"{tuple(t.shape)} {t.dtype} on {t.device}, strides {tuple(t.stride())}" if isinstance(t, torch.Tensor) else type(t).__name__
-        raise ValueError(f"FusedTrainPass: {what} must be ({'B' if n is None else n}, {width}) float32 with unit inner stride"
+        raise ValueError(f"{owner}: {what} must be ({'B' if n is None else n}, {width}) float32 with unit inner stride"
                          + (f" on {device}" if device is not None else "") + f"; got {got}")
     return t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else width)
+
+
+def _fill_chain(ch, c, device, grads=None):
+    """Widths, flags and weight pointers of one LgTrainChain; `grads`: [weight, bias, weight, bias, ...] tensors of its layers."""
+    ch.n_layers = len(c.linears)
+    for li, (lin, elu) in enumerate(zip(c.linears, c.elu)):
+        L = ch.layer[li]
+        _check_param(lin.weight, f"{c.name} layer {li} weight", device)
+        _check_param(lin.bias, f"{c.name} layer {li} bias", device)
+        L.weight, L.bias, L.n_in, L.n_out, L.elu = lin.weight.data_ptr(), lin.bias.data_ptr(), lin.in_features, lin.out_features, int(elu)
+        if grads is not None:
+            L.grad_weight, L.grad_bias = grads[2 * li].data_ptr(), grads[2 * li + 1].data_ptr()
+
+
+def _fill_heads(a, spec, mu, sigma, values, n, device, owner, grad_std=None, grad_mu=None, grad_sigma=None, grad_values=None):
+    """The clip, std, the three outputs and (backward: grad_std is given) the gradient members of an RL descriptor of `owner`."""
+    A, V = spec.num_actions, spec.critic.widths[-1]
+    a.clip_on, a.clip_actions = (1, spec.clip_actions) if spec.clip_actions is not None else (0, 0.0)
+    _check_param(spec.std, "std", device)
+    a.std = spec.std.data_ptr()
+    a.mu, a.mu_stride = _rows(mu, A, "mu", n, device, owner)
+    a.sigma, a.sigma_stride = _rows(sigma, A, "sigma", n, device, owner)
+    a.values, a.values_stride = _rows(values, V, "values", n, device, owner)
+    if grad_std is not None:
+        a.grad_std = grad_std.data_ptr()
+        a.grad_mu, a.grad_mu_stride = _rows(grad_mu, A, "grad_mu", n, device, owner)
+        a.grad_sigma, a.grad_sigma_stride = _rows(grad_sigma, A, "grad_sigma", n, device, owner)
+        a.grad_values, a.grad_values_stride = _rows(grad_values, V, "grad_values", n, device, owner)
+
+
+def _bind_workspace(a, workspace, device, owner=_EE):
+    if workspace is not None:
+        if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float32 or not workspace.is_contiguous() \
+                or (device is not None and workspace.device != device):
+            raise ValueError(f"{owner}: the workspace must be a contiguous float32 tensor" + (f" on {device}" if device is not None else ""))
+        a.workspace, a.workspace_capacity = workspace.data_ptr(), workspace.numel()
+
+
+def _scalar(t, what, device):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != 1 or (device is not None and t.device != device):
+        raise ValueError(f"{_EE}: {what} must be one float32" + (f" on {device}" if device is not None else ""))
+    return t.data_ptr()
 
 
 def train_args(spec, obs, critic_obs, mu, sigma, values, workspace, grads=None, grad_mu=None, grad_sigma=None, grad_values=None, device=None):
@@ -149,37 +205,20 @@ def train_args(spec, obs, critic_obs, mu, sigma, values, workspace, grads=None, 
         raise ValueError(f"FusedTrainPass: obs must be a (B, {spec.actor.widths[0]}) float32 tensor with B >= 1")
     n = int(obs.shape[0])
     a.n_rows = n
-    a.clip_on, a.clip_actions = (1, spec.clip_actions) if spec.clip_actions is not None else (0, 0.0)
-    gi = 1
-    for ci, (c, x, what) in enumerate(zip(spec.chains, (obs, critic_obs), ("obs", "critic_obs"))):
-        ch = a.chain[ci]
+    g0 = 1
+    for ch, c, x, what in zip(a.chain, spec.chains, (obs, critic_obs), ("obs", "critic_obs")):
         ch.input, ch.in_stride = _rows(x, c.widths[0], what, n, device)
-        ch.n_layers = len(c.linears)
-        for li, (lin, elu) in enumerate(zip(c.linears, c.elu)):
-            L = ch.layer[li]
-            _check_param(lin.weight, f"{c.name} layer {li} weight", device)
-            _check_param(lin.bias, f"{c.name} layer {li} bias", device)
-            L.weight, L.bias, L.n_in, L.n_out, L.elu = lin.weight.data_ptr(), lin.bias.data_ptr(), lin.in_features, lin.out_features, int(elu)
-            if grads is not None:
-                L.grad_weight, L.grad_bias = grads[gi].data_ptr(), grads[gi + 1].data_ptr()
-            gi += 2
-    A, V = spec.num_actions, spec.critic.widths[-1]
-    _check_param(spec.std, "std", device)
-    a.std = spec.std.data_ptr()
-    a.mu, a.mu_stride = _rows(mu, A, "mu", n, device)
-    a.sigma, a.sigma_stride = _rows(sigma, A, "sigma", n, device)
-    a.values, a.values_stride = _rows(values, V, "values", n, device)
-    if grads is not None:
-        a.grad_std = grads[0].data_ptr()
-        a.grad_mu, a.grad_mu_stride = _rows(grad_mu, A, "grad_mu", n, device)
-        a.grad_sigma, a.grad_sigma_stride = _rows(grad_sigma, A, "grad_sigma", n, device)
-        a.grad_values, a.grad_values_stride = _rows(grad_values, V, "grad_values", n, device)
-    if workspace is not None:
-        if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float32 or not workspace.is_contiguous() \
-                or (device is not None and workspace.device != device):
-            raise ValueError("FusedTrainPass: the workspace must be a contiguous float32 tensor" + (f" on {device}" if device is not None else ""))
-        a.workspace, a.workspace_capacity = workspace.data_ptr(), workspace.numel()
+        _fill_chain(ch, c, device, None if grads is None else grads[g0:g0 + 2 * len(c.linears)])
+        g0 += 2 * len(c.linears)
+    _fill_heads(a, spec, mu, sigma, values, n, device, _PLAIN, *(() if grads is None else (grads[0], grad_mu, grad_sigma, grad_values)))
+    _bind_workspace(a, workspace, device, _PLAIN)
     return a
+
+
+def _widths_into(ch, w):
+    ch.n_layers = len(w) - 1
+    for li in range(min(len(w) - 1, abi.POLICY_MAX_LAYERS)):
+        ch.layer[li].n_in, ch.layer[li].n_out = w[li], w[li + 1]
 
 
 def plan_of(args):
@@ -190,33 +229,43 @@ def plan_of(args):
     return p
 
 
-_PLANS = {}      # (n_rows, actor widths, critic widths) -> LgTrainPlan: a pure function of the shapes
+_PLANS = {}      # (entry point, n_rows, (chain, widths) ...) -> its plan struct: a pure function of the shapes
+
+
+def _plan(entry, args_cls, plan_cls, n_rows, chains, **scalars):
+    """The plan `entry` gives for n_rows rows and chains of these widths ([in, out_0, out_1, ...] each).  `chains`: (index into the
+    descriptor's chain array, None where it has the one chain; widths) pairs; `scalars`: further descriptor members."""
+    key = (entry, int(n_rows)) + tuple((i, tuple(int(x) for x in w)) for i, w in chains)
+    if key not in _PLANS:
+        lib, a, p = abi.load_lib(), args_cls(), plan_cls()
+        a.n_rows = key[1]
+        for i, w in key[2:]:
+            _widths_into(a.chain if i is None else a.chain[i], w)
+        for k, v in scalars.items():
+            setattr(a, k, v)
+        abi.check(getattr(lib, entry)(C.byref(a), C.byref(p)), lib)
+        _PLANS[key] = p
+    return _PLANS[key]
 
 
 def plan(n_rows, actor_widths, critic_widths):
     """LgTrainPlan for n_rows rows of chains with these widths ([in, out_0, out_1, ...] each)."""
-    key = (int(n_rows), tuple(int(w) for w in actor_widths), tuple(int(w) for w in critic_widths))
-    if key not in _PLANS:
-        a = abi.LgTrainArgs()
-        a.n_rows = key[0]
-        for ci, w in enumerate(key[1:]):
-            a.chain[ci].n_layers = len(w) - 1
-            for li in range(min(len(w) - 1, abi.POLICY_MAX_LAYERS)):
-                a.chain[ci].layer[li].n_in, a.chain[ci].layer[li].n_out = w[li], w[li + 1]
-        _PLANS[key] = plan_of(a)
-    return _PLANS[key]
+    return _plan("lg_train_plan", abi.LgTrainArgs, abi.LgTrainPlan, n_rows, ((0, actor_widths), (1, critic_widths)))
+
+
+def _call(name, args, device):
+    lib = abi.load_lib()
+    abi.check(getattr(lib, name)(C.byref(args), torch.cuda.current_stream(device).cuda_stream), lib)
 
 
 def forward(args, device):
     """lg_train_forward on the current stream of `device`."""
-    lib = abi.load_lib()
-    abi.check(lib.lg_train_forward(C.byref(args), torch.cuda.current_stream(device).cuda_stream), lib)
+    _call("lg_train_forward", args, device)
 
 
 def backward(args, device):
     """lg_train_backward on the current stream of `device`."""
-    lib = abi.load_lib()
-    abi.check(lib.lg_train_backward(C.byref(args), torch.cuda.current_stream(device).cuda_stream), lib)
+    _call("lg_train_backward", args, device)
 
 
 def _grad_rows(g, like):
@@ -228,60 +277,102 @@ def _grad_rows(g, like):
     return g
 
 
-class _Pass(torch.autograd.Function):
+def _module_device(actor_critic, owner):
+    dev = getattr(getattr(actor_critic, "std", None), "device", None)
+    if isinstance(dev, torch.device) and dev.type != "cuda":
+        raise ValueError(f"{owner}: the module is on {dev}, not on a HIP device (there is no CPU path)")
+    return dev
+
+
+class _Pass:
+    """One pass of one pass object: its workspace and call counter, and what drives it: `owner` and `what` (the pass's name in messages:
+    "", "RL ", "estimator ", "encoder "), the entry-point prefix, the descriptor builder, the plan and the parameters in gradient order."""
+
+    def __init__(self, owner, what, entry, args, plan, parameters, spec, device):
+        self.owner, self.what, self.entry, self.args, self.plan, self.parameters = owner, what, entry, args, plan, parameters
+        self.spec, self.device, self.workspace, self.calls = spec, device, None, 0
+
+    def run_forward(self, args, n):
+        """Plan, grow the workspace, launch, count: the number of this forward call."""
+        need = int(self.plan(n).workspace_floats)
+        if self.workspace is None or self.workspace.numel() < need:
+            self.workspace = torch.empty(need, dtype=torch.float32, device=self.device)
+        _bind_workspace(args, self.workspace, self.device)
+        _call(self.entry + "_forward", args, self.device)
+        self.calls += 1
+        return self.calls
+
+    def run_backward(self, call, make_args):
+        if self.calls != call:
+            raise RuntimeError(f"{self.owner}: backward of {self.what}forward call {call}, but {self.what}forward call {self.calls} has overwritten "
+                               f"its activations in the workspace since; run each backward before the next forward"
+                               + (" of the same pass" if self.what else ""))
+        grads = [torch.empty_like(p) for p in self.parameters()]
+        _call(self.entry + "_backward", make_args(grads), self.device)
+        return grads
+
+
+class _RLFunction(torch.autograd.Function):
+    """(mu, sigma, values) of an RL pass `ps` from its inputs; the parameters ride along so that autograd asks for their gradients."""
+
     @staticmethod
-    def forward(ctx, tp, obs, critic_obs, *params):
-        spec, device, n = tp.spec, tp.device, int(obs.shape[0])
+    def forward(ctx, ps, n_inputs, *inputs_and_params):
+        inputs, spec, device = inputs_and_params[:n_inputs], ps.spec, ps.device
+        n = int(inputs[0].shape[0])
         mu = torch.empty((n, spec.num_actions), dtype=torch.float32, device=device)
         sigma = torch.empty_like(mu)
         values = torch.empty((n, spec.critic.widths[-1]), dtype=torch.float32, device=device)
-        args = train_args(spec, obs, critic_obs, mu, sigma, values, None, device=device)      # every refusal before anything grows
-        ws = tp._workspace_for(n)
-        args.workspace, args.workspace_capacity = ws.data_ptr(), ws.numel()
-        forward(args, device)
-        tp._calls += 1
-        ctx.tp, ctx.call, ctx.obs, ctx.critic_obs = tp, tp._calls, obs, critic_obs
+        args = ps.args(spec, *inputs, mu, sigma, values, None, device=device)      # every refusal before anything grows
+        ctx.ps, ctx.inputs, ctx.call = ps, inputs, ps.run_forward(args, n)
         ctx.save_for_backward(mu, sigma, values)
         return mu, sigma, values
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_mu, grad_sigma, grad_values):
-        tp = ctx.tp
-        if tp._calls != ctx.call:
-            raise RuntimeError(f"FusedTrainPass: backward of forward call {ctx.call}, but forward call {tp._calls} has overwritten its "
-                               f"activations in the workspace since; run each backward before the next forward")
+        ps = ctx.ps
         mu, sigma, values = ctx.saved_tensors
-        spec, device = tp.spec, tp.device
-        grads = [torch.empty_like(p) for p in spec.parameters()]
         gm, gs, gv = _grad_rows(grad_mu, mu), _grad_rows(grad_sigma, sigma), _grad_rows(grad_values, values)
-        args = train_args(spec, ctx.obs, ctx.critic_obs, mu, sigma, values, tp._workspace, grads, gm, gs, gv, device=device)
-        backward(args, device)
-        return (None, None, None) + tuple(grads)
+        grads = ps.run_backward(ctx.call, lambda g: ps.args(ps.spec, *ctx.inputs, mu, sigma, values, ps.workspace, g, gm, gs, gv, device=ps.device))
+        return (None,) * (2 + len(ctx.inputs)) + tuple(grads)       # nothing for a chain that is no input of this pass
+
+
+class _LossFunction(torch.autograd.Function):
+    """The masked mean-squared error of a loss pass `ps` as a 0-dim tensor."""
+
+    @staticmethod
+    def forward(ctx, ps, n_inputs, *inputs_and_params):
+        inputs = inputs_and_params[:n_inputs]
+        loss = torch.empty((), dtype=torch.float32, device=ps.device)
+        args = ps.args(ps.spec, *inputs, loss, None, device=ps.device)
+        ctx.ps, ctx.inputs, ctx.call = ps, inputs, ps.run_forward(args, int(inputs[0].shape[0]))
+        return loss
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_loss):
+        ps = ctx.ps
+        up = grad_loss.to(torch.float32).reshape(1).contiguous()        # stays on the device: the kernel reads it there
+        grads = ps.run_backward(ctx.call, lambda grads: ps.args(ps.spec, *ctx.inputs, None, ps.workspace, grads, up, device=ps.device))
+        return (None,) * (2 + len(ctx.inputs)) + tuple(grads)       # the target's chain carries no gradient
+
+
+def _apply(fn, ps, *inputs):
+    return fn.apply(ps, len(inputs), *inputs, *ps.parameters())
 
 
 class FusedTrainPass:
     def __init__(self, actor_critic):
-        dev = getattr(getattr(actor_critic, "std", None), "device", None)
-        if isinstance(dev, torch.device) and dev.type != "cuda":
-            raise ValueError(f"FusedTrainPass: the module is on {dev}, not on a HIP device (there is no CPU path)")
-        self.spec = describe(actor_critic, dev)
-        self.device = dev
-        self._workspace = None
-        self._calls = 0
-
-    def _workspace_for(self, n):
-        need = int(plan(n, self.spec.actor.widths, self.spec.critic.widths).workspace_floats)
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(need, dtype=torch.float32, device=self.device)
-        return self._workspace
+        self.device = _module_device(actor_critic, _PLAIN)
+        self.spec = describe(actor_critic, self.device)
+        self._pass = _Pass(_PLAIN, "", "lg_train", train_args, self.plan, self.spec.parameters, self.spec, self.device)
 
     def plan(self, n_rows):
         return plan(n_rows, self.spec.actor.widths, self.spec.critic.widths)
 
     def __call__(self, obs, critic_obs):
         """(mu, sigma, values) of the mini-batch: (B, A), (B, A), (B, 1).  One launch on the current stream."""
-        return _Pass.apply(self, obs, critic_obs, *self.spec.parameters())
+        return _apply(_RLFunction, self._pass, obs, critic_obs)
 
 
 # ---- the explicit-estimator family (include/lgtrainee.h, csrc/lg_train_ee.hip) ----------------------------------------------------------------
@@ -313,45 +404,25 @@ def describe_ee(actor_critic, device=None):
     Refusals are ValueErrors that name the layer or the member."""
     if getattr(actor_critic, "estimator", None) is None:
         raise ValueError("FusedTrainPassEE: the module has no .estimator; the plain ActorCritic is FusedTrainPass's")
-    for attr, family in _OTHER_FAMILIES:
-        if attr != "estimator" and getattr(actor_critic, attr, None) is not None:
-            raise ValueError(f"FusedTrainPassEE: the module has .{attr} ({family}) beside .estimator; only ActorCriticEE is built")
-    if getattr(actor_critic, "is_recurrent", False):
-        raise ValueError("FusedTrainPassEE: the module is recurrent (is_recurrent); the recurrent update keeps the torch path")
-    for need in ("actor", "critic", "std"):
-        if getattr(actor_critic, need, None) is None:
-            raise ValueError(f"FusedTrainPassEE: the module has no .{need}")
-    estimator = _describe_chain("estimator", actor_critic.estimator, device, False)
-    actor = _describe_chain("actor", actor_critic.actor, device, True)
-    critic = _describe_chain("critic", actor_critic.critic, device, False)
-    if actor.widths[0] != estimator.widths[0] + estimator.widths[-1]:
-        raise ValueError(f"FusedTrainPassEE: actor[0] takes {actor.widths[0]} inputs, but [features | estimator output] has "
-                         f"{estimator.widths[0]} + {estimator.widths[-1]} columns")
-    std = actor_critic.std
-    _check_param(std, "std", device)
-    if tuple(std.shape) != (actor.widths[-1],):
-        raise ValueError(f"FusedTrainPassEE: std has shape {tuple(std.shape)}, the actor has {actor.widths[-1]} outputs")
-    return TrainSpecEE(estimator, actor, critic, std)
+
+    def between(c):
+        if c["actor"].widths[0] != c["estimator"].widths[0] + c["estimator"].widths[-1]:
+            raise ValueError(f"FusedTrainPassEE: actor[0] takes {c['actor'].widths[0]} inputs, but [features | estimator output] has "
+                             f"{c['estimator'].widths[0]} + {c['estimator'].widths[-1]} columns")
+    c, std = _describe(actor_critic, device, _EE, [f for f in _OTHER_FAMILIES if f[0] != "estimator"], " beside .estimator; only ActorCriticEE is built",
+                       (("estimator", False), ("actor", True), ("critic", False)), _PLAIN, between)
+    return TrainSpecEE(c["estimator"], c["actor"], c["critic"], std)
 
 
-def _fill_chain(ch, c, device, grads=None):
-    """Widths, flags and weight pointers of one LgTrainChain; `grads`: [weight, bias, weight, bias, ...] tensors of its layers."""
-    ch.n_layers = len(c.linears)
-    for li, (lin, elu) in enumerate(zip(c.linears, c.elu)):
-        L = ch.layer[li]
-        _check_param(lin.weight, f"{c.name} layer {li} weight", device)
-        _check_param(lin.bias, f"{c.name} layer {li} bias", device)
-        L.weight, L.bias, L.n_in, L.n_out, L.elu = lin.weight.data_ptr(), lin.bias.data_ptr(), lin.in_features, lin.out_features, int(elu)
-        if grads is not None:
-            L.grad_weight, L.grad_bias = grads[2 * li].data_ptr(), grads[2 * li + 1].data_ptr()
-
-
-def _bind_workspace(a, workspace, device):
-    if workspace is not None:
-        if not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.float32 or not workspace.is_contiguous() \
-                or (device is not None and workspace.device != device):
-            raise ValueError("FusedTrainPassEE: the workspace must be a contiguous float32 tensor" + (f" on {device}" if device is not None else ""))
-        a.workspace, a.workspace_capacity = workspace.data_ptr(), workspace.numel()
+def _rl_grads(grads, *chains):
+    """`grads` of an RL backward, [chain by chain in `chains` order ..., std], cut per chain; all None in a forward."""
+    if grads is None:
+        return [None] * (len(chains) + 1)
+    cuts, at = [], 0
+    for c in chains:
+        cuts.append(grads[at:at + 2 * len(c.linears)])
+        at += 2 * len(c.linears)
+    return cuts + [grads[-1]]
 
 
 def ee_args(spec, features, critic_obs, mu, sigma, values, workspace, grads=None, grad_mu=None, grad_sigma=None, grad_values=None, device=None):
@@ -361,33 +432,16 @@ def ee_args(spec, features, critic_obs, mu, sigma, values, workspace, grads=None
         raise ValueError(f"FusedTrainPassEE: estimator_features must be a (B, {spec.num_features}) float32 tensor with B >= 1")
     n = int(features.shape[0])
     a.n_rows = n
-    a.clip_on, a.clip_actions = (1, spec.clip_actions) if spec.clip_actions is not None else (0, 0.0)
-    na = 2 * len(spec.actor.linears)
     est, act, cri = a.chain[abi.TRAIN_EE_ESTIMATOR], a.chain[abi.TRAIN_EE_ACTOR], a.chain[abi.TRAIN_EE_CRITIC]
     est.input, est.in_stride = _rows(features, spec.num_features, "estimator_features", n, device)
     cri.input, cri.in_stride = _rows(critic_obs, spec.critic.widths[0], "critic_obs", n, device)
+    g_act, g_cri, g_std = _rl_grads(grads, spec.actor, spec.critic)
     _fill_chain(est, spec.estimator, device)
-    _fill_chain(act, spec.actor, device, None if grads is None else grads[:na])
-    _fill_chain(cri, spec.critic, device, None if grads is None else grads[na:-1])
-    A, V = spec.num_actions, spec.critic.widths[-1]
-    _check_param(spec.std, "std", device)
-    a.std = spec.std.data_ptr()
-    a.mu, a.mu_stride = _rows(mu, A, "mu", n, device)
-    a.sigma, a.sigma_stride = _rows(sigma, A, "sigma", n, device)
-    a.values, a.values_stride = _rows(values, V, "values", n, device)
-    if grads is not None:
-        a.grad_std = grads[-1].data_ptr()
-        a.grad_mu, a.grad_mu_stride = _rows(grad_mu, A, "grad_mu", n, device)
-        a.grad_sigma, a.grad_sigma_stride = _rows(grad_sigma, A, "grad_sigma", n, device)
-        a.grad_values, a.grad_values_stride = _rows(grad_values, V, "grad_values", n, device)
+    _fill_chain(act, spec.actor, device, g_act)
+    _fill_chain(cri, spec.critic, device, g_cri)
+    _fill_heads(a, spec, mu, sigma, values, n, device, _PLAIN, g_std, grad_mu, grad_sigma, grad_values)
     _bind_workspace(a, workspace, device)
     return a
-
-
-def _scalar(t, what, device):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != 1 or (device is not None and t.device != device):
-        raise ValueError(f"FusedTrainPassEE: {what} must be one float32" + (f" on {device}" if device is not None else ""))
-    return t.data_ptr()
 
 
 def est_args(spec, features, labels, terminated, loss, workspace, grads=None, upstream=None, device=None):
@@ -409,101 +463,14 @@ def est_args(spec, features, labels, terminated, loss, workspace, grads=None, up
     return a
 
 
-def _widths_into(ch, w):
-    ch.n_layers = len(w) - 1
-    for li in range(min(len(w) - 1, abi.POLICY_MAX_LAYERS)):
-        ch.layer[li].n_in, ch.layer[li].n_out = w[li], w[li + 1]
-
-
-_PLANS_EE = {}
-
-
 def plan_ee(n_rows, estimator_widths, actor_widths, critic_widths):
     """LgTrainEEPlan of the RL pass (lg_train_ee_plan) for chains of these widths."""
-    key = (int(n_rows),) + tuple(tuple(int(x) for x in w) for w in (estimator_widths, actor_widths, critic_widths))
-    if key not in _PLANS_EE:
-        lib, a, p = abi.load_lib(), abi.LgTrainEEArgs(), abi.LgTrainEEPlan()
-        a.n_rows = key[0]
-        for ci, w in enumerate(key[1:]):
-            _widths_into(a.chain[ci], w)
-        abi.check(lib.lg_train_ee_plan(C.byref(a), C.byref(p)), lib)
-        _PLANS_EE[key] = p
-    return _PLANS_EE[key]
+    return _plan("lg_train_ee_plan", abi.LgTrainEEArgs, abi.LgTrainEEPlan, n_rows, ((0, estimator_widths), (1, actor_widths), (2, critic_widths)))
 
 
 def plan_est(n_rows, estimator_widths):
     """LgTrainEEPlan of the estimator pass (lg_train_est_plan)."""
-    key = (int(n_rows), tuple(int(x) for x in estimator_widths))
-    if key not in _PLANS_EE:
-        lib, a, p = abi.load_lib(), abi.LgTrainEstArgs(), abi.LgTrainEEPlan()
-        a.n_rows = key[0]
-        _widths_into(a.chain, key[1])
-        abi.check(lib.lg_train_est_plan(C.byref(a), C.byref(p)), lib)
-        _PLANS_EE[key] = p
-    return _PLANS_EE[key]
-
-
-def _call(name, args, device):
-    lib = abi.load_lib()
-    abi.check(getattr(lib, name)(C.byref(args), torch.cuda.current_stream(device).cuda_stream), lib)
-
-
-class _PassEE(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, tp, features, critic_obs, *params):
-        spec, device, n = tp.spec, tp.device, int(features.shape[0])
-        mu = torch.empty((n, spec.num_actions), dtype=torch.float32, device=device)
-        sigma = torch.empty_like(mu)
-        values = torch.empty((n, spec.critic.widths[-1]), dtype=torch.float32, device=device)
-        args = ee_args(spec, features, critic_obs, mu, sigma, values, None, device=device)      # every refusal before anything grows
-        _bind_workspace(args, tp._rl_workspace_for(n), device)
-        _call("lg_train_ee_forward", args, device)
-        tp._rl_calls += 1
-        ctx.tp, ctx.call, ctx.features, ctx.critic_obs = tp, tp._rl_calls, features, critic_obs
-        ctx.save_for_backward(mu, sigma, values)
-        return mu, sigma, values
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_mu, grad_sigma, grad_values):
-        tp = ctx.tp
-        if tp._rl_calls != ctx.call:
-            raise RuntimeError(f"FusedTrainPassEE: backward of RL forward call {ctx.call}, but RL forward call {tp._rl_calls} has overwritten "
-                               f"its activations in the workspace since; run each backward before the next forward of the same pass")
-        mu, sigma, values = ctx.saved_tensors
-        spec, device = tp.spec, tp.device
-        grads = [torch.empty_like(p) for p in spec.rl_parameters()]
-        gm, gs, gv = _grad_rows(grad_mu, mu), _grad_rows(grad_sigma, sigma), _grad_rows(grad_values, values)
-        args = ee_args(spec, ctx.features, ctx.critic_obs, mu, sigma, values, tp._rl_workspace, grads, gm, gs, gv, device=device)
-        _call("lg_train_ee_backward", args, device)
-        return (None, None, None) + tuple(grads)          # nothing for the estimator's parameters: they are no input of this pass
-
-
-class _EstLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, tp, features, labels, terminated, *params):
-        spec, device, n = tp.spec, tp.device, int(features.shape[0])
-        loss = torch.empty((), dtype=torch.float32, device=device)
-        args = est_args(spec, features, labels, terminated, loss, None, device=device)
-        _bind_workspace(args, tp._est_workspace_for(n), device)
-        _call("lg_train_est_forward", args, device)
-        tp._est_calls += 1
-        ctx.tp, ctx.call, ctx.inputs = tp, tp._est_calls, (features, labels, terminated)
-        return loss
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_loss):
-        tp = ctx.tp
-        if tp._est_calls != ctx.call:
-            raise RuntimeError(f"FusedTrainPassEE: backward of estimator forward call {ctx.call}, but estimator forward call {tp._est_calls} has "
-                               f"overwritten its activations in the workspace since; run each backward before the next forward of the same pass")
-        spec, device = tp.spec, tp.device
-        up = grad_loss.to(torch.float32).reshape(1).contiguous()        # stays on the device: the kernel reads it there
-        grads = [torch.empty_like(p) for p in spec.estimator_parameters()]
-        args = est_args(spec, *ctx.inputs, None, tp._est_workspace, grads, up, device=device)
-        _call("lg_train_est_backward", args, device)
-        return (None, None, None, None) + tuple(grads)
+    return _plan("lg_train_est_plan", abi.LgTrainEstArgs, abi.LgTrainEEPlan, n_rows, ((None, estimator_widths),))
 
 
 class FusedTrainPassEE:
@@ -519,13 +486,10 @@ class FusedTrainPassEE:
     invalidate a pending backward of the other; within a pass a backward whose forward has been overwritten raises."""
 
     def __init__(self, actor_critic):
-        dev = getattr(getattr(actor_critic, "std", None), "device", None)
-        if isinstance(dev, torch.device) and dev.type != "cuda":
-            raise ValueError(f"FusedTrainPassEE: the module is on {dev}, not on a HIP device (there is no CPU path)")
-        self.spec = describe_ee(actor_critic, dev)
-        self.device = dev
-        self._rl_workspace = self._est_workspace = None
-        self._rl_calls = self._est_calls = 0
+        self.device = _module_device(actor_critic, _EE)
+        self.spec = describe_ee(actor_critic, self.device)
+        self._rl = _Pass(_EE, "RL ", "lg_train_ee", ee_args, self.plan, self.rl_parameters, self.spec, self.device)
+        self._est = _Pass(_EE, "estimator ", "lg_train_est", est_args, self.estimator_plan, self.estimator_parameters, self.spec, self.device)
 
     def rl_parameters(self):
         return self.spec.rl_parameters()
@@ -540,25 +504,13 @@ class FusedTrainPassEE:
     def estimator_plan(self, n_rows):
         return plan_est(n_rows, self.spec.estimator.widths)
 
-    def _rl_workspace_for(self, n):
-        need = int(self.plan(n).workspace_floats)
-        if self._rl_workspace is None or self._rl_workspace.numel() < need:
-            self._rl_workspace = torch.empty(need, dtype=torch.float32, device=self.device)
-        return self._rl_workspace
-
-    def _est_workspace_for(self, n):
-        need = int(self.estimator_plan(n).workspace_floats)
-        if self._est_workspace is None or self._est_workspace.numel() < need:
-            self._est_workspace = torch.empty(need, dtype=torch.float32, device=self.device)
-        return self._est_workspace
-
     def __call__(self, estimator_features, critic_obs):
         """(mu, sigma, values) of the mini-batch: (B, A), (B, A), (B, 1).  One launch on the current stream."""
-        return _PassEE.apply(self, estimator_features, critic_obs, *self.spec.rl_parameters())
+        return _apply(_RLFunction, self._rl, estimator_features, critic_obs)
 
     def estimator_loss(self, estimator_features, estimator_labels, terminated):
         """mse_loss(estimator(features) * terminated, labels * terminated) as a 0-dim tensor with autograd.  Two launches."""
-        return _EstLoss.apply(self, estimator_features, estimator_labels, terminated, *self.spec.estimator_parameters())
+        return _apply(_LossFunction, self._est, estimator_features, estimator_labels, terminated)
 
 
 # ---- the teacher-student family (include/lgtraints.h, csrc/lg_train_ts.hip) -------------------------------------------------------------------
@@ -598,39 +550,18 @@ def describe_ts(actor_critic, device=None):
     for need in ("privilege_encoder", "history_encoder"):
         if getattr(actor_critic, need, None) is None:
             raise ValueError(f"FusedTrainPassTS: the module has no .{need}; ActorCriticTS has a privilege encoder and a history encoder")
-    for attr, family in _TS_FOREIGN:
-        if getattr(actor_critic, attr, None) is not None:
-            raise ValueError(f"FusedTrainPassTS: the module has .{attr} ({family}) beside its encoders; only ActorCriticTS is built")
-    if getattr(actor_critic, "is_recurrent", False):
-        raise ValueError("FusedTrainPassTS: the module is recurrent (is_recurrent); the recurrent update keeps the torch path")
-    for need in ("actor", "critic", "std"):
-        if getattr(actor_critic, need, None) is None:
-            raise ValueError(f"FusedTrainPassTS: the module has no .{need}")
 
-    def chain(name, clip):
-        try:
-            return _describe_chain(name, getattr(actor_critic, name), device, clip)
-        except ValueError as e:
-            raise ValueError(str(e).replace("FusedTrainPass:", "FusedTrainPassTS:", 1)) from None
-    priv, hist = chain("privilege_encoder", False), chain("history_encoder", False)
-    actor, critic = chain("actor", True), chain("critic", False)
-    if hist.widths[-1] != priv.widths[-1]:
-        raise ValueError(f"FusedTrainPassTS: history_encoder ends at {hist.widths[-1]} columns, privilege_encoder at {priv.widths[-1]}: the "
-                         f"latent widths differ")
-    if actor.widths[0] <= priv.widths[-1]:
-        raise ValueError(f"FusedTrainPassTS: actor[0] takes {actor.widths[0]} inputs, but [obs | latent] has O + {priv.widths[-1]} columns with O >= 1")
-    std = actor_critic.std
-    _check_param(std, "std", device)
-    if tuple(std.shape) != (actor.widths[-1],):
-        raise ValueError(f"FusedTrainPassTS: std has shape {tuple(std.shape)}, the actor has {actor.widths[-1]} outputs")
-    return TrainSpecTS(priv, actor, critic, hist, std)
-
-
-def _rows_ts(t, width, what, n=None, device=None):
-    try:
-        return _rows(t, width, what, n, device)
-    except ValueError as e:
-        raise ValueError(str(e).replace("FusedTrainPass:", "FusedTrainPassTS:", 1)) from None
+    def between(c):
+        hist, priv, actor = c["history_encoder"], c["privilege_encoder"], c["actor"]
+        if hist.widths[-1] != priv.widths[-1]:
+            raise ValueError(f"FusedTrainPassTS: history_encoder ends at {hist.widths[-1]} columns, privilege_encoder at {priv.widths[-1]}: the "
+                             f"latent widths differ")
+        if actor.widths[0] <= priv.widths[-1]:
+            raise ValueError(f"FusedTrainPassTS: actor[0] takes {actor.widths[0]} inputs, but [obs | latent] has O + {priv.widths[-1]} columns with "
+                             f"O >= 1")
+    c, std = _describe(actor_critic, device, _TS, _TS_FOREIGN, " beside its encoders; only ActorCriticTS is built",
+                       (("privilege_encoder", False), ("history_encoder", False), ("actor", True), ("critic", False)), _TS, between)
+    return TrainSpecTS(c["privilege_encoder"], c["actor"], c["critic"], c["history_encoder"], std)
 
 
 def ts_args(spec, obs, privileged_obs, critic_obs, mu, sigma, values, workspace, grads=None, grad_mu=None, grad_sigma=None, grad_values=None,
@@ -645,26 +576,15 @@ def ts_args(spec, obs, privileged_obs, critic_obs, mu, sigma, values, workspace,
         raise ValueError(f"FusedTrainPassTS: actor[0] takes {spec.actor.widths[0]} inputs, but [obs | latent] has {obs.shape[1]} + "
                          f"{spec.num_latent} columns")
     a.n_rows, a.n_obs = n, spec.num_obs
-    a.clip_on, a.clip_actions = (1, spec.clip_actions) if spec.clip_actions is not None else (0, 0.0)
-    na, nc = 2 * len(spec.actor.linears), 2 * len(spec.critic.linears)
     pri, act, cri = a.chain[abi.TRAIN_TS_PRIVILEGE], a.chain[abi.TRAIN_TS_ACTOR], a.chain[abi.TRAIN_TS_CRITIC]
-    act.input, act.in_stride = _rows_ts(obs, spec.num_obs, "obs", n, device)
-    pri.input, pri.in_stride = _rows_ts(privileged_obs, spec.privilege_encoder.widths[0], "privileged_obs", n, device)
-    cri.input, cri.in_stride = _rows_ts(critic_obs, spec.critic.widths[0], "critic_obs", n, device)
-    _fill_chain(act, spec.actor, device, None if grads is None else grads[:na])
-    _fill_chain(cri, spec.critic, device, None if grads is None else grads[na:na + nc])
-    _fill_chain(pri, spec.privilege_encoder, device, None if grads is None else grads[na + nc:-1])
-    A, V = spec.num_actions, spec.critic.widths[-1]
-    _check_param(spec.std, "std", device)
-    a.std = spec.std.data_ptr()
-    a.mu, a.mu_stride = _rows_ts(mu, A, "mu", n, device)
-    a.sigma, a.sigma_stride = _rows_ts(sigma, A, "sigma", n, device)
-    a.values, a.values_stride = _rows_ts(values, V, "values", n, device)
-    if grads is not None:
-        a.grad_std = grads[-1].data_ptr()
-        a.grad_mu, a.grad_mu_stride = _rows_ts(grad_mu, A, "grad_mu", n, device)
-        a.grad_sigma, a.grad_sigma_stride = _rows_ts(grad_sigma, A, "grad_sigma", n, device)
-        a.grad_values, a.grad_values_stride = _rows_ts(grad_values, V, "grad_values", n, device)
+    act.input, act.in_stride = _rows(obs, spec.num_obs, "obs", n, device, _TS)
+    pri.input, pri.in_stride = _rows(privileged_obs, spec.privilege_encoder.widths[0], "privileged_obs", n, device, _TS)
+    cri.input, cri.in_stride = _rows(critic_obs, spec.critic.widths[0], "critic_obs", n, device, _TS)
+    g_act, g_cri, g_pri, g_std = _rl_grads(grads, spec.actor, spec.critic, spec.privilege_encoder)
+    _fill_chain(act, spec.actor, device, g_act)
+    _fill_chain(cri, spec.critic, device, g_cri)
+    _fill_chain(pri, spec.privilege_encoder, device, g_pri)
+    _fill_heads(a, spec, mu, sigma, values, n, device, _TS, g_std, grad_mu, grad_sigma, grad_values)
     _bind_workspace(a, workspace, device)
     return a
 
@@ -678,11 +598,11 @@ def enc_args(spec, obs_history, privileged_obs, terminated, loss, workspace, gra
     n = int(obs_history.shape[0])
     a.n_rows = n
     his, pri = a.chain[abi.TRAIN_ENC_HISTORY], a.chain[abi.TRAIN_ENC_PRIVILEGE]
-    his.input, his.in_stride = _rows_ts(obs_history, spec.history_encoder.widths[0], "obs_history", n, device)
-    pri.input, pri.in_stride = _rows_ts(privileged_obs, spec.privilege_encoder.widths[0], "privileged_obs", n, device)
+    his.input, his.in_stride = _rows(obs_history, spec.history_encoder.widths[0], "obs_history", n, device, _TS)
+    pri.input, pri.in_stride = _rows(privileged_obs, spec.privilege_encoder.widths[0], "privileged_obs", n, device, _TS)
     _fill_chain(his, spec.history_encoder, device, grads)
     _fill_chain(pri, spec.privilege_encoder, device)
-    a.mask, a.mask_stride = _rows_ts(terminated, 1, "terminated", n, device)
+    a.mask, a.mask_stride = _rows(terminated, 1, "terminated", n, device, _TS)
     if loss is not None:
         a.loss = _scalar(loss, "the loss", device)
     if upstream is not None:
@@ -691,91 +611,16 @@ def enc_args(spec, obs_history, privileged_obs, terminated, loss, workspace, gra
     return a
 
 
-_PLANS_TS = {}
-
-
 def plan_ts(n_rows, privilege_widths, actor_widths, critic_widths):
     """LgTrainTSPlan of the RL pass (lg_train_ts_plan) for chains of these widths; O is actor_widths[0] less the latent width."""
-    key = (int(n_rows),) + tuple(tuple(int(x) for x in w) for w in (privilege_widths, actor_widths, critic_widths))
-    if key not in _PLANS_TS:
-        lib, a, p = abi.load_lib(), abi.LgTrainTSArgs(), abi.LgTrainTSPlan()
-        a.n_rows, a.n_obs = key[0], key[2][0] - key[1][-1]
-        for ci, w in enumerate(key[1:]):
-            _widths_into(a.chain[ci], w)
-        abi.check(lib.lg_train_ts_plan(C.byref(a), C.byref(p)), lib)
-        _PLANS_TS[key] = p
-    return _PLANS_TS[key]
+    return _plan("lg_train_ts_plan", abi.LgTrainTSArgs, abi.LgTrainTSPlan, n_rows, ((0, privilege_widths), (1, actor_widths), (2, critic_widths)),
+                 n_obs=int(actor_widths[0]) - int(privilege_widths[-1]))
 
 
 def plan_enc(n_rows, history_widths, privilege_widths):
     """LgTrainTSPlan of the encoder pass (lg_train_enc_plan)."""
-    key = (int(n_rows), "enc", tuple(int(x) for x in history_widths), tuple(int(x) for x in privilege_widths))
-    if key not in _PLANS_TS:
-        lib, a, p = abi.load_lib(), abi.LgTrainEncArgs(), abi.LgTrainTSPlan()
-        a.n_rows = key[0]
-        _widths_into(a.chain[abi.TRAIN_ENC_HISTORY], key[2])
-        _widths_into(a.chain[abi.TRAIN_ENC_PRIVILEGE], key[3])
-        abi.check(lib.lg_train_enc_plan(C.byref(a), C.byref(p)), lib)
-        _PLANS_TS[key] = p
-    return _PLANS_TS[key]
-
-
-class _PassTS(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, tp, obs, privileged_obs, critic_obs, *params):
-        spec, device, n = tp.spec, tp.device, int(obs.shape[0])
-        mu = torch.empty((n, spec.num_actions), dtype=torch.float32, device=device)
-        sigma = torch.empty_like(mu)
-        values = torch.empty((n, spec.critic.widths[-1]), dtype=torch.float32, device=device)
-        args = ts_args(spec, obs, privileged_obs, critic_obs, mu, sigma, values, None, device=device)      # every refusal before anything grows
-        _bind_workspace(args, tp._rl_workspace_for(n), device)
-        _call("lg_train_ts_forward", args, device)
-        tp._rl_calls += 1
-        ctx.tp, ctx.call, ctx.inputs = tp, tp._rl_calls, (obs, privileged_obs, critic_obs)
-        ctx.save_for_backward(mu, sigma, values)
-        return mu, sigma, values
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_mu, grad_sigma, grad_values):
-        tp = ctx.tp
-        if tp._rl_calls != ctx.call:
-            raise RuntimeError(f"FusedTrainPassTS: backward of RL forward call {ctx.call}, but RL forward call {tp._rl_calls} has overwritten "
-                               f"its activations in the workspace since; run each backward before the next forward of the same pass")
-        mu, sigma, values = ctx.saved_tensors
-        spec, device = tp.spec, tp.device
-        grads = [torch.empty_like(p) for p in spec.rl_parameters()]
-        gm, gs, gv = _grad_rows(grad_mu, mu), _grad_rows(grad_sigma, sigma), _grad_rows(grad_values, values)
-        args = ts_args(spec, *ctx.inputs, mu, sigma, values, tp._rl_workspace, grads, gm, gs, gv, device=device)
-        _call("lg_train_ts_backward", args, device)
-        return (None, None, None, None) + tuple(grads)     # nothing for the history encoder's parameters: they are no input of this pass
-
-
-class _EncLoss(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, tp, obs_history, privileged_obs, terminated, *params):
-        spec, device, n = tp.spec, tp.device, int(obs_history.shape[0])
-        loss = torch.empty((), dtype=torch.float32, device=device)
-        args = enc_args(spec, obs_history, privileged_obs, terminated, loss, None, device=device)
-        _bind_workspace(args, tp._enc_workspace_for(n), device)
-        _call("lg_train_enc_forward", args, device)
-        tp._enc_calls += 1
-        ctx.tp, ctx.call, ctx.inputs = tp, tp._enc_calls, (obs_history, privileged_obs, terminated)
-        return loss
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, grad_loss):
-        tp = ctx.tp
-        if tp._enc_calls != ctx.call:
-            raise RuntimeError(f"FusedTrainPassTS: backward of encoder forward call {ctx.call}, but encoder forward call {tp._enc_calls} has "
-                               f"overwritten its activations in the workspace since; run each backward before the next forward of the same pass")
-        spec, device = tp.spec, tp.device
-        up = grad_loss.to(torch.float32).reshape(1).contiguous()        # stays on the device: the kernel reads it there
-        grads = [torch.empty_like(p) for p in spec.encoder_parameters()]
-        args = enc_args(spec, *ctx.inputs, None, tp._enc_workspace, grads, up, device=device)
-        _call("lg_train_enc_backward", args, device)
-        return (None, None, None, None) + tuple(grads)     # the privilege encoder's parameters are no input: the target carries no gradient
+    return _plan("lg_train_enc_plan", abi.LgTrainEncArgs, abi.LgTrainTSPlan, n_rows,
+                 ((abi.TRAIN_ENC_HISTORY, history_widths), (abi.TRAIN_ENC_PRIVILEGE, privilege_widths)))
 
 
 class FusedTrainPassTS:
@@ -796,13 +641,10 @@ class FusedTrainPassTS:
     torch path, and so does a "TCN" (Conv1d) history encoder, which is refused by layer name."""
 
     def __init__(self, actor_critic):
-        dev = getattr(getattr(actor_critic, "std", None), "device", None)
-        if isinstance(dev, torch.device) and dev.type != "cuda":
-            raise ValueError(f"FusedTrainPassTS: the module is on {dev}, not on a HIP device (there is no CPU path)")
-        self.spec = describe_ts(actor_critic, dev)
-        self.device = dev
-        self._rl_workspace = self._enc_workspace = None
-        self._rl_calls = self._enc_calls = 0
+        self.device = _module_device(actor_critic, _TS)
+        self.spec = describe_ts(actor_critic, self.device)
+        self._rl = _Pass(_TS, "RL ", "lg_train_ts", ts_args, self.plan, self.rl_parameters, self.spec, self.device)
+        self._enc = _Pass(_TS, "encoder ", "lg_train_enc", enc_args, self.encoder_plan, self.encoder_parameters, self.spec, self.device)
 
     def rl_parameters(self):
         return self.spec.rl_parameters()
@@ -817,23 +659,11 @@ class FusedTrainPassTS:
     def encoder_plan(self, n_rows):
         return plan_enc(n_rows, self.spec.history_encoder.widths, self.spec.privilege_encoder.widths)
 
-    def _rl_workspace_for(self, n):
-        need = int(self.plan(n).workspace_floats)
-        if self._rl_workspace is None or self._rl_workspace.numel() < need:
-            self._rl_workspace = torch.empty(need, dtype=torch.float32, device=self.device)
-        return self._rl_workspace
-
-    def _enc_workspace_for(self, n):
-        need = int(self.encoder_plan(n).workspace_floats)
-        if self._enc_workspace is None or self._enc_workspace.numel() < need:
-            self._enc_workspace = torch.empty(need, dtype=torch.float32, device=self.device)
-        return self._enc_workspace
-
     def __call__(self, obs, privileged_obs, critic_obs):
         """(mu, sigma, values) of the mini-batch: (B, A), (B, A), (B, 1).  One launch on the current stream."""
-        return _PassTS.apply(self, obs, privileged_obs, critic_obs, *self.spec.rl_parameters())
+        return _apply(_RLFunction, self._rl, obs, privileged_obs, critic_obs)
 
     def encoder_loss(self, obs_history, privileged_obs, terminated):
         """mse_loss(history_encoder(obs_history) * terminated, privilege_encoder(privileged_obs).detach() * terminated) as a 0-dim tensor
         with autograd.  Two launches."""
-        return _EncLoss.apply(self, obs_history, privileged_obs, terminated, *self.spec.encoder_parameters())
+        return _apply(_LossFunction, self._enc, obs_history, privileged_obs, terminated)

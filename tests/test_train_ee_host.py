@@ -24,6 +24,11 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "lgtrainee.h")
 FIXTURE = os.path.join(ROOT, "tests", "golden", "ppo_ee_train.npz")
 CSRC = os.path.join(ROOT, "hcr_genesis_lr_cl_amd", "csrc")
+TILE_ROUTINES = ("stage_rows", "copy_out", "fwd_tile", "bwd_tile", "wgrad_wave", "combine_layer", "lds_stride", "slice_rule")
+PASS_ROUTINES = ("chain_forward", "chain_from_rows", "store_sigma", "seed_last_g", "bwd_layer", "chain_backward", "mse_tile", "loss_finalize",
+                 "wgrad_job", "combine_all", "check_desc", "plan_chain", "plan_layout", "plan_out", "bind_chain", "check_ws", "bind_heads", "done",
+                 "raise_lds", "launch_tile", "launch_backward")
+DEFINES = r"^(?:template <[^>]*> *)?(?:static |inline |__device__ |__forceinline__ )+[\w ]*[ *]"       # a definition at file scope of ...
 
 
 # ---- the structs --------------------------------------------------------------------------------------------------------------------------
@@ -62,18 +67,23 @@ def test_library_exports_the_entry_points():
         assert hasattr(lib, sym), sym
     from hcr_genesis_lr_cl_amd import build
     assert any(u[0] == "lg_train_ee" and u[1] == "lg_train_ee.hip" and any(d.endswith("lgtrainee.h") for d in u[3])
-               and "lg_train_tiles.h" in u[3] for u in build.units())
-    assert any(u[0] == "lg_train" and "lg_train_tiles.h" in u[3] for u in build.units())
+               and "lg_train_tiles.h" in u[3] and "lg_train_pass.h" in u[3] for u in build.units())
+    assert any(u[0] == "lg_train" and "lg_train_tiles.h" in u[3] and "lg_train_pass.h" in u[3] for u in build.units())
     assert "lg_train_ee.hip" in build.__doc__
     assert "TRAIN_EE_EXPORTS" in open(os.path.join(ROOT, "__graft_entry__.py")).read()          # the build's export check covers the list
-    # one copy of the layer routines: both units include the header, neither defines them
-    tiles = open(os.path.join(CSRC, "lg_train_tiles.h")).read()
-    for fn in ("stage_rows", "copy_out", "fwd_tile", "bwd_tile", "wgrad_wave", "combine_layer", "lds_stride", "slice_rule"):
-        assert len(re.findall(r"\b(?:void|int) " + fn + r"\(", tiles)) == 1, fn
-        for unit in ("lg_train.hip", "lg_train_ee.hip"):
-            src = open(os.path.join(CSRC, unit)).read()
-            assert '#include "lg_train_tiles.h"' in src and not re.findall(r"\b(?:void|int) " + fn + r"\(", src), (unit, fn)
-    for unit in ("lg_train_ee.hip", "lg_train_tiles.h"):
+    # one copy of the layer routines and of the pass routines: every unit reaches both headers, none defines any of them
+    units = {u: open(os.path.join(CSRC, u)).read() for u in ("lg_train.hip", "lg_train_ee.hip", "lg_train_ts.hip")}
+    for header, fns in (("lg_train_tiles.h", TILE_ROUTINES), ("lg_train_pass.h", PASS_ROUTINES)):
+        text = open(os.path.join(CSRC, header)).read()
+        other = open(os.path.join(CSRC, "lg_train_pass.h" if header == "lg_train_tiles.h" else "lg_train_tiles.h")).read()
+        for fn in fns:
+            assert len(re.findall(DEFINES + fn + r"\(", text, flags=re.M)) == 1, fn
+            assert not re.findall(DEFINES + fn + r"\(", other, flags=re.M), fn
+            for unit, src in units.items():
+                assert '#include "lg_train_pass.h"' in src and not re.findall(DEFINES + fn + r"\(", src, flags=re.M), (unit, fn)
+    assert not any(re.findall(DEFINES + r"plan_rest\(", src, flags=re.M) for src in units.values())      # plan_layout has taken its place
+    assert '#include "lg_train_tiles.h"' in open(os.path.join(CSRC, "lg_train_pass.h")).read()
+    for unit in ("lg_train_ee.hip", "lg_train_tiles.h", "lg_train_pass.h"):
         assert "atomic" not in open(os.path.join(CSRC, unit)).read().lower()                    # determinism is the house rule
 
 
@@ -355,7 +365,7 @@ def test_entry_points_refuse_null_descriptors_and_the_lds():
         assert getattr(lib, fn + "_backward")(C.byref(a), None) != 0
     # widths within the limit never exceed the LDS at 8 rows, with the loss tree's 2 KB too; the refusal is pinned where it would start
     assert 8 * 2 * tc.lds_stride(abi.POLICY_MAX_WIDTH) * 4 + ec.RED_BYTES <= tc.LDS_BYTES
-    assert "does not fit the 160 KB of LDS" in open(os.path.join(CSRC, "lg_train_ee.hip")).read()
+    assert "does not fit the 160 KB of LDS" in open(os.path.join(CSRC, "lg_train_pass.h")).read()
     # the RL backward leaves the estimator's gradient members alone: null ones are taken
     a = _good_ee()
     assert all(not a.chain[0].layer[i].grad_weight for i in range(3))

@@ -61,10 +61,12 @@ def test_library_exports_the_train_entry_points():
     for sym in declared:
         assert hasattr(lib, sym), sym
     from hcr_genesis_lr_cl_amd import build
-    assert any(u[0] == "lg_train" and u[1] == "lg_train.hip" and any(d.endswith("lgtrain.h") for d in u[3]) for u in build.units())
+    assert any(u[0] == "lg_train" and u[1] == "lg_train.hip" and any(d.endswith("lgtrain.h") for d in u[3]) and "lg_train_pass.h" in u[3]
+               for u in build.units())
     assert f"{len(build.units())} translation units" in build.__doc__ and "lg_train.hip" in build.__doc__
-    source = open(os.path.join(ROOT, "hcr_genesis_lr_cl_amd", "csrc", "lg_train.hip")).read()
-    assert "atomic" not in source.lower().replace("no atomics", "")            # determinism is the house rule
+    for unit in ("lg_train.hip", "lg_train_pass.h"):                           # the pass routines live in the shared header
+        source = open(os.path.join(ROOT, "hcr_genesis_lr_cl_amd", "csrc", unit)).read()
+        assert "atomic" not in source.lower().replace("no atomics", "")        # determinism is the house rule
     assert "lg_train" not in open(os.path.join(ROOT, "hcr_genesis_lr_cl_amd", "csrc", "lg_policy.hip")).read()   # the layer routine is a copy
 
 
@@ -242,7 +244,7 @@ def test_entry_points_refuse_null_descriptors_and_the_lds():
     # widths within the limit never exceed the LDS (two rows of 2052 floats, 8 of them: 131 KB), so the refusal is unreachable through
     # the limits; it is pinned where it would start
     assert 8 * 2 * tc.lds_stride(abi.POLICY_MAX_WIDTH) * 4 <= tc.LDS_BYTES < 16 * 2 * tc.lds_stride(abi.POLICY_MAX_WIDTH) * 4
-    assert "does not fit the 160 KB of LDS" in open(os.path.join(ROOT, "hcr_genesis_lr_cl_amd", "csrc", "lg_train.hip")).read()
+    assert "does not fit the 160 KB of LDS" in open(os.path.join(ROOT, "hcr_genesis_lr_cl_amd", "csrc", "lg_train_pass.h")).read()
     with pytest.raises(RuntimeError, match=r"lg_train_plan: chain\[0\] \(actor\)\.n_layers = 5"):
         train.plan(4, [3] * 6, [3, 1])
     # a forward-only descriptor (no gradient members) is what forward takes and backward refuses

@@ -66,14 +66,18 @@ def test_library_exports_the_entry_points():
         assert hasattr(lib, sym), sym
     from hcr_genesis_lr_cl_amd import build
     assert any(u[0] == "lg_train_ts" and u[1] == "lg_train_ts.hip" and any(d.endswith("lgtraints.h") for d in u[3])
-               and "lg_train_tiles.h" in u[3] for u in build.units())
+               and "lg_train_tiles.h" in u[3] and "lg_train_pass.h" in u[3] for u in build.units())
     assert "lg_train_ts.hip" in build.__doc__ and f"{len(build.units())} translation units" in build.__doc__
     assert "TRAIN_TS_EXPORTS" in open(os.path.join(ROOT, "__graft_entry__.py")).read()          # the build's export check covers the list
-    # one copy of the layer routines: the unit includes the header and defines none of them
+    # one copy of the layer and pass routines: the unit includes the shared header (and through it the tiles) and defines none of them
     src = open(os.path.join(CSRC, "lg_train_ts.hip")).read()
-    for fn in ("stage_rows", "copy_out", "fwd_tile", "bwd_tile", "wgrad_wave", "combine_layer", "lds_stride", "slice_rule"):
-        assert '#include "lg_train_tiles.h"' in src and not re.findall(r"\b(?:void|int) " + fn + r"\(", src), fn
-    assert "atomic" not in src.lower()                                                          # determinism is the house rule
+    assert '#include "lg_train_tiles.h"' in open(os.path.join(CSRC, "lg_train_pass.h")).read()
+    for fn in ("stage_rows", "copy_out", "fwd_tile", "bwd_tile", "wgrad_wave", "combine_layer", "lds_stride", "slice_rule", "chain_forward",
+               "chain_backward", "bwd_layer", "seed_last_g", "mse_tile", "loss_finalize", "wgrad_job", "combine_all", "plan_chain", "plan_layout",
+               "plan_rest", "bind_chain", "bind_heads", "check_ws", "done", "raise_lds", "launch_backward"):
+        assert '#include "lg_train_pass.h"' in src and not re.findall(r"\b(?:void|int|lds_f \*) ?" + fn + r"\(", src), fn
+    for unit in ("lg_train_ts.hip", "lg_train_pass.h"):
+        assert "atomic" not in open(os.path.join(CSRC, unit)).read().lower()                    # determinism is the house rule
 
 
 # ---- the restatement against the fixture ------------------------------------------------------------------------------------------------------
@@ -420,7 +424,7 @@ def test_entry_points_refuse_null_descriptors_and_the_lds():
         a = good(backward=False)                                              # a forward-only descriptor is what backward refuses
         assert getattr(lib, fn + "_backward")(C.byref(a), None) != 0
     assert 8 * 2 * tc.lds_stride(abi.POLICY_MAX_WIDTH) * 4 + sc.RED_BYTES <= tc.LDS_BYTES
-    assert "does not fit the 160 KB of LDS" in open(os.path.join(CSRC, "lg_train_ts.hip")).read()
+    assert "does not fit the 160 KB of LDS" in open(os.path.join(CSRC, "lg_train_pass.h")).read()
     # the encoder pass leaves the privilege encoder's gradient members alone: train.enc_args does not even fill them
     a = _good_enc()
     assert all(not a.chain[abi.TRAIN_ENC_PRIVILEGE].layer[i].grad_weight and not a.chain[abi.TRAIN_ENC_PRIVILEGE].layer[i].grad_bias for i in range(3))
