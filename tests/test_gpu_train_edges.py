@@ -1,7 +1,9 @@
-"""The fused learner passes on the GPU (csrc/lg_train.hip, csrc/lg_train_ee.hip, csrc/lg_train_tiles.h) at the edges of
-tests/train_edges.py, which the tables of tests/test_gpu_train.py and tests/test_gpu_train_ee.py do not reach: the 16- and 8-row tiles,
-NT = 4 over ragged widths, 31 and 32 batch slices with a short last one, layers of unequal slice counts, the finalize kernel's second
-trip, and the 16-byte row accesses under a stride.  Every case runs as those two files run theirs (their `run`) against the float64
+"""The fused learner passes on the GPU (csrc/lg_train.hip, csrc/lg_train_ee.hip, csrc/lg_train_ts.hip, csrc/lg_train_pass.h,
+csrc/lg_train_tiles.h) at the edges of tests/train_edges.py, which the tables of tests/test_gpu_train.py, tests/test_gpu_train_ee.py and
+tests/test_gpu_train_ts.py do not reach: the 16- and 8-row tiles, NT = 4 over ragged widths, 31 and 32 batch slices with a short last one,
+layers of unequal slice counts, the finalize kernels' second trip, and the 16-byte row accesses under a stride; for the teacher-student
+(TS) passes also both placements of the privilege encoder and a latent wider than a 16-column tile under the small tiles, four-layer
+encoders, and the two passes on different row tiles.  Every case runs as those three files run theirs (their `run`) against the float64
 restatement under the same factor-8 parity rule; bit-identical repeats, the independence of rows across the small tiles, and strided
 views with widths that are multiples of 4."""
 import numpy as np
@@ -12,15 +14,18 @@ from hcr_genesis_lr_cl_amd import train
 from tests import train_cases as tc
 from tests import train_edges as te
 from tests import train_ee_cases as ec
+from tests import train_ts_cases as sc
 from tests.test_gpu_train import dev, host, same_bits
 from tests.test_gpu_train import run as run_plain
 from tests.test_gpu_train_ee import run as run_ee
+from tests.test_gpu_train_ts import run as run_ts
 
 pytestmark = pytest.mark.gpu
 
 DEV = torch.device("cuda")
 RATIOS = []
 FILL = 7.25
+RUN = {"plain": run_plain, "ee": run_ee, "ts": run_ts}
 
 
 def run_case(row, B, x=None):
@@ -32,6 +37,12 @@ def run_case(row, B, x=None):
         tp = train.FusedTrainPass(m)
         assert tp.plan(B).row_tile == d["R"]
         return run_plain(x, m, tp)
+    if d["kind"] == "ts":
+        m = sc.Module(x, DEV)
+        tp = train.FusedTrainPassTS(m)
+        assert (tp.plan(B).row_tile, tp.encoder_plan(B).row_tile) == d["R"]
+        assert f"efb={tp.plan(B).enc_first_buffer}" in te.claimed(row, B)
+        return run_ts(x, m, tp)
     m = ec.Module(x, DEV)
     tp = train.FusedTrainPassEE(m)
     assert (tp.plan(B).row_tile, tp.estimator_plan(B).row_tile) == d["R"]
@@ -50,12 +61,13 @@ def test_parity_on_the_edge_table(case):
 
 
 # ---- determinism ------------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("case", [("r8", 25), ("tiny", 2113), ("fixture", 8193)], ids=te.case_id)
+@pytest.mark.parametrize("case", [("r8", 25), ("tiny", 2113), ("fixture", 8193), ("ts_r8_z", 25), ("ts_r16", 2049), ("ts_r8_even", 2049)], ids=te.case_id)
 def test_repeats_are_bit_identical(case):
-    """The 8-row tile, the 32-slice combine and the two-trip finalize: the same pass again on its own workspace, and a fresh one."""
+    """The 8-row tile, the 32-slice combine and the two-trip finalize: the same pass again on its own workspace, and a fresh one.  TS: the
+    8-row tile with Z = 65, unequal slices from 16-row tiles, and the two-trip finalize from 8-row tiles."""
     row, B = case
     assert case in te.CASES
-    run = run_plain if te.ROWS[row]["kind"] == "plain" else run_ee
+    run = RUN[te.ROWS[row]["kind"]]
     x = te.inputs(row, B)
     a, m, tp = run_case(row, B)
     b, _, _ = run(x, m, tp)
@@ -83,6 +95,43 @@ def test_rows_are_independent_across_the_small_tiles(case):
     for k in ("mu", "sigma", "values"):
         assert np.isnan(got[k][~others]).all(), k
         assert np.array_equal(got[k][others].view(np.uint32), clean[k][others].view(np.uint32)), k
+
+
+@pytest.mark.parametrize("case", [("ts_r16", 49), ("ts_r8_z", 25)], ids=te.case_id)
+def test_ts_rows_are_independent_across_the_small_tiles(case):
+    """The same two rows, through the path that only the TS pass has: a NaN in privileged_obs reaches the actor through the latent copied
+    behind the observations.  Those two rows of mu and sigma are NaN, every other row of them and every row of values keeps the clean run's
+    bits, the critic's gradients too, and the encoder loss (whose targets those rows are) is NaN.  A NaN in obs_history alone leaves mu,
+    sigma, values and every RL gradient bit for bit."""
+    row, B = case
+    R = te.ROWS[row]["R"][0]
+    assert case in te.CASES and te.ROWS[row]["R"] in ((8, 8), (16, 16)) and B > 2 * R
+    x = te.inputs(row, B)
+    rl = sc.rl_names(x["actor"], x["critic"], x["priv"])
+    clean, _, _ = run_case(row, B)
+    y = dict(x, privileged_obs=x["privileged_obs"].copy())
+    y["privileged_obs"][R - 1, 2] = np.nan
+    y["privileged_obs"][R, 0] = np.nan
+    got, _, _ = run_case(row, B, y)
+    others = np.ones(B, bool)
+    others[[R - 1, R]] = False
+    for k in ("mu", "sigma"):
+        assert np.isnan(got[k][~others]).all(), k
+        assert np.array_equal(got[k][others].view(np.uint32), clean[k][others].view(np.uint32)), k
+    for k in ["values"] + [n for n in rl if n.startswith("critic")]:
+        assert np.array_equal(got[k].view(np.uint32), clean[k].view(np.uint32)), k
+    assert np.isnan(got["loss"][0])
+    theirs = sc.torch_passes(y)
+    for n, g in zip(rl, theirs["rl_grads"]):                               # wherever torch's gradient is NaN, so is the kernel's
+        assert (np.isnan(got[n]) | ~np.isnan(g)).all(), n
+    assert np.isnan(got["privilege_encoder.0.weight"][:, [0, 2]]).all()    # back through the latent into the encoder's first layer
+    z = dict(x, obs_history=x["obs_history"].copy())
+    z["obs_history"][R - 1, 2] = np.nan
+    z["obs_history"][R, 0] = np.nan
+    got, _, _ = run_case(row, B, z)
+    assert np.isnan(got["loss"][0])
+    for k in ["mu", "sigma", "values"] + rl:                                 # the RL pass never reads the history
+        assert np.array_equal(got[k].view(np.uint32), clean[k].view(np.uint32)), k
 
 
 # ---- the 16-byte rows under a stride ----------------------------------------------------------------------------------------------------------
@@ -170,18 +219,48 @@ def _abi_ee(x, place):
     return ec.named(x, {k: host(v[k]) for k in ("mu", "sigma", "values")}, [host(g) for g in rl_grads], host(loss), [host(g) for g in est_grads])
 
 
-@pytest.mark.parametrize("kind", ["plain", "ee"])
+def _abi_ts(x, place):
+    B, (priv, actor, critic, hist) = te.VEC_B, te.VEC_TS
+    m = sc.Module(x, DEV)
+    D = m.std.device
+    spec = train.describe_ts(m, D)
+    A, V, Z = actor[-1], critic[-1], priv[-1]
+    p = _Placed(x, B, place, dict(obs=actor[0] - Z, privileged_obs=priv[0], critic_obs=critic[0], obs_history=hist[0], terminated=1, grad_mu=A,
+                                  grad_sigma=A, grad_values=V), dict(mu=A, sigma=A, values=V))
+    v = p.view
+    ws = torch.empty(int(train.plan_ts(B, priv, actor, critic).workspace_floats), device=DEV)
+    train._call("lg_train_ts_forward", train.ts_args(spec, v["obs"], v["privileged_obs"], v["critic_obs"], v["mu"], v["sigma"], v["values"], ws, device=D), D)
+    rl_grads = [torch.full_like(q, FILL) for q in spec.rl_parameters()]
+    a = train.ts_args(spec, v["obs"], v["privileged_obs"], v["critic_obs"], v["mu"], v["sigma"], v["values"], ws, rl_grads, v["grad_mu"], v["grad_sigma"],
+                      v["grad_values"], device=D)
+    train._call("lg_train_ts_backward", a, D)
+    ews = torch.empty(int(train.plan_enc(B, hist, priv).workspace_floats), device=DEV)
+    loss, up = torch.full((), FILL, device=DEV), torch.full((1,), float(x["upstream"]), device=DEV)
+    train._call("lg_train_enc_forward", train.enc_args(spec, v["obs_history"], v["privileged_obs"], v["terminated"], loss, ews, device=D), D)
+    enc_grads = [torch.full_like(q, FILL) for q in spec.encoder_parameters()]
+    e = train.enc_args(spec, v["obs_history"], v["privileged_obs"], v["terminated"], None, ews, enc_grads, up, device=D)
+    if place is not None:
+        assert (a.chain[0].in_stride, a.chain[1].in_stride, a.chain[2].in_stride, a.mu_stride, a.sigma_stride, a.values_stride, a.grad_mu_stride,
+                a.grad_sigma_stride, a.grad_values_stride, e.chain[0].in_stride, e.chain[1].in_stride, e.mask_stride) == (place[1],) * 12
+        assert (a.chain[1].input % 16 == 0) == (place[0] % 4 == 0) and (e.chain[0].input % 16 == 0) == (place[0] % 4 == 0)
+    train._call("lg_train_enc_backward", e, D)
+    torch.cuda.synchronize()
+    p.check_untouched()
+    return sc.named(x, {k: host(v[k]) for k in ("mu", "sigma", "values")}, [host(g) for g in rl_grads], host(loss), [host(g) for g in enc_grads])
+
+
+@pytest.mark.parametrize("kind", ["plain", "ee", "ts"])
 def test_vector_rows_under_a_stride(kind):
     """The C ABI on column slices of wider filled matrices, every width a multiple of 4: base and stride on 16 bytes (the 16-byte accesses
     with stride != width), a base off 16 bytes and an odd stride (the fallbacks) each give the bits of the contiguous call, which lies
     within the parity rule; gaps, inputs and incoming gradients are untouched."""
     plain = kind == "plain"
-    x = te.draw(kind, te.VEC_PLAIN if plain else te.VEC_EE, te.VEC_B, 977)
-    call = _abi_plain if plain else _abi_ee
+    x = te.draw(kind, dict(plain=te.VEC_PLAIN, ee=te.VEC_EE, ts=te.VEC_TS)[kind], te.VEC_B, 977)
+    call = dict(plain=_abi_plain, ee=_abi_ee, ts=_abi_ts)[kind]
     clean = call(x, None)
-    ref64, ref32 = te.plain_references(x) if plain else ec.references(x)
-    (tc if plain else ec).check_parity(clean, ref64, ref32, f"vector rows, {kind}, contiguous", RATIOS)
-    through_autograd, _, _ = (run_plain if plain else run_ee)(x)
+    ref64, ref32 = te.plain_references(x) if plain else te.MODULES[kind].references(x)
+    te.MODULES[kind].check_parity(clean, ref64, ref32, f"vector rows, {kind}, contiguous", RATIOS)
+    through_autograd, _, _ = RUN[kind](x)
     assert same_bits(clean, through_autograd)
     for name, place in te.PLACEMENTS.items():
         assert same_bits(call(x, place), clean), name

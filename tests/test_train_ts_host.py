@@ -571,3 +571,9 @@ def test_case_table_covers_the_edges():
         assert 0.1 <= (np.abs(pre) >= x["clip"]).mean() <= 0.9 and np.abs(np.abs(pre) - x["clip"]).min() >= 1e-3
     x = sc.make_inputs("fixture_b257")
     assert 0.1 <= 1 - x["terminated"].mean() <= 0.6                                                     # masked and unmasked rows
+    # what this table stops short of (the 16-row tile in both passes, the 8-row tile beyond net `wide`, four-layer encoders, 31 slices, the
+    # finalize's second trip from 8-row tiles, the two passes on different tiles) are the rows of kind "ts" of tests/train_edges.py
+    from tests import train_edges as te
+    ts = [c for c in te.CASES if te.ROWS[c[0]]["kind"] == "ts"]
+    assert te.TS_TABLE_TAGS <= set().union(*(te.claimed(*c) for c in ts)) and {te.ROWS[r]["R"] for r, _ in ts} >= {(16, 16), (8, 8), (8, 32), (16, 32)}
+    assert all(te.claimed(*c) <= te.tags(*c) for c in ts)

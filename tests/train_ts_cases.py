@@ -204,13 +204,14 @@ def rl_forward(x, dtype=np.float64):
     return dict(mu=mu, sigma=mu * 0 + std, values=ca[-1], cat=cat, acts=(pa, aa, ca))
 
 
-def chain_backward(layers, acts, G, dtype, pers=None, input_grad=False):
+def chain_backward(layers, acts, G, dtype, pers=None, input_grad=False, drop_last=False):
     """The gradients [W0, b0, W1, b1, ...] of one chain from G of its last layer (elu' from the stored output), the batch sums per slice of
-    pers[li] rows as the kernel forms them; with input_grad also G through layer 0, with no activation factor."""
+    pers[li] rows as the kernel forms them; with input_grad also G through layer 0, with no activation factor.  drop_last: every sum without
+    its last slice (a planted defect)."""
     B, out = G.shape[0], []
     for li in range(len(layers) - 1, -1, -1):
         H, per = acts[li], B if pers is None else int(pers[li])
-        out = [tc.slice_sum(per, G, H), tc.slice_sum(per, G, phases=4)] + out
+        out = [tc.slice_sum(per, G, H, drop_last=drop_last), tc.slice_sum(per, G, phases=4, drop_last=drop_last)] + out
         if li:
             G = ((G @ layers[li][0]) * np.where(H > 0, 1, H + 1)).astype(dtype)
     return out, ((G @ layers[0][0]).astype(dtype) if input_grad else None)
@@ -219,7 +220,8 @@ def chain_backward(layers, acts, G, dtype, pers=None, input_grad=False):
 def rl_backward(x, dtype=np.float64, slices=None, wrong=None):
     """The gradients of the RL pass in rl_names order (actor, critic, privilege encoder, std).  The latent columns [O, O + Z) of actor layer
     0's input gradient are G of the privilege encoder's last layer.  `slices`: dict(std=rows, actor=[rows per layer], critic=[...],
-    priv=[...]) as the plan slices each sum, or None.  wrong="latent_cols0": the latent gradient from columns [0, Z) (a planted defect)."""
+    priv=[...]) as the plan slices each sum, or None.  Planted defects: wrong="latent_cols0" takes the latent gradient from columns [0, Z),
+    wrong="priv_drop_last_slice" leaves the last slice out of the privilege encoder's sums (it needs `slices` with more than one)."""
     fw = rl_forward(x, dtype)
     actor, critic, priv, _ = split_rl(x, dtype)
     pa, aa, ca = fw["acts"]
@@ -232,7 +234,10 @@ def rl_backward(x, dtype=np.float64, slices=None, wrong=None):
     Z = pa[-1].shape[1]
     O = dcat.shape[1] - Z
     gz = dcat[:, :Z] if wrong == "latent_cols0" else dcat[:, O:]
-    gp, _ = chain_backward(priv, pa, np.ascontiguousarray(gz), dtype, s.get("priv"))
+    drop = wrong == "priv_drop_last_slice"
+    if drop and not ("priv" in s and B > max(s["priv"])):
+        raise ValueError("priv_drop_last_slice needs more than one slice in every sum of the privilege encoder")
+    gp, _ = chain_backward(priv, pa, np.ascontiguousarray(gz), dtype, s.get("priv"), drop_last=drop)
     return ga + gc + gp + [tc.slice_sum(int(s.get("std", B)), np.asarray(x["grad_sigma"]).astype(dtype))]
 
 
