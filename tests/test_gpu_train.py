@@ -3,33 +3,23 @@ tests/train_cases.py under the project's parity rule, and its conventions: .grad
 repeats, Hardtanh-saturated means, strided views, the NaN row, the non-finite grad_sigma, weights changed in place, the stale-forward
 refusal, the six steps of the reference's PPO.update() end to end (train pass, FusedPPOLoss, FusedAdam) and one whole update step as a
 HIP graph."""
-import copy
 import os
 
 import numpy as np
 import pytest
 import torch
-import torch.nn as nn
 
 from hcr_genesis_lr_cl_amd import optim, ppo_loss, train
-from tests import optim_cases as oc
 from tests import train_cases as tc
+from tests import train_gpu as tg
+from tests.train_gpu import COTANGENTS, DEV, dev, host, same_bits
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "ppo_train.npz")
 RATIOS = []
-COTANGENTS = ("grad_mu", "grad_sigma", "grad_values")
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
-
-
-def host(t):
-    return t.detach().cpu().numpy()
+references = tc.references
 
 
 def run(x, m=None, tp=None):
@@ -45,27 +35,17 @@ def run(x, m=None, tp=None):
     return got, m, tp
 
 
-def same_bits(a, b):
-    return all(np.array_equal(np.asarray(a[k]).view(np.uint32), np.asarray(b[k]).view(np.uint32)) for k in a) and set(a) == set(b)
-
-
-def references(x):
-    t32 = tc.torch_pass(x)
-    return tc.named(x, tc.forward(x), tc.backward(x)), tc.named(x, t32, t32["grads"])
-
-
 # ---- parity -----------------------------------------------------------------------------------------------------------------------------------
-PARITY_CASES = list(tc.CASES) + [f"{net}_ragged" for net in tc.RAGGED_SLICE_NETS]
+PARITY_CASES = tg.parity_cases(tc)
+
+
+def _slices_raggedly(net, b):
+    p = train.plan(b, *tc.NETS[net])
+    assert any(S > 1 and b % per for S, per in zip(list(p.slices[0]) + list(p.slices[1]), list(p.slice_rows[0]) + list(p.slice_rows[1])) if S)
 
 
 def case_inputs(name):
-    if name.endswith("_ragged"):                                      # the smallest batch the plan slices raggedly for that net
-        net = name[:-len("_ragged")]
-        b = tc.smallest_ragged_b(net)
-        p = train.plan(b, *tc.NETS[net])
-        assert any(S > 1 and b % per for S, per in zip(list(p.slices[0]) + list(p.slices[1]), list(p.slice_rows[0]) + list(p.slice_rows[1])) if S)
-        return tc.make_inputs(dict(net=net, B=b, seed=400 + len(net)))
-    return tc.make_inputs(name)
+    return tg.case_inputs(tc, name, 400, _slices_raggedly)
 
 
 @pytest.mark.parametrize("name", PARITY_CASES)
@@ -83,7 +63,7 @@ def _loss_inputs(x, rng):
     f = lambda v: np.ascontiguousarray(v, dtype=np.float32)
     old_mu, old_sigma = f(fw["mu"] + 0.1 * rng.normal(size=(B, A))), f(fw["sigma"] * np.exp(0.03 * rng.normal(size=(B, A))))
     actions = f(old_mu + old_sigma * rng.normal(size=(B, A)))
-    old_lp = f((-(actions - old_mu) ** 2 / (2 * old_sigma ** 2) - np.log(old_sigma) - 0.9189385332046727).sum(-1, keepdims=True))
+    old_lp = f((-(actions - old_mu) ** 2 / (2 * old_sigma ** 2) - np.log(old_sigma) - tg.HALF_LOG_2PI).sum(-1, keepdims=True))
     target = f(rng.normal(size=(B, 1)))
     return dict(actions=actions, old_log_prob=old_lp, advantages=f(rng.normal(size=(B, 1))), returns=f(target + 0.5 * rng.normal(size=(B, 1))),
                 target_values=target, old_mu=old_mu, old_sigma=old_sigma)
@@ -265,57 +245,39 @@ def test_a_non_finite_grad_sigma_reaches_grad_std_only():
         assert np.isnan(theirs["actor.0.weight"]).any()               # the departure: autograd poisons the actor here
 
 
+
+
 # ---- the whole update -------------------------------------------------------------------------------------------------------------------------
+def _init_inputs(fx):
+    return dict(tc.fixture_step(fx, 0), params=[np.asarray(p, np.float32) for p in fx["init"]])
+
+
 def _torch_update(fx, dtype):
-    """The reference's mini-batch steps on the fixture's columns (rounded to float32 first) in torch ops of `dtype` on the CPU: the module,
-    the loss of ppo.py:157-218, the host rate rule and its three lines.  Returns (per step the parameters as float64 numpy, rates)."""
-    cfg = fx["cfg"]
-    x = dict(tc.fixture_step(fx, 0), params=[np.asarray(p, np.float32) for p in fx["init"]])
-    m = tc.Module(x, dtype=dtype)
-    opt = torch.optim.Adam(m.parameters(), lr=cfg["lr0"], betas=(cfg["beta1"], cfg["beta2"]), eps=cfg["eps"])
+    """The reference's mini-batch steps on the fixture's columns in torch ops of `dtype` on the CPU (tests/train_gpu.torch_rl_update).
+    Returns (per step the parameters by name as float64 numpy, rates)."""
+    m = tc.Module(_init_inputs(fx), dtype=dtype)
     assert [n for n, _ in m.named_parameters()] == fx["names"]
-    lr, lrs, out, clip = cfg["lr0"], [], [], cfg["clip_param"]
-    for s in range(cfg["steps"]):
-        t = {k: torch.from_numpy(np.asarray(fx[k][s], np.float32)).to(dtype) for k in tc.FIXTURE_COLUMNS}
-        mu, sigma, value = m(t["obs"], t["critic_obs"])
-        logp = (-(t["actions"] - mu) ** 2 / (2 * sigma ** 2) - sigma.log() - 0.9189385332046727).sum(-1)
-        with torch.no_grad():
-            kl = torch.sum(torch.log(sigma / t["old_sigma"] + 1.e-5) + (t["old_sigma"] ** 2 + (t["old_mu"] - mu) ** 2) / (2.0 * sigma ** 2) - 0.5,
-                           dim=-1).mean()
-        lr = ppo_loss.adjust_learning_rate(kl, lr, cfg["desired_kl"])
-        for group in opt.param_groups:
-            group["lr"] = lr
-        ratio, adv = torch.exp(logp - t["old_log_prob"].squeeze(-1)), t["advantages"].squeeze(-1)
-        surrogate = torch.max(-adv * ratio, -adv * torch.clamp(ratio, 1.0 - clip, 1.0 + clip)).mean()
-        vc = t["target_values"] + (value - t["target_values"]).clamp(-clip, clip)
-        value_loss = torch.max((value - t["returns"]).pow(2), (vc - t["returns"]).pow(2)).mean()
-        entropy = (1.4189385332046727 + sigma.log()).sum(-1).mean()
-        loss = surrogate + cfg["value_loss_coef"] * value_loss - cfg["entropy_coef"] * entropy
-        opt.zero_grad()
-        loss.backward()
-        nn.utils.clip_grad_norm_(m.parameters(), cfg["max_grad_norm"])
-        opt.step()
-        lrs.append(lr)
-        out.append([p.detach().double().numpy().copy() for p in m.parameters()])
-    return out, lrs
+    snap = lambda: {n: p.detach().double().numpy().copy() for n, p in m.named_parameters()}
+    return tg.torch_rl_update(fx, tc.FIXTURE_COLUMNS, lambda c: m(c["obs"], c["critic_obs"]), list(m.parameters()), snap, dtype)
 
 
-def _fused_update(m, batches, cfg, tp=None, loss_fn=None, opt=None):
-    tp = tp or train.FusedTrainPass(m)
-    loss_fn = loss_fn or ppo_loss.FusedPPOLoss(clip_param=cfg["clip_param"], value_loss_coef=cfg["value_loss_coef"], entropy_coef=cfg["entropy_coef"])
-    opt = opt or optim.FusedAdam(m.named_parameters(), lr=cfg["lr0"], betas=(cfg["beta1"], cfg["beta2"]), eps=cfg["eps"],
-                                 max_grad_norm=cfg["max_grad_norm"], desired_kl=cfg["desired_kl"])
-    for t in batches:
-        mu, sigma, values = tp(t["obs"], t["critic_obs"])
-        out = loss_fn(mu, sigma, values, t["actions"], t["old_log_prob"], t["advantages"], t["returns"], t["target_values"], t["old_mu"], t["old_sigma"])
-        opt.zero_grad()
+class _Learner:
+    """FusedTrainPass + FusedPPOLoss + FusedAdam on a module: the fused PPO mini-batch step."""
+
+    def __init__(self, m, cfg):
+        self.tp = train.FusedTrainPass(m)
+        self.loss_fn = ppo_loss.FusedPPOLoss(clip_param=cfg["clip_param"], value_loss_coef=cfg["value_loss_coef"], entropy_coef=cfg["entropy_coef"])
+        self.opt = optim.FusedAdam(m.named_parameters(), lr=cfg["lr0"], betas=(cfg["beta1"], cfg["beta2"]), eps=cfg["eps"],
+                                   max_grad_norm=cfg["max_grad_norm"], desired_kl=cfg["desired_kl"])
+        self.optimizers = (self.opt,)
+
+    def step(self, t):
+        mu, sigma, values = self.tp(t["obs"], t["critic_obs"])
+        out = self.loss_fn(mu, sigma, values, t["actions"], t["old_log_prob"], t["advantages"], t["returns"], t["target_values"], t["old_mu"], t["old_sigma"])
+        self.opt.zero_grad()
         out.loss.backward()
-        opt.step(kl_mean=out.kl_mean)
-        yield opt, out
-
-
-def _fixture_batches(fx):
-    return [{k: dev(fx[k][s]) for k in tc.FIXTURE_COLUMNS} for s in range(fx["cfg"]["steps"])]
+        self.opt.step(kl_mean=out.kl_mean)
+        return out
 
 
 def test_fixture_update_end_to_end():
@@ -327,21 +289,13 @@ def test_fixture_update_end_to_end():
     ref64, lrs64 = _torch_update(fx, torch.float64)
     ref32, lrs32 = _torch_update(fx, torch.float32)
     assert lrs64 == lrs32 == [float(v) for v in fx["lr"]]
-    assert max(np.abs(a - b).max() for a, b in zip(ref64[-1], fx["params"][-1])) < 1e-5
-    x = dict(tc.fixture_step(fx, 0), params=[np.asarray(p, np.float32) for p in fx["init"]])
-    m = tc.Module(x, DEV)
-    for s, (opt, out) in enumerate(_fused_update(m, _fixture_batches(fx), cfg)):
-        assert opt.lr == float(fx["lr"][s]), (s, opt.lr, fx["lr"][s])
-        got = dict(zip(fx["names"], [host(p) for p in m.parameters()]))
-        worst, bad = 0.0, []
-        for name, r64, r32 in zip(fx["names"], ref64[s], ref32[s]):
-            err, bound = oc.max_err(got[name], r64), oc.parity_bound(oc.max_err(r32, r64), r64)
-            worst = max(worst, err / (bound / oc.PARITY_FACTOR))
-            if not err <= bound:
-                bad.append((name, err, bound))
-        print(f"fixture step {s}: worst parameter ratio {worst:.3f} (allowed {oc.PARITY_FACTOR:g})")
-        RATIOS.append((f"fixture step {s}", dict(parameters=worst)))
-        assert not bad, (s, bad)
+    assert max(np.abs(ref64[-1][n] - b).max() for n, b in zip(fx["names"], fx["params"][-1])) < 1e-5
+    m = tc.Module(_init_inputs(fx), DEV)
+    learner = _Learner(m, cfg)
+    for s, t in enumerate(tg.fixture_batches(fx, tc.FIXTURE_COLUMNS, cfg["steps"])):
+        learner.step(t)
+        assert learner.opt.lr == float(fx["lr"][s]), (s, learner.opt.lr, fx["lr"][s])
+        tg.check_parameters({n: host(p) for n, p in m.named_parameters()}, ref64[s], ref32[s], s, RATIOS)
 
 
 def test_captured_update_step_replays_like_eager_steps():
@@ -349,49 +303,11 @@ def test_captured_update_step_replays_like_eager_steps():
     times with the mini-batch rewritten in place in between: the parameters, the rate and the step count are those of three eager steps
     bit for bit."""
     fx = tc.load_fixture(FIXTURE)
-    cfg = fx["cfg"]
-    batches = _fixture_batches(fx)[:3]
-    x = dict(tc.fixture_step(fx, 0), params=[np.asarray(p, np.float32) for p in fx["init"]])
-    eager = tc.Module(x, DEV)
-    for opt_e, _ in _fused_update(eager, batches, cfg):
-        pass
-    torch.cuda.synchronize()
-
-    m = tc.Module(x, DEV)
-    static = {k: torch.zeros_like(v) for k, v in batches[0].items()}
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(stream):                                   # warm-up on the side stream, on a module of its own
-        for _ in _fused_update(copy.deepcopy(m), [batches[0]], cfg):
-            pass
-    torch.cuda.current_stream().wait_stream(stream)
-    torch.cuda.synchronize()
-    tp = train.FusedTrainPass(m)
-    loss_fn = ppo_loss.FusedPPOLoss(clip_param=cfg["clip_param"], value_loss_coef=cfg["value_loss_coef"], entropy_coef=cfg["entropy_coef"])
-    opt = optim.FusedAdam(m.named_parameters(), lr=cfg["lr0"], betas=(cfg["beta1"], cfg["beta2"]), eps=cfg["eps"],
-                          max_grad_norm=cfg["max_grad_norm"], desired_kl=cfg["desired_kl"])
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=stream):
-        for _ in _fused_update(m, [static], cfg, tp, loss_fn, opt):
-            pass
-    torch.cuda.synchronize()
-    assert opt.step_count == 0                                        # capturing runs nothing
-    for t in batches:
-        for k, v in t.items():
-            static[k].copy_(v)
-        graph.replay()
-    torch.cuda.synchronize()
-    assert opt.step_count == 3 and opt.lr == opt_e.lr
-    for (n, a), b in zip(m.named_parameters(), eager.parameters()):
-        assert np.array_equal(host(a).view(np.uint32), host(b).view(np.uint32)), n
+    x = _init_inputs(fx)
+    tg.replays_like_eager_steps(lambda: tc.Module(x, DEV), lambda m: _Learner(m, fx["cfg"]), tg.fixture_batches(fx, tc.FIXTURE_COLUMNS, 3))
 
 
 def test_zz_print_the_parity_ratios():
     """Not a check of its own: the worst |kernel - f64| / max(|torch-f32 - f64|, ulp) per tensor class over every parity check above, for
     DESIGN.md's table."""
-    worst = {}
-    for _, ratios in RATIOS:
-        for k, v in ratios.items():
-            worst[k] = max(worst.get(k, 0.0), v)
-    for k, v in worst.items():
-        print(f"PARITY {k}: {v:.3f} over {len(RATIOS)} checks")
+    tg.print_parity_ratios(RATIOS)

@@ -14,15 +14,15 @@ from hcr_genesis_lr_cl_amd import train
 from tests import train_cases as tc
 from tests import train_edges as te
 from tests import train_ee_cases as ec
+from tests import train_gpu as tg
 from tests import train_ts_cases as sc
-from tests.test_gpu_train import dev, host, same_bits
 from tests.test_gpu_train import run as run_plain
 from tests.test_gpu_train_ee import run as run_ee
 from tests.test_gpu_train_ts import run as run_ts
+from tests.train_gpu import DEV, dev, host, same_bits
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda")
 RATIOS = []
 FILL = 7.25
 RUN = {"plain": run_plain, "ee": run_ee, "ts": run_ts}
@@ -254,12 +254,11 @@ def test_vector_rows_under_a_stride(kind):
     """The C ABI on column slices of wider filled matrices, every width a multiple of 4: base and stride on 16 bytes (the 16-byte accesses
     with stride != width), a base off 16 bytes and an odd stride (the fallbacks) each give the bits of the contiguous call, which lies
     within the parity rule; gaps, inputs and incoming gradients are untouched."""
-    plain = kind == "plain"
     x = te.draw(kind, dict(plain=te.VEC_PLAIN, ee=te.VEC_EE, ts=te.VEC_TS)[kind], te.VEC_B, 977)
     call = dict(plain=_abi_plain, ee=_abi_ee, ts=_abi_ts)[kind]
     clean = call(x, None)
-    ref64, ref32 = te.plain_references(x) if plain else te.MODULES[kind].references(x)
-    te.MODULES[kind].check_parity(clean, ref64, ref32, f"vector rows, {kind}, contiguous", RATIOS)
+    ref64, ref32 = te.KINDS[kind].mod.references(x)
+    te.KINDS[kind].mod.check_parity(clean, ref64, ref32, f"vector rows, {kind}, contiguous", RATIOS)
     through_autograd, _, _ = RUN[kind](x)
     assert same_bits(clean, through_autograd)
     for name, place in te.PLACEMENTS.items():
@@ -269,9 +268,4 @@ def test_vector_rows_under_a_stride(kind):
 def test_zz_print_the_parity_ratios():
     """Not a check of its own: the worst |kernel - f64| / max(|torch-f32 - f64|, ulp) per tensor class over every parity check above, for
     DESIGN.md."""
-    worst = {}
-    for _, ratios in RATIOS:
-        for k, v in ratios.items():
-            worst[k] = max(worst.get(k, 0.0), v)
-    for k, v in worst.items():
-        print(f"PARITY {k}: {v:.3f} over {len(RATIOS)} checks")
+    tg.print_parity_ratios(RATIOS)

@@ -3,7 +3,6 @@ float64 restatement of tests/train_ee_cases.py under the project's parity rule, 
 end to end (6 RL steps, 12 estimator steps; FusedTrainPassEE, FusedPPOLoss, two FusedAdams), bit-identical repeats, one RL step plus one
 estimator step as a HIP graph, strided views, weights changed in place, the stale-forward refusal per pass, the estimator's .grad left
 alone by the RL backward, the fully masked batch and the NaN row."""
-import copy
 import os
 
 import numpy as np
@@ -12,24 +11,15 @@ import torch
 import torch.nn as nn
 
 from hcr_genesis_lr_cl_amd import optim, ppo_loss, train
-from tests import optim_cases as oc
 from tests import train_ee_cases as ec
+from tests import train_gpu as tg
+from tests.train_gpu import COTANGENTS, DEV, dev, host, same_bits
 
 pytestmark = pytest.mark.gpu
 
-DEV = torch.device("cuda")
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 FIXTURE = os.path.join(ROOT, "tests", "golden", "ppo_ee_train.npz")
 RATIOS = []
-COTANGENTS = ("grad_mu", "grad_sigma", "grad_values")
-
-
-def dev(a):
-    return torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32)).to(DEV)
-
-
-def host(t):
-    return t.detach().cpu().numpy()
 
 
 def run(x, m=None, tp=None):
@@ -51,21 +41,12 @@ def run(x, m=None, tp=None):
     return got, m, tp
 
 
-def same_bits(a, b):
-    return set(a) == set(b) and all(np.array_equal(np.asarray(a[k]).view(np.uint32), np.asarray(b[k]).view(np.uint32)) for k in a)
-
-
 # ---- parity -----------------------------------------------------------------------------------------------------------------------------------
-PARITY_CASES = list(ec.CASES) + [f"{net}_ragged" for net in ec.RAGGED_SLICE_NETS]
+PARITY_CASES = tg.parity_cases(ec)
 
 
 def case_inputs(name):
-    if name.endswith("_ragged"):                                      # the smallest batch either plan slices raggedly for that net
-        net = name[:-len("_ragged")]
-        b = ec.smallest_ragged_b(net)
-        assert b <= 257
-        return ec.make_inputs(dict(net=net, B=b, seed=800 + len(net)))
-    return ec.make_inputs(name)
+    return tg.case_inputs(ec, name, 800)
 
 
 @pytest.mark.parametrize("name", PARITY_CASES)
@@ -82,38 +63,15 @@ def _init_inputs(fx):
 
 
 def _torch_update(fx, dtype):
-    """The reference's PPO_EE.update() on the fixture's columns (rounded to float32 first) in torch ops of `dtype` on the CPU.  Returns
-    (per step, RL steps then estimator steps, the parameters by name as float64 numpy; the RL rates)."""
+    """The reference's PPO_EE.update() on the fixture's columns (rounded to float32 first) in torch ops of `dtype` on the CPU: the RL steps
+    of tests/train_gpu.torch_rl_update, then the estimator steps.  Returns (per step, RL steps then estimator steps, the parameters by name
+    as float64 numpy; the RL rates)."""
     cfg = fx["cfg"]
     m = ec.Module(_init_inputs(fx), dtype=dtype)
     t = lambda a: torch.from_numpy(np.asarray(a, np.float32)).to(dtype)
-    betas = (cfg["beta1"], cfg["beta2"])
-    opt = torch.optim.Adam(m.rl_parameters(), lr=cfg["lr0"], betas=betas, eps=cfg["eps"])
-    est_opt = torch.optim.Adam(m.estimator_parameters(), lr=cfg["estimator_lr"], betas=betas, eps=cfg["eps"])
     snap = lambda: {n: p.detach().double().numpy().copy() for n, p in m.named_parameters()}
-    lr, lrs, out, clip = cfg["lr0"], [], [], cfg["clip_param"]
-    for s in range(cfg["steps"]):
-        c = {k: t(fx[k][s]) for k in ec.FIXTURE_COLUMNS}
-        mu, sigma, value = m(c["features"], c["critic_obs"])
-        logp = (-(c["actions"] - mu) ** 2 / (2 * sigma ** 2) - sigma.log() - 0.9189385332046727).sum(-1)
-        with torch.no_grad():
-            kl = torch.sum(torch.log(sigma / c["old_sigma"] + 1.e-5) + (c["old_sigma"] ** 2 + (c["old_mu"] - mu) ** 2) / (2.0 * sigma ** 2) - 0.5,
-                           dim=-1).mean()
-        lr = ppo_loss.adjust_learning_rate(kl, lr, cfg["desired_kl"])
-        for group in opt.param_groups:
-            group["lr"] = lr
-        ratio, adv = torch.exp(logp - c["old_log_prob"].squeeze(-1)), c["advantages"].squeeze(-1)
-        surrogate = torch.max(-adv * ratio, -adv * torch.clamp(ratio, 1.0 - clip, 1.0 + clip)).mean()
-        vc = c["target_values"] + (value - c["target_values"]).clamp(-clip, clip)
-        value_loss = torch.max((value - c["returns"]).pow(2), (vc - c["returns"]).pow(2)).mean()
-        entropy = (1.4189385332046727 + sigma.log()).sum(-1).mean()
-        loss = surrogate + cfg["value_loss_coef"] * value_loss - cfg["entropy_coef"] * entropy
-        opt.zero_grad()
-        loss.backward()
-        nn.utils.clip_grad_norm_(m.rl_parameters(), cfg["max_grad_norm"])
-        opt.step()
-        lrs.append(lr)
-        out.append(snap())
+    out, lrs = tg.torch_rl_update(fx, ec.FIXTURE_COLUMNS, lambda c: m(c["features"], c["critic_obs"]), m.rl_parameters(), snap, dtype)
+    est_opt = torch.optim.Adam(m.estimator_parameters(), lr=cfg["estimator_lr"], betas=(cfg["beta1"], cfg["beta2"]), eps=cfg["eps"])
     for s in range(cfg["est_steps"]):
         loss = m.estimator_loss(t(fx["est_features"][s]), t(fx["est_labels"][s]), t(fx["est_terminated"][s]))
         est_opt.zero_grad()
@@ -135,6 +93,7 @@ class _Learner:
                                       max_grad_norm=cfg["max_grad_norm"], desired_kl=cfg["desired_kl"])
         self.est_opt = optim.FusedAdam(list(zip(self.tp.spec.estimator_parameter_names(), self.tp.estimator_parameters())), lr=cfg["estimator_lr"],
                                        betas=betas, eps=cfg["eps"], max_grad_norm=cfg["max_grad_norm"])
+        self.optimizers = (self.rl_opt, self.est_opt)
 
     def rl_step(self, c):
         mu, sigma, values = self.tp(c["features"], c["critic_obs"])
@@ -151,13 +110,10 @@ class _Learner:
         self.est_opt.step()
         return loss
 
-
-def _rl_batches(fx):
-    return [{k: dev(fx[k][s]) for k in ec.FIXTURE_COLUMNS} for s in range(fx["cfg"]["steps"])]
-
-
-def _est_batches(fx):
-    return [{k: dev(fx[k][s]) for k in ("est_features", "est_labels", "est_terminated")} for s in range(fx["cfg"]["est_steps"])]
+    def step(self, b):
+        """One RL step and one estimator step on a batch that holds the columns of both."""
+        self.rl_step(b)
+        self.est_step(b)
 
 
 def test_fixture_update_end_to_end():
@@ -174,7 +130,7 @@ def test_fixture_update_end_to_end():
     assert max(np.abs(ref64[cfg["steps"] - 1][n] - fx["params"][-1][n]).max() for n in fx["names"]) < 1e-5
     m = ec.Module(_init_inputs(fx), DEV)
     learner = _Learner(m, cfg)
-    rl, est = _rl_batches(fx), _est_batches(fx)
+    rl, est = tg.fixture_batches(fx, ec.FIXTURE_COLUMNS, cfg["steps"]), tg.fixture_batches(fx, ec.EST_COLUMNS, cfg["est_steps"])
     for s in range(cfg["steps"] + cfg["est_steps"]):
         if s < cfg["steps"]:
             learner.rl_step(rl[s])
@@ -182,17 +138,7 @@ def test_fixture_update_end_to_end():
         else:
             loss = learner.est_step(est[s - cfg["steps"]])
             assert abs(float(loss.detach()) - fx["est_loss"][s - cfg["steps"]]) < 1e-4
-        got = {n: host(p) for n, p in m.named_parameters()}
-        worst, bad = 0.0, []
-        for name in fx["names"]:
-            r64, r32 = ref64[s][name], ref32[s][name]
-            err, bound = oc.max_err(got[name], r64), oc.parity_bound(oc.max_err(r32, r64), r64)
-            worst = max(worst, err / (bound / oc.PARITY_FACTOR))
-            if not err <= bound:
-                bad.append((name, err, bound))
-        print(f"fixture step {s}: worst parameter ratio {worst:.3f} (allowed {oc.PARITY_FACTOR:g})")
-        RATIOS.append((f"fixture step {s}", dict(parameters=worst)))
-        assert not bad, (s, bad)
+        tg.check_parameters({n: host(p) for n, p in m.named_parameters()}, ref64[s], ref32[s], s, RATIOS)
     assert learner.rl_opt.step_count == cfg["steps"] and learner.est_opt.step_count == cfg["est_steps"]
 
 
@@ -200,41 +146,9 @@ def test_captured_steps_replay_like_eager_steps():
     """One RL step plus one estimator step captured on one stream as a HIP graph and replayed three times with the mini-batches rewritten
     in place in between: every parameter, the rate and the step counts are those of three eager pairs of steps, bit for bit."""
     fx = ec.load_fixture(FIXTURE)
-    cfg = fx["cfg"]
-    rl, est = _rl_batches(fx)[:3], _est_batches(fx)[:3]
     x = _init_inputs(fx)
-    eager = ec.Module(x, DEV)
-    le = _Learner(eager, cfg)
-    for c, e in zip(rl, est):
-        le.rl_step(c)
-        le.est_step(e)
-    torch.cuda.synchronize()
-
-    m = ec.Module(x, DEV)
-    static = {k: torch.zeros_like(v) for k, v in {**rl[0], **est[0]}.items()}
-    stream = torch.cuda.Stream()
-    stream.wait_stream(torch.cuda.current_stream())
-    with torch.cuda.stream(stream):                                   # warm-up on the side stream, on a module of its own
-        lw = _Learner(copy.deepcopy(m), cfg)
-        lw.rl_step(rl[0])
-        lw.est_step(est[0])
-    torch.cuda.current_stream().wait_stream(stream)
-    torch.cuda.synchronize()
-    lg = _Learner(m, cfg)
-    graph = torch.cuda.CUDAGraph()
-    with torch.cuda.graph(graph, stream=stream):
-        lg.rl_step(static)
-        lg.est_step(static)
-    torch.cuda.synchronize()
-    assert lg.rl_opt.step_count == 0 and lg.est_opt.step_count == 0   # capturing runs nothing
-    for c, e in zip(rl, est):
-        for k, v in {**c, **e}.items():
-            static[k].copy_(v)
-        graph.replay()
-    torch.cuda.synchronize()
-    assert lg.rl_opt.step_count == 3 and lg.est_opt.step_count == 3 and lg.rl_opt.lr == le.rl_opt.lr
-    for (n, a), b in zip(m.named_parameters(), eager.parameters()):
-        assert np.array_equal(host(a).view(np.uint32), host(b).view(np.uint32)), n
+    both = [{**c, **e} for c, e in zip(tg.fixture_batches(fx, ec.FIXTURE_COLUMNS, 3), tg.fixture_batches(fx, ec.EST_COLUMNS, 3))]
+    tg.replays_like_eager_steps(lambda: ec.Module(x, DEV), lambda m: _Learner(m, fx["cfg"]), both)
 
 
 # ---- determinism, addressing, state -----------------------------------------------------------------------------------------------------------
@@ -410,9 +324,4 @@ def test_a_nan_row_stays_in_its_row_and_reaches_what_torch_reaches():
 def test_zz_print_the_parity_ratios():
     """Not a check of its own: the worst |kernel - f64| / max(|torch-f32 - f64|, ulp) per tensor class over every parity check above, for
     DESIGN.md's table."""
-    worst = {}
-    for _, ratios in RATIOS:
-        for k, v in ratios.items():
-            worst[k] = max(worst.get(k, 0.0), v)
-    for k, v in worst.items():
-        print(f"PARITY {k}: {v:.3f} over {len(RATIOS)} checks")
+    tg.print_parity_ratios(RATIOS)

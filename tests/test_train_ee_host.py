@@ -6,8 +6,6 @@ the case table.  No GPU needed: nothing is launched."""
 import ctypes as C
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -15,8 +13,8 @@ import torch
 import torch.nn as nn
 
 from hcr_genesis_lr_cl_amd import abi, train
-from tests import optim_cases as oc
 from tests import ppo_loss_cases as pc
+from tests import train_abi as ta
 from tests import train_cases as tc
 from tests import train_ee_cases as ec
 
@@ -37,39 +35,16 @@ def test_struct_layout_matches_header():
                ("LgTrainChain", abi.LgTrainChain)]
     consts = dict(LG_TRAIN_EE_CHAINS=abi.TRAIN_EE_CHAINS, LG_TRAIN_EE_ESTIMATOR=abi.TRAIN_EE_ESTIMATOR, LG_TRAIN_EE_ACTOR=abi.TRAIN_EE_ACTOR,
                   LG_TRAIN_EE_CRITIC=abi.TRAIN_EE_CRITIC, LG_TRAIN_EE_THREADS=abi.TRAIN_EE_THREADS, LG_TRAIN_EE_TARGET_JOBS=abi.TRAIN_EE_TARGET_JOBS, LG_POLICY_MAX_LAYERS=abi.POLICY_MAX_LAYERS)
-    lines = ["#include <stdio.h>", "#include <stddef.h>", f'#include "{HEADER}"', "int main(void){"]
-    for cname, cls in structs:
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        for fname, _ in cls._fields_:
-            lines.append(f'printf("{cname}.{fname} %zu\\n", offsetof({cname}, {fname}));')
-    lines += [f'printf("{k} %ld\\n", (long)({k}));' for k in consts] + ["return 0;}"]
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "p.c"), os.path.join(d, "p")
-        with open(src, "w") as f:
-            f.write("\n".join(lines))
-        subprocess.run(["gcc", "-o", exe, src], check=True)
-        got = dict(l.split() for l in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.strip().splitlines())
-    for cname, cls in structs:
-        assert int(got[cname]) == C.sizeof(cls), cname
-        for fname, _ in cls._fields_:
-            assert int(got[f"{cname}.{fname}"]) == getattr(cls, fname).offset, f"{cname}.{fname}"
-    for k, v in consts.items():
-        assert int(got[k]) == v, k
+    ta.check_layout(HEADER, structs, consts)
     assert ec.RED_BYTES == abi.TRAIN_EE_THREADS * 8 and ec.TARGET_JOBS == abi.TRAIN_EE_TARGET_JOBS
 
 
 def test_library_exports_the_entry_points():
-    declared = set(re.findall(r"\b(lg_\w+)\s*\(", re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)))
-    assert declared == set(abi.TRAIN_EE_EXPORTS) == {"lg_train_ee_plan", "lg_train_ee_forward", "lg_train_ee_backward", "lg_train_est_plan",
-                                                     "lg_train_est_forward", "lg_train_est_backward"}
-    lib = C.CDLL(abi.lib_path())
-    for sym in declared:
-        assert hasattr(lib, sym), sym
+    declared = ta.check_exports(HEADER, abi.TRAIN_EE_EXPORTS, "lg_train_ee", ["lg_train_tiles.h", "lg_train_pass.h"])
+    assert declared == {"lg_train_ee_plan", "lg_train_ee_forward", "lg_train_ee_backward", "lg_train_est_plan", "lg_train_est_forward",
+                        "lg_train_est_backward"}
     from hcr_genesis_lr_cl_amd import build
-    assert any(u[0] == "lg_train_ee" and u[1] == "lg_train_ee.hip" and any(d.endswith("lgtrainee.h") for d in u[3])
-               and "lg_train_tiles.h" in u[3] and "lg_train_pass.h" in u[3] for u in build.units())
     assert any(u[0] == "lg_train" and "lg_train_tiles.h" in u[3] and "lg_train_pass.h" in u[3] for u in build.units())
-    assert "lg_train_ee.hip" in build.__doc__
     assert "TRAIN_EE_EXPORTS" in open(os.path.join(ROOT, "__graft_entry__.py")).read()          # the build's export check covers the list
     # one copy of the layer routines and of the pass routines: every unit reaches both headers, none defines any of them
     units = {u: open(os.path.join(CSRC, u)).read() for u in ("lg_train.hip", "lg_train_ee.hip", "lg_train_ts.hip")}
@@ -109,15 +84,6 @@ def test_fixture_is_the_tiny_actor_critic_ee(fx):
         assert 0 < t.sum() < t.size and set(np.unique(t)) <= {0.0, 1.0}
 
 
-def _adam(params, grads, state, lr, cfg, kl=None):
-    """One restated optimizer step (tests/optim_cases.restate) on a list of arrays; `state` carries the moments and the step count."""
-    r = oc.restate(params, [grads], lr0=lr, kls=None if kl is None else [kl], betas=(cfg["beta1"], cfg["beta2"]), eps=cfg["eps"],
-                   max_grad_norm=cfg["max_grad_norm"], desired_kl=cfg["desired_kl"], exp_avg=state.get("m"), exp_avg_sq=state.get("v"),
-                   step0=state.get("step", 0))[0]
-    state.update(m=r["exp_avg"], v=r["exp_avg_sq"], step=r["step"])
-    return r
-
-
 def test_restatement_matches_the_reference_update(fx):
     """Every RL step and every estimator step of the reference's PPO_EE.update(): the restated passes, the loss head's restatement and the
     restated optimizer reproduce outputs, losses, gradients, norms, rates and every parameter to 1e-12.  That the parameters agree while
@@ -137,7 +103,7 @@ def test_restatement_matches_the_reference_update(fx):
         grads = ec.rl_backward(x)
         for name, g, want in zip(fx["rl_names"], grads, fx["grads"][s]):
             assert g.shape == want.shape and tc.max_err(g, want) <= 1e-12, (s, name)
-        step = _adam(x["rl_params"], grads, state, lr, cfg, kl=float(r["kl"][0]))
+        step = ta.adam(x["rl_params"], grads, state, lr, cfg, kl=float(r["kl"][0]))
         lr = step["lr"]
         assert lr == fx["lr"][s] and abs(step["grad_norm"] - fx["grad_norm"][s]) <= 1e-12
         params.update(zip(fx["rl_names"], step["params"]))
@@ -150,7 +116,7 @@ def test_restatement_matches_the_reference_update(fx):
         assert abs(float(e["loss"]) - fx["est_loss"][s]) <= 1e-12
         for name, g, want in zip(fx["est_names"], e["grads"], fx["est_grads"][s]):
             assert g.shape == want.shape and tc.max_err(g, want) <= 1e-12, (s, name)
-        step = _adam(x["est_params"], e["grads"], state, cfg["estimator_lr"], cfg)
+        step = ta.adam(x["est_params"], e["grads"], state, cfg["estimator_lr"], cfg)
         assert abs(step["grad_norm"] - fx["est_grad_norm"][s]) <= 1e-12
         params.update(zip(fx["est_names"], step["params"]))
         for n in fx["names"]:
@@ -264,93 +230,66 @@ def _good_est(backward=True):
     return a
 
 
-def _set(path, value):
-    def f(a):
-        obj = a
-        *head, last = path
-        for p in head:
-            obj = obj[p] if isinstance(p, int) else getattr(obj, p)
-        setattr(obj, last, value)
-    return f
-
-
 # (mutation, message, which entry points refuse it: p plan, f forward, b backward)
 EE_REFUSALS = [
-    (_set(("n_rows",), 0), b"n_rows = 0 < 1", "pfb"),
-    (_set(("chain", 0, "n_layers"), 0), b"chain[0] (estimator).n_layers = 0 is outside [1, 4]", "pfb"),
-    (_set(("chain", 1, "n_layers"), 5), b"chain[1] (actor).n_layers = 5 is outside [1, 4]", "pfb"),
-    (_set(("chain", 2, "layer", 1, "n_in"), 15), b"chain[2] (critic).layer[1].n_in = 15, but its input has 16 columns", "pfb"),
-    (_set(("chain", 0, "layer", 2, "n_out"), 0), b"chain[0] (estimator).layer[2].n_out = 0 is outside [1, 2048]", "pfb"),
-    (_set(("chain", 2, "layer", 0, "n_in"), 2049), b"chain[2] (critic).layer[0].n_in = 2049 is outside [1, 2048]", "pfb"),
-    (_set(("chain", 1, "layer", 0, "n_in"), 11), b"chain[1] (actor).layer[0].n_in = 11, but [features | estimator output] has 7 + 3 columns", "pfb"),
-    (_set(("chain", 0, "input"), None), b"chain[0] (estimator).input is null", "fb"),
-    (_set(("chain", 2, "input"), None), b"chain[2] (critic).input is null", "fb"),
-    (_set(("chain", 0, "in_stride"), 6), b"chain[0] (estimator).in_stride = 6 is below its width 7", "fb"),
-    (_set(("chain", 2, "in_stride"), 8), b"chain[2] (critic).in_stride = 8 is below its width 9", "fb"),
-    (_set(("chain", 0, "layer", 1, "weight"), None), b"chain[0] (estimator).layer[1].weight is null", "fb"),
-    (_set(("chain", 1, "layer", 0, "bias"), None), b"chain[1] (actor).layer[0].bias is null", "fb"),
-    (_set(("chain", 1, "layer", 2, "grad_weight"), None), b"chain[1] (actor).layer[2].grad_weight is null", "b"),
-    (_set(("chain", 2, "layer", 1, "grad_bias"), None), b"chain[2] (critic).layer[1].grad_bias is null", "b"),
-    (_set(("clip_actions",), -1.0), b"clip_actions must be >= 0 under clip_on", "fb"),
-    (_set(("clip_actions",), float("nan")), b"clip_actions must be >= 0 under clip_on", "fb"),
-    (_set(("std",), None), b"std is null", "fb"), (_set(("mu",), None), b"mu is null", "fb"), (_set(("sigma",), None), b"sigma is null", "fb"),
-    (_set(("values",), None), b"values is null", "fb"),
-    (_set(("mu_stride",), 2), b"mu_stride = 2 is below its width 3", "fb"), (_set(("sigma_stride",), 0), b"sigma_stride = 0 is below its width 3", "fb"),
-    (_set(("values_stride",), 0), b"values_stride = 0 is below its width 1", "fb"),
-    (_set(("grad_std",), None), b"grad_std is null", "b"), (_set(("grad_mu",), None), b"grad_mu is null", "b"),
-    (_set(("grad_sigma",), None), b"grad_sigma is null", "b"), (_set(("grad_values",), None), b"grad_values is null", "b"),
-    (_set(("grad_mu_stride",), 2), b"grad_mu_stride = 2 is below its width 3", "b"),
-    (_set(("grad_sigma_stride",), 1), b"grad_sigma_stride = 1 is below its width 3", "b"),
-    (_set(("grad_values_stride",), 0), b"grad_values_stride = 0 is below its width 1", "b"),
-    (_set(("workspace",), None), b"workspace is null", "fb"),
-    (_set(("workspace_capacity",), 10), b"workspace_capacity = 10 floats is below the plan's", "fb"),
+    (ta.set_path(("n_rows",), 0), b"n_rows = 0 < 1", "pfb"),
+    (ta.set_path(("chain", 0, "n_layers"), 0), b"chain[0] (estimator).n_layers = 0 is outside [1, 4]", "pfb"),
+    (ta.set_path(("chain", 1, "n_layers"), 5), b"chain[1] (actor).n_layers = 5 is outside [1, 4]", "pfb"),
+    (ta.set_path(("chain", 2, "layer", 1, "n_in"), 15), b"chain[2] (critic).layer[1].n_in = 15, but its input has 16 columns", "pfb"),
+    (ta.set_path(("chain", 0, "layer", 2, "n_out"), 0), b"chain[0] (estimator).layer[2].n_out = 0 is outside [1, 2048]", "pfb"),
+    (ta.set_path(("chain", 2, "layer", 0, "n_in"), 2049), b"chain[2] (critic).layer[0].n_in = 2049 is outside [1, 2048]", "pfb"),
+    (ta.set_path(("chain", 1, "layer", 0, "n_in"), 11), b"chain[1] (actor).layer[0].n_in = 11, but [features | estimator output] has 7 + 3 columns", "pfb"),
+    (ta.set_path(("chain", 0, "input"), None), b"chain[0] (estimator).input is null", "fb"),
+    (ta.set_path(("chain", 2, "input"), None), b"chain[2] (critic).input is null", "fb"),
+    (ta.set_path(("chain", 0, "in_stride"), 6), b"chain[0] (estimator).in_stride = 6 is below its width 7", "fb"),
+    (ta.set_path(("chain", 2, "in_stride"), 8), b"chain[2] (critic).in_stride = 8 is below its width 9", "fb"),
+    (ta.set_path(("chain", 0, "layer", 1, "weight"), None), b"chain[0] (estimator).layer[1].weight is null", "fb"),
+    (ta.set_path(("chain", 1, "layer", 0, "bias"), None), b"chain[1] (actor).layer[0].bias is null", "fb"),
+    (ta.set_path(("chain", 1, "layer", 2, "grad_weight"), None), b"chain[1] (actor).layer[2].grad_weight is null", "b"),
+    (ta.set_path(("chain", 2, "layer", 1, "grad_bias"), None), b"chain[2] (critic).layer[1].grad_bias is null", "b"),
+    (ta.set_path(("clip_actions",), -1.0), b"clip_actions must be >= 0 under clip_on", "fb"),
+    (ta.set_path(("clip_actions",), float("nan")), b"clip_actions must be >= 0 under clip_on", "fb"),
+    (ta.set_path(("std",), None), b"std is null", "fb"), (ta.set_path(("mu",), None), b"mu is null", "fb"), (ta.set_path(("sigma",), None), b"sigma is null", "fb"),
+    (ta.set_path(("values",), None), b"values is null", "fb"),
+    (ta.set_path(("mu_stride",), 2), b"mu_stride = 2 is below its width 3", "fb"), (ta.set_path(("sigma_stride",), 0), b"sigma_stride = 0 is below its width 3", "fb"),
+    (ta.set_path(("values_stride",), 0), b"values_stride = 0 is below its width 1", "fb"),
+    (ta.set_path(("grad_std",), None), b"grad_std is null", "b"), (ta.set_path(("grad_mu",), None), b"grad_mu is null", "b"),
+    (ta.set_path(("grad_sigma",), None), b"grad_sigma is null", "b"), (ta.set_path(("grad_values",), None), b"grad_values is null", "b"),
+    (ta.set_path(("grad_mu_stride",), 2), b"grad_mu_stride = 2 is below its width 3", "b"),
+    (ta.set_path(("grad_sigma_stride",), 1), b"grad_sigma_stride = 1 is below its width 3", "b"),
+    (ta.set_path(("grad_values_stride",), 0), b"grad_values_stride = 0 is below its width 1", "b"),
+    (ta.set_path(("workspace",), None), b"workspace is null", "fb"),
+    (ta.set_path(("workspace_capacity",), 10), b"workspace_capacity = 10 floats is below the plan's", "fb"),
 ]
 EST_REFUSALS = [
-    (_set(("n_rows",), -2), b"n_rows = -2 < 1", "pfb"),
-    (_set(("chain", "n_layers"), 5), b"chain (estimator).n_layers = 5 is outside [1, 4]", "pfb"),
-    (_set(("chain", "layer", 1, "n_in"), 9), b"chain (estimator).layer[1].n_in = 9, but its input has 8 columns", "pfb"),
-    (_set(("chain", "layer", 0, "n_out"), 4000), b"chain (estimator).layer[0].n_out = 4000 is outside [1, 2048]", "pfb"),
-    (_set(("chain", "input"), None), b"chain (estimator).input is null", "fb"),
-    (_set(("chain", "in_stride"), 3), b"chain (estimator).in_stride = 3 is below its width 7", "fb"),
-    (_set(("chain", "layer", 2, "weight"), None), b"chain (estimator).layer[2].weight is null", "fb"),
-    (_set(("chain", "layer", 0, "bias"), None), b"chain (estimator).layer[0].bias is null", "fb"),
-    (_set(("chain", "layer", 0, "grad_weight"), None), b"chain (estimator).layer[0].grad_weight is null", "b"),
-    (_set(("chain", "layer", 2, "grad_bias"), None), b"chain (estimator).layer[2].grad_bias is null", "b"),
-    (_set(("labels",), None), b"labels is null", "fb"), (_set(("mask",), None), b"mask is null", "fb"),
-    (_set(("labels_stride",), 2), b"labels_stride = 2 is below its width 3", "fb"),
-    (_set(("mask_stride",), 0), b"mask_stride = 0 is below its width 1", "fb"),
-    (_set(("loss",), None), b"loss is null", "f"), (_set(("upstream",), None), b"upstream is null", "b"),
-    (_set(("workspace",), None), b"workspace is null", "fb"),
+    (ta.set_path(("n_rows",), -2), b"n_rows = -2 < 1", "pfb"),
+    (ta.set_path(("chain", "n_layers"), 5), b"chain (estimator).n_layers = 5 is outside [1, 4]", "pfb"),
+    (ta.set_path(("chain", "layer", 1, "n_in"), 9), b"chain (estimator).layer[1].n_in = 9, but its input has 8 columns", "pfb"),
+    (ta.set_path(("chain", "layer", 0, "n_out"), 4000), b"chain (estimator).layer[0].n_out = 4000 is outside [1, 2048]", "pfb"),
+    (ta.set_path(("chain", "input"), None), b"chain (estimator).input is null", "fb"),
+    (ta.set_path(("chain", "in_stride"), 3), b"chain (estimator).in_stride = 3 is below its width 7", "fb"),
+    (ta.set_path(("chain", "layer", 2, "weight"), None), b"chain (estimator).layer[2].weight is null", "fb"),
+    (ta.set_path(("chain", "layer", 0, "bias"), None), b"chain (estimator).layer[0].bias is null", "fb"),
+    (ta.set_path(("chain", "layer", 0, "grad_weight"), None), b"chain (estimator).layer[0].grad_weight is null", "b"),
+    (ta.set_path(("chain", "layer", 2, "grad_bias"), None), b"chain (estimator).layer[2].grad_bias is null", "b"),
+    (ta.set_path(("labels",), None), b"labels is null", "fb"), (ta.set_path(("mask",), None), b"mask is null", "fb"),
+    (ta.set_path(("labels_stride",), 2), b"labels_stride = 2 is below its width 3", "fb"),
+    (ta.set_path(("mask_stride",), 0), b"mask_stride = 0 is below its width 1", "fb"),
+    (ta.set_path(("loss",), None), b"loss is null", "f"), (ta.set_path(("upstream",), None), b"upstream is null", "b"),
+    (ta.set_path(("workspace",), None), b"workspace is null", "fb"),
     (lambda a: setattr(a, "workspace", a.workspace + 4), b"workspace is not 8-byte aligned", "fb"),
-    (_set(("workspace_capacity",), 10), b"workspace_capacity = 10 floats is below the plan's", "fb"),
+    (ta.set_path(("workspace_capacity",), 10), b"workspace_capacity = 10 floats is below the plan's", "fb"),
 ]
-
-
-def _refuse(table, i, good, prefix, args_cls):
-    mutate, msg, who = table[i]
-    lib = abi.load_lib()
-    a = good()
-    mutate(a)
-    plan = lambda: getattr(lib, prefix + "_plan")(C.byref(a), C.byref(abi.LgTrainEEPlan()))
-    calls = dict(p=(prefix + "_plan", plan), f=(prefix + "_forward", lambda: getattr(lib, prefix + "_forward")(C.byref(a), None)),
-                 b=(prefix + "_backward", lambda: getattr(lib, prefix + "_backward")(C.byref(a), None)))
-    for key in who:
-        name, call = calls[key]
-        assert call() != 0, name
-        err = lib.lg_last_error()
-        assert err.startswith(name.encode() + b": ") and msg in err, (name, err)
-    if "p" not in who:                                                        # the plan reads the shapes alone
-        assert plan() == 0
 
 
 @pytest.mark.parametrize("i", range(len(EE_REFUSALS)))
 def test_rl_entry_points_refuse(i):
-    _refuse(EE_REFUSALS, i, _good_ee, "lg_train_ee", abi.LgTrainEEArgs)
+    ta.refuse(EE_REFUSALS, i, _good_ee, "lg_train_ee", abi.LgTrainEEPlan)
 
 
 @pytest.mark.parametrize("i", range(len(EST_REFUSALS)))
 def test_estimator_entry_points_refuse(i):
-    _refuse(EST_REFUSALS, i, _good_est, "lg_train_est", abi.LgTrainEstArgs)
+    ta.refuse(EST_REFUSALS, i, _good_est, "lg_train_est", abi.LgTrainEEPlan)
 
 
 def test_entry_points_refuse_null_descriptors_and_the_lds():

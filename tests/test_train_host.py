@@ -5,9 +5,6 @@ surface, the plan of lg_train_plan against the restated rule, the coverage of th
 tests/test_gpu_train.py holds the kernels to.  No GPU needed: nothing is launched."""
 import ctypes as C
 import os
-import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
@@ -16,6 +13,7 @@ import torch.nn as nn
 
 from hcr_genesis_lr_cl_amd import abi, train
 from tests import ppo_loss_cases as pc
+from tests import train_abi as ta
 from tests import train_cases as tc
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -31,39 +29,17 @@ def test_struct_layout_matches_header():
                   LG_TRAIN_WG_TILE=abi.TRAIN_WG_TILE, LG_TRAIN_MIN_SLICE_ROWS=abi.TRAIN_MIN_SLICE_ROWS,
                   LG_TRAIN_TARGET_JOBS=abi.TRAIN_TARGET_JOBS, LG_TRAIN_MAX_SLICES=abi.TRAIN_MAX_SLICES,
                   LG_POLICY_MAX_LAYERS=abi.POLICY_MAX_LAYERS, LG_POLICY_MAX_WIDTH=abi.POLICY_MAX_WIDTH)
-    lines = ["#include <stdio.h>", "#include <stddef.h>", f'#include "{HEADER}"', "int main(void){"]
-    for cname, cls in structs:
-        lines.append(f'printf("{cname} %zu\\n", sizeof({cname}));')
-        for fname, _ in cls._fields_:
-            lines.append(f'printf("{cname}.{fname} %zu\\n", offsetof({cname}, {fname}));')
-    lines += [f'printf("{k} %ld\\n", (long)({k}));' for k in consts] + ["return 0;}"]
-    with tempfile.TemporaryDirectory() as d:
-        src, exe = os.path.join(d, "p.c"), os.path.join(d, "p")
-        with open(src, "w") as f:
-            f.write("\n".join(lines))
-        subprocess.run(["gcc", "-o", exe, src], check=True)
-        got = dict(l.split() for l in subprocess.run([exe], check=True, capture_output=True, text=True).stdout.strip().splitlines())
-    for cname, cls in structs:
-        assert int(got[cname]) == C.sizeof(cls), cname
-        for fname, _ in cls._fields_:
-            assert int(got[f"{cname}.{fname}"]) == getattr(cls, fname).offset, f"{cname}.{fname}"
-    for k, v in consts.items():
-        assert int(got[k]) == v, k
+    ta.check_layout(HEADER, structs, consts)
     assert (tc.WG_TILE, tc.MIN_SLICE_ROWS, tc.TARGET_JOBS, tc.MAX_SLICES) == (abi.TRAIN_WG_TILE, abi.TRAIN_MIN_SLICE_ROWS, abi.TRAIN_TARGET_JOBS,
                                                                              abi.TRAIN_MAX_SLICES)
     assert abi.TRAIN_WG_TILE % 16 == 0 and abi.TRAIN_MIN_SLICE_ROWS % 4 == 0
 
 
 def test_library_exports_the_train_entry_points():
-    declared = set(re.findall(r"\b(lg_\w+)\s*\(", re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)))
-    assert declared == set(abi.TRAIN_EXPORTS) == {"lg_train_plan", "lg_train_forward", "lg_train_backward"}
-    lib = C.CDLL(abi.lib_path())
-    for sym in declared:
-        assert hasattr(lib, sym), sym
+    declared = ta.check_exports(HEADER, abi.TRAIN_EXPORTS, "lg_train", ["lg_train_pass.h"])
+    assert declared == {"lg_train_plan", "lg_train_forward", "lg_train_backward"}
     from hcr_genesis_lr_cl_amd import build
-    assert any(u[0] == "lg_train" and u[1] == "lg_train.hip" and any(d.endswith("lgtrain.h") for d in u[3]) and "lg_train_pass.h" in u[3]
-               for u in build.units())
-    assert f"{len(build.units())} translation units" in build.__doc__ and "lg_train.hip" in build.__doc__
+    assert f"{len(build.units())} translation units" in build.__doc__
     for unit in ("lg_train.hip", "lg_train_pass.h"):                           # the pass routines live in the shared header
         source = open(os.path.join(ROOT, "hcr_genesis_lr_cl_amd", "csrc", unit)).read()
         assert "atomic" not in source.lower().replace("no atomics", "")        # determinism is the house rule
@@ -176,63 +152,40 @@ def _good_args(backward=True):
     return a
 
 
-def _set(path, value):
-    def f(a):
-        obj = a
-        *head, last = path
-        for p in head:
-            obj = obj[p] if isinstance(p, int) else getattr(obj, p)
-        setattr(obj, last, value)
-    return f
-
-
 # (mutation, message, which entry points refuse it: p plan, f forward, b backward)
 ENTRY_REFUSALS = [
-    (_set(("n_rows",), 0), b"n_rows = 0 < 1", "pfb"), (_set(("n_rows",), -3), b"n_rows = -3 < 1", "pfb"),
-    (_set(("chain", 0, "n_layers"), 0), b"chain[0] (actor).n_layers = 0 is outside [1, 4]", "pfb"),
-    (_set(("chain", 1, "n_layers"), 5), b"chain[1] (critic).n_layers = 5 is outside [1, 4]", "pfb"),
-    (_set(("chain", 0, "layer", 1, "n_in"), 32), b"chain[0] (actor).layer[1].n_in = 32, but its input has 33 columns", "pfb"),
-    (_set(("chain", 1, "layer", 0, "n_out"), 16), b"chain[1] (critic).layer[1].n_in = 17, but its input has 16 columns", "pfb"),
-    (_set(("chain", 0, "layer", 2, "n_out"), 0), b"chain[0] (actor).layer[2].n_out = 0 is outside [1, 2048]", "pfb"),
-    (_set(("chain", 0, "layer", 0, "n_in"), 2049), b"chain[0] (actor).layer[0].n_in = 2049 is outside [1, 2048]", "pfb"),
-    (_set(("chain", 0, "input"), None), b"chain[0] (actor).input is null", "fb"),
-    (_set(("chain", 1, "in_stride"), 5), b"chain[1] (critic).in_stride = 5 is below its width 6", "fb"),
-    (_set(("chain", 0, "layer", 1, "weight"), None), b"chain[0] (actor).layer[1].weight is null", "fb"),
-    (_set(("chain", 1, "layer", 0, "bias"), None), b"chain[1] (critic).layer[0].bias is null", "fb"),
-    (_set(("chain", 0, "layer", 2, "grad_weight"), None), b"chain[0] (actor).layer[2].grad_weight is null", "b"),
-    (_set(("chain", 1, "layer", 1, "grad_bias"), None), b"chain[1] (critic).layer[1].grad_bias is null", "b"),
-    (_set(("clip_actions",), -1.0), b"clip_actions must be >= 0 under clip_on", "fb"),
-    (_set(("clip_actions",), float("nan")), b"clip_actions must be >= 0 under clip_on", "fb"),
-    (_set(("std",), None), b"std is null", "fb"), (_set(("mu",), None), b"mu is null", "fb"), (_set(("sigma",), None), b"sigma is null", "fb"),
-    (_set(("values",), None), b"values is null", "fb"),
-    (_set(("mu_stride",), 2), b"mu_stride = 2 is below its width 3", "fb"), (_set(("sigma_stride",), 0), b"sigma_stride = 0 is below its width 3", "fb"),
-    (_set(("values_stride",), 0), b"values_stride = 0 is below its width 1", "fb"),
-    (_set(("grad_std",), None), b"grad_std is null", "b"), (_set(("grad_mu",), None), b"grad_mu is null", "b"),
-    (_set(("grad_sigma",), None), b"grad_sigma is null", "b"), (_set(("grad_values",), None), b"grad_values is null", "b"),
-    (_set(("grad_mu_stride",), 2), b"grad_mu_stride = 2 is below its width 3", "b"),
-    (_set(("grad_sigma_stride",), 1), b"grad_sigma_stride = 1 is below its width 3", "b"),
-    (_set(("grad_values_stride",), 0), b"grad_values_stride = 0 is below its width 1", "b"),
-    (_set(("workspace",), None), b"workspace is null", "fb"),
-    (_set(("workspace_capacity",), 10), b"workspace_capacity = 10 floats is below the plan's", "fb"),
+    (ta.set_path(("n_rows",), 0), b"n_rows = 0 < 1", "pfb"), (ta.set_path(("n_rows",), -3), b"n_rows = -3 < 1", "pfb"),
+    (ta.set_path(("chain", 0, "n_layers"), 0), b"chain[0] (actor).n_layers = 0 is outside [1, 4]", "pfb"),
+    (ta.set_path(("chain", 1, "n_layers"), 5), b"chain[1] (critic).n_layers = 5 is outside [1, 4]", "pfb"),
+    (ta.set_path(("chain", 0, "layer", 1, "n_in"), 32), b"chain[0] (actor).layer[1].n_in = 32, but its input has 33 columns", "pfb"),
+    (ta.set_path(("chain", 1, "layer", 0, "n_out"), 16), b"chain[1] (critic).layer[1].n_in = 17, but its input has 16 columns", "pfb"),
+    (ta.set_path(("chain", 0, "layer", 2, "n_out"), 0), b"chain[0] (actor).layer[2].n_out = 0 is outside [1, 2048]", "pfb"),
+    (ta.set_path(("chain", 0, "layer", 0, "n_in"), 2049), b"chain[0] (actor).layer[0].n_in = 2049 is outside [1, 2048]", "pfb"),
+    (ta.set_path(("chain", 0, "input"), None), b"chain[0] (actor).input is null", "fb"),
+    (ta.set_path(("chain", 1, "in_stride"), 5), b"chain[1] (critic).in_stride = 5 is below its width 6", "fb"),
+    (ta.set_path(("chain", 0, "layer", 1, "weight"), None), b"chain[0] (actor).layer[1].weight is null", "fb"),
+    (ta.set_path(("chain", 1, "layer", 0, "bias"), None), b"chain[1] (critic).layer[0].bias is null", "fb"),
+    (ta.set_path(("chain", 0, "layer", 2, "grad_weight"), None), b"chain[0] (actor).layer[2].grad_weight is null", "b"),
+    (ta.set_path(("chain", 1, "layer", 1, "grad_bias"), None), b"chain[1] (critic).layer[1].grad_bias is null", "b"),
+    (ta.set_path(("clip_actions",), -1.0), b"clip_actions must be >= 0 under clip_on", "fb"),
+    (ta.set_path(("clip_actions",), float("nan")), b"clip_actions must be >= 0 under clip_on", "fb"),
+    (ta.set_path(("std",), None), b"std is null", "fb"), (ta.set_path(("mu",), None), b"mu is null", "fb"), (ta.set_path(("sigma",), None), b"sigma is null", "fb"),
+    (ta.set_path(("values",), None), b"values is null", "fb"),
+    (ta.set_path(("mu_stride",), 2), b"mu_stride = 2 is below its width 3", "fb"), (ta.set_path(("sigma_stride",), 0), b"sigma_stride = 0 is below its width 3", "fb"),
+    (ta.set_path(("values_stride",), 0), b"values_stride = 0 is below its width 1", "fb"),
+    (ta.set_path(("grad_std",), None), b"grad_std is null", "b"), (ta.set_path(("grad_mu",), None), b"grad_mu is null", "b"),
+    (ta.set_path(("grad_sigma",), None), b"grad_sigma is null", "b"), (ta.set_path(("grad_values",), None), b"grad_values is null", "b"),
+    (ta.set_path(("grad_mu_stride",), 2), b"grad_mu_stride = 2 is below its width 3", "b"),
+    (ta.set_path(("grad_sigma_stride",), 1), b"grad_sigma_stride = 1 is below its width 3", "b"),
+    (ta.set_path(("grad_values_stride",), 0), b"grad_values_stride = 0 is below its width 1", "b"),
+    (ta.set_path(("workspace",), None), b"workspace is null", "fb"),
+    (ta.set_path(("workspace_capacity",), 10), b"workspace_capacity = 10 floats is below the plan's", "fb"),
 ]
 
 
 @pytest.mark.parametrize("i", range(len(ENTRY_REFUSALS)))
 def test_entry_points_refuse(i):
-    mutate, msg, who = ENTRY_REFUSALS[i]
-    lib = abi.load_lib()
-    a = _good_args()
-    mutate(a)
-    calls = dict(p=("lg_train_plan", lambda: lib.lg_train_plan(C.byref(a), C.byref(abi.LgTrainPlan()))),
-                 f=("lg_train_forward", lambda: lib.lg_train_forward(C.byref(a), None)),
-                 b=("lg_train_backward", lambda: lib.lg_train_backward(C.byref(a), None)))
-    for key in who:
-        name, call = calls[key]
-        assert call() != 0, name
-        err = lib.lg_last_error()
-        assert err.startswith(name.encode() + b": ") and msg in err, (name, err)
-    if "p" not in who:                                                        # the plan reads the shapes alone
-        assert lib.lg_train_plan(C.byref(a), C.byref(abi.LgTrainPlan())) == 0
+    ta.refuse(ENTRY_REFUSALS, i, _good_args, "lg_train", abi.LgTrainPlan)
 
 
 def test_entry_points_refuse_null_descriptors_and_the_lds():

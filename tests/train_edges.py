@@ -5,14 +5,17 @@ helpers the two test files on it share -- tests/test_train_edges_host.py (no GPU
 plan, the float32 restatement inside half the rule, discrimination) and tests/test_gpu_train_edges.py (the kernels against float64).  No
 test functions here, nothing needs a GPU.
 
-Built on what exists: make_inputs, forward, backward, torch_pass, references, check_parity, restated_plan* and Module of the three case
-modules.  Their NETS dicts take a row's widths only while its inputs are drawn; the old tables stay as they are."""
+Built on what exists: make_inputs, forward, backward, references, restated_plan* and Module of the three case modules, each reached
+through the one record of its kind (KINDS), and the parity rule of tests/train_support.py.  A row's widths go to make_inputs as they
+stand; the old tables stay as they are."""
 import functools
+from types import SimpleNamespace
 
 import numpy as np
 
 from tests import train_cases as tc
 from tests import train_ee_cases as ec
+from tests import train_support as sup
 from tests import train_ts_cases as sc
 
 WAVES = 4                      # csrc/lg_train_tiles.h: kWaves
@@ -103,8 +106,45 @@ VEC_B = 33
 PLACEMENTS = {"vector": (4, 24), "misaligned_base": (1, 24), "odd_stride": (4, 25)}
 
 
-MODULES = {"plain": tc, "ee": ec, "ts": sc}
-CHAINS = {"plain": ("actor", "critic"), "ee": ("est", "actor", "critic"), "ts": ("priv", "actor", "critic", "hist")}
+# ---- one record per kind --------------------------------------------------------------------------------------------------------------------
+def _plain_in_kernel_order(x, ps):
+    f, (p,) = np.float32, ps
+    return tc.named(x, tc.forward(x, f), tc.backward(x, f, slices=(p["std"][1], *p["slice_rows"])))
+
+
+def _ee_in_kernel_order(x, ps):
+    f, (rl, est) = np.float32, ps
+    e = ec.est_pass(x, f, slices=est["slice_rows"][0])
+    loss = f(loss_by_tiles(e["d"], est["row_tile"]))
+    return ec.named(x, ec.rl_forward(x, f), ec.rl_backward(x, f, slices=(rl["std"][1], *rl["slice_rows"])), loss, e["grads"])
+
+
+def _ts_in_kernel_order(x, ps):
+    f, (rl, enc) = np.float32, ps
+    rl_s, enc_s, tile = sc.kernel_order_slices(x)
+    assert (rl_s["std"], rl_s["priv"], rl_s["actor"], rl_s["critic"]) == (rl["std"][1], *rl["slice_rows"]) and \
+        (enc_s, tile) == (enc["slice_rows"][0], enc["row_tile"])
+    e = sc.enc_pass(x, f, slices=enc_s, row_tile=tile)
+    return sc.named(x, sc.rl_forward(x, f), sc.rl_backward(x, f, slices=rl_s), e["loss"], e["grads"])
+
+
+# What a kind of row is made of.  mod: its case module (NETS, make_inputs, references, named); chains: the keys of its widths, in the order
+# of a NETS entry; plans(B, widths): its restated plans, (plan,) of the plain pass, (RL plan, estimator plan) of the EE passes, (RL plan,
+# encoder plan) of the teacher-student passes; kernel_order(x, plans): its float32 restatement with every batch sum sliced as planned.
+KINDS = {
+    "plain": SimpleNamespace(mod=tc, chains=("actor", "critic"), plans=lambda B, w: (tc.restated_plan(B, *w),), kernel_order=_plain_in_kernel_order),
+    "ee": SimpleNamespace(mod=ec, chains=("est", "actor", "critic"), kernel_order=_ee_in_kernel_order,
+                          plans=lambda B, w: (ec.restated_plan_ee(B, *w), ec.restated_plan_est(B, w[0]))),
+    "ts": SimpleNamespace(mod=sc, chains=("priv", "actor", "critic", "hist"), kernel_order=_ts_in_kernel_order,
+                          plans=lambda B, w: (sc.restated_plan_ts(B, *w[:3]), sc.restated_plan_enc(B, w[3], w[0]))),
+}
+
+
+ALL_CHAINS = {c for k in KINDS.values() for c in k.chains}
+
+
+def kind_of(row):
+    return KINDS[ROWS[row]["kind"]]
 
 
 def case_id(case):
@@ -113,10 +153,8 @@ def case_id(case):
 
 def widths(row):
     """The chains of a row: (actor, critic), (est, actor, critic) or (priv, actor, critic, hist)."""
-    d = ROWS[row]
-    if "net" in d:
-        return tuple(list(c) for c in MODULES[d["kind"]].NETS[d["net"]])
-    return tuple(d[k] for k in CHAINS[d["kind"]])
+    d, k = ROWS[row], kind_of(row)
+    return tuple(list(c) for c in k.mod.NETS[d["net"]]) if "net" in d else tuple(d[c] for c in k.chains)
 
 
 def seed_of(row, B):
@@ -124,14 +162,8 @@ def seed_of(row, B):
 
 
 def plans(row, B):
-    """The restated plans of a case: (plan,) of the plain pass, (RL plan, estimator plan) of the EE passes, (RL plan, encoder plan) of the
-    teacher-student passes."""
-    w, kind = widths(row), ROWS[row]["kind"]
-    if kind == "plain":
-        return (tc.restated_plan(B, *w),)
-    if kind == "ts":
-        return sc.restated_plan_ts(B, *w[:3]), sc.restated_plan_enc(B, w[3], w[0])
-    return ec.restated_plan_ee(B, *w), ec.restated_plan_est(B, w[0])
+    """The restated plans of a case, one per pass."""
+    return kind_of(row).plans(B, widths(row))
 
 
 # ---- what a case reaches, from the restated plans -------------------------------------------------------------------------------------------
@@ -153,7 +185,7 @@ def reach_tags(row, B):
     ps, w = plans(row, B), widths(row)
     slices = []
     for p in ps:
-        for S, per in [x for c in zip(p["slices"], p["slice_rows"]) for x in zip(*c)] + ([p["std"]] if "std" in p else []):
+        for S, per in sup.plan_slices(p) + ([p["std"]] if "std" in p else []):
             slices.append((S, per, B - (S - 1) * per))
     max_S = max(s[0] for s in slices)
     return dict(row_tile=tuple(p["row_tile"] for p in ps), lds_bytes=tuple(p["lds_bytes"] for p in ps), weight_jobs=tuple(p["weight_jobs"] for p in ps),
@@ -215,13 +247,8 @@ def claimed(row, B):
 
 # ---- inputs and references, drawn once ------------------------------------------------------------------------------------------------------
 def draw(kind, w, B, seed):
-    """make_inputs of the kind's case module for chains that are no row of its NETS: they stand there while the inputs are drawn."""
-    mod = MODULES[kind]
-    mod.NETS["_edge"] = tuple(list(c) for c in w)
-    try:
-        return mod.make_inputs(dict(net="_edge", B=B, seed=seed))
-    finally:
-        del mod.NETS["_edge"]
+    """make_inputs of the kind's case module for chains of these widths, which need be no row of its NETS."""
+    return KINDS[kind].mod.make_inputs(dict(widths=w, B=B, seed=seed))
 
 
 @functools.lru_cache(maxsize=None)
@@ -230,20 +257,14 @@ def inputs(row, B):
     return draw(ROWS[row]["kind"], widths(row), B, seed_of(row, B))
 
 
-def plain_references(x):
-    t32 = tc.torch_pass(x)
-    return tc.named(x, tc.forward(x), tc.backward(x)), tc.named(x, t32, t32["grads"])
-
-
 @functools.lru_cache(maxsize=None)
 def references(row, B):
     """(float64 restatement, torch CPU float32) of a case as `named` dicts, computed once (shared: treat as read-only)."""
-    x = inputs(row, B)
-    return plain_references(x) if ROWS[row]["kind"] == "plain" else MODULES[ROWS[row]["kind"]].references(x)
+    return kind_of(row).mod.references(inputs(row, B))
 
 
 def check(row, got, ref64, ref32, label, report=None):
-    return MODULES[ROWS[row]["kind"]].check_parity(got, ref64, ref32, label, report)
+    return sup.check_parity(got, ref64, ref32, label, report)
 
 
 # ---- the float32 restatement in the kernel's order ------------------------------------------------------------------------------------------
@@ -262,21 +283,8 @@ def f32_in_kernel_order(x, plan):
     """The numpy float32 restatement of a case with every batch sum formed per slice of its own layer's plan and the loss per tile, as a
     `named` dict.  plan: restated_plan's dict for the plain pass, (restated_plan_ee, restated_plan_est) for the EE passes,
     (restated_plan_ts, restated_plan_enc) for the teacher-student passes."""
-    f = np.float32
-    if "priv" in x:
-        rl_s, enc_s, tile = sc.kernel_order_slices(x)
-        rl, enc = plan
-        assert (rl_s["std"], rl_s["priv"], rl_s["actor"], rl_s["critic"]) == (rl["std"][1], *rl["slice_rows"]) and \
-            (enc_s, tile) == (enc["slice_rows"][0], enc["row_tile"])
-        e = sc.enc_pass(x, f, slices=enc_s, row_tile=tile)
-        return sc.named(x, sc.rl_forward(x, f), sc.rl_backward(x, f, slices=rl_s), e["loss"], e["grads"])
-    if "est" not in x:
-        per = (plan["std"][1], *plan["slice_rows"])
-        return tc.named(x, tc.forward(x, f), tc.backward(x, f, slices=per))
-    rl, est = plan
-    e = ec.est_pass(x, f, slices=est["slice_rows"][0])
-    loss = f(loss_by_tiles(e["d"], est["row_tile"]))
-    return ec.named(x, ec.rl_forward(x, f), ec.rl_backward(x, f, slices=(rl["std"][1], *rl["slice_rows"])), loss, e["grads"])
+    kind = next(k for k in KINDS.values() if set(k.chains) == ALL_CHAINS & set(x))          # the kind whose chains the inputs carry
+    return kind.kernel_order(x, plan if isinstance(plan, tuple) else (plan,))
 
 
 def worst_ratio(got, ref64, ref32):

@@ -1,12 +1,14 @@
 """The cases of the explicit-estimator learner passes (include/lgtrainee.h), shared by tests/test_train_ee_host.py (CPU) and
 tests/test_gpu_train_ee.py (GPU): one net table, one case table, the input generator, a numpy float64 restatement of both passes built on
-tests/train_cases.py's forward / backward, the same passes as torch autograd on the CPU, the plans restated, the parity rule and the
-loader of the golden fixture (tests/golden/gen_ppo_ee_train_fixtures.py).  Nothing here loads the HIP library."""
+tests/train_cases.py's forward / backward, the same passes as torch autograd on the CPU, the plans restated and the loader of the golden
+fixture (tests/golden/gen_ppo_ee_train_fixtures.py); the chain arithmetic, the plan's rules, the parity rule and the fixture readers are
+tests/train_support.py's.  Nothing here loads the HIP library."""
 import numpy as np
 import torch
 
 from tests import train_cases as tc
-from tests.optim_cases import PARITY_FACTOR
+from tests import train_support as sup
+from tests.train_support import CLASSES, check_parity, fixture_loss_inputs, tensor_class          # noqa: F401
 
 # name -> (estimator widths, actor widths, critic widths); actor[0] = F + NL.  Hidden layers carry an ELU, the actor ends in a Hardtanh.
 NETS = {
@@ -36,88 +38,34 @@ RED_BYTES = 256 * 8            # the estimator forward's float64 tree (LG_TRAIN_
 TARGET_JOBS = 2048             # LG_TRAIN_EE_TARGET_JOBS
 
 
-def slice_rule(n_rows, tiles):
-    """tests/train_cases.slice_rule with include/lgtrainee.h's job target."""
-    want = min(max(1, n_rows // tc.MIN_SLICE_ROWS), max(1, TARGET_JOBS // tiles), tc.MAX_SLICES)
-    per = (-(-n_rows // want) + 3) & ~3
-    return -(-n_rows // per), per
-
-
 # ---- the plans ------------------------------------------------------------------------------------------------------------------------------
-def _lds(chains_first):
-    w = [0, 0]
-    for c, first in chains_first:
-        for i, width in enumerate(c):
-            w[(i + first) & 1] = max(w[(i + first) & 1], tc.lds_stride(width))
-    return w
-
-
-def _offsets(n_rows, chains, off):
-    """h_off, g_off, then p_off / slices of the chains, as include/lgtrain.h lays them out; returns (dict, off, jobs)."""
-    h_off, g_off, p_off, slices, rows, jobs = [], [], [], [], [], 0
-    for c in chains:
-        h, g = [], []
-        for li in range(len(c) - 1):
-            if li < len(c) - 2:
-                h.append(off)
-                off += n_rows * c[li + 1]
-            else:
-                h.append(-1)
-            g.append(off)
-            off += n_rows * c[li + 1]
-        h_off.append(h)
-        g_off.append(g)
-    for c in chains:
-        p, s, r = [], [], []
-        for li in range(len(c) - 1):
-            K, M = c[li], c[li + 1]
-            tiles = -(-M // tc.WG_TILE) * -(-K // tc.WG_TILE)
-            S, per = slice_rule(n_rows, tiles)
-            p.append(off)
-            off += S * (M * K + M)
-            jobs += S * tiles
-            s.append(S)
-            r.append(per)
-        p_off.append(p)
-        slices.append(s)
-        rows.append(r)
-    return dict(h_off=h_off, g_off=g_off, p_off=p_off, slices=slices, slice_rows=rows), off, jobs
-
-
 def restated_plan_ee(n_rows, est, actor, critic):
     """include/lgtrainee.h's plan of the RL pass; the per-chain lists hold the actor and the critic (chains 1 and 2)."""
     first = 0 if (len(est) - 1) & 1 else 1
-    w = _lds(((est, first), (actor, 0), (critic, 0)))
-    row_tile = next((r for r in (32, 16, 8) if r * (w[0] + w[1]) * 4 <= tc.LDS_BYTES), 0)
-    d, off, jobs = _offsets(n_rows, (actor, critic), n_rows * actor[0])
-    std = slice_rule(n_rows, 1)
-    d.update(row_tile=row_tile, lds_bytes=row_tile * (w[0] + w[1]) * 4, est_first_buffer=first, cat_off=0, std=std, std_p_off=off,
+    row_tile, lds_bytes = sup.row_tile(sup.lds_widths(((est, first), (actor, 0), (critic, 0))))
+    d, off, jobs = sup.offsets(n_rows, (actor, critic), n_rows * actor[0], TARGET_JOBS)
+    std = sup.slice_rule(n_rows, 1, TARGET_JOBS)
+    d.update(row_tile=row_tile, lds_bytes=lds_bytes, est_first_buffer=first, cat_off=0, std=std, std_p_off=off,
              workspace_floats=off + std[0] * actor[-1], weight_jobs=jobs + std[0])
     return d
 
 
 def restated_plan_est(n_rows, est):
-    w = _lds(((est, 0),))
-    row_tile = next((r for r in (32, 16, 8) if r * (w[0] + w[1]) * 4 + RED_BYTES <= tc.LDS_BYTES), 0)
-    d, off, jobs = _offsets(n_rows, (est,), 0)
+    row_tile, lds_bytes = sup.row_tile(sup.lds_widths(((est, 0),)), RED_BYTES)
+    d, off, jobs = sup.offsets(n_rows, (est,), 0, TARGET_JOBS)
     gl_off = off
     off += n_rows * est[-1]
     off += off & 1
     tiles = -(-n_rows // row_tile)
-    d.update(row_tile=row_tile, lds_bytes=row_tile * (w[0] + w[1]) * 4 + RED_BYTES, gl_off=gl_off, partial_off=off, loss_tiles=tiles,
-             workspace_floats=off + 2 * tiles, weight_jobs=jobs)
+    d.update(row_tile=row_tile, lds_bytes=lds_bytes, gl_off=gl_off, partial_off=off, loss_tiles=tiles, workspace_floats=off + 2 * tiles,
+             weight_jobs=jobs)
     return d
 
 
 def smallest_ragged_b(net):
     """The smallest batch at which some layer of either pass gets more than one slice and a last slice shorter than the others."""
     est, actor, critic = NETS[net]
-    for b in range(1, 4096):
-        for p in (restated_plan_ee(b, est, actor, critic), restated_plan_est(b, est)):
-            for S, per in [x for c in zip(p["slices"], p["slice_rows"]) for x in zip(*c)]:
-                if S > 1 and b % per:
-                    return b
-    raise AssertionError(net)
+    return sup.smallest_ragged_b(lambda b: restated_plan_ee(b, est, actor, critic), lambda b: restated_plan_est(b, est))
 
 
 # ---- inputs ---------------------------------------------------------------------------------------------------------------------------------
@@ -129,46 +77,30 @@ def est_names(est):
     return [f"estimator.{i}.{k}" for i in range(len(est) - 1) for k in ("weight", "bias")]
 
 
-def _layers(rng, ch):
-    out = []
-    for li in range(len(ch) - 1):
-        out.append((rng.normal(size=(ch[li + 1], ch[li])) * (1.3 / np.sqrt(ch[li]))).astype(np.float32))
-        out.append((0.2 * rng.normal(size=ch[li + 1])).astype(np.float32))
-    return out
-
-
 def make_inputs(case):
-    """float32 numpy inputs of a case: dict(est, actor, critic (widths), clip, rl_params (rl_names order: actor, critic, std), est_params,
-    features, critic_obs, labels, terminated, grad_mu, grad_sigma, grad_values, upstream).  The clip as tests/train_cases.make_inputs
-    places it: a good share of the means saturates, no pre-clip mean within 1e-3 of it."""
-    c = CASES[case] if isinstance(case, str) else case
-    est, actor, critic = NETS[c["net"]]
+    """float32 numpy inputs of a case (a name of CASES, or a dict of B, seed and either `net` or `widths` = (est, actor, critic)): dict(est,
+    actor, critic (widths), clip, rl_params (rl_names order: actor, critic, std), est_params, features, critic_obs, labels, terminated,
+    grad_mu, grad_sigma, grad_values, upstream).  The clip as tests/train_support.place_clip places it."""
+    c, (est, actor, critic) = sup.case_of(case, CASES, NETS)
     rng, B, f = np.random.default_rng(c["seed"]), c["B"], np.float32
     std = (0.5 + rng.random(actor[-1])).astype(f)
-    x = dict(est=est, actor=actor, critic=critic, clip=None, rl_params=_layers(rng, actor) + _layers(rng, critic) + [std], est_params=_layers(rng, est),
+    x = dict(est=est, actor=actor, critic=critic, clip=None, rl_params=sup.draw_layers(rng, actor) + sup.draw_layers(rng, critic) + [std],
+             est_params=sup.draw_layers(rng, est),
              features=rng.normal(size=(B, est[0])).astype(f), critic_obs=rng.normal(size=(B, critic[0])).astype(f),
              labels=rng.normal(size=(B, est[-1])).astype(f), terminated=(rng.random((B, 1)) > 0.3).astype(f),
              grad_mu=rng.normal(size=(B, actor[-1])).astype(f), grad_sigma=rng.normal(size=(B, actor[-1])).astype(f),
              grad_values=rng.normal(size=(B, critic[-1])).astype(f), upstream=f(0.75))
     if "clip" in c and c["clip"] is None:
         return x
-    pre = rl_forward(x)["mu"]
-    clip = float(f(np.median(np.abs(pre))))
-    while np.abs(np.abs(pre) - clip).min() < 1e-3:
-        clip = float(f(clip + 2.5e-3))
-    x["clip"] = clip
+    x["clip"] = sup.place_clip(rl_forward(x)["mu"])
     return x
 
 
 # ---- the restatement ------------------------------------------------------------------------------------------------------------------------
-def _pairs(ps, dtype):
-    return [(np.asarray(ps[i]).astype(dtype), np.asarray(ps[i + 1]).astype(dtype)) for i in range(0, len(ps), 2)]
-
-
 def _plain(x, dtype):
     """The RL pass as a plain actor-critic pass of tests/train_cases.py on obs = [features | estimator(features)]."""
     feats = np.asarray(x["features"]).astype(dtype)
-    est = tc._mlp(_pairs(x["est_params"], dtype), feats, dtype)[-1]
+    est = sup.mlp(sup.pairs(x["est_params"], dtype), feats, dtype)[-1]
     y = dict(actor=x["actor"], critic=x["critic"], clip=x["clip"], params=[x["rl_params"][-1]] + list(x["rl_params"][:-1]),
              obs=np.concatenate([feats, est], axis=1), critic_obs=x["critic_obs"])
     for k in ("grad_mu", "grad_sigma", "grad_values"):
@@ -194,29 +126,16 @@ def est_pass(x, dtype=np.float64, upstream=None, slices=None):
     """dict(loss, grads (est_names order), pred, d) of the estimator pass: d = (p - y) t, loss = sum d^2 / (B NL), d loss / d p =
     2 d t / (B NL), times `upstream` (default x["upstream"]).  `slices` (rows per slice, one number or one per layer): the batch sums are
     formed per slice and added in slice order, as the kernel does."""
-    layers = _pairs(x["est_params"], dtype)
-    acts = tc._mlp(layers, np.asarray(x["features"]).astype(dtype), dtype)
+    layers = sup.pairs(x["est_params"], dtype)
+    acts = sup.mlp(layers, np.asarray(x["features"]).astype(dtype), dtype)
     t, y = np.asarray(x["terminated"]).astype(dtype), np.asarray(x["labels"]).astype(dtype)
     d = (acts[-1] - y) * t
-    n, B = d.size, d.shape[0]
+    n = d.size
     up = dtype(x["upstream"] if upstream is None else upstream)
     G = (2 * d * t / n * up).astype(dtype)
-    grads = []
-    for li in range(len(layers) - 1, -1, -1):
-        H = acts[li]
-        per = B if slices is None else int(slices) if isinstance(slices, (int, np.integer)) else int(slices[li])
-        grads = [tc.slice_sum(per, G, H), tc.slice_sum(per, G, phases=4)] + grads
-        if li:
-            G = ((G @ layers[li][0]) * np.where(H > 0, 1, H + 1)).astype(dtype)
+    pers = [int(slices)] * len(layers) if isinstance(slices, (int, np.integer)) else slices
+    grads, _ = sup.chain_backward(layers, acts, G, dtype, pers)
     return dict(loss=(d * d).sum() / n, grads=grads, pred=acts[-1], d=d)
-
-
-def _mlp_t(h, ps):
-    for i in range(0, len(ps), 2):
-        h = torch.nn.functional.linear(h, ps[i], ps[i + 1])
-        if i < len(ps) - 2:
-            h = torch.nn.functional.elu(h)
-    return h
 
 
 def torch_passes(x, dtype=torch.float32):
@@ -227,11 +146,11 @@ def torch_passes(x, dtype=torch.float32):
     est = [t(p).requires_grad_(True) for p in x["est_params"]]
     na = 2 * (len(x["actor"]) - 1)
     feats = t(x["features"])
-    mu = _mlp_t(torch.cat((feats, _mlp_t(feats, est)), dim=-1), rl[:na])
+    mu = sup.mlp_t(torch.cat((feats, sup.mlp_t(feats, est)), dim=-1), rl[:na])
     if x["clip"] is not None:
         mu = torch.nn.functional.hardtanh(mu, -x["clip"], x["clip"])
     sigma = mu * 0.0 + rl[-1]
-    values = _mlp_t(t(x["critic_obs"]), rl[na:-1])
+    values = sup.mlp_t(t(x["critic_obs"]), rl[na:-1])
     n = lambda v: v.detach().double().numpy().copy()
     out = dict(mu=n(mu), sigma=n(sigma), values=n(values))
     if "grad_mu" in x:
@@ -240,38 +159,10 @@ def torch_passes(x, dtype=torch.float32):
         for p in est:
             p.grad = None
     term = t(x["terminated"])
-    loss = torch.nn.functional.mse_loss(_mlp_t(feats, est) * term, t(x["labels"]) * term)
+    loss = torch.nn.functional.mse_loss(sup.mlp_t(feats, est) * term, t(x["labels"]) * term)
     (loss * float(x.get("upstream", 1.0))).backward()
     out.update(loss=n(loss), est_grads=[n(p.grad) for p in est])
     return out
-
-
-# ---- the parity rule (tests/train_cases.py's, with the loss as an output) -------------------------------------------------------------------
-CLASSES = ("outputs", "loss", "grad_weight", "grad_bias", "grad_std")
-
-
-def tensor_class(name):
-    return "outputs" if name in ("mu", "sigma", "values") else "loss" if name == "loss" else "grad_std" if name == "std" else \
-        "grad_weight" if name.endswith("weight") else "grad_bias"
-
-
-def check_parity(got, ref64, ref32, label, report=None):
-    """Every tensor of ref64 against |kernel - f64| <= PARITY_FACTOR * max(|torch-CPU-f32 - f64|, ulp of the tensor's largest magnitude);
-    prints the worst ratio of each class before it asserts."""
-    worst, bad = {}, []
-    for name, r64 in ref64.items():
-        err, err32 = tc.max_err(got[name], r64), tc.max_err(ref32[name], r64)
-        bound = tc.parity_bound(err32, r64)
-        ratio = err / (bound / PARITY_FACTOR) if bound else (0.0 if err == 0.0 else float("inf"))
-        k = tensor_class(name)
-        worst[k] = max(worst.get(k, 0.0), ratio if np.isfinite(ratio) else float("inf"))
-        if not (np.isfinite(err) and err <= bound):
-            bad.append(f"{label} {name}: |kernel - f64| = {err:.3e} above {bound:.3e} (torch f32 {err32:.3e})")
-    print(f"{label}: worst |kernel - f64| / max(|f32 - f64|, ulp): " + ", ".join(f"{k} {v:.3f}" for k, v in worst.items()) + f" (allowed {PARITY_FACTOR:g})")
-    if report is not None:
-        report.append((label, worst))
-    assert not bad, "\n".join(bad)
-    return worst
 
 
 def named(x, outs, rl_grads, loss, est_grads):
@@ -295,23 +186,10 @@ class Module(torch.nn.Module):
 
     def __init__(self, x, device="cpu", dtype=torch.float32):
         super().__init__()
-        nn = torch.nn
-
-        def chain(widths, clip):
-            mods = []
-            for i in range(len(widths) - 1):
-                mods.append(nn.Linear(widths[i], widths[i + 1]))
-                if i < len(widths) - 2:
-                    mods.append(nn.ELU())
-            if clip is not None:
-                mods.append(nn.Hardtanh(-clip, clip))
-            return nn.Sequential(*mods)
-        self.actor, self.critic, self.estimator = chain(x["actor"], x["clip"]), chain(x["critic"], None), chain(x["est"], None)
-        self.std = nn.Parameter(torch.zeros(x["actor"][-1]))
+        self.actor, self.critic, self.estimator = sup.sequential(x["actor"], x["clip"]), sup.sequential(x["critic"], None), sup.sequential(x["est"], None)
+        self.std = torch.nn.Parameter(torch.zeros(x["actor"][-1]))
         self.to(device=device, dtype=dtype)
-        with torch.no_grad():
-            for p, v in zip(self.rl_parameters() + self.estimator_parameters(), list(x["rl_params"]) + list(x["est_params"])):
-                p.copy_(torch.as_tensor(np.asarray(v)).to(dtype))
+        sup.set_parameters(self.rl_parameters() + self.estimator_parameters(), list(x["rl_params"]) + list(x["est_params"]), dtype)
 
     def rl_parameters(self):
         return list(self.actor.parameters()) + list(self.critic.parameters()) + [self.std]
@@ -327,42 +205,19 @@ class Module(torch.nn.Module):
         return torch.nn.functional.mse_loss(self.estimator(features) * terminated, labels * terminated)
 
 
-# ---- the golden fixture ---------------------------------------------------------------------------------------------------------------------
+# ---- the golden fixture (tests/golden/gen_ppo_ee_train_fixtures.py) -------------------------------------------------------------------------
 FIXTURE_COLUMNS = ("critic_obs", "features", "actions", "target_values", "advantages", "returns", "old_log_prob", "old_mu", "old_sigma")
+EST_COLUMNS = ("est_features", "est_labels", "est_terminated")
 CFG_KEYS = ("lr0", "beta1", "beta2", "eps", "max_grad_norm", "desired_kl", "steps", "clip_param", "value_loss_coef", "entropy_coef", "clip_actions",
             "estimator_lr", "est_steps", "est_epochs")
 
 
 def load_fixture(path):
-    """dict(names, rl_names, est_names, shapes (by name), est / actor / critic widths, cfg, init, per RL step the columns, mu, sigma, values,
-    loss, kl, lr, grad_norm, grads, params; per estimator step est_features, est_labels, est_terminated, est_loss, est_grads, est_grad_norm,
-    est_params), float64; init / params / est_params as dicts name -> array, grads / est_grads as lists in rl_names / est_names order."""
-    z = np.load(path)
-    names = [str(n) for n in z["names"]]
-    shapes = {n: tuple(int(d) for d in s if d) for n, s in zip(names, z["shapes"])}
-
-    def split(flat, order):
-        out, at = [], 0
-        for n in order:
-            size = int(np.prod(shapes[n]))
-            out.append(flat[at:at + size].reshape(shapes[n]).copy())
-            at += size
-        assert at == flat.size
-        return out
-    cfg = dict(zip(CFG_KEYS, (float(v) for v in z["cfg"])))
-    for k in ("steps", "est_steps", "est_epochs"):
-        cfg[k] = int(cfg[k])
-    rl, est = [str(n) for n in z["rl_names"]], [str(n) for n in z["est_names"]]
-    widths = lambda chain: [shapes[n][1] for n in names if n.startswith(chain) and n.endswith("weight")][:1] + \
-        [shapes[n][0] for n in names if n.startswith(chain) and n.endswith("weight")]
-    out = dict(names=names, rl_names=rl, est_names=est, shapes=shapes, cfg=cfg, est=widths("estimator"), actor=widths("actor"), critic=widths("critic"),
-               init=dict(zip(names, split(z["init"], names))), params=[dict(zip(names, split(p, names))) for p in z["params"]],
-               est_params=[dict(zip(names, split(p, names))) for p in z["est_params"]], grads=[split(g, rl) for g in z["grads"]],
-               est_grads=[split(g, est) for g in z["est_grads"]])
-    for k in FIXTURE_COLUMNS + ("mu", "sigma", "values", "loss", "kl", "lr", "grad_norm", "est_features", "est_labels", "est_terminated", "est_loss",
-                                "est_grad_norm"):
-        out[k] = z[k]
-    return out
+    """tests/train_support.load_two_pass_fixture's dict with est / actor / critic widths: per RL step the columns, mu, sigma, values, loss,
+    kl, lr, grad_norm, grads, params; per estimator step est_features, est_labels, est_terminated, est_loss, est_grads, est_grad_norm,
+    est_params."""
+    return sup.load_two_pass_fixture(path, CFG_KEYS, dict(est="estimator", actor="actor", critic="critic"), "est", FIXTURE_COLUMNS + EST_COLUMNS + (
+        "mu", "sigma", "values", "loss", "kl", "lr", "grad_norm", "est_loss", "est_grad_norm"))
 
 
 def fixture_inputs(fx, params, rl_step=None, est_step=None):
@@ -374,10 +229,3 @@ def fixture_inputs(fx, params, rl_step=None, est_step=None):
     if est_step is not None:
         x.update(features=fx["est_features"][est_step], labels=fx["est_labels"][est_step], terminated=fx["est_terminated"][est_step])
     return x
-
-
-def fixture_loss_inputs(fx, s, mu, sigma, values):
-    """tests/ppo_loss_cases.restate's input for RL step s of the fixture around the given network outputs."""
-    g = dict(mu=mu, sigma=sigma, actions=fx["actions"][s], advantages=fx["advantages"][s], old_log_prob=fx["old_log_prob"][s],
-             old_mu=fx["old_mu"][s], old_sigma=fx["old_sigma"][s])
-    return dict(groups=[g], values=values, returns=fx["returns"][s], target_values=fx["target_values"][s])
