@@ -318,6 +318,13 @@ def load_lib():
         lib.lg_train_enc_plan.argtypes = [C.POINTER(LgTrainEncArgs), C.POINTER(LgTrainTSPlan)]
         lib.lg_train_enc_forward.argtypes = [C.POINTER(LgTrainEncArgs), vp]
         lib.lg_train_enc_backward.argtypes = [C.POINTER(LgTrainEncArgs), vp]
+    if hasattr(lib, "lg_train_dwaq_forward"):    # absent from libraries older than the DreamWaQ learner passes
+        lib.lg_train_dwaq_plan.argtypes = [C.POINTER(LgTrainDwaqArgs), C.POINTER(LgTrainDwaqPlan)]
+        lib.lg_train_dwaq_forward.argtypes = [C.POINTER(LgTrainDwaqArgs), vp]
+        lib.lg_train_dwaq_backward.argtypes = [C.POINTER(LgTrainDwaqArgs), vp]
+        lib.lg_train_vae_plan.argtypes = [C.POINTER(LgTrainVaeArgs), C.POINTER(LgTrainDwaqPlan)]
+        lib.lg_train_vae_forward.argtypes = [C.POINTER(LgTrainVaeArgs), vp]
+        lib.lg_train_vae_backward.argtypes = [C.POINTER(LgTrainVaeArgs), vp]
         for f in TRAIN_TS_EXPORTS:
             getattr(lib, f).restype = C.c_int
     lib.lg_last_error.restype = C.c_char_p
@@ -361,6 +368,11 @@ TRAIN_TS_EXPORTS = ["lg_train_ts_plan", "lg_train_enc_plan", "lg_train_ts_forwar
 TRAIN_TS_CHAINS, TRAIN_TS_PRIVILEGE, TRAIN_TS_ACTOR, TRAIN_TS_CRITIC, TRAIN_TS_HISTORY, TRAIN_TS_RL_CHAINS = 4, 0, 1, 2, 3, 3
 TRAIN_ENC_CHAINS, TRAIN_ENC_HISTORY, TRAIN_ENC_PRIVILEGE = 2, 0, 1
 TRAIN_TS_TARGET_JOBS, TRAIN_TS_THREADS = 2048, 256
+TRAIN_DWAQ_EXPORTS = ["lg_train_dwaq_plan", "lg_train_vae_plan", "lg_train_dwaq_forward", "lg_train_dwaq_backward", "lg_train_vae_forward",
+                      "lg_train_vae_backward"]                                                # include/lgtraindwaq.h
+TRAIN_DWAQ_CHAINS, TRAIN_DWAQ_ENCODER, TRAIN_DWAQ_LATENT_MU, TRAIN_DWAQ_LATENT_VAR, TRAIN_DWAQ_VEL_MU, TRAIN_DWAQ_VEL_VAR = 7, 0, 1, 2, 3, 4
+TRAIN_DWAQ_ACTOR, TRAIN_DWAQ_CRITIC, TRAIN_DWAQ_HEADS, TRAIN_VAE_CHAINS, TRAIN_VAE_DECODER, TRAIN_VAE_LOSSES = 5, 6, 4, 6, 5, 4
+TRAIN_DWAQ_TARGET_JOBS, TRAIN_DWAQ_THREADS = 2048, 256
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 2048
 POLICY_MAX_RNN_LAYERS, POLICY_MAX_RNN_HIDDEN = 2, 512
 POLICY_LSTM, POLICY_GRU = 1, 2
@@ -537,6 +549,33 @@ class LgTrainTSPlan(C.Structure):
                 ("h_off", i64 * POLICY_MAX_LAYERS * TRAIN_TS_CHAINS), ("g_off", i64 * POLICY_MAX_LAYERS * TRAIN_TS_CHAINS),
                 ("p_off", i64 * POLICY_MAX_LAYERS * TRAIN_TS_CHAINS), ("std_p_off", i64), ("cat_off", i64), ("gl_off", i64), ("y_off", i64),
                 ("partial_off", i64), ("workspace_floats", i64)]
+
+
+class LgTrainDwaqArgs(C.Structure):
+    _fields_ = [("n_rows", i32), ("clip_on", i32), ("clip_actions", f32), ("n_obs", i32), ("var_clip", f32), ("noise_stride", i32),
+                ("reserved", i32 * 2), ("chain", LgTrainChain * TRAIN_DWAQ_CHAINS), ("noise", C.c_void_p),
+                ("std", C.c_void_p), ("grad_std", C.c_void_p), ("mu", C.c_void_p), ("sigma", C.c_void_p), ("values", C.c_void_p),
+                ("grad_mu", C.c_void_p), ("grad_sigma", C.c_void_p), ("grad_values", C.c_void_p),
+                ("mu_stride", i32), ("sigma_stride", i32), ("values_stride", i32),
+                ("grad_mu_stride", i32), ("grad_sigma_stride", i32), ("grad_values_stride", i32),
+                ("workspace", C.c_void_p), ("workspace_capacity", i64)]
+
+
+class LgTrainVaeArgs(C.Structure):
+    _fields_ = [("n_rows", i32), ("labels_stride", i32), ("next_states_stride", i32), ("mask_stride", i32), ("noise_stride", i32),
+                ("var_clip", f32), ("kld_weight", f32), ("reserved", i32), ("chain", LgTrainChain * TRAIN_VAE_CHAINS),
+                ("labels", C.c_void_p), ("next_states", C.c_void_p), ("mask", C.c_void_p), ("noise", C.c_void_p), ("loss", C.c_void_p),
+                ("upstream", C.c_void_p), ("workspace", C.c_void_p), ("workspace_capacity", i64)]
+
+
+class LgTrainDwaqPlan(C.Structure):
+    _fields_ = [("row_tile", i32), ("lds_bytes", i32), ("slices", i32 * POLICY_MAX_LAYERS * TRAIN_DWAQ_CHAINS),
+                ("slice_rows", i32 * POLICY_MAX_LAYERS * TRAIN_DWAQ_CHAINS), ("std_slices", i32), ("std_slice_rows", i32),
+                ("weight_jobs", i32), ("loss_tiles", i32), ("lds_x", i32), ("lds_y", i32),
+                ("h_off", i64 * POLICY_MAX_LAYERS * TRAIN_DWAQ_CHAINS), ("g_off", i64 * POLICY_MAX_LAYERS * TRAIN_DWAQ_CHAINS),
+                ("p_off", i64 * POLICY_MAX_LAYERS * TRAIN_DWAQ_CHAINS), ("std_p_off", i64), ("cat_off", i64), ("enc_out_off", i64),
+                ("head_off", i64 * TRAIN_DWAQ_HEADS), ("gl_rec_off", i64), ("gl_est_off", i64), ("partial_off", i64), ("scale_off", i64),
+                ("workspace_floats", i64)]
 
 
 def check(rc, lib=None):

@@ -16,9 +16,11 @@ gradient for the observations and no double backward.  There is no CPU path: the
 
 FusedTrainPassEE (below; include/lgtrainee.h, csrc/lg_train_ee.hip) is the same for ActorCriticEE under PPO_EE: the RL pass and the
 supervised estimator pass.  FusedTrainPassTS (include/lgtraints.h, csrc/lg_train_ts.hip) is the same for ActorCriticTS under PPO_TS: the RL
-pass, whose gradient reaches the privilege encoder through the latent, and the supervised history-encoder pass.
+pass, whose gradient reaches the privilege encoder through the latent, and the supervised history-encoder pass.  FusedTrainPassDreamWaQ
+(include/lgtraindwaq.h, csrc/lg_train_dwaq.hip) is the same for ActorCriticDreamWaQ under PPO_DreamWaQ: the RL pass behind the VAE's
+encoder, heads and reparameterised draw, and the VAE pass with its three losses.
 
-The three families share what is below `_Pass`: one record per pass (workspace, call counter, entry points, descriptor builder), one
+The four families share what is below `_Pass`: one record per pass (workspace, call counter, entry points, descriptor builder), one
 autograd.Function for an RL pass and one for a loss pass, driven by that record.  A refusal carries the name of the surface that first
 raised it, which is why the helpers take an `owner`."""
 from __future__ import annotations
@@ -33,7 +35,7 @@ from . import abi
 _OTHER_FAMILIES = (("estimator", "ActorCriticEE"), ("privilege_encoder", "ActorCriticTS / ActorCriticCTS"),
                    ("history_encoder", "ActorCriticTS / ActorCriticCTS"), ("vae", "ActorCriticDreamWaQ"),
                    ("memory_a", "ActorCriticRecurrent"), ("memory_c", "ActorCriticRecurrent"))
-_PLAIN, _EE, _TS = "FusedTrainPass", "FusedTrainPassEE", "FusedTrainPassTS"
+_PLAIN, _EE, _TS, _DWAQ = "FusedTrainPass", "FusedTrainPassEE", "FusedTrainPassTS", "FusedTrainPassDreamWaQ"
 
 
 class TrainChainSpec:
@@ -70,7 +72,7 @@ def _check_param(t, what, device, owner=_PLAIN):
         raise ValueError(f"{owner}: {what} is on {t.device}, not on {device}")
 
 
-def _describe_chain(name, seq, device, allow_clip, owner=_PLAIN):
+def _describe_chain(name, seq, device, allow_clip, owner=_PLAIN, allow_last_elu=False):
     if not isinstance(seq, nn.Sequential):
         raise ValueError(f"{owner}: {name} is {type(seq).__name__}, expected an nn.Sequential of Linear / ELU"
                          + (" / Hardtanh" if allow_clip else ""))
@@ -108,7 +110,7 @@ def _describe_chain(name, seq, device, allow_clip, owner=_PLAIN):
         raise ValueError(f"{owner}: {name} has no Linear layer")
     if len(linears) > abi.POLICY_MAX_LAYERS:
         raise ValueError(f"{owner}: {name} has {len(linears)} Linear layers, the kernel takes {abi.POLICY_MAX_LAYERS}")
-    if elu[-1]:
+    if elu[-1] and not allow_last_elu:
         raise ValueError(f"{owner}: {name} ends in an ELU, expected a Linear output layer")
     return TrainChainSpec(name, linears, elu, clip)
 
@@ -190,9 +192,9 @@ def _bind_workspace(a, workspace, device, owner=_EE):
         a.workspace, a.workspace_capacity = workspace.data_ptr(), workspace.numel()
 
 
-def _scalar(t, what, device):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != 1 or (device is not None and t.device != device):
-        raise ValueError(f"{_EE}: {what} must be one float32" + (f" on {device}" if device is not None else ""))
+def _scalar(t, what, device, n=1, owner=_EE):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.numel() != n or not t.is_contiguous() or (device is not None and t.device != device):
+        raise ValueError(f"{owner}: {what} must be {'one' if n == 1 else n} float32" + (f" on {device}" if device is not None else ""))
     return t.data_ptr()
 
 
@@ -667,3 +669,252 @@ class FusedTrainPassTS:
         """mse_loss(history_encoder(obs_history) * terminated, privilege_encoder(privileged_obs).detach() * terminated) as a 0-dim tensor
         with autograd.  Two launches."""
         return _apply(_LossFunction, self._enc, obs_history, privileged_obs, terminated)
+
+
+# ---- the DreamWaQ family (include/lgtraindwaq.h, csrc/lg_train_dwaq.hip) ------------------------------------------------------------------------
+_DWAQ_FOREIGN = (("estimator", "ActorCriticEE"), ("privilege_encoder", "ActorCriticTS / ActorCriticCTS"),
+                 ("history_encoder", "ActorCriticTS / ActorCriticCTS"), ("memory_a", "ActorCriticRecurrent"), ("memory_c", "ActorCriticRecurrent"))
+_HEADS = ("latent_mu", "latent_var", "vel_mu", "vel_var")          # abi.TRAIN_DWAQ_LATENT_MU + h, and the order of vae.parameters()
+
+
+class TrainSpecDreamWaQ:
+    """ActorCriticDreamWaQ as the kernels take it: the VAE's encoder (every Linear behind an ELU, the last too), its four one-layer heads,
+    its decoder, the actor (whose input is [obs | z | v]) and the critic."""
+
+    def __init__(self, encoder, heads, decoder, actor, critic, std, var_clip):
+        self.encoder, self.heads, self.decoder, self.actor, self.critic, self.std, self.var_clip = encoder, heads, decoder, actor, critic, std, var_clip
+        self.num_actions, self.clip_actions = actor.widths[-1], actor.clip
+        self.num_latent, self.num_explicit = heads[0].widths[-1], heads[2].widths[-1]
+        self.num_obs = actor.widths[0] - self.num_latent - self.num_explicit
+        self.vae_chains = (encoder,) + tuple(heads) + (decoder,)
+
+    def rl_parameters(self):
+        """Actor, critic, then std: the order of PPO_DreamWaQ.rl_parameters and of the RL pass's gradients."""
+        return [p for c in (self.actor, self.critic) for l in c.linears for p in (l.weight, l.bias)] + [self.std]
+
+    def rl_parameter_names(self):
+        return [f"{c.name}.{i}.{n}" for c in (self.actor, self.critic) for i in range(len(c.linears)) for n in ("weight", "bias")] + ["std"]
+
+    def vae_parameters(self):
+        """Encoder, latent_mu, latent_var, vel_mu, vel_var, decoder: the order of actor_critic.vae.parameters() and of the VAE pass's gradients."""
+        return [p for c in self.vae_chains for l in c.linears for p in (l.weight, l.bias)]
+
+    def vae_parameter_names(self):
+        return [f"vae.{c.name}.{i}.{n}" for c in self.vae_chains for i in range(len(c.linears)) for n in ("weight", "bias")]
+
+
+def _describe_dwaq_head(vae, name, device):
+    """One head by the rules of policy.py's _describe_head: a Linear, behind a symmetric Hardtanh for a log-variance.  (chain, clip)."""
+    m, where, clip = getattr(vae, name, None), f"vae.{name}", None
+    if name.endswith("_var"):
+        if not isinstance(m, nn.Sequential) or len(m) != 2 or not isinstance(m[0], nn.Linear) or not isinstance(m[1], nn.Hardtanh):
+            raise ValueError(f"{_DWAQ}: {where} is not Sequential(Linear, Hardtanh): the log-variance head of the VAE")
+        if m[1].min_val != -m[1].max_val or not m[1].max_val >= 0:
+            raise ValueError(f"{_DWAQ}: {where}[1] (Hardtanh({m[1].min_val}, {m[1].max_val})) must be a symmetric clip")
+        clip, m, where = float(m[1].max_val), m[0], where + "[0]"
+    if not isinstance(m, nn.Linear):
+        raise ValueError(f"{_DWAQ}: {where} is {type(m).__name__}, expected a Linear")
+    if m.bias is None:
+        raise ValueError(f"{_DWAQ}: {where} has no bias")
+    if m.in_features > abi.POLICY_MAX_WIDTH or m.out_features > abi.POLICY_MAX_WIDTH:
+        raise ValueError(f"{_DWAQ}: {where} is {m.in_features} -> {m.out_features}, widths are limited to {abi.POLICY_MAX_WIDTH}")
+    _check_param(m.weight, f"{where}.weight", device, _DWAQ)
+    _check_param(m.bias, f"{where}.bias", device, _DWAQ)
+    return TrainChainSpec(name, [m], [False], None), clip
+
+
+def describe_dwaq(actor_critic, device=None):
+    """ActorCriticDreamWaQ as the kernels take it (duck-typed: .vae with .encoder, the four heads and .decoder; .actor, .critic, .std).  The
+    encoder may end in an ELU, as the reference's does, on this path only; the actor may end in a Hardtanh or not.  Refusals are ValueErrors
+    that name the layer or the member."""
+    vae = getattr(actor_critic, "vae", None)
+    if vae is None:
+        raise ValueError(f"{_DWAQ}: the module has no .vae; the plain ActorCritic is FusedTrainPass's")
+    c, std = _describe(actor_critic, device, _DWAQ, _DWAQ_FOREIGN, " beside .vae; only ActorCriticDreamWaQ is built", (("actor", True), ("critic", False)), _DWAQ)
+    for need in ("encoder", "decoder"):
+        if getattr(vae, need, None) is None:
+            raise ValueError(f"{_DWAQ}: the module's .vae has no .{need}")
+    encoder = _describe_chain("encoder", vae.encoder, device, False, _DWAQ, allow_last_elu=True)
+    decoder = _describe_chain("decoder", vae.decoder, device, False, _DWAQ)
+    heads, clips = zip(*(_describe_dwaq_head(vae, name, device) for name in _HEADS))
+    if clips[1] != clips[3]:
+        raise ValueError(f"{_DWAQ}: vae.latent_var clips to {clips[1]}, vae.vel_var to {clips[3]}; the kernel takes one clip")
+    H = encoder.widths[-1]
+    for h in heads:
+        if h.widths[0] != H:
+            raise ValueError(f"{_DWAQ}: vae.{h.name} takes {h.widths[0]} inputs, the encoder ends at {H} columns")
+    for a, b in ((heads[0], heads[1]), (heads[2], heads[3])):
+        if a.widths[-1] != b.widths[-1]:
+            raise ValueError(f"{_DWAQ}: vae.{a.name} has {a.widths[-1]} outputs, vae.{b.name} {b.widths[-1]}")
+    L, E = heads[0].widths[-1], heads[2].widths[-1]
+    if decoder.widths[0] != L + E:
+        raise ValueError(f"{_DWAQ}: decoder[0] takes {decoder.widths[0]} inputs, but [z | v] has {L} + {E} columns")
+    if c["actor"].widths[0] <= L + E:
+        raise ValueError(f"{_DWAQ}: actor[0] takes {c['actor'].widths[0]} inputs, but [obs | z | v] has O + {L} + {E} columns with O >= 1")
+    spec = TrainSpecDreamWaQ(encoder, heads, decoder, c["actor"], c["critic"], std, clips[1])
+    if isinstance(vae, nn.Module):
+        theirs = list(vae.parameters())
+        if len(theirs) != len(spec.vae_parameters()) or any(a is not b for a, b in zip(theirs, spec.vae_parameters())):
+            raise ValueError(f"{_DWAQ}: vae.parameters() are not the encoder's, latent_mu's, latent_var's, vel_mu's, vel_var's and the decoder's, in that order")
+    return spec
+
+
+def _dwaq_front(a, spec, obs_history, noise, n, device, grads=None):
+    """The encoder, the four heads and the noise of either descriptor; `grads`: the gradient tensors of those five chains, or None."""
+    enc = a.chain[abi.TRAIN_DWAQ_ENCODER]
+    enc.input, enc.in_stride = _rows(obs_history, spec.encoder.widths[0], "obs_history", n, device, _DWAQ)
+    at = 0
+    for ci, c in enumerate((spec.encoder,) + tuple(spec.heads)):
+        _fill_chain(a.chain[ci], c, device, None if grads is None else grads[at:at + 2 * len(c.linears)])
+        at += 2 * len(c.linears)
+    a.var_clip = spec.var_clip
+    a.noise, a.noise_stride = _rows(noise, spec.num_latent + spec.num_explicit, "latent_noise", n, device, _DWAQ)
+    return at
+
+
+def dwaq_args(spec, obs, obs_history, critic_obs, noise, mu, sigma, values, workspace, grads=None, grad_mu=None, grad_sigma=None, grad_values=None,
+              device=None):
+    """LgTrainDwaqArgs of one call of the RL pass.  `grads` (backward): the tensors that take the gradients, in spec.rl_parameters() order
+    (actor, critic, std).  The encoder's and the heads' gradient pointers stay null: the pass has no use for them."""
+    a = abi.LgTrainDwaqArgs()
+    if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or obs.shape[0] < 1:
+        raise ValueError(f"{_DWAQ}: obs must be a (B, {spec.num_obs}) float32 tensor with B >= 1")
+    n = int(obs.shape[0])
+    a.n_rows, a.n_obs = n, spec.num_obs
+    act, cri = a.chain[abi.TRAIN_DWAQ_ACTOR], a.chain[abi.TRAIN_DWAQ_CRITIC]
+    act.input, act.in_stride = _rows(obs, spec.num_obs, "obs", n, device, _DWAQ)
+    cri.input, cri.in_stride = _rows(critic_obs, spec.critic.widths[0], "critic_obs", n, device, _DWAQ)
+    _dwaq_front(a, spec, obs_history, noise, n, device)
+    g_act, g_cri, g_std = _rl_grads(grads, spec.actor, spec.critic)
+    _fill_chain(act, spec.actor, device, g_act)
+    _fill_chain(cri, spec.critic, device, g_cri)
+    _fill_heads(a, spec, mu, sigma, values, n, device, _DWAQ, g_std, grad_mu, grad_sigma, grad_values)
+    _bind_workspace(a, workspace, device, _DWAQ)
+    return a
+
+
+def vae_args(spec, obs_history, labels, next_states, terminated, noise, kld_weight, loss, workspace, grads=None, upstream=None, device=None):
+    """LgTrainVaeArgs of one call of the VAE pass.  `loss`: the tensor of abi.TRAIN_VAE_LOSSES floats (total, estimation, reconstruction,
+    kld); `grads` (backward): in spec.vae_parameters() order."""
+    a = abi.LgTrainVaeArgs()
+    if not isinstance(obs_history, torch.Tensor) or obs_history.dim() != 2 or obs_history.shape[0] < 1:
+        raise ValueError(f"{_DWAQ}: obs_history must be a (B, {spec.encoder.widths[0]}) float32 tensor with B >= 1")
+    n = int(obs_history.shape[0])
+    a.n_rows, a.kld_weight = n, float(kld_weight)
+    at = _dwaq_front(a, spec, obs_history, noise, n, device, grads)
+    _fill_chain(a.chain[abi.TRAIN_VAE_DECODER], spec.decoder, device, None if grads is None else grads[at:])
+    a.labels, a.labels_stride = _rows(labels, spec.num_explicit, "explicit_info_labels", n, device, _DWAQ)
+    a.next_states, a.next_states_stride = _rows(next_states, spec.decoder.widths[-1], "next_states", n, device, _DWAQ)
+    a.mask, a.mask_stride = _rows(terminated, 1, "terminated", n, device, _DWAQ)
+    if loss is not None:
+        a.loss = _scalar(loss, "the losses", device, abi.TRAIN_VAE_LOSSES, _DWAQ)
+    if upstream is not None:
+        a.upstream = _scalar(upstream, "the upstream gradient", device, 1, _DWAQ)
+    _bind_workspace(a, workspace, device, _DWAQ)
+    return a
+
+
+def plan_dwaq(n_rows, encoder_widths, latent, explicit, actor_widths, critic_widths):
+    """LgTrainDwaqPlan of the RL pass (lg_train_dwaq_plan): the encoder ends at H columns, the heads are H -> latent, latent, explicit, explicit."""
+    H = encoder_widths[-1]
+    heads = tuple((abi.TRAIN_DWAQ_LATENT_MU + h, (H, w)) for h, w in enumerate((latent, latent, explicit, explicit)))
+    return _plan("lg_train_dwaq_plan", abi.LgTrainDwaqArgs, abi.LgTrainDwaqPlan, n_rows,
+                 ((abi.TRAIN_DWAQ_ENCODER, encoder_widths),) + heads + ((abi.TRAIN_DWAQ_ACTOR, actor_widths), (abi.TRAIN_DWAQ_CRITIC, critic_widths)),
+                 n_obs=int(actor_widths[0]) - int(latent) - int(explicit))
+
+
+def plan_vae(n_rows, encoder_widths, latent, explicit, decoder_widths):
+    """LgTrainDwaqPlan of the VAE pass (lg_train_vae_plan)."""
+    H = encoder_widths[-1]
+    heads = tuple((abi.TRAIN_DWAQ_LATENT_MU + h, (H, w)) for h, w in enumerate((latent, latent, explicit, explicit)))
+    return _plan("lg_train_vae_plan", abi.LgTrainVaeArgs, abi.LgTrainDwaqPlan, n_rows,
+                 ((abi.TRAIN_DWAQ_ENCODER, encoder_widths),) + heads + ((abi.TRAIN_VAE_DECODER, decoder_widths),))
+
+
+class VaeLosses:
+    """What FusedTrainPassDreamWaQ.vae_loss returns: .loss (0-dim, with autograd) = explicit_estimation_loss + reconstruction_loss +
+    kld_weight * kld_loss, and the three terms as detached device scalars."""
+
+    def __init__(self, losses):
+        self.loss = losses[0]
+        d = losses.detach()
+        self.explicit_estimation_loss, self.reconstruction_loss, self.kld_loss = d[1], d[2], d[3]
+
+
+class _VaeFunction(torch.autograd.Function):
+    """The four losses of the VAE pass `ps` as one (4,) tensor; only element 0, the total, carries a gradient."""
+
+    @staticmethod
+    def forward(ctx, ps, kld_weight, n_inputs, *inputs_and_params):
+        inputs = inputs_and_params[:n_inputs]
+        losses = torch.empty(abi.TRAIN_VAE_LOSSES, dtype=torch.float32, device=ps.device)
+        args = ps.args(ps.spec, *inputs, kld_weight, losses, None, device=ps.device)
+        ctx.ps, ctx.inputs, ctx.kld_weight, ctx.call = ps, inputs, kld_weight, ps.run_forward(args, int(inputs[0].shape[0]))
+        return losses
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_losses):
+        ps = ctx.ps
+        up = grad_losses.to(torch.float32)[:1].contiguous()             # stays on the device: the kernel reads it there
+        grads = ps.run_backward(ctx.call, lambda grads: ps.args(ps.spec, *ctx.inputs, ctx.kld_weight, None, ps.workspace, grads, up, device=ps.device))
+        return (None,) * (3 + len(ctx.inputs)) + tuple(grads)
+
+
+class FusedTrainPassDreamWaQ:
+    """The two network passes of PPO_DreamWaQ.update() on an ActorCriticDreamWaQ (include/lgtraindwaq.h):
+
+        tp = FusedTrainPassDreamWaQ(actor_critic_dreamwaq, kld_weight=vae_kld_weight)
+        mu, sigma, values = tp(obs, obs_history, critic_obs)                              # RL step: one launch; backward three
+        out = tp.vae_loss(obs_history, explicit_info_labels, next_states, terminated)     # VAE step: two launches; backward three
+        out.loss.backward()       # out.explicit_estimation_loss, out.reconstruction_loss, out.kld_loss: detached device scalars
+
+    Optimise tp.rl_parameters() (actor, critic, std: the reference's order) and tp.vae_parameters() (the order of
+    actor_critic.vae.parameters()) apart.  The RL pass gives the VAE's parameters no gradient (their .grad is left as it was): the reference
+    clears that gradient before anything reads it.  The VAE pass leaves the actor, the critic and std alone.  Each pass has its own workspace
+    and call counter: a forward of one does not invalidate a pending backward of the other; within a pass a backward whose forward has been
+    overwritten raises.
+
+    The KL term is the reference's arithmetic: its (B,) row sums times its (B, 1) mask broadcast to (B, B) before the mean, so that
+    kld = -0.5 * (sum of the row sums) * (sum of the mask) / B^2 whatever a row's own mask.
+
+    latent_noise is the (B, L + E) standard-normal draw of the reparameterisation, columns [z | vel] (FusedPolicy's latent_noise
+    convention).  With latent_noise=None each call draws one torch.randn((B, L + E)) on the device: that is NOT the reference's stream,
+    which draws two randn_like tensors (z, then vel) per call.  The draw is an allocation under torch's generator, so a captured HIP graph
+    needs a caller-owned noise tensor, refilled in place between replays; the VAE backward reads the noise again, so it must not change
+    between a vae_loss and its backward."""
+
+    def __init__(self, actor_critic, kld_weight=1.0):
+        self.device = _module_device(actor_critic, _DWAQ)
+        self.spec = describe_dwaq(actor_critic, self.device)
+        self.kld_weight = float(kld_weight)
+        self._rl = _Pass(_DWAQ, "RL ", "lg_train_dwaq", dwaq_args, self.plan, self.rl_parameters, self.spec, self.device)
+        self._vae = _Pass(_DWAQ, "VAE ", "lg_train_vae", vae_args, self.vae_plan, self.vae_parameters, self.spec, self.device)
+
+    def rl_parameters(self):
+        return self.spec.rl_parameters()
+
+    def vae_parameters(self):
+        return self.spec.vae_parameters()
+
+    def plan(self, n_rows):
+        s = self.spec
+        return plan_dwaq(n_rows, s.encoder.widths, s.num_latent, s.num_explicit, s.actor.widths, s.critic.widths)
+
+    def vae_plan(self, n_rows):
+        s = self.spec
+        return plan_vae(n_rows, s.encoder.widths, s.num_latent, s.num_explicit, s.decoder.widths)
+
+    def _noise(self, like, latent_noise):
+        if latent_noise is not None:
+            return latent_noise
+        return torch.randn((int(like.shape[0]), self.spec.num_latent + self.spec.num_explicit), dtype=torch.float32, device=self.device)
+
+    def __call__(self, obs, obs_history, critic_obs, latent_noise=None):
+        """(mu, sigma, values) of the mini-batch: (B, A), (B, A), (B, 1).  One launch on the current stream."""
+        return _apply(_RLFunction, self._rl, obs, obs_history, critic_obs, self._noise(obs, latent_noise))
+
+    def vae_loss(self, obs_history, explicit_info_labels, next_states, terminated, latent_noise=None):
+        """The VAE loss of PPO_DreamWaQ._compute_vae_loss and its three terms, as a VaeLosses.  Two launches."""
+        inputs = (obs_history, explicit_info_labels, next_states, terminated, self._noise(obs_history, latent_noise))
+        return VaeLosses(_VaeFunction.apply(self._vae, self.kld_weight, len(inputs), *inputs, *self.vae_parameters()))
