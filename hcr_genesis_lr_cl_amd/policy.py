@@ -14,7 +14,7 @@ Three more module shapes are recognised, each still one launch per step (the key
              the privilege encoder and the others the history encoder in the same launch (ppo_cts.py:110-135: two actor passes and four
              torch.cat otherwise).
   DreamWaQ   `.vae` with `.encoder` (Linear / ELU, may end in ELU), `.latent_mu`, `.vel_mu` (Linear), `.latent_var`, `.vel_var`
-             (Sequential(Linear, Hardtanh(-c, c)), one c): the four heads, the clip, the reparameterised draw and the concatenation
+             (a Linear behind Hardtanh(-c, c), one c): the four heads, the clip, the reparameterised draw and the concatenation
              [obs | z | vel] of vae.py:65-101 / actor_critic_dreamwaq.py:145-171 run in the launch.  `.vae.decoder` is the learner's.
   recurrent  `is_recurrent` with `.memory_a.rnn` and `.memory_c.rnn`, each an `nn.LSTM` or `nn.GRU` of one or two layers, H <= 512, in
              front of `.actor` / `.critic` (`ActorCriticRecurrent`): the cell of both memories, the reset of finished envs (`reset=`) and the
@@ -22,6 +22,7 @@ Three more module shapes are recognised, each still one launch per step (the key
              place (`get_hidden_states`, `set_hidden_states`, `reset`, `last_hidden_states`), so a captured call keeps its addresses.
 A history encoder with Conv1d / Flatten (the "TCN" option) and activations other than ELU are refused, with a message that names the
 layer; so is an rnn that is bidirectional, projected, batch-first, without bias, with dropout, of more than two layers or H above 512.
+What a chain, the four heads, a parameter tensor, std and a row matrix must be is nets.py's, one copy shared with train.py.
 
 The draw is torch's when `noise` is given, otherwise the project's Philox4x32-10: counter (env, action quad, call counter, stream tag),
 key = seed, Box-Muller on the uniforms; the call counter is a device cell that a one-lane launch behind the act launch increments, so a
@@ -49,17 +50,10 @@ import ctypes as C
 import torch
 import torch.nn as nn
 
-from . import abi
+from . import abi, nets
+from .nets import ChainSpec, HeadSpec      # the names callers know them by here
 
-class ChainSpec:
-    """One MLP chain as the kernel takes it: its Linear modules in order, which of them an ELU follows, and (actor only) the clip."""
-
-    def __init__(self, name, linears, elu, clip):
-        self.name, self.linears, self.elu, self.clip = name, linears, elu, clip
-
-    @property
-    def widths(self):
-        return [self.linears[0].in_features] + [l.out_features for l in self.linears]
+_OWNER = "FusedPolicy"
 
 
 class MemorySpec:
@@ -108,101 +102,6 @@ class PolicySpec:
                                  self.memory_c, self.critic) if c is not None]
 
 
-class HeadSpec:
-    """The four Linear heads of a DreamWaQ VAE (rsl_rl/modules/vae.py:40-50) and the symmetric clip of the two log-variances."""
-
-    def __init__(self, latent_mu, latent_var, vel_mu, vel_var, clip):
-        self.latent_mu, self.latent_var, self.vel_mu, self.vel_var, self.clip = latent_mu, latent_var, vel_mu, vel_var, clip
-        self.H, self.L, self.E = latent_mu.in_features, latent_mu.out_features, vel_mu.out_features
-
-    @property
-    def linears(self):
-        return (self.latent_mu, self.latent_var, self.vel_mu, self.vel_var)
-
-
-def _check_tensor(t, what, device):
-    if t.dtype != torch.float32:
-        raise ValueError(f"FusedPolicy: {what} is {t.dtype}, the kernel reads float32")
-    if not t.is_contiguous():
-        raise ValueError(f"FusedPolicy: {what} is not contiguous")
-    if device is not None and t.device != device:
-        raise ValueError(f"FusedPolicy: {what} is on {t.device}, not on the HIP device {device}")
-
-
-def _describe_chain(name, seq, device, allow_clip, allow_trailing_elu=False):
-    if not isinstance(seq, nn.Sequential):
-        raise ValueError(f"FusedPolicy: {name} is {type(seq).__name__}, expected an nn.Sequential of Linear / ELU"
-                         + (" / Hardtanh" if allow_clip else "") + " (recurrent and encoder policies keep the torch path)")
-    linears, elu, clip = [], [], None
-    mods = list(seq)
-    for i, m in enumerate(mods):
-        where = f"{name}[{i}]"
-        if clip is not None:
-            raise ValueError(f"FusedPolicy: {where} ({type(m).__name__}) follows the Hardtanh, which must end the actor")
-        if isinstance(m, nn.Linear):
-            if m.bias is None:
-                raise ValueError(f"FusedPolicy: {where} has no bias")
-            if m.in_features > abi.POLICY_MAX_WIDTH or m.out_features > abi.POLICY_MAX_WIDTH:
-                raise ValueError(f"FusedPolicy: {where} is {m.in_features} -> {m.out_features}, widths are limited to {abi.POLICY_MAX_WIDTH}")
-            if linears and linears[-1].out_features != m.in_features:
-                raise ValueError(f"FusedPolicy: {where} takes {m.in_features} inputs, the layer before it gives {linears[-1].out_features}")
-            _check_tensor(m.weight.data, f"{where}.weight", device)
-            _check_tensor(m.bias.data, f"{where}.bias", device)
-            linears.append(m)
-            elu.append(False)
-        elif isinstance(m, nn.ELU):
-            if not linears or elu[-1]:
-                raise ValueError(f"FusedPolicy: {where} (ELU) does not follow a Linear")
-            if m.alpha != 1.0:
-                raise ValueError(f"FusedPolicy: {where} is ELU(alpha={m.alpha}), only alpha = 1 is built")
-            elu[-1] = True
-        elif isinstance(m, nn.Hardtanh) and allow_clip:
-            if i != len(mods) - 1 or not linears or elu[-1] or m.min_val != -m.max_val or not m.max_val >= 0:
-                raise ValueError(f"FusedPolicy: {where} (Hardtanh({m.min_val}, {m.max_val})) must be the symmetric clip behind the actor's last Linear")
-            clip = float(m.max_val)
-        else:
-            raise ValueError(f"FusedPolicy: {where} is {type(m).__name__}; only Linear and ELU"
-                             + (" (and a final Hardtanh)" if allow_clip else "") + " are built into the kernel")
-    if not linears:
-        raise ValueError(f"FusedPolicy: {name} has no Linear layer")
-    if len(linears) > abi.POLICY_MAX_LAYERS:
-        raise ValueError(f"FusedPolicy: {name} has {len(linears)} Linear layers, the kernel takes {abi.POLICY_MAX_LAYERS}")
-    if elu[-1] and not allow_trailing_elu:
-        raise ValueError(f"FusedPolicy: {name} ends in an ELU, expected a Linear output layer")
-    return ChainSpec(name, linears, elu, clip)
-
-
-def _describe_head(vae, device):
-    lin, clips = {}, {}
-    for name in ("latent_mu", "latent_var", "vel_mu", "vel_var"):
-        m = getattr(vae, name, None)
-        where = f"vae.{name}"
-        if name.endswith("_var"):
-            if not isinstance(m, nn.Sequential) or len(m) != 2 or not isinstance(m[0], nn.Linear) or not isinstance(m[1], nn.Hardtanh):
-                raise ValueError(f"FusedPolicy: {where} is not Sequential(Linear, Hardtanh): the log-variance head of the VAE")
-            if m[1].min_val != -m[1].max_val or not m[1].max_val >= 0:
-                raise ValueError(f"FusedPolicy: {where}[1] (Hardtanh({m[1].min_val}, {m[1].max_val})) must be a symmetric clip")
-            clips[name] = float(m[1].max_val)
-            m, where = m[0], where + "[0]"
-        if not isinstance(m, nn.Linear):
-            raise ValueError(f"FusedPolicy: {where} is {type(m).__name__}, expected a Linear")
-        if m.bias is None:
-            raise ValueError(f"FusedPolicy: {where} has no bias")
-        _check_tensor(m.weight.data, f"{where}.weight", device)
-        _check_tensor(m.bias.data, f"{where}.bias", device)
-        lin[name] = m
-    if clips["latent_var"] != clips["vel_var"]:
-        raise ValueError(f"FusedPolicy: vae.latent_var clips to {clips['latent_var']}, vae.vel_var to {clips['vel_var']}; the kernel takes one clip")
-    H = lin["latent_mu"].in_features
-    for name, m in lin.items():
-        if m.in_features != H or m.in_features > abi.POLICY_MAX_WIDTH:
-            raise ValueError(f"FusedPolicy: vae.{name} takes {m.in_features} inputs, vae.latent_mu {H} (limit {abi.POLICY_MAX_WIDTH})")
-    for a, b in (("latent_mu", "latent_var"), ("vel_mu", "vel_var")):
-        if lin[a].out_features != lin[b].out_features:
-            raise ValueError(f"FusedPolicy: vae.{a} has {lin[a].out_features} outputs, vae.{b} {lin[b].out_features}")
-    return HeadSpec(lin["latent_mu"], lin["latent_var"], lin["vel_mu"], lin["vel_var"], clips["latent_var"])
-
-
 def _describe_memory(name, mem, device):
     rnn = getattr(mem, "rnn", None)
     where = f"{name}.rnn"
@@ -228,7 +127,7 @@ def _describe_memory(name, mem, device):
     spec = MemorySpec(name, rnn)
     for k in range(spec.layers):
         for n, t in zip(("weight_ih", "weight_hh", "bias_ih", "bias_hh"), spec.params(k)):
-            _check_tensor(t, f"{where}.{n}_l{k}", device)
+            nets.check_tensor(t, f"{where}.{n}_l{k}", device, _OWNER)
     return spec
 
 
@@ -246,15 +145,13 @@ def _describe_recurrent(actor_critic, device):
     mem_a, mem_c = _describe_memory("memory_a", ma, device), _describe_memory("memory_c", mc, device)
     if mem_a.kind != mem_c.kind:
         raise ValueError(f"FusedPolicy: memory_a.rnn is an {mem_a.kind.upper()}, memory_c.rnn a {mem_c.kind.upper()}; one kind for both")
-    actor = _describe_chain("actor", actor_critic.actor, device, True)
-    critic = _describe_chain("critic", actor_critic.critic, device, False)
+    actor = nets.describe_chain("actor", actor_critic.actor, device, True, _OWNER)
+    critic = nets.describe_chain("critic", actor_critic.critic, device, False, _OWNER)
     for ch, mem in ((actor, mem_a), (critic, mem_c)):
         if ch.widths[0] != mem.hidden:
             raise ValueError(f"FusedPolicy: {ch.name}[0] takes {ch.widths[0]} inputs (in_features), {mem.name}.rnn gives hidden_size = {mem.hidden}")
     std = actor_critic.std
-    _check_tensor(std.data, "std", device)
-    if tuple(std.shape) != (actor.widths[-1],):
-        raise ValueError(f"FusedPolicy: std has shape {tuple(std.shape)}, the actor has {actor.widths[-1]} outputs")
+    nets.check_std(std, actor, device, _OWNER)
     return PolicySpec(None, actor, critic, std, memory_a=mem_a, memory_c=mem_c)
 
 
@@ -267,13 +164,11 @@ def describe(actor_critic, device=None):
         if not hasattr(actor_critic, need):
             raise ValueError(f"FusedPolicy: the module has no .{need}")
     est = getattr(actor_critic, "estimator", None)
-    estimator = _describe_chain("estimator", est, device, False) if est is not None else None
-    actor = _describe_chain("actor", actor_critic.actor, device, True)
-    critic = _describe_chain("critic", actor_critic.critic, device, False)
+    estimator = nets.describe_chain("estimator", est, device, False, _OWNER) if est is not None else None
+    actor = nets.describe_chain("actor", actor_critic.actor, device, True, _OWNER)
+    critic = nets.describe_chain("critic", actor_critic.critic, device, False, _OWNER)
     std = actor_critic.std
-    _check_tensor(std.data, "std", device)
-    if tuple(std.shape) != (actor.widths[-1],):
-        raise ValueError(f"FusedPolicy: std has shape {tuple(std.shape)}, the actor has {actor.widths[-1]} outputs")
+    nets.check_std(std, actor, device, _OWNER)
     ts = hasattr(actor_critic, "privilege_encoder") or hasattr(actor_critic, "history_encoder")
     vae = getattr(actor_critic, "vae", None)
     if (ts or vae is not None) and (estimator is not None or (ts and vae is not None)):
@@ -282,18 +177,16 @@ def describe(actor_critic, device=None):
         for need in ("privilege_encoder", "history_encoder"):
             if not hasattr(actor_critic, need):
                 raise ValueError(f"FusedPolicy: the module has no .{need}")
-        pe = _describe_chain("privilege_encoder", actor_critic.privilege_encoder, device, False)
-        he = _describe_chain("history_encoder", actor_critic.history_encoder, device, False)
+        pe = nets.describe_chain("privilege_encoder", actor_critic.privilege_encoder, device, False, _OWNER)
+        he = nets.describe_chain("history_encoder", actor_critic.history_encoder, device, False, _OWNER)
         if pe.widths[-1] != he.widths[-1]:
             raise ValueError(f"FusedPolicy: privilege_encoder gives {pe.widths[-1]} latent dims, history_encoder {he.widths[-1]}")
         if actor.widths[0] <= pe.widths[-1]:
             raise ValueError(f"FusedPolicy: actor[0] takes {actor.widths[0]} inputs, the latent alone has {pe.widths[-1]}")
         return PolicySpec(None, actor, critic, std, privilege_encoder=pe, history_encoder=he)
     if vae is not None:
-        enc = _describe_chain("vae.encoder", getattr(vae, "encoder", None), device, False, allow_trailing_elu=True)
-        head = _describe_head(vae, device)
-        if head.H != enc.widths[-1]:
-            raise ValueError(f"FusedPolicy: vae.latent_mu takes {head.H} inputs, vae.encoder gives {enc.widths[-1]}")
+        enc = nets.describe_chain("vae.encoder", getattr(vae, "encoder", None), device, False, _OWNER, allow_last_elu=True)
+        head = nets.describe_heads(vae, enc.widths[-1], device, _OWNER)
         if actor.widths[0] <= head.L + head.E:
             raise ValueError(f"FusedPolicy: actor[0] takes {actor.widths[0]} inputs, (z, vel) alone has {head.L} + {head.E}")
         return PolicySpec(None, actor, critic, std, vae_encoder=enc, head=head)
@@ -301,16 +194,6 @@ def describe(actor_critic, device=None):
         raise ValueError(f"FusedPolicy: actor[0] takes {actor.widths[0]} inputs, (features, estimator output) has "
                          f"{estimator.widths[0]} + {estimator.widths[-1]}")
     return PolicySpec(estimator, actor, critic, std)
-
-
-def _rows(x, width, what, n=None, device=None):
-    """(pointer, row stride) of an (N, width) float32 matrix with unit inner stride, as the kernel addresses it."""
-    if (not torch.is_tensor(x) or x.dtype != torch.float32 or x.dim() != 2 or x.shape[1] != width or (n is not None and x.shape[0] != n)
-            or (x.shape[1] > 1 and x.stride(1) != 1) or (x.shape[0] > 1 and x.stride(0) < width) or (device is not None and x.device != device)):
-        got = f"{tuple(x.shape)} {x.dtype} strides {x.stride()} on {x.device}" if torch.is_tensor(x) else type(x).__name__
-        raise ValueError(f"FusedPolicy: {what} must be ({'N' if n is None else n}, {width}) float32 with unit inner stride"
-                         + (f" on {device}" if device is not None else "") + f", got {got}")
-    return x.data_ptr(), (x.stride(0) if x.shape[0] > 1 else width)
 
 
 def _fill_chain(dst, spec, inp, in_width, out):
@@ -420,60 +303,60 @@ def policy_args(spec, obs, critic_obs=None, actions=None, mu=None, sigma=None, l
         F = spec.obs_width
         if spec.family in ("ts", "dreamwaq") and torch.is_tensor(obs) and obs.dim() == 2 and obs.shape[1] != F:
             raise ValueError(f"FusedPolicy: actor[0] takes {spec.actor.widths[0]} inputs, (obs, latent) has {obs.shape[1]} + {spec.latent_width}")
-        src = _rows(obs, F, "obs", None, device)
+        src = nets.rows(obs, F, "obs", None, device, _OWNER)
         if spec.concat:
             E = spec.estimator.widths[-1]
-            _fill_chain(a.estimator, spec.estimator, src, F, None if labels is None else _rows(labels, E, "labels", n, device))
+            _fill_chain(a.estimator, spec.estimator, src, F, None if labels is None else nets.rows(labels, E, "labels", n, device, _OWNER))
         elif labels is not None:
             raise ValueError("FusedPolicy: a labels row was given, the module has no estimator")
         if ts is not None:
             lead, rows, lead_b, rows_b = ts
-            _fill_chain(a.estimator, lead, _rows(rows, lead.widths[0], "privileged_obs" if lead is spec.privilege_encoder else "obs_history", n, device),
-                        lead.widths[0], None)
+            what = "privileged_obs" if lead is spec.privilege_encoder else "obs_history"
+            _fill_chain(a.estimator, lead, nets.rows(rows, lead.widths[0], what, n, device, _OWNER), lead.widths[0], None)
             if lead_b is not None:
-                _fill_chain(a.encoder_b, lead_b, _rows(rows_b, lead_b.widths[0], "obs_history", n, device), lead_b.widths[0], None)
+                _fill_chain(a.encoder_b, lead_b, nets.rows(rows_b, lead_b.widths[0], "obs_history", n, device, _OWNER), lead_b.widths[0], None)
                 a.n_split, a.has_split = int(num_teacher), 1
         if spec.family == "dreamwaq":
             enc, h = spec.vae_encoder, spec.head
-            _fill_chain(a.estimator, enc, _rows(obs_history, enc.widths[0], "obs_history", n, device), enc.widths[0], None)
+            _fill_chain(a.estimator, enc, nets.rows(obs_history, enc.widths[0], "obs_history", n, device, _OWNER), enc.widths[0], None)
             hd = a.head
-            for name, m in zip(("latent_mu", "latent_var", "vel_mu", "vel_var"), h.linears):
+            for name, m in zip(nets.HEADS, h.linears):
                 setattr(hd, name + "_w", m.weight.data.data_ptr())
                 setattr(hd, name + "_b", m.bias.data.data_ptr())
             hd.H, hd.L, hd.E, hd.logvar_clip = h.H, h.L, h.E, h.clip
             if latent is not None:
-                hd.latent_out, hd.latent_stride = _rows(latent, h.L + h.E, "latent", n, device)
+                hd.latent_out, hd.latent_stride = nets.rows(latent, h.L + h.E, "latent", n, device, _OWNER)
             if latent_params is not None:
-                hd.params_out, hd.params_stride = _rows(latent_params, 2 * (h.L + h.E), "latent_params", n, device)
+                hd.params_out, hd.params_stride = nets.rows(latent_params, 2 * (h.L + h.E), "latent_params", n, device, _OWNER)
             if not determ:
                 if latent_noise is not None:
-                    hd.noise, hd.noise_stride = _rows(latent_noise, h.L + h.E, "latent_noise", n, device)
+                    hd.noise, hd.noise_stride = nets.rows(latent_noise, h.L + h.E, "latent_noise", n, device, _OWNER)
                 elif dbg_latent_uniform is not None:
                     if not dbg_latent_uniform.is_contiguous():
                         raise ValueError("FusedPolicy: the debug uniforms must be a contiguous (N, 4 * ceil((L + E) / 4)) float32 tensor")
-                    hd.dbg_latent_uniform = _rows(dbg_latent_uniform, 4 * ((h.L + h.E + 3) // 4), "dbg_latent_uniform", n, device)[0]
+                    hd.dbg_latent_uniform = nets.rows(dbg_latent_uniform, 4 * ((h.L + h.E + 3) // 4), "dbg_latent_uniform", n, device, _OWNER)[0]
         _fill_chain(a.actor, spec.actor, src, F, None)
         if spec.family == "recurrent":
             _fill_memory(a.memory_a, spec.memory_a, "a", src, memory, n, device)
-        a.mu, a.mu_stride = _rows(mu, A, "mu", n, device)
+        a.mu, a.mu_stride = nets.rows(mu, A, "mu", n, device, _OWNER)
         if spec.clip_actions is not None:
             a.clip_on, a.clip_actions = 1, spec.clip_actions
         if not determ:
             a.std = spec.std.data.data_ptr()
-            a.actions, a.actions_stride = _rows(actions, A, "actions", n, device)
-            a.sigma, a.sigma_stride = _rows(sigma, A, "sigma", n, device)
-            a.log_prob, a.log_prob_stride = _rows(log_prob, 1, "log_prob", n, device)
+            a.actions, a.actions_stride = nets.rows(actions, A, "actions", n, device, _OWNER)
+            a.sigma, a.sigma_stride = nets.rows(sigma, A, "sigma", n, device, _OWNER)
+            a.log_prob, a.log_prob_stride = nets.rows(log_prob, 1, "log_prob", n, device, _OWNER)
             if noise is not None:
-                a.noise, a.noise_stride = _rows(noise, A, "noise", n, device)
+                a.noise, a.noise_stride = nets.rows(noise, A, "noise", n, device, _OWNER)
             if noise is None or (spec.family == "dreamwaq" and latent_noise is None):
                 a.counter, a.seed = counter.data_ptr(), int(seed) & (2 ** 64 - 1)
             if noise is None and dbg_uniform is not None:    # the kernel writes it densely: no stride is carried
                 if not dbg_uniform.is_contiguous():
                     raise ValueError("FusedPolicy: the debug uniforms must be a contiguous (N, 4 * ceil(A / 4)) float32 tensor")
-                a.dbg_uniform = _rows(dbg_uniform, 4 * ((A + 3) // 4), "dbg_uniform", n, device)[0]
+                a.dbg_uniform = nets.rows(dbg_uniform, 4 * ((A + 3) // 4), "dbg_uniform", n, device, _OWNER)[0]
     if critic_obs is not None and not determ:
-        csrc = _rows(critic_obs, spec.critic_obs_width, "critic_obs", n, device)
-        _fill_chain(a.critic, spec.critic, csrc, spec.critic_obs_width, _rows(values, 1, "values", n, device))
+        csrc = nets.rows(critic_obs, spec.critic_obs_width, "critic_obs", n, device, _OWNER)
+        _fill_chain(a.critic, spec.critic, csrc, spec.critic_obs_width, nets.rows(values, 1, "values", n, device, _OWNER))
         if spec.family == "recurrent":
             _fill_memory(a.memory_c, spec.memory_c, "c", csrc, memory, n, device)
     return a

@@ -22,7 +22,8 @@ encoder, heads and reparameterised draw, and the VAE pass with its three losses.
 
 The four families share what is below `_Pass`: one record per pass (workspace, call counter, entry points, descriptor builder), one
 autograd.Function for an RL pass and one for a loss pass, driven by that record.  A refusal carries the name of the surface that first
-raised it, which is why the helpers take an `owner`."""
+raised it, which is why the helpers take an `owner`.  What a chain, a head, a parameter tensor or a row matrix must be is nets.py's, shared
+with policy.py; this module keeps what must hold between a family's chains."""
 from __future__ import annotations
 
 import ctypes as C
@@ -30,23 +31,13 @@ import ctypes as C
 import torch
 import torch.nn as nn
 
-from . import abi
+from . import abi, nets
+from .nets import ChainSpec as TrainChainSpec      # the name callers and tests know it by here
 
 _OTHER_FAMILIES = (("estimator", "ActorCriticEE"), ("privilege_encoder", "ActorCriticTS / ActorCriticCTS"),
                    ("history_encoder", "ActorCriticTS / ActorCriticCTS"), ("vae", "ActorCriticDreamWaQ"),
                    ("memory_a", "ActorCriticRecurrent"), ("memory_c", "ActorCriticRecurrent"))
 _PLAIN, _EE, _TS, _DWAQ = "FusedTrainPass", "FusedTrainPassEE", "FusedTrainPassTS", "FusedTrainPassDreamWaQ"
-
-
-class TrainChainSpec:
-    """One chain as the kernel takes it: its Linear modules in order, which of them an ELU follows, and (actor only) the clip."""
-
-    def __init__(self, name, linears, elu, clip):
-        self.name, self.linears, self.elu, self.clip = name, linears, elu, clip
-
-    @property
-    def widths(self):
-        return [self.linears[0].in_features] + [l.out_features for l in self.linears]
 
 
 class TrainSpec:
@@ -63,61 +54,9 @@ class TrainSpec:
         return ["std"] + [f"{c.name}.{i}.{n}" for c in self.chains for i in range(len(c.linears)) for n in ("weight", "bias")]
 
 
-def _check_param(t, what, device, owner=_PLAIN):
-    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
-        raise ValueError(f"{owner}: {what} is {getattr(t, 'dtype', type(t).__name__)}, the kernel reads float32")
-    if not t.is_contiguous():
-        raise ValueError(f"{owner}: {what} is not contiguous")
-    if device is not None and t.device != device:
-        raise ValueError(f"{owner}: {what} is on {t.device}, not on {device}")
-
-
-def _describe_chain(name, seq, device, allow_clip, owner=_PLAIN, allow_last_elu=False):
-    if not isinstance(seq, nn.Sequential):
-        raise ValueError(f"{owner}: {name} is {type(seq).__name__}, expected an nn.Sequential of Linear / ELU"
-                         + (" / Hardtanh" if allow_clip else ""))
-    linears, elu, clip = [], [], None
-    mods = list(seq)
-    for i, m in enumerate(mods):
-        where = f"{name}[{i}]"
-        if clip is not None:
-            raise ValueError(f"{owner}: {where} ({type(m).__name__}) follows the Hardtanh, which must end the actor")
-        if isinstance(m, nn.Linear):
-            if m.bias is None:
-                raise ValueError(f"{owner}: {where} has no bias")
-            if m.in_features > abi.POLICY_MAX_WIDTH or m.out_features > abi.POLICY_MAX_WIDTH:
-                raise ValueError(f"{owner}: {where} is {m.in_features} -> {m.out_features}, widths are limited to {abi.POLICY_MAX_WIDTH}")
-            if linears and linears[-1].out_features != m.in_features:
-                raise ValueError(f"{owner}: {where} takes {m.in_features} inputs, the layer before it gives {linears[-1].out_features}")
-            _check_param(m.weight, f"{where}.weight", device, owner)
-            _check_param(m.bias, f"{where}.bias", device, owner)
-            linears.append(m)
-            elu.append(False)
-        elif isinstance(m, nn.ELU):
-            if not linears or elu[-1]:
-                raise ValueError(f"{owner}: {where} (ELU) does not follow a Linear")
-            if m.alpha != 1.0:
-                raise ValueError(f"{owner}: {where} is ELU(alpha={m.alpha}), only alpha = 1 is built")
-            elu[-1] = True
-        elif isinstance(m, nn.Hardtanh) and allow_clip:
-            if i != len(mods) - 1 or not linears or elu[-1] or m.min_val != -m.max_val or not m.max_val >= 0:
-                raise ValueError(f"{owner}: {where} (Hardtanh({m.min_val}, {m.max_val})) must be the symmetric clip behind the actor's last Linear")
-            clip = float(m.max_val)
-        else:
-            raise ValueError(f"{owner}: {where} is {type(m).__name__}; only Linear and ELU"
-                             + (" (and a final Hardtanh)" if allow_clip else "") + " are built into the kernel")
-    if not linears:
-        raise ValueError(f"{owner}: {name} has no Linear layer")
-    if len(linears) > abi.POLICY_MAX_LAYERS:
-        raise ValueError(f"{owner}: {name} has {len(linears)} Linear layers, the kernel takes {abi.POLICY_MAX_LAYERS}")
-    if elu[-1] and not allow_last_elu:
-        raise ValueError(f"{owner}: {name} ends in an ELU, expected a Linear output layer")
-    return TrainChainSpec(name, linears, elu, clip)
-
-
-def _describe(actor_critic, device, owner, foreign, beside, chains, chain_owner, between=None):
+def _describe(actor_critic, device, owner, foreign, beside, chains, between=None):
     """What describe, describe_ee and describe_ts share: no member of another family (`foreign`; `beside` ends that refusal), not
-    recurrent, .actor / .critic / .std there, the chains of `chains` ((name, may end in a Hardtanh) pairs) by _describe_chain, the
+    recurrent, .actor / .critic / .std there, the chains of `chains` ((name, may end in a Hardtanh) pairs) by nets.describe_chain, the
     family's own checks across them (`between`) and the shape of std.  Returns the chain specs by name, and std."""
     for attr, family in foreign:
         if getattr(actor_critic, attr, None) is not None:
@@ -127,13 +66,11 @@ def _describe(actor_critic, device, owner, foreign, beside, chains, chain_owner,
     for need in ("actor", "critic", "std"):
         if getattr(actor_critic, need, None) is None:
             raise ValueError(f"{owner}: the module has no .{need}")
-    c = {name: _describe_chain(name, getattr(actor_critic, name), device, clip, chain_owner) for name, clip in chains}
+    c = {name: nets.describe_chain(name, getattr(actor_critic, name), device, clip, owner) for name, clip in chains}
     if between is not None:
         between(c)
     std = actor_critic.std
-    _check_param(std, "std", device)
-    if tuple(std.shape) != (c["actor"].widths[-1],):
-        raise ValueError(f"{owner}: std has shape {tuple(std.shape)}, the actor has {c['actor'].widths[-1]} outputs")
+    nets.check_std(std, c["actor"], device, owner)
     return c, std
 
 
@@ -141,19 +78,8 @@ def describe(actor_critic, device=None):
     """The plain ActorCritic as the kernel takes it (duck-typed: .actor, .critic, .std).  Refusals are ValueErrors that name the layer or
     the member; with `device` every parameter must live there."""
     c, std = _describe(actor_critic, device, _PLAIN, _OTHER_FAMILIES, "; only the plain ActorCritic is built, the other learners keep the torch path",
-                       (("actor", True), ("critic", False)), _PLAIN)
+                       (("actor", True), ("critic", False)))
     return TrainSpec(c["actor"], c["critic"], std)
-
-
-def _rows(t, width, what, n=None, device=None, owner=_PLAIN):
-    """(n, width) float32 with unit inner stride: (pointer, row stride)."""
-    ok = isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.dim() == 2 and t.shape[1] == width and (n is None or t.shape[0] == n) \
-        and (t.shape[1] == 1 or t.stride(1) == 1) and (t.shape[0] == 1 or t.stride(0) >= width) and (device is None or t.device == device)
-    if not ok:
-        got = f"{tuple(t.shape)} {t.dtype} on {t.device}, strides {tuple(t.stride())}" if isinstance(t, torch.Tensor) else type(t).__name__
-        raise ValueError(f"{owner}: {what} must be ({'B' if n is None else n}, {width}) float32 with unit inner stride"
-                         + (f" on {device}" if device is not None else "") + f"; got {got}")
-    return t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else width)
 
 
 def _fill_chain(ch, c, device, grads=None):
@@ -161,8 +87,8 @@ def _fill_chain(ch, c, device, grads=None):
     ch.n_layers = len(c.linears)
     for li, (lin, elu) in enumerate(zip(c.linears, c.elu)):
         L = ch.layer[li]
-        _check_param(lin.weight, f"{c.name} layer {li} weight", device)
-        _check_param(lin.bias, f"{c.name} layer {li} bias", device)
+        nets.check_tensor(lin.weight, f"{c.name} layer {li} weight", device, _PLAIN)        # in the plain pass's name for every family: no owner
+        nets.check_tensor(lin.bias, f"{c.name} layer {li} bias", device, _PLAIN)            # reaches here, and test_train_host.py pins this text
         L.weight, L.bias, L.n_in, L.n_out, L.elu = lin.weight.data_ptr(), lin.bias.data_ptr(), lin.in_features, lin.out_features, int(elu)
         if grads is not None:
             L.grad_weight, L.grad_bias = grads[2 * li].data_ptr(), grads[2 * li + 1].data_ptr()
@@ -172,16 +98,16 @@ def _fill_heads(a, spec, mu, sigma, values, n, device, owner, grad_std=None, gra
     """The clip, std, the three outputs and (backward: grad_std is given) the gradient members of an RL descriptor of `owner`."""
     A, V = spec.num_actions, spec.critic.widths[-1]
     a.clip_on, a.clip_actions = (1, spec.clip_actions) if spec.clip_actions is not None else (0, 0.0)
-    _check_param(spec.std, "std", device)
+    nets.check_tensor(spec.std, "std", device, owner)
     a.std = spec.std.data_ptr()
-    a.mu, a.mu_stride = _rows(mu, A, "mu", n, device, owner)
-    a.sigma, a.sigma_stride = _rows(sigma, A, "sigma", n, device, owner)
-    a.values, a.values_stride = _rows(values, V, "values", n, device, owner)
+    a.mu, a.mu_stride = nets.rows(mu, A, "mu", n, device, owner)
+    a.sigma, a.sigma_stride = nets.rows(sigma, A, "sigma", n, device, owner)
+    a.values, a.values_stride = nets.rows(values, V, "values", n, device, owner)
     if grad_std is not None:
         a.grad_std = grad_std.data_ptr()
-        a.grad_mu, a.grad_mu_stride = _rows(grad_mu, A, "grad_mu", n, device, owner)
-        a.grad_sigma, a.grad_sigma_stride = _rows(grad_sigma, A, "grad_sigma", n, device, owner)
-        a.grad_values, a.grad_values_stride = _rows(grad_values, V, "grad_values", n, device, owner)
+        a.grad_mu, a.grad_mu_stride = nets.rows(grad_mu, A, "grad_mu", n, device, owner)
+        a.grad_sigma, a.grad_sigma_stride = nets.rows(grad_sigma, A, "grad_sigma", n, device, owner)
+        a.grad_values, a.grad_values_stride = nets.rows(grad_values, V, "grad_values", n, device, owner)
 
 
 def _bind_workspace(a, workspace, device, owner=_EE):
@@ -209,7 +135,7 @@ def train_args(spec, obs, critic_obs, mu, sigma, values, workspace, grads=None, 
     a.n_rows = n
     g0 = 1
     for ch, c, x, what in zip(a.chain, spec.chains, (obs, critic_obs), ("obs", "critic_obs")):
-        ch.input, ch.in_stride = _rows(x, c.widths[0], what, n, device)
+        ch.input, ch.in_stride = nets.rows(x, c.widths[0], what, n, device, _PLAIN)
         _fill_chain(ch, c, device, None if grads is None else grads[g0:g0 + 2 * len(c.linears)])
         g0 += 2 * len(c.linears)
     _fill_heads(a, spec, mu, sigma, values, n, device, _PLAIN, *(() if grads is None else (grads[0], grad_mu, grad_sigma, grad_values)))
@@ -412,7 +338,7 @@ def describe_ee(actor_critic, device=None):
             raise ValueError(f"FusedTrainPassEE: actor[0] takes {c['actor'].widths[0]} inputs, but [features | estimator output] has "
                              f"{c['estimator'].widths[0]} + {c['estimator'].widths[-1]} columns")
     c, std = _describe(actor_critic, device, _EE, [f for f in _OTHER_FAMILIES if f[0] != "estimator"], " beside .estimator; only ActorCriticEE is built",
-                       (("estimator", False), ("actor", True), ("critic", False)), _PLAIN, between)
+                       (("estimator", False), ("actor", True), ("critic", False)), between)
     return TrainSpecEE(c["estimator"], c["actor"], c["critic"], std)
 
 
@@ -435,13 +361,13 @@ def ee_args(spec, features, critic_obs, mu, sigma, values, workspace, grads=None
     n = int(features.shape[0])
     a.n_rows = n
     est, act, cri = a.chain[abi.TRAIN_EE_ESTIMATOR], a.chain[abi.TRAIN_EE_ACTOR], a.chain[abi.TRAIN_EE_CRITIC]
-    est.input, est.in_stride = _rows(features, spec.num_features, "estimator_features", n, device)
-    cri.input, cri.in_stride = _rows(critic_obs, spec.critic.widths[0], "critic_obs", n, device)
+    est.input, est.in_stride = nets.rows(features, spec.num_features, "estimator_features", n, device, _EE)
+    cri.input, cri.in_stride = nets.rows(critic_obs, spec.critic.widths[0], "critic_obs", n, device, _EE)
     g_act, g_cri, g_std = _rl_grads(grads, spec.actor, spec.critic)
     _fill_chain(est, spec.estimator, device)
     _fill_chain(act, spec.actor, device, g_act)
     _fill_chain(cri, spec.critic, device, g_cri)
-    _fill_heads(a, spec, mu, sigma, values, n, device, _PLAIN, g_std, grad_mu, grad_sigma, grad_values)
+    _fill_heads(a, spec, mu, sigma, values, n, device, _EE, g_std, grad_mu, grad_sigma, grad_values)
     _bind_workspace(a, workspace, device)
     return a
 
@@ -453,10 +379,10 @@ def est_args(spec, features, labels, terminated, loss, workspace, grads=None, up
         raise ValueError(f"FusedTrainPassEE: estimator_features must be a (B, {spec.num_features}) float32 tensor with B >= 1")
     n = int(features.shape[0])
     a.n_rows = n
-    a.chain.input, a.chain.in_stride = _rows(features, spec.num_features, "estimator_features", n, device)
+    a.chain.input, a.chain.in_stride = nets.rows(features, spec.num_features, "estimator_features", n, device, _EE)
     _fill_chain(a.chain, spec.estimator, device, grads)
-    a.labels, a.labels_stride = _rows(labels, spec.num_labels, "estimator_labels", n, device)
-    a.mask, a.mask_stride = _rows(terminated, 1, "terminated", n, device)
+    a.labels, a.labels_stride = nets.rows(labels, spec.num_labels, "estimator_labels", n, device, _EE)
+    a.mask, a.mask_stride = nets.rows(terminated, 1, "terminated", n, device, _EE)
     if loss is not None:
         a.loss = _scalar(loss, "the loss", device)
     if upstream is not None:
@@ -562,7 +488,7 @@ def describe_ts(actor_critic, device=None):
             raise ValueError(f"FusedTrainPassTS: actor[0] takes {actor.widths[0]} inputs, but [obs | latent] has O + {priv.widths[-1]} columns with "
                              f"O >= 1")
     c, std = _describe(actor_critic, device, _TS, _TS_FOREIGN, " beside its encoders; only ActorCriticTS is built",
-                       (("privilege_encoder", False), ("history_encoder", False), ("actor", True), ("critic", False)), _TS, between)
+                       (("privilege_encoder", False), ("history_encoder", False), ("actor", True), ("critic", False)), between)
     return TrainSpecTS(c["privilege_encoder"], c["actor"], c["critic"], c["history_encoder"], std)
 
 
@@ -579,9 +505,9 @@ def ts_args(spec, obs, privileged_obs, critic_obs, mu, sigma, values, workspace,
                          f"{spec.num_latent} columns")
     a.n_rows, a.n_obs = n, spec.num_obs
     pri, act, cri = a.chain[abi.TRAIN_TS_PRIVILEGE], a.chain[abi.TRAIN_TS_ACTOR], a.chain[abi.TRAIN_TS_CRITIC]
-    act.input, act.in_stride = _rows(obs, spec.num_obs, "obs", n, device, _TS)
-    pri.input, pri.in_stride = _rows(privileged_obs, spec.privilege_encoder.widths[0], "privileged_obs", n, device, _TS)
-    cri.input, cri.in_stride = _rows(critic_obs, spec.critic.widths[0], "critic_obs", n, device, _TS)
+    act.input, act.in_stride = nets.rows(obs, spec.num_obs, "obs", n, device, _TS)
+    pri.input, pri.in_stride = nets.rows(privileged_obs, spec.privilege_encoder.widths[0], "privileged_obs", n, device, _TS)
+    cri.input, cri.in_stride = nets.rows(critic_obs, spec.critic.widths[0], "critic_obs", n, device, _TS)
     g_act, g_cri, g_pri, g_std = _rl_grads(grads, spec.actor, spec.critic, spec.privilege_encoder)
     _fill_chain(act, spec.actor, device, g_act)
     _fill_chain(cri, spec.critic, device, g_cri)
@@ -600,11 +526,11 @@ def enc_args(spec, obs_history, privileged_obs, terminated, loss, workspace, gra
     n = int(obs_history.shape[0])
     a.n_rows = n
     his, pri = a.chain[abi.TRAIN_ENC_HISTORY], a.chain[abi.TRAIN_ENC_PRIVILEGE]
-    his.input, his.in_stride = _rows(obs_history, spec.history_encoder.widths[0], "obs_history", n, device, _TS)
-    pri.input, pri.in_stride = _rows(privileged_obs, spec.privilege_encoder.widths[0], "privileged_obs", n, device, _TS)
+    his.input, his.in_stride = nets.rows(obs_history, spec.history_encoder.widths[0], "obs_history", n, device, _TS)
+    pri.input, pri.in_stride = nets.rows(privileged_obs, spec.privilege_encoder.widths[0], "privileged_obs", n, device, _TS)
     _fill_chain(his, spec.history_encoder, device, grads)
     _fill_chain(pri, spec.privilege_encoder, device)
-    a.mask, a.mask_stride = _rows(terminated, 1, "terminated", n, device, _TS)
+    a.mask, a.mask_stride = nets.rows(terminated, 1, "terminated", n, device, _TS)
     if loss is not None:
         a.loss = _scalar(loss, "the loss", device)
     if upstream is not None:
@@ -674,7 +600,6 @@ class FusedTrainPassTS:
 # ---- the DreamWaQ family (include/lgtraindwaq.h, csrc/lg_train_dwaq.hip) ------------------------------------------------------------------------
 _DWAQ_FOREIGN = (("estimator", "ActorCriticEE"), ("privilege_encoder", "ActorCriticTS / ActorCriticCTS"),
                  ("history_encoder", "ActorCriticTS / ActorCriticCTS"), ("memory_a", "ActorCriticRecurrent"), ("memory_c", "ActorCriticRecurrent"))
-_HEADS = ("latent_mu", "latent_var", "vel_mu", "vel_var")          # abi.TRAIN_DWAQ_LATENT_MU + h, and the order of vae.parameters()
 
 
 class TrainSpecDreamWaQ:
@@ -703,26 +628,6 @@ class TrainSpecDreamWaQ:
         return [f"vae.{c.name}.{i}.{n}" for c in self.vae_chains for i in range(len(c.linears)) for n in ("weight", "bias")]
 
 
-def _describe_dwaq_head(vae, name, device):
-    """One head by the rules of policy.py's _describe_head: a Linear, behind a symmetric Hardtanh for a log-variance.  (chain, clip)."""
-    m, where, clip = getattr(vae, name, None), f"vae.{name}", None
-    if name.endswith("_var"):
-        if not isinstance(m, nn.Sequential) or len(m) != 2 or not isinstance(m[0], nn.Linear) or not isinstance(m[1], nn.Hardtanh):
-            raise ValueError(f"{_DWAQ}: {where} is not Sequential(Linear, Hardtanh): the log-variance head of the VAE")
-        if m[1].min_val != -m[1].max_val or not m[1].max_val >= 0:
-            raise ValueError(f"{_DWAQ}: {where}[1] (Hardtanh({m[1].min_val}, {m[1].max_val})) must be a symmetric clip")
-        clip, m, where = float(m[1].max_val), m[0], where + "[0]"
-    if not isinstance(m, nn.Linear):
-        raise ValueError(f"{_DWAQ}: {where} is {type(m).__name__}, expected a Linear")
-    if m.bias is None:
-        raise ValueError(f"{_DWAQ}: {where} has no bias")
-    if m.in_features > abi.POLICY_MAX_WIDTH or m.out_features > abi.POLICY_MAX_WIDTH:
-        raise ValueError(f"{_DWAQ}: {where} is {m.in_features} -> {m.out_features}, widths are limited to {abi.POLICY_MAX_WIDTH}")
-    _check_param(m.weight, f"{where}.weight", device, _DWAQ)
-    _check_param(m.bias, f"{where}.bias", device, _DWAQ)
-    return TrainChainSpec(name, [m], [False], None), clip
-
-
 def describe_dwaq(actor_critic, device=None):
     """ActorCriticDreamWaQ as the kernels take it (duck-typed: .vae with .encoder, the four heads and .decoder; .actor, .critic, .std).  The
     encoder may end in an ELU, as the reference's does, on this path only; the actor may end in a Hardtanh or not.  Refusals are ValueErrors
@@ -730,28 +635,19 @@ def describe_dwaq(actor_critic, device=None):
     vae = getattr(actor_critic, "vae", None)
     if vae is None:
         raise ValueError(f"{_DWAQ}: the module has no .vae; the plain ActorCritic is FusedTrainPass's")
-    c, std = _describe(actor_critic, device, _DWAQ, _DWAQ_FOREIGN, " beside .vae; only ActorCriticDreamWaQ is built", (("actor", True), ("critic", False)), _DWAQ)
+    c, std = _describe(actor_critic, device, _DWAQ, _DWAQ_FOREIGN, " beside .vae; only ActorCriticDreamWaQ is built", (("actor", True), ("critic", False)))
     for need in ("encoder", "decoder"):
         if getattr(vae, need, None) is None:
             raise ValueError(f"{_DWAQ}: the module's .vae has no .{need}")
-    encoder = _describe_chain("encoder", vae.encoder, device, False, _DWAQ, allow_last_elu=True)
-    decoder = _describe_chain("decoder", vae.decoder, device, False, _DWAQ)
-    heads, clips = zip(*(_describe_dwaq_head(vae, name, device) for name in _HEADS))
-    if clips[1] != clips[3]:
-        raise ValueError(f"{_DWAQ}: vae.latent_var clips to {clips[1]}, vae.vel_var to {clips[3]}; the kernel takes one clip")
-    H = encoder.widths[-1]
-    for h in heads:
-        if h.widths[0] != H:
-            raise ValueError(f"{_DWAQ}: vae.{h.name} takes {h.widths[0]} inputs, the encoder ends at {H} columns")
-    for a, b in ((heads[0], heads[1]), (heads[2], heads[3])):
-        if a.widths[-1] != b.widths[-1]:
-            raise ValueError(f"{_DWAQ}: vae.{a.name} has {a.widths[-1]} outputs, vae.{b.name} {b.widths[-1]}")
-    L, E = heads[0].widths[-1], heads[2].widths[-1]
+    encoder = nets.describe_chain("encoder", vae.encoder, device, False, _DWAQ, allow_last_elu=True)
+    decoder = nets.describe_chain("decoder", vae.decoder, device, False, _DWAQ)
+    head = nets.describe_heads(vae, encoder.widths[-1], device, _DWAQ)
+    L, E = head.L, head.E
     if decoder.widths[0] != L + E:
         raise ValueError(f"{_DWAQ}: decoder[0] takes {decoder.widths[0]} inputs, but [z | v] has {L} + {E} columns")
     if c["actor"].widths[0] <= L + E:
         raise ValueError(f"{_DWAQ}: actor[0] takes {c['actor'].widths[0]} inputs, but [obs | z | v] has O + {L} + {E} columns with O >= 1")
-    spec = TrainSpecDreamWaQ(encoder, heads, decoder, c["actor"], c["critic"], std, clips[1])
+    spec = TrainSpecDreamWaQ(encoder, head.chains, decoder, c["actor"], c["critic"], std, head.clip)
     if isinstance(vae, nn.Module):
         theirs = list(vae.parameters())
         if len(theirs) != len(spec.vae_parameters()) or any(a is not b for a, b in zip(theirs, spec.vae_parameters())):
@@ -762,13 +658,13 @@ def describe_dwaq(actor_critic, device=None):
 def _dwaq_front(a, spec, obs_history, noise, n, device, grads=None):
     """The encoder, the four heads and the noise of either descriptor; `grads`: the gradient tensors of those five chains, or None."""
     enc = a.chain[abi.TRAIN_DWAQ_ENCODER]
-    enc.input, enc.in_stride = _rows(obs_history, spec.encoder.widths[0], "obs_history", n, device, _DWAQ)
+    enc.input, enc.in_stride = nets.rows(obs_history, spec.encoder.widths[0], "obs_history", n, device, _DWAQ)
     at = 0
     for ci, c in enumerate((spec.encoder,) + tuple(spec.heads)):
         _fill_chain(a.chain[ci], c, device, None if grads is None else grads[at:at + 2 * len(c.linears)])
         at += 2 * len(c.linears)
     a.var_clip = spec.var_clip
-    a.noise, a.noise_stride = _rows(noise, spec.num_latent + spec.num_explicit, "latent_noise", n, device, _DWAQ)
+    a.noise, a.noise_stride = nets.rows(noise, spec.num_latent + spec.num_explicit, "latent_noise", n, device, _DWAQ)
     return at
 
 
@@ -782,8 +678,8 @@ def dwaq_args(spec, obs, obs_history, critic_obs, noise, mu, sigma, values, work
     n = int(obs.shape[0])
     a.n_rows, a.n_obs = n, spec.num_obs
     act, cri = a.chain[abi.TRAIN_DWAQ_ACTOR], a.chain[abi.TRAIN_DWAQ_CRITIC]
-    act.input, act.in_stride = _rows(obs, spec.num_obs, "obs", n, device, _DWAQ)
-    cri.input, cri.in_stride = _rows(critic_obs, spec.critic.widths[0], "critic_obs", n, device, _DWAQ)
+    act.input, act.in_stride = nets.rows(obs, spec.num_obs, "obs", n, device, _DWAQ)
+    cri.input, cri.in_stride = nets.rows(critic_obs, spec.critic.widths[0], "critic_obs", n, device, _DWAQ)
     _dwaq_front(a, spec, obs_history, noise, n, device)
     g_act, g_cri, g_std = _rl_grads(grads, spec.actor, spec.critic)
     _fill_chain(act, spec.actor, device, g_act)
@@ -803,9 +699,9 @@ def vae_args(spec, obs_history, labels, next_states, terminated, noise, kld_weig
     a.n_rows, a.kld_weight = n, float(kld_weight)
     at = _dwaq_front(a, spec, obs_history, noise, n, device, grads)
     _fill_chain(a.chain[abi.TRAIN_VAE_DECODER], spec.decoder, device, None if grads is None else grads[at:])
-    a.labels, a.labels_stride = _rows(labels, spec.num_explicit, "explicit_info_labels", n, device, _DWAQ)
-    a.next_states, a.next_states_stride = _rows(next_states, spec.decoder.widths[-1], "next_states", n, device, _DWAQ)
-    a.mask, a.mask_stride = _rows(terminated, 1, "terminated", n, device, _DWAQ)
+    a.labels, a.labels_stride = nets.rows(labels, spec.num_explicit, "explicit_info_labels", n, device, _DWAQ)
+    a.next_states, a.next_states_stride = nets.rows(next_states, spec.decoder.widths[-1], "next_states", n, device, _DWAQ)
+    a.mask, a.mask_stride = nets.rows(terminated, 1, "terminated", n, device, _DWAQ)
     if loss is not None:
         a.loss = _scalar(loss, "the losses", device, abi.TRAIN_VAE_LOSSES, _DWAQ)
     if upstream is not None:
