@@ -327,6 +327,12 @@ def load_lib():
         lib.lg_train_vae_backward.argtypes = [C.POINTER(LgTrainVaeArgs), vp]
         for f in TRAIN_TS_EXPORTS:
             getattr(lib, f).restype = C.c_int
+    if hasattr(lib, "lg_train_cts_forward"):     # absent from libraries older than the concurrent teacher-student learner pass
+        lib.lg_train_cts_plan.argtypes = [C.POINTER(LgTrainCTSArgs), C.POINTER(LgTrainCTSPlan)]
+        lib.lg_train_cts_forward.argtypes = [C.POINTER(LgTrainCTSArgs), vp]
+        lib.lg_train_cts_backward.argtypes = [C.POINTER(LgTrainCTSArgs), vp]
+        for f in TRAIN_CTS_EXPORTS:
+            getattr(lib, f).restype = C.c_int
     lib.lg_last_error.restype = C.c_char_p
     lib.lg_last_kernel.argtypes = [H]
     lib.lg_last_kernel.restype = C.c_char_p
@@ -373,6 +379,9 @@ TRAIN_DWAQ_EXPORTS = ["lg_train_dwaq_plan", "lg_train_vae_plan", "lg_train_dwaq_
 TRAIN_DWAQ_CHAINS, TRAIN_DWAQ_ENCODER, TRAIN_DWAQ_LATENT_MU, TRAIN_DWAQ_LATENT_VAR, TRAIN_DWAQ_VEL_MU, TRAIN_DWAQ_VEL_VAR = 7, 0, 1, 2, 3, 4
 TRAIN_DWAQ_ACTOR, TRAIN_DWAQ_CRITIC, TRAIN_DWAQ_HEADS, TRAIN_VAE_CHAINS, TRAIN_VAE_DECODER, TRAIN_VAE_LOSSES = 5, 6, 4, 6, 5, 4
 TRAIN_DWAQ_TARGET_JOBS, TRAIN_DWAQ_THREADS = 2048, 256
+TRAIN_CTS_EXPORTS = ["lg_train_cts_plan", "lg_train_cts_forward", "lg_train_cts_backward"]   # include/lgtraincts.h
+TRAIN_CTS_CHAINS, TRAIN_CTS_PRIVILEGE, TRAIN_CTS_ACTOR, TRAIN_CTS_CRITIC, TRAIN_CTS_HISTORY = 4, 0, 1, 2, 3
+TRAIN_CTS_GROUPS, TRAIN_CTS_TEACHER, TRAIN_CTS_STUDENT, TRAIN_CTS_ROLES, TRAIN_CTS_ROLE_CRITIC = 2, 0, 1, 3, 2
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 2048
 POLICY_MAX_RNN_LAYERS, POLICY_MAX_RNN_HIDDEN = 2, 512
 POLICY_LSTM, POLICY_GRU = 1, 2
@@ -576,6 +585,25 @@ class LgTrainDwaqPlan(C.Structure):
                 ("p_off", i64 * POLICY_MAX_LAYERS * TRAIN_DWAQ_CHAINS), ("std_p_off", i64), ("cat_off", i64), ("enc_out_off", i64),
                 ("head_off", i64 * TRAIN_DWAQ_HEADS), ("gl_rec_off", i64), ("gl_est_off", i64), ("partial_off", i64), ("scale_off", i64),
                 ("workspace_floats", i64)]
+
+
+class LgTrainCTSArgs(C.Structure):
+    _fields_ = [("n_teacher", i32), ("n_student", i32), ("n_critic", i32), ("clip_on", i32), ("clip_actions", f32), ("n_obs", i32),
+                ("student_obs_stride", i32), ("reserved", i32), ("chain", LgTrainChain * TRAIN_CTS_CHAINS), ("student_obs", C.c_void_p),
+                ("std", C.c_void_p), ("grad_std", C.c_void_p), ("mu", C.c_void_p * TRAIN_CTS_GROUPS), ("sigma", C.c_void_p * TRAIN_CTS_GROUPS),
+                ("values", C.c_void_p), ("grad_mu", C.c_void_p * TRAIN_CTS_GROUPS), ("grad_sigma", C.c_void_p * TRAIN_CTS_GROUPS),
+                ("grad_values", C.c_void_p), ("mu_stride", i32 * TRAIN_CTS_GROUPS), ("sigma_stride", i32 * TRAIN_CTS_GROUPS),
+                ("grad_mu_stride", i32 * TRAIN_CTS_GROUPS), ("grad_sigma_stride", i32 * TRAIN_CTS_GROUPS), ("values_stride", i32),
+                ("grad_values_stride", i32), ("workspace", C.c_void_p), ("workspace_capacity", i64)]
+
+
+class LgTrainCTSPlan(C.Structure):
+    _fields_ = [("row_tile", i32), ("lds_bytes", i32), ("slices", i32 * POLICY_MAX_LAYERS * TRAIN_CTS_CHAINS),
+                ("slice_rows", i32 * POLICY_MAX_LAYERS * TRAIN_CTS_CHAINS), ("std_slices", i32 * TRAIN_CTS_GROUPS),
+                ("std_slice_rows", i32 * TRAIN_CTS_GROUPS), ("tiles", i32 * TRAIN_CTS_ROLES), ("weight_jobs", i32),
+                ("enc_first_buffer", i32 * TRAIN_CTS_GROUPS), ("h_off", i64 * POLICY_MAX_LAYERS * TRAIN_CTS_CHAINS),
+                ("g_off", i64 * POLICY_MAX_LAYERS * TRAIN_CTS_CHAINS), ("p_off", i64 * POLICY_MAX_LAYERS * TRAIN_CTS_CHAINS), ("std_p_off", i64),
+                ("cat_off", i64), ("workspace_floats", i64)]
 
 
 def check(rc, lib=None):

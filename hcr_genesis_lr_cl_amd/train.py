@@ -18,9 +18,11 @@ FusedTrainPassEE (below; include/lgtrainee.h, csrc/lg_train_ee.hip) is the same 
 supervised estimator pass.  FusedTrainPassTS (include/lgtraints.h, csrc/lg_train_ts.hip) is the same for ActorCriticTS under PPO_TS: the RL
 pass, whose gradient reaches the privilege encoder through the latent, and the supervised history-encoder pass.  FusedTrainPassDreamWaQ
 (include/lgtraindwaq.h, csrc/lg_train_dwaq.hip) is the same for ActorCriticDreamWaQ under PPO_DreamWaQ: the RL pass behind the VAE's
-encoder, heads and reparameterised draw, and the VAE pass with its three losses.
+encoder, heads and reparameterised draw, and the VAE pass with its three losses.  FusedTrainPassCTS (include/lgtraincts.h,
+csrc/lg_train_cts.hip) is the same for ActorCriticCTS under PPO_CTS: the RL pass over the teacher's, the student's and the critic's rows, and
+the history-encoder pass on the teacher-student family's encoder kernels with a mask of ones.
 
-The four families share what is below `_Pass`: one record per pass (workspace, call counter, entry points, descriptor builder), one
+The five families share what is below `_Pass`: one record per pass (workspace, call counter, entry points, descriptor builder), one
 autograd.Function for an RL pass and one for a loss pass, driven by that record.  A refusal carries the name of the surface that first
 raised it, which is why the helpers take an `owner`.  What a chain, a head, a parameter tensor or a row matrix must be is nets.py's, shared
 with policy.py; this module keeps what must hold between a family's chains."""
@@ -37,7 +39,7 @@ from .nets import ChainSpec as TrainChainSpec      # the name callers and tests 
 _OTHER_FAMILIES = (("estimator", "ActorCriticEE"), ("privilege_encoder", "ActorCriticTS / ActorCriticCTS"),
                    ("history_encoder", "ActorCriticTS / ActorCriticCTS"), ("vae", "ActorCriticDreamWaQ"),
                    ("memory_a", "ActorCriticRecurrent"), ("memory_c", "ActorCriticRecurrent"))
-_PLAIN, _EE, _TS, _DWAQ = "FusedTrainPass", "FusedTrainPassEE", "FusedTrainPassTS", "FusedTrainPassDreamWaQ"
+_PLAIN, _EE, _TS, _DWAQ, _CTS = "FusedTrainPass", "FusedTrainPassEE", "FusedTrainPassTS", "FusedTrainPassDreamWaQ", "FusedTrainPassCTS"
 
 
 class TrainSpec:
@@ -471,25 +473,30 @@ class TrainSpecTS:
         return [f"history_encoder.{i}.{n}" for i in range(len(self.history_encoder.linears)) for n in ("weight", "bias")]
 
 
-def describe_ts(actor_critic, device=None):
-    """ActorCriticTS as the kernels take it (duck-typed: .privilege_encoder, .history_encoder, .actor, .critic, .std), by the rules of
-    `describe` for each of the four chains: a Conv1d / Flatten "TCN" history encoder is refused by its layer's name.  Refusals are
-    ValueErrors that name the layer or the member."""
+def _describe_ts(actor_critic, device, owner, family):
+    """describe_ts's rules under `owner`'s name; `family`: the module class the refusals speak of."""
     for need in ("privilege_encoder", "history_encoder"):
         if getattr(actor_critic, need, None) is None:
-            raise ValueError(f"FusedTrainPassTS: the module has no .{need}; ActorCriticTS has a privilege encoder and a history encoder")
+            raise ValueError(f"{owner}: the module has no .{need}; {family} has a privilege encoder and a history encoder")
 
     def between(c):
         hist, priv, actor = c["history_encoder"], c["privilege_encoder"], c["actor"]
         if hist.widths[-1] != priv.widths[-1]:
-            raise ValueError(f"FusedTrainPassTS: history_encoder ends at {hist.widths[-1]} columns, privilege_encoder at {priv.widths[-1]}: the "
+            raise ValueError(f"{owner}: history_encoder ends at {hist.widths[-1]} columns, privilege_encoder at {priv.widths[-1]}: the "
                              f"latent widths differ")
         if actor.widths[0] <= priv.widths[-1]:
-            raise ValueError(f"FusedTrainPassTS: actor[0] takes {actor.widths[0]} inputs, but [obs | latent] has O + {priv.widths[-1]} columns with "
+            raise ValueError(f"{owner}: actor[0] takes {actor.widths[0]} inputs, but [obs | latent] has O + {priv.widths[-1]} columns with "
                              f"O >= 1")
-    c, std = _describe(actor_critic, device, _TS, _TS_FOREIGN, " beside its encoders; only ActorCriticTS is built",
+    c, std = _describe(actor_critic, device, owner, _TS_FOREIGN, f" beside its encoders; only {family} is built",
                        (("privilege_encoder", False), ("history_encoder", False), ("actor", True), ("critic", False)), between)
     return TrainSpecTS(c["privilege_encoder"], c["actor"], c["critic"], c["history_encoder"], std)
+
+
+def describe_ts(actor_critic, device=None):
+    """ActorCriticTS as the kernels take it (duck-typed: .privilege_encoder, .history_encoder, .actor, .critic, .std), by the rules of
+    `describe` for each of the four chains: a Conv1d / Flatten "TCN" history encoder is refused by its layer's name.  Refusals are
+    ValueErrors that name the layer or the member."""
+    return _describe_ts(actor_critic, device, _TS, "ActorCriticTS")
 
 
 def ts_args(spec, obs, privileged_obs, critic_obs, mu, sigma, values, workspace, grads=None, grad_mu=None, grad_sigma=None, grad_values=None,
@@ -517,25 +524,25 @@ def ts_args(spec, obs, privileged_obs, critic_obs, mu, sigma, values, workspace,
     return a
 
 
-def enc_args(spec, obs_history, privileged_obs, terminated, loss, workspace, grads=None, upstream=None, device=None):
+def enc_args(spec, obs_history, privileged_obs, terminated, loss, workspace, grads=None, upstream=None, device=None, owner=_TS):
     """LgTrainEncArgs of one call of the encoder pass.  `grads` (backward): in spec.encoder_parameters() order.  The privilege encoder's
     gradient pointers stay null: the pass has no use for them."""
     a = abi.LgTrainEncArgs()
     if not isinstance(obs_history, torch.Tensor) or obs_history.dim() != 2 or obs_history.shape[0] < 1:
-        raise ValueError(f"FusedTrainPassTS: obs_history must be a (B, {spec.history_encoder.widths[0]}) float32 tensor with B >= 1")
+        raise ValueError(f"{owner}: obs_history must be a (B, {spec.history_encoder.widths[0]}) float32 tensor with B >= 1")
     n = int(obs_history.shape[0])
     a.n_rows = n
     his, pri = a.chain[abi.TRAIN_ENC_HISTORY], a.chain[abi.TRAIN_ENC_PRIVILEGE]
-    his.input, his.in_stride = nets.rows(obs_history, spec.history_encoder.widths[0], "obs_history", n, device, _TS)
-    pri.input, pri.in_stride = nets.rows(privileged_obs, spec.privilege_encoder.widths[0], "privileged_obs", n, device, _TS)
+    his.input, his.in_stride = nets.rows(obs_history, spec.history_encoder.widths[0], "obs_history", n, device, owner)
+    pri.input, pri.in_stride = nets.rows(privileged_obs, spec.privilege_encoder.widths[0], "privileged_obs", n, device, owner)
     _fill_chain(his, spec.history_encoder, device, grads)
     _fill_chain(pri, spec.privilege_encoder, device)
-    a.mask, a.mask_stride = nets.rows(terminated, 1, "terminated", n, device, _TS)
+    a.mask, a.mask_stride = nets.rows(terminated, 1, "terminated", n, device, owner)
     if loss is not None:
-        a.loss = _scalar(loss, "the loss", device)
+        a.loss = _scalar(loss, "the loss", device, 1, owner)
     if upstream is not None:
-        a.upstream = _scalar(upstream, "the upstream gradient", device)
-    _bind_workspace(a, workspace, device)
+        a.upstream = _scalar(upstream, "the upstream gradient", device, 1, owner)
+    _bind_workspace(a, workspace, device, owner)
     return a
 
 
@@ -565,8 +572,8 @@ class FusedTrainPassTS:
     invalidate a pending backward of the other; within a pass a backward whose forward has been overwritten raises.  The actor may end in a
     Hardtanh or not (ActorCriticTS has none).
 
-    This is PPO_TS's update only.  ActorCriticCTS has the same members, but PPO_CTS updates two env groups with other losses: it keeps the
-    torch path, and so does a "TCN" (Conv1d) history encoder, which is refused by layer name."""
+    This is PPO_TS's update only.  ActorCriticCTS has the same members, but PPO_CTS updates two env groups with other losses: that is
+    FusedTrainPassCTS.  A "TCN" (Conv1d) history encoder keeps the torch path and is refused by layer name."""
 
     def __init__(self, actor_critic):
         self.device = _module_device(actor_critic, _TS)
@@ -595,6 +602,152 @@ class FusedTrainPassTS:
         """mse_loss(history_encoder(obs_history) * terminated, privilege_encoder(privileged_obs).detach() * terminated) as a 0-dim tensor
         with autograd.  Two launches."""
         return _apply(_LossFunction, self._enc, obs_history, privileged_obs, terminated)
+
+
+# ---- the concurrent teacher-student family (include/lgtraincts.h, csrc/lg_train_cts.hip) --------------------------------------------------------
+def describe_cts(actor_critic, device=None):
+    """ActorCriticCTS as the kernels take it: describe_ts's rules (the module has the same members) under FusedTrainPassCTS's name.  A
+    Conv1d / Flatten "TCN" history encoder is refused by its layer's name."""
+    return _describe_ts(actor_critic, device, _CTS, "ActorCriticCTS")
+
+
+def cts_args(spec, teacher_obs, teacher_privileged_obs, student_obs, student_obs_history, critic_obs, mu_t, sigma_t, mu_s, sigma_s, values, workspace,
+             grads=None, grad_mu_t=None, grad_sigma_t=None, grad_mu_s=None, grad_sigma_s=None, grad_values=None, device=None):
+    """LgTrainCTSArgs of one call of the RL pass.  `grads` (backward): the tensors that take the gradients, in spec.rl_parameters() order
+    (actor, critic, privilege encoder, std).  The history encoder's gradient pointers stay null: the pass has no use for them."""
+    a = abi.LgTrainCTSArgs()
+    for x, what in ((teacher_obs, "teacher_obs"), (student_obs, "student_obs"), (critic_obs, "critic_obs")):
+        if not isinstance(x, torch.Tensor) or x.dim() != 2 or x.shape[0] < 1:
+            raise ValueError(f"{_CTS}: {what} must be a (B, {spec.critic.widths[0] if what == 'critic_obs' else spec.num_obs}) float32 tensor with B >= 1")
+    nt, ns, nc = int(teacher_obs.shape[0]), int(student_obs.shape[0]), int(critic_obs.shape[0])
+    a.n_teacher, a.n_student, a.n_critic, a.n_obs = nt, ns, nc, spec.num_obs
+    A, V = spec.num_actions, spec.critic.widths[-1]
+    T, S = abi.TRAIN_CTS_TEACHER, abi.TRAIN_CTS_STUDENT
+    pri, act, cri, his = (a.chain[i] for i in (abi.TRAIN_CTS_PRIVILEGE, abi.TRAIN_CTS_ACTOR, abi.TRAIN_CTS_CRITIC, abi.TRAIN_CTS_HISTORY))
+    act.input, act.in_stride = nets.rows(teacher_obs, spec.num_obs, "teacher_obs", nt, device, _CTS)
+    pri.input, pri.in_stride = nets.rows(teacher_privileged_obs, spec.privilege_encoder.widths[0], "teacher_privileged_obs", nt, device, _CTS)
+    a.student_obs, a.student_obs_stride = nets.rows(student_obs, spec.num_obs, "student_obs", ns, device, _CTS)
+    his.input, his.in_stride = nets.rows(student_obs_history, spec.history_encoder.widths[0], "student_obs_history", ns, device, _CTS)
+    cri.input, cri.in_stride = nets.rows(critic_obs, spec.critic.widths[0], "critic_obs", nc, device, _CTS)
+    g_act, g_cri, g_pri, g_std = _rl_grads(grads, spec.actor, spec.critic, spec.privilege_encoder)
+    _fill_chain(act, spec.actor, device, g_act)
+    _fill_chain(cri, spec.critic, device, g_cri)
+    _fill_chain(pri, spec.privilege_encoder, device, g_pri)
+    _fill_chain(his, spec.history_encoder, device)
+    a.clip_on, a.clip_actions = (1, spec.clip_actions) if spec.clip_actions is not None else (0, 0.0)
+    nets.check_tensor(spec.std, "std", device, _CTS)
+    a.std = spec.std.data_ptr()
+    for g, n, mu, sigma, tag in ((T, nt, mu_t, sigma_t, "teacher"), (S, ns, mu_s, sigma_s, "student")):
+        a.mu[g], a.mu_stride[g] = nets.rows(mu, A, f"{tag} mu", n, device, _CTS)
+        a.sigma[g], a.sigma_stride[g] = nets.rows(sigma, A, f"{tag} sigma", n, device, _CTS)
+    a.values, a.values_stride = nets.rows(values, V, "values", nc, device, _CTS)
+    if grads is not None:
+        a.grad_std = g_std.data_ptr()
+        for g, n, gm, gs, tag in ((T, nt, grad_mu_t, grad_sigma_t, "teacher"), (S, ns, grad_mu_s, grad_sigma_s, "student")):
+            a.grad_mu[g], a.grad_mu_stride[g] = nets.rows(gm, A, f"{tag} grad_mu", n, device, _CTS)
+            a.grad_sigma[g], a.grad_sigma_stride[g] = nets.rows(gs, A, f"{tag} grad_sigma", n, device, _CTS)
+        a.grad_values, a.grad_values_stride = nets.rows(grad_values, V, "grad_values", nc, device, _CTS)
+    _bind_workspace(a, workspace, device, _CTS)
+    return a
+
+
+def plan_cts(n_teacher, n_student, n_critic, privilege_widths, actor_widths, critic_widths, history_widths):
+    """LgTrainCTSPlan of the RL pass (lg_train_cts_plan) for chains of these widths; O is actor_widths[0] less the latent width."""
+    key = ("lg_train_cts_plan", int(n_teacher), int(n_student), int(n_critic)) + tuple(tuple(int(x) for x in w) for w in
+                                                                                       (privilege_widths, actor_widths, critic_widths, history_widths))
+    if key not in _PLANS:
+        lib, a, p = abi.load_lib(), abi.LgTrainCTSArgs(), abi.LgTrainCTSPlan()
+        a.n_teacher, a.n_student, a.n_critic = key[1:4]
+        for i, w in zip((abi.TRAIN_CTS_PRIVILEGE, abi.TRAIN_CTS_ACTOR, abi.TRAIN_CTS_CRITIC, abi.TRAIN_CTS_HISTORY), key[4:]):
+            _widths_into(a.chain[i], w)
+        a.n_obs = int(actor_widths[0]) - int(privilege_widths[-1])
+        abi.check(lib.lg_train_cts_plan(C.byref(a), C.byref(p)), lib)
+        _PLANS[key] = p
+    return _PLANS[key]
+
+
+class _CTSFunction(torch.autograd.Function):
+    """(teacher mu, teacher sigma, student mu, student sigma, values) of the RL pass `ps` from its five inputs; the parameters ride along so
+    that autograd asks for their gradients."""
+
+    @staticmethod
+    def forward(ctx, ps, n_inputs, *inputs_and_params):
+        inputs, spec, device = inputs_and_params[:n_inputs], ps.spec, ps.device
+        n = tuple(int(x.shape[0]) if isinstance(x, torch.Tensor) and x.dim() == 2 else 0 for x in (inputs[0], inputs[2], inputs[4]))
+        new = lambda rows, w: torch.empty((max(rows, 1), w), dtype=torch.float32, device=device)
+        A = spec.num_actions
+        outs = (new(n[0], A), new(n[0], A), new(n[1], A), new(n[1], A), new(n[2], spec.critic.widths[-1]))
+        args = ps.args(spec, *inputs, *outs, None, device=device)      # every refusal before anything grows
+        ctx.ps, ctx.inputs, ctx.call = ps, inputs, ps.run_forward(args, n)
+        ctx.save_for_backward(*outs)
+        return outs
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *cotangents):
+        ps, outs = ctx.ps, ctx.saved_tensors
+        gs = [_grad_rows(g, like) for g, like in zip(cotangents, outs)]
+        grads = ps.run_backward(ctx.call, lambda g: ps.args(ps.spec, *ctx.inputs, *outs, ps.workspace, g, *gs, device=ps.device))
+        return (None,) * (2 + len(ctx.inputs)) + tuple(grads)
+
+
+class FusedTrainPassCTS:
+    """The two network passes of PPO_CTS.update() on an ActorCriticCTS (include/lgtraincts.h):
+
+        tp = FusedTrainPassCTS(actor_critic_cts)
+        mu_t, sigma_t, mu_s, sigma_s, values = tp(teacher_obs, teacher_privileged_obs, student_obs, student_obs_history, critic_obs)
+        out = loss_fn.cts(teacher=dict(mu=mu_t, sigma=sigma_t, ...), student=dict(mu=mu_s, sigma=sigma_s, ...), values=values, ...)
+        enc_loss = tp.encoder_loss(student_obs_history, student_privileged_obs)      # encoder step: two launches; backward three
+
+    The RL forward is one launch over the teacher's, the student's and the critic's rows (three independent row counts), its backward
+    three.  Optimise tp.rl_parameters() (actor, critic, privilege encoder, std: PPO_CTS.rl_params' order) and tp.encoder_parameters()
+    (the history encoder) apart.  The RL gradient reaches the privilege encoder through the latent columns of the teacher rows; the student
+    rows' latent is a constant of the RL pass and the history encoder's .grad is left as it was.  Torch does accumulate an RL gradient
+    there, which the reference zeroes before the only optimizer that owns those parameters steps: the parameters after every step are the
+    reference's, that .grad is not.  The encoder pass is mse_loss(history_encoder(h), privilege_encoder(p).detach()) on the teacher-student
+    family's encoder kernels with a column of ones, which the pass owns, as the mask; it leaves the privilege encoder's .grad as it was.
+    Each pass has its own workspace and call counter: a forward of one does not invalidate a pending backward of the other; within a pass a
+    backward whose forward has been overwritten raises.  The actor may end in a Hardtanh or not.  A "TCN" (Conv1d) history encoder keeps
+    the torch path and is refused by layer name."""
+
+    def __init__(self, actor_critic):
+        self.device = _module_device(actor_critic, _CTS)
+        self.spec = describe_cts(actor_critic, self.device)
+        self._ones = None
+        self._rl = _Pass(_CTS, "RL ", "lg_train_cts", cts_args, lambda n: self.plan(*n), self.rl_parameters, self.spec, self.device)
+        self._enc = _Pass(_CTS, "encoder ", "lg_train_enc", self._enc_args, self.encoder_plan, self.encoder_parameters, self.spec, self.device)
+
+    def rl_parameters(self):
+        return self.spec.rl_parameters()
+
+    def encoder_parameters(self):
+        return self.spec.encoder_parameters()
+
+    def plan(self, n_teacher, n_student, n_critic):
+        s = self.spec
+        return plan_cts(n_teacher, n_student, n_critic, s.privilege_encoder.widths, s.actor.widths, s.critic.widths, s.history_encoder.widths)
+
+    def encoder_plan(self, n_rows):
+        return plan_enc(n_rows, self.spec.history_encoder.widths, self.spec.privilege_encoder.widths)
+
+    def _enc_args(self, spec, obs_history, privileged_obs, loss, workspace, grads=None, upstream=None, device=None):
+        """enc_args with the pass's own ones column as the mask: grow-only, filled when it grows."""
+        ones = None
+        if isinstance(obs_history, torch.Tensor) and obs_history.dim() == 2 and obs_history.shape[0] >= 1:
+            n = int(obs_history.shape[0])
+            if self._ones is None or self._ones.shape[0] < n:
+                self._ones = torch.ones((n, 1), dtype=torch.float32, device=self.device)
+            ones = self._ones[:n]
+        return enc_args(spec, obs_history, privileged_obs, ones, loss, workspace, grads, upstream, device=device, owner=_CTS)
+
+    def __call__(self, teacher_obs, teacher_privileged_obs, student_obs, student_obs_history, critic_obs):
+        """(mu_t, sigma_t, mu_s, sigma_s, values): (Bt, A), (Bt, A), (Bs, A), (Bs, A), (Bc, 1).  One launch on the current stream."""
+        return _apply(_CTSFunction, self._rl, teacher_obs, teacher_privileged_obs, student_obs, student_obs_history, critic_obs)
+
+    def encoder_loss(self, student_obs_history, student_privileged_obs):
+        """mse_loss(history_encoder(student_obs_history), privilege_encoder(student_privileged_obs).detach()) as a 0-dim tensor with
+        autograd.  Two launches."""
+        return _apply(_LossFunction, self._enc, student_obs_history, student_privileged_obs)
 
 
 # ---- the DreamWaQ family (include/lgtraindwaq.h, csrc/lg_train_dwaq.hip) ------------------------------------------------------------------------

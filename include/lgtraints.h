@@ -4,7 +4,7 @@
  * lgtrainee.h, whose layer and chain structs are reused: plain device pointers and row strides in floats, the caller's HIP stream as void*;
  * 0 on success, otherwise non-zero with the message in lgsim.h's last-error call; nothing is allocated, nothing synchronised.  Everything is
  * float32.  Weights are read in place on every call.  This is PPO_TS's update only: ActorCriticCTS has the same members but updates two env
- * groups with other losses and is not served.
+ * groups with other losses; its RL pass is lgtraincts.h's, its encoder step the encoder pass below with a mask of ones.
  *
  * The RL pass (lg_train_ts_*), per row:   z = privilege_encoder(privileged_obs);   mu = actor([obs | z]) (behind the Hardtanh under
  *   clip_on);   sigma = mu * 0 + std;   values = critic(critic_obs).  The forward stores the concatenated actor input [obs | z] (n_rows x
