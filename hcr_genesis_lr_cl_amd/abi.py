@@ -333,6 +333,12 @@ def load_lib():
         lib.lg_train_cts_backward.argtypes = [C.POINTER(LgTrainCTSArgs), vp]
         for f in TRAIN_CTS_EXPORTS:
             getattr(lib, f).restype = C.c_int
+    if hasattr(lib, "lg_train_rnn_forward"):     # absent from libraries older than the recurrent learner pass
+        lib.lg_train_rnn_plan.argtypes = [C.POINTER(LgTrainRnnArgs), C.POINTER(LgTrainRnnPlan)]
+        lib.lg_train_rnn_forward.argtypes = [C.POINTER(LgTrainRnnArgs), vp]
+        lib.lg_train_rnn_backward.argtypes = [C.POINTER(LgTrainRnnArgs), vp]
+        for f in TRAIN_RNN_EXPORTS:
+            getattr(lib, f).restype = C.c_int
     lib.lg_last_error.restype = C.c_char_p
     lib.lg_last_kernel.argtypes = [H]
     lib.lg_last_kernel.restype = C.c_char_p
@@ -382,6 +388,8 @@ TRAIN_DWAQ_TARGET_JOBS, TRAIN_DWAQ_THREADS = 2048, 256
 TRAIN_CTS_EXPORTS = ["lg_train_cts_plan", "lg_train_cts_forward", "lg_train_cts_backward"]   # include/lgtraincts.h
 TRAIN_CTS_CHAINS, TRAIN_CTS_PRIVILEGE, TRAIN_CTS_ACTOR, TRAIN_CTS_CRITIC, TRAIN_CTS_HISTORY = 4, 0, 1, 2, 3
 TRAIN_CTS_GROUPS, TRAIN_CTS_TEACHER, TRAIN_CTS_STUDENT, TRAIN_CTS_ROLES, TRAIN_CTS_ROLE_CRITIC = 2, 0, 1, 3, 2
+TRAIN_RNN_EXPORTS = ["lg_train_rnn_plan", "lg_train_rnn_forward", "lg_train_rnn_backward"]   # include/lgtrainrnn.h
+TRAIN_RNN_MEMORIES, TRAIN_RNN_MAX_LAYERS, TRAIN_RNN_MAX_HIDDEN, TRAIN_RNN_LSTM, TRAIN_RNN_GRU, TRAIN_RNN_TARGET_JOBS = 2, 2, 512, 1, 2, 2048
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 2048
 POLICY_MAX_RNN_LAYERS, POLICY_MAX_RNN_HIDDEN = 2, 512
 POLICY_LSTM, POLICY_GRU = 1, 2
@@ -610,3 +618,30 @@ def check(rc, lib=None):
     if rc != 0:
         lib = lib or load_lib()
         raise RuntimeError("lgsim: " + lib.lg_last_error().decode())
+
+
+class LgTrainRnnLayer(C.Structure):
+    _fields_ = [("weight_ih", C.c_void_p), ("weight_hh", C.c_void_p), ("bias_ih", C.c_void_p), ("bias_hh", C.c_void_p),
+                ("grad_weight_ih", C.c_void_p), ("grad_weight_hh", C.c_void_p), ("grad_bias_ih", C.c_void_p), ("grad_bias_hh", C.c_void_p)]
+
+
+class LgTrainRnnMemory(C.Structure):
+    _fields_ = [("kind", i32), ("n_layers", i32), ("hidden", i32), ("n_in", i32), ("layer", LgTrainRnnLayer * TRAIN_RNN_MAX_LAYERS),
+                ("x", C.c_void_p), ("x_time_stride", i64), ("x_row_stride", i64), ("h0", C.c_void_p), ("c0", C.c_void_p),
+                ("h0_layer_stride", i64), ("h0_row_stride", i64), ("c0_layer_stride", i64), ("c0_row_stride", i64), ("mask", C.c_void_p),
+                ("mask_time_stride", i64), ("max_len", i32), ("n_traj", i32), ("T", i32), ("reserved", i32)]
+
+
+class LgTrainRnnArgs(C.Structure):
+    _fields_ = [("train", LgTrainArgs), ("memory", LgTrainRnnMemory * TRAIN_RNN_MEMORIES)]
+
+
+_RNN_I32 = i32 * 2 * TRAIN_RNN_MAX_LAYERS * TRAIN_RNN_MEMORIES
+_RNN_OFF = i64 * TRAIN_RNN_MAX_LAYERS * TRAIN_RNN_MEMORIES
+
+
+class LgTrainRnnPlan(C.Structure):
+    _fields_ = [("train", LgTrainPlan), ("time_row_tile", i32), ("time_lds_bytes", i32), ("time_tiles", i32), ("n_envs", i32), ("weight_jobs", i32),
+                ("reserved", i32), ("slices", _RNN_I32), ("slice_rows", _RNN_I32), ("gate_off", _RNN_OFF), ("h_off", _RNN_OFF),
+                ("hprev_off", _RNN_OFF), ("c_off", _RNN_OFF), ("nh_off", _RNN_OFF), ("dout_off", _RNN_OFF), ("dx_off", _RNN_OFF), ("dh_off", _RNN_OFF),
+                ("p_off", i64 * 2 * TRAIN_RNN_MAX_LAYERS * TRAIN_RNN_MEMORIES), ("index_off", i64), ("workspace_floats", i64)]

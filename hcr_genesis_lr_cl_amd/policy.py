@@ -102,56 +102,57 @@ class PolicySpec:
                                  self.memory_c, self.critic) if c is not None]
 
 
-def _describe_memory(name, mem, device):
+def _describe_memory(name, mem, device, owner=_OWNER):
     rnn = getattr(mem, "rnn", None)
     where = f"{name}.rnn"
     if not isinstance(rnn, (nn.LSTM, nn.GRU)):
-        raise ValueError(f"FusedPolicy: {where} is {type(rnn).__name__}, expected an nn.LSTM or nn.GRU")
+        raise ValueError(f"{owner}: {where} is {type(rnn).__name__}, expected an nn.LSTM or nn.GRU")
     if rnn.bidirectional:
-        raise ValueError(f"FusedPolicy: {where} is bidirectional; a rollout step has no backward direction")
+        raise ValueError(f"{owner}: {where} is bidirectional; a rollout step has no backward direction")
     if getattr(rnn, "proj_size", 0) != 0:
-        raise ValueError(f"FusedPolicy: {where} has proj_size={rnn.proj_size}; projections are not built into the kernel")
+        raise ValueError(f"{owner}: {where} has proj_size={rnn.proj_size}; projections are not built into the kernel")
     if rnn.dropout != 0:
-        raise ValueError(f"FusedPolicy: {where} has dropout={rnn.dropout}; dropout between rnn layers is not built into the kernel")
+        raise ValueError(f"{owner}: {where} has dropout={rnn.dropout}; dropout between rnn layers is not built into the kernel")
     if not rnn.bias:
-        raise ValueError(f"FusedPolicy: {where} has bias=False; the kernel reads bias_ih and bias_hh")
+        raise ValueError(f"{owner}: {where} has bias=False; the kernel reads bias_ih and bias_hh")
     if rnn.batch_first:
-        raise ValueError(f"FusedPolicy: {where} has batch_first=True; the reference's Memory feeds (1, N, in)")
+        raise ValueError(f"{owner}: {where} has batch_first=True; the reference's Memory feeds (1, N, in)")
     if rnn.num_layers > abi.POLICY_MAX_RNN_LAYERS:
-        raise ValueError(f"FusedPolicy: {where} has num_layers={rnn.num_layers}, the kernel takes {abi.POLICY_MAX_RNN_LAYERS}")
+        raise ValueError(f"{owner}: {where} has num_layers={rnn.num_layers}, the kernel takes {abi.POLICY_MAX_RNN_LAYERS}")
     if rnn.hidden_size > abi.POLICY_MAX_RNN_HIDDEN:
-        raise ValueError(f"FusedPolicy: {where} has hidden_size={rnn.hidden_size}, the gates (4 H) are limited to {abi.POLICY_MAX_WIDTH}: H <= "
+        raise ValueError(f"{owner}: {where} has hidden_size={rnn.hidden_size}, the gates (4 H) are limited to {abi.POLICY_MAX_WIDTH}: H <= "
                          f"{abi.POLICY_MAX_RNN_HIDDEN}")
     if rnn.input_size > abi.POLICY_MAX_WIDTH:
-        raise ValueError(f"FusedPolicy: {where} has input_size={rnn.input_size}, widths are limited to {abi.POLICY_MAX_WIDTH}")
+        raise ValueError(f"{owner}: {where} has input_size={rnn.input_size}, widths are limited to {abi.POLICY_MAX_WIDTH}")
     spec = MemorySpec(name, rnn)
     for k in range(spec.layers):
         for n, t in zip(("weight_ih", "weight_hh", "bias_ih", "bias_hh"), spec.params(k)):
-            nets.check_tensor(t, f"{where}.{n}_l{k}", device, _OWNER)
+            nets.check_tensor(t, f"{where}.{n}_l{k}", device, owner)
     return spec
 
 
-def _describe_recurrent(actor_critic, device):
+def _describe_recurrent(actor_critic, device, owner=_OWNER):
+    """The recurrent module as the kernels take it; `owner` names the surface in every refusal (train.py reads the module through this too)."""
     ma, mc = getattr(actor_critic, "memory_a", None), getattr(actor_critic, "memory_c", None)
     if ma is None or mc is None:
-        raise ValueError("FusedPolicy: a recurrent policy (actor_critic.is_recurrent) needs .memory_a and .memory_c, each with an nn.LSTM or "
+        raise ValueError(f"{owner}: a recurrent policy (actor_critic.is_recurrent) needs .memory_a and .memory_c, each with an nn.LSTM or "
                          "nn.GRU as .rnn; other recurrent modules keep the torch path")
     for need in ("actor", "critic", "std"):
         if not hasattr(actor_critic, need):
-            raise ValueError(f"FusedPolicy: the module has no .{need}")
+            raise ValueError(f"{owner}: the module has no .{need}")
     for other in ("estimator", "privilege_encoder", "history_encoder", "vae"):
         if getattr(actor_critic, other, None) is not None:
-            raise ValueError(f"FusedPolicy: a memory together with .{other}; memories are built for the plain actor-critic only")
-    mem_a, mem_c = _describe_memory("memory_a", ma, device), _describe_memory("memory_c", mc, device)
+            raise ValueError(f"{owner}: a memory together with .{other}; memories are built for the plain actor-critic only")
+    mem_a, mem_c = _describe_memory("memory_a", ma, device, owner), _describe_memory("memory_c", mc, device, owner)
     if mem_a.kind != mem_c.kind:
-        raise ValueError(f"FusedPolicy: memory_a.rnn is an {mem_a.kind.upper()}, memory_c.rnn a {mem_c.kind.upper()}; one kind for both")
-    actor = nets.describe_chain("actor", actor_critic.actor, device, True, _OWNER)
-    critic = nets.describe_chain("critic", actor_critic.critic, device, False, _OWNER)
+        raise ValueError(f"{owner}: memory_a.rnn is an {mem_a.kind.upper()}, memory_c.rnn a {mem_c.kind.upper()}; one kind for both")
+    actor = nets.describe_chain("actor", actor_critic.actor, device, True, owner)
+    critic = nets.describe_chain("critic", actor_critic.critic, device, False, owner)
     for ch, mem in ((actor, mem_a), (critic, mem_c)):
         if ch.widths[0] != mem.hidden:
-            raise ValueError(f"FusedPolicy: {ch.name}[0] takes {ch.widths[0]} inputs (in_features), {mem.name}.rnn gives hidden_size = {mem.hidden}")
+            raise ValueError(f"{owner}: {ch.name}[0] takes {ch.widths[0]} inputs (in_features), {mem.name}.rnn gives hidden_size = {mem.hidden}")
     std = actor_critic.std
-    nets.check_std(std, actor, device, _OWNER)
+    nets.check_std(std, actor, device, owner)
     return PolicySpec(None, actor, critic, std, memory_a=mem_a, memory_c=mem_c)
 
 

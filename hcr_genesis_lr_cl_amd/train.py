@@ -20,7 +20,9 @@ pass, whose gradient reaches the privilege encoder through the latent, and the s
 (include/lgtraindwaq.h, csrc/lg_train_dwaq.hip) is the same for ActorCriticDreamWaQ under PPO_DreamWaQ: the RL pass behind the VAE's
 encoder, heads and reparameterised draw, and the VAE pass with its three losses.  FusedTrainPassCTS (include/lgtraincts.h,
 csrc/lg_train_cts.hip) is the same for ActorCriticCTS under PPO_CTS: the RL pass over the teacher's, the student's and the critic's rows, and
-the history-encoder pass on the teacher-student family's encoder kernels with a mask of ones.
+the history-encoder pass on the teacher-student family's encoder kernels with a mask of ones.  FusedTrainPassRecurrent
+(include/lgtrainrnn.h, csrc/lg_train_rnn.hip) is the same for ActorCriticRecurrent under PPO: the two memories over the padded trajectories
+of a recurrent mini-batch, the two MLPs on the unpadded rows, and the backward through the MLPs, through time and into the memories.
 
 The five families share what is below `_Pass`: one record per pass (workspace, call counter, entry points, descriptor builder), one
 autograd.Function for an RL pass and one for a loss pass, driven by that record.  A refusal carries the name of the surface that first
@@ -33,13 +35,14 @@ import ctypes as C
 import torch
 import torch.nn as nn
 
-from . import abi, nets
+from . import abi, nets, policy
 from .nets import ChainSpec as TrainChainSpec      # the name callers and tests know it by here
 
 _OTHER_FAMILIES = (("estimator", "ActorCriticEE"), ("privilege_encoder", "ActorCriticTS / ActorCriticCTS"),
                    ("history_encoder", "ActorCriticTS / ActorCriticCTS"), ("vae", "ActorCriticDreamWaQ"),
                    ("memory_a", "ActorCriticRecurrent"), ("memory_c", "ActorCriticRecurrent"))
 _PLAIN, _EE, _TS, _DWAQ, _CTS = "FusedTrainPass", "FusedTrainPassEE", "FusedTrainPassTS", "FusedTrainPassDreamWaQ", "FusedTrainPassCTS"
+_RNN = "FusedTrainPassRecurrent"
 
 
 class TrainSpec:
@@ -222,12 +225,13 @@ class _Pass:
         self.owner, self.what, self.entry, self.args, self.plan, self.parameters = owner, what, entry, args, plan, parameters
         self.spec, self.device, self.workspace, self.calls = spec, device, None, 0
 
-    def run_forward(self, args, n):
-        """Plan, grow the workspace, launch, count: the number of this forward call."""
+    def run_forward(self, args, n, heads=None):
+        """Plan, grow the workspace, launch, count: the number of this forward call.  `heads`: the member of `args` that holds the workspace,
+        where that is not `args` itself."""
         need = int(self.plan(n).workspace_floats)
         if self.workspace is None or self.workspace.numel() < need:
             self.workspace = torch.empty(need, dtype=torch.float32, device=self.device)
-        _bind_workspace(args, self.workspace, self.device)
+        _bind_workspace(args if heads is None else heads, self.workspace, self.device)
         _call(self.entry + "_forward", args, self.device)
         self.calls += 1
         return self.calls
@@ -967,3 +971,192 @@ class FusedTrainPassDreamWaQ:
         """The VAE loss of PPO_DreamWaQ._compute_vae_loss and its three terms, as a VaeLosses.  Two launches."""
         inputs = (obs_history, explicit_info_labels, next_states, terminated, self._noise(obs_history, latent_noise))
         return VaeLosses(_VaeFunction.apply(self._vae, self.kld_weight, len(inputs), *inputs, *self.vae_parameters()))
+
+
+# ---- the recurrent family (include/lgtrainrnn.h, csrc/lg_train_rnn.hip) -------------------------------------------------------------------------
+_RNN_PARAMS = ("weight_ih", "weight_hh", "bias_ih", "bias_hh")
+
+
+class TrainSpecRecurrent:
+    """ActorCriticRecurrent as the kernels take it: policy.py's reading of the module (the two memories, the two chains, std)."""
+
+    def __init__(self, ps):
+        self.actor, self.critic, self.std, self.memory_a, self.memory_c = ps.actor, ps.critic, ps.std, ps.memory_a, ps.memory_c
+        self.chains, self.memories = (ps.actor, ps.critic), (ps.memory_a, ps.memory_c)
+        self.num_actions, self.clip_actions = ps.num_actions, ps.clip_actions
+
+    def parameters(self):
+        """std, the actor's and the critic's weight and bias per layer, then per memory and layer weight_ih, weight_hh, bias_ih, bias_hh:
+        the order of ActorCriticRecurrent.parameters() and of the pass's gradients."""
+        return [self.std] + [p for c in self.chains for l in c.linears for p in (l.weight, l.bias)] + \
+            [getattr(m.rnn, f"{n}_l{k}") for m in self.memories for k in range(m.layers) for n in _RNN_PARAMS]
+
+    def parameter_names(self):
+        return ["std"] + [f"{c.name}.{i}.{n}" for c in self.chains for i in range(len(c.linears)) for n in ("weight", "bias")] + \
+            [f"{m.name}.rnn.{n}_l{k}" for m in self.memories for k in range(m.layers) for n in _RNN_PARAMS]
+
+
+def describe_recurrent(actor_critic, device=None):
+    """ActorCriticRecurrent through FusedPolicy's reader (policy.py), so that what can be rolled out can be trained; refusals are
+    ValueErrors of FusedTrainPassRecurrent that name the member."""
+    if not getattr(actor_critic, "is_recurrent", False):
+        raise ValueError(f"{_RNN}: the module is not recurrent (is_recurrent); FusedTrainPass is the pass of the plain ActorCritic")
+    return TrainSpecRecurrent(policy._describe_recurrent(actor_critic, device, _RNN))
+
+
+def _padded(t, width, what, device):
+    """A (max_len, n_traj, width) float32 tensor addressed in place: (pointer, time stride, row stride, max_len, n_traj)."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or t.dim() != 3 or t.shape[2] != width or t.shape[0] < 1 or t.shape[1] < 1 \
+            or (width > 1 and t.stride(2) != 1) or (device is not None and t.device != device):
+        got = f"{tuple(t.shape)} {t.dtype} with strides {t.stride()} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+        raise ValueError(f"{_RNN}: {what} must be (max_len, n_traj, {width}) float32 with unit inner stride" + (f" on {device}" if device is not None else "")
+                         + f"; got {got}")
+    return t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else 0), (t.stride(1) if t.shape[1] > 1 else width), int(t.shape[0]), int(t.shape[1])
+
+
+def _start_states(hid, mem, n_traj, what, device):
+    """[h] (GRU) or [h, c] (LSTM) of one memory from what the generator yields: a tensor or a list, each (layers, n_traj, H)."""
+    states = list(hid) if isinstance(hid, (list, tuple)) else [hid]
+    want = 2 if mem.kind == "lstm" else 1
+    if len(states) != want:
+        raise ValueError(f"{_RNN}: {what} holds {len(states)} tensors, an {mem.kind.upper()} has {want}")
+    out = []
+    for t, n in zip(states, ("h", "c")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (mem.layers, n_traj, mem.hidden) \
+                or (mem.hidden > 1 and t.stride(2) != 1) or (device is not None and t.device != device):
+            got = f"{tuple(t.shape)} {t.dtype} with strides {t.stride()} on {t.device}" if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{_RNN}: {what} {n} must be ({mem.layers}, {n_traj}, {mem.hidden}) float32 with unit inner stride"
+                             + (f" on {device}" if device is not None else "") + f"; got {got}")
+        out.append((t.data_ptr(), t.stride(0) if mem.layers > 1 else 0, t.stride(1) if n_traj > 1 else mem.hidden))
+    return out
+
+
+def rnn_sizes(masks, obs, n_envs):
+    """(n_rows, max_len, n_traj, T) of a recurrent mini-batch from the shapes and the env count."""
+    if not isinstance(masks, torch.Tensor) or masks.dtype not in (torch.bool, torch.uint8) or masks.dim() != 2 or masks.shape[0] < 1 \
+            or (masks.shape[1] > 1 and masks.stride(1) != 1):
+        got = f"{tuple(masks.shape)} {masks.dtype} with strides {masks.stride()}" if isinstance(masks, torch.Tensor) else type(masks).__name__
+        raise ValueError(f"{_RNN}: masks must be (T, n_traj) bool with unit inner stride; got {got}")
+    T, n_traj = int(masks.shape[0]), int(masks.shape[1])
+    if not isinstance(obs, torch.Tensor) or obs.dim() != 3 or obs.shape[1] != n_traj or not 1 <= obs.shape[0] <= T:
+        got = tuple(obs.shape) if isinstance(obs, torch.Tensor) else type(obs).__name__
+        raise ValueError(f"{_RNN}: obs must be (max_len, {n_traj}, width) with 1 <= max_len <= T = {T}, as the masks say; got {got}")
+    if not isinstance(n_envs, int) or not 1 <= n_envs <= n_traj:
+        raise ValueError(f"{_RNN}: n_envs = {n_envs!r} must be an int in [1, n_traj = {n_traj}]")
+    return T * n_envs, int(obs.shape[0]), n_traj, T
+
+
+def rnn_args(spec, obs, critic_obs, masks, hid, n_envs, mu, sigma, values, workspace, grads=None, grad_mu=None, grad_sigma=None, grad_values=None,
+             device=None):
+    """LgTrainRnnArgs of one call; the padded observations, the masks and the start states are addressed in place.  `grads` (backward):
+    the tensors that take the gradients, in spec.parameters() order.  Refusals are ValueErrors; the library is not touched."""
+    a = abi.LgTrainRnnArgs()
+    n, max_len, n_traj, T = rnn_sizes(masks, obs, n_envs)
+    if device is not None and masks.device != device:
+        raise ValueError(f"{_RNN}: masks is on {masks.device}, not on {device}")
+    if not isinstance(hid, (list, tuple)) or len(hid) != 2:
+        raise ValueError(f"{_RNN}: hid_states must be the pair (hid_a, hid_c) of the mini-batch generator")
+    a.train.n_rows = n
+    g0 = 1
+    for ch, c in zip(a.train.chain, spec.chains):
+        _fill_chain(ch, c, device, None if grads is None else grads[g0:g0 + 2 * len(c.linears)])
+        g0 += 2 * len(c.linears)
+    for m, ms, x, h, what in zip(a.memory, spec.memories, (obs, critic_obs), hid, ("obs", "critic_obs")):
+        m.kind, m.n_layers, m.hidden, m.n_in = (abi.TRAIN_RNN_LSTM if ms.kind == "lstm" else abi.TRAIN_RNN_GRU), ms.layers, ms.hidden, ms.input_size
+        m.x, m.x_time_stride, m.x_row_stride, ml, nt = _padded(x, ms.input_size, what, device)
+        if (ml, nt) != (max_len, n_traj):
+            raise ValueError(f"{_RNN}: {what} is ({ml}, {nt}, .), obs ({max_len}, {n_traj}, .)")
+        st = _start_states(h, ms, n_traj, f"hid_states of {ms.name}", device)
+        m.h0, m.h0_layer_stride, m.h0_row_stride = st[0]
+        if len(st) > 1:
+            m.c0, m.c0_layer_stride, m.c0_row_stride = st[1]
+        m.mask, m.mask_time_stride = masks.data_ptr(), (masks.stride(0) if T > 1 else n_traj)
+        m.max_len, m.n_traj, m.T = max_len, n_traj, T
+        for k in range(ms.layers):
+            L = m.layer[k]
+            L.weight_ih, L.weight_hh, L.bias_ih, L.bias_hh = (t.data_ptr() for t in ms.params(k))
+            if grads is not None:
+                L.grad_weight_ih, L.grad_weight_hh, L.grad_bias_ih, L.grad_bias_hh = (t.data_ptr() for t in grads[g0:g0 + 4])
+                g0 += 4
+    _fill_heads(a.train, spec, mu, sigma, values, n, device, _RNN, *(() if grads is None else (grads[0], grad_mu, grad_sigma, grad_values)))
+    _bind_workspace(a.train, workspace, device, _RNN)
+    return a
+
+
+def plan_rnn(n_rows, max_len, n_traj, T, kind, memories, actor_widths, critic_widths):
+    """LgTrainRnnPlan of a mini-batch of these sizes; `kind`: "lstm" or "gru"; `memories`: (layers, hidden, input width) of memory_a and
+    memory_c; the widths [in, out_0, out_1, ...] of the two chains."""
+    key = ("lg_train_rnn_plan", int(n_rows), int(max_len), int(n_traj), int(T), kind, tuple(tuple(int(v) for v in m) for m in memories),
+           tuple(int(x) for x in actor_widths), tuple(int(x) for x in critic_widths))
+    if key not in _PLANS:
+        lib, a, p = abi.load_lib(), abi.LgTrainRnnArgs(), abi.LgTrainRnnPlan()
+        a.train.n_rows = key[1]
+        for m, (layers, hidden, n_in) in zip(a.memory, key[6]):
+            m.kind, m.n_layers, m.hidden, m.n_in = (abi.TRAIN_RNN_LSTM if kind == "lstm" else abi.TRAIN_RNN_GRU), layers, hidden, n_in
+            m.max_len, m.n_traj, m.T = key[2:5]
+        _widths_into(a.train.chain[0], key[7])
+        _widths_into(a.train.chain[1], key[8])
+        abi.check(lib.lg_train_rnn_plan(C.byref(a), C.byref(p)), lib)
+        _PLANS[key] = p
+    return _PLANS[key]
+
+
+class _RnnFunction(torch.autograd.Function):
+    """(mu, sigma, values) of the recurrent pass `ps` from a recurrent mini-batch; the parameters ride along as in _RLFunction."""
+
+    @staticmethod
+    def forward(ctx, ps, obs, critic_obs, masks, hid, n_envs, *params):
+        spec, device = ps.spec, ps.device
+        sizes = rnn_sizes(masks, obs, n_envs)
+        mu = torch.empty((sizes[0], spec.num_actions), dtype=torch.float32, device=device)
+        sigma = torch.empty_like(mu)
+        values = torch.empty((sizes[0], spec.critic.widths[-1]), dtype=torch.float32, device=device)
+        args = rnn_args(spec, obs, critic_obs, masks, hid, n_envs, mu, sigma, values, None, device=device)
+        ctx.ps, ctx.inputs, ctx.call = ps, (obs, critic_obs, masks, hid, n_envs), ps.run_forward(args, sizes, args.train)
+        ctx.save_for_backward(mu, sigma, values)
+        return mu, sigma, values
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_mu, grad_sigma, grad_values):
+        ps = ctx.ps
+        mu, sigma, values = ctx.saved_tensors
+        gm, gs, gv = _grad_rows(grad_mu, mu), _grad_rows(grad_sigma, sigma), _grad_rows(grad_values, values)
+        grads = ps.run_backward(ctx.call, lambda g: rnn_args(ps.spec, *ctx.inputs, mu, sigma, values, ps.workspace, g, gm, gs, gv, device=ps.device))
+        return (None,) * 6 + tuple(grads)           # nothing for the observations, the masks or the start states
+
+
+class FusedTrainPassRecurrent:
+    """The network passes of PPO.update() on an ActorCriticRecurrent (include/lgtrainrnn.h), fed by what
+    RolloutStorage.reccurent_mini_batch_generator yields:
+
+        tp = FusedTrainPassRecurrent(actor_critic_recurrent)
+        mu, sigma, values = tp(obs_batch, critic_obs_batch, masks_batch, hid_states_batch, n_envs=actions_batch.shape[1])
+        out = loss_fn(mu, sigma, values, actions_batch.flatten(0, 1), ...)        # FusedPPOLoss, rows in unpad_trajectories' order
+        opt.zero_grad(); out.loss.backward(); opt.step(kl_mean=out.kl_mean)       # FusedAdam over tp.parameters()
+
+    obs_batch / critic_obs_batch are the (max_len, n_traj, width) views of the padded set, masks_batch the (T, n_traj) bool view and
+    hid_states_batch = (hid_a, hid_c), a tensor each for a GRU and a list [h, c] each for an LSTM (hid_c may be hid_a); all are read in
+    place.  mu and sigma are (T E, A), values (T E, 1), row t E + e as `unpad_trajectories(...).flatten(0, 1)` orders them.  E, the number
+    of envs of the mini-batch, is mask.sum() / T and in no shape: pass it as n_envs (PPO.update has it as the second dimension of every
+    stored column) and nothing synchronises with the host; without it the pass reads mask.sum() back once, which a HIP graph capture cannot
+    do.  There is no gradient for the observations or the start states."""
+
+    def __init__(self, actor_critic):
+        self.device = _module_device(actor_critic, _RNN)
+        self.spec = describe_recurrent(actor_critic, self.device)
+        self._pass = _Pass(_RNN, "", "lg_train_rnn", rnn_args, lambda sizes: self.plan(*sizes), self.spec.parameters, self.spec, self.device)
+
+    def parameters(self):
+        return self.spec.parameters()
+
+    def plan(self, n_rows, max_len, n_traj, T):
+        s = self.spec
+        return plan_rnn(n_rows, max_len, n_traj, T, s.memory_a.kind, [(m.layers, m.hidden, m.input_size) for m in s.memories], s.actor.widths,
+                        s.critic.widths)
+
+    def __call__(self, obs_batch, critic_obs_batch, masks_batch, hid_states_batch, n_envs=None):
+        """(mu, sigma, values) of the mini-batch: (T E, A), (T E, A), (T E, 1).  2 + 2 layers launches on the current stream."""
+        if n_envs is None:
+            n_envs = int(masks_batch.sum().item()) // int(masks_batch.shape[0])          # the one read-back; see the class docstring
+        return _RnnFunction.apply(self._pass, obs_batch, critic_obs_batch, masks_batch, hid_states_batch, int(n_envs), *self.spec.parameters())
