@@ -1150,6 +1150,12 @@ class FusedTrainPassRecurrent:
     def parameters(self):
         return self.spec.parameters()
 
+    @property
+    def workspace(self):
+        """The float32 workspace of the last forward call, laid out by its plan (LgTrainRnnPlan's offsets); None before the first call.
+        For reading only: the next forward call overwrites or replaces it."""
+        return self._pass.workspace
+
     def plan(self, n_rows, max_len, n_traj, T):
         s = self.spec
         return plan_rnn(n_rows, max_len, n_traj, T, s.memory_a.kind, [(m.layers, m.hidden, m.input_size) for m in s.memories], s.actor.widths,

@@ -18,6 +18,8 @@ DEFECTS = ("gate_order", "no_dh_carry", "no_dc_carry", "whh_uses_ht", "zero_star
 # in the middle and nowhere else, so that every trajectory is short and max_len < T), or a number of further dones drawn before the last step;
 # obs / critic obs widths; the hidden widths of the two MLPs; clip: a Hardtanh behind the actor; first: the padded tensors are views
 # [:, first:first + n_traj] of a wider padded set; shared: memory_c is handed memory_a's start states (the same objects).
+# critic_mem=(layers, H): memory_c's own depth and width (tests/train_rnn_edges.py); without it memory_c has memory_a's.  obs_scale: a factor on
+# both observations (the same file's saturated rows).  A case without either draws what it drew before they existed.
 # The time loop's tile is 32 trajectories below H = 128: n_traj = E + dones is 31, 32, 33 in the first three; 8 at H = 512: 9 there.
 CASES = {
     "lstm1_h7_t6":      dict(kind="lstm", layers=1, H=7, T=6, E=27, dones=4, obs=(11, 13), actor=(24, 10), critic=(20,), clip=True, seed=1),
@@ -84,8 +86,13 @@ def plan(n_rows, max_len, n_traj, T, kind, memories, actor_widths, critic_widths
     return out
 
 
+def mems_of(c):
+    """[(layers, H)] of memory_a and memory_c of a case: memory_c has memory_a's unless the case carries critic_mem."""
+    return [(c["layers"], c["H"]), tuple(c.get("critic_mem") or (c["layers"], c["H"]))]
+
+
 def plan_of_case(inp):
-    mem = [(inp["layers"], inp["H"], o) for o in inp["obs_widths"]]
+    mem = [(L, H, o) for (L, H), o in zip(mems_of(inp), inp["obs_widths"])]
     return plan(inp["T"] * inp["E"], inp["max_len"], inp["n_traj"], inp["T"], inp["kind"], mem, inp["actor_widths"], inp["critic_widths"])
 
 
@@ -130,9 +137,10 @@ def positions(lens, T, E, traj_major=False):
 
 def names_of(case):
     c = case
-    a, k = [c["H"], *c["actor"], c["A"]], [c["H"], *c["critic"], 1]
+    (La, Ha), (Lc, Hc) = mems_of(c)
+    a, k = [Ha, *c["actor"], c["A"]], [Hc, *c["critic"], 1]
     return ["std"] + [f"{ch}.{i}.{n}" for ch, w in (("actor", a), ("critic", k)) for i in range(len(w) - 1) for n in ("weight", "bias")] + \
-        [f"{m}.rnn.{n}_l{l}" for m in ("memory_a", "memory_c") for l in range(c["layers"]) for n in RNN_PARAMS]
+        [f"{m}.rnn.{n}_l{l}" for m, L in (("memory_a", La), ("memory_c", Lc)) for l in range(L) for n in RNN_PARAMS]
 
 
 def make_inputs(case, pad=0.0):
@@ -141,31 +149,34 @@ def make_inputs(case, pad=0.0):
     c.setdefault("A", 3)
     rng = np.random.default_rng(1000 + c["seed"])
     f = np.float32
-    kind, L, H, T, E, G = c["kind"], c["layers"], c["H"], c["T"], c["E"], GATES[c["kind"]]
+    kind, H, T, E, G = c["kind"], c["H"], c["T"], c["E"], GATES[c["kind"]]
+    mems = mems_of(c)
     lens = lengths_of(draw_dones(rng, T, E, c["dones"]))
     n_traj, max_len = len(lens), int(lens.max())
     t_idx, j_idx, _ = positions(lens, T, E)
     first, shared = c.get("first", 0), bool(c.get("shared", False))
     inp = dict(c, lens=lens, n_traj=n_traj, max_len=max_len, first=first, shared=shared, obs_widths=c["obs"], pad=pad,
-               actor_widths=[H, *c["actor"], c["A"]], critic_widths=[H, *c["critic"], 1])
+               actor_widths=[H, *c["actor"], c["A"]], critic_widths=[mems[1][1], *c["critic"], 1])
     masks = np.zeros((T, n_traj), bool)
     masks[t_idx, j_idx] = True
     inp["masks"] = masks
     for key, O in zip(("obs", "critic_obs"), c["obs"]):
         x = np.full((max_len, n_traj, O), pad, f)
         x[t_idx, j_idx] = rng.normal(size=(len(t_idx), O)).astype(f)
+        if "obs_scale" in c:                                                       # tests/train_rnn_edges.py: observations that saturate the gates
+            x[t_idx, j_idx] *= f(c["obs_scale"])
         inp[key] = x
-    for m in "ac":
-        inp["h0_" + m] = (0.5 * rng.normal(size=(L, n_traj, H))).astype(f)
-        inp["c0_" + m] = (0.5 * rng.normal(size=(L, n_traj, H))).astype(f) if kind == "lstm" else None
+    for m, (L, Hm) in zip("ac", mems):
+        inp["h0_" + m] = (0.5 * rng.normal(size=(L, n_traj, Hm))).astype(f)
+        inp["c0_" + m] = (0.5 * rng.normal(size=(L, n_traj, Hm))).astype(f) if kind == "lstm" else None
     if shared:
         inp["h0_c"], inp["c0_c"] = inp["h0_a"], inp["c0_a"]
     values = [(0.5 + 0.5 * rng.random(c["A"])).astype(f)] + ts.draw_layers(rng, inp["actor_widths"]) + ts.draw_layers(rng, inp["critic_widths"])
-    bound = 1.0 / np.sqrt(H)
-    for O in c["obs"]:
+    for O, (L, Hm) in zip(c["obs"], mems):
+        bound = 1.0 / np.sqrt(Hm)
         for l in range(L):
-            K = H if l else O
-            values += [rng.uniform(-bound, bound, size=s).astype(f) for s in ((G * H, K), (G * H, H), (G * H,), (G * H,))]
+            K = Hm if l else O
+            values += [rng.uniform(-bound, bound, size=s).astype(f) for s in ((G * Hm, K), (G * Hm, Hm), (G * Hm,), (G * Hm,))]
     inp["names"] = names_of(c)
     inp["params"] = dict(zip(inp["names"], values))
     N = T * E
@@ -182,7 +193,7 @@ def _sig(v):
 
 
 def _memory_params(inp, m, dtype):
-    return [[np.asarray(inp["params"][f"memory_{m}.rnn.{n}_l{l}"]).astype(dtype) for n in RNN_PARAMS] for l in range(inp["layers"])]
+    return [[np.asarray(inp["params"][f"memory_{m}.rnn.{n}_l{l}"]).astype(dtype) for n in RNN_PARAMS] for l in range(mems_of(inp)["ac".index(m)][0])]
 
 
 def memory_forward(kind, params, x, lens, h0, c0, dtype, defects=()):
@@ -278,13 +289,19 @@ def memory_backward(kind, params, stored, lens, h0, c0, d_top, order, pers, dtyp
     return grads
 
 
-def restate(inp, dtype, defects=(), sliced=False):
+def restate(inp, dtype, defects=(), sliced=False, rows=None):
     """mu, sigma, values and every parameter gradient (by name) of a case under the cotangents grad_mu, grad_sigma, grad_values, and
     `pre_clip`, the means before the Hardtanh.  sliced: the batch sums per slice in slice order as the plan cuts them (the float32 side of
-    the host tests); otherwise one sum."""
+    the host tests); otherwise one sum.  rows: a function (lens, T, E) -> (t, j, row) in place of `positions` (tests/train_rnn_edges.py's
+    restatement of the index kernel, which may give a row to two steps: the later one in (j, t) order holds it, as a store would).  Two
+    defects beside DEFECTS, for memories that differ and observations wider than a gradient tile (tests/train_rnn_edges.py):
+    shallow_loop, both memories run memory_a's depth (the critic reads the last layer that ran, the layers behind get no gradient);
+    ih_first_k_tile, grad weight_ih_l0 keeps its columns below WG_TILE only."""
     kind, T, E, A = inp["kind"], inp["T"], inp["E"], inp["A"]
     lens = np.minimum(inp["lens"] + 1, inp["max_len"]) if "padded_step" in defects else inp["lens"]
-    t_idx, j_idx, row = positions(lens, T, E, "traj_major_rows" in defects)
+    t_idx, j_idx, row = positions(lens, T, E, "traj_major_rows" in defects) if rows is None else rows(lens, T, E)
+    depth = mems_of(inp)[0][0] if "shallow_loop" in defects else MAX_LAYERS
+    mem_params = [_memory_params(inp, m, dtype) for m in "ac"]
     N = T * E
     if "padded_step" in defects:                     # the counted steps run over the rows: keep what lands inside
         keep = row < N
@@ -295,8 +312,8 @@ def restate(inp, dtype, defects=(), sliced=False):
     P = {k: np.asarray(v).astype(dtype) for k, v in inp["params"].items()}
     out, tops, stored = {}, [], []
     for mi, (m, key) in enumerate((("a", "obs"), ("c", "critic_obs"))):
-        st = memory_forward(kind, _memory_params(inp, m, dtype), inp[key].astype(dtype), lens, inp["h0_" + m], inp["c0_" + m], dtype, defects)
-        top = np.zeros((N, inp["H"]), dtype)
+        st = memory_forward(kind, mem_params[mi][:depth], inp[key].astype(dtype), lens, inp["h0_" + m], inp["c0_" + m], dtype, defects)
+        top = np.zeros((N, mems_of(inp)[mi][1]), dtype)
         top[row] = st[-1]["h"][t_idx, j_idx]
         tops.append(top)
         stored.append(st)
@@ -315,13 +332,16 @@ def restate(inp, dtype, defects=(), sliced=False):
         g, gin = ts.chain_backward(layers, acts, G, dtype, pl["train"]["slice_rows"][ci] if sliced else None, input_grad=True)
         for i in range(len(layers)):
             out[f"{ch}.{i}.weight"], out[f"{ch}.{i}.bias"] = g[2 * i], g[2 * i + 1]
-        d_top = np.zeros((inp["max_len"], inp["n_traj"], inp["H"]), dtype)
+        d_top = np.zeros((inp["max_len"], inp["n_traj"], mems_of(inp)[mi][1]), dtype)
         d_top[t_idx, j_idx] = gin[row]
-        mg = memory_backward(kind, _memory_params(inp, m, dtype), stored[mi], lens, inp["h0_" + m], inp["c0_" + m], d_top, order,
+        mg = memory_backward(kind, mem_params[mi][:depth], stored[mi], lens, inp["h0_" + m], inp["c0_" + m], d_top, order,
                              pl["slice_rows"][mi] if sliced else None, dtype, defects)
+        mg += [[np.zeros_like(p) for p in layer] for layer in mem_params[mi][depth:]]
         for l, gl in enumerate(mg):
             for n, v in zip(RNN_PARAMS, gl):
                 out[f"memory_{m}.rnn.{n}_l{l}"] = v
+        if "ih_first_k_tile" in defects:
+            out[f"memory_{m}.rnn.weight_ih_l0"] = np.where(np.arange(inp["obs_widths"][mi]) < ts.WG_TILE, out[f"memory_{m}.rnn.weight_ih_l0"], 0).astype(dtype)
     return out
 
 
@@ -340,8 +360,9 @@ class Recurrent(torch.nn.Module):
         super().__init__()
         self.actor, self.critic = ts.sequential(inp["actor_widths"], inp["clip"]), ts.sequential(inp["critic_widths"], None)
         self.std = torch.nn.Parameter(torch.ones(inp["A"]))
-        self.memory_a = Memory(inp["kind"], inp["obs_widths"][0], inp["H"], inp["layers"])
-        self.memory_c = Memory(inp["kind"], inp["obs_widths"][1], inp["H"], inp["layers"])
+        (La, Ha), (Lc, Hc) = mems_of(inp)
+        self.memory_a = Memory(inp["kind"], inp["obs_widths"][0], Ha, La)
+        self.memory_c = Memory(inp["kind"], inp["obs_widths"][1], Hc, Lc)
         self.to(dtype)
         params = list(self.parameters())                  # std, actor, critic, memory_a, memory_c: the order of inp["names"]
         assert len(params) == len(inp["names"])
