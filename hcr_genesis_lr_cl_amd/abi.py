@@ -1,4 +1,4 @@
-"""ctypes mirror of include/lgsim.h, include/lgrollout.h, include/lgsensor.h, include/lgpolicy.h, include/lgppo.h, include/lgoptim.h, include/lgtrain.h, include/lgtrainee.h and include/lgtraints.h (the C ABI) and the loader of the HIP library.
+"""ctypes mirror of include/lgsim.h, include/lgrollout.h, include/lgsensor.h, include/lgpolicy.h, include/lgppo.h, include/lgoptim.h, include/lgtrain.h, include/lgtrainee.h, include/lgtraints.h and include/lgtraintcn.h (the C ABI) and the loader of the HIP library.
 
 Field order and types must match the header exactly; tests/test_abi.py compiles a C
 probe that prints sizeof/offsetof for every struct and compares them with these classes.
@@ -339,6 +339,12 @@ def load_lib():
         lib.lg_train_rnn_backward.argtypes = [C.POINTER(LgTrainRnnArgs), vp]
         for f in TRAIN_RNN_EXPORTS:
             getattr(lib, f).restype = C.c_int
+    if hasattr(lib, "lg_train_tcn_forward"):     # absent from libraries older than the TCN history-encoder pass
+        lib.lg_train_tcn_plan.argtypes = [C.POINTER(LgTrainTcnArgs), C.POINTER(LgTrainTcnPlan)]
+        lib.lg_train_tcn_forward.argtypes = [C.POINTER(LgTrainTcnArgs), vp]
+        lib.lg_train_tcn_backward.argtypes = [C.POINTER(LgTrainTcnArgs), vp]
+        for f in TRAIN_TCN_EXPORTS:
+            getattr(lib, f).restype = C.c_int
     lib.lg_last_error.restype = C.c_char_p
     lib.lg_last_kernel.argtypes = [H]
     lib.lg_last_kernel.restype = C.c_char_p
@@ -390,6 +396,9 @@ TRAIN_CTS_CHAINS, TRAIN_CTS_PRIVILEGE, TRAIN_CTS_ACTOR, TRAIN_CTS_CRITIC, TRAIN_
 TRAIN_CTS_GROUPS, TRAIN_CTS_TEACHER, TRAIN_CTS_STUDENT, TRAIN_CTS_ROLES, TRAIN_CTS_ROLE_CRITIC = 2, 0, 1, 3, 2
 TRAIN_RNN_EXPORTS = ["lg_train_rnn_plan", "lg_train_rnn_forward", "lg_train_rnn_backward"]   # include/lgtrainrnn.h
 TRAIN_RNN_MEMORIES, TRAIN_RNN_MAX_LAYERS, TRAIN_RNN_MAX_HIDDEN, TRAIN_RNN_LSTM, TRAIN_RNN_GRU, TRAIN_RNN_TARGET_JOBS = 2, 2, 512, 1, 2, 2048
+TRAIN_TCN_EXPORTS = ["lg_train_tcn_plan", "lg_train_tcn_forward", "lg_train_tcn_backward"]   # include/lgtraintcn.h
+TRAIN_TCN_MAX_CONV, TRAIN_TCN_MAX_CHANNELS, TRAIN_TCN_MAX_KERNEL, TRAIN_TCN_MAX_STRIDE, TRAIN_TCN_MAX_DILATION = 6, 32, 9, 4, 8
+TRAIN_TCN_TARGET_JOBS, TRAIN_TCN_THREADS, TRAIN_TCN_WG_ELEMS, TRAIN_TCN_MAX_BLOCKS = 2048, 256, 8, 2048
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 2048
 POLICY_MAX_RNN_LAYERS, POLICY_MAX_RNN_HIDDEN = 2, 512
 POLICY_LSTM, POLICY_GRU = 1, 2
@@ -612,6 +621,27 @@ class LgTrainCTSPlan(C.Structure):
                 ("enc_first_buffer", i32 * TRAIN_CTS_GROUPS), ("h_off", i64 * POLICY_MAX_LAYERS * TRAIN_CTS_CHAINS),
                 ("g_off", i64 * POLICY_MAX_LAYERS * TRAIN_CTS_CHAINS), ("p_off", i64 * POLICY_MAX_LAYERS * TRAIN_CTS_CHAINS), ("std_p_off", i64),
                 ("cat_off", i64), ("workspace_floats", i64)]
+
+
+class LgTrainConv(C.Structure):
+    _fields_ = [("weight", C.c_void_p), ("bias", C.c_void_p), ("grad_weight", C.c_void_p), ("grad_bias", C.c_void_p),
+                ("c_in", i32), ("c_out", i32), ("kernel", i32), ("stride", i32), ("padding", i32), ("dilation", i32)]
+
+
+class LgTrainTcnArgs(C.Structure):
+    _fields_ = [("n_rows", i32), ("mask_stride", i32), ("n_conv", i32), ("n_history", i32), ("conv", LgTrainConv * TRAIN_TCN_MAX_CONV),
+                ("history", C.c_void_p), ("history_stride", i32), ("reserved", i32), ("tail", LgTrainChain), ("privilege", LgTrainChain),
+                ("mask", C.c_void_p), ("loss", C.c_void_p), ("upstream", C.c_void_p), ("workspace", C.c_void_p), ("workspace_capacity", i64)]
+
+
+class LgTrainTcnPlan(C.Structure):
+    _fields_ = [("row_tile", i32), ("lds_bytes", i32), ("n_conv", i32), ("flat", i32), ("length", i32 * (TRAIN_TCN_MAX_CONV + 1)),
+                ("conv_block_rows", i32), ("conv_blocks", i32), ("conv_jobs", i32), ("conv_slices", i32 * TRAIN_TCN_MAX_CONV),
+                ("conv_slice_rows", i32 * TRAIN_TCN_MAX_CONV), ("conv_job0", i32 * TRAIN_TCN_MAX_CONV), ("slices", i32 * POLICY_MAX_LAYERS),
+                ("slice_rows", i32 * POLICY_MAX_LAYERS), ("weight_jobs", i32), ("loss_tiles", i32),
+                ("x_off", i64 * (TRAIN_TCN_MAX_CONV + 1)), ("cg_off", i64 * (TRAIN_TCN_MAX_CONV + 1)), ("conv_p_off", i64 * TRAIN_TCN_MAX_CONV),
+                ("h_off", i64 * POLICY_MAX_LAYERS), ("g_off", i64 * POLICY_MAX_LAYERS), ("p_off", i64 * POLICY_MAX_LAYERS),
+                ("gl_off", i64), ("y_off", i64), ("partial_off", i64), ("workspace_floats", i64)]
 
 
 def check(rc, lib=None):

@@ -60,16 +60,16 @@ def _check_linear(m, where, device, owner):
     check_tensor(m.bias, f"{where}.bias", device, owner)
 
 
-def describe_chain(name, seq, device, allow_clip, owner, allow_last_elu=False):
+def describe_chain(name, seq, device, allow_clip, owner, allow_last_elu=False, index0=0):
     """The ChainSpec of `seq`, or the refusal that names its layer.  `allow_clip`: a symmetric Hardtanh may end it (the actor);
-    `allow_last_elu`: an ELU may (the DreamWaQ encoder)."""
+    `allow_last_elu`: an ELU may (the DreamWaQ encoder); `index0`: the index of seq[0] in the module the refusals name (a TCN's tail)."""
     if not isinstance(seq, nn.Sequential):
         raise ValueError(f"{owner}: {name} is {type(seq).__name__}, expected an nn.Sequential of Linear / ELU"
                          + (" / Hardtanh" if allow_clip else ""))
     linears, elu, clip = [], [], None
     mods = list(seq)
     for i, m in enumerate(mods):
-        where = f"{name}[{i}]"
+        where = f"{name}[{i + index0}]"
         if clip is not None:
             raise ValueError(f"{owner}: {where} ({type(m).__name__}) follows the Hardtanh, which must end the actor")
         if isinstance(m, nn.Linear):
@@ -146,3 +146,102 @@ def rows(t, width, what, n, device, owner):
         raise ValueError(f"{owner}: {what} must be ({'B' if n is None else n}, {width}) float32 with unit inner stride"
                          + (f" on {device}" if device is not None else "") + f"; got {got}")
     return t.data_ptr(), (t.stride(0) if t.shape[0] > 1 else width)
+
+
+class TcnSpec:
+    """A "TCN" history encoder as the kernels take it (include/lgtraintcn.h): its Conv1d modules in order and the Linear / ELU tail
+    behind the Flatten.  The history length H is no property of the module: `lengths(H)` gives [H, L_1, ..., L_n] or the refusal."""
+
+    def __init__(self, name, convs, tail, owner):
+        self.name, self.convs, self.tail, self.owner = name, convs, tail, owner
+
+    @property
+    def shapes(self):
+        """(c_in, c_out, kernel, stride, padding, dilation) of every conv."""
+        return [(m.in_channels, m.out_channels, m.kernel_size[0], m.stride[0], m.padding[0], m.dilation[0]) for m in self.convs]
+
+    def lengths(self, n_history):
+        out = conv_lengths(self.name, self.convs, n_history, self.owner)
+        C, F = self.convs[-1].out_channels, self.convs[-1].out_channels * out[-1]
+        if self.tail.widths[0] != F:
+            raise ValueError(f"{self.owner}: {self.name}[{len(self.convs) + 1}].in_features = {self.tail.widths[0]}, but the flattened conv output has "
+                             f"{C} * {out[-1]} = {F} columns for H = {int(n_history)}")
+        return out
+
+    def parameters(self):
+        """In `seq.parameters()` order: every conv's weight and bias, then the tail's."""
+        return [p for m in list(self.convs) + list(self.tail.linears) for p in (m.weight, m.bias)]
+
+
+def conv_lengths(name, convs, n_history, owner):
+    """[H, L_1, ..., L_n] of a stack of Conv1d modules on a history of H columns, or the refusal: H outside the kernel's widths, a window
+    longer than its padded input, more columns behind the Flatten than the tail's first operand may have."""
+    H = int(n_history)
+    if not 1 <= H <= abi.POLICY_MAX_WIDTH:
+        raise ValueError(f"{owner}: obs_history has {H} columns, the kernel takes 1 to {abi.POLICY_MAX_WIDTH}")
+    out = [H]
+    for i, m in enumerate(convs):
+        k, s, p, d = m.kernel_size[0], m.stride[0], m.padding[0], m.dilation[0]
+        span = out[-1] + 2 * p - d * (k - 1) - 1
+        if span < 0:
+            raise ValueError(f"{owner}: {name}[{i}] has a window of dilation * (kernel_size - 1) + 1 = {d * (k - 1) + 1} on a padded input "
+                             f"of {out[-1] + 2 * p}: the output length is below 1")
+        out.append(span // s + 1)
+    C, F = convs[-1].out_channels, convs[-1].out_channels * out[-1]
+    if F > abi.POLICY_MAX_WIDTH:
+        raise ValueError(f"{owner}: {name}[{len(convs) - 1}] leaves out_channels * L = {C} * {out[-1]} = {F} columns behind the Flatten "
+                         f"for H = {H}, the kernel takes {abi.POLICY_MAX_WIDTH}")
+    return out
+
+
+def describe_tcn(name, seq, device, owner, n_history=None):
+    """The TcnSpec of `seq` = Conv1d+, Flatten, <a Linear / ELU chain by describe_chain's rules>, or the refusal that names `name[i]` and
+    the attribute.  With `n_history` the lengths are checked too (TcnSpec.lengths)."""
+    if not isinstance(seq, nn.Sequential):
+        raise ValueError(f"{owner}: {name} is {type(seq).__name__}, expected an nn.Sequential of Conv1d, Flatten, Linear / ELU")
+    mods, convs = list(seq), []
+    lim = dict(kernel_size=abi.TRAIN_TCN_MAX_KERNEL, stride=abi.TRAIN_TCN_MAX_STRIDE, dilation=abi.TRAIN_TCN_MAX_DILATION)
+    for i, m in enumerate(mods):
+        where = f"{name}[{i}]"
+        if isinstance(m, nn.Flatten):
+            break
+        if not isinstance(m, nn.Conv1d):
+            what = "an activation between the convolutions is not built" if convs and not isinstance(m, nn.Linear) else "expected Conv1d layers, then a Flatten"
+            raise ValueError(f"{owner}: {where} is {type(m).__name__}; {what}")
+        if len(convs) == abi.TRAIN_TCN_MAX_CONV:
+            raise ValueError(f"{owner}: {where} is Conv1d number {len(convs) + 1}, the kernel takes {abi.TRAIN_TCN_MAX_CONV}")
+        if m.groups != 1:
+            raise ValueError(f"{owner}: {where}.groups = {m.groups}, only groups = 1 is built")
+        if m.padding_mode != "zeros":
+            raise ValueError(f"{owner}: {where}.padding_mode = {m.padding_mode!r}, only 'zeros' is built")
+        if isinstance(m.padding, str):
+            raise ValueError(f"{owner}: {where}.padding = {m.padding!r}, only an integer padding is built")
+        if m.bias is None:
+            raise ValueError(f"{owner}: {where}.bias is None, the kernel adds a bias")
+        want_in = convs[-1].out_channels if convs else 1
+        if m.in_channels != want_in:
+            raise ValueError(f"{owner}: {where}.in_channels = {m.in_channels}, " + (f"the conv before it gives {want_in}" if convs else "obs_history is one channel"))
+        for attr, hi in (("in_channels", abi.TRAIN_TCN_MAX_CHANNELS), ("out_channels", abi.TRAIN_TCN_MAX_CHANNELS)):
+            if not 1 <= getattr(m, attr) <= hi:
+                raise ValueError(f"{owner}: {where}.{attr} = {getattr(m, attr)} is outside [1, {hi}]")
+        for attr, hi in lim.items():
+            if not 1 <= getattr(m, attr)[0] <= hi:
+                raise ValueError(f"{owner}: {where}.{attr} = {getattr(m, attr)[0]} is outside [1, {hi}]")
+        if not 0 <= m.padding[0] <= m.dilation[0] * (m.kernel_size[0] - 1):
+            raise ValueError(f"{owner}: {where}.padding = {m.padding[0]} is outside [0, dilation * (kernel_size - 1) = {m.dilation[0] * (m.kernel_size[0] - 1)}]")
+        check_tensor(m.weight, f"{where}.weight", device, owner)
+        check_tensor(m.bias, f"{where}.bias", device, owner)
+        convs.append(m)
+    else:
+        raise ValueError(f"{owner}: {name} has no Flatten behind its Conv1d layers")
+    if not convs:
+        raise ValueError(f"{owner}: {name}[0] is Flatten; expected Conv1d layers before it")
+    if (m.start_dim, m.end_dim) != (1, -1):
+        raise ValueError(f"{owner}: {name}[{i}] is Flatten({m.start_dim}, {m.end_dim}), only Flatten(1, -1) is built")
+    if n_history is not None:
+        conv_lengths(name, convs, n_history, owner)                   # before the tail: F above the limit is refused as F, with its factors
+    tail = describe_chain(name, nn.Sequential(*mods[i + 1:]), device, False, owner, index0=i + 1)
+    spec = TcnSpec(name, convs, tail, owner)
+    if n_history is not None:
+        spec.lengths(n_history)
+    return spec

@@ -21,7 +21,8 @@ Three more module shapes are recognised, each still one launch per step (the key
              pre-step hidden-state rows the storage keeps run in the launch.  The states live in tensors this object owns, updated in
              place (`get_hidden_states`, `set_hidden_states`, `reset`, `last_hidden_states`), so a captured call keeps its addresses.
 A history encoder with Conv1d / Flatten (the "TCN" option) and activations other than ELU are refused, with a message that names the
-layer; so is an rnn that is bidirectional, projected, batch-first, without bias, with dropout, of more than two layers or H above 512.
+layer (`FusedPolicy(module, student=False)` does not read the history encoder at all and serves the rollout of such a module: every call but
+`act_student` and `num_teacher`); so is an rnn that is bidirectional, projected, batch-first, without bias, with dropout, of more than two layers or H above 512.
 What a chain, the four heads, a parameter tensor, std and a row matrix must be is nets.py's, one copy shared with train.py.
 
 The draw is torch's when `noise` is given, otherwise the project's Philox4x32-10: counter (env, action quad, call counter, stream tag),
@@ -156,9 +157,11 @@ def _describe_recurrent(actor_critic, device, owner=_OWNER):
     return PolicySpec(None, actor, critic, std, memory_a=mem_a, memory_c=mem_c)
 
 
-def describe(actor_critic, device=None):
+def describe(actor_critic, device=None, student=True):
     """What the kernel will be told about `actor_critic`, with every refusal; touches neither the library nor the device.  `device`:
-    the HIP device every parameter must live on (None: not checked, for inspecting a module on the host)."""
+    the HIP device every parameter must live on (None: not checked, for inspecting a module on the host).  `student=False`: the history
+    encoder of a TS / CTS module is not read at all (it may be a Conv1d "TCN"); the spec then has no history_encoder, and only the calls
+    that run the privilege encoder are served."""
     if getattr(actor_critic, "is_recurrent", False):
         return _describe_recurrent(actor_critic, device)
     for need in ("actor", "critic", "std"):
@@ -175,12 +178,12 @@ def describe(actor_critic, device=None):
     if (ts or vae is not None) and (estimator is not None or (ts and vae is not None)):
         raise ValueError("FusedPolicy: the module mixes .estimator, .privilege_encoder / .history_encoder and .vae; one family at a time")
     if ts:
-        for need in ("privilege_encoder", "history_encoder"):
+        for need in ("privilege_encoder", "history_encoder") if student else ("privilege_encoder",):
             if not hasattr(actor_critic, need):
                 raise ValueError(f"FusedPolicy: the module has no .{need}")
         pe = nets.describe_chain("privilege_encoder", actor_critic.privilege_encoder, device, False, _OWNER)
-        he = nets.describe_chain("history_encoder", actor_critic.history_encoder, device, False, _OWNER)
-        if pe.widths[-1] != he.widths[-1]:
+        he = nets.describe_chain("history_encoder", actor_critic.history_encoder, device, False, _OWNER) if student else None
+        if he is not None and pe.widths[-1] != he.widths[-1]:
             raise ValueError(f"FusedPolicy: privilege_encoder gives {pe.widths[-1]} latent dims, history_encoder {he.widths[-1]}")
         if actor.widths[0] <= pe.widths[-1]:
             raise ValueError(f"FusedPolicy: actor[0] takes {actor.widths[0]} inputs, the latent alone has {pe.widths[-1]}")
@@ -267,6 +270,9 @@ def _family_inputs(spec, n, privileged_obs, obs_history, num_teacher, student, l
         raise ValueError("FusedPolicy: obs_history is missing: the VAE's encoder reads it")
     if fam != "ts":
         return None
+    if spec.history_encoder is None and (student or num_teacher is not None):
+        raise ValueError("FusedPolicy: " + ("the student call" if student else "num_teacher") + " runs the history encoder, which student=False left "
+                         "unread; build the FusedPolicy with student=True (a Conv1d history encoder keeps act_student on torch)")
     if num_teacher is not None:
         if student:
             raise ValueError("FusedPolicy: num_teacher and the student call exclude each other")
@@ -367,7 +373,7 @@ class FusedPolicy:
     """`FusedPolicy(actor_critic, seed=...)`; `act`, `act_inference`, `act_teacher`, `act_student`, `evaluate`, `fill_transition`; for a
     recurrent module also `reset`, `get_hidden_states`, `set_hidden_states` and `last_hidden_states`.  See the module docstring."""
 
-    def __init__(self, actor_critic, seed=0, device=None):
+    def __init__(self, actor_critic, seed=0, device=None, student=True):
         std = getattr(actor_critic, "std", None)
         dev = torch.device(device) if device is not None else (std.device if torch.is_tensor(std) else torch.device("cpu"))
         if dev.type != "cuda":
@@ -376,7 +382,8 @@ class FusedPolicy:
             dev = torch.device("cuda", torch.cuda.current_device())
         self.device = dev
         self.module = actor_critic
-        self.spec = describe(actor_critic, dev)          # every refusal comes before the library is loaded
+        self.student = bool(student)                     # False: a TS module's history encoder is never read (it may be a "TCN")
+        self.spec = describe(actor_critic, dev, self.student)          # every refusal comes before the library is loaded
         self.seed = int(seed)
         self.lib = abi.load_lib()
         self.counter = torch.zeros(1, dtype=torch.int32, device=dev)        # the Philox call counter (read as uint32)
@@ -419,7 +426,7 @@ class FusedPolicy:
                                                                          if torch.is_tensor(v))
         a = self._args.get(key)
         if a is None:
-            self.spec = describe(self.module, self.device)
+            self.spec = describe(self.module, self.device, self.student)
             if len(self._args) >= 256:
                 self._args.clear()
             a = self._args[key] = policy_args(self.spec, t.get("obs"), t.get("critic_obs"), t.get("actions"), t.get("mu"), t.get("sigma"),
@@ -587,7 +594,12 @@ class FusedPolicy:
         return mu
 
     def act_student(self, obs, obs_history):
-        """TS / CTS: the mean with the history encoder's latent (actor_critic_ts.py:186-195)."""
+        """TS / CTS: the mean with the history encoder's latent (actor_critic_ts.py:186-195).  Under `student=False` this raises: the
+        history encoder was not read.  For a Conv1d "TCN" history encoder act_student stays on torch (module.act_student): it is play-time
+        only, PPO_TS's rollout never runs the history encoder."""
+        if not self.student:
+            raise ValueError("FusedPolicy: act_student runs the history encoder, which student=False left unread; build the FusedPolicy with "
+                             "student=True (a Conv1d history encoder keeps act_student on torch)")
         mu = self._buffers(int(obs.shape[0]))["student"]
         self._launch(abi.POLICY_DETERMINISTIC, None, True, obs=obs, mu=mu, obs_history=obs_history)
         return mu

@@ -20,7 +20,8 @@ pass, whose gradient reaches the privilege encoder through the latent, and the s
 (include/lgtraindwaq.h, csrc/lg_train_dwaq.hip) is the same for ActorCriticDreamWaQ under PPO_DreamWaQ: the RL pass behind the VAE's
 encoder, heads and reparameterised draw, and the VAE pass with its three losses.  FusedTrainPassCTS (include/lgtraincts.h,
 csrc/lg_train_cts.hip) is the same for ActorCriticCTS under PPO_CTS: the RL pass over the teacher's, the student's and the critic's rows, and
-the history-encoder pass on the teacher-student family's encoder kernels with a mask of ones.  FusedTrainPassRecurrent
+the history-encoder pass on the teacher-student family's encoder kernels with a mask of ones.  FusedTrainPassTSTcn (include/lgtraintcn.h,
+csrc/lg_train_tcn.hip) is FusedTrainPassTS for an ActorCriticTS whose history encoder is a "TCN" (Conv1d stack, Flatten, Linear tail).  FusedTrainPassRecurrent
 (include/lgtrainrnn.h, csrc/lg_train_rnn.hip) is the same for ActorCriticRecurrent under PPO: the two memories over the padded trajectories
 of a recurrent mini-batch, the two MLPs on the unpadded rows, and the backward through the MLPs, through time and into the memories.
 
@@ -504,27 +505,27 @@ def describe_ts(actor_critic, device=None):
 
 
 def ts_args(spec, obs, privileged_obs, critic_obs, mu, sigma, values, workspace, grads=None, grad_mu=None, grad_sigma=None, grad_values=None,
-            device=None):
+            device=None, owner=_TS):
     """LgTrainTSArgs of one call of the RL pass.  `grads` (backward): the tensors that take the gradients, in spec.rl_parameters() order
     (actor, critic, privilege encoder, std)."""
     a = abi.LgTrainTSArgs()
     if not isinstance(obs, torch.Tensor) or obs.dim() != 2 or obs.shape[0] < 1:
-        raise ValueError(f"FusedTrainPassTS: obs must be a (B, O) float32 tensor with B >= 1 and O = actor[0].in_features - {spec.num_latent}")
+        raise ValueError(f"{owner}: obs must be a (B, O) float32 tensor with B >= 1 and O = actor[0].in_features - {spec.num_latent}")
     n = int(obs.shape[0])
     if obs.shape[1] + spec.num_latent != spec.actor.widths[0]:
-        raise ValueError(f"FusedTrainPassTS: actor[0] takes {spec.actor.widths[0]} inputs, but [obs | latent] has {obs.shape[1]} + "
+        raise ValueError(f"{owner}: actor[0] takes {spec.actor.widths[0]} inputs, but [obs | latent] has {obs.shape[1]} + "
                          f"{spec.num_latent} columns")
     a.n_rows, a.n_obs = n, spec.num_obs
     pri, act, cri = a.chain[abi.TRAIN_TS_PRIVILEGE], a.chain[abi.TRAIN_TS_ACTOR], a.chain[abi.TRAIN_TS_CRITIC]
-    act.input, act.in_stride = nets.rows(obs, spec.num_obs, "obs", n, device, _TS)
-    pri.input, pri.in_stride = nets.rows(privileged_obs, spec.privilege_encoder.widths[0], "privileged_obs", n, device, _TS)
-    cri.input, cri.in_stride = nets.rows(critic_obs, spec.critic.widths[0], "critic_obs", n, device, _TS)
+    act.input, act.in_stride = nets.rows(obs, spec.num_obs, "obs", n, device, owner)
+    pri.input, pri.in_stride = nets.rows(privileged_obs, spec.privilege_encoder.widths[0], "privileged_obs", n, device, owner)
+    cri.input, cri.in_stride = nets.rows(critic_obs, spec.critic.widths[0], "critic_obs", n, device, owner)
     g_act, g_cri, g_pri, g_std = _rl_grads(grads, spec.actor, spec.critic, spec.privilege_encoder)
     _fill_chain(act, spec.actor, device, g_act)
     _fill_chain(cri, spec.critic, device, g_cri)
     _fill_chain(pri, spec.privilege_encoder, device, g_pri)
-    _fill_heads(a, spec, mu, sigma, values, n, device, _TS, g_std, grad_mu, grad_sigma, grad_values)
-    _bind_workspace(a, workspace, device)
+    _fill_heads(a, spec, mu, sigma, values, n, device, owner, g_std, grad_mu, grad_sigma, grad_values)
+    _bind_workspace(a, workspace, device, owner)
     return a
 
 
@@ -577,7 +578,7 @@ class FusedTrainPassTS:
     Hardtanh or not (ActorCriticTS has none).
 
     This is PPO_TS's update only.  ActorCriticCTS has the same members, but PPO_CTS updates two env groups with other losses: that is
-    FusedTrainPassCTS.  A "TCN" (Conv1d) history encoder keeps the torch path and is refused by layer name."""
+    FusedTrainPassCTS.  A "TCN" (Conv1d) history encoder is refused by layer name here: its passes are FusedTrainPassTSTcn."""
 
     def __init__(self, actor_critic):
         self.device = _module_device(actor_critic, _TS)
@@ -606,6 +607,189 @@ class FusedTrainPassTS:
         """mse_loss(history_encoder(obs_history) * terminated, privilege_encoder(privileged_obs).detach() * terminated) as a 0-dim tensor
         with autograd.  Two launches."""
         return _apply(_LossFunction, self._enc, obs_history, privileged_obs, terminated)
+
+
+# ---- ActorCriticTS with a "TCN" history encoder (include/lgtraintcn.h, csrc/lg_train_tcn.hip) ------------------------------------------------
+_TCN = "FusedTrainPassTSTcn"
+
+
+class TrainSpecTSTcn:
+    """ActorCriticTS with history_encoder_type = "TCN" as the kernels take it: the privilege encoder, the actor and the critic as
+    TrainSpecTS has them (the RL pass is the same), and the history encoder as a nets.TcnSpec."""
+
+    def __init__(self, privilege_encoder, actor, critic, history_encoder, std):
+        self.privilege_encoder, self.actor, self.critic, self.history_encoder, self.std = privilege_encoder, actor, critic, history_encoder, std
+        self.num_actions, self.clip_actions = actor.widths[-1], actor.clip
+        self.num_latent = privilege_encoder.widths[-1]
+        self.num_obs = actor.widths[0] - self.num_latent
+
+    rl_parameters, rl_parameter_names = TrainSpecTS.rl_parameters, TrainSpecTS.rl_parameter_names
+
+    def encoder_parameters(self):
+        """In history_encoder.parameters() order: every conv's weight and bias, then the tail's."""
+        return self.history_encoder.parameters()
+
+    def encoder_parameter_names(self):
+        h = self.history_encoder
+        at = [i for i in range(len(h.convs))] + [len(h.convs) + 1 + 2 * j for j in range(len(h.tail.linears))]      # ELU behind every tail layer but the last
+        return [f"history_encoder.{i}.{n}" for i in at for n in ("weight", "bias")]
+
+
+def describe_ts_tcn(actor_critic, device=None, n_history=None):
+    """ActorCriticTS with a Conv1d+ / Flatten / Linear-ELU history encoder, by describe_ts's rules for the other three chains and
+    nets.describe_tcn's for the history encoder; with `n_history` (H, which the module does not record) the lengths are checked too.  A
+    module whose history encoder is an MLP is FusedTrainPassTS's."""
+    for need in ("privilege_encoder", "history_encoder"):
+        if getattr(actor_critic, need, None) is None:
+            raise ValueError(f"{_TCN}: the module has no .{need}; ActorCriticTS has a privilege encoder and a history encoder")
+    he = actor_critic.history_encoder
+    if isinstance(he, nn.Sequential) and not any(isinstance(m, (nn.Conv1d, nn.Flatten)) for m in he):
+        raise ValueError(f"{_TCN}: history_encoder has no Conv1d layer: it is an MLP, which FusedTrainPassTS builds")
+
+    def between(c):
+        if c["actor"].widths[0] <= c["privilege_encoder"].widths[-1]:
+            raise ValueError(f"{_TCN}: actor[0] takes {c['actor'].widths[0]} inputs, but [obs | latent] has O + {c['privilege_encoder'].widths[-1]} "
+                             f"columns with O >= 1")
+    c, std = _describe(actor_critic, device, _TCN, _TS_FOREIGN, " beside its encoders; only ActorCriticTS is built",
+                       (("privilege_encoder", False), ("actor", True), ("critic", False)), between)
+    tcn = nets.describe_tcn("history_encoder", he, device, _TCN, n_history)
+    if tcn.tail.widths[-1] != c["privilege_encoder"].widths[-1]:
+        raise ValueError(f"{_TCN}: history_encoder ends at {tcn.tail.widths[-1]} columns, privilege_encoder at {c['privilege_encoder'].widths[-1]}: the "
+                         f"latent widths differ")
+    return TrainSpecTSTcn(c["privilege_encoder"], c["actor"], c["critic"], tcn, std)
+
+
+def _history_rows(obs_history, owner):
+    """obs_history as (B, H) rows: (B, H) itself, or the (B, 1, H) the reference hands its Conv1d stack (ppo_ts.py:176-178), in place."""
+    if isinstance(obs_history, torch.Tensor) and obs_history.dim() == 3 and obs_history.shape[1] == 1:
+        obs_history = obs_history[:, 0, :]
+    if not isinstance(obs_history, torch.Tensor) or obs_history.dim() != 2 or obs_history.shape[0] < 1:
+        raise ValueError(f"{owner}: obs_history must be a (B, H) or (B, 1, H) float32 tensor with B >= 1")
+    return obs_history
+
+
+def tcn_args(spec, obs_history, privileged_obs, terminated, loss, workspace, grads=None, upstream=None, device=None):
+    """LgTrainTcnArgs of one call of the encoder pass.  `grads` (backward): in spec.encoder_parameters() order.  The privilege encoder's
+    gradient pointers stay null."""
+    a = abi.LgTrainTcnArgs()
+    obs_history = _history_rows(obs_history, _TCN)
+    n, H = int(obs_history.shape[0]), int(obs_history.shape[1])
+    tcn = spec.history_encoder
+    tcn.lengths(H)
+    a.n_rows, a.n_history, a.n_conv = n, H, len(tcn.convs)
+    a.history, a.history_stride = nets.rows(obs_history, H, "obs_history", n, device, _TCN)
+    for l, (m, shape) in enumerate(zip(tcn.convs, tcn.shapes)):
+        v = a.conv[l]
+        nets.check_tensor(m.weight, f"history_encoder[{l}].weight", device, _TCN)
+        nets.check_tensor(m.bias, f"history_encoder[{l}].bias", device, _TCN)
+        v.weight, v.bias = m.weight.data_ptr(), m.bias.data_ptr()
+        v.c_in, v.c_out, v.kernel, v.stride, v.padding, v.dilation = shape
+        if grads is not None:
+            v.grad_weight, v.grad_bias = grads[2 * l].data_ptr(), grads[2 * l + 1].data_ptr()
+    a.privilege.input, a.privilege.in_stride = nets.rows(privileged_obs, spec.privilege_encoder.widths[0], "privileged_obs", n, device, _TCN)
+    _fill_chain(a.tail, tcn.tail, device, None if grads is None else grads[2 * len(tcn.convs):])
+    _fill_chain(a.privilege, spec.privilege_encoder, device)
+    a.mask, a.mask_stride = nets.rows(terminated, 1, "terminated", n, device, _TCN)
+    if loss is not None:
+        a.loss = _scalar(loss, "the loss", device, 1, _TCN)
+    if upstream is not None:
+        a.upstream = _scalar(upstream, "the upstream gradient", device, 1, _TCN)
+    _bind_workspace(a, workspace, device, _TCN)
+    return a
+
+
+def plan_tcn(n_rows, n_history, convs, tail_widths, privilege_widths):
+    """LgTrainTcnPlan (lg_train_tcn_plan) for n_rows histories of length n_history; `convs`: (c_in, c_out, kernel, stride, padding,
+    dilation) per layer; the chains' widths as [in, out_0, ...]."""
+    key = ("lg_train_tcn_plan", int(n_rows), int(n_history), tuple(tuple(int(x) for x in c) for c in convs), tuple(int(x) for x in tail_widths),
+           tuple(int(x) for x in privilege_widths))
+    if key not in _PLANS:
+        lib, a, p = abi.load_lib(), abi.LgTrainTcnArgs(), abi.LgTrainTcnPlan()
+        a.n_rows, a.n_history, a.n_conv = key[1], key[2], len(key[3])
+        for v, c in zip(a.conv, key[3]):
+            v.c_in, v.c_out, v.kernel, v.stride, v.padding, v.dilation = c
+        _widths_into(a.tail, key[4])
+        _widths_into(a.privilege, key[5])
+        abi.check(lib.lg_train_tcn_plan(C.byref(a), C.byref(p)), lib)
+        _PLANS[key] = p
+    return _PLANS[key]
+
+
+class _TcnLossFunction(torch.autograd.Function):
+    """_LossFunction for the TCN encoder pass, whose plan takes the history length beside the row count."""
+
+    @staticmethod
+    def forward(ctx, ps, n_inputs, *inputs_and_params):
+        inputs = inputs_and_params[:n_inputs]
+        loss = torch.empty((), dtype=torch.float32, device=ps.device)
+        args = ps.args(ps.spec, *inputs, loss, None, device=ps.device)
+        ctx.ps, ctx.inputs, ctx.call = ps, inputs, ps.run_forward(args, (int(args.n_rows), int(args.n_history)))
+        return loss
+
+    backward = _LossFunction.backward
+
+
+class FusedTrainPassTSTcn:
+    """The two network passes of PPO_TS.update() on an ActorCriticTS built with history_encoder_type = "TCN" (include/lgtraintcn.h):
+
+        tp = FusedTrainPassTSTcn(actor_critic_ts)
+        mu, sigma, values = tp(obs, privileged_obs, critic_obs)                   # RL step: FusedTrainPassTS's, unchanged
+        enc_loss = tp.encoder_loss(obs_history, privileged_obs, terminated)       # encoder step: three launches; backward five
+
+    The RL pass is lg_train_ts_forward / _backward as FusedTrainPassTS runs it: PPO_TS's RL step never runs the history encoder.  The
+    encoder pass carries obs_history, (B, H) or the (B, 1, H) the reference unsqueezes it to, through the Conv1d stack, the Flatten and the
+    Linear / ELU tail, against the privilege encoder's output as a constant.  Optimise tp.rl_parameters() and tp.encoder_parameters() (in
+    history_encoder.parameters() order) apart.  Each pass has its own workspace and call counter; within a pass a backward whose forward
+    has been overwritten raises.  H is fixed by the first encoder_loss call unless `n_history` is given.  The rollout of such a module is
+    FusedPolicy(actor_critic, student=False): act_student through the TCN stays on torch."""
+
+    def __init__(self, actor_critic, n_history=None):
+        self.device = _module_device(actor_critic, _TCN)
+        self.spec = describe_ts_tcn(actor_critic, self.device, n_history)
+        self.n_history = None if n_history is None else int(n_history)
+        rl_args = lambda *a, **kw: ts_args(*a, owner=_TCN, **kw)
+        self._rl = _Pass(_TCN, "RL ", "lg_train_ts", rl_args, self.plan, self.rl_parameters, self.spec, self.device)
+        self._enc = _Pass(_TCN, "encoder ", "lg_train_tcn", tcn_args, lambda sizes: self._plan_encoder(*sizes), self.encoder_parameters, self.spec, self.device)
+
+    def rl_parameters(self):
+        return self.spec.rl_parameters()
+
+    def encoder_parameters(self):
+        return self.spec.encoder_parameters()
+
+    @property
+    def workspace(self):
+        """The float32 workspace of the last encoder forward, laid out by its plan (LgTrainTcnPlan's offsets); None before the first call.
+        For reading only: the next encoder forward overwrites or replaces it."""
+        return self._enc.workspace
+
+    def plan(self, n_rows):
+        s = self.spec
+        return plan_ts(n_rows, s.privilege_encoder.widths, s.actor.widths, s.critic.widths)
+
+    def _plan_encoder(self, n_rows, n_history):
+        s = self.spec
+        return plan_tcn(n_rows, n_history, s.history_encoder.shapes, s.history_encoder.tail.widths, s.privilege_encoder.widths)
+
+    def plan_encoder(self, n_rows):
+        if self.n_history is None:
+            raise ValueError(f"{_TCN}: the history length is not known yet: pass n_history, or call encoder_loss first")
+        return self._plan_encoder(n_rows, self.n_history)
+
+    def __call__(self, obs, privileged_obs, critic_obs):
+        """(mu, sigma, values) of the mini-batch: (B, A), (B, A), (B, 1).  One launch on the current stream."""
+        return _apply(_RLFunction, self._rl, obs, privileged_obs, critic_obs)
+
+    def encoder_loss(self, obs_history, privileged_obs, terminated):
+        """mse_loss(history_encoder(obs_history) * terminated, privilege_encoder(privileged_obs).detach() * terminated) as a 0-dim tensor
+        with autograd.  Three launches."""
+        obs_history = _history_rows(obs_history, _TCN)
+        H = int(obs_history.shape[1])
+        if self.n_history is not None and H != self.n_history:
+            raise ValueError(f"{_TCN}: obs_history has {H} columns, this pass was set up for H = {self.n_history}")
+        self.spec.history_encoder.lengths(H)
+        self.n_history = H
+        return _apply(_TcnLossFunction, self._enc, obs_history, privileged_obs, terminated)
 
 
 # ---- the concurrent teacher-student family (include/lgtraincts.h, csrc/lg_train_cts.hip) --------------------------------------------------------
@@ -711,8 +895,8 @@ class FusedTrainPassCTS:
     reference's, that .grad is not.  The encoder pass is mse_loss(history_encoder(h), privilege_encoder(p).detach()) on the teacher-student
     family's encoder kernels with a column of ones, which the pass owns, as the mask; it leaves the privilege encoder's .grad as it was.
     Each pass has its own workspace and call counter: a forward of one does not invalidate a pending backward of the other; within a pass a
-    backward whose forward has been overwritten raises.  The actor may end in a Hardtanh or not.  A "TCN" (Conv1d) history encoder keeps
-    the torch path and is refused by layer name."""
+    backward whose forward has been overwritten raises.  The actor may end in a Hardtanh or not.  A "TCN" (Conv1d) history encoder is
+    refused by layer name: ActorCriticCTS has no such option in the reference (ActorCriticTS has: FusedTrainPassTSTcn)."""
 
     def __init__(self, actor_critic):
         self.device = _module_device(actor_critic, _CTS)
