@@ -1,4 +1,4 @@
-"""ctypes mirror of include/lgsim.h, include/lgrollout.h, include/lgsensor.h, include/lgpolicy.h, include/lgppo.h, include/lgoptim.h, include/lgtrain.h, include/lgtrainee.h, include/lgtraints.h and include/lgtraintcn.h (the C ABI) and the loader of the HIP library.
+"""ctypes mirror of include/lgsim.h, include/lgrollout.h, include/lgsensor.h, include/lgpolicy.h, include/lgppo.h, include/lgoptim.h, include/lgtrain.h, include/lgtrainee.h, include/lgtraints.h, include/lgtraintcn.h and include/lgrunner.h (the C ABI) and the loader of the HIP library.
 
 Field order and types must match the header exactly; tests/test_abi.py compiles a C
 probe that prints sizeof/offsetof for every struct and compares them with these classes.
@@ -345,6 +345,11 @@ def load_lib():
         lib.lg_train_tcn_backward.argtypes = [C.POINTER(LgTrainTcnArgs), vp]
         for f in TRAIN_TCN_EXPORTS:
             getattr(lib, f).restype = C.c_int
+    if hasattr(lib, "lg_runner_episode_stats"):  # absent from libraries older than the runner's book-keeping kernels
+        lib.lg_runner_episode_stats.argtypes = [i32, vp, vp, vp, vp, vp, vp, i32, vp, vp]
+        lib.lg_runner_episode_info.argtypes = [i32, i32, vp, i32, i32, vp, i32, vp, i32, C.c_double, vp, vp, vp, vp]
+        for f in RUNNER_EXPORTS:
+            getattr(lib, f).restype = C.c_int
     lib.lg_last_error.restype = C.c_char_p
     lib.lg_last_kernel.argtypes = [H]
     lib.lg_last_kernel.restype = C.c_char_p
@@ -399,6 +404,14 @@ TRAIN_RNN_MEMORIES, TRAIN_RNN_MAX_LAYERS, TRAIN_RNN_MAX_HIDDEN, TRAIN_RNN_LSTM, 
 TRAIN_TCN_EXPORTS = ["lg_train_tcn_plan", "lg_train_tcn_forward", "lg_train_tcn_backward"]   # include/lgtraintcn.h
 TRAIN_TCN_MAX_CONV, TRAIN_TCN_MAX_CHANNELS, TRAIN_TCN_MAX_KERNEL, TRAIN_TCN_MAX_STRIDE, TRAIN_TCN_MAX_DILATION = 6, 32, 9, 4, 8
 TRAIN_TCN_TARGET_JOBS, TRAIN_TCN_THREADS, TRAIN_TCN_WG_ELEMS, TRAIN_TCN_MAX_BLOCKS = 2048, 256, 8, 2048
+RUNNER_EXPORTS = ["lg_runner_episode_stats", "lg_runner_episode_info"]                       # include/lgrunner.h
+RUNNER_THREADS, RUNNER_INFO_THREADS, RUNNER_MAX_ROWS = 1024, 256, 1024
+# argument types by entry point, in the header's order (tests/test_runner_host.py compares them with the prototypes)
+RUNNER_SIGNATURES = {
+    "lg_runner_episode_stats": ("int32_t", "const float *", "const uint8_t *", "float *", "float *", "float *", "float *", "int32_t", "int64_t *", "void *"),
+    "lg_runner_episode_info": ("int32_t", "int32_t", "const float *", "int32_t", "int32_t", "const float *", "int32_t", "const int32_t *", "int32_t",
+                               "double", "double *", "double *", "int64_t *", "void *"),
+}
 POLICY_MAX_LAYERS, POLICY_MAX_WIDTH = 4, 2048
 POLICY_MAX_RNN_LAYERS, POLICY_MAX_RNN_HIDDEN = 2, 512
 POLICY_LSTM, POLICY_GRU = 1, 2

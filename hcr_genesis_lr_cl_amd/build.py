@@ -1,6 +1,6 @@
 """Builds csrc/liblgsim.so with hipcc for gfx950 (in-tree, so it travels to the GPU box).
 
-The library is 35 translation units: lg_host.hip (C ABI), lg_rollout.hip, lg_sensor.hip, lg_policy.hip, lg_ppo.hip, lg_optim.hip, lg_train.hip, lg_train_ee.hip, lg_train_ts.hip, lg_train_dwaq.hip, lg_train_cts.hip, lg_train_rnn.hip, lg_train_tcn.hip and lg_inst.hip compiled once per
+The library is 36 translation units: lg_host.hip (C ABI), lg_rollout.hip, lg_sensor.hip, lg_policy.hip, lg_ppo.hip, lg_optim.hip, lg_train.hip, lg_train_ee.hip, lg_train_ts.hip, lg_train_dwaq.hip, lg_train_cts.hip, lg_train_rnn.hip, lg_train_tcn.hip, lg_runner.hip and lg_inst.hip compiled once per
 kernel-instantiation group (-DLG_GROUP=0..21).  They are compiled in parallel into csrc/obj/ and linked; an object is reused while the sources it depends on and
 the flags are unchanged (content hash), so an edit of lg_quad.h rebuilds the twelve component-per-lane groups only.
 
@@ -59,7 +59,8 @@ def units():
          ("lg_train_rnn", "lg_train_rnn.hip", [], [os.path.join(INC, "lgtrainrnn.h"), os.path.join(INC, "lgtrain.h"), os.path.join(INC, "lgpolicy.h"),
                                                    "lg_train_tiles.h", "lg_train_pass.h"]),
          ("lg_train_tcn", "lg_train_tcn.hip", [], [os.path.join(INC, "lgtraintcn.h"), os.path.join(INC, "lgtrain.h"), os.path.join(INC, "lgpolicy.h"),
-                                                   "lg_train_tiles.h", "lg_train_pass.h"])]
+                                                   "lg_train_tiles.h", "lg_train_pass.h"]),
+         ("lg_runner", "lg_runner.hip", [], [os.path.join(INC, "lgrunner.h")])]
     for g in range(N_GROUPS):
         deps = COMMON + ["lg_kernel.h"] + (["lg_quad.h"] if g in QUAD_GROUPS else []) + ([os.path.join(HERE, "dpp_hazard_pass.py")] if DPP_PASS else [])
         u.append((f"lg_inst_{g}", "lg_inst.hip", [f"-DLG_GROUP={g}"], deps))

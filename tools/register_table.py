@@ -1,5 +1,5 @@
 """Register / scratch table of every kernel instantiation of the library: compiles each group of csrc/lg_inst.hip, csrc/lg_policy.hip
-(group "policy"), csrc/lg_ppo.hip (group "ppo"), csrc/lg_optim.hip (group "optim") csrc/lg_train.hip (group "train"), csrc/lg_train_ee.hip (group "train_ee"), csrc/lg_train_ts.hip (group "train_ts"), csrc/lg_train_dwaq.hip (group "train_dwaq") csrc/lg_train_cts.hip (group "train_cts") csrc/lg_train_rnn.hip (group "train_rnn") and csrc/lg_train_tcn.hip (group "train_tcn"), with -Rpass-analysis=kernel-resource-usage (device pass only, nothing is linked) and prints one line per kernel.
+(group "policy"), csrc/lg_ppo.hip (group "ppo"), csrc/lg_optim.hip (group "optim") csrc/lg_train.hip (group "train"), csrc/lg_train_ee.hip (group "train_ee"), csrc/lg_train_ts.hip (group "train_ts"), csrc/lg_train_dwaq.hip (group "train_dwaq") csrc/lg_train_cts.hip (group "train_cts") csrc/lg_train_rnn.hip (group "train_rnn") csrc/lg_train_tcn.hip (group "train_tcn") and csrc/lg_runner.hip (group "runner"), with -Rpass-analysis=kernel-resource-usage (device pass only, nothing is linked) and prints one line per kernel.
 usage: python tools/register_table.py [> profiles/rNN_register_table.md]"""
 import os, re, subprocess, sys
 from concurrent.futures import ThreadPoolExecutor
@@ -8,7 +8,7 @@ from hcr_genesis_lr_cl_amd import build as b
 
 
 def one(g):
-    src, defs = ({"policy": "lg_policy.hip", "ppo": "lg_ppo.hip", "optim": "lg_optim.hip", "train": "lg_train.hip", "train_ee": "lg_train_ee.hip", "train_ts": "lg_train_ts.hip", "train_dwaq": "lg_train_dwaq.hip", "train_cts": "lg_train_cts.hip", "train_rnn": "lg_train_rnn.hip", "train_tcn": "lg_train_tcn.hip"}[g], []) if isinstance(g, str) else ("lg_inst.hip", [f"-DLG_GROUP={g}"])
+    src, defs = ({"policy": "lg_policy.hip", "ppo": "lg_ppo.hip", "optim": "lg_optim.hip", "train": "lg_train.hip", "train_ee": "lg_train_ee.hip", "train_ts": "lg_train_ts.hip", "train_dwaq": "lg_train_dwaq.hip", "train_cts": "lg_train_cts.hip", "train_rnn": "lg_train_rnn.hip", "train_tcn": "lg_train_tcn.hip", "runner": "lg_runner.hip"}[g], []) if isinstance(g, str) else ("lg_inst.hip", [f"-DLG_GROUP={g}"])
     cmd = [os.environ.get("HIPCC", "/opt/rocm/bin/hipcc"), "--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", *b.EXTRA_FLAGS, *defs,
            "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(b.CSRC, src), "-o", "/dev/null"]
     return g, subprocess.run(cmd, capture_output=True, text=True).stderr
@@ -16,7 +16,7 @@ def one(g):
 
 rows = []
 with ThreadPoolExecutor(max_workers=8) as ex:
-    for g, err in ex.map(one, [*range(b.N_GROUPS), "policy", "ppo", "optim", "train", "train_ee", "train_ts", "train_dwaq", "train_cts", "train_rnn", "train_tcn"]):
+    for g, err in ex.map(one, [*range(b.N_GROUPS), "policy", "ppo", "optim", "train", "train_ee", "train_ts", "train_dwaq", "train_cts", "train_rnn", "train_tcn", "runner"]):
         cur = {}
         for line in err.splitlines():
             m = re.search(r"remark: (?:.*?: )?\s*(Function Name|VGPRs|AGPRs|SGPRs Spill|VGPRs Spill|ScratchSize \[bytes/lane\]|Occupancy \[waves/SIMD\]|LDS Size \[bytes/block\]): (.*)$", line)
